@@ -157,6 +157,60 @@ def _dp_parity(arc):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this many bytes of .npy files (headers included)
+DUMP_SEED = 8                 # ... and the seed of its row sample when the whole grid does not fit
+
+
+def dump_rows(plan, n_point_rows, n_cell_rows):
+    """Rows of the stitched fields that --dump-outputs writes: all of them when the six fields fit in DUMP_LIMIT_BYTES, else the same
+    seeded sample of whole rows on every run of the workload (point rows for x, y, dx, angle_dx; cell rows for dy, area)."""
+    ni1 = plan.Ni + 1
+    per_row = 8 * (4 * ni1 + 2 * plan.Ni + 2)   # one point row and one cell row of every field, and their two indices
+    budget = DUMP_LIMIT_BYTES - 8 * 128            # (the eight .npy headers)
+    if max(n_point_rows, n_cell_rows) * per_row <= budget:
+        return np.arange(n_point_rows), np.arange(n_cell_rows)
+    k = budget // per_row
+    rng = np.random.default_rng(DUMP_SEED)
+    return (np.sort(rng.choice(n_point_rows, min(k, n_point_rows), replace=False)),
+            np.sort(rng.choice(n_cell_rows, min(k, n_cell_rows), replace=False)))
+
+
+def take_dump_rows(sg, cut, rows, torch):
+    """This rank's share of the dumped rows, copied to the host: {field: (rows of the stitched field, values)}."""
+    out = {}
+    for f in ("x", "y", "dx", "dy", "area", "angle_dx"):
+        point = f in ("x", "y", "dx", "angle_dx")
+        want = rows[0] if point else rows[1]
+        idx, vals = [], []
+        for s, lo, hi, row0 in sg._pieces(cut, point)[0]:
+            a, b = np.searchsorted(want, [row0, row0 + hi - lo])
+            if b > a:
+                sel = torch.as_tensor(want[a:b] - row0 + lo, device=sg.device)
+                vals.append(sg.buf[s.name][f].index_select(0, sel).cpu().numpy())
+                idx.append(want[a:b])
+        cols = sg.buf[sg.plan.subs[0].name][f].shape[1]
+        out[f] = (np.concatenate(idx) if idx else np.zeros(0, np.int64), np.concatenate(vals) if vals else np.zeros((0, cols)))
+    return out
+
+
+def write_dump(dirname, rows, parts):
+    """Assemble the ranks' shares row by row and write DIR/<field>.npy (float64), with the stitched row indices of the point and
+    cell fields as rows_point.npy / rows_cell.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    for f in parts[0]:
+        want = rows[0] if f in ("x", "y", "dx", "angle_dx") else rows[1]
+        arr = np.empty((len(want), parts[0][f][1].shape[1]), dtype=np.float64)
+        seen = np.zeros(len(want), dtype=bool)
+        for part in parts:
+            idx, vals = part[f]
+            pos = np.searchsorted(want, idx)
+            arr[pos], seen[pos] = vals, True
+        assert seen.all(), "--dump-outputs: rows of %s that no rank holds" % f
+        np.save(os.path.join(dirname, f + ".npy"), arr)
+    np.save(os.path.join(dirname, "rows_point.npy"), rows[0].astype(np.float64))
+    np.save(os.path.join(dirname, "rows_cell.npy"), rows[1].astype(np.float64))
+
+
 VALU_PEAK_GINSTR = 1024 * 2.4 / 4   # wave64 fp64 VALU instructions per ns over the chip: 1024 SIMDs, 2.4 GHz, 4 cycles per instruction
 
 
@@ -376,7 +430,13 @@ def main():
     ap.add_argument("--launch", default="auto", choices=["auto", "pass", "kernels"],
                     help="pass: ogg_tripolar_pass_dev (three launches, lat-lon and cap workgroups share them); kernels: one launch per "
                          "sub-grid and phase (--overlap: caps on side streams); auto: time both during set-up and keep the faster")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed -- the stitched supergrid fields x, y, dx, dy, area, angle_dx as "
+                         "main() returns them -- to DIR/<field>.npy (float64): every row when the six fit in 64 MB, else a fixed "
+                         "seeded sample of whole rows; rows_point.npy / rows_cell.npy hold the row indices")
     args = ap.parse_args()
+    if args.dump_outputs and args.as_rank is not None:
+        ap.error("--dump-outputs needs the whole grid: not with --as-rank")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks as CHILD processes, before anything here touches the GPU (no exec)
@@ -500,8 +560,11 @@ def main():
     elif args.latlon == "fused" and args.launch == "auto":
         # set-up, untimed: every rank keeps the launch scheme that is fastest for ITS share (there is no collective in a pass)
         tuned = {}
-        # (the pass is launched eagerly: a graph of its three launches gains nothing and would hide them from the events)
-        cands = [("pass", 0, 0), ("kernels", 1, 1), ("kernels", 0, 0)]
+        # (the pass is launched eagerly: a graph of its three launches gains nothing and would hide them from the events).  The
+        # per-kernel scheme is tried eagerly too: the replay of its captured graph with the caps on side streams ends the process with a
+        # segmentation fault inside the HIP runtime on some configurations (r4_om4; r2 after a world-size-1 RCCL group), and that
+        # candidate never won (round 5: 1.5-2.6x the fused pass's time)
+        cands = [("pass", 0, 0), ("kernels", 1, 0), ("kernels", 0, 0)]
         for launch, overlap, graph in cands:
             sg.launch, sg.overlap = launch, bool(overlap)
             if graph and not can_graph:
@@ -605,6 +668,20 @@ def main():
     # ... and the same through a closing barrier + synchronize (an all-reduce and two host wake-ups: tens of microseconds, which is
     # noise at one rank's 5 ms and a tenth of the region at eight ranks' 0.7 ms): reported beside it, `ms_per_step_with_closing_barrier`
     dt_barrier = time.perf_counter() - t0
+    # --dump-outputs: the fields as the last timed step left them, copied before any other pass runs (untimed)
+    dump = None
+    if args.dump_outputs:
+        cut = sg.south_cut() if world == 1 else plan.south_cut()
+        rows = dump_rows(plan, sg._pieces(cut, True)[1], sg._pieces(cut, False)[1])
+        parts = [take_dump_rows(sg, cut, rows, torch)]
+        if use_dist and world > 1:
+            gathered = [None] * world
+            dist.all_gather_object(gathered, parts[0])
+            parts = gathered
+        if rank == 0:
+            write_dump(args.dump_outputs, rows, parts)
+            dump = {"dir": args.dump_outputs, "rows": "all" if len(rows[0]) == sg._pieces(cut, True)[1] else "sample (seed %d)" % DUMP_SEED,
+                    "point_rows": int(len(rows[0])), "cell_rows": int(len(rows[1]))}
     plan_slots, carried1 = sg.pass_plan_info()
     launches = None
     if sample:
@@ -856,6 +933,7 @@ def main():
             "d2h_pinned_after_pass": d2h,
             "kernels": kernels,
             "power": power,
+            **({"dump_outputs": dump} if dump else {}),
         }
         fp = (power or {}).get("fused_pass")
         if fp and "watts" in fp:

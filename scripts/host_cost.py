@@ -3,7 +3,7 @@
 Round 2 (every pass re-planned): 15 us of host time per pass; an eighth of the 1/8 degree grid needs 41 us on the GPU (GPU-bound), of the
 1/2 degree grid 18 us.  With the plan handle (ogg_supergrid_pass_plan_dev / _run_dev) a pass is one ctypes call + its launches."""
 import sys, time, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
 from ocean_model_grid_generator_amd import supergrid
 for wl, world in (("r8", 8), ("r2", 8), ("r8", 1)):

@@ -1,7 +1,7 @@
 """The (field, row)-ordered lat-lon kernel (OGG_LATLON_ROWS=1) against the column-tile kernel, stand-alone, in one process on one box:
 1/8, 1/16 and 1/2 degree."""
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ocean_model_grid_generator_amd import supergrid as SG
 import bench

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures in this directory FROM THE REFERENCE ITSELF.
 
-Run in the build container only (needs /root/reference; never on the GPU box):
+Run where the reference checkout exists (never on the GPU box), with OGG_REFERENCE_DIR naming its directory:
 
-    python tests/golden/make_golden.py [--big]
+    OGG_REFERENCE_DIR=<reference checkout> python tests/golden/make_golden.py [--big]
 
 The reference script imports ``numpypi.numpypi_series`` (OGG:5), which is not installed and cannot be fetched.
 This script therefore puts a three-line *scratch* module on sys.path (under a temp dir, outside the repo) that
-re-exports plain numpy under that name, imports the UNMODIFIED reference file from /root/reference, stubs its
+re-exports plain numpy under that name, imports the UNMODIFIED reference file from OGG_REFERENCE_DIR, stubs its
 NetCDF writer to capture arrays, and records:
 
   * ``ref_small_*.npz``      full output arrays of small CLI configurations (inputs = the flags);
@@ -88,7 +88,7 @@ def load_reference():
     with open(os.path.join(shim, "numpypi", "numpypi_series.py"), "w") as f:
         f.write("from numpy import *\nimport numpy as _n\nfloat64=_n.float64\n")
     sys.dont_write_bytecode = True
-    sys.path[:0] = [shim, "/root/reference"]
+    sys.path[:0] = [shim, os.environ["OGG_REFERENCE_DIR"]]
     import ocean_grid_generator as ogg
     return ogg
 
