@@ -418,6 +418,76 @@ int ogg_libm_check_dev(int which, long n, const double* x, const double* y, unsi
  * device pointer.  A band-sharded run adds the out5 of all ranks (one all-reduce) and evaluates OGG:735-770 on the host. */
 int ogg_metrics_sums_dev(long n_dx_rows, long n_cell_rows, long ni, const double* dx, const double* dy, const double* area,
                          long col_a, long col_b, int want_first_row, int want_last_row, double* out5, void* stream);
+/* ------------------------------------------------------------------------------------------------------
+ * Grid-quality report (an addition: the reference has no such check).  One read-only pass over the STITCHED supergrid as
+ * written to the file: x, y, angle_dx nyp x nxp, dx nyp x nx, dy ny x nxp, area ny x nx (nxp = nx + 1, ny = nyp - 1).
+ * P(j, i) = (cos y cos x, cos y sin x, sin y), x and y in degrees.  An edge or chord shorter than OGG_QUALITY_DEGENERATE_M is
+ * degenerate: counted, and left out of every minimum, ratio and angle.  Items, each indexed (j, i) in the written arrays:
+ *   sizes        min over non-degenerate (area: non-zero) values and max of dx, dy, area
+ *   aspect       cell (j, i): a = (dx[j,i] + dx[j+1,i]) / 2, b = (dy[j,i] + dy[j,i+1]) / 2, max(a/b, b/a)
+ *   corner       SW corner of cell (j, i): chords A = P(j,i+1) - P(j,i), B = P(j+1,i) - P(j,i) projected onto the tangent plane at
+ *                P(j,i); delta = |angle(A', B') - 90 deg|, evaluated as atan2(|A'.B'|, |A' x B'|)
+ *   rx           max(dx[j,i+1] / dx[j,i], inverse), i + 1 taken periodically (the pair (nx-1, 0) is reported at i = nx-1)
+ *   ry           max(dy[j+1,i] / dy[j,i], inverse), reported at the lower row j
+ *   ry_next      ry of the pair (last cell row of a band, first cell row of the band that follows it): at a sub-grid joint, the
+ *                jump in dy across the joint
+ *   seam         Re |P_seam(i) - P(next row, i)| in metres: the lower sub-grid's own last point row (which stitching drops) against
+ *                the upper sub-grid's first one
+ * Extrema tie to the smallest (j, i); no floating-point sum is taken anywhere, so a result is bit-identical whatever the split of the
+ * grid into bands and blocks.
+ * ---------------------------------------------------------------------------------------------------- */
+#define OGG_QUALITY_DEGENERATE_M 1.0e-3
+#define OGG_QUALITY_N_BINS 7 /* corner-delta histogram: [0, 1e-6), [1e-6, 1e-3), ..., [20, inf) degrees */
+#define OGG_QUALITY_BIN_EDGES_DEG {1.0e-6, 1.0e-3, 0.1, 1.0, 5.0, 20.0}
+enum {
+    OGG_Q_DX_MIN = 0, OGG_Q_DX_MAX, OGG_Q_DY_MIN, OGG_Q_DY_MAX, OGG_Q_AREA_MIN, OGG_Q_AREA_MAX, OGG_Q_ASPECT_MAX, OGG_Q_DELTA_MAX,
+    OGG_Q_RX_MAX, OGG_Q_RY_MAX, OGG_Q_RY_NEXT_MAX, OGG_Q_SEAM_MAX, OGG_Q_N_EXTREMA
+};
+enum {
+    OGG_Q_N_DX = 0,           /* dx values seen */
+    OGG_Q_N_DX_DEGENERATE,
+    OGG_Q_N_DY,
+    OGG_Q_N_DY_DEGENERATE,
+    OGG_Q_N_AREA,
+    OGG_Q_N_AREA_ZERO,
+    OGG_Q_N_CORNERS,          /* corners seen (degenerate ones included) */
+    OGG_Q_N_CORNER_DEGENERATE,
+    OGG_Q_HIST,               /* OGG_QUALITY_N_BINS counts from here */
+    OGG_Q_N_COUNTS = OGG_Q_HIST + OGG_QUALITY_N_BINS
+};
+/* one extremum: j < 0 when nothing was seen (value is then meaningless); lon, lat = x[j, i], y[j, i].  The corner extremum
+ * (OGG_Q_DELTA_MAX) holds tan(delta) = |A'.B'| / |A' x B'|, which delta is monotonic in; degrees(atan(value)) is delta. */
+typedef struct ogg_quality_extremum {
+    double value, lon, lat;
+    long long j, i;
+} ogg_quality_extremum;
+typedef struct ogg_grid_quality_result {
+    ogg_quality_extremum ext[OGG_Q_N_EXTREMA];
+    long long count[OGG_Q_N_COUNTS];
+} ogg_grid_quality_result;
+/* A band: point rows j0 .. j0 + n_pt_rows - 1 of the stitched grid (x, y, dx; row strides nx + 1, nx + 1, nx) and cell rows
+ * j0 .. j0 + n_cell_rows - 1 (dy, area; strides nx + 1, nx), n_cell_rows = n_pt_rows, or n_pt_rows - 1 for the band that ends the
+ * grid.  The cells of the last row need point row j0 + n_pt_rows (x_next, y_next, dx_next: required when n_cell_rows = n_pt_rows) and
+ * cell row j0 + n_cell_rows (dy_next: NULL where the grid has no such row).  x_seam, y_seam (or NULL): the dropped last point row of
+ * the sub-grid this band ends, compared with x_next, y_next.  metrics = 0 (--skip_metrics): dx, dy, area are not read and every item
+ * that needs them is left empty. */
+typedef struct ogg_quality_band {
+    long nx, j0, n_pt_rows, n_cell_rows;
+    const double *x, *y, *dx, *dy, *area;
+    const double *x_next, *y_next, *dx_next, *dy_next;
+    const double *x_seam, *y_seam;
+    double Re;
+    int metrics;
+} ogg_quality_band;
+long ogg_grid_quality_result_bytes(void); /* sizeof(ogg_grid_quality_result) (lets a binding verify its layout) */
+long ogg_grid_quality_workspace_bytes(long nx, long n_pt_rows);
+/* device pointers throughout: the band's result into *out (device memory); the workspace (device memory, at least
+ * ogg_grid_quality_workspace_bytes) holds one record per workgroup, merged in workgroup order by a second kernel */
+int ogg_grid_quality_band_dev(const ogg_quality_band* band, void* workspace, long workspace_bytes, ogg_grid_quality_result* out,
+                              void* stream);
+/* the same with HOST pointers in *band, staged through device memory; *out is host memory */
+int ogg_grid_quality(const ogg_quality_band* band, ogg_grid_quality_result* out);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

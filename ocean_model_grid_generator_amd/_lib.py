@@ -43,6 +43,32 @@ class DpoleBand(ctypes.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_long), ("symmetry", c_int)]
 
 
+class QualityBand(ctypes.Structure):
+    """ogg_quality_band of include/ogg_hip.h"""
+    _fields_ = [("nx", c_long), ("j0", c_long), ("n_pt_rows", c_long), ("n_cell_rows", c_long)] + \
+        [(f, c_void_p) for f in ("x", "y", "dx", "dy", "area", "x_next", "y_next", "dx_next", "dy_next", "x_seam", "y_seam")] + \
+        [("Re", c_double), ("metrics", c_int)]
+
+
+QUALITY_N_EXTREMA, QUALITY_N_COUNTS, QUALITY_N_BINS = 12, 15, 7   # OGG_Q_N_EXTREMA, OGG_Q_N_COUNTS, OGG_QUALITY_N_BINS
+QUALITY_EXTREMA = ("dx_min", "dx_max", "dy_min", "dy_max", "area_min", "area_max", "aspect_max", "delta_max", "rx_max", "ry_max",
+                   "ry_next_max", "seam_max")   # OGG_Q_DX_MIN ... OGG_Q_SEAM_MAX
+QUALITY_COUNTS = ("n_dx", "n_dx_degenerate", "n_dy", "n_dy_degenerate", "n_area", "n_area_zero", "n_corners", "n_corner_degenerate") + \
+    tuple("hist%d" % k for k in range(QUALITY_N_BINS))   # OGG_Q_N_DX ... OGG_Q_HIST + 6
+QUALITY_DEGENERATE_M = 1.0e-3          # OGG_QUALITY_DEGENERATE_M
+QUALITY_BIN_EDGES_DEG = (1.0e-6, 1.0e-3, 0.1, 1.0, 5.0, 20.0)   # OGG_QUALITY_BIN_EDGES_DEG
+
+
+class QualityExtremum(ctypes.Structure):
+    """ogg_quality_extremum of include/ogg_hip.h"""
+    _fields_ = [("value", c_double), ("lon", c_double), ("lat", c_double), ("j", c_longlong), ("i", c_longlong)]
+
+
+class QualityResult(ctypes.Structure):
+    """ogg_grid_quality_result of include/ogg_hip.h"""
+    _fields_ = [("ext", QualityExtremum * QUALITY_N_EXTREMA), ("count", c_longlong * QUALITY_N_COUNTS)]
+
+
 # name -> argtypes; every function returns int except the two string getters.  Must list EVERY symbol of ogg_hip.h
 # (tests/test_abi.py checks this list against the header).
 SIGNATURES = {
@@ -149,6 +175,8 @@ SIGNATURES = {
     "ogg_bswap64_dev": [c_long, c_void_p, c_void_p, c_void_p],
     "ogg_libm_check_dev": [c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_metrics_sums_dev": [c_long, c_long, c_long, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_void_p],
+    "ogg_grid_quality_band_dev": [ctypes.POINTER(QualityBand), c_void_p, c_long, c_void_p, c_void_p],
+    "ogg_grid_quality": [ctypes.POINTER(QualityBand), ctypes.POINTER(QualityResult)],
     "ogg_event_create": [ctypes.POINTER(c_void_p)],
     "ogg_event_destroy": [c_void_p],
     "ogg_event_record": [c_void_p, c_void_p],
@@ -163,7 +191,9 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_dpole_band_workspace_bytes": [c_int, c_long, c_long],
                 "ogg_latlon_rows_workspace_bytes": [c_int, ctypes.POINTER(LatlonBand), c_long],
                 "ogg_supergrid_pass_plan_slots": [c_void_p],
-                "ogg_supergrid_pass_plan_carried_runs": [c_void_p]}
+                "ogg_supergrid_pass_plan_carried_runs": [c_void_p],
+                "ogg_grid_quality_result_bytes": [],
+                "ogg_grid_quality_workspace_bytes": [c_long, c_long]}
 
 _lib = None
 

@@ -118,3 +118,117 @@ class Dataset(object):
                     for r0 in range(0, flat.shape[0], chunk_rows):
                         f.write(np.ascontiguousarray(flat[r0:r0 + chunk_rows]).astype(">f8").tobytes())
                 f.write(b"\0" * _pad4(s))
+
+
+# ---- reader ------------------------------------------------------------------------------------------------------
+_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 4, 6: 8}   # NC_BYTE, NC_CHAR, NC_SHORT, NC_INT, NC_FLOAT, NC_DOUBLE
+
+
+class Variable(object):
+    def __init__(self, name, nc_type, shape, begin, is_record):
+        self.name, self.nc_type, self.shape, self.begin, self.is_record = name, nc_type, tuple(shape), begin, is_record
+
+
+class Header(object):
+    """What read_header() finds: version (1 or 2), dims [(name, length)], vars {name: Variable}."""
+
+    def __init__(self, version, dims, vars):
+        self.version, self.dims, self.vars = version, dims, vars
+
+
+def read_header(path):
+    """Header of a NetCDF classic (CDF-1) or 64-bit-offset (CDF-2) file.  CDF-5 and NetCDF-4 / HDF5 files are refused."""
+    with open(path, "rb") as f:
+        head = f.read(4)
+        if head[:3] == b"CDF" and head[3:4] == b"\x05":
+            raise ValueError("%s: NetCDF CDF-5 (64-bit data) is not supported; write the grid as NETCDF3_64BIT" % path)
+        if head[:4] == b"\x89HDF":
+            raise ValueError("%s: NetCDF-4 / HDF5 is not supported; write the grid as NETCDF3_64BIT" % path)
+        if head[:3] != b"CDF" or head[3:4] not in (b"\x01", b"\x02"):
+            raise ValueError("%s: not a NetCDF classic file" % path)
+        version = head[3]
+        data = head + f.read(1 << 20)
+        while True:   # headers of grid files are small; read more only if one is not
+            try:
+                return _parse_header(path, data, version)
+            except IndexError:
+                more = f.read(len(data))
+                if not more:
+                    raise ValueError("%s: truncated NetCDF header" % path)
+                data += more
+
+
+def _parse_header(path, data, version):
+    pos = [4]
+
+    def take(n):
+        if pos[0] + n > len(data):
+            raise IndexError
+        b = data[pos[0]:pos[0] + n]
+        pos[0] += n
+        return b
+
+    def i32():
+        return struct.unpack(">i", take(4))[0]
+
+    def name():
+        n = i32()
+        s = take(n).decode("utf-8")
+        take(_pad4(n))
+        return s
+
+    def atts():
+        tag, n = i32(), i32()
+        if tag not in (0, NC_ATTRIBUTE):
+            raise ValueError("%s: bad attribute list" % path)
+        for _ in range(n):
+            name()
+            t, m = i32(), i32()
+            nb = m * _TYPE_SIZE[t]
+            take(nb + _pad4(nb))
+
+    numrecs = i32()
+    tag, ndims = i32(), i32()
+    if tag not in (0, NC_DIMENSION):
+        raise ValueError("%s: bad dimension list" % path)
+    dims = [(name(), i32()) for _ in range(ndims)]
+    atts()
+    tag, nvars = i32(), i32()
+    if tag not in (0, NC_VARIABLE):
+        raise ValueError("%s: bad variable list" % path)
+    out = {}
+    for _ in range(nvars):
+        vname = name()
+        ids = [i32() for _ in range(i32())]
+        atts()
+        nc_type = i32()
+        take(4)   # vsize
+        begin = struct.unpack(">q" if version == 2 else ">i", take(8 if version == 2 else 4))[0]
+        is_rec = bool(ids) and dims[ids[0]][1] == 0
+        shape = [numrecs if (k == 0 and is_rec) else dims[d][1] for k, d in enumerate(ids)]
+        out[vname] = Variable(vname, nc_type, shape, begin, is_rec)
+    return Header(version, dims, out)
+
+
+def read_var_bytes(path, header, name, dtype=NC_DOUBLE):
+    """The raw (big-endian) bytes of a fixed-size variable."""
+    if name not in header.vars:
+        raise KeyError("%s: no variable %r" % (path, name))
+    v = header.vars[name]
+    if v.is_record:
+        raise ValueError("%s: %s is a record variable (only fixed-size variables are read)" % (path, name))
+    if v.nc_type != dtype:
+        raise ValueError("%s: %s has NetCDF type %d, expected %d" % (path, name, v.nc_type, dtype))
+    n = int(np.prod(v.shape, dtype=np.int64)) * _TYPE_SIZE[v.nc_type]
+    with open(path, "rb") as f:
+        f.seek(v.begin)
+        b = f.read(n)
+    if len(b) != n:
+        raise ValueError("%s: %s is truncated" % (path, name))
+    return b
+
+
+def read_doubles(path, names=("x", "y", "dx", "dy", "area")):
+    """{name: host float64 array} of fixed-size double variables (host byte swap; the GPU checker swaps on the device)."""
+    h = read_header(path)
+    return {n: np.frombuffer(read_var_bytes(path, h, n), dtype=">f8").astype(np.float64).reshape(h.vars[n].shape) for n in names}

@@ -641,7 +641,7 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          no_changing_meta=False, enhanced_equatorial=0, debug=False, grids="all", match_dy=(), skip_metrics=False,
          ensure_nj_even=False, shift_equator_to_u_point=True, bipolar_lower_lat=-99.0, mercator_lower_lat=-99.0,
          mercator_upper_lat=-99.0, south_ocean_lower_lat=-99.0, south_ocean_upper_lat=-99.0, no_south_cap=False,
-         return_arrays=False, path=None, dp_arc=None, cap_symmetry=None):
+         return_arrays=False, path=None, dp_arc=None, cap_symmetry=None, quality_report=None):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -654,7 +654,9 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     reference is) or "literal" (the reference's operation sequence).  ``cap_symmetry`` (or OGG_CAP_SYMMETRY=0): None / True: the caps
     are evaluated on the columns that determine the rest and mirrored (_sym; DESIGN.md section 2: a mirrored value is as far from the exact
     value of the reference's formula as the reference's own), False: every column, as the reference does.  ``return_arrays=True``
-    additionally returns the six stitched fields and the sub-grid pieces (used by tests)."""
+    additionally returns the six stitched fields and the sub-grid pieces (used by tests).  ``quality_report`` (--quality_report FILE):
+    write the grid-quality report of the stitched grid (grid_quality.py) to that file as JSON and print a summary of it after the
+    CHECK_metrics lines; an addition the reference does not have."""
     import time
 
     path = path or os.environ.get("OGG_MAIN_PATH", "pass")
@@ -664,7 +666,7 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
                                    reproduce_MIDAS_grids, write_subgrid_files, plotem, no_changing_meta, enhanced_equatorial, debug, grids,
                                    match_dy, skip_metrics, ensure_nj_even, shift_equator_to_u_point, bipolar_lower_lat, mercator_lower_lat,
                                    mercator_upper_lat, south_ocean_lower_lat, south_ocean_upper_lat, no_south_cap, return_arrays, dp_arc,
-                                   cap_symmetry)
+                                   cap_symmetry, quality_report)
     from . import supergrid as SG
 
     _validate_flags(match_dy, r_dp, lat_dp)
@@ -692,6 +694,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
                 print("   " + labels.get(name, "CHECK_metrics_hquad: % errors in (area, lat arc, lon arc)" if sc_dp else labels["SO"]), errs[name])
     # south cuts (OGG:1268-1313) and the final guards (OGG:1371-1375, 1425-1436) need two columns of y only
     cut = g.south_cut()
+    if quality_report:
+        _write_quality_report(g.quality(cut), quality_report)
     print("Stitching the grids together...")
     SG.check_guards(g.stitched_column("y", plan.Ni // 4, cut), any(s.name == "BP" for s in plan.subs))
     names = [s.name for s in plan.subs if not (s.name == "SC" and cut[2])]
@@ -757,7 +761,7 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
                         no_changing_meta=False, enhanced_equatorial=0, debug=False, grids="all", match_dy=(), skip_metrics=False,
                         ensure_nj_even=False, shift_equator_to_u_point=True, bipolar_lower_lat=-99.0, mercator_lower_lat=-99.0,
                         mercator_upper_lat=-99.0, south_ocean_lower_lat=-99.0, south_ocean_upper_lat=-99.0, no_south_cap=False,
-                        return_arrays=False, dp_arc=None, cap_symmetry=None):
+                        return_arrays=False, dp_arc=None, cap_symmetry=None, quality_report=None):
     """The reference's own sequence of calls (OGG:855-1449), every callee a host-array function of this module (numpy in, numpy
     out, one staged device call each) and the stitching on the host: what a user gets who swaps the reference's module for this
     one function by function.  main() produces the same bits from one device-resident pass."""
@@ -972,6 +976,13 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
         if np.any((np.roll(ycol, shift=-1, axis=0) - ycol) == 0):
             raise Exception("lattitude array has repeated values along symmetry meridian!")
     x3, y3, dx3, dy3, area3, angle3 = g
+    if quality_report:   # the same report as the device pass gives, from the stitched host arrays
+        names = [n for n in ("SC", "SO", "Merc", "BP") if n in sub]
+        starts = list(np.cumsum([0] + [sub[n][0].shape[0] - 1 for n in names[:-1]]))
+        seams = [(sub[n][0][-1], sub[n][1][-1]) for n in names[:-1]]
+        metric_fields = (dx3, dy3, area3) if calculate_metrics else (None, None, None)
+        _write_quality_report(grid_quality(x3, y3, *metric_fields, Re=_default_Re, sections=list(zip(names, starts)), seams=seams),
+                              quality_report)
 
     if write_subgrid_files:
         if "SC" in sub:
@@ -1016,6 +1027,23 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
         return {"x": x3, "y": y3, "dx": dx3, "dy": dy3, "area": area3, "angle_dx": angle3, "sub": sub}
 
 
+def grid_quality(x, y, dx=None, dy=None, area=None, Re=_default_Re, sections=None, seams=None):
+    """Grid-quality report of a stitched supergrid given as numpy arrays (see grid_quality.grid_quality): sizes, aspect ratio, corner
+    non-orthogonality and smoothness of the whole grid, and with ``sections`` / ``seams`` per sub-grid and per joint.  A dict."""
+    from . import grid_quality as Q
+    return Q.grid_quality(x, y, dx, dy, area, Re=Re, sections=sections, seams=seams)
+
+
+def _write_quality_report(rep, fnam):
+    import json
+
+    from . import grid_quality as Q
+    for line in Q.summary_lines(rep):
+        print(line)
+    with open(str(fnam), "w") as f:
+        json.dump(rep, f, indent=1)
+
+
 def build_parser():
     """The reference's flag surface (OGG:1452-1524), flag for flag."""
     parser = argparse.ArgumentParser(description="create ocean hgrid")
@@ -1058,6 +1086,9 @@ def build_parser():
                         help="if the equator is not a u point shift the Mercator subgrid by 1 j-point to make it a u point , default=True")
     parser.add_argument("--grids", type=str, nargs="+", required=False, default="all",
                         help="specify the subgrids to generate, choices are bipolar, mercator, so, sc, all. Default is all")
+    parser.add_argument("--quality_report", type=str, required=False, default=None,
+                        help="write a grid-quality report (cell sizes, aspect ratio, non-orthogonality, smoothness, sub-grid seams) "
+                             "of the stitched grid to this JSON file and print a summary")
     return parser
 
 

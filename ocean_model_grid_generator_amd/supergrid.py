@@ -1135,6 +1135,133 @@ class Supergrid(object):
         barrier()   # every rank's bytes are in the file
         return stream.bytes, time.perf_counter() - t0
 
+    # -- grid-quality report ------------------------------------------------------------------------------------
+    def quality_pieces(self, cut):
+        """Every rank's pieces of the stitched grid, south -> north, for the quality report: dicts with the rank, the sub-grid, the
+        band row the piece starts at ("row"), its point and cell rows (n_pt, n_cell) and its first stitched row (j0).  The same list on
+        every rank (rows_of is a function of the plan and the world size only)."""
+        c_sc, c_so, gone = cut
+        subs = [s for s in self.plan.subs if not (s.name == "SC" and gone)]
+        out, off = [], 0
+        for k, s in enumerate(subs):
+            first = c_sc if s.name == "SC" else (c_so if (s.name == "SO" and gone) else 0)
+            last_pt = s.nj1 - (0 if k == len(subs) - 1 else 1)
+            for r in range(self.world):
+                blo, bhi = self.rows_of(s, r, self.world)
+                lo, hi_pt, hi_c = max(blo, first), min(bhi, last_pt), min(bhi, s.nj1 - 1)
+                if hi_pt > lo:
+                    out.append({"rank": r, "sub": s, "row": lo - blo, "n_pt": hi_pt - lo, "n_cell": max(hi_c - lo, 0),
+                                "j0": off + lo - first})
+            off += max(last_pt - first, 0)
+        return out
+
+    def quality_halo(self, cut):
+        """The rows the pieces of THIS rank need from elsewhere, as {piece index: {"next": {x, y, dx, dy}, "seam": {x, y}}} of 1-D
+        tensors: the first point row (x, y, dx) and cell row (dy) of the piece that follows in stitched order, and at a sub-grid joint the
+        lower sub-grid's own last point row (x, y), which stitching drops.  Rows of this rank are views of its buffers; rows of another
+        rank come device-to-device from its Supergrid (halo="local") or over torch.distributed (batch_isend_irecv), as in exchange_halo."""
+        torch = self.torch
+        pieces = self.quality_pieces(cut)
+        metrics = not self.plan.skip_metrics
+        wanted = []   # (dst piece, kind, field, src rank, src sub-grid name, src band row), the same order on every rank
+        for k, p in enumerate(pieces[:-1]):
+            q = pieces[k + 1]
+            for f in ("x", "y") + (("dx",) if metrics else ()) + (("dy",) if metrics and q["n_cell"] > 0 else ()):
+                wanted.append((k, "next", f, q["rank"], q["sub"].name, q["row"]))
+            s = p["sub"]
+            if q["sub"] is not s:   # a joint: the lower sub-grid's row nj1 - 1
+                src = next(r for r in range(self.world) if self.rows_of(s, r, self.world)[1] == s.nj1)
+                row = s.nj1 - 1 - self.rows_of(s, src, self.world)[0]
+                for f in ("x", "y"):
+                    wanted.append((k, "seam", f, src, s.name, row))
+        out = {}
+        ops = []
+        for k, kind, f, src, name, row in wanted:
+            dst_rank = pieces[k]["rank"]
+            if dst_rank == self.rank:
+                if src == self.rank:
+                    t = self.buf[name][f][row]
+                elif self.halo == "local":
+                    t = self.peers[src].buf[name][f][row].clone()
+                else:
+                    t = torch.empty(self.plan.Ni + (0 if f == "dx" else 1), dtype=torch.float64, device=self.device)
+                    ops.append(("recv", t, src))
+                out.setdefault(k, {}).setdefault(kind, {})[f] = t
+            elif src == self.rank and self.halo != "local":
+                ops.append(("send", self.buf[name][f][row].contiguous(), dst_rank))
+        if ops:
+            import torch.distributed as dist
+            if all(t.is_cuda for _, t, _ in ops) and dist.get_backend() != "gloo":
+                p2p = [dist.P2POp(dist.isend if d == "send" else dist.irecv, t, r) for d, t, r in ops]
+                for w in dist.batch_isend_irecv(p2p):
+                    w.wait()
+            else:   # gloo (the CPU tests, the one-GPU rehearsal): through host copies, in the common order
+                for d, t, r in ops:
+                    if d == "send":
+                        dist.send(t.cpu(), r)
+                    else:
+                        c = torch.empty(t.shape, dtype=t.dtype)
+                        dist.recv(c, r)
+                        t.copy_(c)
+        return out
+
+    def quality_records(self, cut, halo=None):
+        """Device tensor (n_pieces, record words) of int64: the ogg_grid_quality_result of every piece of this rank, zeros elsewhere."""
+        from . import grid_quality as Q
+        torch, st = self.torch, self._stream()
+        halo = self.quality_halo(cut) if halo is None else halo   # (held until the kernels have run: the bands point into it)
+        bands = self.quality_bands(cut, halo)
+        words = ctypes.sizeof(L.QualityResult) // 8
+        out = torch.zeros((len(self.quality_pieces(cut)), words), dtype=torch.int64, device=self.device)
+        keep = []
+        for k, band in bands:
+            rec, ws = Q.band_record_dev(band, st, self.device)
+            out[k].copy_(rec)
+            keep.append((rec, ws))
+        self.torch.cuda.synchronize(self.device)
+        return out
+
+    def quality_bands(self, cut, halo):
+        """[(piece index, ogg_quality_band of device pointers)] of this rank's pieces; `halo` from quality_halo (kept alive by the caller)."""
+        p = self.plan
+        metrics = not p.skip_metrics
+        out = []
+        for k, q in enumerate(self.quality_pieces(cut)):
+            if q["rank"] != self.rank:
+                continue
+            b, r = self.buf[q["sub"].name], q["row"]
+            band = L.QualityBand(nx=p.Ni, j0=q["j0"], n_pt_rows=q["n_pt"], n_cell_rows=q["n_cell"], Re=float(p.Re), metrics=int(metrics))
+            band.x, band.y = self._p(b["x"], r), self._p(b["y"], r)
+            if metrics:
+                band.dx = self._p(b["dx"], r)
+                band.dy = self._p(b["dy"], r) if q["n_cell"] else None
+                band.area = self._p(b["area"], r) if q["n_cell"] else None
+            h = halo.get(k, {})
+            nxt, seam = h.get("next", {}), h.get("seam", {})
+            band.x_next, band.y_next = (nxt["x"].data_ptr() if "x" in nxt else None), (nxt["y"].data_ptr() if "y" in nxt else None)
+            band.dx_next = nxt["dx"].data_ptr() if "dx" in nxt else None
+            band.dy_next = nxt["dy"].data_ptr() if "dy" in nxt else None
+            if seam:
+                band.x_seam, band.y_seam = seam["x"].data_ptr(), seam["y"].data_ptr()
+            out.append((k, band))
+        return out
+
+    def quality(self, cut):
+        """The grid-quality report (grid_quality.report) of the stitched grid of every rank: a record per piece of every rank, one
+        all-reduce of the int64 records (each piece is non-zero on one rank only, so the sum is a gather, bit for bit), merged on the
+        host in stitched order."""
+        from . import grid_quality as Q
+        t = self.quality_records(cut)
+        if self.world > 1:
+            if self.halo == "local":
+                t = sum(g.quality_records(cut) for g in self.peers if g is not self) + t
+            else:
+                all_reduce(t)
+        host = t.cpu().numpy()
+        pieces = self.quality_pieces(cut)
+        recs = [(q["sub"].name, q["j0"], Q.record_from_bytes(host[k])) for k, q in enumerate(pieces)]
+        return Q.report(recs, self.plan.Re, self.stitched_rows(cut), self.plan.Ni, not self.plan.skip_metrics)
+
     def bands_to_host(self):
         """This rank's bands as numpy arrays (halo rows dropped): {sub: {field: array}}."""
         out = {}

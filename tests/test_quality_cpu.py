@@ -1,0 +1,218 @@
+"""CPU tests of the grid-quality report: the numpy definition (oracle/quality_oracle.py) on hand-built grids and on the golden
+fixtures, the NetCDF classic reader the file checker uses, the report's host-side merge, and the quality halo exchange of
+supergrid.Supergrid over gloo at world 2 and 3."""
+import json
+import os
+import socket
+import struct
+
+import numpy as np
+import pytest
+
+from oracle import quality_oracle as qo
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RE = 6371.0e3
+
+
+def latlon_patch(lon0=10.0, lat0=20.0, dlon=0.5, dlat=0.25, nj=9, ni=12):
+    lam, phi = lon0 + dlon * np.arange(ni + 1), lat0 + dlat * np.arange(nj + 1)
+    x, y = np.meshgrid(lam, phi)
+    dx = np.ascontiguousarray(RE * np.cos(np.radians(y[:, :ni])) * np.radians(dlon))
+    dy = np.full((nj, ni + 1), RE * np.radians(dlat))
+    area = (dx[:-1] + dx[1:]) / 2 * dy[:, :-1]
+    return x, y, dx, dy, area
+
+
+def test_regular_patch():
+    x, y, dx, dy, area = latlon_patch()
+    s = qo.grid_section(x, y, dx, dy, area, RE)
+    # chords of a parallel are not its tangent: the corner of a lat-lon cell with great-circle edges is off 90 degrees by
+    # atan(sin(phi) tan(dlon / 2)) -- on the equator it is square
+    d = qo.corner_delta(x, y, RE)
+    want = np.degrees(np.arctan(np.sin(np.radians(y[:-1, :-1])) * np.tan(np.radians(0.5) / 2)))
+    assert np.allclose(d, want, rtol=1e-9, atol=1e-12)
+    xe, ye, *_ = latlon_patch(lat0=-1.0, dlat=1.0, nj=2)
+    assert np.all(qo.corner_delta(xe, ye, RE)[1] <= 1e-9)   # the row on the equator
+    assert s["rx_max"]["value"] == 1.0 and (s["rx_max"]["j"], s["rx_max"]["i"]) == (0, 0)
+    a = (dx[:-1, 0] + dx[1:, 0]) / 2
+    want_aspect = np.max(np.maximum(a / dy[:, 0], dy[:, 0] / a))
+    assert abs(s["aspect_ratio_max"]["value"] - want_aspect) <= 1e-12 * want_aspect
+    cosphi = (np.cos(np.radians(y[:-1, 0])) + np.cos(np.radians(y[1:, 0]))) / 2
+    assert np.isclose(s["aspect_ratio_max"]["value"], np.max(np.maximum(cosphi * 0.5 / 0.25, 0.25 / (cosphi * 0.5))), rtol=1e-12)
+    assert s["corner"]["n"] == 9 * 12 and s["corner"]["n_degenerate"] == 0
+    assert sum(s["corner"]["histogram"]) == s["corner"]["n"]
+
+
+def test_one_displaced_point_moves_the_maxima_to_its_cell():
+    x, y, dx, dy, area = latlon_patch(lat0=-2.0, dlat=0.5)
+    j, i = 4, 6
+    x = x.copy()
+    x[j, i] += 0.2
+    dx = dx.copy()
+    dy = dy.copy()
+    dx[j, i] *= 1.5       # a cell whose metrics jump as well
+    dy[j, i] *= 1.7
+    s = qo.grid_section(x, y, dx, dy, area, RE)
+    dm = s["corner"]["delta_max_deg"]
+    assert (dm["j"], dm["i"]) in ((j, i), (j, i - 1), (j - 1, i))
+    assert (s["rx_max"]["j"], s["rx_max"]["i"]) in ((j, i - 1), (j, i))
+    assert (s["ry_max"]["j"], s["ry_max"]["i"]) in ((j - 1, i), (j, i))
+    assert dm["lon"] == x[dm["j"], dm["i"]] and dm["lat"] == y[dm["j"], dm["i"]]
+
+
+def test_pole_row_of_a_cap_is_degenerate_not_a_maximum():
+    x, y, dx, dy, area = latlon_patch(lon0=0.0, lat0=-90.0, dlon=30.0, dlat=10.0, nj=3, ni=12)
+    dx[0, :] = 0.0 * dx[0, :] + 1e-12     # the pole row: every point the same
+    s = qo.grid_section(x, y, dx, dy, area, RE)
+    assert s["corner"]["n_degenerate"] == 12          # chords along the pole row
+    assert s["dx"]["n_degenerate"] == 12 and s["dx"]["min"]["j"] == 1
+    assert s["corner"]["delta_max_deg"]["j"] >= 1
+    assert sum(s["corner"]["histogram"]) + s["corner"]["n_degenerate"] == s["corner"]["n"]
+
+
+@pytest.mark.parametrize("fixture", ["ref_small_r0.25_even", "ref_small_r0.5_dp"])
+def test_oracle_on_golden_fixtures(fixture):
+    d = np.load(os.path.join(ROOT, "tests", "golden", fixture + ".npz"))
+    s = qo.grid_section(*(d[k] for k in ("x", "y", "dx", "dy", "area")), Re=RE)
+    assert sorted(s) == ["area", "aspect_ratio_max", "corner", "dx", "dy", "rx_max", "ry_max"]
+    assert sorted(s["corner"]) == ["delta_max_deg", "histogram", "n", "n_degenerate"]
+    for k in ("aspect_ratio_max", "rx_max", "ry_max"):
+        assert sorted(s[k]) == ["i", "j", "lat", "lon", "value"] and np.isfinite(s[k]["value"])
+    assert np.isfinite(s["corner"]["delta_max_deg"]["value"])
+    assert sum(s["corner"]["histogram"]) + s["corner"]["n_degenerate"] == s["corner"]["n"]
+    json.dumps(s)
+
+
+def test_host_merge_is_order_free():
+    from ocean_model_grid_generator_amd import _lib as L
+    from ocean_model_grid_generator_amd import grid_quality as Q
+    rng = np.random.default_rng(3)
+    recs = []
+    for _ in range(6):
+        ext = [None if rng.random() < 0.2 else (float(rng.integers(0, 3)), int(rng.integers(0, 4)), int(rng.integers(0, 4)), 0.0, 0.0)
+               for _ in range(L.QUALITY_N_EXTREMA)]
+        recs.append((ext, [int(v) for v in rng.integers(0, 100, L.QUALITY_N_COUNTS)]))
+    want = Q.merge(recs)
+    for _ in range(5):
+        perm = rng.permutation(len(recs))
+        assert Q.merge([recs[k] for k in perm]) == want
+    assert L.load().ogg_grid_quality_result_bytes() == __import__("ctypes").sizeof(L.QualityResult)
+
+
+# ---- NetCDF classic reader -----------------------------------------------------------------------------------
+def test_reader_round_trip_of_our_writer(tmp_path):
+    from ocean_model_grid_generator_amd import netcdf3
+    rng = np.random.default_rng(0)
+    f = {"x": rng.random((5, 7)), "y": rng.random((5, 7)), "dx": rng.random((5, 6)), "dy": rng.random((4, 7)), "area": rng.random((4, 6))}
+    p = str(tmp_path / "g.nc")
+    ds = netcdf3.Dataset(p, [("nyp", 5), ("nxp", 7), ("ny", 4), ("nx", 6), ("string", 255)], [("history", "h")])
+    ds.def_var("tile", netcdf3.NC_CHAR, ("string",), [], np.frombuffer(b"tile1".ljust(255, b"\0"), dtype="S1"))
+    for k, dims in (("y", ("nyp", "nxp")), ("x", ("nyp", "nxp")), ("dy", ("ny", "nxp")), ("dx", ("nyp", "nx")), ("area", ("ny", "nx"))):
+        ds.def_var(k, netcdf3.NC_DOUBLE, dims, [("units", "m")], f[k])
+    ds.write()
+    got = netcdf3.read_doubles(p)
+    for k in f:
+        assert got[k].tobytes() == f[k].tobytes()
+
+
+@pytest.mark.parametrize("version", [1, 2])
+def test_reader_round_trip_of_scipy_files(tmp_path, version):
+    netcdf_file = pytest.importorskip("scipy.io").netcdf_file
+    from ocean_model_grid_generator_amd import netcdf3
+    rng = np.random.default_rng(version)
+    x = rng.random((6, 9))
+    p = str(tmp_path / "s.nc")
+    fh = netcdf_file(p, "w", version=version)
+    fh.history = "test"
+    fh.createDimension("t", None)
+    fh.createDimension("nyp", 6)
+    fh.createDimension("nxp", 9)
+    v = fh.createVariable("x", "d", ("nyp", "nxp"))
+    v[:] = x
+    v.units = "degrees"
+    r = fh.createVariable("rec", "i", ("t",))
+    r[:3] = [1, 2, 3]
+    fh.close()
+    h = netcdf3.read_header(p)
+    assert h.version == version and h.vars["rec"].is_record
+    assert netcdf3.read_doubles(p, ("x",))["x"].tobytes() == x.tobytes()
+    with pytest.raises(ValueError, match="record variable"):
+        netcdf3.read_var_bytes(p, h, "rec", dtype=4)
+
+
+@pytest.mark.parametrize("magic,what", [(b"CDF\x05", "CDF-5"), (b"\x89HDF\r\n\x1a\n", "HDF5")])
+def test_reader_refuses_cdf5_and_hdf5(tmp_path, magic, what):
+    from ocean_model_grid_generator_amd import netcdf3
+    p = str(tmp_path / "bad.nc")
+    open(p, "wb").write(magic + struct.pack(">q", 0) + b"\0" * 64)
+    with pytest.raises(ValueError, match=what):
+        netcdf3.read_header(p)
+
+
+# ---- quality halo over gloo ------------------------------------------------------------------------------------
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _worker(rank, world, port, q):
+    import torch
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from test_distributed_cpu import _plan
+        import ocean_model_grid_generator_amd.supergrid as sg_mod
+        plan = _plan(sg_mod, 1.0, ensure_nj_even=True, south_cutoff_row=3)
+        g = sg_mod.Supergrid(plan, rank=rank, world=world, device="cpu", halo="rccl")
+        # every field of every band: a code of (sub-grid, field, row of the sub-grid, column)
+        code = {"x": 1, "y": 2, "dx": 3, "dy": 4}
+        for si, s in enumerate(plan.subs):
+            b = g.buf[s.name]
+            for f, c in code.items():
+                t = b[f]
+                rows = torch.arange(t.shape[0], dtype=torch.float64)[:, None] + b["lo"]
+                t.copy_(si * 1e6 + c * 1e5 + rows * 10 + torch.arange(t.shape[1], dtype=torch.float64)[None, :] * 0)
+        cut = g.south_cut()
+        pieces = g.quality_pieces(cut)
+        halo = g.quality_halo(cut)
+        ok = True
+        sub_index = {s.name: si for si, s in enumerate(plan.subs)}
+        for k, p in enumerate(pieces):
+            if p["rank"] != rank or k == len(pieces) - 1:
+                continue
+            nxt = pieces[k + 1]
+            row = nxt["row"] + g.rows_of(nxt["sub"], nxt["rank"], world)[0]
+            for f, t in halo[k]["next"].items():
+                ok &= bool(torch.all(t == sub_index[nxt["sub"].name] * 1e6 + code[f] * 1e5 + row * 10))
+            ok &= ("dy" in halo[k]["next"]) == (nxt["n_cell"] > 0)
+            if nxt["sub"] is not p["sub"]:
+                for f, t in halo[k]["seam"].items():
+                    ok &= bool(torch.all(t == sub_index[p["sub"].name] * 1e6 + code[f] * 1e5 + (p["sub"].nj1 - 1) * 10))
+            else:
+                ok &= "seam" not in halo[k]
+            ok &= p["j0"] + p["n_pt"] == nxt["j0"]
+        q.put((rank, ok, len(pieces), pieces[-1]["j0"] + pieces[-1]["n_pt"] == g.stitched_rows(cut)))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_quality_halo_over_gloo(world):
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=300) for _ in range(world)]
+    for p in procs:
+        p.join(timeout=60)
+    assert all(ok for _, ok, _, _ in res), res
+    assert all(last for _, _, _, last in res), res
