@@ -488,6 +488,84 @@ int ogg_grid_quality_band_dev(const ogg_quality_band* band, void* workspace, lon
 /* the same with HOST pointers in *band, staged through device memory; *out is host memory */
 int ogg_grid_quality(const ogg_quality_band* band, ogg_grid_quality_result* out);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Topography by refined sampling (an addition: the reference has no topography step).  Inputs: the STITCHED supergrid x, y
+ * ((ny + 1) x (nx + 1), degrees) and a source raster S[js][is] (Ny x Nx, row 0 southmost) whose cell EDGES are lon0 + is * dlon and
+ * lat0 + js * dlat (dlat > 0).  The raster is periodic in longitude when |Nx * dlon - 360| <= 1e-9, regional otherwise.
+ * Values: int16 sources are used as they are (q = v); float32 / float64 sources are quantised by ogg_topog_quantize_dev,
+ * q = rint(v / quantum), |q| <= 2^21 or the call fails.  NaN and the source's fill values are MISSING.  All accumulation is in
+ * integers, so a record is exact and independent of any order.
+ * Supergrid cell (j, i), corners P00 = (x, y)[j][i], P01 = [j][i+1], P10 = [j+1][i], P11 = [j+1][i+1], all in fp64 in this order:
+ *   unwrap    l = x00 + (((x - x00 + 180) mod 360) - 180) for each corner x (mod with numpy's % semantics: the result has the sign
+ *             of 360); then a corner with |y| >= 90 - 1e-10 takes the unwrapped longitude (before this substitution) of the other
+ *             corner of its own row (P00 <-> P01, P10 <-> P11): L00 .. L11
+ *   refine    R = clamp(ceil(oversample * max(spanL / dlon, spanY / dlat)), 1, 256), spans = max - min over the four corners; R
+ *             above 256 (or not a number) is CLAMPED; refine > 0 replaces R for every cell (and nothing is clamped)
+ *   pole      the cell ENCLOSES a pole when |w(L01 - L00) + w(L11 - L01) + w(L10 - L11) + w(L00 - L10)| > 180, w(d) =
+ *             ((d + 180) mod 360) - 180, summed left to right; the north pole when y00 + y01 + y10 + y11 > 0 (summed left to
+ *             right), else the south pole
+ *   samples   a, b = 0 .. R-1; s = (a + 0.5) / R, t = (b + 0.5) / R, u = 1 - s, v = 1 - t;
+ *             lon = (u * v) * L00 + (s * v) * L01 + (u * t) * L10 + (s * t) * L11 (left to right), lat the same of y00 .. y11;
+ *             a pole-enclosing cell samples the polar raster row instead: lon = L00 + 360 * s, js = 0 (south) or Ny - 1 (north)
+ *   index     is = floor((lon - lon0) * inv_dlon), js = floor((lat - lat0) * inv_dlat), inv_d = 1.0 / d once in fp64.  Periodic:
+ *             is mod Nx, js clamped to [0, Ny - 1].  Regional: an index outside the raster makes the sample MISSING
+ *   record    n (samples that are not missing), n_missing, n_wet ((double)q < wet_below, wet_below = sea_level / quantum), sum q and
+ *             sum q^2 (int64), min q, max q (INT32_MAX / INT32_MIN when n = 0), R
+ * A MODEL cell (a MOM6 h-cell) is the 2 x 2 block of supergrid cells (2 jm + dj, 2 im + di): its record is the exact integer
+ * combination of theirs (R the largest; n_pole, n_clamped counted over the four).  nx and ny must then be even.
+ * Outputs (host side, from the integers): height = sum / n * quantum; h_std = sqrt((double)(n * sumsq - sum^2)) / n * quantum with
+ * the difference formed exactly in 128 bits; h_min, h_max = q * quantum; wet_fraction = n_wet / n; depth = max(0, -height).
+ * ---------------------------------------------------------------------------------------------------- */
+#define OGG_TOPOG_MAX_REFINE 256
+#define OGG_TOPOG_MAX_Q (1 << 21)                 /* |q| bound of a quantised source */
+#define OGG_TOPOG_MISSING_Q ((int)0x80000000)     /* the missing value of an int32 (quantised) source */
+#define OGG_TOPOG_POLE_EPS 1.0e-10
+enum { OGG_TOPOG_INT16 = 0, OGG_TOPOG_INT32 = 1, OGG_TOPOG_FLOAT32 = 2, OGG_TOPOG_FLOAT64 = 3 };
+enum { OGG_TOPOG_MODEL_CELLS = 0, OGG_TOPOG_SUPERGRID_CELLS = 1 };
+/* the source raster.  dtype OGG_TOPOG_INT16 or OGG_TOPOG_INT32 for sampling (an int32 source holds quantised values, missing ones
+ * OGG_TOPOG_MISSING_Q); the host-pointer ogg_topog also takes FLOAT32 / FLOAT64 and quantises them on the device.  n_fill (0..2)
+ * values of fill[] mark missing raw values (compared as (double)v == fill[k]) in an int16 or a float source. */
+typedef struct ogg_topog_source {
+    const void* data;
+    int dtype, n_fill;
+    double fill[2];
+    long Nx, Ny;
+    double lon0, dlon, lat0, dlat;
+    double quantum;      /* float sources: q = rint(v / quantum) */
+    double wet_below;    /* a sample is wet when (double)q < wet_below (= sea_level / quantum) */
+} ogg_topog_source;
+/* a band: supergrid cell rows j0 .. j0 + n_cell_rows - 1 of the stitched grid (j0 counted in the whole grid: it decides the pairing
+ * into model rows).  x, y hold the band's n_cell_rows point rows (stride nx + 1), x_next, y_next the point row that follows them
+ * (the next band's first row).  Output rows: m = j >> shift for j in the band (shift = 1 for model cells, 0 for supergrid cells),
+ * rows m0 = j0 >> shift .. m1 = (j0 + n_cell_rows - 1) >> shift, nx >> shift records each.  A model row whose two supergrid rows
+ * lie in two bands gets a PARTIAL record from each (the cells of this band only); the two combine exactly (sums, min, max). */
+typedef struct ogg_topog_band {
+    long nx, j0, n_cell_rows;
+    const double *x, *y, *x_next, *y_next;
+    int cells;           /* OGG_TOPOG_MODEL_CELLS or OGG_TOPOG_SUPERGRID_CELLS */
+    int refine;          /* 0: R from the spans; 1 .. 256: this R for every cell */
+    double oversample;
+} ogg_topog_band;
+typedef struct ogg_topog_record {
+    long long n, n_missing, n_wet, sum, sumsq;
+    int min, max, R;
+    short n_pole, n_clamped;   /* supergrid cells of this record that enclose a pole / whose R was clamped */
+} ogg_topog_record;
+long ogg_topog_record_bytes(void);                         /* sizeof(ogg_topog_record) */
+long ogg_topog_band_out_rows(const ogg_topog_band* band);  /* m1 - m0 + 1 (0 for an empty band), -1 on a bad band */
+long ogg_topog_workspace_bytes(void);                      /* the work counter of ogg_topog_band_dev */
+/* device pointers throughout: the band's records, row-major (m - m0, i_out), into out (device memory, out_rows * (nx >> shift)
+ * records).  One wavefront owns each output record and reduces its samples in registers; wavefronts take runs of records from a
+ * counter in the workspace (work distribution only: no result is accumulated across wavefronts, so none depends on the order). */
+int ogg_topog_band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* workspace, long workspace_bytes,
+                       ogg_topog_record* out, void* stream);
+/* a float32 / float64 raster (src->dtype) -> int32 q (device memory, Nx * Ny); *n_bad (device int) is set non-zero when some
+ * |q| > OGG_TOPOG_MAX_Q, and the caller must then refuse the result (the host form does) */
+int ogg_topog_quantize_dev(const ogg_topog_source* src, int* q, int* n_bad, void* stream);
+/* HOST pointers in *band and *src (x, y hold n_cell_rows + 1 point rows when x_next is NULL), staged through device memory; out is
+ * host memory.  A float source is quantised on the device first (OGG_EARG when |q| > OGG_TOPOG_MAX_Q). */
+int ogg_topog(const ogg_topog_band* band, const ogg_topog_source* src, ogg_topog_record* out);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

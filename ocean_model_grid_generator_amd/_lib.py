@@ -69,6 +69,28 @@ class QualityResult(ctypes.Structure):
     _fields_ = [("ext", QualityExtremum * QUALITY_N_EXTREMA), ("count", c_longlong * QUALITY_N_COUNTS)]
 
 
+class TopogSource(ctypes.Structure):
+    """ogg_topog_source of include/ogg_hip.h"""
+    _fields_ = [("data", c_void_p), ("dtype", c_int), ("n_fill", c_int), ("fill", c_double * 2), ("Nx", c_long), ("Ny", c_long),
+                ("lon0", c_double), ("dlon", c_double), ("lat0", c_double), ("dlat", c_double), ("quantum", c_double),
+                ("wet_below", c_double)]
+
+
+class TopogBand(ctypes.Structure):
+    """ogg_topog_band of include/ogg_hip.h"""
+    _fields_ = [("nx", c_long), ("j0", c_long), ("n_cell_rows", c_long), ("x", c_void_p), ("y", c_void_p), ("x_next", c_void_p),
+                ("y_next", c_void_p), ("cells", c_int), ("refine", c_int), ("oversample", c_double)]
+
+
+TOPOG_INT16, TOPOG_INT32, TOPOG_FLOAT32, TOPOG_FLOAT64 = 0, 1, 2, 3   # OGG_TOPOG_INT16 ... of include/ogg_hip.h
+TOPOG_MODEL_CELLS, TOPOG_SUPERGRID_CELLS = 0, 1
+TOPOG_MAX_REFINE, TOPOG_MAX_Q = 256, 1 << 21                           # OGG_TOPOG_MAX_REFINE, OGG_TOPOG_MAX_Q
+TOPOG_POLE_EPS = 1.0e-10                                               # OGG_TOPOG_POLE_EPS
+# ogg_topog_record as a numpy record (56 bytes)
+TOPOG_RECORD = np.dtype([("n", "<i8"), ("n_missing", "<i8"), ("n_wet", "<i8"), ("sum", "<i8"), ("sumsq", "<i8"), ("min", "<i4"),
+                         ("max", "<i4"), ("R", "<i4"), ("n_pole", "<i2"), ("n_clamped", "<i2")])
+
+
 # name -> argtypes; every function returns int except the two string getters.  Must list EVERY symbol of ogg_hip.h
 # (tests/test_abi.py checks this list against the header).
 SIGNATURES = {
@@ -177,6 +199,9 @@ SIGNATURES = {
     "ogg_metrics_sums_dev": [c_long, c_long, c_long, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_void_p],
     "ogg_grid_quality_band_dev": [ctypes.POINTER(QualityBand), c_void_p, c_long, c_void_p, c_void_p],
     "ogg_grid_quality": [ctypes.POINTER(QualityBand), ctypes.POINTER(QualityResult)],
+    "ogg_topog_band_dev": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p, c_long, c_void_p, c_void_p],
+    "ogg_topog_quantize_dev": [ctypes.POINTER(TopogSource), c_void_p, c_void_p, c_void_p],
+    "ogg_topog": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p],
     "ogg_event_create": [ctypes.POINTER(c_void_p)],
     "ogg_event_destroy": [c_void_p],
     "ogg_event_record": [c_void_p, c_void_p],
@@ -193,7 +218,10 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_supergrid_pass_plan_slots": [c_void_p],
                 "ogg_supergrid_pass_plan_carried_runs": [c_void_p],
                 "ogg_grid_quality_result_bytes": [],
-                "ogg_grid_quality_workspace_bytes": [c_long, c_long]}
+                "ogg_grid_quality_workspace_bytes": [c_long, c_long],
+                "ogg_topog_record_bytes": [],
+                "ogg_topog_band_out_rows": [ctypes.POINTER(TopogBand)],
+                "ogg_topog_workspace_bytes": []}
 
 _lib = None
 

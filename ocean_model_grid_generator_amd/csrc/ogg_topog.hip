@@ -1,0 +1,448 @@
+// Topography by refined sampling (include/ogg_hip.h, "Topography by refined sampling"): every output cell (a model cell = 2 x 2
+// supergrid cells, or one supergrid cell) is filled with R x R samples per supergrid cell, each sample looks up its source raster
+// element, and the cell keeps integer sums, extremes and counts.
+//
+// topog_band_kernel: one wavefront per workgroup.  A wavefront takes runs of TR consecutive output cells of a row from a counter in
+// the workspace (so the cells that need many samples -- R up to 256 next to a pole -- do not hold up a static share), and owns each
+// output cell it takes: lanes 0..3 set up the (up to) four supergrid cells of it (unwrapped corners, R, pole test) into LDS, then the
+// whole wavefront walks the flattened samples f = b * R + a of each supergrid cell, lane l taking f = l, l + 64, ...: consecutive
+// lanes are consecutive a (along i, i.e. along a raster row), so one gather instruction touches a few 128-B lines.  s = (a + 0.5) / R
+// and 1 - s come from a per-wavefront LDS table rebuilt when R changes (two fp64 divisions per sample would otherwise dominate).
+// Each lane keeps its own counts, sums and extremes in registers; the wavefront reduces them with shuffles (integers: exact, in any
+// order) and lane 0 stores the record.  No atomics touch a result; the only atomic is the work counter.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <vector>
+
+#include "ogg_common.h"
+#include "ogg_math.h"
+
+namespace {
+
+constexpr int TT = 64;        // threads per workgroup: one wavefront
+constexpr int TR = 4;         // output cells per take from the counter
+constexpr int RMAX = OGG_TOPOG_MAX_REFINE;
+
+static_assert(sizeof(ogg_topog_record) == 56, "ogg_topog_record layout");
+
+struct Src {
+    const void* data;
+    int dtype;
+    int fill0, fill1;   // int16 fill values as integers (INT_MIN: none, or a fill that no int16 equals); int32 sources: unused
+    int wet_q;          // (double)q < wet_below  <=>  q < wet_q = ceil(wet_below) for an integer q (clamped to the int range)
+    long Nx, Ny;
+    double lon0, lat0, inv_dlon, inv_dlat, dlon, dlat;
+    bool periodic;
+};
+
+struct Geo {
+    const double *x, *y, *x_next, *y_next;
+    long nx, nxp, j0, n, m0, nxo, total;
+    int shift, refine;
+    double oversample;
+};
+
+// one supergrid cell, set up once per output cell
+struct Cell {
+    double L00, L01, L10, L11, y00, y01, y10, y11;
+    int R, pole;   // pole: 0, -1 south, +1 north
+    int clamped, valid;
+};
+
+// x mod 360 with numpy's % semantics (the result takes the sign of the divisor; an exact zero is +0)
+OGG_DEV double mod360(double x) {
+    double m = fmod(x, 360.0);
+    if (m != 0.0) {
+        if (m < 0.0) m += 360.0;
+    } else {
+        m = 0.0;
+    }
+    return m;
+}
+
+OGG_DEV double wrap180(double d) { return mod360(d + 180.0) - 180.0; }
+
+OGG_DEV Cell setup_cell(const Geo& g, const Src& s, long j, long i) {
+    Cell c;
+    c.valid = 1;
+    const long r = j - g.j0;   // 0 .. n - 1
+    const double* x0 = g.x + r * g.nxp;
+    const double* y0 = g.y + r * g.nxp;
+    const double* x1 = (r + 1 < g.n) ? g.x + (r + 1) * g.nxp : g.x_next;
+    const double* y1 = (r + 1 < g.n) ? g.y + (r + 1) * g.nxp : g.y_next;
+    const double x00 = x0[i], x01 = x0[i + 1], x10 = x1[i], x11 = x1[i + 1];
+    c.y00 = y0[i], c.y01 = y0[i + 1], c.y10 = y1[i], c.y11 = y1[i + 1];
+    const double l00 = x00 + wrap180(x00 - x00), l01 = x00 + wrap180(x01 - x00), l10 = x00 + wrap180(x10 - x00),
+                 l11 = x00 + wrap180(x11 - x00);
+    const double pl = 90.0 - OGG_TOPOG_POLE_EPS;
+    c.L00 = fabs(c.y00) >= pl ? l01 : l00;
+    c.L01 = fabs(c.y01) >= pl ? l00 : l01;
+    c.L10 = fabs(c.y10) >= pl ? l11 : l10;
+    c.L11 = fabs(c.y11) >= pl ? l10 : l11;
+    c.clamped = 0;
+    if (g.refine > 0) {
+        c.R = g.refine;
+    } else {
+        const double span_l = fmax(fmax(c.L00, c.L01), fmax(c.L10, c.L11)) - fmin(fmin(c.L00, c.L01), fmin(c.L10, c.L11));
+        const double span_y = fmax(fmax(c.y00, c.y01), fmax(c.y10, c.y11)) - fmin(fmin(c.y00, c.y01), fmin(c.y10, c.y11));
+        const double v = ceil(g.oversample * fmax(span_l / s.dlon, span_y / s.dlat));
+        if (!(v <= (double)RMAX)) {
+            c.R = RMAX, c.clamped = 1;
+        } else {
+            c.R = v < 1.0 ? 1 : (int)v;
+        }
+    }
+    const double w = wrap180(c.L01 - c.L00) + wrap180(c.L11 - c.L01) + wrap180(c.L10 - c.L11) + wrap180(c.L00 - c.L10);
+    c.pole = fabs(w) > 180.0 ? ((c.y00 + c.y01 + c.y10 + c.y11 > 0.0) ? 1 : -1) : 0;
+    return c;
+}
+
+struct Acc {
+    int n, nm, nw, mn, mx;
+    long long sum, sumsq;
+};
+
+template <int DT>
+OGG_DEV void sample_cell(const Src& s, const Cell& c, const double* S, const double* U, int lane, Acc& acc) {
+    const int R = c.R;
+    const int RR = R * R;
+    int f = lane;
+    if (f >= RR) return;
+    int a = f % R, b = f / R;
+    const int step_b = TT / R, step_a = TT % R;
+    const long Nx = s.Nx, Ny = s.Ny;
+    const double dNx = (double)Nx, dNy = (double)Ny, inv_Nx = 1.0 / dNx;
+    for (; f < RR; f += TT) {
+        const double sa = S[a], ua = U[a];
+        double lon, lat = 0.0;
+        if (c.pole == 0) {
+            const double tb = S[b], vb = U[b];
+            const double w00 = ua * vb, w01 = sa * vb, w10 = ua * tb, w11 = sa * tb;
+            lon = w00 * c.L00 + w01 * c.L01 + w10 * c.L10 + w11 * c.L11;
+            lat = w00 * c.y00 + w01 * c.y01 + w10 * c.y10 + w11 * c.y11;
+        } else {
+            lon = c.L00 + 360.0 * sa;
+        }
+        double fi = floor((lon - s.lon0) * s.inv_dlon);
+        bool miss = false;
+        int is, js;
+        if (s.periodic) {
+            // fi mod Nx without an integer division: fi is an integral double (|fi| < 2^52 below), so fi - Nx * floor(fi / Nx),
+            // taken with the reciprocal and set right by one step either way, is exact
+            miss = !(fabs(fi) < 4.0e15);   // not a number (a grid without NaN never gets here): no index is formed from it
+            double r = miss ? 0.0 : fi - dNx * floor(fi * inv_Nx);
+            r = r < 0.0 ? r + dNx : r;
+            r = r >= dNx ? r - dNx : r;
+            is = (int)r;
+        } else {
+            miss = !(fi >= 0.0 && fi < dNx);
+            is = miss ? 0 : (int)fi;
+        }
+        if (c.pole != 0) {
+            js = c.pole < 0 ? 0 : (int)(Ny - 1);
+        } else {
+            double fj = floor((lat - s.lat0) * s.inv_dlat);
+            if (s.periodic && fj == fj) {
+                fj = fj < 0.0 ? 0.0 : (fj > dNy - 1.0 ? dNy - 1.0 : fj);
+            } else if (!(fj >= 0.0 && fj < dNy)) {
+                miss = true, fj = 0.0;
+            }
+            js = (int)fj;
+        }
+        if (!miss) {
+            int q;
+            if (DT == OGG_TOPOG_INT16) {
+                const int v = static_cast<const short*>(s.data)[(long)js * Nx + is];
+                miss = v == s.fill0 || v == s.fill1;
+                q = v;
+            } else {
+                q = static_cast<const int*>(s.data)[(long)js * Nx + is];
+                miss = q == OGG_TOPOG_MISSING_Q;
+            }
+            if (!miss) {
+                acc.n += 1;
+                acc.nw += q < s.wet_q ? 1 : 0;
+                acc.sum += q;
+                acc.sumsq += (long long)q * q;
+                acc.mn = q < acc.mn ? q : acc.mn;
+                acc.mx = q > acc.mx ? q : acc.mx;
+            }
+        }
+        if (miss) acc.nm += 1;
+        a += step_a, b += step_b;
+        if (a >= R) a -= R, b += 1;
+    }
+}
+
+OGG_DEV long long wave_sum(long long v) {
+    for (int o = TT / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, TT);
+    return v;
+}
+OGG_DEV int wave_sum(int v) {
+    for (int o = TT / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, TT);
+    return v;
+}
+OGG_DEV int wave_min(int v) {
+    for (int o = TT / 2; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, TT));
+    return v;
+}
+OGG_DEV int wave_max(int v) {
+    for (int o = TT / 2; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, TT));
+    return v;
+}
+
+template <int DT>
+__global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned long long* counter, ogg_topog_record* out) {
+    __shared__ double S[RMAX], U[RMAX];
+    __shared__ Cell cells[4];
+    __shared__ long long take;
+    const int lane = threadIdx.x;
+    int table_R = 0;
+    const int side = 1 << g.shift;
+    for (;;) {
+        if (lane == 0) take = (long long)atomicAdd(counter, (unsigned long long)TR);
+        __syncthreads();
+        const long long c0 = take;
+        __syncthreads();
+        if (c0 >= g.total) break;
+        const long long c1 = c0 + TR < g.total ? c0 + TR : g.total;
+        for (long long c = c0; c < c1; ++c) {
+            const long m = g.m0 + (long)(c / g.nxo), io = (long)(c % g.nxo);
+            if (lane < side * side) {   // lane = 2 dj + di
+                const long j = (m << g.shift) + (lane >> 1), i = (io << g.shift) + (lane & 1);
+                Cell cl;
+                if (j >= g.j0 && j < g.j0 + g.n) {
+                    cl = setup_cell(g, s, j, i);
+                } else {
+                    cl.valid = 0, cl.R = 0, cl.pole = 0, cl.clamped = 0;
+                }
+                cells[lane] = cl;
+            }
+            __syncthreads();
+            Acc acc{0, 0, 0, INT_MAX, INT_MIN, 0, 0};
+            int Rmax = 0, n_pole = 0, n_clamped = 0;
+            for (int k = 0; k < side * side; ++k) {
+                const Cell cl = cells[k];
+                if (!cl.valid) continue;
+                Rmax = cl.R > Rmax ? cl.R : Rmax;
+                n_pole += cl.pole != 0;
+                n_clamped += cl.clamped;
+                if (cl.R != table_R) {   // s = (a + 0.5) / R and 1 - s for this R
+                    __syncthreads();
+                    for (int a = lane; a < cl.R; a += TT) {
+                        const double sv = ((double)a + 0.5) / (double)cl.R;
+                        S[a] = sv, U[a] = 1.0 - sv;
+                    }
+                    __syncthreads();
+                    table_R = cl.R;
+                }
+                sample_cell<DT>(s, cl, S, U, lane, acc);
+            }
+            const int n = wave_sum(acc.n), nm = wave_sum(acc.nm), nw = wave_sum(acc.nw);
+            const long long sum = wave_sum(acc.sum), sumsq = wave_sum(acc.sumsq);
+            const int mn = wave_min(acc.mn), mx = wave_max(acc.mx);
+            if (lane == 0) {
+                ogg_topog_record r;
+                r.n = n, r.n_missing = nm, r.n_wet = nw, r.sum = sum, r.sumsq = sumsq;
+                r.min = mn, r.max = mx, r.R = Rmax, r.n_pole = (short)n_pole, r.n_clamped = (short)n_clamped;
+                out[c] = r;
+            }
+            __syncthreads();   // cells[] is rewritten for the next output cell
+        }
+    }
+}
+
+template <typename T>
+__global__ void topog_quantize_kernel(const T* v, long n, double quantum, int n_fill, double f0, double f1, int* q, int* n_bad) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
+        const double d = (double)v[k];
+        int out = OGG_TOPOG_MISSING_Q;
+        if (!(d != d) && !(n_fill > 0 && d == f0) && !(n_fill > 1 && d == f1)) {
+            const double r = rint(d / quantum);
+            if (!(fabs(r) <= (double)OGG_TOPOG_MAX_Q)) {
+                *n_bad = 1;   // every writer stores the same value
+            } else {
+                out = (int)r;
+            }
+        }
+        q[k] = out;
+    }
+}
+
+int check_source(const ogg_topog_source& s, bool sampled) {
+    OGG_REQUIRE(s.Nx >= 1 && s.Ny >= 1 && s.Nx < (1L << 30) && s.Ny < (1L << 30), OGG_ESHAPE, "ogg_topog: source of %ld x %ld", s.Ny,
+                s.Nx);
+    OGG_REQUIRE(s.dlon > 0.0 && s.dlat > 0.0, OGG_EARG, "ogg_topog: dlon and dlat must be positive (%g, %g)", s.dlon, s.dlat);
+    OGG_REQUIRE(s.n_fill >= 0 && s.n_fill <= 2, OGG_EARG, "ogg_topog: n_fill = %d", s.n_fill);
+    OGG_REQUIRE(s.data, OGG_EARG, "ogg_topog: null source data");
+    if (sampled)
+        OGG_REQUIRE(s.dtype == OGG_TOPOG_INT16 || s.dtype == OGG_TOPOG_INT32, OGG_EARG,
+                    "ogg_topog_band: source dtype %d: quantise a float source first (ogg_topog_quantize_dev)", s.dtype);
+    else
+        OGG_REQUIRE(s.dtype >= OGG_TOPOG_INT16 && s.dtype <= OGG_TOPOG_FLOAT64, OGG_EARG, "ogg_topog: source dtype %d", s.dtype);
+    if (s.dtype >= OGG_TOPOG_FLOAT32)
+        OGG_REQUIRE(s.quantum > 0.0 && std::isfinite(s.quantum), OGG_EARG, "ogg_topog: quantum must be positive (%g)", s.quantum);
+    return OGG_OK;
+}
+
+int check_band(const ogg_topog_band& b) {
+    OGG_REQUIRE(b.nx >= 1 && b.j0 >= 0 && b.n_cell_rows >= 0, OGG_ESHAPE, "ogg_topog_band: nx %ld, j0 %ld, %ld rows", b.nx, b.j0,
+                b.n_cell_rows);
+    OGG_REQUIRE(b.cells == OGG_TOPOG_MODEL_CELLS || b.cells == OGG_TOPOG_SUPERGRID_CELLS, OGG_EARG, "ogg_topog_band: cells = %d", b.cells);
+    OGG_REQUIRE(b.cells != OGG_TOPOG_MODEL_CELLS || b.nx % 2 == 0, OGG_ESHAPE,
+                "ogg_topog_band: model cells need an even number of supergrid columns (nx = %ld)", b.nx);
+    OGG_REQUIRE(b.refine >= 0 && b.refine <= RMAX, OGG_EARG, "ogg_topog_band: refine = %d (0 or 1 .. %d)", b.refine, RMAX);
+    OGG_REQUIRE(b.refine > 0 || (b.oversample > 0.0 && std::isfinite(b.oversample)), OGG_EARG, "ogg_topog_band: oversample = %g",
+                b.oversample);
+    return OGG_OK;
+}
+
+// fill[k] of an int16 source as the int an int16 v must equal ((double)v == fill[k]); INT_MIN when there is none or no int16 equals it
+int int16_fill(const ogg_topog_source& s, int k) {
+    if (s.dtype != OGG_TOPOG_INT16 || k >= s.n_fill) return INT_MIN;
+    const double f = s.fill[k];
+    return (f >= -32768.0 && f <= 32767.0 && f == floor(f)) ? (int)f : INT_MIN;
+}
+
+// the integer threshold of "wet": for an integer q, q < w <=> q < ceil(w); |q| <= 2^31 - 1 bounds what matters
+int wet_threshold(double w) {
+    if (w != w) return INT_MIN;   // NaN: nothing is wet
+    const double c = ceil(w);
+    return c > 2147483647.0 ? INT_MAX : (c < -2147483647.0 ? INT_MIN + 1 : (int)c);
+}
+
+long out_rows(const ogg_topog_band& b) {
+    if (b.n_cell_rows == 0) return 0;
+    const int sh = b.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0;
+    return ((b.j0 + b.n_cell_rows - 1) >> sh) - (b.j0 >> sh) + 1;
+}
+
+}  // namespace
+
+extern "C" long ogg_topog_record_bytes(void) { return (long)sizeof(ogg_topog_record); }
+
+extern "C" long ogg_topog_workspace_bytes(void) { return 256; }
+
+extern "C" long ogg_topog_band_out_rows(const ogg_topog_band* band) {
+    if (!band || band->nx < 1 || band->j0 < 0 || band->n_cell_rows < 0) return -1;
+    return out_rows(*band);
+}
+
+extern "C" int ogg_topog_band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* workspace, long workspace_bytes,
+                                  ogg_topog_record* out, void* stream) {
+    OGG_REQUIRE(band && src, OGG_EARG, "ogg_topog_band: null pointer");
+    if (int e = check_band(*band)) return e;
+    if (int e = check_source(*src, true)) return e;
+    const ogg_topog_band& b = *band;
+    const long rows = out_rows(b);
+    if (rows == 0) return OGG_OK;
+    OGG_REQUIRE(b.x && b.y && b.x_next && b.y_next && out, OGG_EARG, "ogg_topog_band: null x / y / x_next / y_next / out");
+    OGG_REQUIRE(workspace && workspace_bytes >= ogg_topog_workspace_bytes(), OGG_EARG, "ogg_topog_band: workspace of %ld bytes, %ld needed",
+                workspace_bytes, ogg_topog_workspace_bytes());
+    const ogg_topog_source& q = *src;
+    const int shift = b.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0;
+    Geo g{b.x, b.y, b.x_next, b.y_next, b.nx, b.nx + 1, b.j0, b.n_cell_rows, b.j0 >> shift, b.nx >> shift, 0, shift, b.refine,
+          b.oversample};
+    g.total = rows * g.nxo;
+    Src s{q.data, q.dtype, int16_fill(q, 0), int16_fill(q, 1), wet_threshold(q.wet_below), q.Nx, q.Ny, q.lon0, q.lat0, 1.0 / q.dlon,
+          1.0 / q.dlat, q.dlon, q.dlat, fabs((double)q.Nx * q.dlon - 360.0) <= 1e-9};
+    hipStream_t st = ogg::as_stream(stream);
+    OGG_HIP_CHECK(hipMemsetAsync(workspace, 0, sizeof(unsigned long long), st));
+    int dev = 0, n_cu = 0;
+    OGG_HIP_CHECK(hipGetDevice(&dev));
+    OGG_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    const long takes = (g.total + TR - 1) / TR;
+    const long wgs = std::min(takes, (long)(n_cu > 0 ? n_cu : 256) * 32);   // 32 one-wave workgroups per CU, persistent
+    auto* counter = static_cast<unsigned long long*>(workspace);
+    if (q.dtype == OGG_TOPOG_INT16)
+        topog_band_kernel<OGG_TOPOG_INT16><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+    else
+        topog_band_kernel<OGG_TOPOG_INT32><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+extern "C" int ogg_topog_quantize_dev(const ogg_topog_source* src, int* q, int* n_bad, void* stream) {
+    OGG_REQUIRE(src && q && n_bad, OGG_EARG, "ogg_topog_quantize: null pointer");
+    if (int e = check_source(*src, false)) return e;
+    OGG_REQUIRE(src->dtype == OGG_TOPOG_FLOAT32 || src->dtype == OGG_TOPOG_FLOAT64, OGG_EARG,
+                "ogg_topog_quantize: source dtype %d is not a float type", src->dtype);
+    hipStream_t st = ogg::as_stream(stream);
+    OGG_HIP_CHECK(hipMemsetAsync(n_bad, 0, sizeof(int), st));
+    const long n = src->Nx * src->Ny;
+    const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 65536);
+    const double f0 = src->n_fill > 0 ? src->fill[0] : 0.0, f1 = src->n_fill > 1 ? src->fill[1] : 0.0;
+    if (src->dtype == OGG_TOPOG_FLOAT32)
+        topog_quantize_kernel<float><<<blocks, 256, 0, st>>>(static_cast<const float*>(src->data), n, src->quantum, src->n_fill, f0, f1,
+                                                             q, n_bad);
+    else
+        topog_quantize_kernel<double><<<blocks, 256, 0, st>>>(static_cast<const double*>(src->data), n, src->quantum, src->n_fill, f0,
+                                                              f1, q, n_bad);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+// the host-pointer form: grid rows and raster copied to device memory, one band, the records copied back (synchronous)
+extern "C" int ogg_topog(const ogg_topog_band* band, const ogg_topog_source* src, ogg_topog_record* out) {
+    OGG_REQUIRE(band && src && out, OGG_EARG, "ogg_topog: null pointer");
+    if (int e = check_band(*band)) return e;
+    if (int e = check_source(*src, false)) return e;
+    const ogg_topog_band& h = *band;
+    OGG_REQUIRE(h.x && h.y, OGG_EARG, "ogg_topog: null x / y");
+    const long rows = out_rows(h);
+    if (rows == 0) return OGG_OK;
+    struct Buffers {   // freed on every exit path
+        std::vector<void*> p;
+        ~Buffers() {
+            for (void* q : p) (void)hipFree(q);
+        }
+        int alloc(void** out, size_t bytes) {
+            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
+            if (e != hipSuccess)
+                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
+                                      hipGetErrorString(e));
+            p.push_back(*out);
+            return OGG_OK;
+        }
+    } bufs;
+    const long nxp = h.nx + 1, n = h.n_cell_rows;
+    ogg_topog_band d = h;
+    void *px = nullptr, *py = nullptr;
+    if (int e = bufs.alloc(&px, (size_t)(n + 1) * nxp * sizeof(double))) return e;
+    if (int e = bufs.alloc(&py, (size_t)(n + 1) * nxp * sizeof(double))) return e;
+    const size_t body = (size_t)n * nxp * sizeof(double), row = (size_t)nxp * sizeof(double);
+    OGG_HIP_CHECK(hipMemcpy(px, h.x, body, hipMemcpyHostToDevice));
+    OGG_HIP_CHECK(hipMemcpy(py, h.y, body, hipMemcpyHostToDevice));
+    OGG_HIP_CHECK(hipMemcpy(static_cast<char*>(px) + body, h.x_next ? h.x_next : h.x + n * nxp, row, hipMemcpyHostToDevice));
+    OGG_HIP_CHECK(hipMemcpy(static_cast<char*>(py) + body, h.y_next ? h.y_next : h.y + n * nxp, row, hipMemcpyHostToDevice));
+    d.x = static_cast<const double*>(px), d.y = static_cast<const double*>(py);
+    d.x_next = d.x + n * nxp, d.y_next = d.y + n * nxp;
+    const ogg_topog_source& hs = *src;
+    ogg_topog_source ds = hs;
+    const long nsrc = hs.Nx * hs.Ny;
+    const size_t esize = hs.dtype == OGG_TOPOG_INT16 ? 2 : (hs.dtype == OGG_TOPOG_FLOAT64 ? 8 : 4);
+    void* raw = nullptr;
+    if (int e = bufs.alloc(&raw, (size_t)nsrc * esize)) return e;
+    OGG_HIP_CHECK(hipMemcpy(raw, hs.data, (size_t)nsrc * esize, hipMemcpyHostToDevice));
+    ds.data = raw;
+    if (hs.dtype == OGG_TOPOG_FLOAT32 || hs.dtype == OGG_TOPOG_FLOAT64) {
+        void *qd = nullptr, *bad = nullptr;
+        if (int e = bufs.alloc(&qd, (size_t)nsrc * sizeof(int))) return e;
+        if (int e = bufs.alloc(&bad, sizeof(int))) return e;
+        if (int e = ogg_topog_quantize_dev(&ds, static_cast<int*>(qd), static_cast<int*>(bad), nullptr)) return e;
+        int nb = 0;
+        OGG_HIP_CHECK(hipMemcpy(&nb, bad, sizeof(int), hipMemcpyDeviceToHost));
+        OGG_REQUIRE(nb == 0, OGG_EARG, "ogg_topog: a quantised source value exceeds %d in magnitude (quantum %g too small)", OGG_TOPOG_MAX_Q,
+                    hs.quantum);
+        ds.data = qd, ds.dtype = OGG_TOPOG_INT32, ds.n_fill = 0;
+    }
+    const long nrec = rows * (h.nx >> (h.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0));
+    void *ws = nullptr, *res = nullptr;
+    if (int e = bufs.alloc(&ws, (size_t)ogg_topog_workspace_bytes())) return e;
+    if (int e = bufs.alloc(&res, (size_t)nrec * sizeof(ogg_topog_record))) return e;
+    if (int e = ogg_topog_band_dev(&d, &ds, ws, ogg_topog_workspace_bytes(), static_cast<ogg_topog_record*>(res), nullptr)) return e;
+    OGG_HIP_CHECK(hipMemcpy(out, res, (size_t)nrec * sizeof(ogg_topog_record), hipMemcpyDeviceToHost));
+    return OGG_OK;
+}

@@ -1,6 +1,6 @@
 """Minimal writer for the NetCDF classic format, 64-bit-offset variant (CDF-2) -- what the reference asks netCDF4 for
-with format="NETCDF3_64BIT" (OGG:773-779).  Only what write_nc needs: fixed-size dimensions, char and double
-variables, text attributes, variables laid out in definition order.  The file is a fixed header followed by the
+with format="NETCDF3_64BIT" (OGG:773-779).  Only what write_nc and topog.nc need: fixed-size dimensions, char, numeric
+variables, text and single-number attributes, variables laid out in definition order.  The file is a fixed header followed by the
 variables' data, big-endian, each padded to 4 bytes, so writing it is a bandwidth-bound stream of the six fields.
 
 Format reference: "The NetCDF Classic Format Specification" (header := magic numrecs dim_list gatt_list var_list).
@@ -9,7 +9,8 @@ import struct
 
 import numpy as np
 
-NC_CHAR, NC_DOUBLE = 2, 6
+NC_BYTE, NC_CHAR, NC_SHORT, NC_INT, NC_FLOAT, NC_DOUBLE = 1, 2, 3, 4, 5, 6
+_NUMPY_TYPE = {NC_BYTE: ">i1", NC_SHORT: ">i2", NC_INT: ">i4", NC_FLOAT: ">f4", NC_DOUBLE: ">f8"}
 NC_DIMENSION, NC_VARIABLE, NC_ATTRIBUTE = 0x0A, 0x0B, 0x0C
 _ABSENT = struct.pack(">ii", 0, 0)
 
@@ -28,6 +29,11 @@ def _att_list(atts):
         return _ABSENT
     out = struct.pack(">ii", NC_ATTRIBUTE, len(atts))
     for k, v in atts:
+        if isinstance(v, (float, np.floating)) or isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+            t = NC_DOUBLE if isinstance(v, (float, np.floating)) else NC_INT   # one number: a double or int attribute
+            b = np.array([v], dtype=_NUMPY_TYPE[t]).tobytes()
+            out += _name(k) + struct.pack(">ii", t, 1) + b + b"\0" * _pad4(len(b))
+            continue
         b = v if isinstance(v, bytes) else str(v).encode("utf-8")
         out += _name(k) + struct.pack(">ii", NC_CHAR, len(b)) + b + b"\0" * _pad4(len(b))
     return out
@@ -65,7 +71,7 @@ class Dataset(object):
         if self._layout is not None:
             return self._layout
         dimid = {n: k for k, (n, _) in enumerate(self.dims)}
-        esize = {NC_CHAR: 1, NC_DOUBLE: 8}
+        esize = {NC_CHAR: 1, NC_BYTE: 1, NC_SHORT: 2, NC_INT: 4, NC_FLOAT: 4, NC_DOUBLE: 8}
 
         def var_header(name, nc_type, dnames, atts, nbytes, begin):
             vsize = nbytes + _pad4(nbytes)
@@ -116,7 +122,7 @@ class Dataset(object):
                 else:
                     flat = data.reshape(-1, data.shape[-1]) if data.ndim > 1 else data.reshape(1, -1)
                     for r0 in range(0, flat.shape[0], chunk_rows):
-                        f.write(np.ascontiguousarray(flat[r0:r0 + chunk_rows]).astype(">f8").tobytes())
+                        f.write(np.ascontiguousarray(flat[r0:r0 + chunk_rows]).astype(_NUMPY_TYPE[v[1]]).tobytes())
                 f.write(b"\0" * _pad4(s))
 
 
@@ -125,8 +131,13 @@ _TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 4, 6: 8}   # NC_BYTE, NC_CHAR, NC_SHORT
 
 
 class Variable(object):
-    def __init__(self, name, nc_type, shape, begin, is_record):
+    def __init__(self, name, nc_type, shape, begin, is_record, atts=None):
         self.name, self.nc_type, self.shape, self.begin, self.is_record = name, nc_type, tuple(shape), begin, is_record
+        self.atts = atts if atts is not None else {}   # name -> str (char attribute) or 1-D numpy array
+        self.dims = ()                                  # dimension names
+
+
+NUMPY_DTYPE = {t: np.dtype(d) for t, d in _NUMPY_TYPE.items()}   # NetCDF type -> big-endian numpy dtype of its data
 
 
 class Header(object):
@@ -181,11 +192,17 @@ def _parse_header(path, data, version):
         tag, n = i32(), i32()
         if tag not in (0, NC_ATTRIBUTE):
             raise ValueError("%s: bad attribute list" % path)
+        out = {}
         for _ in range(n):
-            name()
+            k = name()
             t, m = i32(), i32()
+            if t not in _TYPE_SIZE:
+                raise ValueError("%s: attribute %s has NetCDF type %d (not a classic type)" % (path, k, t))
             nb = m * _TYPE_SIZE[t]
-            take(nb + _pad4(nb))
+            raw = take(nb + _pad4(nb))[:nb]
+            out[k] = raw.decode("utf-8", "replace") if t == NC_CHAR else np.frombuffer(raw, dtype=_NUMPY_TYPE[t]).astype(
+                _NUMPY_TYPE[t].replace(">", "="))
+        return out
 
     numrecs = i32()
     tag, ndims = i32(), i32()
@@ -200,13 +217,14 @@ def _parse_header(path, data, version):
     for _ in range(nvars):
         vname = name()
         ids = [i32() for _ in range(i32())]
-        atts()
+        vatts = atts()
         nc_type = i32()
         take(4)   # vsize
         begin = struct.unpack(">q" if version == 2 else ">i", take(8 if version == 2 else 4))[0]
         is_rec = bool(ids) and dims[ids[0]][1] == 0
         shape = [numrecs if (k == 0 and is_rec) else dims[d][1] for k, d in enumerate(ids)]
-        out[vname] = Variable(vname, nc_type, shape, begin, is_rec)
+        out[vname] = Variable(vname, nc_type, shape, begin, is_rec, vatts)
+        out[vname].dims = tuple(dims[d][0] for d in ids)
     return Header(version, dims, out)
 
 

@@ -641,7 +641,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          no_changing_meta=False, enhanced_equatorial=0, debug=False, grids="all", match_dy=(), skip_metrics=False,
          ensure_nj_even=False, shift_equator_to_u_point=True, bipolar_lower_lat=-99.0, mercator_lower_lat=-99.0,
          mercator_upper_lat=-99.0, south_ocean_lower_lat=-99.0, south_ocean_upper_lat=-99.0, no_south_cap=False,
-         return_arrays=False, path=None, dp_arc=None, cap_symmetry=None, quality_report=None):
+         return_arrays=False, path=None, dp_arc=None, cap_symmetry=None, quality_report=None, topog_source=None, topog_var="elevation",
+         topog_file="topog.nc", topog_refine=None):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -656,7 +657,9 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     value of the reference's formula as the reference's own), False: every column, as the reference does.  ``return_arrays=True``
     additionally returns the six stitched fields and the sub-grid pieces (used by tests).  ``quality_report`` (--quality_report FILE):
     write the grid-quality report of the stitched grid (grid_quality.py) to that file as JSON and print a summary of it after the
-    CHECK_metrics lines; an addition the reference does not have."""
+    CHECK_metrics lines; an addition the reference does not have.  ``topog_source`` (--topog_source FILE, or a topography.Source):
+    sample that raster (variable ``topog_var``) on the model cells of the stitched grid straight from HBM and write ``topog_file``
+    (topography.py; ``topog_refine``: R x R samples per supergrid cell instead of R from the cell's size); also an addition."""
     import time
 
     path = path or os.environ.get("OGG_MAIN_PATH", "pass")
@@ -666,7 +669,7 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
                                    reproduce_MIDAS_grids, write_subgrid_files, plotem, no_changing_meta, enhanced_equatorial, debug, grids,
                                    match_dy, skip_metrics, ensure_nj_even, shift_equator_to_u_point, bipolar_lower_lat, mercator_lower_lat,
                                    mercator_upper_lat, south_ocean_lower_lat, south_ocean_upper_lat, no_south_cap, return_arrays, dp_arc,
-                                   cap_symmetry, quality_report)
+                                   cap_symmetry, quality_report, topog_source, topog_var, topog_file, topog_refine)
     from . import supergrid as SG
 
     _validate_flags(match_dy, r_dp, lat_dp)
@@ -696,6 +699,10 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     cut = g.south_cut()
     if quality_report:
         _write_quality_report(g.quality(cut), quality_report)
+    if topog_source is not None:
+        from . import topography as T
+        src = _topog_source(topog_source, topog_var)
+        _write_topog(g.topography(cut, T.DeviceSource(src, g.device), refine=topog_refine), topog_file)
     print("Stitching the grids together...")
     SG.check_guards(g.stitched_column("y", plan.Ni // 4, cut), any(s.name == "BP" for s in plan.subs))
     names = [s.name for s in plan.subs if not (s.name == "SC" and cut[2])]
@@ -761,7 +768,8 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
                         no_changing_meta=False, enhanced_equatorial=0, debug=False, grids="all", match_dy=(), skip_metrics=False,
                         ensure_nj_even=False, shift_equator_to_u_point=True, bipolar_lower_lat=-99.0, mercator_lower_lat=-99.0,
                         mercator_upper_lat=-99.0, south_ocean_lower_lat=-99.0, south_ocean_upper_lat=-99.0, no_south_cap=False,
-                        return_arrays=False, dp_arc=None, cap_symmetry=None, quality_report=None):
+                        return_arrays=False, dp_arc=None, cap_symmetry=None, quality_report=None, topog_source=None,
+                        topog_var="elevation", topog_file="topog.nc", topog_refine=None):
     """The reference's own sequence of calls (OGG:855-1449), every callee a host-array function of this module (numpy in, numpy
     out, one staged device call each) and the stitching on the host: what a user gets who swaps the reference's module for this
     one function by function.  main() produces the same bits from one device-resident pass."""
@@ -983,6 +991,9 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
         metric_fields = (dx3, dy3, area3) if calculate_metrics else (None, None, None)
         _write_quality_report(grid_quality(x3, y3, *metric_fields, Re=_default_Re, sections=list(zip(names, starts)), seams=seams),
                               quality_report)
+    if topog_source is not None:   # the same topography as the device pass gives, from the stitched host arrays
+        from . import topography as T
+        _write_topog(T.topography(x3, y3, _topog_source(topog_source, topog_var), refine=topog_refine), topog_file)
 
     if write_subgrid_files:
         if "SC" in sub:
@@ -1044,6 +1055,22 @@ def _write_quality_report(rep, fnam):
         json.dump(rep, f, indent=1)
 
 
+def _topog_source(source, var):
+    from . import topography as T
+    if isinstance(source, T.Source):
+        return source
+    src = T.read_source(str(source), var)
+    print(src.note)
+    return src
+
+
+def _write_topog(res, fnam):
+    from . import topography as T
+    for line in T.summary_lines(res):
+        print(line)
+    T.write_topog(str(fnam), res)
+
+
 def build_parser():
     """The reference's flag surface (OGG:1452-1524), flag for flag."""
     parser = argparse.ArgumentParser(description="create ocean hgrid")
@@ -1089,6 +1116,12 @@ def build_parser():
     parser.add_argument("--quality_report", type=str, required=False, default=None,
                         help="write a grid-quality report (cell sizes, aspect ratio, non-orthogonality, smoothness, sub-grid seams) "
                              "of the stitched grid to this JSON file and print a summary")
+    parser.add_argument("--topog_source", type=str, required=False, default=None,
+                        help="bathymetry raster (NetCDF classic / 64-bit offset) to sample on the model cells of the grid into --topog_file")
+    parser.add_argument("--topog_var", type=str, required=False, default="elevation", help="variable of --topog_source, default elevation")
+    parser.add_argument("--topog_file", type=str, required=False, default="topog.nc", help="topography output file, default topog.nc")
+    parser.add_argument("--topog_refine", type=int, required=False, default=None,
+                        help="R x R samples in every supergrid cell (default: from each cell's size, twice the raster's resolution)")
     return parser
 
 

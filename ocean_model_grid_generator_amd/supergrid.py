@@ -1262,6 +1262,71 @@ class Supergrid(object):
         recs = [(q["sub"].name, q["j0"], Q.record_from_bytes(host[k])) for k, q in enumerate(pieces)]
         return Q.report(recs, self.plan.Re, self.stitched_rows(cut), self.plan.Ni, not self.plan.skip_metrics)
 
+    # -- topography by refined sampling -------------------------------------------------------------------------
+    def topography_records(self, cut, source, refine=None, oversample=2.0, cells="model", halo=None):
+        """[(piece index, first output row, int64 device tensor of records)] of THIS rank's pieces of the stitched grid, sampled on the
+        buffers the pass left in HBM.  A piece's last cell row takes its upper point row from the next piece (quality_halo); a model
+        row whose two supergrid rows lie in two pieces gets a partial record from each, combined exactly by the caller."""
+        from . import topography as T
+        p, st = self.plan, self._stream()
+        halo = self.quality_halo(cut) if halo is None else halo   # (held until the kernels have run: the bands point into it)
+        desc = source.desc
+        out, keep = [], []
+        for k, q in enumerate(self.quality_pieces(cut)):
+            if q["rank"] != self.rank or q["n_cell"] == 0:
+                continue
+            b, r = self.buf[q["sub"].name], q["row"]
+            band = L.TopogBand(nx=p.Ni, j0=q["j0"], n_cell_rows=q["n_cell"], refine=int(refine or 0), oversample=float(oversample),
+                               cells=L.TOPOG_MODEL_CELLS if cells == "model" else L.TOPOG_SUPERGRID_CELLS)
+            band.x, band.y = self._p(b["x"], r), self._p(b["y"], r)
+            nxt = halo.get(k, {}).get("next")
+            if nxt is not None:
+                band.x_next, band.y_next = nxt["x"].data_ptr(), nxt["y"].data_ptr()
+            else:   # the piece that ends the grid holds its own last point row
+                band.x_next, band.y_next = self._p(b["x"], r + q["n_cell"]), self._p(b["y"], r + q["n_cell"])
+            m0, rec, ws = T.band_records_dev(band, desc, st, self.device)
+            out.append((k, m0, rec))
+            keep.append(ws)
+        self.torch.cuda.synchronize(self.device)
+        return out
+
+    def topography(self, cut, source, refine=None, oversample=2.0, cells="model"):
+        """Topography of the stitched grid of every rank (topography.result on rank 0, None on the other ranks): ``source`` a
+        topography.DeviceSource on this rank's GPU.  Every piece is sampled by the rank that holds it; rank 0 gathers the integer records
+        (from peer objects with halo="local", over torch.distributed otherwise) and combines them exactly, so the result is
+        bit-identical for any number of ranks."""
+        from . import topography as T
+        torch = self.torch
+        nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
+        T.check_args(nyp, nxp, cells, refine, oversample)
+        sh = 1 if cells == "model" else 0
+        pieces = self.quality_pieces(cut)
+        if self.world > 1 and self.halo == "local" and self.rank != 0:
+            return None   # rank 0 samples the pieces of every virtual rank through its peer objects
+        mine = self.topography_records(cut, source, refine, oversample, cells)
+        got = [(m0, rec) for _, m0, rec in mine]
+        if self.world > 1 and self.halo == "local":
+            for g in self.peers:
+                if g is not self:
+                    got += [(m0, rec) for _, m0, rec in g.topography_records(cut, source, refine, oversample, cells)]
+        elif self.world > 1:
+            import torch.distributed as dist
+            words = L.TOPOG_RECORD.itemsize // 8
+            gloo = dist.get_backend() == "gloo"
+            if self.rank != 0:
+                for _, _, rec in mine:
+                    dist.send(rec.cpu() if gloo else rec.contiguous(), 0)
+                return None
+            for q in pieces:   # in piece order, as every other rank sends its own
+                if q["rank"] == 0 or q["n_cell"] == 0:
+                    continue
+                rows = ((q["j0"] + q["n_cell"] - 1) >> sh) - (q["j0"] >> sh) + 1
+                t = torch.empty((rows, self.plan.Ni >> sh, words), dtype=torch.int64, device="cpu" if gloo else self.device)
+                dist.recv(t, q["rank"])
+                got.append((q["j0"] >> sh, t))
+        recs = T.assemble([(m0, T.records_to_host(t)) for m0, t in got], (nyp - 1) >> sh, (nxp - 1) >> sh)
+        return T.result(recs, source.source.quantum, source.sea_level, cells, refine, oversample, source.source)
+
     def bands_to_host(self):
         """This rank's bands as numpy arrays (halo rows dropped): {sub: {field: array}}."""
         out = {}

@@ -1,0 +1,434 @@
+"""Topography by refined sampling: the cell mean, spread, extremes and wet fraction of a bathymetry raster on a supergrid, the
+``topog.nc`` MOM6 reads (include/ogg_hip.h, "Topography by refined sampling", gives the definition).  The reference has no such step.
+
+Every sample is taken on the device by libogg_hip.so (ogg_topog_band_dev / ogg_topog): one integer record per output cell (counts,
+sum q, sum q^2, min, max of the quantised source values q), combined here only by integer sums, minima and maxima, so the result is
+bit-identical whatever the split of the grid into bands or ranks.  The floating outputs are a fixed function of those integers.
+
+    python -m ocean_model_grid_generator_amd.topography ocean_hgrid.nc SOURCE -o topog.nc [--var elevation] [--refine R]
+        [--oversample F] [--quantum Q] [--sea_level L] [--supergrid_cells] [--json summary.json] [--source_box LON0 DLON LAT0 DLAT]
+
+SOURCE is a NetCDF classic / 64-bit-offset file (a short, float or double variable on uniform 1-D lon / lat coordinates) or a .npy
+array with --source_box (cell edges: lon0 + is * dlon, lat0 + js * dlat, row 0 southmost).
+"""
+import argparse
+import ctypes
+import json
+import sys
+
+import numpy as np
+
+from . import _lib as L
+from . import netcdf3
+
+FILL = 1.0e20                 # _FillValue of the floating outputs (cells without a valid sample)
+DEFAULT_QUANTUM = 0.01        # float sources: q = rint(v / quantum)
+_NCCOPY = "convert it with `nccopy -k 64-bit-offset IN OUT`"
+_EMPTY = (0, 0, 0, 0, 0, np.iinfo(np.int32).max, np.iinfo(np.int32).min, 0, 0, 0)   # a record with no sample
+_DTYPES = {np.dtype(np.int16): L.TOPOG_INT16, np.dtype(np.float32): L.TOPOG_FLOAT32, np.dtype(np.float64): L.TOPOG_FLOAT64}
+
+
+# ---- sources -------------------------------------------------------------------------------------------------
+class Source(object):
+    """A raster on the host: data (Ny x Nx; int16, float32 or float64, row 0 southmost), its cell edges lon0 + is * dlon,
+    lat0 + js * dlat, the raw values that mark missing (``fill``), and the quantum of one integer step (int16: 1, or the
+    variable's scale_factor; float: DEFAULT_QUANTUM unless given).  ``note`` says how the box was found."""
+
+    def __init__(self, data, lon0, dlon, lat0, dlat, fill=(), quantum=None, note=""):
+        data = np.asarray(data)
+        if data.ndim != 2 or data.dtype.newbyteorder("=") not in _DTYPES:
+            raise ValueError("topography source: a 2-D int16, float32 or float64 array is needed, not %s %s" % (data.dtype, data.shape))
+        self.data = np.ascontiguousarray(data, dtype=data.dtype.newbyteorder("="))
+        self.lon0, self.dlon, self.lat0, self.dlat = float(lon0), float(dlon), float(lat0), float(dlat)
+        if not (self.dlon > 0 and self.dlat > 0):
+            raise ValueError("topography source: dlon and dlat must be positive (%g, %g); rows go south to north" % (dlon, dlat))
+        self.fill = tuple(float(self.data.dtype.type(f)) for f in fill)   # a fill value as the raster's type holds it
+        if len(self.fill) > 2:
+            raise ValueError("topography source: at most two fill values")
+        is_int = self.data.dtype == np.int16
+        self.quantum = float(quantum if quantum is not None else (1.0 if is_int else DEFAULT_QUANTUM))
+        if not (self.quantum > 0 and np.isfinite(self.quantum)):
+            raise ValueError("topography source: the quantum must be positive (%r)" % quantum)
+        self.note = note
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def periodic(self):
+        return abs(self.data.shape[1] * self.dlon - 360.0) <= 1e-9
+
+    def descriptor(self, sea_level=0.0):
+        Ny, Nx = self.data.shape
+        d = L.TopogSource(data=self.data.ctypes.data, dtype=_DTYPES[self.data.dtype], n_fill=len(self.fill), Nx=Nx, Ny=Ny, lon0=self.lon0,
+                          dlon=self.dlon, lat0=self.lat0, dlat=self.dlat, quantum=self.quantum, wet_below=float(sea_level) / self.quantum)
+        for k, f in enumerate(self.fill):
+            d.fill[k] = f
+        return d
+
+
+class DeviceSource(object):
+    """A Source uploaded once to one GPU: int16 as it is, a float raster quantised there to int32 (ogg_topog_quantize_dev)."""
+
+    def __init__(self, source, device, sea_level=0.0):
+        import torch
+        self.source, self.device, self.sea_level = source, torch.device(device), float(sea_level)
+        raw = torch.from_numpy(source.data).to(self.device)
+        d = source.descriptor(sea_level)
+        if source.data.dtype == np.int16:
+            self.tensor = raw
+        else:
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            q = torch.empty(source.data.shape, dtype=torch.int32, device=self.device)
+            bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+            d.data = raw.data_ptr()
+            L.call("ogg_topog_quantize_dev", ctypes.byref(d), q.data_ptr(), bad.data_ptr(), st)
+            if int(bad.item()) != 0:
+                raise ValueError("topography source: a value / quantum exceeds 2^21 in magnitude; use a larger --quantum than %g"
+                                 % source.quantum)
+            del raw
+            self.tensor = q
+            d.dtype, d.n_fill = L.TOPOG_INT32, 0
+        d.data = self.tensor.data_ptr()
+        self.desc = d
+
+
+def _uniform_axis(path, name, c):
+    c = np.asarray(c, dtype=np.float64).reshape(-1)
+    if c.size < 2:
+        raise ValueError("%s: coordinate %s has %d values; two or more are needed" % (path, name, c.size))
+    step = (c[-1] - c[0]) / (c.size - 1)
+    if step == 0 or np.max(np.abs(np.diff(c) - step)) > 1e-9 * abs(step):
+        raise ValueError("%s: coordinate %s is not uniform within 1e-9 of its step %r" % (path, name, step))
+    return c, step
+
+
+def _edges(c0, step):
+    """(first edge, note): coordinates at half-steps of the lattice k * step are cell centres, any others are taken as edges."""
+    r = c0 / abs(step) - 0.5
+    if abs(r - round(r)) <= 1e-6:
+        return c0 - 0.5 * abs(step), "centres"
+    return c0, "edges"
+
+
+_LAT_NAMES, _LON_NAMES = ("lat", "latitude", "y", "nlat"), ("lon", "longitude", "x", "nlon")
+
+
+def _lat_lon_dims(path, h, v):
+    """(latitude dimension, longitude dimension) of a 2-D variable, from its coordinate variables' units (degrees_north /
+    degrees_east, as CF has them) or, without units, their names; a file where neither decides is refused."""
+    kinds = []
+    for d in v.dims:
+        cv = h.vars.get(d)
+        units = cv.atts.get("units", "") if cv is not None else ""
+        units = units.strip().lower() if isinstance(units, str) else ""
+        if units in ("degrees_north", "degree_north", "degrees_n", "degree_n"):
+            kinds.append("lat")
+        elif units in ("degrees_east", "degree_east", "degrees_e", "degree_e"):
+            kinds.append("lon")
+        elif d.lower() in _LAT_NAMES:
+            kinds.append("lat")
+        elif d.lower() in _LON_NAMES:
+            kinds.append("lon")
+        else:
+            kinds.append(None)
+    if sorted(k for k in kinds if k) != ["lat", "lon"]:
+        raise ValueError("%s: cannot tell the latitude and longitude dimensions of %s%s: give the coordinate variables units "
+                         "degrees_north / degrees_east" % (path, v.name, tuple(v.dims)))
+    return (v.dims[0], v.dims[1]) if kinds[0] == "lat" else (v.dims[1], v.dims[0])
+
+
+def read_source_nc(path, var="elevation", quantum=None):
+    """A Source from a NetCDF classic (CDF-1) or 64-bit-offset (CDF-2) file: the short / float / double variable ``var`` of
+    dimensions (lat, lon) or (lon, lat) (told apart by the coordinates' units or names), its box from the 1-D coordinate variables of those dimensions (uniform within 1e-9 of their step; cell
+    centres or edges, as ``note`` says); rows are flipped when latitude decreases.  _FillValue / missing_value mark missing values;
+    a short variable's scale_factor is its quantum.  CDF-5 and NetCDF-4 / HDF5 files are refused."""
+    try:
+        h = netcdf3.read_header(path)
+    except ValueError as e:
+        if "CDF-5" in str(e) or "HDF5" in str(e):
+            raise ValueError("%s: only NetCDF classic / 64-bit-offset sources are read; %s" % (str(e).split(";")[0], _NCCOPY))
+        raise
+    if var not in h.vars:
+        raise KeyError("%s: no variable %r (variables: %s); choose one with --var" % (path, var, ", ".join(sorted(h.vars))))
+    v = h.vars[var]
+    if v.nc_type not in (netcdf3.NC_SHORT, netcdf3.NC_FLOAT, netcdf3.NC_DOUBLE) or len(v.shape) != 2:
+        raise ValueError("%s: %s must be a 2-D short, float or double variable (type %d, shape %s)" % (path, var, v.nc_type, v.shape))
+    if "add_offset" in v.atts and float(np.asarray(v.atts["add_offset"]).reshape(-1)[0]) != 0.0:
+        raise ValueError("%s: %s has a non-zero add_offset, which is not supported" % (path, var))
+    lat_name, lon_name = _lat_lon_dims(path, h, v)
+    axes = {}
+    for dname in (lat_name, lon_name):
+        if dname not in h.vars:
+            raise ValueError("%s: no coordinate variable for dimension %s of %s" % (path, dname, var))
+        cv = h.vars[dname]
+        raw = netcdf3.read_var_bytes(path, h, dname, dtype=cv.nc_type)
+        axes[dname] = _uniform_axis(path, dname, np.frombuffer(raw, dtype=netcdf3.NUMPY_DTYPE[cv.nc_type]))
+    data = np.frombuffer(netcdf3.read_var_bytes(path, h, var, dtype=v.nc_type), dtype=netcdf3.NUMPY_DTYPE[v.nc_type]).reshape(v.shape)
+    data = data.astype(data.dtype.newbyteorder("="))
+    if v.dims[0] == lon_name:   # stored (lon, lat): rows are latitudes here
+        data = np.ascontiguousarray(data.T)
+    (lat, dlat), (lon, dlon) = axes[lat_name], axes[lon_name]
+    if dlon < 0:
+        raise ValueError("%s: longitude %s decreases" % (path, lon_name))
+    if dlat < 0:
+        data, lat, dlat = data[::-1], lat[::-1], -dlat
+    fill = []
+    for k in ("_FillValue", "missing_value"):
+        if k in v.atts and not isinstance(v.atts[k], str):
+            fv = float(np.asarray(v.atts[k]).reshape(-1)[0])
+            if fv not in fill:
+                fill.append(fv)
+    if quantum is None and v.nc_type == netcdf3.NC_SHORT and "scale_factor" in v.atts:
+        quantum = float(np.asarray(v.atts["scale_factor"]).reshape(-1)[0])
+    lon0, kind_lon = _edges(lon[0], dlon)
+    lat0, kind_lat = _edges(lat[0], dlat)
+    note = "%s: %s %s x %s, longitude coordinates taken as cell %s, latitude as cell %s: box lon0 %.10g dlon %.10g lat0 %.10g dlat %.10g" % (
+        path, var, data.shape[0], data.shape[1], kind_lon, kind_lat, lon0, dlon, lat0, dlat)
+    return Source(data, lon0, dlon, lat0, dlat, fill=fill, quantum=quantum, note=note)
+
+
+def read_source_npy(path, box, quantum=None, fill=()):
+    """A Source from a .npy array (Ny x Nx, row 0 southmost) with its box (lon0, dlon, lat0, dlat) of cell edges."""
+    if box is None or len(box) != 4:
+        raise ValueError("%s: a .npy source needs --source_box LON0 DLON LAT0 DLAT (cell edges)" % path)
+    data = np.load(path)
+    return Source(data, *box, fill=fill, quantum=quantum, note="%s: %s %s, box %s (edges)" % (path, data.dtype, data.shape, tuple(box)))
+
+
+def read_source(path, var="elevation", box=None, quantum=None):
+    if str(path).endswith(".npy"):
+        return read_source_npy(path, box, quantum=quantum)
+    return read_source_nc(path, var, quantum=quantum)
+
+
+# ---- records -------------------------------------------------------------------------------------------------
+def empty_records(shape):
+    r = np.empty(shape, dtype=L.TOPOG_RECORD)
+    r[...] = _EMPTY
+    return r
+
+
+def merge_into(acc, rec):
+    """acc <- the exact combination of acc and rec (same shape): sums of counts, min, max, the larger R."""
+    for f in ("n", "n_missing", "n_wet", "sum", "sumsq", "n_pole", "n_clamped"):
+        acc[f] += rec[f]
+    acc["min"] = np.minimum(acc["min"], rec["min"])
+    acc["max"] = np.maximum(acc["max"], rec["max"])
+    acc["R"] = np.maximum(acc["R"], rec["R"])
+
+
+def assemble(pieces, ny_out, nx_out):
+    """The records of the whole grid from [(first output row, records (rows x nx_out))]: rows split between two bands combine exactly."""
+    out = empty_records((ny_out, nx_out))
+    for m0, rec in pieces:
+        merge_into(out[m0:m0 + rec.shape[0]], rec)
+    return out
+
+
+def exact_variance_numerator(n, s, ss):
+    """(double) of n * ss - s^2, formed exactly in 128-bit integers (n, ss >= 0 and |s| < 2^63; the result is >= 0) and rounded once."""
+    n, ss = np.asarray(n, dtype=np.uint64), np.asarray(ss, dtype=np.uint64)
+    s = np.abs(np.asarray(s, dtype=np.int64)).astype(np.uint64)
+    M = np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+
+    def mul(a, b):
+        a0, a1, b0, b1 = a & M, a >> s32, b & M, b >> s32
+        ll, m1, m2, hh = a0 * b0, a1 * b0, a0 * b1, a1 * b1
+        t = (ll >> s32) + (m1 & M) + (m2 & M)
+        return hh + (m1 >> s32) + (m2 >> s32) + (t >> s32), (ll & M) | ((t & M) << s32)
+
+    h1, l1 = mul(n, ss)
+    h2, l2 = mul(s, s)
+    lo = l1 - l2
+    hi = h1 - h2 - (l1 < l2).astype(np.uint64)
+    out = lo.astype(np.float64)
+    big = hi != 0
+    if np.any(big):   # rare (n * ss >= 2^64): Python integers round once
+        out[big] = [float((int(h) << 64) | int(lo_)) for h, lo_ in zip(hi[big], lo[big])]
+    return out
+
+
+def fields_from_records(rec, quantum):
+    """The outputs of include/ogg_hip.h from the integer records (floats: FILL where n = 0)."""
+    n = rec["n"]
+    ok = n > 0
+    nf = np.where(ok, n, 1).astype(np.float64)
+    q = float(quantum)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        height = rec["sum"].astype(np.float64) / nf * q
+        std = np.sqrt(exact_variance_numerator(n, rec["sum"], rec["sumsq"])) / nf * q
+        hmin = rec["min"].astype(np.float64) * q
+        hmax = rec["max"].astype(np.float64) * q
+        wet = rec["n_wet"].astype(np.float64) / nf
+    depth = np.maximum(0.0, -height)
+    out = {"height": height, "h_std": std, "h_min": hmin, "h_max": hmax, "wet_fraction": wet, "depth": depth}
+    for k in out:
+        out[k] = np.where(ok, out[k], FILL)
+    out["n_samples"] = n.astype(np.int32)
+    return out
+
+
+def summary_of(rec):
+    return {"n_cells": int(rec.size), "n_pole_cells": int(rec["n_pole"].sum()), "n_clamped_cells": int(rec["n_clamped"].sum()),
+            "n_cells_with_missing": int(np.count_nonzero(rec["n_missing"])), "R_max": int(rec["R"].max()) if rec.size else 0,
+            "n_samples": int(rec["n"].sum()) + int(rec["n_missing"].sum()), "n_valid_samples": int(rec["n"].sum()),
+            "n_empty_cells": int(np.count_nonzero(rec["n"] == 0))}
+
+
+def result(rec, quantum, sea_level, cells, refine, oversample, source=None):
+    """What topography() returns: the output fields, the integer records, and the summary."""
+    out = fields_from_records(rec, quantum)
+    out["records"] = rec
+    out["summary"] = dict(summary_of(rec), cells=cells, quantum=float(quantum), sea_level=float(sea_level),
+                          refine=None if refine is None else int(refine), oversample=float(oversample))
+    if source is not None:
+        out["summary"]["source"] = {"shape": list(source.shape), "dtype": str(source.data.dtype), "lon0": source.lon0,
+                                    "dlon": source.dlon, "lat0": source.lat0, "dlat": source.dlat, "periodic": bool(source.periodic)}
+    return out
+
+
+def check_args(nyp, nxp, cells, refine, oversample):
+    if cells not in ("model", "supergrid"):
+        raise ValueError("topography: cells must be 'model' or 'supergrid', not %r" % (cells,))
+    ny, nx = nyp - 1, nxp - 1
+    if ny < 1 or nx < 1:
+        raise ValueError("topography: a grid of %d x %d points has no cells" % (nyp, nxp))
+    if cells == "model" and (ny % 2 or nx % 2):
+        raise ValueError("topography: model cells are 2 x 2 supergrid cells, but the supergrid has %d x %d cells; generate it with "
+                         "--ensure_nj_even, or ask for supergrid cells (--supergrid_cells)" % (ny, nx))
+    if refine is not None and not 1 <= int(refine) <= L.TOPOG_MAX_REFINE:
+        raise ValueError("topography: refine must be 1 .. %d (%r)" % (L.TOPOG_MAX_REFINE, refine))
+    if refine is None and not (oversample > 0 and np.isfinite(oversample)):
+        raise ValueError("topography: oversample must be positive (%r)" % (oversample,))
+
+
+def as_source(source, lon0=None, dlon=None, lat0=None, dlat=None, quantum=None, fill=()):
+    if isinstance(source, Source):
+        if quantum is not None and float(quantum) != source.quantum:
+            source = Source(source.data, source.lon0, source.dlon, source.lat0, source.dlat, source.fill, quantum, source.note)
+        return source
+    if None in (lon0, dlon, lat0, dlat):
+        raise ValueError("topography: a raster array needs its box lon0, dlon, lat0, dlat")
+    return Source(source, lon0, dlon, lat0, dlat, fill=fill, quantum=quantum)
+
+
+# ---- host arrays -----------------------------------------------------------------------------------------------
+def topography(x, y, source, lon0=None, dlon=None, lat0=None, dlat=None, refine=None, oversample=2.0, quantum=None, sea_level=0.0,
+               cells="model", fill=()):
+    """Topography of a stitched supergrid x, y ((ny + 1) x (nx + 1), degrees) from a raster (a Source, or an int16 / float32 /
+    float64 array with its box of cell edges lon0 + is * dlon, lat0 + js * dlat), on one GPU.  ``quantum``: the value of one integer
+    step (float rasters: default 0.01); ``fill``: raw values that mark missing samples.  A dict of arrays (height, h_std, h_min, h_max,
+    wet_fraction, depth, n_samples, and the integer records) and "summary"."""
+    src = as_source(source, lon0, dlon, lat0, dlat, quantum, fill)
+    x, y = L.as_f64(x), L.as_f64(y)
+    if x.ndim != 2 or y.shape != x.shape:
+        raise ValueError("topography: x %s and y %s must be 2-D of one shape" % (x.shape, y.shape))
+    nyp, nxp = x.shape
+    check_args(nyp, nxp, cells, refine, oversample)
+    band = L.TopogBand(nx=nxp - 1, j0=0, n_cell_rows=nyp - 1, cells=L.TOPOG_MODEL_CELLS if cells == "model" else L.TOPOG_SUPERGRID_CELLS,
+                       refine=int(refine or 0), oversample=float(oversample))
+    band.x, band.y = L.ptr(x), L.ptr(y)
+    desc = src.descriptor(sea_level)
+    sh = 1 if cells == "model" else 0
+    rec = empty_records(((nyp - 1) >> sh, (nxp - 1) >> sh))
+    L.call("ogg_topog", ctypes.byref(band), ctypes.byref(desc), rec.ctypes.data)
+    return result(rec, src.quantum, sea_level, cells, refine, oversample, src)
+
+
+# ---- device arrays ---------------------------------------------------------------------------------------------
+def band_records_dev(band, desc, stream, device):
+    """ogg_topog_band_dev on a descriptor of device pointers: (first output row, records as an int64 device tensor rows x n x 7,
+    workspace), not synchronised."""
+    import torch
+    rows = int(L.load().ogg_topog_band_out_rows(ctypes.byref(band)))
+    nxo = band.nx >> (1 if band.cells == L.TOPOG_MODEL_CELLS else 0)
+    words = L.TOPOG_RECORD.itemsize // 8
+    out = torch.empty((rows, nxo, words), dtype=torch.int64, device=device)
+    ws_bytes = int(L.load().ogg_topog_workspace_bytes())
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    L.call("ogg_topog_band_dev", ctypes.byref(band), ctypes.byref(desc), ws.data_ptr(), ws_bytes, out.data_ptr(), stream)
+    return band.j0 >> (1 if band.cells == L.TOPOG_MODEL_CELLS else 0), out, ws
+
+
+def records_to_host(t):
+    return np.ascontiguousarray(t.cpu().numpy()).view(L.TOPOG_RECORD).reshape(t.shape[0], t.shape[1])
+
+
+# ---- files -----------------------------------------------------------------------------------------------------
+_VARS = (("height", "m", "mean height of the source over the cell (positive up)"),
+         ("depth", "m", "depth of the sea floor, max(0, -height) (positive down)"),
+         ("h_std", "m", "standard deviation of the source height over the cell"),
+         ("h_min", "m", "smallest source height in the cell"),
+         ("h_max", "m", "largest source height in the cell"),
+         ("wet_fraction", "1", "fraction of the cell's samples below sea level"))
+
+
+def write_topog(path, res, units="m"):
+    """topog.nc (NetCDF 64-bit offset): dims (ny, nx), the floating outputs as doubles with _FillValue, n_samples as int."""
+    h = res["height"]
+    ny, nx = h.shape
+    s = res["summary"]
+    ds = netcdf3.Dataset(path, [("ny", ny), ("nx", nx)], global_atts=[
+        ("title", "topography by refined sampling of a source raster"),
+        ("cells", "MOM6 model (h) cells: 2 x 2 supergrid cells" if s["cells"] == "model" else "supergrid cells"),
+        ("quantum", float(s["quantum"])), ("sea_level", float(s["sea_level"])), ("oversample", float(s["oversample"])),
+        ("refine", int(s["refine"] or 0))])
+    for name, u, long_name in _VARS:
+        ds.def_var(name, netcdf3.NC_DOUBLE, ("ny", "nx"), [("units", units if u == "m" else u), ("long_name", long_name),
+                                                            ("_FillValue", FILL)], res[name])
+    ds.def_var("n_samples", netcdf3.NC_INT, ("ny", "nx"), [("units", "1"), ("long_name", "number of valid samples in the cell")],
+               res["n_samples"])
+    ds.write()
+
+
+def summary_lines(res):
+    s = res["summary"]
+    h = res["height"]
+    ok = res["n_samples"] > 0
+    lines = ["   topography: %d %s cells, %d samples (%d valid), R up to %d; %d pole-enclosing, %d clamped, %d with missing samples"
+             % (s["n_cells"], s["cells"], s["n_samples"], s["n_valid_samples"], s["R_max"], s["n_pole_cells"], s["n_clamped_cells"],
+                s["n_cells_with_missing"])]
+    if np.any(ok):
+        wet = res["wet_fraction"][ok]
+        lines.append("   topography: height %.6g .. %.6g, %d cells all wet, %d all dry, %d partly wet"
+                     % (float(h[ok].min()), float(h[ok].max()), int(np.sum(wet == 1.0)), int(np.sum(wet == 0.0)),
+                        int(np.sum((wet > 0) & (wet < 1)))))
+    return lines
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(prog="python -m ocean_model_grid_generator_amd.topography",
+                                description="topography of a supergrid file by refined sampling of a source raster")
+    p.add_argument("grid", help="ocean_hgrid.nc (NetCDF classic / 64-bit offset)")
+    p.add_argument("source", help="source raster: NetCDF classic / 64-bit offset, or .npy with --source_box")
+    p.add_argument("-o", "--output", default="topog.nc")
+    p.add_argument("--var", default="elevation", help="source variable (default %(default)s)")
+    p.add_argument("--source_box", type=float, nargs=4, default=None, metavar=("LON0", "DLON", "LAT0", "DLAT"),
+                   help="cell edges of a .npy source: lon0 + is * dlon, lat0 + js * dlat")
+    p.add_argument("--refine", type=int, default=None, help="R x R samples in every supergrid cell (default: from the cell's spans)")
+    p.add_argument("--oversample", type=float, default=2.0)
+    p.add_argument("--quantum", type=float, default=None, help="value of one integer step of a float source (default 0.01)")
+    p.add_argument("--sea_level", type=float, default=0.0)
+    p.add_argument("--supergrid_cells", action="store_true", help="one output cell per supergrid cell instead of per model cell")
+    p.add_argument("--json", default=None, help="write the summary as JSON to this file")
+    a = p.parse_args(argv)
+    src = read_source(a.source, a.var, a.source_box, a.quantum)
+    print(src.note)
+    g = netcdf3.read_doubles(a.grid, names=("x", "y"))
+    res = topography(g["x"], g["y"], src, refine=a.refine, oversample=a.oversample, sea_level=a.sea_level,
+                     cells="supergrid" if a.supergrid_cells else "model")
+    for line in summary_lines(res):
+        print(line)
+    write_topog(a.output, res)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(res["summary"], fh, indent=1)
+    return res
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)
