@@ -566,6 +566,82 @@ int ogg_topog_quantize_dev(const ogg_topog_source* src, int* q, int* n_bad, void
  * host memory.  A float source is quantised on the device first (OGG_EARG when |q| > OGG_TOPOG_MAX_Q). */
 int ogg_topog(const ogg_topog_band* band, const ogg_topog_source* src, ogg_topog_record* out);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Atmosphere x ocean exchange grid (an addition: the reference has none).  First-order conservative overlaps of a rectilinear global
+ * atmosphere with the MOM6 h-cells of the STITCHED supergrid x, y ((ny + 1) x (nx + 1), degrees; nx and ny even), as FMS's
+ * make_coupler_mosaic lists them.  All arithmetic is fp64 without fused multiply-add.
+ * Atmosphere: lon edges a_0 < .. < a_NA with |a_NA - a_0 - 360| <= 1e-9 (global, periodic), lat edges b_0 < .. < b_NB inside
+ * [-90, 90]; cell (J, I) = [a_I, a_I+1] x [b_J, b_J+1].  ogg_xgrid and ogg_xgrid_check_atm refuse any other edges with OGG_EARG
+ * before any device work (the _dev steps take the edges in device memory and do not read them on the host).
+ * Ocean cell (m, n): corners C0 = (x, y)[2m][2n], C1 = [2m][2n+2], C2 = [2m+2][2n+2], C3 = [2m+2][2n] (counter-clockwise).
+ *   unwrap    L_k = x_C0 + (((x_k - x_C0 + 180) mod 360) - 180), mod with numpy's % semantics (as for topography)
+ *   pole      a corner with |y| >= 90 - OGG_TOPOG_POLE_EPS is a pole corner; 3 or 4 of them: the cell is DEGENERATE.  The polygon
+ *             walks k = 0 .. 3: a non-pole corner gives (L_k, y_k); a pole corner whose cyclic predecessor is not a pole corner
+ *             starts a run and gives (L_b, p), (L_a, p), L_b / L_a the longitudes of the non-pole corners just before / after
+ *             the run, p = +90 when the corner's y > 0, else -90; a pole corner inside a run gives nothing
+ *   encloses  w = sum over the polygon's edges of wrap(lambda_k+1 - lambda_k), wrap(d) = ((d + 180) mod 360) - 180, left to right;
+ *             |w| > 180: the cell encloses a pole
+ *   area      lam^ = lam * D, phi^ = phi * D, D = pi / 180 (one fp64 constant); phi_r = phi^_0;
+ *             A = -(Re * Re) * S, S = sum_k (lam^_k+1 - lam^_k) * G(phi^_k, phi^_k+1) left to right (vertex V is vertex 0),
+ *             G = 2 cos((pm + phi_r) / 2) sin((pm - phi_r) / 2) - sin(pm) E(h), pm = (p1 + p2) / 2, h = (p2 - p1) / 2,
+ *             E(h) = h2 (1/6 - h2 (1/120 - h2 (1/5040 - h2 / 362880))), h2 = h * h, for |h| < 0.1, else 1 - sin(h) / h
+ *             (the exact mean of sin(phi) - sin(phi_r) along an edge straight in (lambda, phi)); a cell with A_poly <= 0 is
+ *             INVERTED.  Degenerate, pole-enclosing and inverted cells emit nothing; A_poly is NaN for the first two.
+ *   rows      every J with b_J < phi_max and b_J+1 > phi_min (the polygon's latitude range)
+ *   columns   every I and shift s in 360 Z with a_I + s < lam_max and a_I+1 + s > lam_min (fp64 sums), in order of a_I + s
+ *   clip      Sutherland-Hodgman against lam >= a_I + s, lam <= a_I+1 + s, phi >= b_J, phi <= b_J+1, in this order, inclusive
+ *             inside tests; a pass over v_0 .. v_n-1 emits v_0 when it is inside, then for k = 0 .. n-1 the crossing of the edge
+ *             (v_k, v_k+1 mod n) when its ends are on two sides and, for k < n - 1, v_k+1 when it is inside.  A crossing of lam = c
+ *             orders the edge's ends (e, f) by (lam, phi) and
+ *             is (c, phi_e + (c - lam_e) * ((phi_f - phi_e) / (lam_f - lam_e))); of phi = c the same with the roles swapped
+ *   keep      A_x (the area of the clipped polygon) > 0 and A_x > threshold * min(A_poly, A_atm), A_atm = (Re * Re) *
+ *             (a_I+1 * D - a_I * D) * ds_J, ds_J = sin b^_J+1 - sin b^_J formed as 2 cos((b^_J + b^_J+1) / 2) sin((b^_J+1 - b^_J) / 2);
+ *             an optional uint8 mask (0: the cell emits nothing)
+ * Order: ocean cells row-major (m, n), then J ascending, then a_I + s ascending.  Nothing is summed across cells, so the list is
+ * bit-identical for any band split.  The integer counts are over the band's cells; the first four ignore the mask.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { OGG_XGRID_BAND = 0, OGG_XGRID_ATM = 1, OGG_XGRID_COUNTS = 2 };
+typedef struct ogg_xgrid_atm {
+    const double *lon, *lat;   /* NA + 1 and NB + 1 edges */
+    long NA, NB;
+} ogg_xgrid_atm;
+/* a band: stitched supergrid cell rows j0 .. j0 + n_cell_rows - 1 of a grid of ny cell rows.  Its model rows are the m with
+ * j0 <= 2 m < j0 + n_cell_rows (a model row belongs to the band that holds its cell row 2 m): m0 = (j0 + 1) / 2 ..
+ * m1 = (j0 + n_cell_rows + 1) / 2 (exclusive).  x, y hold the band's n_cell_rows point rows (stride nx + 1); x_next, y_next the
+ * ogg_xgrid_band_next_rows() point rows that follow them in stitched order (rows j0 + n_cell_rows .., contiguous, stride nx + 1).
+ * mask: NULL, or one byte per model cell of rows m0 .. m1 - 1 (row-major, nx / 2 per row). */
+typedef struct ogg_xgrid_band {
+    long nx, ny, j0, n_cell_rows;
+    const double *x, *y, *x_next, *y_next;
+    const unsigned char* mask;
+    double Re, threshold;
+} ogg_xgrid_band;
+/* per call; every count over the band's model cells */
+typedef struct ogg_xgrid_counts {
+    long long cells, pole_cells, pole_enclosing, inverted, degenerate, masked, candidates, kept;
+} ogg_xgrid_counts;
+long ogg_xgrid_struct_bytes(int which);                    /* sizeof of OGG_XGRID_BAND / ATM / COUNTS, -1 otherwise */
+long ogg_xgrid_band_first_row(const ogg_xgrid_band* band); /* m0, -1 on a bad band */
+long ogg_xgrid_band_out_rows(const ogg_xgrid_band* band);  /* m1 - m0 (0 for a band without a model row), -1 on a bad band */
+long ogg_xgrid_band_next_rows(const ogg_xgrid_band* band); /* point rows needed after the band: 0, 1 or 2; -1 on a bad band */
+long ogg_xgrid_workspace_bytes(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm); /* of the count and write steps, -1 if bad */
+/* the checks of the edges (HOST pointers in *atm): OGG_EARG unless they are as above */
+int ogg_xgrid_check_atm(const ogg_xgrid_atm* atm);
+/* count step, device pointers, on a stream: A_poly of the band's cells into a_poly ((m1 - m0) x nx / 2 doubles), the counts into
+ * *counts (device memory), and into the workspace what the write step needs.  counts->kept is the length of the band's list. */
+int ogg_xgrid_count_dev(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, void* workspace, long workspace_bytes, double* a_poly,
+                        ogg_xgrid_counts* counts, void* stream);
+/* write step, after the count step on the same band, atmosphere and workspace: the list (counts->kept entries, device memory):
+ * atm_ij[k] = (I, J), ocn_ij[k] = (n, m) (0-based, m counted in the whole grid), area[k] = A_x.  The step redoes the clipping and
+ * uses the workspace's per-wavefront offsets. */
+int ogg_xgrid_write_dev(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, const void* workspace, long workspace_bytes, int* atm_ij,
+                        int* ocn_ij, double* area, void* stream);
+/* HOST pointers throughout (x, y hold n_cell_rows + next_rows point rows when x_next is NULL), staged through device memory: both
+ * steps, then the list is copied into atm_ij / ocn_ij / area when counts->kept <= capacity (OGG_ESHAPE otherwise, with *counts and
+ * a_poly filled: call again with that capacity). */
+int ogg_xgrid(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, long capacity, int* atm_ij, int* ocn_ij, double* area,
+              double* a_poly, ogg_xgrid_counts* counts);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

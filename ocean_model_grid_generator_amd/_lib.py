@@ -91,6 +91,28 @@ TOPOG_RECORD = np.dtype([("n", "<i8"), ("n_missing", "<i8"), ("n_wet", "<i8"), (
                          ("max", "<i4"), ("R", "<i4"), ("n_pole", "<i2"), ("n_clamped", "<i2")])
 
 
+class XgridAtm(ctypes.Structure):
+    """ogg_xgrid_atm of include/ogg_hip.h"""
+    _fields_ = [("lon", c_void_p), ("lat", c_void_p), ("NA", c_long), ("NB", c_long)]
+
+
+class XgridBand(ctypes.Structure):
+    """ogg_xgrid_band of include/ogg_hip.h"""
+    _fields_ = [("nx", c_long), ("ny", c_long), ("j0", c_long), ("n_cell_rows", c_long), ("x", c_void_p), ("y", c_void_p),
+                ("x_next", c_void_p), ("y_next", c_void_p), ("mask", c_void_p), ("Re", c_double), ("threshold", c_double)]
+
+
+XGRID_COUNT_FIELDS = ("cells", "pole_cells", "pole_enclosing", "inverted", "degenerate", "masked", "candidates", "kept")
+
+
+class XgridCounts(ctypes.Structure):
+    """ogg_xgrid_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in XGRID_COUNT_FIELDS]
+
+
+XGRID_BAND, XGRID_ATM, XGRID_COUNTS = 0, 1, 2                          # OGG_XGRID_BAND ... of include/ogg_hip.h
+
+
 # name -> argtypes; every function returns int except the two string getters.  Must list EVERY symbol of ogg_hip.h
 # (tests/test_abi.py checks this list against the header).
 SIGNATURES = {
@@ -202,6 +224,12 @@ SIGNATURES = {
     "ogg_topog_band_dev": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p, c_long, c_void_p, c_void_p],
     "ogg_topog_quantize_dev": [ctypes.POINTER(TopogSource), c_void_p, c_void_p, c_void_p],
     "ogg_topog": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p],
+    "ogg_xgrid_check_atm": [ctypes.POINTER(XgridAtm)],
+    "ogg_xgrid_count_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_void_p, c_long, c_void_p, c_void_p, c_void_p],
+    "ogg_xgrid_write_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_void_p, c_long, c_void_p, c_void_p, c_void_p,
+                            c_void_p],
+    "ogg_xgrid": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_long, c_void_p, c_void_p, c_void_p, c_void_p,
+                  ctypes.POINTER(XgridCounts)],
     "ogg_event_create": [ctypes.POINTER(c_void_p)],
     "ogg_event_destroy": [c_void_p],
     "ogg_event_record": [c_void_p, c_void_p],
@@ -221,7 +249,12 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_grid_quality_workspace_bytes": [c_long, c_long],
                 "ogg_topog_record_bytes": [],
                 "ogg_topog_band_out_rows": [ctypes.POINTER(TopogBand)],
-                "ogg_topog_workspace_bytes": []}
+                "ogg_topog_workspace_bytes": [],
+                "ogg_xgrid_struct_bytes": [c_int],
+                "ogg_xgrid_band_first_row": [ctypes.POINTER(XgridBand)],
+                "ogg_xgrid_band_out_rows": [ctypes.POINTER(XgridBand)],
+                "ogg_xgrid_band_next_rows": [ctypes.POINTER(XgridBand)],
+                "ogg_xgrid_workspace_bytes": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm)]}
 
 _lib = None
 

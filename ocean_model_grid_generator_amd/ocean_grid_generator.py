@@ -642,7 +642,7 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          ensure_nj_even=False, shift_equator_to_u_point=True, bipolar_lower_lat=-99.0, mercator_lower_lat=-99.0,
          mercator_upper_lat=-99.0, south_ocean_lower_lat=-99.0, south_ocean_upper_lat=-99.0, no_south_cap=False,
          return_arrays=False, path=None, dp_arc=None, cap_symmetry=None, quality_report=None, topog_source=None, topog_var="elevation",
-         topog_file="topog.nc", topog_refine=None):
+         topog_file="topog.nc", topog_refine=None, xgrid_atm=None, xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc"):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -659,7 +659,9 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     write the grid-quality report of the stitched grid (grid_quality.py) to that file as JSON and print a summary of it after the
     CHECK_metrics lines; an addition the reference does not have.  ``topog_source`` (--topog_source FILE, or a topography.Source):
     sample that raster (variable ``topog_var``) on the model cells of the stitched grid straight from HBM and write ``topog_file``
-    (topography.py; ``topog_refine``: R x R samples per supergrid cell instead of R from the cell's size); also an addition."""
+    (topography.py; ``topog_refine``: R x R samples per supergrid cell instead of R from the cell's size); also an addition.
+    ``xgrid_atm`` (--xgrid_atm NLON NLAT): write the exchange grid of the model cells with a regular global NLON x NLAT atmosphere to
+    ``xgrid_file`` (exchange_grid.py; only cells with depth > 0 when ``topog_source`` is given too); also an addition."""
     import time
 
     path = path or os.environ.get("OGG_MAIN_PATH", "pass")
@@ -669,7 +671,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
                                    reproduce_MIDAS_grids, write_subgrid_files, plotem, no_changing_meta, enhanced_equatorial, debug, grids,
                                    match_dy, skip_metrics, ensure_nj_even, shift_equator_to_u_point, bipolar_lower_lat, mercator_lower_lat,
                                    mercator_upper_lat, south_ocean_lower_lat, south_ocean_upper_lat, no_south_cap, return_arrays, dp_arc,
-                                   cap_symmetry, quality_report, topog_source, topog_var, topog_file, topog_refine)
+                                   cap_symmetry, quality_report, topog_source, topog_var, topog_file, topog_refine, xgrid_atm,
+                                   xgrid_file)
     from . import supergrid as SG
 
     _validate_flags(match_dy, r_dp, lat_dp)
@@ -699,10 +702,14 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     cut = g.south_cut()
     if quality_report:
         _write_quality_report(g.quality(cut), quality_report)
+    topo = None
     if topog_source is not None:
         from . import topography as T
         src = _topog_source(topog_source, topog_var)
-        _write_topog(g.topography(cut, T.DeviceSource(src, g.device), refine=topog_refine), topog_file)
+        topo = _write_topog(g.topography(cut, T.DeviceSource(src, g.device), refine=topog_refine), topog_file)
+    if xgrid_atm is not None:
+        from . import exchange_grid as X
+        _write_xgrid(g.exchange_grid(cut, X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo)), xgrid_file)
     print("Stitching the grids together...")
     SG.check_guards(g.stitched_column("y", plan.Ni // 4, cut), any(s.name == "BP" for s in plan.subs))
     names = [s.name for s in plan.subs if not (s.name == "SC" and cut[2])]
@@ -769,7 +776,8 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
                         ensure_nj_even=False, shift_equator_to_u_point=True, bipolar_lower_lat=-99.0, mercator_lower_lat=-99.0,
                         mercator_upper_lat=-99.0, south_ocean_lower_lat=-99.0, south_ocean_upper_lat=-99.0, no_south_cap=False,
                         return_arrays=False, dp_arc=None, cap_symmetry=None, quality_report=None, topog_source=None,
-                        topog_var="elevation", topog_file="topog.nc", topog_refine=None):
+                        topog_var="elevation", topog_file="topog.nc", topog_refine=None, xgrid_atm=None,
+                        xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc"):
     """The reference's own sequence of calls (OGG:855-1449), every callee a host-array function of this module (numpy in, numpy
     out, one staged device call each) and the stitching on the host: what a user gets who swaps the reference's module for this
     one function by function.  main() produces the same bits from one device-resident pass."""
@@ -991,9 +999,13 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
         metric_fields = (dx3, dy3, area3) if calculate_metrics else (None, None, None)
         _write_quality_report(grid_quality(x3, y3, *metric_fields, Re=_default_Re, sections=list(zip(names, starts)), seams=seams),
                               quality_report)
+    topo = None
     if topog_source is not None:   # the same topography as the device pass gives, from the stitched host arrays
         from . import topography as T
-        _write_topog(T.topography(x3, y3, _topog_source(topog_source, topog_var), refine=topog_refine), topog_file)
+        topo = _write_topog(T.topography(x3, y3, _topog_source(topog_source, topog_var), refine=topog_refine), topog_file)
+    if xgrid_atm is not None:   # the same list as the device pass gives, through the host-pointer entry
+        from . import exchange_grid as X
+        _write_xgrid(X.exchange_grid(x3, y3, *X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo), Re=_default_Re), xgrid_file)
 
     if write_subgrid_files:
         if "SC" in sub:
@@ -1069,6 +1081,22 @@ def _write_topog(res, fnam):
     for line in T.summary_lines(res):
         print(line)
     T.write_topog(str(fnam), res)
+    return res
+
+
+def _xgrid_mask(topo):
+    """depth > 0 of the topography just computed (cells without a valid sample are dry), or None without one"""
+    if topo is None:
+        return None
+    from . import exchange_grid as X
+    return X.wet_mask(topo["depth"])
+
+
+def _write_xgrid(res, fnam):
+    from . import exchange_grid as X
+    for line in X.summary_lines(res):
+        print(line)
+    X.write_xgrid(str(fnam), res)
 
 
 def build_parser():
@@ -1122,6 +1150,11 @@ def build_parser():
     parser.add_argument("--topog_file", type=str, required=False, default="topog.nc", help="topography output file, default topog.nc")
     parser.add_argument("--topog_refine", type=int, required=False, default=None,
                         help="R x R samples in every supergrid cell (default: from each cell's size, twice the raster's resolution)")
+    parser.add_argument("--xgrid_atm", type=int, nargs=2, required=False, default=None, metavar=("NLON", "NLAT"),
+                        help="write the atmosphere x ocean exchange grid of a regular global NLON x NLAT atmosphere into --xgrid_file "
+                             "(wet cells only when --topog_source is given)")
+    parser.add_argument("--xgrid_file", type=str, required=False, default="atmos_mosaic_tile1Xocean_mosaic_tile1.nc",
+                        help="exchange-grid output file, default atmos_mosaic_tile1Xocean_mosaic_tile1.nc")
     return parser
 
 

@@ -1327,6 +1327,146 @@ class Supergrid(object):
         recs = T.assemble([(m0, T.records_to_host(t)) for m0, t in got], (nyp - 1) >> sh, (nxp - 1) >> sh)
         return T.result(recs, source.source.quantum, source.sea_level, cells, refine, oversample, source.source)
 
+    # -- atmosphere x ocean exchange grid --------------------------------------------------------------------------
+    @staticmethod
+    def _xgrid_rows(q):
+        """(first model row, model rows, point rows needed after the piece) of a piece: its model rows are the m with 2 m in its cell
+        rows (include/ogg_hip.h, ogg_xgrid_band)."""
+        m0, m1 = (q["j0"] + 1) // 2, (q["j0"] + q["n_cell"] + 1) // 2
+        rows = max(m1 - m0, 0)
+        return m0, rows, (2 * m1 - (q["j0"] + q["n_cell"]) + 1) if rows else 0
+
+    def xgrid_halo(self, cut):
+        """{piece index: (x rows, y rows)} of THIS rank's pieces: the (one or two) stitched point rows that follow each piece, as
+        contiguous (rows, nx + 1) tensors.  Rows of this rank come from its buffers, rows of another rank from its Supergrid
+        (halo="local") or over torch.distributed, as in quality_halo."""
+        torch = self.torch
+        pieces = self.quality_pieces(cut)
+        wanted = []   # (dst piece, t, field, src rank, src sub-grid name, src band row), the same order on every rank
+        for k, p in enumerate(pieces):
+            _, _, nr = self._xgrid_rows(p)
+            for t in range(nr):
+                R = p["j0"] + p["n_cell"] + t
+                src = next(q for q in pieces if q["j0"] <= R < q["j0"] + q["n_pt"])
+                for f in ("x", "y"):
+                    wanted.append((k, t, f, src["rank"], src["sub"].name, src["row"] + R - src["j0"]))
+        got, ops = {}, []
+        for k, t, f, src, name, row in wanted:
+            dst = pieces[k]["rank"]
+            if dst == self.rank:
+                if src == self.rank:
+                    r = self.buf[name][f][row]
+                elif self.halo == "local":
+                    r = self.peers[src].buf[name][f][row].clone()
+                else:
+                    r = torch.empty(self.plan.Ni + 1, dtype=torch.float64, device=self.device)
+                    ops.append(("recv", r, src))
+                got.setdefault(k, {}).setdefault(f, []).append(r)
+            elif src == self.rank and self.halo != "local":
+                ops.append(("send", self.buf[name][f][row].contiguous(), dst))
+        if ops:
+            import torch.distributed as dist
+            if all(r.is_cuda for _, r, _ in ops) and dist.get_backend() != "gloo":
+                p2p = [dist.P2POp(dist.isend if d == "send" else dist.irecv, r, s) for d, r, s in ops]
+                for w in dist.batch_isend_irecv(p2p):
+                    w.wait()
+            else:   # gloo: through host copies, in the common order
+                for d, r, s in ops:
+                    if d == "send":
+                        dist.send(r.cpu(), s)
+                    else:
+                        c = torch.empty(r.shape, dtype=r.dtype)
+                        dist.recv(c, s)
+                        r.copy_(c)
+        return {k: (torch.stack(v["x"]).contiguous(), torch.stack(v["y"]).contiguous()) for k, v in got.items()}
+
+    def xgrid_lists(self, cut, atm, mask=None, threshold=1e-6, halo=None):
+        """[(piece index, first model row, counts, a_poly, atm, ocn, area)] of THIS rank's pieces (device tensors), the exchange grid
+        of each piece computed on the buffers the pass left in HBM.  ``atm``: (lon, lat) edges as float64 device tensors; ``mask``:
+        None or a uint8 device tensor of every model cell of the stitched grid."""
+        from . import exchange_grid as X
+        p, st = self.plan, self._stream()
+        halo = self.xgrid_halo(cut) if halo is None else halo   # (held until the kernels have run: the bands point into it)
+        lon, lat = atm
+        desc = L.XgridAtm(lon=lon.data_ptr(), lat=lat.data_ptr(), NA=lon.numel() - 1, NB=lat.numel() - 1)
+        ny = self.stitched_rows(cut) - 1
+        out = []
+        for k, q in enumerate(self.quality_pieces(cut)):
+            m0, rows, _ = self._xgrid_rows(q)
+            if q["rank"] != self.rank or rows == 0:
+                continue
+            b, r = self.buf[q["sub"].name], q["row"]
+            band = L.XgridBand(nx=p.Ni, ny=ny, j0=q["j0"], n_cell_rows=q["n_cell"], Re=float(p.Re), threshold=float(threshold))
+            band.x, band.y = self._p(b["x"], r), self._p(b["y"], r)
+            band.x_next, band.y_next = halo[k][0].data_ptr(), halo[k][1].data_ptr()
+            band.mask = None if mask is None else mask.data_ptr() + m0 * (p.Ni // 2)
+            out.append((k,) + X.band_lists_dev(band, desc, st, self.device))
+        self.torch.cuda.synchronize(self.device)
+        return out
+
+    def exchange_grid(self, cut, atm, mask=None, threshold=1e-6):
+        """The atmosphere x ocean exchange grid of the stitched grid of every rank (exchange_grid.result on rank 0, None on the other
+        ranks).  ``atm``: (lon_edges, lat_edges) of a global rectilinear atmosphere; ``mask``: None or one value per model cell (0:
+        the cell emits nothing).  Every piece is done by the rank that holds it; rank 0 gathers the lists in piece order (from peer
+        objects with halo="local", by send / recv over torch.distributed otherwise), which is the canonical order, so the result is
+        bit-identical for any number of ranks."""
+        from . import exchange_grid as X
+        torch = self.torch
+        nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
+        X.check_grid(nyp, nxp)
+        X.check_args(threshold, self.plan.Re)
+        lon, lat = X.atm_edges(*atm)
+        shape = ((nyp - 1) // 2, (nxp - 1) // 2)
+        dmask = None
+        if mask is not None:
+            hm = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if hm.shape != shape:
+                raise ValueError("exchange grid: the mask is %s, the model cells %s" % (hm.shape, shape))
+            dmask = torch.from_numpy(hm).to(self.device)
+        pieces = self.quality_pieces(cut)
+        if self.world > 1 and self.halo == "local" and self.rank != 0:
+            return None   # rank 0 does the pieces of every virtual rank through its peer objects
+        dev_atm = (torch.from_numpy(lon).to(self.device), torch.from_numpy(lat).to(self.device))
+        mine = self.xgrid_lists(cut, dev_atm, dmask, threshold)
+        got = list(mine)
+        if self.world > 1 and self.halo == "local":
+            for g in self.peers:
+                if g is not self:
+                    got += g.xgrid_lists(cut, (dev_atm[0].to(g.device), dev_atm[1].to(g.device)),
+                                         None if dmask is None else dmask.to(g.device), threshold)
+        elif self.world > 1:
+            import torch.distributed as dist
+            gloo = dist.get_backend() == "gloo"
+            host = (lambda t: t.cpu()) if gloo else (lambda t: t.contiguous())   # noqa: E731
+            if self.rank != 0:
+                for _, _, counts, a_poly, atm_ij, ocn_ij, area in mine:   # in piece order: counts first, then the arrays
+                    dist.send(host(counts), 0)
+                    if atm_ij.shape[0]:
+                        for t in (atm_ij, ocn_ij, area):
+                            dist.send(host(t), 0)
+                    dist.send(host(a_poly), 0)
+                return None
+            where = "cpu" if gloo else self.device
+            for k, q in enumerate(pieces):
+                m0, rows, _ = self._xgrid_rows(q)
+                if q["rank"] == 0 or rows == 0:
+                    continue
+                counts = torch.empty(len(L.XGRID_COUNT_FIELDS), dtype=torch.int64, device=where)
+                dist.recv(counts, q["rank"])
+                n = int(counts[L.XGRID_COUNT_FIELDS.index("kept")])
+                atm_ij = torch.empty((n, 2), dtype=torch.int32, device=where)
+                ocn_ij = torch.empty((n, 2), dtype=torch.int32, device=where)
+                area = torch.empty(n, dtype=torch.float64, device=where)
+                if n:
+                    for t in (atm_ij, ocn_ij, area):
+                        dist.recv(t, q["rank"])
+                a_poly = torch.empty((rows, shape[1]), dtype=torch.float64, device=where)
+                dist.recv(a_poly, q["rank"])
+                got.append((k, m0, counts, a_poly, atm_ij, ocn_ij, area))
+        got.sort(key=lambda e: e[0])   # piece order: the canonical order of the list
+        hostp = [(m0,) + tuple(t.cpu().numpy() for t in ts) for _, m0, *ts in got]
+        return X.assemble(hostp, shape, lon, lat, float(self.plan.Re), threshold, mask is not None)
+
     def bands_to_host(self):
         """This rank's bands as numpy arrays (halo rows dropped): {sub: {field: array}}."""
         out = {}
