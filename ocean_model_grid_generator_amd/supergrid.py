@@ -1135,6 +1135,81 @@ class Supergrid(object):
         barrier()   # every rank's bytes are in the file
         return stream.bytes, time.perf_counter() - t0
 
+    def _fetch_rows(self, pieces, wanted):
+        """{(dst piece, key, field): 1-D row} of the entries of ``wanted`` whose destination piece is on THIS rank.  ``wanted``: (dst
+        piece, key, field, src rank, src sub-grid name, src band row), built in the same order on every rank.  Rows of this rank are
+        views of its buffers; rows of another rank come device-to-device from its Supergrid (halo="local") or over torch.distributed
+        (batch_isend_irecv), as in exchange_halo.  A received row is nx wide for dx, nx + 1 for every other field."""
+        torch = self.torch
+        out, ops = {}, []
+        for k, key, f, src, name, row in wanted:
+            if pieces[k]["rank"] == self.rank:
+                if src == self.rank:
+                    t = self.buf[name][f][row]
+                elif self.halo == "local":
+                    t = self.peers[src].buf[name][f][row].clone()
+                else:
+                    t = torch.empty(self.plan.Ni + (0 if f == "dx" else 1), dtype=torch.float64, device=self.device)
+                    ops.append(("recv", t, src))
+                out[k, key, f] = t
+            elif src == self.rank and self.halo != "local":
+                ops.append(("send", self.buf[name][f][row].contiguous(), pieces[k]["rank"]))
+        if ops:
+            import torch.distributed as dist
+            if all(t.is_cuda for _, t, _ in ops) and dist.get_backend() != "gloo":
+                p2p = [dist.P2POp(dist.isend if d == "send" else dist.irecv, t, r) for d, t, r in ops]
+                for w in dist.batch_isend_irecv(p2p):
+                    w.wait()
+            else:   # gloo (the CPU tests, the one-GPU rehearsal): through host copies, in the common order
+                for d, t, r in ops:
+                    if d == "send":
+                        dist.send(t.cpu(), r)
+                    else:
+                        c = torch.empty(t.shape, dtype=t.dtype)
+                        dist.recv(c, r)
+                        t.copy_(c)
+        return out
+
+    def _bands(self, cut, make, skip=lambda q: False):
+        """(piece index, piece, its buffers, band) of THIS rank's pieces but those ``skip`` names: band = make(q) with x and y set at the
+        piece's first row."""
+        for k, q in enumerate(self.quality_pieces(cut)):
+            if q["rank"] == self.rank and not skip(q):
+                b = self.buf[q["sub"].name]
+                band = make(q)
+                band.x, band.y = self._p(b["x"], q["row"]), self._p(b["y"], q["row"])
+                yield k, q, b, band
+
+    def _gather(self, pieces, records, send, recv):
+        """Every rank's per-piece results on rank 0, None on the other ranks.  ``records(g)``: the list of Supergrid g's pieces; rank 0
+        holds its own, then the peers' (halo="local") or what the other ranks send over torch.distributed: each sends the tensors of
+        ``send(entry)`` for its entries in piece order, and rank 0 walks ``pieces`` calling ``recv(k, piece, take)``, which returns the
+        piece's entry (None for a piece that sends nothing), ``take(shape, dtype)`` receiving the next tensor from the piece's rank
+        (on the CPU under gloo, on the device otherwise)."""
+        if self.world > 1 and self.halo == "local" and self.rank != 0:
+            return None   # rank 0 does the pieces of every virtual rank through its peer objects
+        got = records(self)
+        if self.world > 1 and self.halo == "local":
+            for g in self.peers:
+                if g is not self:
+                    got += records(g)
+        elif self.world > 1:
+            import torch.distributed as dist
+            gloo = dist.get_backend() == "gloo"
+            if self.rank != 0:
+                for e in got:
+                    for t in send(e):
+                        dist.send(t.cpu() if gloo else t.contiguous(), 0)
+                return None
+            for k, q in enumerate(pieces):   # in piece order, as every other rank sends its own
+                def take(shape, dtype, src=q["rank"]):
+                    t = self.torch.empty(shape, dtype=dtype, device="cpu" if gloo else self.device)
+                    dist.recv(t, src)
+                    return t
+                e = recv(k, q, take) if q["rank"] != 0 else None
+                got += [e] if e is not None else []
+        return got
+
     # -- grid-quality report ------------------------------------------------------------------------------------
     def quality_pieces(self, cut):
         """Every rank's pieces of the stitched grid, south -> north, for the quality report: dicts with the rank, the sub-grid, the
@@ -1156,14 +1231,12 @@ class Supergrid(object):
         return out
 
     def quality_halo(self, cut):
-        """The rows the pieces of THIS rank need from elsewhere, as {piece index: {"next": {x, y, dx, dy}, "seam": {x, y}}} of 1-D
-        tensors: the first point row (x, y, dx) and cell row (dy) of the piece that follows in stitched order, and at a sub-grid joint the
-        lower sub-grid's own last point row (x, y), which stitching drops.  Rows of this rank are views of its buffers; rows of another
-        rank come device-to-device from its Supergrid (halo="local") or over torch.distributed (batch_isend_irecv), as in exchange_halo."""
-        torch = self.torch
+        """The rows the pieces of THIS rank need from elsewhere (_fetch_rows), as {piece index: {"next": {x, y, dx, dy}, "seam": {x,
+        y}}} of 1-D tensors: the first point row (x, y, dx) and cell row (dy) of the piece that follows in stitched order, and at a
+        sub-grid joint the lower sub-grid's own last point row (x, y), which stitching drops."""
         pieces = self.quality_pieces(cut)
         metrics = not self.plan.skip_metrics
-        wanted = []   # (dst piece, kind, field, src rank, src sub-grid name, src band row), the same order on every rank
+        wanted = []
         for k, p in enumerate(pieces[:-1]):
             q = pieces[k + 1]
             for f in ("x", "y") + (("dx",) if metrics else ()) + (("dy",) if metrics and q["n_cell"] > 0 else ()):
@@ -1175,34 +1248,8 @@ class Supergrid(object):
                 for f in ("x", "y"):
                     wanted.append((k, "seam", f, src, s.name, row))
         out = {}
-        ops = []
-        for k, kind, f, src, name, row in wanted:
-            dst_rank = pieces[k]["rank"]
-            if dst_rank == self.rank:
-                if src == self.rank:
-                    t = self.buf[name][f][row]
-                elif self.halo == "local":
-                    t = self.peers[src].buf[name][f][row].clone()
-                else:
-                    t = torch.empty(self.plan.Ni + (0 if f == "dx" else 1), dtype=torch.float64, device=self.device)
-                    ops.append(("recv", t, src))
-                out.setdefault(k, {}).setdefault(kind, {})[f] = t
-            elif src == self.rank and self.halo != "local":
-                ops.append(("send", self.buf[name][f][row].contiguous(), dst_rank))
-        if ops:
-            import torch.distributed as dist
-            if all(t.is_cuda for _, t, _ in ops) and dist.get_backend() != "gloo":
-                p2p = [dist.P2POp(dist.isend if d == "send" else dist.irecv, t, r) for d, t, r in ops]
-                for w in dist.batch_isend_irecv(p2p):
-                    w.wait()
-            else:   # gloo (the CPU tests, the one-GPU rehearsal): through host copies, in the common order
-                for d, t, r in ops:
-                    if d == "send":
-                        dist.send(t.cpu(), r)
-                    else:
-                        c = torch.empty(t.shape, dtype=t.dtype)
-                        dist.recv(c, r)
-                        t.copy_(c)
+        for (k, kind, f), t in self._fetch_rows(pieces, wanted).items():
+            out.setdefault(k, {}).setdefault(kind, {})[f] = t
         return out
 
     def quality_records(self, cut, halo=None):
@@ -1226,21 +1273,15 @@ class Supergrid(object):
         p = self.plan
         metrics = not p.skip_metrics
         out = []
-        for k, q in enumerate(self.quality_pieces(cut)):
-            if q["rank"] != self.rank:
-                continue
-            b, r = self.buf[q["sub"].name], q["row"]
-            band = L.QualityBand(nx=p.Ni, j0=q["j0"], n_pt_rows=q["n_pt"], n_cell_rows=q["n_cell"], Re=float(p.Re), metrics=int(metrics))
-            band.x, band.y = self._p(b["x"], r), self._p(b["y"], r)
+        for k, q, b, band in self._bands(cut, lambda q: L.QualityBand(nx=p.Ni, j0=q["j0"], n_pt_rows=q["n_pt"], n_cell_rows=q["n_cell"],
+                                                                     Re=float(p.Re), metrics=int(metrics))):
+            r = q["row"]
             if metrics:
                 band.dx = self._p(b["dx"], r)
                 band.dy = self._p(b["dy"], r) if q["n_cell"] else None
                 band.area = self._p(b["area"], r) if q["n_cell"] else None
-            h = halo.get(k, {})
-            nxt, seam = h.get("next", {}), h.get("seam", {})
-            band.x_next, band.y_next = (nxt["x"].data_ptr() if "x" in nxt else None), (nxt["y"].data_ptr() if "y" in nxt else None)
-            band.dx_next = nxt["dx"].data_ptr() if "dx" in nxt else None
-            band.dy_next = nxt["dy"].data_ptr() if "dy" in nxt else None
+            nxt, seam = halo.get(k, {}).get("next", {}), halo.get(k, {}).get("seam", {})
+            band.x_next, band.y_next, band.dx_next, band.dy_next = (nxt[f].data_ptr() if f in nxt else None for f in ("x", "y", "dx", "dy"))
             if seam:
                 band.x_seam, band.y_seam = seam["x"].data_ptr(), seam["y"].data_ptr()
             out.append((k, band))
@@ -1270,21 +1311,17 @@ class Supergrid(object):
         from . import topography as T
         p, st = self.plan, self._stream()
         halo = self.quality_halo(cut) if halo is None else halo   # (held until the kernels have run: the bands point into it)
-        desc = source.desc
+        kind = L.TOPOG_MODEL_CELLS if cells == "model" else L.TOPOG_SUPERGRID_CELLS
         out, keep = [], []
-        for k, q in enumerate(self.quality_pieces(cut)):
-            if q["rank"] != self.rank or q["n_cell"] == 0:
-                continue
-            b, r = self.buf[q["sub"].name], q["row"]
-            band = L.TopogBand(nx=p.Ni, j0=q["j0"], n_cell_rows=q["n_cell"], refine=int(refine or 0), oversample=float(oversample),
-                               cells=L.TOPOG_MODEL_CELLS if cells == "model" else L.TOPOG_SUPERGRID_CELLS)
-            band.x, band.y = self._p(b["x"], r), self._p(b["y"], r)
+        for k, q, b, band in self._bands(cut, lambda q: L.TopogBand(nx=p.Ni, j0=q["j0"], n_cell_rows=q["n_cell"], refine=int(refine or 0),
+                                                                   oversample=float(oversample), cells=kind),
+                                         skip=lambda q: q["n_cell"] == 0):
             nxt = halo.get(k, {}).get("next")
             if nxt is not None:
                 band.x_next, band.y_next = nxt["x"].data_ptr(), nxt["y"].data_ptr()
             else:   # the piece that ends the grid holds its own last point row
-                band.x_next, band.y_next = self._p(b["x"], r + q["n_cell"]), self._p(b["y"], r + q["n_cell"])
-            m0, rec, ws = T.band_records_dev(band, desc, st, self.device)
+                band.x_next, band.y_next = self._p(b["x"], q["row"] + q["n_cell"]), self._p(b["y"], q["row"] + q["n_cell"])
+            m0, rec, ws = T.band_records_dev(band, source.desc, st, self.device)
             out.append((k, m0, rec))
             keep.append(ws)
         self.torch.cuda.synchronize(self.device)
@@ -1293,38 +1330,23 @@ class Supergrid(object):
     def topography(self, cut, source, refine=None, oversample=2.0, cells="model"):
         """Topography of the stitched grid of every rank (topography.result on rank 0, None on the other ranks): ``source`` a
         topography.DeviceSource on this rank's GPU.  Every piece is sampled by the rank that holds it; rank 0 gathers the integer records
-        (from peer objects with halo="local", over torch.distributed otherwise) and combines them exactly, so the result is
-        bit-identical for any number of ranks."""
+        (_gather) and combines them exactly, so the result is bit-identical for any number of ranks."""
         from . import topography as T
-        torch = self.torch
         nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
         T.check_args(nyp, nxp, cells, refine, oversample)
         sh = 1 if cells == "model" else 0
-        pieces = self.quality_pieces(cut)
-        if self.world > 1 and self.halo == "local" and self.rank != 0:
-            return None   # rank 0 samples the pieces of every virtual rank through its peer objects
-        mine = self.topography_records(cut, source, refine, oversample, cells)
-        got = [(m0, rec) for _, m0, rec in mine]
-        if self.world > 1 and self.halo == "local":
-            for g in self.peers:
-                if g is not self:
-                    got += [(m0, rec) for _, m0, rec in g.topography_records(cut, source, refine, oversample, cells)]
-        elif self.world > 1:
-            import torch.distributed as dist
-            words = L.TOPOG_RECORD.itemsize // 8
-            gloo = dist.get_backend() == "gloo"
-            if self.rank != 0:
-                for _, _, rec in mine:
-                    dist.send(rec.cpu() if gloo else rec.contiguous(), 0)
+        words = L.TOPOG_RECORD.itemsize // 8
+
+        def recv(k, q, take):
+            if q["n_cell"] == 0:
                 return None
-            for q in pieces:   # in piece order, as every other rank sends its own
-                if q["rank"] == 0 or q["n_cell"] == 0:
-                    continue
-                rows = ((q["j0"] + q["n_cell"] - 1) >> sh) - (q["j0"] >> sh) + 1
-                t = torch.empty((rows, self.plan.Ni >> sh, words), dtype=torch.int64, device="cpu" if gloo else self.device)
-                dist.recv(t, q["rank"])
-                got.append((q["j0"] >> sh, t))
-        recs = T.assemble([(m0, T.records_to_host(t)) for m0, t in got], (nyp - 1) >> sh, (nxp - 1) >> sh)
+            rows = ((q["j0"] + q["n_cell"] - 1) >> sh) - (q["j0"] >> sh) + 1
+            return k, q["j0"] >> sh, take((rows, self.plan.Ni >> sh, words), self.torch.int64)
+        got = self._gather(self.quality_pieces(cut), lambda g: g.topography_records(cut, source, refine, oversample, cells),
+                           lambda e: (e[2],), recv)
+        if got is None:
+            return None
+        recs = T.assemble([(m0, T.records_to_host(t)) for _, m0, t in got], (nyp - 1) >> sh, (nxp - 1) >> sh)
         return T.result(recs, source.source.quantum, source.sea_level, cells, refine, oversample, source.source)
 
     # -- atmosphere x ocean exchange grid --------------------------------------------------------------------------
@@ -1338,46 +1360,19 @@ class Supergrid(object):
 
     def xgrid_halo(self, cut):
         """{piece index: (x rows, y rows)} of THIS rank's pieces: the (one or two) stitched point rows that follow each piece, as
-        contiguous (rows, nx + 1) tensors.  Rows of this rank come from its buffers, rows of another rank from its Supergrid
-        (halo="local") or over torch.distributed, as in quality_halo."""
+        contiguous (rows, nx + 1) tensors, fetched by _fetch_rows."""
         torch = self.torch
         pieces = self.quality_pieces(cut)
-        wanted = []   # (dst piece, t, field, src rank, src sub-grid name, src band row), the same order on every rank
+        wanted = []
         for k, p in enumerate(pieces):
-            _, _, nr = self._xgrid_rows(p)
-            for t in range(nr):
+            for t in range(self._xgrid_rows(p)[2]):
                 R = p["j0"] + p["n_cell"] + t
                 src = next(q for q in pieces if q["j0"] <= R < q["j0"] + q["n_pt"])
                 for f in ("x", "y"):
                     wanted.append((k, t, f, src["rank"], src["sub"].name, src["row"] + R - src["j0"]))
-        got, ops = {}, []
-        for k, t, f, src, name, row in wanted:
-            dst = pieces[k]["rank"]
-            if dst == self.rank:
-                if src == self.rank:
-                    r = self.buf[name][f][row]
-                elif self.halo == "local":
-                    r = self.peers[src].buf[name][f][row].clone()
-                else:
-                    r = torch.empty(self.plan.Ni + 1, dtype=torch.float64, device=self.device)
-                    ops.append(("recv", r, src))
-                got.setdefault(k, {}).setdefault(f, []).append(r)
-            elif src == self.rank and self.halo != "local":
-                ops.append(("send", self.buf[name][f][row].contiguous(), dst))
-        if ops:
-            import torch.distributed as dist
-            if all(r.is_cuda for _, r, _ in ops) and dist.get_backend() != "gloo":
-                p2p = [dist.P2POp(dist.isend if d == "send" else dist.irecv, r, s) for d, r, s in ops]
-                for w in dist.batch_isend_irecv(p2p):
-                    w.wait()
-            else:   # gloo: through host copies, in the common order
-                for d, r, s in ops:
-                    if d == "send":
-                        dist.send(r.cpu(), s)
-                    else:
-                        c = torch.empty(r.shape, dtype=r.dtype)
-                        dist.recv(c, s)
-                        r.copy_(c)
+        got = {}
+        for (k, _, f), r in self._fetch_rows(pieces, wanted).items():   # (in the order of t)
+            got.setdefault(k, {}).setdefault(f, []).append(r)
         return {k: (torch.stack(v["x"]).contiguous(), torch.stack(v["y"]).contiguous()) for k, v in got.items()}
 
     def xgrid_lists(self, cut, atm, mask=None, threshold=1e-6, halo=None):
@@ -1391,15 +1386,11 @@ class Supergrid(object):
         desc = L.XgridAtm(lon=lon.data_ptr(), lat=lat.data_ptr(), NA=lon.numel() - 1, NB=lat.numel() - 1)
         ny = self.stitched_rows(cut) - 1
         out = []
-        for k, q in enumerate(self.quality_pieces(cut)):
-            m0, rows, _ = self._xgrid_rows(q)
-            if q["rank"] != self.rank or rows == 0:
-                continue
-            b, r = self.buf[q["sub"].name], q["row"]
-            band = L.XgridBand(nx=p.Ni, ny=ny, j0=q["j0"], n_cell_rows=q["n_cell"], Re=float(p.Re), threshold=float(threshold))
-            band.x, band.y = self._p(b["x"], r), self._p(b["y"], r)
+        for k, q, _, band in self._bands(cut, lambda q: L.XgridBand(nx=p.Ni, ny=ny, j0=q["j0"], n_cell_rows=q["n_cell"], Re=float(p.Re),
+                                                                   threshold=float(threshold)),
+                                         skip=lambda q: self._xgrid_rows(q)[1] == 0):
             band.x_next, band.y_next = halo[k][0].data_ptr(), halo[k][1].data_ptr()
-            band.mask = None if mask is None else mask.data_ptr() + m0 * (p.Ni // 2)
+            band.mask = None if mask is None else mask.data_ptr() + self._xgrid_rows(q)[0] * (p.Ni // 2)
             out.append((k,) + X.band_lists_dev(band, desc, st, self.device))
         self.torch.cuda.synchronize(self.device)
         return out
@@ -1407,9 +1398,8 @@ class Supergrid(object):
     def exchange_grid(self, cut, atm, mask=None, threshold=1e-6):
         """The atmosphere x ocean exchange grid of the stitched grid of every rank (exchange_grid.result on rank 0, None on the other
         ranks).  ``atm``: (lon_edges, lat_edges) of a global rectilinear atmosphere; ``mask``: None or one value per model cell (0:
-        the cell emits nothing).  Every piece is done by the rank that holds it; rank 0 gathers the lists in piece order (from peer
-        objects with halo="local", by send / recv over torch.distributed otherwise), which is the canonical order, so the result is
-        bit-identical for any number of ranks."""
+        the cell emits nothing).  Every piece is done by the rank that holds it; rank 0 gathers the lists in piece order (_gather:
+        the counts first, then the arrays), which is the canonical order, so the result is bit-identical for any number of ranks."""
         from . import exchange_grid as X
         torch = self.torch
         nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
@@ -1417,52 +1407,32 @@ class Supergrid(object):
         X.check_args(threshold, self.plan.Re)
         lon, lat = X.atm_edges(*atm)
         shape = ((nyp - 1) // 2, (nxp - 1) // 2)
-        dmask = None
+        hm = None
         if mask is not None:
             hm = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
             if hm.shape != shape:
                 raise ValueError("exchange grid: the mask is %s, the model cells %s" % (hm.shape, shape))
-            dmask = torch.from_numpy(hm).to(self.device)
-        pieces = self.quality_pieces(cut)
-        if self.world > 1 and self.halo == "local" and self.rank != 0:
-            return None   # rank 0 does the pieces of every virtual rank through its peer objects
-        dev_atm = (torch.from_numpy(lon).to(self.device), torch.from_numpy(lat).to(self.device))
-        mine = self.xgrid_lists(cut, dev_atm, dmask, threshold)
-        got = list(mine)
-        if self.world > 1 and self.halo == "local":
-            for g in self.peers:
-                if g is not self:
-                    got += g.xgrid_lists(cut, (dev_atm[0].to(g.device), dev_atm[1].to(g.device)),
-                                         None if dmask is None else dmask.to(g.device), threshold)
-        elif self.world > 1:
-            import torch.distributed as dist
-            gloo = dist.get_backend() == "gloo"
-            host = (lambda t: t.cpu()) if gloo else (lambda t: t.contiguous())   # noqa: E731
-            if self.rank != 0:
-                for _, _, counts, a_poly, atm_ij, ocn_ij, area in mine:   # in piece order: counts first, then the arrays
-                    dist.send(host(counts), 0)
-                    if atm_ij.shape[0]:
-                        for t in (atm_ij, ocn_ij, area):
-                            dist.send(host(t), 0)
-                    dist.send(host(a_poly), 0)
+
+        def records(g):
+            to = lambda a: torch.from_numpy(a).to(g.device)   # noqa: E731
+            return g.xgrid_lists(cut, (to(lon), to(lat)), None if hm is None else to(hm), threshold)
+
+        def send(e):   # counts first, then the arrays (when there are any), then a_poly
+            _, _, counts, a_poly, atm_ij, ocn_ij, area = e
+            return (counts,) + ((atm_ij, ocn_ij, area) if atm_ij.shape[0] else ()) + (a_poly,)
+
+        def recv(k, q, take):
+            m0, rows, _ = self._xgrid_rows(q)
+            if rows == 0:
                 return None
-            where = "cpu" if gloo else self.device
-            for k, q in enumerate(pieces):
-                m0, rows, _ = self._xgrid_rows(q)
-                if q["rank"] == 0 or rows == 0:
-                    continue
-                counts = torch.empty(len(L.XGRID_COUNT_FIELDS), dtype=torch.int64, device=where)
-                dist.recv(counts, q["rank"])
-                n = int(counts[L.XGRID_COUNT_FIELDS.index("kept")])
-                atm_ij = torch.empty((n, 2), dtype=torch.int32, device=where)
-                ocn_ij = torch.empty((n, 2), dtype=torch.int32, device=where)
-                area = torch.empty(n, dtype=torch.float64, device=where)
-                if n:
-                    for t in (atm_ij, ocn_ij, area):
-                        dist.recv(t, q["rank"])
-                a_poly = torch.empty((rows, shape[1]), dtype=torch.float64, device=where)
-                dist.recv(a_poly, q["rank"])
-                got.append((k, m0, counts, a_poly, atm_ij, ocn_ij, area))
+            counts = take(len(L.XGRID_COUNT_FIELDS), torch.int64)
+            n = int(counts[L.XGRID_COUNT_FIELDS.index("kept")])
+            lists = [take(s, d) if n else torch.empty(s, dtype=d, device=counts.device)
+                     for s, d in (((n, 2), torch.int32), ((n, 2), torch.int32), (n, torch.float64))]
+            return (k, m0, counts, take((rows, shape[1]), torch.float64), *lists)
+        got = self._gather(self.quality_pieces(cut), records, send, recv)
+        if got is None:
+            return None
         got.sort(key=lambda e: e[0])   # piece order: the canonical order of the list
         hostp = [(m0,) + tuple(t.cpu().numpy() for t in ts) for _, m0, *ts in got]
         return X.assemble(hostp, shape, lon, lat, float(self.plan.Re), threshold, mask is not None)

@@ -195,9 +195,60 @@ def _worker(rank, world, port, q):
             else:
                 ok &= "seam" not in halo[k]
             ok &= p["j0"] + p["n_pt"] == nxt["j0"]
-        q.put((rank, ok, len(pieces), pieces[-1]["j0"] + pieces[-1]["n_pt"] == g.stitched_rows(cut)))
+        q.put((rank, ok, len(pieces), pieces[-1]["j0"] + pieces[-1]["n_pt"] == g.stitched_rows(cut), _xgrid_halo_ok(g, pieces, code, sub_index),
+               _gather_ok(g, pieces)))
     finally:
         dist.destroy_process_group()
+
+
+def _xgrid_halo_ok(g, pieces, code, sub_index):
+    """Every row xgrid_halo returns is stitched point row j0 + n_cell + t, taken from the sub-grid that holds it."""
+    import torch
+    halo = g.xgrid_halo(g.south_cut())
+    ok = sorted(halo) == [k for k, p in enumerate(pieces) if p["rank"] == g.rank and g._xgrid_rows(p)[2]]
+    for k, (xr, yr) in halo.items():
+        p = pieces[k]
+        nr = g._xgrid_rows(p)[2]
+        for f, t in (("x", xr), ("y", yr)):
+            ok &= t.shape == (nr, g.plan.Ni + 1) and t.is_contiguous()
+            for r in range(nr):
+                R = p["j0"] + p["n_cell"] + r
+                src = next(s for s in pieces if s["j0"] <= R < s["j0"] + s["n_pt"])
+                row = src["row"] + R - src["j0"] + g.rows_of(src["sub"], src["rank"], g.world)[0]
+                ok &= bool(torch.all(t[r] == sub_index[src["sub"].name] * 1e6 + code[f] * 1e5 + row * 10))
+    return ok
+
+
+def _gather_ok(g, pieces):
+    """The rank-0 gather on made-up pieces: a count first, then a variable list (empty for some pieces), then a fixed-shape tensor; every
+    fourth piece sends nothing.  Rank 0 gets its own pieces, then the others' in piece order, with their shapes and bits."""
+    import torch
+
+    def made_up(k):   # the first piece of every rank sends an empty list
+        n = 0 if all(q["rank"] != pieces[k]["rank"] for q in pieces[:k]) else 1 + k % 3
+        return (k, torch.tensor([n], dtype=torch.int64), torch.arange(3 * n, dtype=torch.float64).reshape(n, 3) + k / 7,
+                torch.full((k + 1, 2), -k, dtype=torch.int32))
+
+    def recv(k, q, take):
+        if k % 4 == 3:
+            return None
+        counts = take(1, torch.int64)
+        n = int(counts[0])
+        lst = take((n, 3), torch.float64) if n else torch.empty((0, 3), dtype=torch.float64)
+        return k, counts, lst, take((k + 1, 2), torch.int32)
+
+    def records(h):
+        return [made_up(k) for k, q in enumerate(pieces) if q["rank"] == h.rank and k % 4 != 3]
+    got = g._gather(pieces, records, lambda e: (e[1],) + ((e[2],) if e[2].shape[0] else ()) + (e[3],), recv)
+    if g.rank != 0:
+        return got is None
+    mine = [k for k, q in enumerate(pieces) if q["rank"] == 0 and k % 4 != 3]
+    want = mine + [k for k, q in enumerate(pieces) if q["rank"] != 0 and k % 4 != 3]
+    ok = [e[0] for e in got] == want and any(made_up(k)[1] == 0 and pieces[k]["rank"] != 0 for k in want)
+    for e in got:
+        for a, b in zip(e[1:], made_up(e[0])[1:]):
+            ok &= a.dtype == b.dtype and a.shape == b.shape and a.numpy().tobytes() == b.numpy().tobytes()
+    return ok
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -214,5 +265,7 @@ def test_quality_halo_over_gloo(world):
     res = [q.get(timeout=300) for _ in range(world)]
     for p in procs:
         p.join(timeout=60)
-    assert all(ok for _, ok, _, _ in res), res
-    assert all(last for _, _, _, last in res), res
+    assert all(ok for _, ok, _, _, _, _ in res), res
+    assert all(last for _, _, _, last, _, _ in res), res
+    assert all(xgrid_ok for *_, xgrid_ok, _ in res), res
+    assert all(gather_ok for *_, gather_ok in res), res
