@@ -642,6 +642,77 @@ int ogg_xgrid_write_dev(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, co
 int ogg_xgrid(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, long capacity, int* atm_ij, int* ocn_ij, double* area,
               double* a_poly, ogg_xgrid_counts* counts);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Ocean mask: minimum depth and connected basins (an addition: the reference has none; GFDL's preprocessing calls this step "ice9").
+ * Cells: the ny x nx cells of a topography result (model or supergrid cells), (j, i) with row 0 southmost, linear index c = j * nx + i,
+ * ny * nx < 2^31.  Input: depth (ny x nx fp64), fill (topography's FILL), min_depth >= 0 and a mode.
+ *   wet rule  a cell starts wet when depth > 0 and depth != fill (exchange_grid.wet_mask).  A wet cell with depth < min_depth
+ *             becomes land in mode OGG_MASK_MASK, stays wet with depth min_depth in mode OGG_MASK_DEEPEN.  The rule is applied
+ *             BEFORE connectivity: a sill made land cuts a basin off.
+ *   topology  two wet cells are connected through a shared face only: (j, i) ~ (j, i+1), (j, i) ~ (j+1, i); with OGG_MASK_PERIODIC
+ *             (j, nx-1) ~ (j, 0); with OGG_MASK_FOLD (ny-1, i) ~ (ny-1, nx-1-i).  Diagonal neighbours are not connected.  (The
+ *             flags come from the grid's corner points, ocean_mask.detect_topology: periodic when every point row's first and last
+ *             points are one point on the sphere, folded when the top point row maps onto itself reversed and is not one point;
+ *             unit vectors compared, chordal distance <= 1e-9.)
+ *   root      the root of a component is the smallest linear index among its cells: root[c] (-1 for land) does not depend on how
+ *             the kernels ran
+ *   seeds     (lon, lat) pairs; each picks the cell whose centre is nearest by chordal distance |u_c - u_s|^2 (unit vectors
+ *             (cos lat cos lon, cos lat sin lon, sin lat), lon, lat * (pi / 180)), ties to the smaller index; the centre of a model
+ *             cell is supergrid point (2j+1, 2i+1).  A seed on a land cell is an error (OGG_EARG naming the cell and its depth).
+ *   keep      every component that holds a seed; without seeds the one with the most cells (ties: the smaller root); with
+ *             keep_min_cells N > 0 also every component of at least N cells.  Every other wet cell becomes land.
+ *   outputs   depth: removed and masked cells 0, deepened cells min_depth, kept cells and all others (land, fill, NaN) unchanged;
+ *             wet (uint8) the final mask; root taken before selection; integer counts.  Everything is integer or a copy: the
+ *             result is bit-identical for any launch geometry (OGG_MASK_TILE_ROWS).
+ * A component list entry is (cells << 32) | (INT32_MAX - root): the largest entry is the largest component (ties: smaller root).
+ * ---------------------------------------------------------------------------------------------------- */
+enum { OGG_MASK_MASK = 0, OGG_MASK_DEEPEN = 1 };
+#define OGG_MASK_PERIODIC 1
+#define OGG_MASK_FOLD 2
+#define OGG_MASK_MAX_SEEDS 1024
+enum { OGG_MASK_PARAMS = 0, OGG_MASK_COUNTS = 1 };
+typedef struct ogg_mask_params {
+    long ny, nx;
+    int topology;             /* OGG_MASK_PERIODIC | OGG_MASK_FOLD */
+    int mode;                 /* OGG_MASK_MASK or OGG_MASK_DEEPEN */
+    double fill, min_depth;
+    long long keep_min_cells; /* 0: off */
+} ogg_mask_params;
+typedef struct ogg_mask_counts {
+    long long wet_in;         /* depth > 0 and != fill (apply step) */
+    long long masked;         /* of those, made land by min_depth in mode mask (apply step) */
+    long long deepened;       /* of those, deepened to min_depth in mode deepen (apply step) */
+    long long components;     /* connected components of the wet set after the wet rule (= entries of the component list; label step) */
+    long long largest;        /* the largest component list entry, 0 without a component (label step) */
+    long long kept;           /* components kept (apply step) */
+    long long removed;        /* wet cells made land by the selection (apply step) */
+    long long wet_out;        /* wet cells of the final mask (apply step) */
+} ogg_mask_counts;
+long ogg_mask_struct_bytes(int which);                        /* sizeof of OGG_MASK_PARAMS / COUNTS, -1 otherwise */
+long ogg_mask_workspace_bytes(const ogg_mask_params* p);      /* of the label and apply steps, -1 on bad sizes */
+/* the checks of *p (sizes, mode, min_depth, fill, keep_min_cells): OGG_EARG with the reason, before any device work */
+int ogg_mask_check(const ogg_mask_params* p);
+/* label step, device pointers, on a stream: the wet rule, root[] (ny * nx), the component list into components (device memory, room
+ * for ny * nx entries, in no particular order: sort it); *counts (device memory) is zeroed and gets components and largest.  The workspace
+ * keeps what the apply step needs (the parents and the per-root cell counts). */
+int ogg_mask_label_dev(const ogg_mask_params* p, const double* depth, void* workspace, long workspace_bytes, int* root,
+                       long long* components, ogg_mask_counts* counts, void* stream);
+/* seed lookup, device pointers: for seed s (lonlat[2 s], lonlat[2 s + 1] in degrees) the nearest model-cell centre, point (2j+1, 2i+1)
+ * of x, y (point rows of ld doubles): out[2 s] the bits of the squared chordal distance, out[2 s + 1] the cell index */
+int ogg_mask_seed_dev(const ogg_mask_params* p, const double* x, const double* y, long ld, int n_seeds, const double* lonlat,
+                      long long* out, void* stream);
+/* apply step, after the label step on the same workspace: kept[0 .. n_kept-1] the roots chosen on the host (sorted ascending, device
+ * memory); also every root of at least keep_min_cells cells.  depth_out and wet (ny * nx); every count but components and largest
+ * into *counts. */
+int ogg_mask_apply_dev(const ogg_mask_params* p, const double* depth, const int* root, const void* workspace, long workspace_bytes,
+                       const int* kept, int n_kept, double* depth_out, unsigned char* wet, ogg_mask_counts* counts, void* stream);
+/* HOST pointers throughout, staged through device memory: both steps with the choice of kept roots in between.  x, y: the supergrid
+ * points ((2 ny + 1) x (2 nx + 1)), needed only with seeds; seed_cells[n_seeds] the seeds' cells; components: the sorted component
+ * list (largest first), at most capacity entries copied (counts->components says how many there are). */
+int ogg_ocean_mask(const ogg_mask_params* p, const double* depth, const double* x, const double* y, int n_seeds, const double* lonlat,
+                   double* depth_out, unsigned char* wet, int* root, long long* seed_cells, long long* components, long capacity,
+                   ogg_mask_counts* counts);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

@@ -113,6 +113,26 @@ class XgridCounts(ctypes.Structure):
 XGRID_BAND, XGRID_ATM, XGRID_COUNTS = 0, 1, 2                          # OGG_XGRID_BAND ... of include/ogg_hip.h
 
 
+class MaskParams(ctypes.Structure):
+    """ogg_mask_params of include/ogg_hip.h"""
+    _fields_ = [("ny", c_long), ("nx", c_long), ("topology", c_int), ("mode", c_int), ("fill", c_double), ("min_depth", c_double),
+                ("keep_min_cells", c_longlong)]
+
+
+MASK_COUNT_FIELDS = ("wet_in", "masked", "deepened", "components", "largest", "kept", "removed", "wet_out")
+
+
+class MaskCounts(ctypes.Structure):
+    """ogg_mask_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in MASK_COUNT_FIELDS]
+
+
+MASK_MASK, MASK_DEEPEN = 0, 1                                          # OGG_MASK_MASK, OGG_MASK_DEEPEN
+MASK_PERIODIC, MASK_FOLD = 1, 2                                        # OGG_MASK_PERIODIC, OGG_MASK_FOLD
+MASK_MAX_SEEDS = 1024                                                  # OGG_MASK_MAX_SEEDS
+MASK_PARAMS, MASK_COUNTS = 0, 1                                        # OGG_MASK_PARAMS, OGG_MASK_COUNTS
+
+
 # name -> argtypes; every function returns int except the two string getters.  Must list EVERY symbol of ogg_hip.h
 # (tests/test_abi.py checks this list against the header).
 SIGNATURES = {
@@ -230,6 +250,13 @@ SIGNATURES = {
                             c_void_p],
     "ogg_xgrid": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_long, c_void_p, c_void_p, c_void_p, c_void_p,
                   ctypes.POINTER(XgridCounts)],
+    "ogg_mask_check": [ctypes.POINTER(MaskParams)],
+    "ogg_mask_label_dev": [ctypes.POINTER(MaskParams), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_mask_seed_dev": [ctypes.POINTER(MaskParams), c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p],
+    "ogg_mask_apply_dev": [ctypes.POINTER(MaskParams), c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p,
+                           c_void_p, c_void_p],
+    "ogg_ocean_mask": [ctypes.POINTER(MaskParams), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                       c_void_p, c_void_p, c_long, ctypes.POINTER(MaskCounts)],
     "ogg_event_create": [ctypes.POINTER(c_void_p)],
     "ogg_event_destroy": [c_void_p],
     "ogg_event_record": [c_void_p, c_void_p],
@@ -254,7 +281,9 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_xgrid_band_first_row": [ctypes.POINTER(XgridBand)],
                 "ogg_xgrid_band_out_rows": [ctypes.POINTER(XgridBand)],
                 "ogg_xgrid_band_next_rows": [ctypes.POINTER(XgridBand)],
-                "ogg_xgrid_workspace_bytes": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm)]}
+                "ogg_xgrid_workspace_bytes": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm)],
+                "ogg_mask_struct_bytes": [c_int],
+                "ogg_mask_workspace_bytes": [ctypes.POINTER(MaskParams)]}
 
 _lib = None
 

@@ -141,10 +141,12 @@ NUMPY_DTYPE = {t: np.dtype(d) for t, d in _NUMPY_TYPE.items()}   # NetCDF type -
 
 
 class Header(object):
-    """What read_header() finds: version (1 or 2), dims [(name, length)], vars {name: Variable}."""
+    """What read_header() finds: version (1 or 2), dims [(name, length)], vars {name: Variable}, global attributes gatts {name:
+    str or 1-D numpy array}."""
 
-    def __init__(self, version, dims, vars):
+    def __init__(self, version, dims, vars, gatts=None):
         self.version, self.dims, self.vars = version, dims, vars
+        self.gatts = gatts if gatts is not None else {}
 
 
 def read_header(path):
@@ -209,7 +211,7 @@ def _parse_header(path, data, version):
     if tag not in (0, NC_DIMENSION):
         raise ValueError("%s: bad dimension list" % path)
     dims = [(name(), i32()) for _ in range(ndims)]
-    atts()
+    gatts = atts()
     tag, nvars = i32(), i32()
     if tag not in (0, NC_VARIABLE):
         raise ValueError("%s: bad variable list" % path)
@@ -225,7 +227,7 @@ def _parse_header(path, data, version):
         shape = [numrecs if (k == 0 and is_rec) else dims[d][1] for k, d in enumerate(ids)]
         out[vname] = Variable(vname, nc_type, shape, begin, is_rec, vatts)
         out[vname].dims = tuple(dims[d][0] for d in ids)
-    return Header(version, dims, out)
+    return Header(version, dims, out, gatts)
 
 
 def read_var_bytes(path, header, name, dtype=NC_DOUBLE):

@@ -642,7 +642,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          ensure_nj_even=False, shift_equator_to_u_point=True, bipolar_lower_lat=-99.0, mercator_lower_lat=-99.0,
          mercator_upper_lat=-99.0, south_ocean_lower_lat=-99.0, south_ocean_upper_lat=-99.0, no_south_cap=False,
          return_arrays=False, path=None, dp_arc=None, cap_symmetry=None, quality_report=None, topog_source=None, topog_var="elevation",
-         topog_file="topog.nc", topog_refine=None, xgrid_atm=None, xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc"):
+         topog_file="topog.nc", topog_refine=None, xgrid_atm=None, xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc",
+         ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False, mask_seed=None, mask_keep_cells=0):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -661,7 +662,11 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     sample that raster (variable ``topog_var``) on the model cells of the stitched grid straight from HBM and write ``topog_file``
     (topography.py; ``topog_refine``: R x R samples per supergrid cell instead of R from the cell's size); also an addition.
     ``xgrid_atm`` (--xgrid_atm NLON NLAT): write the exchange grid of the model cells with a regular global NLON x NLAT atmosphere to
-    ``xgrid_file`` (exchange_grid.py; only cells with depth > 0 when ``topog_source`` is given too); also an addition."""
+    ``xgrid_file`` (exchange_grid.py; only cells with depth > 0 when ``topog_source`` is given too); also an addition.
+    ``ocean_mask_file`` (--ocean_mask_file FILE, needs ``topog_source``): the ocean mask of that topography (ocean_mask.py: cells
+    shallower than ``mask_min_depth`` made land, or deepened with ``mask_deepen``; only the basins holding a ``mask_seed`` (lon, lat),
+    or the largest, kept, and those of at least ``mask_keep_cells`` cells), written to FILE; topog_file then holds the edited depth
+    and depth_sampled, and the exchange grid uses the edited wet set; also an addition."""
     import time
 
     path = path or os.environ.get("OGG_MAIN_PATH", "pass")
@@ -672,10 +677,11 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
                                    match_dy, skip_metrics, ensure_nj_even, shift_equator_to_u_point, bipolar_lower_lat, mercator_lower_lat,
                                    mercator_upper_lat, south_ocean_lower_lat, south_ocean_upper_lat, no_south_cap, return_arrays, dp_arc,
                                    cap_symmetry, quality_report, topog_source, topog_var, topog_file, topog_refine, xgrid_atm,
-                                   xgrid_file)
+                                   xgrid_file, ocean_mask_file, mask_min_depth, mask_deepen, mask_seed, mask_keep_cells)
     from . import supergrid as SG
 
     _validate_flags(match_dy, r_dp, lat_dp)
+    _validate_mask_flags(ocean_mask_file, topog_source)
     hist, source, desc = _meta_strings(inverse_resolution, no_changing_meta)
     start_time = time.time()
     plan = SG.SupergridPlan(inverse_resolution, r_dp=r_dp, lon_dp=lon_dp, lat_dp=lat_dp, exfracdp=exfracdp, south_cutoff_row=south_cutoff_row,
@@ -706,7 +712,11 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     if topog_source is not None:
         from . import topography as T
         src = _topog_source(topog_source, topog_var)
-        topo = _write_topog(g.topography(cut, T.DeviceSource(src, g.device), refine=topog_refine), topog_file)
+        topo = g.topography(cut, T.DeviceSource(src, g.device), refine=topog_refine)
+        mask = None
+        if ocean_mask_file:
+            mask = g.ocean_mask(cut, topo, **_mask_args(mask_min_depth, mask_deepen, mask_seed, mask_keep_cells))
+        topo = _write_topog_and_mask(topo, mask, topog_file, ocean_mask_file)
     if xgrid_atm is not None:
         from . import exchange_grid as X
         _write_xgrid(g.exchange_grid(cut, X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo)), xgrid_file)
@@ -777,12 +787,14 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
                         mercator_upper_lat=-99.0, south_ocean_lower_lat=-99.0, south_ocean_upper_lat=-99.0, no_south_cap=False,
                         return_arrays=False, dp_arc=None, cap_symmetry=None, quality_report=None, topog_source=None,
                         topog_var="elevation", topog_file="topog.nc", topog_refine=None, xgrid_atm=None,
-                        xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc"):
+                        xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0,
+                        mask_deepen=False, mask_seed=None, mask_keep_cells=0):
     """The reference's own sequence of calls (OGG:855-1449), every callee a host-array function of this module (numpy in, numpy
     out, one staged device call each) and the stitching on the host: what a user gets who swaps the reference's module for this
     one function by function.  main() produces the same bits from one device-resident pass."""
     import time
 
+    _validate_mask_flags(ocean_mask_file, topog_source)
     known_options = ["bp", "so", "p125sc", ""]
     unknown = list(set(match_dy).difference(known_options))
     if len(unknown) != 0:
@@ -1002,7 +1014,12 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
     topo = None
     if topog_source is not None:   # the same topography as the device pass gives, from the stitched host arrays
         from . import topography as T
-        topo = _write_topog(T.topography(x3, y3, _topog_source(topog_source, topog_var), refine=topog_refine), topog_file)
+        topo = T.topography(x3, y3, _topog_source(topog_source, topog_var), refine=topog_refine)
+        mask = None
+        if ocean_mask_file:   # the same mask as the device pass gives, through the host-pointer entry
+            from . import ocean_mask as M
+            mask = M.ocean_mask(topo["depth"], x3, y3, fill=T.FILL, **_mask_args(mask_min_depth, mask_deepen, mask_seed, mask_keep_cells))
+        topo = _write_topog_and_mask(topo, mask, topog_file, ocean_mask_file)
     if xgrid_atm is not None:   # the same list as the device pass gives, through the host-pointer entry
         from . import exchange_grid as X
         _write_xgrid(X.exchange_grid(x3, y3, *X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo), Re=_default_Re), xgrid_file)
@@ -1084,6 +1101,29 @@ def _write_topog(res, fnam):
     return res
 
 
+def _validate_mask_flags(ocean_mask_file, topog_source):
+    if ocean_mask_file and topog_source is None:
+        raise ValueError("--ocean_mask_file needs --topog_source: the ocean mask is made from the topography")
+
+
+def _mask_args(min_depth, deepen, seeds, keep_cells):
+    return dict(min_depth=float(min_depth or 0.0), mode="deepen" if deepen else "mask", seeds=[tuple(s) for s in (seeds or ())],
+                keep_min_cells=int(keep_cells or 0))
+
+
+def _write_topog_and_mask(topo, mask, topog_file, mask_file):
+    """topog_file (with the edited depth and depth_sampled when there is a mask), then the mask's summary and mask_file; the topography
+    as written (the exchange grid's wet set comes from its depth)"""
+    if mask is None:
+        return _write_topog(topo, topog_file)
+    from . import ocean_mask as M
+    topo = _write_topog(M.edit_topog(topo, mask), topog_file)
+    for line in M.summary_lines(mask):
+        print(line)
+    M.write_mask(str(mask_file), mask)
+    return topo
+
+
 def _xgrid_mask(topo):
     """depth > 0 of the topography just computed (cells without a valid sample are dry), or None without one"""
     if topo is None:
@@ -1155,6 +1195,15 @@ def build_parser():
                              "(wet cells only when --topog_source is given)")
     parser.add_argument("--xgrid_file", type=str, required=False, default="atmos_mosaic_tile1Xocean_mosaic_tile1.nc",
                         help="exchange-grid output file, default atmos_mosaic_tile1Xocean_mosaic_tile1.nc")
+    parser.add_argument("--ocean_mask_file", type=str, required=False, default=None,
+                        help="make the ocean mask of the --topog_source topography (minimum depth, connected basins) and write it to this "
+                             "file; --topog_file then holds the edited depth (and depth_sampled), and --xgrid_atm uses it")
+    parser.add_argument("--mask_min_depth", type=float, required=False, default=0.0,
+                        help="wet cells shallower than this become land (default 0: none)")
+    parser.add_argument("--mask_deepen", action="store_true", help="deepen cells shallower than --mask_min_depth instead")
+    parser.add_argument("--mask_seed", type=float, nargs=2, action="append", required=False, default=None, metavar=("LON", "LAT"),
+                        help="a point in the open ocean (repeatable): every basin holding one is kept (default: the largest basin)")
+    parser.add_argument("--mask_keep_cells", type=int, required=False, default=0, help="also keep every basin of at least N cells")
     return parser
 
 

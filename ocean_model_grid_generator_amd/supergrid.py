@@ -1437,6 +1437,41 @@ class Supergrid(object):
         hostp = [(m0,) + tuple(t.cpu().numpy() for t in ts) for _, m0, *ts in got]
         return X.assemble(hostp, shape, lon, lat, float(self.plan.Re), threshold, mask is not None)
 
+    # -- ocean mask ---------------------------------------------------------------------------------------------------
+    def stitched_xy(self, cut):
+        """The stitched x and y ((nyp, nxp) float64 device tensors) on rank 0's device, None on the other ranks: every piece's point rows
+        gathered in piece order (_gather)."""
+        torch, nxp = self.torch, self.plan.Ni + 1
+
+        def records(g):
+            out = []
+            for k, q in enumerate(g.quality_pieces(cut)):
+                if q["rank"] == g.rank:
+                    b = g.buf[q["sub"].name]
+                    out.append((k, b["x"][q["row"]:q["row"] + q["n_pt"]].to(self.device), b["y"][q["row"]:q["row"] + q["n_pt"]].to(self.device)))
+            return out
+
+        def recv(k, q, take):
+            return k, take((q["n_pt"], nxp), torch.float64), take((q["n_pt"], nxp), torch.float64)
+        got = self._gather(self.quality_pieces(cut), records, lambda e: (e[1], e[2]), recv)
+        if got is None:
+            return None
+        got.sort(key=lambda e: e[0])
+        return (torch.cat([e[1].to(self.device) for e in got]).contiguous(), torch.cat([e[2].to(self.device) for e in got]).contiguous())
+
+    def ocean_mask(self, cut, topo, min_depth=0.0, mode="mask", seeds=(), keep_min_cells=0):
+        """The ocean mask (ocean_mask.result on rank 0, None on the other ranks) of the topography ``topo`` that topography() gathered on
+        rank 0, computed on rank 0's GPU with the stitched grid gathered there: the same for any number of ranks by construction."""
+        from . import ocean_mask as M
+        from . import topography as T
+        xy = self.stitched_xy(cut)
+        if xy is None:
+            return None
+        depth = self.torch.from_numpy(np.ascontiguousarray(topo["depth"], dtype=np.float64)).to(self.device)
+        res = M.ocean_mask_dev(depth, xy[0], xy[1], min_depth=min_depth, mode=mode, seeds=seeds, keep_min_cells=keep_min_cells,
+                               fill=T.FILL)
+        return res
+
     def bands_to_host(self):
         """This rank's bands as numpy arrays (halo rows dropped): {sub: {field: array}}."""
         out = {}

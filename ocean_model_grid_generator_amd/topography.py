@@ -381,6 +381,10 @@ def write_topog(path, res, units="m"):
                                                             ("_FillValue", FILL)], res[name])
     ds.def_var("n_samples", netcdf3.NC_INT, ("ny", "nx"), [("units", "1"), ("long_name", "number of valid samples in the cell")],
                res["n_samples"])
+    if "depth_sampled" in res:   # the ocean mask edited depth (ocean_mask.edit_topog): the depth as sampled
+        ds.def_var("depth_sampled", netcdf3.NC_DOUBLE, ("ny", "nx"), [("units", units), ("long_name", "depth as sampled, before the "
+                                                                                                      "ocean mask"), ("_FillValue", FILL)],
+                   res["depth_sampled"])
     ds.write()
 
 

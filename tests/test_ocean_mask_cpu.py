@@ -1,0 +1,188 @@
+"""CPU tests of the ocean mask: the numpy definition (tests/ocean_mask_definition.py) on hand-made cases, detect_topology on the golden
+grids and on grids without a fold, the library's argument checks through ctypes (no device work), the struct sizes, and the flags of
+main()."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import ocean_mask_definition as D
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def n_comp(root):
+    return len(np.unique(root[root >= 0]))
+
+
+def spiral(n):
+    """a square spiral corridor one cell wide with walls one cell wide, walked from the outside in"""
+    w = np.zeros((n, n), bool)
+    j, i, dj, di, steps = 0, 0, 0, 1, [n - 1]
+    k = n - 1
+    while k > 0:
+        steps += [k, k] if len(steps) > 1 else [k]
+        k -= 2
+    w[0, 0] = True
+    for s in steps:
+        for _ in range(s):
+            j, i = j + dj, i + di
+            w[j, i] = True
+        dj, di = di, -dj
+    return w
+
+
+def test_spiral_and_serpentine_are_one_component():
+    w = spiral(31)
+    r = D.roots(w)
+    assert n_comp(r) == 1 and np.all(r[w] == 0) and w.sum() > 400
+    cut = w.copy()
+    cut[15, 15] = False   # the corridor's end: still one
+    assert n_comp(D.roots(cut)) == 1
+    cut = w.copy()
+    cut[0, 10] = False    # the outer corridor cut: two
+    assert n_comp(D.roots(cut)) == 2
+    s = np.zeros((9, 12), bool)
+    s[::2] = True
+    for k, j in enumerate(range(1, 9, 2)):
+        s[j, -1 if k % 2 == 0 else 0] = True
+    r = D.roots(s)
+    assert n_comp(r) == 1 and np.all(r[s] == 0)
+
+
+def test_checkerboard_diagonals_do_not_connect():
+    w = (np.add.outer(np.arange(6), np.arange(8)) % 2) == 0
+    r = D.roots(w)
+    assert n_comp(r) == w.sum()
+    assert np.array_equal(r[w], np.flatnonzero(w.ravel()))
+
+
+def test_seam_and_fold_join_basins():
+    w = np.zeros((4, 8), bool)
+    w[1:3, 0] = True
+    w[1:3, 7] = True   # two basins that touch only across the periodic seam
+    assert n_comp(D.roots(w)) == 2 and n_comp(D.roots(w, periodic=True)) == 1
+    f = np.zeros((4, 8), bool)
+    f[2:4, 1] = True
+    f[2:4, 6] = True   # (3, 1) ~ (3, 8 - 1 - 1) across the fold only
+    assert n_comp(D.roots(f)) == 2 and n_comp(D.roots(f, fold=True)) == 1
+    assert n_comp(D.roots(f, periodic=True)) == 2
+    r = D.roots(f, fold=True)
+    assert r[3, 6] == r[2, 6] == r[3, 1] == 2 * 8 + 1   # the root is the smallest index: (2, 1)
+
+
+def test_sill_masked_or_deepened():
+    d = np.zeros((5, 11))
+    d[1:4, 0:4] = 1000.0    # open sea
+    d[2, 4:7] = 5.0         # a 5 m sill
+    d[1:4, 7:11] = 800.0    # the sea behind it
+    m = D.ocean_mask(d, min_depth=10.0, mode="mask")
+    assert m["n_components"] == 2 and m["masked"] == 3
+    assert np.all(m["depth"][1:4, 7:11] == 0) and np.all(m["depth"][2, 4:7] == 0) and np.all(m["depth"][1:4, 0:4] == 1000)
+    k = D.ocean_mask(d, min_depth=10.0, mode="deepen")
+    assert k["n_components"] == 1 and k["deepened"] == 3
+    assert np.all(k["depth"][2, 4:7] == 10.0) and np.all(k["depth"][1:4, 7:11] == 800.0) and k["wet"].sum() == 27
+    # fill values and negative depths stay as they are
+    d2 = d.copy()
+    d2[0, 0], d2[4, 10] = D.FILL, -3.0
+    assert D.ocean_mask(d2)["depth"][0, 0] == D.FILL and D.ocean_mask(d2)["depth"][4, 10] == -3.0
+
+
+def test_largest_tie_goes_to_smaller_root_and_seed_rules():
+    d = np.zeros((3, 7))
+    d[1, 0:2] = 50.0
+    d[1, 5:7] = 60.0
+    m = D.ocean_mask(d)
+    assert m["kept_roots"] == [7] and m["removed"] == 2
+    X, Y = np.meshgrid(np.arange(15) * 0.5 - 1.0, np.arange(7) * 0.5)   # centres at (i - 0.5, j + 0.5)
+    m = D.ocean_mask(d, X, Y, seeds=[(5.25, 1.25)])
+    assert m["seed_cells"] == [13] and m["kept_roots"] == [12]
+    with pytest.raises(ValueError, match="land"):
+        D.ocean_mask(d, X, Y, seeds=[(2.0, 1.5)])    # half way between cells 9 and 10: 9, on land
+    # a seed half way between two centres goes to the smaller index
+    assert D.seed_cell(X, Y, 0.0, 1.5) == 7
+    m = D.ocean_mask(d, keep_min_cells=2)
+    assert m["removed"] == 0
+
+
+@pytest.mark.parametrize("name", ["ref_small_r0.25_even", "ref_small_r0.5_dp"])
+def test_detect_topology_on_golden_grids(name):
+    from ocean_model_grid_generator_amd import ocean_mask as M
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    assert M.detect_topology(z["x"], z["y"], 2) == (True, True)
+    assert M.detect_topology(z["x"], z["y"], 1) == (True, True)
+    # opened: the last column dropped (not periodic, and the top row no longer maps onto itself)
+    assert M.detect_topology(z["x"][:, :-2], z["y"][:, :-2], 2) == (False, False)
+
+
+def test_pole_topped_latlon_grid_is_not_folded():
+    from ocean_model_grid_generator_amd import ocean_mask as M
+    lon = np.linspace(-300.0, 60.0, 73)
+    lat = np.linspace(-80.0, 90.0, 35)
+    X, Y = np.meshgrid(lon, lat)
+    assert M.detect_topology(X, Y, 2) == (True, False)
+    assert M.detect_topology(X[:, :40], Y[:, :40], 2) == (False, False)
+    lat2 = np.linspace(-80.0, 80.0, 35)
+    X, Y = np.meshgrid(lon, lat2)
+    assert M.detect_topology(X, Y, 1) == (True, False)
+
+
+def test_argument_errors_without_a_device(hip_lib):
+    L, lib = hip_lib
+    d = np.ones(4)
+    c = L.MaskCounts()
+
+    def rc(ny, nx, **kw):
+        p = L.MaskParams(ny=ny, nx=nx, **kw)
+        code = lib.ogg_ocean_mask(ctypes.byref(p), d.ctypes.data, None, None, 0, None, d.ctypes.data, d.ctypes.data, d.ctypes.data,
+                                  None, None, 0, ctypes.byref(c))
+        return code, lib.ogg_last_error().decode()
+
+    assert rc(0, 4) == (L.OGG_EARG, "ocean mask: 0 x 4 cells")
+    assert rc(3, -1) == (L.OGG_EARG, "ocean mask: 3 x -1 cells")
+    assert rc(1 << 16, 1 << 15) == (L.OGG_EARG, "ocean mask: 65536 x 32768 cells: ny * nx must be < 2^31")
+    assert rc(46341, 46341)[0] == L.OGG_EARG
+    assert rc(2, 2, mode=7) == (L.OGG_EARG, "ocean mask: mode 7 (0: mask, 1: deepen)")
+    assert rc(2, 2, min_depth=-1.0) == (L.OGG_EARG, "ocean mask: min_depth must be >= 0 (-1)")
+    assert rc(2, 2, keep_min_cells=-5) == (L.OGG_EARG, "ocean mask: keep_min_cells must be >= 0 (-5)")
+    assert rc(2, 2, topology=4) == (L.OGG_EARG, "ocean mask: topology flags 4")
+    p = L.MaskParams(ny=1 << 16, nx=1 << 15)
+    assert lib.ogg_mask_workspace_bytes(ctypes.byref(p)) == -1
+    p = L.MaskParams(ny=10, nx=10)
+    assert lib.ogg_mask_workspace_bytes(ctypes.byref(p)) == 1024
+    assert lib.ogg_mask_label_dev(ctypes.byref(p), None, None, 0, None, None, None, None) == L.OGG_EARG
+    from ocean_model_grid_generator_amd import ocean_mask as M
+    with pytest.raises(ValueError, match="mode"):
+        M.params(2, 2, False, False, mode="flood")
+    with pytest.raises(ValueError, match="2\\^31"):
+        M.params(1 << 16, 1 << 15, False, False)
+
+
+def test_struct_sizes_equal_the_ctypes_mirrors(hip_lib):
+    L, lib = hip_lib
+    assert lib.ogg_mask_struct_bytes(L.MASK_PARAMS) == ctypes.sizeof(L.MaskParams)
+    assert lib.ogg_mask_struct_bytes(L.MASK_COUNTS) == ctypes.sizeof(L.MaskCounts)
+    assert lib.ogg_mask_struct_bytes(2) == -1
+
+
+def test_main_flags():
+    from ocean_model_grid_generator_amd import ocean_grid_generator as ogg
+    a = ogg.build_parser().parse_args(["-r", "1", "--topog_source", "s.nc", "--ocean_mask_file", "m.nc", "--mask_min_depth", "10",
+                                       "--mask_deepen", "--mask_seed", "-150", "0", "--mask_seed", "-30", "-40", "--mask_keep_cells",
+                                       "100"])
+    assert a.ocean_mask_file == "m.nc" and a.mask_min_depth == 10.0 and a.mask_deepen
+    assert a.mask_seed == [[-150.0, 0.0], [-30.0, -40.0]] and a.mask_keep_cells == 100
+    b = ogg.build_parser().parse_args(["-r", "1"])
+    assert b.ocean_mask_file is None and b.mask_seed is None and not b.mask_deepen and b.mask_min_depth == 0 and b.mask_keep_cells == 0
+    with pytest.raises(ValueError, match="needs --topog_source"):
+        ogg.main(1.0, gridfilename=None, ocean_mask_file="m.nc")
+
+
+@pytest.fixture(scope="module")
+def hip_lib():
+    from ocean_model_grid_generator_amd import _lib as L
+    if not os.path.exists(L.LIB_PATH):
+        pytest.fail("libogg_hip.so is not built: run __graft_entry__.build()")
+    return L, L.load()
