@@ -713,6 +713,76 @@ int ogg_ocean_mask(const ogg_mask_params* p, const double* depth, const double* 
                    double* depth_out, unsigned char* wet, int* root, long long* seed_cells, long long* components, long capacity,
                    ogg_mask_counts* counts);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Conservative remap (an addition: the reference has none).  First-order conservative remapping of fields on a global rectilinear
+ * (lat-lon) source grid onto the model cells, with the exchange list of ogg_xgrid as the weights.
+ *   source   edges lon (NA + 1) and lat (NB + 1) as ogg_xgrid_check_atm accepts them; values f[r][J][I], r < nrec (every dimension
+ *            ahead of lat / lon), row 0 southmost, float32 or fp64 (dtype).  A value is MISSING when it is NaN or equals one of the
+ *            n_fill <= 2 fill values, compared in the source's own type (the fill value converted to it).
+ *   weights  the list of ogg_xgrid between the source edges (as the atmosphere) and the model cells, same threshold, optional uint8
+ *            wet mask (dry cells have no entries), in list order: ocean cells row-major, then J, then a_I + s.
+ *   remap    model cell c, record r, entries e_1 .. e_n of c in list order: W = sum A_e, S = sum (A_e * f_e) over the entries whose
+ *            value is not missing, both left to right in fp64, each product rounded before it is added (no FMA).  W > 0: value S / W,
+ *            flag OGG_REMAP_REMAPPED.
+ *   fill     per record, by graph distance d through wet cells across faces: i +- 1 (with OGG_MASK_PERIODIC, (j, nx-1) ~ (j, 0)),
+ *            j +- 1, and on the top row with OGG_MASK_FOLD the partner (ny-1, nx-1-i) (the ocean mask's topology).  Remapped cells
+ *            have d = 0; a wet cell with W = 0 has d = 1 + min d(neighbour), and its value is the sum of the values of its neighbours
+ *            with d = d(c) - 1, in the order S, W, E, N (N: the fold partner on the top row), left to right from 0, divided by
+ *            their count: flag OGG_REMAP_FILLED.  Cells the fill does not reach, those with d > fill_max (fill_max >= 0) and every
+ *            wet cell with W = 0 when the fill step is not run: flag OGG_REMAP_UNFILLED and value OGG_REMAP_FILL.
+ *   dry      cells where the mask is 0: flag OGG_REMAP_DRY and value OGG_REMAP_FILL.
+ * A value depends only on the list, the source and values at smaller distance, so the result is BIT-IDENTICAL for any launch geometry
+ * (the OGG_REMAP_* environment knobs) and any split of the grid into ranks.  Output layout: values (fp64) and flags (uint8), both
+ * (nrec, ny, nx), record-major.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { OGG_REMAP_FLOAT32 = 0, OGG_REMAP_FLOAT64 = 1 };
+enum { OGG_REMAP_DRY = 0, OGG_REMAP_REMAPPED = 1, OGG_REMAP_FILLED = 2, OGG_REMAP_UNFILLED = 3 };
+#define OGG_REMAP_FILL 1.0e20
+#define OGG_REMAP_MAX_FILLS 2
+enum { OGG_REMAP_PARAMS = 0, OGG_REMAP_COUNTS = 1 };
+/* the cells are model rows m0 .. m0 + ny - 1 of a grid nx cells wide (the list's m are counted in the whole grid); the fill step
+ * needs the whole grid (m0 = 0).  ny * nx < 2^31, nrec * ny * nx < 2^32, NA * NB < 2^31. */
+typedef struct ogg_remap_params {
+    long ny, nx, m0;
+    long NA, NB, nrec;
+    int dtype;                 /* OGG_REMAP_FLOAT32 / FLOAT64 */
+    int n_fill;                /* 0 .. OGG_REMAP_MAX_FILLS */
+    double fill[2];            /* the values that mark missing */
+    int topology;              /* fill step: OGG_MASK_PERIODIC | OGG_MASK_FOLD */
+    int fill_max;              /* fill step: the largest distance filled, < 0 for no limit */
+} ogg_remap_params;
+/* (record, cell) pairs by flag, and what the fill did */
+typedef struct ogg_remap_counts {
+    long long dry, remapped, filled, unfilled;
+    long long bad_entries;     /* list entries outside the cells or the source (a list of other edges or rows): refuse the result */
+    long long max_distance;    /* the largest distance filled */
+    long long fronts;          /* fill fronts with cells (= max_distance) */
+    long long launches;        /* fill launches, those on an empty frontier included */
+} ogg_remap_counts;
+long ogg_remap_struct_bytes(int which);                     /* sizeof of OGG_REMAP_PARAMS / COUNTS, -1 otherwise */
+long ogg_remap_workspace_bytes(const ogg_remap_params* p);  /* of the segment, remap and fill steps, -1 on a bad *p */
+/* the checks of *p (sizes, dtype, n_fill, topology): OGG_EARG with the reason, before any device work */
+int ogg_remap_check(const ogg_remap_params* p);
+/* segment step, device pointers, on a stream: the [start, end) range of every cell's entries in the list (ocn_ij, n_entries pairs
+ * (n, m) as ogg_xgrid_write_dev writes them), from the boundaries of ocn_ij (one pass, no sort), into the workspace */
+int ogg_remap_segments_dev(const ogg_remap_params* p, const int* ocn_ij, long n_entries, void* workspace, long workspace_bytes,
+                           void* stream);
+/* remap step, after the segment step on the same workspace: f the source (nrec * NB * NA values of dtype), atm_ij / area the list,
+ * mask NULL (every cell wet) or one byte per cell; values and flags (nrec * ny * nx) as above, wet cells with W = 0 flagged
+ * OGG_REMAP_UNFILLED; *counts (device memory) is zeroed and gets dry, remapped, unfilled and bad_entries.  flags: an allocation
+ * rounded up to a multiple of 4 bytes (the fill step changes flags by 32-bit compare-and-swap). */
+int ogg_remap_dev(const ogg_remap_params* p, const void* f, const int* atm_ij, const double* area, long n_entries,
+                  const unsigned char* mask, const void* workspace, long workspace_bytes, double* values, unsigned char* flags,
+                  ogg_remap_counts* counts, void* stream);
+/* fill step on the remap step's values and flags of the whole grid (m0 = 0): front by front, one launch per front for all records;
+ * the host reads the frontier length every few fronts.  Updates filled, unfilled, max_distance, fronts and launches in *counts. */
+int ogg_remap_fill_dev(const ogg_remap_params* p, void* workspace, long workspace_bytes, double* values, unsigned char* flags,
+                       ogg_remap_counts* counts, void* stream);
+/* HOST pointers throughout, staged through device memory: the three steps (the fill when do_fill != 0) on the list atm_ij / ocn_ij /
+ * area of n_entries entries; mask NULL or one byte per cell. */
+int ogg_remap(const ogg_remap_params* p, const void* f, const int* atm_ij, const int* ocn_ij, const double* area, long n_entries,
+              const unsigned char* mask, int do_fill, double* values, unsigned char* flags, ogg_remap_counts* counts);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

@@ -133,6 +133,27 @@ MASK_MAX_SEEDS = 1024                                                  # OGG_MAS
 MASK_PARAMS, MASK_COUNTS = 0, 1                                        # OGG_MASK_PARAMS, OGG_MASK_COUNTS
 
 
+class RemapParams(ctypes.Structure):
+    """ogg_remap_params of include/ogg_hip.h"""
+    _fields_ = [("ny", c_long), ("nx", c_long), ("m0", c_long), ("NA", c_long), ("NB", c_long), ("nrec", c_long), ("dtype", c_int),
+                ("n_fill", c_int), ("fill", c_double * 2), ("topology", c_int), ("fill_max", c_int)]
+
+
+REMAP_COUNT_FIELDS = ("dry", "remapped", "filled", "unfilled", "bad_entries", "max_distance", "fronts", "launches")
+
+
+class RemapCounts(ctypes.Structure):
+    """ogg_remap_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in REMAP_COUNT_FIELDS]
+
+
+REMAP_FLOAT32, REMAP_FLOAT64 = 0, 1                                    # OGG_REMAP_FLOAT32, OGG_REMAP_FLOAT64
+REMAP_DRY, REMAP_REMAPPED, REMAP_FILLED, REMAP_UNFILLED = 0, 1, 2, 3   # OGG_REMAP_DRY ... OGG_REMAP_UNFILLED
+REMAP_FILL = 1.0e20                                                    # OGG_REMAP_FILL
+REMAP_MAX_FILLS = 2                                                    # OGG_REMAP_MAX_FILLS
+REMAP_PARAMS, REMAP_COUNTS = 0, 1                                      # OGG_REMAP_PARAMS, OGG_REMAP_COUNTS
+
+
 # name -> argtypes; every function returns int except the two string getters.  Must list EVERY symbol of ogg_hip.h
 # (tests/test_abi.py checks this list against the header).
 SIGNATURES = {
@@ -257,6 +278,13 @@ SIGNATURES = {
                            c_void_p, c_void_p],
     "ogg_ocean_mask": [ctypes.POINTER(MaskParams), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p, c_void_p, c_long, ctypes.POINTER(MaskCounts)],
+    "ogg_remap_check": [ctypes.POINTER(RemapParams)],
+    "ogg_remap_segments_dev": [ctypes.POINTER(RemapParams), c_void_p, c_long, c_void_p, c_long, c_void_p],
+    "ogg_remap_dev": [ctypes.POINTER(RemapParams), c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_void_p,
+                      c_void_p, c_void_p],
+    "ogg_remap_fill_dev": [ctypes.POINTER(RemapParams), c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_remap": [ctypes.POINTER(RemapParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p,
+                  ctypes.POINTER(RemapCounts)],
     "ogg_event_create": [ctypes.POINTER(c_void_p)],
     "ogg_event_destroy": [c_void_p],
     "ogg_event_record": [c_void_p, c_void_p],
@@ -283,7 +311,9 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_xgrid_band_next_rows": [ctypes.POINTER(XgridBand)],
                 "ogg_xgrid_workspace_bytes": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm)],
                 "ogg_mask_struct_bytes": [c_int],
-                "ogg_mask_workspace_bytes": [ctypes.POINTER(MaskParams)]}
+                "ogg_mask_workspace_bytes": [ctypes.POINTER(MaskParams)],
+                "ogg_remap_struct_bytes": [c_int],
+                "ogg_remap_workspace_bytes": [ctypes.POINTER(RemapParams)]}
 
 _lib = None
 

@@ -643,7 +643,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          mercator_upper_lat=-99.0, south_ocean_lower_lat=-99.0, south_ocean_upper_lat=-99.0, no_south_cap=False,
          return_arrays=False, path=None, dp_arc=None, cap_symmetry=None, quality_report=None, topog_source=None, topog_var="elevation",
          topog_file="topog.nc", topog_refine=None, xgrid_atm=None, xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc",
-         ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False, mask_seed=None, mask_keep_cells=0):
+         ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False, mask_seed=None, mask_keep_cells=0,
+         remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -666,7 +667,10 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     ``ocean_mask_file`` (--ocean_mask_file FILE, needs ``topog_source``): the ocean mask of that topography (ocean_mask.py: cells
     shallower than ``mask_min_depth`` made land, or deepened with ``mask_deepen``; only the basins holding a ``mask_seed`` (lon, lat),
     or the largest, kept, and those of at least ``mask_keep_cells`` cells), written to FILE; topog_file then holds the edited depth
-    and depth_sampled, and the exchange grid uses the edited wet set; also an addition."""
+    and depth_sampled, and the exchange grid uses the edited wet set; also an addition.  ``remap_source`` (--remap_source FILE): the
+    variables ``remap_var`` of that lat-lon file remapped conservatively onto the model cells (remap.py; wet cells only when
+    ``topog_source`` is given, the exchange grid's wet set; the wet cells the source leaves empty filled unless ``remap_no_fill``, at
+    most ``remap_fill_max`` cells away), written to ``remap_file``; also an addition."""
     import time
 
     path = path or os.environ.get("OGG_MAIN_PATH", "pass")
@@ -677,11 +681,13 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
                                    match_dy, skip_metrics, ensure_nj_even, shift_equator_to_u_point, bipolar_lower_lat, mercator_lower_lat,
                                    mercator_upper_lat, south_ocean_lower_lat, south_ocean_upper_lat, no_south_cap, return_arrays, dp_arc,
                                    cap_symmetry, quality_report, topog_source, topog_var, topog_file, topog_refine, xgrid_atm,
-                                   xgrid_file, ocean_mask_file, mask_min_depth, mask_deepen, mask_seed, mask_keep_cells)
+                                   xgrid_file, ocean_mask_file, mask_min_depth, mask_deepen, mask_seed, mask_keep_cells,
+                                   remap_source, remap_var, remap_file, remap_no_fill, remap_fill_max)
     from . import supergrid as SG
 
     _validate_flags(match_dy, r_dp, lat_dp)
     _validate_mask_flags(ocean_mask_file, topog_source)
+    _validate_remap_flags(remap_source, remap_var)
     hist, source, desc = _meta_strings(inverse_resolution, no_changing_meta)
     start_time = time.time()
     plan = SG.SupergridPlan(inverse_resolution, r_dp=r_dp, lon_dp=lon_dp, lat_dp=lat_dp, exfracdp=exfracdp, south_cutoff_row=south_cutoff_row,
@@ -720,6 +726,9 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     if xgrid_atm is not None:
         from . import exchange_grid as X
         _write_xgrid(g.exchange_grid(cut, X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo)), xgrid_file)
+    if remap_source is not None:
+        _write_remap([(src, g.remap(cut, src, mask=_xgrid_mask(topo), fill=not remap_no_fill, fill_max=remap_fill_max))
+                      for src in _remap_sources(remap_source, remap_var)], remap_file)
     print("Stitching the grids together...")
     SG.check_guards(g.stitched_column("y", plan.Ni // 4, cut), any(s.name == "BP" for s in plan.subs))
     names = [s.name for s in plan.subs if not (s.name == "SC" and cut[2])]
@@ -788,13 +797,15 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
                         return_arrays=False, dp_arc=None, cap_symmetry=None, quality_report=None, topog_source=None,
                         topog_var="elevation", topog_file="topog.nc", topog_refine=None, xgrid_atm=None,
                         xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0,
-                        mask_deepen=False, mask_seed=None, mask_keep_cells=0):
+                        mask_deepen=False, mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None,
+                        remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None):
     """The reference's own sequence of calls (OGG:855-1449), every callee a host-array function of this module (numpy in, numpy
     out, one staged device call each) and the stitching on the host: what a user gets who swaps the reference's module for this
     one function by function.  main() produces the same bits from one device-resident pass."""
     import time
 
     _validate_mask_flags(ocean_mask_file, topog_source)
+    _validate_remap_flags(remap_source, remap_var)
     known_options = ["bp", "so", "p125sc", ""]
     unknown = list(set(match_dy).difference(known_options))
     if len(unknown) != 0:
@@ -1023,6 +1034,10 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
     if xgrid_atm is not None:   # the same list as the device pass gives, through the host-pointer entry
         from . import exchange_grid as X
         _write_xgrid(X.exchange_grid(x3, y3, *X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo), Re=_default_Re), xgrid_file)
+    if remap_source is not None:   # the same values as the device pass gives, through the host-pointer entries
+        from . import remap as R
+        _write_remap([(src, R.remap(x3, y3, src, mask=_xgrid_mask(topo), fill=not remap_no_fill, fill_max=remap_fill_max, Re=_default_Re))
+                      for src in _remap_sources(remap_source, remap_var)], remap_file)
 
     if write_subgrid_files:
         if "SC" in sub:
@@ -1106,6 +1121,11 @@ def _validate_mask_flags(ocean_mask_file, topog_source):
         raise ValueError("--ocean_mask_file needs --topog_source: the ocean mask is made from the topography")
 
 
+def _validate_remap_flags(remap_source, remap_var):
+    if remap_source is not None and not remap_var:
+        raise ValueError("--remap_source needs at least one --remap_var")
+
+
 def _mask_args(min_depth, deepen, seeds, keep_cells):
     return dict(min_depth=float(min_depth or 0.0), mode="deepen" if deepen else "mask", seeds=[tuple(s) for s in (seeds or ())],
                 keep_min_cells=int(keep_cells or 0))
@@ -1137,6 +1157,24 @@ def _write_xgrid(res, fnam):
     for line in X.summary_lines(res):
         print(line)
     X.write_xgrid(str(fnam), res)
+
+
+def _remap_sources(path, names):
+    from . import remap as R
+    out = []
+    for name in names:
+        src = R.read_source(str(path), name)
+        print(src.note)
+        out.append(src)
+    return out
+
+
+def _write_remap(results, fnam):
+    from . import remap as R
+    for _, res in results:
+        for line in R.summary_lines(res):
+            print(line)
+    R.write_remapped(str(fnam), results)
 
 
 def build_parser():
@@ -1204,6 +1242,15 @@ def build_parser():
     parser.add_argument("--mask_seed", type=float, nargs=2, action="append", required=False, default=None, metavar=("LON", "LAT"),
                         help="a point in the open ocean (repeatable): every basin holding one is kept (default: the largest basin)")
     parser.add_argument("--mask_keep_cells", type=int, required=False, default=0, help="also keep every basin of at least N cells")
+    parser.add_argument("--remap_source", type=str, required=False, default=None,
+                        help="a global lat-lon file (NetCDF classic / 64-bit offset) whose --remap_var variables are remapped "
+                             "conservatively onto the model cells into --remap_file (wet cells only when --topog_source is given)")
+    parser.add_argument("--remap_var", type=str, action="append", required=False, default=None,
+                        help="a variable of --remap_source (repeatable)")
+    parser.add_argument("--remap_file", type=str, required=False, default="remapped.nc", help="remap output file, default remapped.nc")
+    parser.add_argument("--remap_no_fill", action="store_true", help="leave wet cells the source does not cover unfilled")
+    parser.add_argument("--remap_fill_max", type=int, required=False, default=None,
+                        help="fill wet cells at most N cells away from a remapped cell (default: no limit)")
     return parser
 
 

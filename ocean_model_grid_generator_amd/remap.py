@@ -1,0 +1,380 @@
+"""Conservative remap: fields on a global lat-lon grid (temperature and salinity climatologies, monthly SST, chlorophyll, tides) put on
+the model cells of a supergrid, first-order conservatively, with the wet cells the source leaves empty filled from their neighbours.
+include/ogg_hip.h, "Conservative remap", gives the definition; the reference has no such step.
+
+The weights are the exchange list of exchange_grid.py between the source's cell edges and the model cells.  The segmented, masked,
+weighted sums and the fill run on the device (ogg_remap_segments_dev / ogg_remap_dev / ogg_remap_fill_dev, or the host-pointer
+ogg_remap); every value is a fixed function of the list, the source and values at smaller fill distance, so the result is
+bit-identical for any launch geometry and any number of ranks.
+
+    python -m ocean_model_grid_generator_amd.remap ocean_hgrid.nc SOURCE --var V [--var V2 ...] [--topog topog.nc | --mask ocean_mask.nc]
+        [--no_fill] [--fill_max N] -o remapped.nc [--json summary.json]
+
+SOURCE is a NetCDF classic / 64-bit-offset file; each variable's last two dimensions are latitude and longitude (either order) on
+uniform 1-D coordinates spanning 360 degrees of longitude; every dimension ahead of them is a record dimension.
+"""
+import argparse
+import ctypes
+import json
+import sys
+
+import numpy as np
+
+from . import _lib as L
+from . import exchange_grid as X
+from . import netcdf3
+
+FILL = L.REMAP_FILL
+FLAG_NAMES = ("dry", "remapped", "filled", "unfilled")
+CDF2_VAR_LIMIT = (1 << 32) - 4      # bytes of one fixed-size variable of a 64-bit-offset file
+_DTYPES = {np.dtype(np.float32): L.REMAP_FLOAT32, np.dtype(np.float64): L.REMAP_FLOAT64}
+
+
+# ---- sources -------------------------------------------------------------------------------------------------
+class Source(object):
+    """A field on a global rectilinear grid: data (..., NB, NA), float32 or float64, row 0 southmost; its cell edges lon (NA + 1,
+    spanning 360 degrees) and lat (NB + 1, increasing, inside [-90, 90]); the values that mark missing (``fill``, at most two, in
+    the data's type; NaN is always missing); the leading dimensions [(name, length)] and their coordinate variables [(name, nc type,
+    attributes, values)] for the writer; ``note`` says how the grid was read."""
+
+    def __init__(self, data, lon_edges, lat_edges, fill=(), name="field", lead_dims=None, coords=(), atts=(), note=""):
+        data = np.asarray(data)
+        if data.ndim < 2 or data.dtype.newbyteorder("=") not in _DTYPES:
+            raise ValueError("remap source: a float32 or float64 array of two or more dimensions is needed, not %s %s" % (data.dtype, data.shape))
+        self.data = np.ascontiguousarray(data, dtype=data.dtype.newbyteorder("="))
+        self.lon, self.lat = X.atm_edges(lon_edges, lat_edges)
+        if self.data.shape[-2:] != (self.lat.size - 1, self.lon.size - 1):
+            raise ValueError("remap source: data %s and %d x %d cells (lat x lon edges - 1)" % (self.data.shape, self.lat.size - 1, self.lon.size - 1))
+        self.fill = tuple(self.data.dtype.type(f) for f in fill)
+        if len(self.fill) > L.REMAP_MAX_FILLS:
+            raise ValueError("remap source: at most %d fill values" % L.REMAP_MAX_FILLS)
+        self.name = name
+        lead = self.data.shape[:-2]
+        self.lead_dims = list(lead_dims) if lead_dims is not None else [("record%d" % k, n) for k, n in enumerate(lead)]
+        self.coords, self.atts, self.note = list(coords), list(atts), note
+
+    @property
+    def nrec(self):
+        return int(np.prod(self.data.shape[:-2], dtype=np.int64))
+
+    @property
+    def records(self):
+        """the data as (nrec, NB, NA)"""
+        return self.data.reshape((self.nrec,) + self.data.shape[-2:])
+
+
+def _num(atts, key):
+    v = atts.get(key)
+    return None if v is None or isinstance(v, str) else float(np.asarray(v).reshape(-1)[0])
+
+
+class _Last2(object):
+    """the last two dimensions of a variable, as topography's dimension helper reads them"""
+
+    def __init__(self, v):
+        self.name, self.dims = v.name, v.dims[-2:]
+
+
+def read_source(path, var):
+    """A Source from a NetCDF classic (CDF-1) or 64-bit-offset (CDF-2) file: the byte / short / float / double variable ``var``,
+    whose last two dimensions are latitude and longitude in either order (told apart by the coordinates' units or names, as for
+    topography), on uniform 1-D coordinates (cell centres or edges).  Latitude edges at centres +- half a step are clamped to +-90;
+    rows are flipped when latitude decreases.  A byte or short variable is unpacked to float64 as raw * scale_factor + add_offset,
+    with missing values (_FillValue, missing_value, tested on the raw values) as NaN; float and double keep their type and their fill
+    values.  CDF-5 and NetCDF-4 / HDF5 files are refused."""
+    from . import topography as T
+    try:
+        h = netcdf3.read_header(path)
+    except ValueError as e:
+        if "CDF-5" in str(e) or "HDF5" in str(e):
+            raise ValueError("%s: only NetCDF classic / 64-bit-offset sources are read; %s" % (str(e).split(";")[0], T._NCCOPY))
+        raise
+    if var not in h.vars:
+        raise KeyError("%s: no variable %r (variables: %s); choose one with --var" % (path, var, ", ".join(sorted(h.vars))))
+    v = h.vars[var]
+    if v.nc_type not in (netcdf3.NC_BYTE, netcdf3.NC_SHORT, netcdf3.NC_FLOAT, netcdf3.NC_DOUBLE) or len(v.shape) < 2:
+        raise ValueError("%s: %s must be a byte, short, float or double variable of two or more dimensions (type %d, shape %s)"
+                         % (path, var, v.nc_type, v.shape))
+    if v.is_record:
+        raise ValueError("%s: %s is a record (unlimited) variable; only fixed-size variables are read" % (path, var))
+    lat_name, lon_name = T._lat_lon_dims(path, h, _Last2(v))
+    axes = {}
+    for dname in (lat_name, lon_name):
+        if dname not in h.vars:
+            raise ValueError("%s: no coordinate variable for dimension %s of %s" % (path, dname, var))
+        cv = h.vars[dname]
+        raw = netcdf3.read_var_bytes(path, h, dname, dtype=cv.nc_type)
+        axes[dname] = T._uniform_axis(path, dname, np.frombuffer(raw, dtype=netcdf3.NUMPY_DTYPE[cv.nc_type]))
+    data = np.frombuffer(netcdf3.read_var_bytes(path, h, var, dtype=v.nc_type), dtype=netcdf3.NUMPY_DTYPE[v.nc_type]).reshape(v.shape)
+    data = data.astype(data.dtype.newbyteorder("="))
+    if v.dims[-2] == lon_name:   # stored (..., lon, lat)
+        data = np.swapaxes(data, -1, -2)
+    (lat, dlat), (lon, dlon) = axes[lat_name], axes[lon_name]
+    if dlon < 0:
+        raise ValueError("%s: longitude %s decreases" % (path, lon_name))
+    if dlat < 0:
+        data, lat, dlat = data[..., ::-1, :], lat[::-1], -dlat
+    NB, NA = data.shape[-2:]
+    if abs(NA * dlon - 360.0) > 1e-9 * 360.0:
+        raise ValueError("%s: %s covers %.10g degrees of longitude (%d x %.10g); the remap needs a global source (360 degrees)"
+                         % (path, var, NA * dlon, NA, dlon))
+    lon0, kind_lon = T._edges(lon[0], dlon)
+    if min(abs(lat[0] - 0.5 * dlat + 90.0), abs(lat[-1] + 0.5 * dlat - 90.0)) <= 1e-6 * dlat:
+        lat0, kind_lat = lat[0] - 0.5 * dlat, "centres"   # centres whose half-step edges reach a pole
+    else:
+        lat0, kind_lat = T._edges(lat[0], dlat)
+    lon_edges = lon0 + dlon * np.arange(NA + 1)
+    lon_edges[-1] = lon_edges[0] + 360.0
+    lat_edges = np.clip(lat0 + dlat * np.arange(NB + 1), -90.0, 90.0)
+    for k, pole in ((0, -90.0), (NB, 90.0)):   # an edge within rounding of a pole is the pole
+        if abs(lat_edges[k] - pole) <= 1e-6 * dlat:
+            lat_edges[k] = pole
+    fills = []
+    for k in ("_FillValue", "missing_value"):
+        fv = _num(v.atts, k)
+        if fv is not None and fv not in fills:
+            fills.append(fv)
+    if v.nc_type in (netcdf3.NC_BYTE, netcdf3.NC_SHORT):
+        scale, offset = _num(v.atts, "scale_factor"), _num(v.atts, "add_offset")
+        miss = np.zeros(data.shape, dtype=bool)
+        for fv in fills:
+            miss |= data == data.dtype.type(fv)
+        out = data.astype(np.float64) * (1.0 if scale is None else scale) + (0.0 if offset is None else offset)
+        out[miss] = np.nan
+        data, fills = out, []
+    lead = [(d, n) for d, n in zip(v.dims[:-2], v.shape[:-2])]
+    coords = []
+    for d, _ in lead:
+        cv = h.vars.get(d)
+        if cv is not None and len(cv.shape) == 1 and not cv.is_record and cv.nc_type != netcdf3.NC_CHAR:
+            vals = np.frombuffer(netcdf3.read_var_bytes(path, h, d, dtype=cv.nc_type), dtype=netcdf3.NUMPY_DTYPE[cv.nc_type])
+            atts = [(k, a if isinstance(a, str) else np.asarray(a).reshape(-1)[0].item()) for k, a in cv.atts.items()
+                    if isinstance(a, str) or np.asarray(a).size == 1]
+            coords.append((d, cv.nc_type, atts, vals))
+    keep = [(k, a) for k, a in v.atts.items() if k in ("units", "long_name", "standard_name") and isinstance(a, str)]
+    note = "%s: %s %s, %d records of %d x %d cells, longitude coordinates taken as cell %s, latitude as cell %s" % (
+        path, var, tuple(v.dims), int(np.prod(v.shape[:-2], dtype=np.int64)), NB, NA, kind_lon, kind_lat)
+    return Source(data, lon_edges, lat_edges, fill=fills, name=var, lead_dims=lead, coords=coords, atts=keep, note=note)
+
+
+# ---- arguments -----------------------------------------------------------------------------------------------
+def params(ny, nx, source, m0=0, periodic=False, fold=False, fill_max=None):
+    """an ogg_remap_params, checked by the library (OGG_EARG -> ValueError)"""
+    from . import ocean_mask as M
+    p = L.RemapParams(ny=int(ny), nx=int(nx), m0=int(m0), NA=source.lon.size - 1, NB=source.lat.size - 1, nrec=source.nrec,
+                      dtype=_DTYPES[source.data.dtype], n_fill=len(source.fill), topology=M.topology_flags(periodic, fold),
+                      fill_max=-1 if fill_max is None else int(fill_max))
+    for k, f in enumerate(source.fill):
+        p.fill[k] = float(f)
+    if fill_max is not None and int(fill_max) < 0:
+        raise ValueError("remap: fill_max must be >= 0 (%r)" % (fill_max,))
+    if L.load().ogg_remap_check(ctypes.byref(p)) != L.OGG_OK:
+        raise ValueError(L.load().ogg_last_error().decode())
+    return p
+
+
+def _mask(mask, shape):
+    if mask is None:
+        return None
+    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    if m.shape != shape:
+        raise ValueError("remap: the mask is %s, the model cells %s" % (m.shape, shape))
+    return m
+
+
+def counts_dict(c):
+    return {f: int(c[k]) for k, f in enumerate(L.REMAP_COUNT_FIELDS)}
+
+
+def result(values, flags, counts, source, periodic, fold, fill, fill_max, masked):
+    """What remap() returns: values and flags (lead dims of the source, ny, nx), the counts and a summary."""
+    if counts["bad_entries"]:
+        raise ValueError("remap: %d list entries lie outside the cells or the source: the list belongs to other edges or rows"
+                         % counts["bad_entries"])
+    shape = tuple(source.data.shape[:-2]) + values.shape[-2:]
+    summary = dict(counts, var=source.name, records=source.nrec, source_shape=[source.lat.size - 1, source.lon.size - 1],
+                   shape=list(values.shape[-2:]), periodic=bool(periodic), fold=bool(fold), fill=bool(fill),
+                   fill_max=None if fill_max is None else int(fill_max), masked=bool(masked))
+    del summary["bad_entries"]
+    return {"values": values.reshape(shape), "flags": flags.reshape(shape), "counts": counts, "summary": summary}
+
+
+# ---- host arrays -----------------------------------------------------------------------------------------------
+def remap(x, y, source, lon_edges=None, lat_edges=None, mask=None, fill=True, fill_max=None, fill_values=(),
+          threshold=X.DEFAULT_THRESHOLD, Re=X.DEFAULT_RE):
+    """The conservative remap of ``source`` onto the model cells of a stitched supergrid x, y ((ny + 1) x (nx + 1), degrees; nx, ny
+    even), on one GPU through the host-pointer entries (ogg_xgrid for the list, ogg_remap for the rest).  ``source``: a Source, or an
+    array (..., NB, NA) with lon_edges, lat_edges and fill_values.  mask: None or one value per model cell (0: dry).  fill: fill
+    the wet cells the source leaves empty (up to fill_max steps, None: no limit).  A dict: values, flags (the source's leading
+    dimensions, then (ny / 2, nx / 2)), counts, summary."""
+    from . import ocean_mask as M
+    if not isinstance(source, Source):
+        source = Source(source, lon_edges, lat_edges, fill=fill_values)
+    x, y = L.as_f64(x), L.as_f64(y)
+    lists = X.exchange_grid(x, y, source.lon, source.lat, mask=mask, Re=Re, threshold=threshold)
+    shape = lists["a_poly"].shape
+    m = _mask(mask, shape)
+    periodic, fold = M.detect_topology(x, y, 2)
+    p = params(shape[0], shape[1], source, 0, periodic, fold, fill_max)
+    npair = source.nrec * shape[0] * shape[1]
+    values = np.empty(npair, dtype=np.float64)
+    flags = np.empty((npair + 3) // 4 * 4, dtype=np.uint8)
+    counts = L.RemapCounts()
+    atm, ocn, area = (np.ascontiguousarray(lists[k]) for k in ("atm", "ocn", "area"))
+    L.call("ogg_remap", ctypes.byref(p), source.records.ctypes.data, atm.ctypes.data, ocn.ctypes.data, area.ctypes.data, area.size,
+           None if m is None else m.ctypes.data, 1 if fill else 0, values.ctypes.data, flags.ctypes.data, ctypes.byref(counts))
+    c = {f: int(getattr(counts, f)) for f in L.REMAP_COUNT_FIELDS}
+    rs = (source.nrec,) + shape
+    return result(values.reshape(rs), flags[:npair].reshape(rs), c, source, periodic, fold, fill, fill_max, m is not None)
+
+
+# ---- device arrays ---------------------------------------------------------------------------------------------
+def flags_buffer(torch, n, device):
+    """n flag bytes in an allocation rounded up to 4 bytes (the fill changes them by 32-bit compare-and-swap)"""
+    return torch.empty((n + 3) // 4 * 4, dtype=torch.uint8, device=device)[:n]
+
+
+def piece_dev(p, f, atm, ocn, area, mask, stream, device):
+    """The segment and remap steps of one piece (device tensors: f (nrec, NB, NA), the piece's list, mask None or its rows' bytes):
+    values (nrec, rows, nx) float64, flags (nrec, rows, nx) uint8, counts (int64 device tensor of 8)."""
+    import torch
+    lib = L.load()
+    wsb = int(lib.ogg_remap_workspace_bytes(ctypes.byref(p)))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=device)
+    n = int(area.numel())
+    shape = (p.nrec, p.ny, p.nx)
+    values = torch.empty(shape, dtype=torch.float64, device=device)
+    flags = flags_buffer(torch, p.nrec * p.ny * p.nx, device).view(shape)
+    counts = torch.zeros(len(L.REMAP_COUNT_FIELDS), dtype=torch.int64, device=device)
+    L.call("ogg_remap_segments_dev", ctypes.byref(p), ocn.data_ptr() if n else None, n, ws.data_ptr(), wsb, stream)
+    L.call("ogg_remap_dev", ctypes.byref(p), f.data_ptr(), atm.data_ptr() if n else None, area.data_ptr() if n else None, n,
+           None if mask is None else mask.data_ptr(), ws.data_ptr(), wsb, values.data_ptr(), flags.data_ptr(), counts.data_ptr(), stream)
+    return values, flags, counts
+
+
+def fill_dev(p, values, flags, counts, stream, device):
+    """The fill step on the whole grid's values and flags (device tensors from piece_dev or gathered; flags in an allocation rounded
+    up to 4 bytes), in place; counts (int64 device tensor of 8) gets the fill's counts."""
+    import torch
+    wsb = int(L.load().ogg_remap_workspace_bytes(ctypes.byref(p)))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=device)
+    L.call("ogg_remap_fill_dev", ctypes.byref(p), ws.data_ptr(), wsb, values.data_ptr(), flags.data_ptr(), counts.data_ptr(), stream)
+
+
+def remap_dev(x, y, source, mask=None, fill=True, fill_max=None, threshold=X.DEFAULT_THRESHOLD, Re=X.DEFAULT_RE):
+    """remap() on one GPU with the grid x, y as float64 device tensors ((ny + 1) x (nx + 1), contiguous rows) and a Source: the
+    list, the segments, the remap and the fill all on the device, on its current stream.  The same dict as remap(), with host arrays."""
+    import torch
+    from . import ocean_mask as M
+    dev = x.device
+    x, y = x.contiguous(), y.contiguous()
+    nyp, nxp = x.shape
+    X.check_grid(nyp, nxp)
+    shape = ((nyp - 1) // 2, (nxp - 1) // 2)
+    m = _mask(mask, shape)
+    xs, ys = x[::2, ::2], y[::2, ::2]
+    periodic, fold = M.topology_of_edges(*[(xs[sl].cpu().numpy(), ys[sl].cpu().numpy())
+                                          for sl in ((slice(None), 0), (slice(None), -1), (-1, slice(None)))])
+    p = params(shape[0], shape[1], source, 0, periodic, fold, fill_max)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    lon, lat = torch.from_numpy(source.lon).to(dev), torch.from_numpy(source.lat).to(dev)
+    desc = L.XgridAtm(lon=lon.data_ptr(), lat=lat.data_ptr(), NA=lon.numel() - 1, NB=lat.numel() - 1)
+    band = L.XgridBand(nx=nxp - 1, ny=nyp - 1, j0=0, n_cell_rows=nyp - 1, Re=float(Re), threshold=float(threshold))
+    band.x, band.y = x.data_ptr(), y.data_ptr()
+    band.x_next, band.y_next = x[nyp - 1:].data_ptr(), y[nyp - 1:].data_ptr()
+    mt = None if m is None else torch.from_numpy(m).to(dev)
+    band.mask = None if mt is None else mt.data_ptr()
+    _, _, _, atm, ocn, area = X.band_lists_dev(band, desc, st, dev)
+    f = torch.from_numpy(source.records).to(dev)
+    values, flags, counts = piece_dev(p, f, atm, ocn, area, mt, st, dev)
+    if fill:
+        fill_dev(p, values, flags, counts, st, dev)
+    return result(values.cpu().numpy(), flags.cpu().numpy(), counts_dict(counts.cpu().numpy()), source, periodic, fold, fill, fill_max,
+                  m is not None)
+
+
+# ---- files -----------------------------------------------------------------------------------------------------
+def write_remapped(path, results, title="conservative remap onto the model cells"):
+    """One float64 variable per remapped field (its source's leading dimensions, then ny, nx; _FillValue FILL) and a byte variable
+    <var>_remap_flag (0 dry, 1 remapped, 2 filled, 3 unfilled), the leading coordinate variables copied from the source, as a
+    NetCDF 64-bit-offset file.  ``results``: [(Source, remap() result)]."""
+    dims, coords, seen = [], [], set()
+    for src, res in results:
+        for d, n in src.lead_dims:
+            if d in seen:
+                if dict(dims)[d] != n:
+                    raise ValueError("remap: dimension %s has length %d in one variable and %d in another" % (d, dict(dims)[d], n))
+                continue
+            seen.add(d)
+            dims.append((d, n))
+            coords += [c for c in src.coords if c[0] == d]
+        nbytes = int(np.prod(res["values"].shape, dtype=np.int64)) * 8
+        if nbytes > CDF2_VAR_LIMIT:
+            raise ValueError("remap: %s takes %d bytes, more than one variable of a NetCDF 64-bit-offset file can hold (%d); remap "
+                             "fewer records at a time" % (src.name, nbytes, CDF2_VAR_LIMIT))
+    ny, nx = results[0][1]["values"].shape[-2:]
+    dims += [("ny", ny), ("nx", nx)]
+    ds = netcdf3.Dataset(path, dims, global_atts=[("title", title), ("cells", "MOM6 model (h) cells: 2 x 2 supergrid cells"),
+                                                  ("flag_values", "0 dry, 1 remapped, 2 filled, 3 unfilled")])
+    for name, nc_type, atts, vals in coords:
+        ds.def_var(name, nc_type, (name,), atts, vals)
+    for src, res in results:
+        lead = tuple(d for d, _ in src.lead_dims)
+        ds.def_var(src.name, netcdf3.NC_DOUBLE, lead + ("ny", "nx"), list(src.atts) + [("_FillValue", FILL)], res["values"])
+        ds.def_var(src.name + "_remap_flag", netcdf3.NC_BYTE, lead + ("ny", "nx"),
+                   [("long_name", "remap flag of " + src.name), ("flag_meanings", "dry remapped filled unfilled")],
+                   res["flags"].astype(np.int8))
+    ds.write()
+
+
+def summary_lines(res):
+    s = res["summary"]
+    fill = ("%d filled (largest distance %d, %d fronts in %d launches)" % (s["filled"], s["max_distance"], s["fronts"], s["launches"])
+            if s["fill"] else "no fill")
+    return ["   remap: %s, %d records of %d x %d source cells onto %d x %d cells%s: %d remapped, %s, %d unfilled, %d dry"
+            % (s["var"], s["records"], s["source_shape"][1], s["source_shape"][0], s["shape"][1], s["shape"][0],
+               " (masked)" if s["masked"] else "", s["remapped"], fill, s["unfilled"], s["dry"])]
+
+
+def mask_from_file(path):
+    """the wet set of a topog.nc (depth > 0, exchange_grid.mask_from_topog) or of an ocean_mask.nc (mask != 0)"""
+    h = netcdf3.read_header(path)
+    if "mask" in h.vars and "depth" not in h.vars:
+        return (netcdf3.read_doubles(path, names=("mask",))["mask"] != 0).astype(np.uint8)
+    return X.mask_from_topog(path)
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(prog="python -m ocean_model_grid_generator_amd.remap",
+                                description="conservative remap of lat-lon fields onto the model cells of a supergrid file")
+    p.add_argument("grid", help="ocean_hgrid.nc (NetCDF classic / 64-bit offset)")
+    p.add_argument("source", help="the lat-lon source (NetCDF classic / 64-bit offset)")
+    p.add_argument("--var", action="append", required=True, help="a variable of the source (repeatable)")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--topog", default=None, help="topog.nc: cells with depth > 0 are wet")
+    g.add_argument("--mask", default=None, help="ocean_mask.nc: cells with mask != 0 are wet")
+    p.add_argument("--no_fill", action="store_true", help="leave wet cells the source does not cover unfilled")
+    p.add_argument("--fill_max", type=int, default=None, help="fill at most N cells away from a remapped cell")
+    p.add_argument("-o", "--output", default="remapped.nc")
+    p.add_argument("--json", default=None, help="write the summaries as JSON to this file")
+    a = p.parse_args(argv)
+    grid = netcdf3.read_doubles(a.grid, names=("x", "y"))
+    mask = mask_from_file(a.topog or a.mask) if (a.topog or a.mask) else None
+    out = []
+    for var in a.var:
+        src = read_source(a.source, var)
+        print(src.note)
+        res = remap(grid["x"], grid["y"], src, mask=mask, fill=not a.no_fill, fill_max=a.fill_max)
+        for line in summary_lines(res):
+            print(line)
+        out.append((src, res))
+    write_remapped(a.output, out)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump([r["summary"] for _, r in out], fh, indent=1)
+    return out
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)

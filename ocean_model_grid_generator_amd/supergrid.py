@@ -1472,6 +1472,60 @@ class Supergrid(object):
                                fill=T.FILL)
         return res
 
+    # -- conservative remap -------------------------------------------------------------------------------------------
+    def remap(self, cut, source, mask=None, fill=True, fill_max=None, threshold=1e-6):
+        """The conservative remap (remap.result on rank 0, None on the other ranks) of ``source`` (a remap.Source) onto the model cells
+        of the stitched grid.  ``mask``: None or one value per model cell (0: dry).  Every rank builds the lists of its own pieces
+        (xgrid_lists, the source's edges as the atmosphere) and remaps their cells on its GPU; rank 0 gathers the values, flags and
+        counts in piece order (_gather) and fills on its GPU with the topology of the stitched grid, as ocean_mask does.  Nothing is
+        summed across pieces, so the result is bit-identical for any number of ranks."""
+        from . import exchange_grid as X
+        from . import ocean_mask as M
+        from . import remap as R
+        torch = self.torch
+        nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
+        X.check_grid(nyp, nxp)
+        shape = ((nyp - 1) // 2, (nxp - 1) // 2)
+        hm = R._mask(mask, shape)
+        R.params(shape[0], shape[1], source, 0, False, False, fill_max)   # the checks, before any device work
+        nrec = source.nrec
+
+        def records(g):
+            to = lambda a: torch.from_numpy(a).to(g.device)   # noqa: E731
+            mt = None if hm is None else to(hm)
+            f = to(source.records)
+            out = []
+            for k, m0, _, a_poly, atm, ocn, area in g.xgrid_lists(cut, (to(source.lon), to(source.lat)), mt, threshold):
+                p = R.params(a_poly.shape[0], shape[1], source, m0)
+                rows = None if mt is None else mt[m0:m0 + a_poly.shape[0]]
+                out.append((k,) + R.piece_dev(p, f, atm, ocn, area, rows, g._stream(), g.device))
+            torch.cuda.synchronize(g.device)
+            return out
+
+        def recv(k, q, take):
+            _, rows, _ = self._xgrid_rows(q)
+            if rows == 0:
+                return None
+            return (k, take((nrec, rows, shape[1]), torch.float64), take((nrec, rows, shape[1]), torch.uint8),
+                    take(len(L.REMAP_COUNT_FIELDS), torch.int64))
+        got = self._gather(self.quality_pieces(cut), records, lambda e: (e[1].contiguous(), e[2].contiguous(), e[3]), recv)
+        xy = self.stitched_xy(cut)
+        if got is None:
+            return None
+        got.sort(key=lambda e: e[0])
+        values = torch.cat([e[1].to(self.device) for e in got], dim=1).contiguous()
+        flags = R.flags_buffer(torch, values.numel(), self.device).view(values.shape)
+        flags.copy_(torch.cat([e[2].to(self.device) for e in got], dim=1))
+        counts = torch.stack([e[3].to(self.device) for e in got]).sum(dim=0)
+        xs, ys = xy[0][::2, ::2], xy[1][::2, ::2]
+        periodic, fold = M.topology_of_edges(*[(xs[sl].cpu().numpy(), ys[sl].cpu().numpy())
+                                              for sl in ((slice(None), 0), (slice(None), -1), (-1, slice(None)))])
+        if fill:
+            p = R.params(shape[0], shape[1], source, 0, periodic, fold, fill_max)
+            R.fill_dev(p, values, flags, counts, self._stream(), self.device)
+        return R.result(values.cpu().numpy(), flags.cpu().numpy(), R.counts_dict(counts.cpu().numpy()), source, periodic, fold, fill,
+                        fill_max, hm is not None)
+
     def bands_to_host(self):
         """This rank's bands as numpy arrays (halo rows dropped): {sub: {field: array}}."""
         out = {}

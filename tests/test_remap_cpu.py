@@ -1,0 +1,236 @@
+"""CPU tests of the conservative remap: the NetCDF reader of remap.py on small files written here, the definition's own properties
+(tests/remap_definition.py), and the library's checks, struct sizes and refusals (no device work)."""
+import collections
+import ctypes
+
+import numpy as np
+import pytest
+
+import remap_definition as D
+
+
+def write(path, dims, variables):
+    from ocean_model_grid_generator_amd import netcdf3
+    ds = netcdf3.Dataset(str(path), dims)
+    for name, t, vd, atts, data in variables:
+        ds.def_var(name, t, vd, atts, data)
+    ds.write()
+    return str(path)
+
+
+def lonlat(nlon=8, nlat=4):
+    return -180.0 + (360.0 / nlon) * (np.arange(nlon) + 0.5), -90.0 + (180.0 / nlat) * (np.arange(nlat) + 0.5)
+
+
+# ---- reader ----------------------------------------------------------------------------------------------------
+def test_reader_time_depth_lat_lon_decreasing_latitude_and_fill(tmp_path):
+    from ocean_model_grid_generator_amd import netcdf3
+    from ocean_model_grid_generator_amd import remap as R
+    lon, lat = lonlat()
+    data = np.arange(2 * 3 * 4 * 8, dtype=np.float32).reshape(2, 3, 4, 8)
+    data[1, 2, 0, 0] = -999.0
+    path = write(tmp_path / "s.nc", [("time", 2), ("depth", 3), ("lat", 4), ("lon", 8)], [
+        ("time", netcdf3.NC_DOUBLE, ("time",), [("units", "days since 2000-01-01")], np.array([15.0, 45.0])),
+        ("depth", netcdf3.NC_DOUBLE, ("depth",), [("units", "m"), ("positive", "down")], np.array([5.0, 50.0, 500.0])),
+        ("lat", netcdf3.NC_DOUBLE, ("lat",), [("units", "degrees_north")], lat[::-1].copy()),
+        ("lon", netcdf3.NC_DOUBLE, ("lon",), [("units", "degrees_east")], lon),
+        ("temp", netcdf3.NC_FLOAT, ("time", "depth", "lat", "lon"), [("units", "degC"), ("_FillValue", -999.0)], data)])
+    s = R.read_source(path, "temp")
+    assert s.data.dtype == np.float32 and s.data.shape == (2, 3, 4, 8) and s.nrec == 6
+    np.testing.assert_array_equal(s.data, data[:, :, ::-1, :])        # rows flipped: row 0 southmost
+    assert s.fill == (np.float32(-999.0),)
+    assert s.lead_dims == [("time", 2), ("depth", 3)]
+    assert [c[0] for c in s.coords] == ["time", "depth"] and np.array_equal(s.coords[1][3], [5.0, 50.0, 500.0])
+    np.testing.assert_array_equal(s.lon, -180.0 + 45.0 * np.arange(9))
+    np.testing.assert_array_equal(s.lat, [-90.0, -45.0, 0.0, 45.0, 90.0])
+    assert ("units", "degC") in s.atts
+
+
+def test_reader_lon_lat_order_and_packed_shorts(tmp_path):
+    from ocean_model_grid_generator_amd import netcdf3
+    from ocean_model_grid_generator_amd import remap as R
+    lon, lat = lonlat()
+    raw = (np.arange(32, dtype=np.int16).reshape(8, 4) - 5)                 # stored (lon, lat)
+    raw[3, 1] = -32767
+    raw[4, 2] = 77
+    path = write(tmp_path / "p.nc", [("lon", 8), ("lat", 4)], [
+        ("lon", netcdf3.NC_DOUBLE, ("lon",), [("units", "degrees_east")], lon),
+        ("lat", netcdf3.NC_DOUBLE, ("lat",), [("units", "degrees_north")], lat),
+        ("sst", netcdf3.NC_SHORT, ("lon", "lat"), [("scale_factor", 0.01), ("add_offset", 20.0), ("_FillValue", -32767),
+                                                   ("missing_value", 77)], raw)])
+    s = R.read_source(path, "sst")
+    assert s.data.dtype == np.float64 and s.data.shape == (4, 8) and s.fill == ()
+    want = raw.T.astype(np.float64) * 0.01 + 20.0
+    want[1, 3] = want[2, 4] = np.nan
+    np.testing.assert_array_equal(s.data, want)
+
+
+def test_reader_clamps_polar_edges(tmp_path):
+    from ocean_model_grid_generator_amd import netcdf3
+    from ocean_model_grid_generator_amd import remap as R
+    dlat = 180.0 / 7
+    lat = -90.0 + dlat * (np.arange(7) + 0.5)
+    lon = 360.0 / 5 * np.arange(5) + 36.0
+    path = write(tmp_path / "c.nc", [("latitude", 7), ("longitude", 5)], [
+        ("latitude", netcdf3.NC_DOUBLE, ("latitude",), [], lat), ("longitude", netcdf3.NC_DOUBLE, ("longitude",), [], lon),
+        ("chl", netcdf3.NC_DOUBLE, ("latitude", "longitude"), [], np.ones((7, 5)))])
+    s = R.read_source(path, "chl")
+    assert s.lat[0] == -90.0 and s.lat[-1] == 90.0 and np.all(np.diff(s.lat) > 0)
+    assert s.lon[0] == 0.0 and s.lon[-1] == 360.0
+
+
+def test_reader_refuses_regional_longitude_and_hdf5(tmp_path):
+    from ocean_model_grid_generator_amd import netcdf3
+    from ocean_model_grid_generator_amd import remap as R
+    lon, lat = 22.5 * np.arange(8) + 11.25, lonlat()[1]       # 180 degrees of longitude
+    path = write(tmp_path / "r.nc", [("lat", 4), ("lon", 8)], [
+        ("lat", netcdf3.NC_DOUBLE, ("lat",), [("units", "degrees_north")], lat),
+        ("lon", netcdf3.NC_DOUBLE, ("lon",), [("units", "degrees_east")], lon),
+        ("v", netcdf3.NC_DOUBLE, ("lat", "lon"), [], np.zeros((4, 8)))])
+    with pytest.raises(ValueError, match="global source"):
+        R.read_source(path, "v")
+    h5 = tmp_path / "h.nc"
+    h5.write_bytes(b"\x89HDF\r\n\x1a\n" + b"\0" * 64)
+    with pytest.raises(ValueError, match="HDF5.*nccopy"):
+        R.read_source(str(h5), "v")
+
+
+# ---- the definition ----------------------------------------------------------------------------------------------
+def synthetic_list(ny, nx, NB, NA, seed=0):
+    """a list sorted by cell: every cell takes 0 .. 5 random source cells with random positive areas"""
+    rng = np.random.default_rng(seed)
+    atm, ocn, area = [], [], []
+    for c in range(ny * nx):
+        for _ in range(rng.integers(0, 6) if c % 7 else 40):
+            atm.append((rng.integers(0, NA), rng.integers(0, NB)))
+            ocn.append((c % nx, c // nx))
+            area.append(rng.uniform(1e6, 1e9))
+    return np.array(atm, np.int32), np.array(ocn, np.int32), np.array(area)
+
+
+def test_constant_field_stays_constant_and_sums_are_conserved():
+    atm, ocn, area = synthetic_list(6, 10, 5, 9)
+    f = np.full((2, 5, 9), 3.7)
+    v, fl = D.remap(atm, ocn, area, f, 6, 10)
+    rem = fl == D.REMAPPED
+    assert rem.sum() > 0 and np.all(np.abs(v[rem] / 3.7 - 1) <= 1e-14)
+    g = np.random.default_rng(1).normal(size=(2, 5, 9))
+    v, fl = D.remap(atm, ocn, area, g, 6, 10)
+    W = np.bincount(ocn[:, 1].astype(np.int64) * 10 + ocn[:, 0], weights=area, minlength=60).reshape(6, 10)
+    for r in range(2):
+        lhs = np.sum(np.where(fl[r] == D.REMAPPED, v[r], 0.0) * W)
+        rhs = np.sum(area * g[r, atm[:, 1], atm[:, 0]])
+        assert abs(lhs - rhs) <= 1e-12 * np.sum(np.abs(area * g[r, atm[:, 1], atm[:, 0]]))
+
+
+def bfs_fill(values, flags, periodic, fold):
+    """the fill, one cell at a time with a queue: an independent statement of the definition"""
+    nrec, ny, nx = values.shape
+    v, fl = values.copy(), flags.copy()
+    nb = D.neighbours(ny, nx, periodic, fold)
+    for r in range(nrec):
+        vr, fr = v[r].reshape(-1), fl[r].reshape(-1)
+        dist = {c: 0 for c in range(ny * nx) if fr[c] == D.REMAPPED}
+        q = collections.deque(sorted(dist))
+        while q:
+            c = q.popleft()
+            for d in range(4):
+                n = int(nb[d][c])
+                if n >= 0 and n not in dist and fr[n] == D.UNFILLED:
+                    dist[n] = dist[c] + 1
+                    q.append(n)
+        for c in sorted((c for c in dist if dist[c] > 0), key=lambda c: dist[c]):
+            s, m = 0.0, 0
+            for d in range(4):
+                n = int(nb[d][c])
+                if n >= 0 and dist.get(n, -1) == dist[c] - 1:
+                    s += float(vr[n])
+                    m += 1
+            vr[c] = s / m
+            fr[c] = D.FILLED
+    return v, fl
+
+
+def test_fill_hand_worked_periodic_and_folded():
+    v = np.full((1, 4, 6), D.FILL)
+    fl = np.full((1, 4, 6), D.UNFILLED, np.uint8)
+    for (j, i), val in (((0, 0), 1.0), ((0, 2), 4.0), ((3, 5), 10.0)):
+        v[0, j, i], fl[0, j, i] = val, D.REMAPPED
+    fl[0, 2, 2], v[0, 2, 2] = D.DRY, D.FILL
+    got, gfl, dmax = D.fill(v, fl, periodic=True, fold=True)
+    g = got[0]
+    assert g[0, 1] == 2.5          # W 1, E 4
+    assert g[0, 3] == 4.0 and g[0, 5] == 1.0 and g[1, 0] == 1.0 and g[1, 2] == 4.0   # (0, 5): E across the seam
+    assert g[3, 0] == 10.0         # W across the seam and N through the fold: the same cell twice
+    assert g[3, 4] == 10.0 and g[2, 5] == 10.0
+    assert g[1, 1] == 2.5          # distance 2: S 2.5, W 1, E 4
+    assert gfl[0, 2, 2] == D.DRY and g[2, 2] == D.FILL and np.all(gfl[0][fl[0] == D.UNFILLED] == D.FILLED)
+    want, wfl = bfs_fill(v, fl, True, True)
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(gfl, wfl)
+    # without the seam and the fold, and a fill limit of one step
+    got2, gfl2, d2 = D.fill(v, fl, periodic=False, fold=False, fill_max=1)
+    assert d2 == 1 and gfl2[0, 0, 3] == D.FILLED and got2[0, 0, 3] == 4.0 and got2[0, 2, 5] == 10.0
+    assert gfl2[0, 0, 5] == gfl2[0, 1, 1] == D.UNFILLED and got2[0, 0, 5] == got2[0, 1, 1] == D.FILL   # distance 2 without the seam
+    w2, _ = bfs_fill(v, fl, False, False)
+    done = gfl2[0] == D.FILLED
+    np.testing.assert_array_equal(got2[0][done], w2[0][done])
+    assert dmax == 3
+
+
+def test_unreachable_wet_cell_stays_unfilled():
+    v = np.full((1, 3, 4), D.FILL)
+    fl = np.full((1, 3, 4), D.UNFILLED, np.uint8)
+    v[0, 0, 0], fl[0, 0, 0] = 5.0, D.REMAPPED
+    fl[0, 1, :], fl[0, 2, :2] = D.DRY, D.DRY
+    got, gfl, _ = D.fill(v, fl, periodic=False, fold=False)
+    assert np.all(gfl[0, 0, 1:] == D.FILLED) and np.all(gfl[0, 2, 2:] == D.UNFILLED) and np.all(got[0, 2, 2:] == D.FILL)
+
+
+# ---- the library's checks ---------------------------------------------------------------------------------------
+def test_struct_sizes_and_refusals():
+    from ocean_model_grid_generator_amd import _lib as L
+    lib = L.load()
+    assert lib.ogg_remap_struct_bytes(L.REMAP_PARAMS) == ctypes.sizeof(L.RemapParams) == 80
+    assert lib.ogg_remap_struct_bytes(L.REMAP_COUNTS) == ctypes.sizeof(L.RemapCounts) == 64
+    assert lib.ogg_remap_struct_bytes(7) == -1
+
+    def p(**kw):
+        d = dict(ny=4, nx=6, m0=0, NA=8, NB=4, nrec=2, dtype=L.REMAP_FLOAT64, n_fill=1, topology=3, fill_max=-1)
+        d.update(kw)
+        return L.RemapParams(**d)
+
+    assert lib.ogg_remap_check(ctypes.byref(p())) == L.OGG_OK
+    assert lib.ogg_remap_workspace_bytes(ctypes.byref(p())) > 0
+    for bad, text in ((dict(ny=0), b"cells"), (dict(dtype=7), b"dtype"), (dict(n_fill=3), b"fill values"), (dict(topology=8), b"topology"),
+                      (dict(nrec=1 << 20, ny=4096, nx=4096), b"2^32"), (dict(NA=0), b"source cells"), (dict(m0=-1), b"first row")):
+        q = p(**bad)
+        assert lib.ogg_remap_check(ctypes.byref(q)) == L.OGG_EARG and text in lib.ogg_last_error(), bad
+        assert lib.ogg_remap_workspace_bytes(ctypes.byref(q)) == -1
+        # every step refuses the same before any device work (the pointers are never dereferenced)
+        assert lib.ogg_remap_dev(ctypes.byref(q), 8, 8, 8, 1, None, 8, 1 << 30, 8, 8, 8, None) == L.OGG_EARG
+        assert lib.ogg_remap_segments_dev(ctypes.byref(q), 8, 1, 8, 1 << 30, None) == L.OGG_EARG
+        assert lib.ogg_remap_fill_dev(ctypes.byref(q), 8, 1 << 30, 8, 8, 8, None) == L.OGG_EARG
+    q = p()
+    assert lib.ogg_remap_dev(ctypes.byref(q), 8, 8, 8, 1, None, 8, 16, 8, 8, 8, None) == L.OGG_EARG     # workspace too small
+    assert b"workspace" in lib.ogg_last_error()
+    assert lib.ogg_remap_fill_dev(ctypes.byref(p(m0=2)), 8, 1 << 40, 8, 8, 8, None) == L.OGG_EARG
+    assert b"whole grid" in lib.ogg_last_error()
+
+
+def test_python_arguments_are_checked():
+    from ocean_model_grid_generator_amd import remap as R
+    with pytest.raises(ValueError, match="spanning|360|lon edges"):
+        R.Source(np.zeros((2, 3)), [0.0, 100.0, 200.0, 300.0], [-90.0, 0.0, 90.0])
+    s = R.Source(np.zeros((2, 3), np.float32), [0.0, 120.0, 240.0, 360.0], [-90.0, 0.0, 90.0], fill=(1e20,))
+    with pytest.raises(ValueError, match="fill_max"):
+        R.params(4, 6, s, fill_max=-2)
+    with pytest.raises(ValueError, match="at most 2"):
+        R.Source(np.zeros((2, 3)), [0.0, 120.0, 240.0, 360.0], [-90.0, 0.0, 90.0], fill=(1.0, 2.0, 3.0))
+
+
+def test_main_refuses_a_source_without_variables():
+    from ocean_model_grid_generator_amd import ocean_grid_generator as ogg
+    for path in ("pass", "functions"):
+        with pytest.raises(ValueError, match="remap_var"):
+            ogg.main(1.0, gridfilename=None, ensure_nj_even=True, remap_source="src.nc", path=path)
