@@ -783,6 +783,86 @@ int ogg_remap_fill_dev(const ogg_remap_params* p, void* workspace, long workspac
 int ogg_remap(const ogg_remap_params* p, const void* f, const int* atm_ij, const int* ocn_ij, const double* area, long n_entries,
               const unsigned char* mask, int do_fill, double* values, unsigned char* flags, ogg_remap_counts* counts);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Runoff mapping (an addition: the reference has none).  The discharge of every source cell of a global lat-lon runoff field moved to
+ * the nearest wet coastal cell of the model grid, conserving the mass flux, as MOM6 set-ups do with river runoff and calving.
+ *   cells    the ny x nx model cells of the stitched grid, c = j * nx + i.  Wet set: one byte per cell (0: land), depth > 0 of a
+ *            topography or mask != 0 of an ocean mask.  Centre: supergrid point (2j+1, 2i+1), as the mask's seeds.  Area:
+ *            A_c = (a[2j][2i] + a[2j+1][2i+1]) + (a[2j][2i+1] + a[2j+1][2i]) of the supergrid area (2 ny x 2 nx), fp64, in this order.
+ *   targets  OGG_RUNOFF_COAST: the wet cells with at least one face neighbour that is land or does not exist; face neighbours are
+ *            i +- 1 (with OGG_MASK_PERIODIC, (j, nx-1) ~ (j, 0)), j +- 1, and on the top row with OGG_MASK_FOLD the partner
+ *            (ny-1, nx-1-i) (the ocean mask's topology).  OGG_RUNOFF_WET: every wet cell.  The target list is in ascending c.
+ *   sources  edges lon (NA + 1) and lat (NB + 1) as ogg_xgrid_check_atm accepts them; values f[r][J][I], r < nrec, float32 or fp64,
+ *            MISSING when NaN or equal to one of n_fill <= 2 fill values (compared in the source's type), as for the remap.  A
+ *            source cell is MAPPED when some record holds a value there that is neither missing nor zero; every other source cell
+ *            contributes nothing (SKIPPED when it has a non-missing value, MISSING when it has none).  Centre
+ *            ((a_I + a_I+1) / 2, (b_J + b_J+1) / 2); area A_s = (Re * Re) * (a_I+1 * D - a_I * D) * ds_J, left to right, ds_J as
+ *            for A_atm of the exchange grid.
+ *   nearest  unit vectors u = (cos phi cos lam, cos phi sin lam, sin phi), lam = lon * D, phi = lat * D (D = pi / 180, one fp64
+ *            constant); d2 = (dx * dx + dy * dy) + dz * dz, d = u_s - u_t, no FMA.  Every mapped source goes to the target with
+ *            the smallest (d2, c): ties to the smaller cell.  The answer is a function of the unit vectors alone: the search index
+ *            (OGG_RUNOFF_BINS, OGG_RUNOFF_BRUTE) changes no bit.  No target while a source is mapped: OGG_EARG.
+ *   values   for cell c and record r, the mapped sources s with target c in ASCENDING s: S = sum (f_s * A_s), left to right from
+ *            +0.0, missing values skipped, each product rounded before it is added; value S / A_c.  Every cell without a source,
+ *            land included, is +0.0.  n_sources[c]: the number of mapped sources of c.
+ * Nothing is summed across cells in an order that depends on the launch, so the result is BIT-IDENTICAL for any launch geometry and,
+ * on the gathered grid, for any rank count.  Output layout: values (nrec, ny, nx) fp64, record-major; n_sources (ny, nx) int32.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { OGG_RUNOFF_COAST = 0, OGG_RUNOFF_WET = 1 };
+enum { OGG_RUNOFF_PARAMS = 0, OGG_RUNOFF_COUNTS = 1 };
+#define OGG_RUNOFF_MAX_BINS 160   /* the largest OGG_RUNOFF_BINS: cubes per axis of the search index */
+/* ny * nx < 2^31, NA * NB < 2^31, nrec * ny * nx < 2^32, nrec * NA * NB < 2^40 */
+typedef struct ogg_runoff_params {
+    long ny, nx;               /* model cells */
+    long NA, NB, nrec;         /* source cells and records */
+    int dtype;                 /* OGG_REMAP_FLOAT32 / FLOAT64 */
+    int n_fill;                /* 0 .. OGG_REMAP_MAX_FILLS */
+    double fill[2];            /* the values that mark missing */
+    int topology;              /* OGG_MASK_PERIODIC | OGG_MASK_FOLD */
+    int targets;               /* OGG_RUNOFF_COAST / OGG_RUNOFF_WET */
+    double Re;                 /* sphere radius of A_s */
+} ogg_runoff_params;
+typedef struct ogg_runoff_counts {
+    long long targets;         /* target cells (targets step) */
+    long long mapped, skipped, missing;   /* source cells by kind (sources step) */
+    long long cells;           /* model cells with at least one source (accumulate step) */
+    long long max_sources;     /* the largest n_sources (accumulate step) */
+    long long tests;           /* distance tests of the search (search step) */
+    long long bins;            /* cubes per axis of the search index, 0 for brute force (search step) */
+} ogg_runoff_counts;
+long ogg_runoff_struct_bytes(int which);                     /* sizeof of OGG_RUNOFF_PARAMS / COUNTS, -1 otherwise */
+long ogg_runoff_workspace_bytes(const ogg_runoff_params* p); /* of every step, -1 on a bad *p */
+/* the checks of *p (sizes, dtype, n_fill, topology, targets, Re): OGG_EARG with the reason, before any device work */
+int ogg_runoff_check(const ogg_runoff_params* p);
+/* targets step, device pointers, on a stream: x, y the supergrid points (2 ny + 1 rows of ld doubles), wet one byte per cell; the
+ * target list tgt_cell (room for ny * nx) in ascending c with its unit vectors tgt_u (3 per target); *counts (device memory) is
+ * zeroed and gets targets. */
+int ogg_runoff_targets_dev(const ogg_runoff_params* p, const double* x, const double* y, long ld, const unsigned char* wet,
+                           void* workspace, long workspace_bytes, int* tgt_cell, double* tgt_u, ogg_runoff_counts* counts, void* stream);
+/* sources step: f (nrec * NB * NA values of dtype), lon / lat the edges (device memory); the mapped list src_cell (room for NA * NB,
+ * J * NA + I) in ascending order with its unit vectors src_u (3 per source), ds (NB values of ds_J); mapped, skipped and missing into
+ * *counts.  The workspace keeps A_s of every mapped source for the accumulate step. */
+int ogg_runoff_sources_dev(const ogg_runoff_params* p, const void* f, const double* lon, const double* lat, void* workspace,
+                           long workspace_bytes, int* src_cell, double* src_u, double* ds, ogg_runoff_counts* counts, void* stream);
+/* search step, after the first two (n_targets, n_mapped their counts): for every mapped source its target cell src_target and the
+ * bits of its d2 (src_d2); tests and bins into *counts. */
+int ogg_runoff_search_dev(const ogg_runoff_params* p, const int* tgt_cell, const double* tgt_u, long n_targets, const double* src_u,
+                          long n_mapped, void* workspace, long workspace_bytes, int* src_target, double* src_d2,
+                          ogg_runoff_counts* counts, void* stream);
+/* segments step: the mapped sources grouped by target cell, in ascending source order within a cell, into the workspace */
+int ogg_runoff_segments_dev(const ogg_runoff_params* p, const int* src_target, long n_mapped, void* workspace, long workspace_bytes,
+                            void* stream);
+/* accumulate step, after the segments step: values (nrec * ny * nx) and n_sources (ny * nx) as above, from f, src_cell and the
+ * supergrid area (2 ny rows of lda doubles); cells and max_sources into *counts. */
+int ogg_runoff_accumulate_dev(const ogg_runoff_params* p, const void* f, const int* src_cell, long n_mapped, const double* area, long lda,
+                              const void* workspace, long workspace_bytes, double* values, int* n_sources, ogg_runoff_counts* counts,
+                              void* stream);
+/* HOST pointers throughout, staged through device memory: the five steps on the supergrid x, y ((2 ny + 1) x (2 nx + 1)) and area
+ * (2 ny x 2 nx).  src_cell, src_target, src_d2: room for NA * NB (counts->mapped are written). */
+int ogg_runoff(const ogg_runoff_params* p, const double* x, const double* y, const double* area, const unsigned char* wet,
+               const void* f, const double* lon, const double* lat, double* values, int* n_sources, int* src_cell, int* src_target,
+               double* src_d2, ogg_runoff_counts* counts);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

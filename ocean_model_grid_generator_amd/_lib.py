@@ -154,6 +154,25 @@ REMAP_MAX_FILLS = 2                                                    # OGG_REM
 REMAP_PARAMS, REMAP_COUNTS = 0, 1                                      # OGG_REMAP_PARAMS, OGG_REMAP_COUNTS
 
 
+class RunoffParams(ctypes.Structure):
+    """ogg_runoff_params of include/ogg_hip.h"""
+    _fields_ = [("ny", c_long), ("nx", c_long), ("NA", c_long), ("NB", c_long), ("nrec", c_long), ("dtype", c_int), ("n_fill", c_int),
+                ("fill", c_double * 2), ("topology", c_int), ("targets", c_int), ("Re", c_double)]
+
+
+RUNOFF_COUNT_FIELDS = ("targets", "mapped", "skipped", "missing", "cells", "max_sources", "tests", "bins")
+
+
+class RunoffCounts(ctypes.Structure):
+    """ogg_runoff_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in RUNOFF_COUNT_FIELDS]
+
+
+RUNOFF_COAST, RUNOFF_WET = 0, 1                                        # OGG_RUNOFF_COAST, OGG_RUNOFF_WET
+RUNOFF_PARAMS, RUNOFF_COUNTS = 0, 1                                    # OGG_RUNOFF_PARAMS, OGG_RUNOFF_COUNTS
+RUNOFF_MAX_BINS = 160                                                  # OGG_RUNOFF_MAX_BINS
+
+
 # name -> argtypes; every function returns int except the two string getters.  Must list EVERY symbol of ogg_hip.h
 # (tests/test_abi.py checks this list against the header).
 SIGNATURES = {
@@ -285,6 +304,18 @@ SIGNATURES = {
     "ogg_remap_fill_dev": [ctypes.POINTER(RemapParams), c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_remap": [ctypes.POINTER(RemapParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_void_p, c_void_p,
                   ctypes.POINTER(RemapCounts)],
+    "ogg_runoff_check": [ctypes.POINTER(RunoffParams)],
+    "ogg_runoff_targets_dev": [ctypes.POINTER(RunoffParams), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_void_p,
+                               c_void_p, c_void_p],
+    "ogg_runoff_sources_dev": [ctypes.POINTER(RunoffParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p],
+    "ogg_runoff_search_dev": [ctypes.POINTER(RunoffParams), c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p,
+                              c_void_p, c_void_p, c_void_p],
+    "ogg_runoff_segments_dev": [ctypes.POINTER(RunoffParams), c_void_p, c_long, c_void_p, c_long, c_void_p],
+    "ogg_runoff_accumulate_dev": [ctypes.POINTER(RunoffParams), c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p,
+                                  c_void_p, c_void_p, c_void_p],
+    "ogg_runoff": [ctypes.POINTER(RunoffParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                   c_void_p, c_void_p, c_void_p, ctypes.POINTER(RunoffCounts)],
     "ogg_event_create": [ctypes.POINTER(c_void_p)],
     "ogg_event_destroy": [c_void_p],
     "ogg_event_record": [c_void_p, c_void_p],
@@ -313,7 +344,9 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_mask_struct_bytes": [c_int],
                 "ogg_mask_workspace_bytes": [ctypes.POINTER(MaskParams)],
                 "ogg_remap_struct_bytes": [c_int],
-                "ogg_remap_workspace_bytes": [ctypes.POINTER(RemapParams)]}
+                "ogg_remap_workspace_bytes": [ctypes.POINTER(RemapParams)],
+                "ogg_runoff_struct_bytes": [c_int],
+                "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)]}
 
 _lib = None
 

@@ -1,0 +1,894 @@
+// Runoff mapping (include/ogg_hip.h, "Runoff mapping"): every mapped source cell of a lat-lon runoff field to its nearest target
+// cell of the model grid, then a per-cell, in-order sum of the discharge.
+//
+// targets / sources   one flag byte per cell (target) or per source cell (mapped), then an ordered compaction: a block count over
+//                     2048 items, one exclusive scan of the block counts, a block scan that writes each flagged item's slot.  The
+//                     lists come out in ascending index with their unit vectors (and A_s for the sources).
+// search              one thread per mapped source.  The index is a uniform grid of G^3 cubes of side h = 2 / G over [-1, 1]^3,
+//                     filled by an atomic counting sort: chordal distance is 3-D Euclidean distance, so the distance from a point
+//                     to a cube is an exact lower bound with no pole or seam case.  Shells of cubes at Chebyshev distance k = 0, 1,
+//                     .. are visited outward, skipping cubes that miss the unit sphere or lie farther than the best so far; after
+//                     shell k every unvisited target is at least k h away, and the walk stops when (k h)^2 > best (1 + 1e-12), a
+//                     margin that covers the rounding of a computed d2.  The best is kept as the key (d2 bits, cell), so the order
+//                     in which targets are met does not matter.  OGG_RUNOFF_BRUTE=1 tests every target instead (LDS tiles).
+// segments            keys (target cell << 32 | source position) sorted by a rank sort of 256 keys in LDS and merge passes whose
+//                     slots come from a binary search in the partner run (the keys are unique); a boundary pass gives every
+//                     cell its [start, end) in the sorted keys, in ascending source order because the positions ascend.
+// accumulate          one wavefront per 64 consecutive cells of a model row looping over the records (remap_kernel's shape): a
+//                     cell of at most REG sources keeps their offsets and areas in registers, a cell of more than LONG sources is
+//                     walked by the whole wavefront with the products taken in order by shuffles.  Almost every store is +0.0.
+//
+// Every result is a fixed function of the unit vectors, the source and the order of the source index: nothing depends on the launch
+// geometry or on the order in which the atomics land.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "ogg_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int NT = 256;                 // threads per workgroup (four wavefronts)
+constexpr int PER = 8;                  // items per thread of the scan
+constexpr int CH = NT * PER;            // items per scan block
+constexpr int REG = 8;                  // sources a lane keeps in registers across records
+constexpr int LONG_N = 32;              // cells with more sources are walked by the whole wavefront
+constexpr long HEAD = 256;
+constexpr double D = 0.017453292519943295;   // pi / 180
+constexpr double PAD = 1e-9;            // cubes widened by this much: covers the rounding of a point's cube index
+constexpr double MARGIN = 1.0 + 1e-12;  // covers the rounding of a computed d2
+
+static_assert(sizeof(ogg_runoff_params) == 80, "ogg_runoff_params layout");
+static_assert(sizeof(ogg_runoff_counts) == 64, "ogg_runoff_counts layout");
+
+struct Head {
+    long long total;                    // the last scan's total
+};
+static_assert(sizeof(Head) <= HEAD, "workspace head");
+
+__device__ inline unsigned long long* ull(long long* p) { return reinterpret_cast<unsigned long long*>(p); }
+
+template <int K>
+__device__ inline void block_add(long long (&v)[K], long long* const (&dst)[K]) {
+    __shared__ long long part[NT / 64][K];
+    for (int k = 0; k < K; ++k)
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < K; ++k) part[threadIdx.x / 64][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x < K) {
+        long long t = 0;
+        for (int w = 0; w < NT / 64; ++w) t += part[w][threadIdx.x];
+        if (t) atomicAdd(ull(dst[threadIdx.x]), (unsigned long long)t);
+    }
+}
+
+// exclusive prefix of v over the workgroup; *total the sum
+__device__ inline long long block_scan(long long v, long long* total) {
+    __shared__ long long wsum[NT / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x / 64;
+    long long incl = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    long long base = 0, tot = 0;
+    for (int k = 0; k < NT / 64; ++k) {
+        if (k < w) base += wsum[k];
+        tot += wsum[k];
+    }
+    __syncthreads();
+    *total = tot;
+    return base + incl - v;
+}
+
+__device__ inline void unit(double lon, double lat, double* u) {
+    const double cl = cos(lat * D);
+    u[0] = cl * cos(lon * D);
+    u[1] = cl * sin(lon * D);
+    u[2] = sin(lat * D);
+}
+
+__device__ inline double dist2(double ax, double ay, double az, double bx, double by, double bz) {
+    const double dx = ax - bx, dy = ay - by, dz = az - bz;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+__device__ inline unsigned long long bits_of(double v) {
+    unsigned long long b;
+    memcpy(&b, &v, 8);
+    return b;
+}
+
+// ---- ordered compaction --------------------------------------------------------------------------------------------
+// bsum[b] = the number of items of block b (CH items) that are non-zero
+template <typename T>
+__global__ __launch_bounds__(NT) void scan_count_kernel(const T* __restrict__ in, long n, long long* __restrict__ bsum) {
+    const long b0 = (long)blockIdx.x * CH;
+    long long v = 0;
+    for (int k = 0; k < PER; ++k) {
+        const long i = b0 + k * NT + threadIdx.x;
+        if (i < n) v += (long long)in[i];
+    }
+    long long tot;
+    (void)block_scan(v, &tot);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+// exclusive scan of the nb block counts in place (one workgroup); head->total the sum
+__global__ __launch_bounds__(NT) void scan_blocks_kernel(long long* bsum, long nb, Head* head) {
+    long long carry = 0;
+    for (long base = 0; base < nb; base += NT) {
+        const long i = base + threadIdx.x;
+        const long long v = i < nb ? bsum[i] : 0;
+        long long tot;
+        const long long ex = block_scan(v, &tot);
+        if (i < nb) bsum[i] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) head->total = carry;
+}
+
+// every item's exclusive prefix (in[i] summed over i' < i): PER consecutive items per thread, so the order is the index order
+template <typename T>
+__global__ __launch_bounds__(NT) void scan_write_kernel(const T* __restrict__ in, long n, const long long* __restrict__ bsum,
+                                                        int* __restrict__ out) {
+    const long i0 = (long)blockIdx.x * CH + (long)threadIdx.x * PER;
+    long long v[PER], s = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        v[k] = i0 + k < n ? (long long)in[i0 + k] : 0;
+        s += v[k];
+    }
+    long long tot;
+    long long run = bsum[blockIdx.x] + block_scan(s, &tot);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        if (i0 + k < n) out[i0 + k] = (int)run;
+        run += v[k];
+    }
+}
+
+// ---- targets -------------------------------------------------------------------------------------------------------
+struct Cells {
+    long ny, nx;
+    int periodic, fold, coast;
+};
+
+__global__ __launch_bounds__(NT) void target_flag_kernel(Cells g, const unsigned char* __restrict__ wet, unsigned char* __restrict__ flag,
+                                                         ogg_runoff_counts* counts) {
+    const long n = g.ny * g.nx;
+    long long v[1] = {0};
+    for (long c = (long)blockIdx.x * NT + threadIdx.x; c < n; c += (long)gridDim.x * NT) {
+        unsigned char t = 0;
+        if (wet[c]) {
+            if (!g.coast) {
+                t = 1;
+            } else {
+                const long j = c / g.nx, i = c % g.nx;
+                const long s = j > 0 ? c - g.nx : -1;
+                const long w = i > 0 ? c - 1 : (g.periodic ? c + g.nx - 1 : -1);
+                const long e = i < g.nx - 1 ? c + 1 : (g.periodic ? c - (g.nx - 1) : -1);
+                const long nn = j < g.ny - 1 ? c + g.nx : (g.fold ? j * g.nx + (g.nx - 1 - i) : -1);
+                t = (s < 0 || !wet[s] || w < 0 || !wet[w] || e < 0 || !wet[e] || nn < 0 || !wet[nn]) ? 1 : 0;
+            }
+        }
+        flag[c] = t;
+        v[0] += t;
+    }
+    long long* const dst[1] = {&counts->targets};
+    block_add<1>(v, dst);
+}
+
+__global__ __launch_bounds__(NT) void target_list_kernel(long ny, long nx, const unsigned char* __restrict__ flag, const int* __restrict__ pos,
+                                                         const double* __restrict__ x, const double* __restrict__ y, long ld,
+                                                         int* __restrict__ cell, double* __restrict__ u) {
+    const long n = ny * nx;
+    for (long c = (long)blockIdx.x * NT + threadIdx.x; c < n; c += (long)gridDim.x * NT) {
+        if (!flag[c]) continue;
+        const long j = c / nx, i = c % nx, k = (2 * j + 1) * ld + 2 * i + 1;
+        const long q = pos[c];
+        double v[3];
+        unit(x[k], y[k], v);
+        cell[q] = (int)c;
+        u[3 * q] = v[0];
+        u[3 * q + 1] = v[1];
+        u[3 * q + 2] = v[2];
+    }
+}
+
+// ---- sources -------------------------------------------------------------------------------------------------------
+template <typename T>
+__device__ inline bool missing(T v, T f0, T f1, int nf) {
+    return v != v || (nf > 0 && v == f0) || (nf > 1 && v == f1);
+}
+
+template <typename T>
+__global__ __launch_bounds__(NT) void source_flag_kernel(const T* __restrict__ f, long nsrc, long nrec, int nf, double fill0, double fill1,
+                                                         unsigned char* __restrict__ flag, ogg_runoff_counts* counts) {
+    const T f0 = static_cast<T>(fill0), f1 = static_cast<T>(fill1);
+    long long v[3] = {0, 0, 0};
+    for (long s = (long)blockIdx.x * NT + threadIdx.x; s < nsrc; s += (long)gridDim.x * NT) {
+        bool any = false, nz = false;
+        for (long r = 0; r < nrec; ++r) {
+            const T x = f[r * nsrc + s];
+            if (!missing(x, f0, f1, nf)) {
+                any = true;
+                nz = nz || x != T(0);
+            }
+        }
+        flag[s] = nz ? 1 : 0;
+        v[0] += nz;
+        v[1] += any && !nz;
+        v[2] += !any;
+    }
+    long long* const dst[3] = {&counts->mapped, &counts->skipped, &counts->missing};
+    block_add<3>(v, dst);
+}
+
+__global__ __launch_bounds__(NT) void source_ds_kernel(const double* __restrict__ lat, long NB, double* __restrict__ ds) {
+    for (long J = (long)blockIdx.x * NT + threadIdx.x; J < NB; J += (long)gridDim.x * NT) {
+        const double b1 = lat[J] * D, b2 = lat[J + 1] * D;
+        ds[J] = 2.0 * cos((b1 + b2) / 2.0) * sin((b2 - b1) / 2.0);
+    }
+}
+
+__global__ __launch_bounds__(NT) void source_list_kernel(long NA, long NB, const unsigned char* __restrict__ flag, const int* __restrict__ pos,
+                                                         const double* __restrict__ lon, const double* __restrict__ lat,
+                                                         const double* __restrict__ ds, double Re, int* __restrict__ cell,
+                                                         double* __restrict__ u, double* __restrict__ As) {
+    const long n = NA * NB;
+    for (long s = (long)blockIdx.x * NT + threadIdx.x; s < n; s += (long)gridDim.x * NT) {
+        if (!flag[s]) continue;
+        const long J = s / NA, I = s % NA;
+        const long q = pos[s];
+        double v[3];
+        unit((lon[I] + lon[I + 1]) / 2.0, (lat[J] + lat[J + 1]) / 2.0, v);
+        cell[q] = (int)s;
+        u[3 * q] = v[0];
+        u[3 * q + 1] = v[1];
+        u[3 * q + 2] = v[2];
+        As[q] = (Re * Re) * (lon[I + 1] * D - lon[I] * D) * ds[J];
+    }
+}
+
+// ---- search --------------------------------------------------------------------------------------------------------
+__device__ inline int cube_of(double v, int G) {
+    const int k = (int)floor((v + 1.0) * (0.5 * (double)G));
+    return k < 0 ? 0 : (k >= G ? G - 1 : k);
+}
+
+__global__ __launch_bounds__(NT) void bin_count_kernel(const double* __restrict__ u, long n, int G, int* __restrict__ cnt,
+                                                       int* __restrict__ bin) {
+    for (long k = (long)blockIdx.x * NT + threadIdx.x; k < n; k += (long)gridDim.x * NT) {
+        const int b = cube_of(u[3 * k], G) + G * (cube_of(u[3 * k + 1], G) + G * cube_of(u[3 * k + 2], G));
+        bin[k] = b;
+        atomicAdd(&cnt[b], 1);
+    }
+}
+
+// every target copied into its cube's range (the order inside a cube does not matter: the key breaks ties)
+__global__ __launch_bounds__(NT) void bin_fill_kernel(const double* __restrict__ u, const int* __restrict__ cell, long n,
+                                                      const int* __restrict__ bin, const int* __restrict__ start, int* __restrict__ cursor,
+                                                      double* __restrict__ bu, int* __restrict__ bc) {
+    for (long k = (long)blockIdx.x * NT + threadIdx.x; k < n; k += (long)gridDim.x * NT) {
+        const int b = bin[k];
+        const long q = (long)start[b] + atomicAdd(&cursor[b], 1);
+        bu[3 * q] = u[3 * k];
+        bu[3 * q + 1] = u[3 * k + 1];
+        bu[3 * q + 2] = u[3 * k + 2];
+        bc[q] = cell[k];
+    }
+}
+
+struct Index {
+    int G;
+    double h;
+    const int* start;   // G^3 + 1
+    const double* bu;
+    const int* bc;
+};
+
+struct Best {
+    unsigned long long bits;
+    int cell;
+    long long tests;
+};
+
+// the targets of cube (a, b, c) against the point (px, py, pz), unless the cube misses the sphere or lies beyond the best
+__device__ inline void visit(const Index& ix, int a, int b, int c, double px, double py, double pz, Best& best) {
+    const double lx = -1.0 + a * ix.h - PAD, hx = -1.0 + (a + 1) * ix.h + PAD;
+    const double ly = -1.0 + b * ix.h - PAD, hy = -1.0 + (b + 1) * ix.h + PAD;
+    const double lz = -1.0 + c * ix.h - PAD, hz = -1.0 + (c + 1) * ix.h + PAD;
+    const double ox = lx > 0.0 ? lx : (hx < 0.0 ? -hx : 0.0), oy = ly > 0.0 ? ly : (hy < 0.0 ? -hy : 0.0),
+                 oz = lz > 0.0 ? lz : (hz < 0.0 ? -hz : 0.0);
+    const double fx = fmax(lx * lx, hx * hx), fy = fmax(ly * ly, hy * hy), fz = fmax(lz * lz, hz * hz);
+    if ((ox * ox + oy * oy) + oz * oz > 1.0 + 1e-6 || (fx + fy) + fz < 1.0 - 1e-6) return;   // misses the unit sphere
+    const double gx = lx > px ? lx - px : (px > hx ? px - hx : 0.0), gy = ly > py ? ly - py : (py > hy ? py - hy : 0.0),
+                 gz = lz > pz ? lz - pz : (pz > hz ? pz - hz : 0.0);
+    if (best.cell != INT_MAX) {
+        double bd;
+        memcpy(&bd, &best.bits, 8);
+        if ((gx * gx + gy * gy) + gz * gz > bd * MARGIN) return;
+    }
+    const int cube = a + ix.G * (b + ix.G * c);
+    const int s0 = ix.start[cube], s1 = ix.start[cube + 1];
+    for (int t = s0; t < s1; ++t) {
+        const unsigned long long bb = bits_of(dist2(px, py, pz, ix.bu[3 * t], ix.bu[3 * t + 1], ix.bu[3 * t + 2]));
+        const int cc = ix.bc[t];
+        if (bb < best.bits || (bb == best.bits && cc < best.cell)) best.bits = bb, best.cell = cc;
+    }
+    best.tests += s1 - s0;
+}
+
+__global__ __launch_bounds__(NT) void search_kernel(Index ix, const double* __restrict__ su, long n, int* __restrict__ tgt,
+                                                    double* __restrict__ d2, ogg_runoff_counts* counts) {
+    long long v[1] = {0};
+    for (long s = (long)blockIdx.x * NT + threadIdx.x; s < n; s += (long)gridDim.x * NT) {
+        const double px = su[3 * s], py = su[3 * s + 1], pz = su[3 * s + 2];
+        const int ca = cube_of(px, ix.G), cb = cube_of(py, ix.G), cc = cube_of(pz, ix.G);
+        Best best{ULLONG_MAX, INT_MAX, 0};
+        for (int k = 0; k <= ix.G; ++k) {
+            for (int da = -k; da <= k; ++da) {
+                const int a = ca + da;
+                if (a < 0 || a >= ix.G) continue;
+                for (int db = -k; db <= k; ++db) {
+                    const int b = cb + db;
+                    if (b < 0 || b >= ix.G) continue;
+                    const bool rim = da == -k || da == k || db == -k || db == k;
+                    const int step = rim ? 1 : (k > 0 ? 2 * k : 1);
+                    for (int dc = -k; dc <= k; dc += step) {
+                        const int c = cc + dc;
+                        if (c >= 0 && c < ix.G) visit(ix, a, b, c, px, py, pz, best);
+                    }
+                }
+            }
+            if (best.cell != INT_MAX) {
+                const double lb = k * ix.h - 2.0 * PAD;   // every target not yet visited is at least this far
+                double bd;
+                memcpy(&bd, &best.bits, 8);
+                if (lb > 0.0 && lb * lb > bd * MARGIN) break;
+            }
+        }
+        tgt[s] = best.cell;
+        memcpy(&d2[s], &best.bits, 8);
+        v[0] += best.tests;
+    }
+    long long* const dst[1] = {&counts->tests};
+    block_add<1>(v, dst);
+}
+
+// every target for every source, tiles of NT targets through LDS
+__global__ __launch_bounds__(NT) void brute_kernel(const int* __restrict__ cell, const double* __restrict__ tu, long nt,
+                                                   const double* __restrict__ su, long n, int* __restrict__ tgt, double* __restrict__ d2,
+                                                   ogg_runoff_counts* counts) {
+    __shared__ double lu[3][NT];
+    __shared__ int lc[NT];
+    const long s = (long)blockIdx.x * NT + threadIdx.x;
+    const bool act = s < n;
+    const double px = act ? su[3 * s] : 0.0, py = act ? su[3 * s + 1] : 0.0, pz = act ? su[3 * s + 2] : 0.0;
+    Best best{ULLONG_MAX, INT_MAX, 0};
+    for (long base = 0; base < nt; base += NT) {
+        const long t = base + threadIdx.x;
+        if (t < nt) {
+            lu[0][threadIdx.x] = tu[3 * t];
+            lu[1][threadIdx.x] = tu[3 * t + 1];
+            lu[2][threadIdx.x] = tu[3 * t + 2];
+            lc[threadIdx.x] = cell[t];
+        }
+        __syncthreads();
+        const int m = nt - base < NT ? (int)(nt - base) : NT;
+        for (int k = 0; k < m; ++k) {
+            const unsigned long long bb = bits_of(dist2(px, py, pz, lu[0][k], lu[1][k], lu[2][k]));
+            const int cc = lc[k];
+            if (bb < best.bits || (bb == best.bits && cc < best.cell)) best.bits = bb, best.cell = cc;
+        }
+        __syncthreads();
+    }
+    long long v[1] = {act ? (long long)nt : 0};
+    if (act) {
+        tgt[s] = best.cell;
+        memcpy(&d2[s], &best.bits, 8);
+    }
+    long long* const dst[1] = {&counts->tests};
+    block_add<1>(v, dst);
+}
+
+// ---- segments ------------------------------------------------------------------------------------------------------
+// keys of NT consecutive sources sorted in LDS by rank (the keys are unique)
+__global__ __launch_bounds__(NT) void sort_block_kernel(const int* __restrict__ tgt, long n, unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long lk[NT];
+    const long i = (long)blockIdx.x * NT + threadIdx.x;
+    const unsigned long long key = i < n ? ((unsigned long long)(unsigned)tgt[i] << 32) | (unsigned long long)i : ULLONG_MAX;
+    lk[threadIdx.x] = key;
+    __syncthreads();
+    int rank = 0;
+    for (int k = 0; k < NT; ++k) rank += lk[k] < key;
+    if (i < n) out[(long)blockIdx.x * NT + rank] = key;
+}
+
+// runs of w sorted keys merged in pairs: a key's slot is its place in its run plus the keys of the partner run below it
+__global__ __launch_bounds__(NT) void merge_kernel(const unsigned long long* __restrict__ in, long n, long w, unsigned long long* __restrict__ out) {
+    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
+        const unsigned long long key = in[i];
+        const long r = i / w, rs = r * w;
+        long lo = (r & 1) ? rs - w : rs + w;
+        long hi = (r & 1) ? rs : (rs + 2 * w < n ? rs + 2 * w : n);
+        const long p0 = lo;
+        if (lo > n) lo = hi = n;
+        while (lo < hi) {
+            const long m = lo + (hi - lo) / 2;
+            if (in[m] < key) lo = m + 1;
+            else hi = m;
+        }
+        out[(r & ~1L) * w + (i - rs) + (lo - (p0 > n ? n : p0))] = key;
+    }
+}
+
+__global__ __launch_bounds__(NT) void seg_kernel(const unsigned long long* __restrict__ key, long n, long ncell, int2* __restrict__ seg) {
+    for (long k = (long)blockIdx.x * NT + threadIdx.x; k < n; k += (long)gridDim.x * NT) {
+        const unsigned c = (unsigned)(key[k] >> 32);
+        if ((long)c >= ncell) continue;   // no target (refused before the search): never written
+        if (k == 0 || (unsigned)(key[k - 1] >> 32) != c) seg[c].x = (int)k;
+        if (k + 1 == n || (unsigned)(key[k + 1] >> 32) != c) seg[c].y = (int)(k + 1);
+    }
+}
+
+// ---- accumulate ----------------------------------------------------------------------------------------------------
+struct Geo {
+    long ny, nx, nsrc, nrec, lda;
+    int n_fill;
+    double fill0, fill1;
+};
+
+template <typename T>
+__global__ __launch_bounds__(NT) void accumulate_kernel(Geo g, const T* __restrict__ f, const int2* __restrict__ seg,
+                                                        const unsigned long long* __restrict__ key, const int* __restrict__ src_cell,
+                                                        const double* __restrict__ As, const double* __restrict__ area,
+                                                        double* __restrict__ out, int* __restrict__ nsrc_out, ogg_runoff_counts* counts) {
+    const int lane = threadIdx.x & 63;
+    const long tiles = (g.nx + 63) / 64;
+    const long wave = (long)blockIdx.x * (NT / 64) + threadIdx.x / 64;
+    const long row = wave / tiles, i = (wave % tiles) * 64 + lane;
+    const bool inb = row < g.ny && i < g.nx;
+    const long c = row * g.nx + i, ncell = g.ny * g.nx;
+    const T f0 = static_cast<T>(g.fill0), f1 = static_cast<T>(g.fill1);
+    int s = 0, n = 0;
+    double Ac = 1.0;
+    if (inb) {
+        const int2 sg = seg[c];
+        s = sg.x;
+        n = sg.y - sg.x;
+        if (n < 0) n = 0;
+        nsrc_out[c] = n;
+        if (n > 0) {
+            const double* a0 = area + 2 * row * g.lda + 2 * i;
+            const double* a1 = a0 + g.lda;
+            Ac = (a0[0] + a1[1]) + (a0[1] + a1[0]);
+        }
+    }
+    double ca[REG];
+    long co[REG];
+#pragma unroll
+    for (int t = 0; t < REG; ++t) {
+        ca[t] = 0.0;
+        co[t] = -1;
+        if (t < n && n <= REG) {
+            const int q = (int)(key[s + t] & 0xFFFFFFFFull);
+            ca[t] = As[q];
+            co[t] = src_cell[q];
+        }
+    }
+    const bool is_long = n > LONG_N;
+    const unsigned long long longmask = __ballot(is_long);
+    for (long r = 0; r < g.nrec; ++r) {
+        const T* fr = f + r * g.nsrc;
+        double S = 0.0;
+        if (n <= REG) {
+#pragma unroll
+            for (int t = 0; t < REG; ++t) {
+                if (co[t] >= 0) {
+                    const T v = fr[co[t]];
+                    if (!missing(v, f0, f1, g.n_fill)) S += (double)v * ca[t];
+                }
+            }
+        } else if (!is_long) {
+            for (int k = s; k < s + n; ++k) {
+                const int q = (int)(key[k] & 0xFFFFFFFFull);
+                const T v = fr[src_cell[q]];
+                if (!missing(v, f0, f1, g.n_fill)) S += (double)v * As[q];
+            }
+        }
+        // the long cells, one after the other, by the whole wavefront (longmask is the same in every lane)
+        for (unsigned long long m = longmask; m; m &= m - 1) {
+            const int L = __ffsll((long long)m) - 1;
+            const int sL = __shfl(s, L, 64), nL = __shfl(n, L, 64);
+            double sum = 0.0;
+            for (int base = 0; base < nL; base += 64) {
+                double p = 0.0;
+                int ok = 0;
+                if (base + lane < nL) {
+                    const int q = (int)(key[sL + base + lane] & 0xFFFFFFFFull);
+                    const T v = fr[src_cell[q]];
+                    ok = !missing(v, f0, f1, g.n_fill);
+                    p = (double)v * As[q];
+                }
+                const int cnt = nL - base < 64 ? nL - base : 64;
+                for (int t = 0; t < cnt; ++t) {
+                    const double pt = __shfl(p, t, 64);
+                    if (__shfl(ok, t, 64)) sum += pt;
+                }
+            }
+            if (lane == L) S = sum;
+        }
+        if (inb) out[r * ncell + c] = n > 0 ? S / Ac : 0.0;
+    }
+    long long mx = inb ? n : 0;
+    for (int off = 32; off > 0; off >>= 1) {
+        const long long t = __shfl_xor(mx, off, 64);
+        mx = t > mx ? t : mx;
+    }
+    if (lane == 0 && mx > 0) atomicMax(ull(&counts->max_sources), (unsigned long long)mx);
+    long long v[1] = {inb && n > 0 ? 1 : 0};
+    long long* const dst[1] = {&counts->cells};
+    block_add<1>(v, dst);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+long round256(long v) { return (v + 255) / 256 * 256; }
+
+int check_params(const ogg_runoff_params* p) {
+    OGG_REQUIRE(p, OGG_EARG, "runoff: null parameters");
+    OGG_REQUIRE(p->ny >= 1 && p->nx >= 1 && p->ny <= (long)INT_MAX && p->nx <= (long)INT_MAX && p->ny * p->nx < (1L << 31), OGG_EARG,
+                "runoff: %ld x %ld cells: ny, nx >= 1 and ny * nx < 2^31", p->ny, p->nx);
+    OGG_REQUIRE(p->NA >= 1 && p->NB >= 1 && p->NA <= (long)INT_MAX && p->NB <= (long)INT_MAX && p->NA * p->NB < (1L << 31), OGG_EARG,
+                "runoff: %ld x %ld source cells: NA, NB >= 1 and NA * NB < 2^31", p->NA, p->NB);
+    OGG_REQUIRE(p->nrec >= 1 && p->nrec <= (long)INT_MAX && p->nrec * p->ny * p->nx < (1L << 32) && p->nrec * p->NA * p->NB < (1L << 40),
+                OGG_EARG, "runoff: %ld records of %ld x %ld cells and %ld x %ld source cells: nrec >= 1, nrec * ny * nx < 2^32 and "
+                "nrec * NA * NB < 2^40", p->nrec, p->ny, p->nx, p->NA, p->NB);
+    OGG_REQUIRE(p->dtype == OGG_REMAP_FLOAT32 || p->dtype == OGG_REMAP_FLOAT64, OGG_EARG, "runoff: source dtype %d (0: float32, 1: float64)",
+                p->dtype);
+    OGG_REQUIRE(p->n_fill >= 0 && p->n_fill <= OGG_REMAP_MAX_FILLS, OGG_EARG, "runoff: %d fill values (at most %d)", p->n_fill,
+                OGG_REMAP_MAX_FILLS);
+    OGG_REQUIRE((p->topology & ~(OGG_MASK_PERIODIC | OGG_MASK_FOLD)) == 0, OGG_EARG, "runoff: topology flags %d", p->topology);
+    OGG_REQUIRE(p->targets == OGG_RUNOFF_COAST || p->targets == OGG_RUNOFF_WET, OGG_EARG, "runoff: targets %d (0: coast, 1: wet)",
+                p->targets);
+    OGG_REQUIRE(std::isfinite(p->Re) && p->Re > 0.0, OGG_EARG, "runoff: radius %g", p->Re);
+    return OGG_OK;
+}
+
+long ncell_of(const ogg_runoff_params& p) { return p.ny * p.nx; }
+long nsrc_of(const ogg_runoff_params& p) { return p.NA * p.NB; }
+long nitem(const ogg_runoff_params& p) { return std::max(ncell_of(p), nsrc_of(p)); }
+long nbins_max() { return (long)OGG_RUNOFF_MAX_BINS * OGG_RUNOFF_MAX_BINS * OGG_RUNOFF_MAX_BINS + 1; }
+
+// workspace: head | flag bytes | positions | block sums | A_s | cube counts | cube starts | cube of target | binned u | binned cells |
+// keys (two buffers) | segments
+struct Layout {
+    long flag, pos, bsum, As, cnt, start, bin, bu, bc, key0, key1, seg, total;
+};
+
+Layout layout(const ogg_runoff_params& p) {
+    Layout l;
+    const long ni = nitem(p), nc = ncell_of(p), ns = nsrc_of(p), nb = nbins_max();
+    l.flag = HEAD;
+    l.pos = l.flag + round256(ni);
+    l.bsum = l.pos + round256(ni * 4);
+    l.As = l.bsum + round256((std::max(ni, nb) / CH + 2) * 8);
+    l.cnt = l.As + round256(ns * 8);
+    l.start = l.cnt + round256(nb * 4);
+    l.bin = l.start + round256(nb * 4);
+    l.bu = l.bin + round256(nc * 4);
+    l.bc = l.bu + round256(nc * 24);
+    l.key0 = l.bc + round256(nc * 4);
+    l.key1 = l.key0 + round256(ns * 8);
+    l.seg = l.key1 + round256(ns * 8);
+    l.total = l.seg + round256(nc * 8);
+    return l;
+}
+
+template <typename P>
+P* at(void* ws, long off) { return reinterpret_cast<P*>(static_cast<char*>(ws) + off); }
+template <typename P>
+const P* at(const void* ws, long off) { return reinterpret_cast<const P*>(static_cast<const char*>(ws) + off); }
+
+int knob(const char* name, int def, int lo, int hi, int* out) {
+    *out = def;
+    if (const char* e = getenv(name)) {
+        const long v = atol(e);
+        OGG_REQUIRE(v >= lo && v <= hi, OGG_EARG, "%s=%s: %d .. %d", name, e, lo, hi);
+        *out = (int)v;
+    }
+    return OGG_OK;
+}
+
+int check_ws(const ogg_runoff_params& p, const void* ws, long wsb, const char* who) {
+    const long need = layout(p).total;
+    OGG_REQUIRE(ws && wsb >= need, OGG_EARG, "%s: workspace of %ld bytes, %ld needed", who, wsb, need);
+    return OGG_OK;
+}
+
+unsigned grid_for(long n, long cap) { return (unsigned)std::min<long>(std::max<long>((n + NT - 1) / NT, 1), cap); }
+
+// pos[i] = the number of non-zero in[i'] for i' < i, for i < n; head->total their sum
+template <typename T>
+int scan(const T* in, long n, void* ws, const Layout& l, hipStream_t st) {
+    const long nb = (n + CH - 1) / CH;
+    scan_count_kernel<T><<<(unsigned)nb, NT, 0, st>>>(in, n, at<long long>(ws, l.bsum));
+    OGG_LAUNCH_CHECK();
+    scan_blocks_kernel<<<1, NT, 0, st>>>(at<long long>(ws, l.bsum), nb, at<Head>(ws, 0));
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+template <typename T>
+int scan_write(const T* in, long n, int* out, void* ws, const Layout& l, hipStream_t st) {
+    const long nb = (n + CH - 1) / CH;
+    scan_write_kernel<T><<<(unsigned)nb, NT, 0, st>>>(in, n, at<long long>(ws, l.bsum), out);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+// the number of merge passes after the block sort, so which key buffer holds the sorted keys
+int merge_passes(long n) {
+    int k = 0;
+    for (long w = NT; w < n; w *= 2) ++k;
+    return k;
+}
+
+}  // namespace
+
+extern "C" long ogg_runoff_struct_bytes(int which) {
+    return which == OGG_RUNOFF_PARAMS ? (long)sizeof(ogg_runoff_params) : (which == OGG_RUNOFF_COUNTS ? (long)sizeof(ogg_runoff_counts) : -1L);
+}
+
+extern "C" long ogg_runoff_workspace_bytes(const ogg_runoff_params* p) {
+    if (!p || check_params(p) != OGG_OK) return -1;
+    return layout(*p).total;
+}
+
+extern "C" int ogg_runoff_check(const ogg_runoff_params* p) { return check_params(p); }
+
+extern "C" int ogg_runoff_targets_dev(const ogg_runoff_params* p, const double* x, const double* y, long ld, const unsigned char* wet,
+                                      void* workspace, long workspace_bytes, int* tgt_cell, double* tgt_u, ogg_runoff_counts* counts,
+                                      void* stream) {
+    if (int e = check_params(p)) return e;
+    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_runoff_targets")) return e;
+    OGG_REQUIRE(x && y && wet && tgt_cell && tgt_u && counts, OGG_EARG, "ogg_runoff_targets: null x / y / wet / tgt_cell / tgt_u / counts");
+    OGG_REQUIRE(ld >= 2 * p->nx + 1, OGG_EARG, "ogg_runoff_targets: row stride %ld < 2 nx + 1", ld);
+    hipStream_t st = ogg::as_stream(stream);
+    const Layout l = layout(*p);
+    const long nc = ncell_of(*p);
+    OGG_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(ogg_runoff_counts), st));
+    const Cells g{p->ny, p->nx, (p->topology & OGG_MASK_PERIODIC) ? 1 : 0, (p->topology & OGG_MASK_FOLD) ? 1 : 0,
+                  p->targets == OGG_RUNOFF_COAST ? 1 : 0};
+    unsigned char* flag = at<unsigned char>(workspace, l.flag);
+    int* pos = at<int>(workspace, l.pos);
+    target_flag_kernel<<<grid_for(nc, 4096), NT, 0, st>>>(g, wet, flag, counts);
+    OGG_LAUNCH_CHECK();
+    if (int e = scan<unsigned char>(flag, nc, workspace, l, st)) return e;
+    if (int e = scan_write<unsigned char>(flag, nc, pos, workspace, l, st)) return e;
+    target_list_kernel<<<grid_for(nc, 4096), NT, 0, st>>>(p->ny, p->nx, flag, pos, x, y, ld, tgt_cell, tgt_u);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+extern "C" int ogg_runoff_sources_dev(const ogg_runoff_params* p, const void* f, const double* lon, const double* lat, void* workspace,
+                                      long workspace_bytes, int* src_cell, double* src_u, double* ds, ogg_runoff_counts* counts,
+                                      void* stream) {
+    if (int e = check_params(p)) return e;
+    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_runoff_sources")) return e;
+    OGG_REQUIRE(f && lon && lat && src_cell && src_u && ds && counts, OGG_EARG,
+                "ogg_runoff_sources: null f / lon / lat / src_cell / src_u / ds / counts");
+    hipStream_t st = ogg::as_stream(stream);
+    const Layout l = layout(*p);
+    const long ns = nsrc_of(*p);
+    unsigned char* flag = at<unsigned char>(workspace, l.flag);
+    int* pos = at<int>(workspace, l.pos);
+    if (p->dtype == OGG_REMAP_FLOAT32)
+        source_flag_kernel<float><<<grid_for(ns, 4096), NT, 0, st>>>(static_cast<const float*>(f), ns, p->nrec, p->n_fill, p->fill[0],
+                                                                    p->fill[1], flag, counts);
+    else
+        source_flag_kernel<double><<<grid_for(ns, 4096), NT, 0, st>>>(static_cast<const double*>(f), ns, p->nrec, p->n_fill, p->fill[0],
+                                                                     p->fill[1], flag, counts);
+    OGG_LAUNCH_CHECK();
+    source_ds_kernel<<<grid_for(p->NB, 64), NT, 0, st>>>(lat, p->NB, ds);
+    OGG_LAUNCH_CHECK();
+    if (int e = scan<unsigned char>(flag, ns, workspace, l, st)) return e;
+    if (int e = scan_write<unsigned char>(flag, ns, pos, workspace, l, st)) return e;
+    source_list_kernel<<<grid_for(ns, 4096), NT, 0, st>>>(p->NA, p->NB, flag, pos, lon, lat, ds, p->Re, src_cell, src_u,
+                                                          at<double>(workspace, l.As));
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+extern "C" int ogg_runoff_search_dev(const ogg_runoff_params* p, const int* tgt_cell, const double* tgt_u, long n_targets, const double* src_u,
+                                     long n_mapped, void* workspace, long workspace_bytes, int* src_target, double* src_d2,
+                                     ogg_runoff_counts* counts, void* stream) {
+    if (int e = check_params(p)) return e;
+    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_runoff_search")) return e;
+    OGG_REQUIRE(n_targets >= 0 && n_targets <= ncell_of(*p) && n_mapped >= 0 && n_mapped <= nsrc_of(*p), OGG_EARG,
+                "ogg_runoff_search: %ld targets of %ld cells, %ld mapped of %ld source cells", n_targets, ncell_of(*p), n_mapped,
+                nsrc_of(*p));
+    OGG_REQUIRE(n_targets > 0 || n_mapped == 0, OGG_EARG,
+                "runoff: no target cell (no wet cell%s) while %ld source cells hold runoff", p->targets == OGG_RUNOFF_COAST ? " on a coast" : "",
+                n_mapped);
+    OGG_REQUIRE(counts && ((tgt_cell && tgt_u) || n_targets == 0) && ((src_u && src_target && src_d2) || n_mapped == 0), OGG_EARG,
+                "ogg_runoff_search: null tgt_cell / tgt_u / src_u / src_target / src_d2 / counts");
+    int brute = 0, bins = 0;
+    if (int e = knob("OGG_RUNOFF_BRUTE", 0, 0, 1, &brute)) return e;
+    if (int e = knob("OGG_RUNOFF_BINS", 0, 0, OGG_RUNOFF_MAX_BINS, &bins)) return e;
+    hipStream_t st = ogg::as_stream(stream);
+    const Layout l = layout(*p);
+    long long G = 0;
+    if (!brute) G = bins > 0 ? bins : std::min<long>(std::max<long>((long)ceil(sqrt((double)n_targets / 24.0)), 1), OGG_RUNOFF_MAX_BINS);
+    OGG_HIP_CHECK(hipMemcpyAsync(&counts->bins, &G, sizeof(G), hipMemcpyHostToDevice, st));
+    OGG_HIP_CHECK(hipStreamSynchronize(st));   // G lives on this frame
+    if (n_mapped == 0) return OGG_OK;
+    if (brute) {
+        brute_kernel<<<(unsigned)((n_mapped + NT - 1) / NT), NT, 0, st>>>(tgt_cell, tgt_u, n_targets, src_u, n_mapped, src_target, src_d2,
+                                                                          counts);
+        OGG_LAUNCH_CHECK();
+        return OGG_OK;
+    }
+    const long nb = G * G * G;
+    int* cnt = at<int>(workspace, l.cnt);
+    int* start = at<int>(workspace, l.start);
+    int* bin = at<int>(workspace, l.bin);
+    OGG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)(nb + 1) * 4, st));
+    bin_count_kernel<<<grid_for(n_targets, 4096), NT, 0, st>>>(tgt_u, n_targets, (int)G, cnt, bin);
+    OGG_LAUNCH_CHECK();
+    // starts: the exclusive prefix of the counts over nb + 1 cubes (cnt[nb] = 0, so start[nb] = n_targets)
+    const long nb1 = nb + 1, nblk = (nb1 + CH - 1) / CH;
+    scan_count_kernel<int><<<(unsigned)nblk, NT, 0, st>>>(cnt, nb1, at<long long>(workspace, l.bsum));
+    OGG_LAUNCH_CHECK();
+    scan_blocks_kernel<<<1, NT, 0, st>>>(at<long long>(workspace, l.bsum), nblk, at<Head>(workspace, 0));
+    OGG_LAUNCH_CHECK();
+    scan_write_kernel<int><<<(unsigned)nblk, NT, 0, st>>>(cnt, nb1, at<long long>(workspace, l.bsum), start);
+    OGG_LAUNCH_CHECK();
+    OGG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)nb1 * 4, st));   // the cursors of the fill
+    double* bu = at<double>(workspace, l.bu);
+    int* bc = at<int>(workspace, l.bc);
+    bin_fill_kernel<<<grid_for(n_targets, 4096), NT, 0, st>>>(tgt_u, tgt_cell, n_targets, bin, start, cnt, bu, bc);
+    OGG_LAUNCH_CHECK();
+    const Index ix{(int)G, 2.0 / (double)G, start, bu, bc};
+    search_kernel<<<grid_for(n_mapped, 1L << 20), NT, 0, st>>>(ix, src_u, n_mapped, src_target, src_d2, counts);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+extern "C" int ogg_runoff_segments_dev(const ogg_runoff_params* p, const int* src_target, long n_mapped, void* workspace,
+                                       long workspace_bytes, void* stream) {
+    if (int e = check_params(p)) return e;
+    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_runoff_segments")) return e;
+    OGG_REQUIRE(n_mapped >= 0 && n_mapped <= nsrc_of(*p), OGG_EARG, "ogg_runoff_segments: %ld mapped of %ld source cells", n_mapped,
+                nsrc_of(*p));
+    OGG_REQUIRE(src_target || n_mapped == 0, OGG_EARG, "ogg_runoff_segments: null src_target");
+    hipStream_t st = ogg::as_stream(stream);
+    const Layout l = layout(*p);
+    int2* seg = at<int2>(workspace, l.seg);
+    OGG_HIP_CHECK(hipMemsetAsync(seg, 0, (size_t)ncell_of(*p) * 8, st));
+    if (n_mapped == 0) return OGG_OK;
+    unsigned long long* buf[2] = {at<unsigned long long>(workspace, l.key0), at<unsigned long long>(workspace, l.key1)};
+    sort_block_kernel<<<(unsigned)((n_mapped + NT - 1) / NT), NT, 0, st>>>(src_target, n_mapped, buf[0]);
+    OGG_LAUNCH_CHECK();
+    int k = 0;
+    for (long w = NT; w < n_mapped; w *= 2, ++k) {
+        merge_kernel<<<grid_for(n_mapped, 1L << 20), NT, 0, st>>>(buf[k & 1], n_mapped, w, buf[(k + 1) & 1]);
+        OGG_LAUNCH_CHECK();
+    }
+    seg_kernel<<<grid_for(n_mapped, 1L << 20), NT, 0, st>>>(buf[k & 1], n_mapped, ncell_of(*p), seg);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+extern "C" int ogg_runoff_accumulate_dev(const ogg_runoff_params* p, const void* f, const int* src_cell, long n_mapped, const double* area,
+                                         long lda, const void* workspace, long workspace_bytes, double* values, int* n_sources,
+                                         ogg_runoff_counts* counts, void* stream) {
+    if (int e = check_params(p)) return e;
+    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_runoff_accumulate")) return e;
+    OGG_REQUIRE(n_mapped >= 0 && n_mapped <= nsrc_of(*p), OGG_EARG, "ogg_runoff_accumulate: %ld mapped of %ld source cells", n_mapped,
+                nsrc_of(*p));
+    OGG_REQUIRE(f && area && values && n_sources && counts && (src_cell || n_mapped == 0), OGG_EARG,
+                "ogg_runoff_accumulate: null f / src_cell / area / values / n_sources / counts");
+    OGG_REQUIRE(lda >= 2 * p->nx, OGG_EARG, "ogg_runoff_accumulate: area row stride %ld < 2 nx", lda);
+    hipStream_t st = ogg::as_stream(stream);
+    const Layout l = layout(*p);
+    const unsigned long long* key = at<unsigned long long>(workspace, (merge_passes(n_mapped) & 1) ? l.key1 : l.key0);
+    const Geo g{p->ny, p->nx, nsrc_of(*p), p->nrec, lda, p->n_fill, p->fill[0], p->fill[1]};
+    const long waves = p->ny * ((p->nx + 63) / 64);
+    const unsigned grid = (unsigned)((waves + NT / 64 - 1) / (NT / 64));
+    const int2* seg = at<int2>(workspace, l.seg);
+    const double* As = at<double>(workspace, l.As);
+    if (p->dtype == OGG_REMAP_FLOAT32)
+        accumulate_kernel<float><<<grid, NT, 0, st>>>(g, static_cast<const float*>(f), seg, key, src_cell, As, area, values, n_sources, counts);
+    else
+        accumulate_kernel<double><<<grid, NT, 0, st>>>(g, static_cast<const double*>(f), seg, key, src_cell, As, area, values, n_sources,
+                                                       counts);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+// the host-pointer form: everything copied to device memory, the five steps, the results copied back (synchronous)
+extern "C" int ogg_runoff(const ogg_runoff_params* p, const double* x, const double* y, const double* area, const unsigned char* wet,
+                          const void* f, const double* lon, const double* lat, double* values, int* n_sources, int* src_cell, int* src_target,
+                          double* src_d2, ogg_runoff_counts* counts) {
+    if (int e = check_params(p)) return e;
+    OGG_REQUIRE(x && y && area && wet && f && lon && lat && values && n_sources && src_cell && src_target && src_d2 && counts, OGG_EARG,
+                "ogg_runoff: null argument");
+    struct Buffers {   // freed on every exit path
+        std::vector<void*> p;
+        ~Buffers() {
+            for (void* q : p) (void)hipFree(q);
+        }
+        int alloc(void** out, size_t bytes) {
+            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
+            if (e != hipSuccess)
+                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
+                                      hipGetErrorString(e));
+            p.push_back(*out);
+            return OGG_OK;
+        }
+    } bufs;
+    const size_t nc = (size_t)ncell_of(*p), ns = (size_t)nsrc_of(*p), npt = (size_t)(2 * p->ny + 1) * (2 * p->nx + 1);
+    const size_t fbytes = (size_t)p->nrec * ns * (p->dtype == OGG_REMAP_FLOAT32 ? 4 : 8);
+    const long wsb = layout(*p).total;
+    void *dx, *dy, *da, *dw, *df, *dlon, *dlat, *ws, *tc, *tu, *sc, *su, *sds, *st, *sd, *dv, *dn, *ct;
+    if (int e = bufs.alloc(&dx, npt * 8)) return e;
+    if (int e = bufs.alloc(&dy, npt * 8)) return e;
+    if (int e = bufs.alloc(&da, nc * 4 * 8)) return e;
+    if (int e = bufs.alloc(&dw, nc)) return e;
+    if (int e = bufs.alloc(&df, fbytes)) return e;
+    if (int e = bufs.alloc(&dlon, (size_t)(p->NA + 1) * 8)) return e;
+    if (int e = bufs.alloc(&dlat, (size_t)(p->NB + 1) * 8)) return e;
+    if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
+    if (int e = bufs.alloc(&tc, nc * 4)) return e;
+    if (int e = bufs.alloc(&tu, nc * 24)) return e;
+    if (int e = bufs.alloc(&sc, ns * 4)) return e;
+    if (int e = bufs.alloc(&su, ns * 24)) return e;
+    if (int e = bufs.alloc(&sds, (size_t)p->NB * 8)) return e;
+    if (int e = bufs.alloc(&st, ns * 4)) return e;
+    if (int e = bufs.alloc(&sd, ns * 8)) return e;
+    if (int e = bufs.alloc(&dv, (size_t)p->nrec * nc * 8)) return e;
+    if (int e = bufs.alloc(&dn, nc * 4)) return e;
+    if (int e = bufs.alloc(&ct, sizeof(ogg_runoff_counts))) return e;
+    OGG_HIP_CHECK(hipMemcpy(dx, x, npt * 8, hipMemcpyHostToDevice));
+    OGG_HIP_CHECK(hipMemcpy(dy, y, npt * 8, hipMemcpyHostToDevice));
+    OGG_HIP_CHECK(hipMemcpy(da, area, nc * 4 * 8, hipMemcpyHostToDevice));
+    OGG_HIP_CHECK(hipMemcpy(dw, wet, nc, hipMemcpyHostToDevice));
+    OGG_HIP_CHECK(hipMemcpy(df, f, fbytes, hipMemcpyHostToDevice));
+    OGG_HIP_CHECK(hipMemcpy(dlon, lon, (size_t)(p->NA + 1) * 8, hipMemcpyHostToDevice));
+    OGG_HIP_CHECK(hipMemcpy(dlat, lat, (size_t)(p->NB + 1) * 8, hipMemcpyHostToDevice));
+    ogg_runoff_counts* dct = static_cast<ogg_runoff_counts*>(ct);
+    if (int e = ogg_runoff_targets_dev(p, static_cast<double*>(dx), static_cast<double*>(dy), 2 * p->nx + 1, static_cast<unsigned char*>(dw),
+                                       ws, wsb, static_cast<int*>(tc), static_cast<double*>(tu), dct, nullptr))
+        return e;
+    if (int e = ogg_runoff_sources_dev(p, df, static_cast<double*>(dlon), static_cast<double*>(dlat), ws, wsb, static_cast<int*>(sc),
+                                       static_cast<double*>(su), static_cast<double*>(sds), dct, nullptr))
+        return e;
+    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_runoff_counts), hipMemcpyDeviceToHost));
+    const long nt = (long)counts->targets, nm = (long)counts->mapped;
+    if (int e = ogg_runoff_search_dev(p, static_cast<int*>(tc), static_cast<double*>(tu), nt, static_cast<double*>(su), nm, ws, wsb,
+                                      static_cast<int*>(st), static_cast<double*>(sd), dct, nullptr))
+        return e;
+    if (int e = ogg_runoff_segments_dev(p, static_cast<int*>(st), nm, ws, wsb, nullptr)) return e;
+    if (int e = ogg_runoff_accumulate_dev(p, df, static_cast<int*>(sc), nm, static_cast<double*>(da), 2 * p->nx, ws, wsb,
+                                          static_cast<double*>(dv), static_cast<int*>(dn), dct, nullptr))
+        return e;
+    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_runoff_counts), hipMemcpyDeviceToHost));
+    OGG_HIP_CHECK(hipMemcpy(values, dv, (size_t)p->nrec * nc * 8, hipMemcpyDeviceToHost));
+    OGG_HIP_CHECK(hipMemcpy(n_sources, dn, nc * 4, hipMemcpyDeviceToHost));
+    if (nm > 0) {
+        OGG_HIP_CHECK(hipMemcpy(src_cell, sc, (size_t)nm * 4, hipMemcpyDeviceToHost));
+        OGG_HIP_CHECK(hipMemcpy(src_target, st, (size_t)nm * 4, hipMemcpyDeviceToHost));
+        OGG_HIP_CHECK(hipMemcpy(src_d2, sd, (size_t)nm * 8, hipMemcpyDeviceToHost));
+    }
+    return OGG_OK;
+}

@@ -42,14 +42,21 @@ def _att_list(atts):
 class Dataset(object):
     """dims: [(name, length)], in order.  Variables are added with def_var (host array) or decl_var (layout only: the data is
     streamed into the file by the caller at var_begin(name)); write() writes header and host arrays, write_header() the header
-    alone."""
+    alone.  ``record_dim`` (opt-in): the name of one dimension written as the unlimited (record) dimension; the variables whose first
+    dimension it is are record variables, stored after the fixed-size ones one record at a time (write() only)."""
 
-    def __init__(self, path, dims, global_atts=()):
+    def __init__(self, path, dims, global_atts=(), record_dim=None):
         self.path = path
         self.dims = list(dims)
         self.gatts = list(global_atts)
         self.vars = []  # (name, nc_type, dim names, attrs, array or None)
         self._layout = None
+        if record_dim is not None and record_dim not in dict(self.dims):
+            raise ValueError("record dimension %s is not one of the dimensions" % record_dim)
+        self.record_dim = record_dim
+
+    def _is_record(self, v):
+        return self.record_dim is not None and len(v[2]) > 0 and v[2][0] == self.record_dim
 
     def _shape(self, dim_names):
         return tuple(dict(self.dims)[d] for d in dim_names)
@@ -69,6 +76,9 @@ class Dataset(object):
     def layout(self):
         """(header bytes, [begin offset of each variable], [byte size of each variable], total file size)"""
         if self._layout is not None:
+            return self._layout
+        if self.record_dim is not None:
+            self._layout = self._record_layout()
             return self._layout
         dimid = {n: k for k, (n, _) in enumerate(self.dims)}
         esize = {NC_CHAR: 1, NC_BYTE: 1, NC_SHORT: 2, NC_INT: 4, NC_FLOAT: 4, NC_DOUBLE: 8}
@@ -97,6 +107,43 @@ class Dataset(object):
         self._layout = (head + var_list + body, begins, sizes, begin)
         return self._layout
 
+    def _record_layout(self):
+        """layout() with a record dimension: for a record variable the size is that of one record (padded to 4 bytes unless it is the
+        only record variable) and the begin that of its slab in record 0; the file's records follow the fixed-size data."""
+        dimid = {n: k for k, (n, _) in enumerate(self.dims)}
+        esize = {NC_CHAR: 1, NC_BYTE: 1, NC_SHORT: 2, NC_INT: 4, NC_FLOAT: 4, NC_DOUBLE: 8}
+        nrec = dict(self.dims)[self.record_dim]
+        recs = [v for v in self.vars if self._is_record(v)]
+
+        def size(v):
+            shape = self._shape(v[2][1:] if self._is_record(v) else v[2])
+            n = int(np.prod(shape, dtype=np.int64)) * esize[v[1]]
+            return n + (_pad4(n) if not (self._is_record(v) and len(recs) == 1) else 0)
+
+        def var_header(name, nc_type, dnames, atts, vsize, begin):
+            h = _name(name) + struct.pack(">i", len(dnames)) + b"".join(struct.pack(">i", dimid[d]) for d in dnames)
+            return h + _att_list(atts) + struct.pack(">iI", nc_type, min(vsize, 2 ** 32 - 1)) + struct.pack(">q", begin)
+
+        head = b"CDF\x02" + struct.pack(">i", nrec)
+        head += struct.pack(">ii", NC_DIMENSION, len(self.dims)) + b"".join(
+            _name(n) + struct.pack(">i", 0 if n == self.record_dim else l) for n, l in self.dims)
+        head += _att_list(self.gatts)
+        sizes = [size(v) for v in self.vars]
+        var_list = struct.pack(">ii", NC_VARIABLE, len(self.vars)) if self.vars else _ABSENT
+        begin = len(head + var_list + b"".join(var_header(v[0], v[1], v[2], v[3], s, 0) for v, s in zip(self.vars, sizes)))
+        begins = [0] * len(self.vars)
+        for k, v in enumerate(self.vars):
+            if not self._is_record(v):
+                begins[k] = begin
+                begin += sizes[k]
+        recsize = 0
+        for k, v in enumerate(self.vars):
+            if self._is_record(v):
+                begins[k] = begin + recsize
+                recsize += sizes[k]
+        body = b"".join(var_header(v[0], v[1], v[2], v[3], s, b) for v, s, b in zip(self.vars, sizes, begins))
+        return (head + var_list + body, begins, sizes, begin + nrec * recsize)
+
     def var_begin(self, name):
         _, begins, _, _ = self.layout()
         return begins[[v[0] for v in self.vars].index(name)]
@@ -109,6 +156,8 @@ class Dataset(object):
         os.pwrite(fd, header, 0)
 
     def write(self, chunk_rows=256):
+        if self.record_dim is not None:
+            return self._write_records()
         header, begins, sizes, _ = self.layout()
         with open(self.path, "wb") as f:
             f.write(header)
@@ -124,6 +173,27 @@ class Dataset(object):
                     for r0 in range(0, flat.shape[0], chunk_rows):
                         f.write(np.ascontiguousarray(flat[r0:r0 + chunk_rows]).astype(_NUMPY_TYPE[v[1]]).tobytes())
                 f.write(b"\0" * _pad4(s))
+
+
+    def _write_records(self):
+        header, begins, sizes, total = self.layout()
+        for v in self.vars:
+            if v[4] is None:
+                raise ValueError("variable %s was declared without data: a file with a record dimension is written whole" % v[0])
+        with open(self.path, "wb") as f:
+            f.write(header)
+            for v, s, b in zip(self.vars, sizes, begins):
+                if self._is_record(v):
+                    continue
+                assert f.tell() == b
+                raw = np.ascontiguousarray(v[4]).astype(_NUMPY_TYPE.get(v[1], "S1")).tobytes()
+                f.write(raw + b"\0" * (s - len(raw)))
+            recs = [(v, s) for v, s in zip(self.vars, sizes) if self._is_record(v)]
+            for r in range(dict(self.dims)[self.record_dim]):
+                for v, s in recs:
+                    raw = np.ascontiguousarray(v[4][r]).astype(_NUMPY_TYPE.get(v[1], "S1")).tobytes()
+                    f.write(raw + b"\0" * (s - len(raw)))
+            assert f.tell() == total
 
 
 # ---- reader ------------------------------------------------------------------------------------------------------
@@ -246,6 +316,35 @@ def read_var_bytes(path, header, name, dtype=NC_DOUBLE):
     if len(b) != n:
         raise ValueError("%s: %s is truncated" % (path, name))
     return b
+
+
+def read_record_var_bytes(path, header, name, dtype=NC_DOUBLE):
+    """The raw (big-endian) bytes of a record variable, its records one after the other (the file interleaves them with the
+    other record variables: one record of every record variable after the other, each slab padded to 4 bytes unless the file has a
+    single record variable)."""
+    if name not in header.vars:
+        raise KeyError("%s: no variable %r" % (path, name))
+    v = header.vars[name]
+    if not v.is_record:
+        raise ValueError("%s: %s is not a record variable" % (path, name))
+    if v.nc_type != dtype:
+        raise ValueError("%s: %s has NetCDF type %d, expected %d" % (path, name, v.nc_type, dtype))
+    recs = [u for u in header.vars.values() if u.is_record]
+
+    def slab(u):
+        n = int(np.prod(u.shape[1:], dtype=np.int64)) * _TYPE_SIZE[u.nc_type]
+        return n + (_pad4(n) if len(recs) > 1 else 0)
+    recsize = sum(slab(u) for u in recs)
+    n = int(np.prod(v.shape[1:], dtype=np.int64)) * _TYPE_SIZE[v.nc_type]
+    out = []
+    with open(path, "rb") as f:
+        for r in range(v.shape[0]):
+            f.seek(v.begin + r * recsize)
+            b = f.read(n)
+            if len(b) != n:
+                raise ValueError("%s: %s is truncated at record %d" % (path, name, r))
+            out.append(b)
+    return b"".join(out)
 
 
 def read_doubles(path, names=("x", "y", "dx", "dy", "area")):

@@ -644,7 +644,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          return_arrays=False, path=None, dp_arc=None, cap_symmetry=None, quality_report=None, topog_source=None, topog_var="elevation",
          topog_file="topog.nc", topog_refine=None, xgrid_atm=None, xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc",
          ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False, mask_seed=None, mask_keep_cells=0,
-         remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None):
+         remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None,
+         runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast"):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -682,12 +683,14 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
                                    mercator_upper_lat, south_ocean_lower_lat, south_ocean_upper_lat, no_south_cap, return_arrays, dp_arc,
                                    cap_symmetry, quality_report, topog_source, topog_var, topog_file, topog_refine, xgrid_atm,
                                    xgrid_file, ocean_mask_file, mask_min_depth, mask_deepen, mask_seed, mask_keep_cells,
-                                   remap_source, remap_var, remap_file, remap_no_fill, remap_fill_max)
+                                   remap_source, remap_var, remap_file, remap_no_fill, remap_fill_max, runoff_source, runoff_var,
+                                   runoff_file, runoff_targets)
     from . import supergrid as SG
 
     _validate_flags(match_dy, r_dp, lat_dp)
     _validate_mask_flags(ocean_mask_file, topog_source)
     _validate_remap_flags(remap_source, remap_var)
+    _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targets, skip_metrics)
     hist, source, desc = _meta_strings(inverse_resolution, no_changing_meta)
     start_time = time.time()
     plan = SG.SupergridPlan(inverse_resolution, r_dp=r_dp, lon_dp=lon_dp, lat_dp=lat_dp, exfracdp=exfracdp, south_cutoff_row=south_cutoff_row,
@@ -729,6 +732,9 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     if remap_source is not None:
         _write_remap([(src, g.remap(cut, src, mask=_xgrid_mask(topo), fill=not remap_no_fill, fill_max=remap_fill_max))
                       for src in _remap_sources(remap_source, remap_var)], remap_file)
+    if runoff_source is not None:
+        _write_runoff([(src, g.runoff(cut, src, _xgrid_mask(topo), targets=runoff_targets))
+                       for src in _runoff_sources(runoff_source, runoff_var)], runoff_file)
     print("Stitching the grids together...")
     SG.check_guards(g.stitched_column("y", plan.Ni // 4, cut), any(s.name == "BP" for s in plan.subs))
     names = [s.name for s in plan.subs if not (s.name == "SC" and cut[2])]
@@ -798,7 +804,8 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
                         topog_var="elevation", topog_file="topog.nc", topog_refine=None, xgrid_atm=None,
                         xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0,
                         mask_deepen=False, mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None,
-                        remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None):
+                        remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None, runoff_source=None, runoff_var=None,
+                        runoff_file="runoff.nc", runoff_targets="coast"):
     """The reference's own sequence of calls (OGG:855-1449), every callee a host-array function of this module (numpy in, numpy
     out, one staged device call each) and the stitching on the host: what a user gets who swaps the reference's module for this
     one function by function.  main() produces the same bits from one device-resident pass."""
@@ -806,6 +813,7 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
 
     _validate_mask_flags(ocean_mask_file, topog_source)
     _validate_remap_flags(remap_source, remap_var)
+    _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targets, skip_metrics)
     known_options = ["bp", "so", "p125sc", ""]
     unknown = list(set(match_dy).difference(known_options))
     if len(unknown) != 0:
@@ -1038,6 +1046,10 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
         from . import remap as R
         _write_remap([(src, R.remap(x3, y3, src, mask=_xgrid_mask(topo), fill=not remap_no_fill, fill_max=remap_fill_max, Re=_default_Re))
                       for src in _remap_sources(remap_source, remap_var)], remap_file)
+    if runoff_source is not None:   # the same values as the device pass gives, through the host-pointer entry
+        from . import runoff as RO
+        _write_runoff([(src, RO.runoff(x3, y3, area3, src, _xgrid_mask(topo), targets=runoff_targets, Re=_default_Re))
+                       for src in _runoff_sources(runoff_source, runoff_var)], runoff_file)
 
     if write_subgrid_files:
         if "SC" in sub:
@@ -1126,6 +1138,19 @@ def _validate_remap_flags(remap_source, remap_var):
         raise ValueError("--remap_source needs at least one --remap_var")
 
 
+def _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targets, skip_metrics):
+    if runoff_source is None:
+        return
+    if skip_metrics:
+        raise ValueError("--runoff_source needs the cell areas: drop --skip_metrics")
+    if not runoff_var:
+        raise ValueError("--runoff_source needs at least one --runoff_var")
+    if topog_source is None:
+        raise ValueError("--runoff_source needs --topog_source: the runoff goes to the wet cells of the topography")
+    if runoff_targets not in ("coast", "wet"):
+        raise ValueError("--runoff_targets must be coast or wet, not %r" % (runoff_targets,))
+
+
 def _mask_args(min_depth, deepen, seeds, keep_cells):
     return dict(min_depth=float(min_depth or 0.0), mode="deepen" if deepen else "mask", seeds=[tuple(s) for s in (seeds or ())],
                 keep_min_cells=int(keep_cells or 0))
@@ -1175,6 +1200,24 @@ def _write_remap(results, fnam):
         for line in R.summary_lines(res):
             print(line)
     R.write_remapped(str(fnam), results)
+
+
+def _runoff_sources(path, names):
+    from . import runoff as RO
+    out = []
+    for name in names:
+        src = RO.read_source(str(path), name)
+        print(src.note)
+        out.append(src)
+    return out
+
+
+def _write_runoff(results, fnam):
+    from . import runoff as RO
+    for _, res in results:
+        for line in RO.summary_lines(res):
+            print(line)
+    RO.write_runoff(str(fnam), results)
 
 
 def build_parser():
@@ -1251,6 +1294,14 @@ def build_parser():
     parser.add_argument("--remap_no_fill", action="store_true", help="leave wet cells the source does not cover unfilled")
     parser.add_argument("--remap_fill_max", type=int, required=False, default=None,
                         help="fill wet cells at most N cells away from a remapped cell (default: no limit)")
+    parser.add_argument("--runoff_source", type=str, required=False, default=None,
+                        help="a global lat-lon runoff file (NetCDF classic / 64-bit offset) whose --runoff_var variables are moved to "
+                             "the nearest coastal wet cells into --runoff_file (needs --topog_source)")
+    parser.add_argument("--runoff_var", type=str, action="append", required=False, default=None,
+                        help="a variable of --runoff_source (repeatable)")
+    parser.add_argument("--runoff_file", type=str, required=False, default="runoff.nc", help="runoff output file, default runoff.nc")
+    parser.add_argument("--runoff_targets", type=str, choices=["coast", "wet"], required=False, default="coast",
+                        help="coast (default): wet cells next to land; wet: every wet cell")
     return parser
 
 

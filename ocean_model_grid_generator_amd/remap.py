@@ -76,12 +76,18 @@ class _Last2(object):
 
 
 def read_source(path, var):
+    """A Source from a NetCDF classic or 64-bit-offset file (_read_source); record (unlimited) variables are refused."""
+    return _read_source(path, var)
+
+
+def _read_source(path, var, records=False):
     """A Source from a NetCDF classic (CDF-1) or 64-bit-offset (CDF-2) file: the byte / short / float / double variable ``var``,
     whose last two dimensions are latitude and longitude in either order (told apart by the coordinates' units or names, as for
     topography), on uniform 1-D coordinates (cell centres or edges).  Latitude edges at centres +- half a step are clamped to +-90;
     rows are flipped when latitude decreases.  A byte or short variable is unpacked to float64 as raw * scale_factor + add_offset,
     with missing values (_FillValue, missing_value, tested on the raw values) as NaN; float and double keep their type and their fill
-    values.  CDF-5 and NetCDF-4 / HDF5 files are refused."""
+    values.  CDF-5 and NetCDF-4 / HDF5 files are refused.  ``records`` (opt-in): a record (unlimited) variable is read too, its
+    record dimension the first leading dimension (the Source's ``record_dim``), and so is the coordinate variable of that dimension."""
     from . import topography as T
     try:
         h = netcdf3.read_header(path)
@@ -95,8 +101,11 @@ def read_source(path, var):
     if v.nc_type not in (netcdf3.NC_BYTE, netcdf3.NC_SHORT, netcdf3.NC_FLOAT, netcdf3.NC_DOUBLE) or len(v.shape) < 2:
         raise ValueError("%s: %s must be a byte, short, float or double variable of two or more dimensions (type %d, shape %s)"
                          % (path, var, v.nc_type, v.shape))
-    if v.is_record:
+    if v.is_record and not records:
         raise ValueError("%s: %s is a record (unlimited) variable; only fixed-size variables are read" % (path, var))
+
+    def raw_bytes(name, u):
+        return (netcdf3.read_record_var_bytes if u.is_record else netcdf3.read_var_bytes)(path, h, name, dtype=u.nc_type)
     lat_name, lon_name = T._lat_lon_dims(path, h, _Last2(v))
     axes = {}
     for dname in (lat_name, lon_name):
@@ -105,7 +114,7 @@ def read_source(path, var):
         cv = h.vars[dname]
         raw = netcdf3.read_var_bytes(path, h, dname, dtype=cv.nc_type)
         axes[dname] = T._uniform_axis(path, dname, np.frombuffer(raw, dtype=netcdf3.NUMPY_DTYPE[cv.nc_type]))
-    data = np.frombuffer(netcdf3.read_var_bytes(path, h, var, dtype=v.nc_type), dtype=netcdf3.NUMPY_DTYPE[v.nc_type]).reshape(v.shape)
+    data = np.frombuffer(raw_bytes(var, v), dtype=netcdf3.NUMPY_DTYPE[v.nc_type]).reshape(v.shape)
     data = data.astype(data.dtype.newbyteorder("="))
     if v.dims[-2] == lon_name:   # stored (..., lon, lat)
         data = np.swapaxes(data, -1, -2)
@@ -146,15 +155,17 @@ def read_source(path, var):
     coords = []
     for d, _ in lead:
         cv = h.vars.get(d)
-        if cv is not None and len(cv.shape) == 1 and not cv.is_record and cv.nc_type != netcdf3.NC_CHAR:
-            vals = np.frombuffer(netcdf3.read_var_bytes(path, h, d, dtype=cv.nc_type), dtype=netcdf3.NUMPY_DTYPE[cv.nc_type])
+        if cv is not None and len(cv.shape) == 1 and (records or not cv.is_record) and cv.nc_type != netcdf3.NC_CHAR:
+            vals = np.frombuffer(raw_bytes(d, cv), dtype=netcdf3.NUMPY_DTYPE[cv.nc_type])
             atts = [(k, a if isinstance(a, str) else np.asarray(a).reshape(-1)[0].item()) for k, a in cv.atts.items()
                     if isinstance(a, str) or np.asarray(a).size == 1]
             coords.append((d, cv.nc_type, atts, vals))
     keep = [(k, a) for k, a in v.atts.items() if k in ("units", "long_name", "standard_name") and isinstance(a, str)]
     note = "%s: %s %s, %d records of %d x %d cells, longitude coordinates taken as cell %s, latitude as cell %s" % (
         path, var, tuple(v.dims), int(np.prod(v.shape[:-2], dtype=np.int64)), NB, NA, kind_lon, kind_lat)
-    return Source(data, lon_edges, lat_edges, fill=fills, name=var, lead_dims=lead, coords=coords, atts=keep, note=note)
+    src = Source(data, lon_edges, lat_edges, fill=fills, name=var, lead_dims=lead, coords=coords, atts=keep, note=note)
+    src.record_dim = v.dims[0] if v.is_record else None
+    return src
 
 
 # ---- arguments -----------------------------------------------------------------------------------------------

@@ -1459,6 +1459,29 @@ class Supergrid(object):
         got.sort(key=lambda e: e[0])
         return (torch.cat([e[1].to(self.device) for e in got]).contiguous(), torch.cat([e[2].to(self.device) for e in got]).contiguous())
 
+    def stitched_area(self, cut):
+        """The stitched supergrid area ((nyp - 1, nxp - 1) float64 device tensor) on rank 0's device, None on the other ranks: every
+        piece's cell rows gathered in piece order (_gather), as stitched_xy gathers the points."""
+        torch, nx = self.torch, self.plan.Ni
+        if self.plan.skip_metrics:
+            raise ValueError("the supergrid area is not computed with --skip_metrics")
+
+        def records(g):
+            out = []
+            for k, q in enumerate(g.quality_pieces(cut)):
+                if q["rank"] == g.rank and q["n_cell"] > 0:
+                    b = g.buf[q["sub"].name]
+                    out.append((k, b["area"][q["row"]:q["row"] + q["n_cell"]].to(self.device)))
+            return out
+
+        def recv(k, q, take):
+            return (k, take((q["n_cell"], nx), torch.float64)) if q["n_cell"] > 0 else None
+        got = self._gather(self.quality_pieces(cut), records, lambda e: (e[1].contiguous(),), recv)
+        if got is None:
+            return None
+        got.sort(key=lambda e: e[0])
+        return torch.cat([e[1].to(self.device) for e in got]).contiguous()
+
     def ocean_mask(self, cut, topo, min_depth=0.0, mode="mask", seeds=(), keep_min_cells=0):
         """The ocean mask (ocean_mask.result on rank 0, None on the other ranks) of the topography ``topo`` that topography() gathered on
         rank 0, computed on rank 0's GPU with the stitched grid gathered there: the same for any number of ranks by construction."""
@@ -1525,6 +1548,18 @@ class Supergrid(object):
             R.fill_dev(p, values, flags, counts, self._stream(), self.device)
         return R.result(values.cpu().numpy(), flags.cpu().numpy(), R.counts_dict(counts.cpu().numpy()), source, periodic, fold, fill,
                         fill_max, hm is not None)
+
+    # -- runoff mapping -----------------------------------------------------------------------------------------------
+    def runoff(self, cut, source, wet, targets="coast"):
+        """The runoff mapping (runoff.result on rank 0, None on the other ranks) of ``source`` (a remap.Source) onto the model cells of
+        the stitched grid with the wet set ``wet`` (one value per model cell, 0: land), on rank 0's GPU with the stitched points and
+        area gathered there, as ocean_mask does: the same bits for any number of ranks by construction."""
+        from . import runoff as RO
+        xy = self.stitched_xy(cut)
+        area = self.stitched_area(cut)
+        if xy is None:
+            return None
+        return RO.runoff_dev(xy[0], xy[1], area, source, wet, targets=targets, Re=float(self.plan.Re))
 
     def bands_to_host(self):
         """This rank's bands as numpy arrays (halo rows dropped): {sub: {field: array}}."""
