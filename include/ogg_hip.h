@@ -863,6 +863,69 @@ int ogg_runoff(const ogg_runoff_params* p, const double* x, const double* y, con
                const void* f, const double* lon, const double* lat, double* values, int* n_sources, int* src_cell, int* src_target,
                double* src_d2, ogg_runoff_counts* counts);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Conservative regrid to a lat-lon grid (an addition: the reference has none).  Fields on the model cells aggregated first-order
+ * conservatively onto the cells of a global rectilinear grid: the remap's direction reversed, with the same exchange list as weights.
+ *   target   edges lon (NA + 1) and lat (NB + 1) as ogg_xgrid_check_atm accepts them; cell k = J * NA + I; A_atm(J, I) its area by
+ *            the keep step's formula of the exchange grid, passed in by the caller (a_atm, NB x NA fp64: exchange_grid.atm_area forms
+ *            it on the host, so the device's fractions and the host's share it bit for bit).  The calls take neither the edges nor a
+ *            check of a_atm: the CALLER is responsible for a_atm belonging to the edges the list was built with (it is used as given).
+ *   field    g[r][m][n], r < nrec, (m, n) the ny x nx model cells of the stitched grid, float32 or fp64 (dtype; float32 converted
+ *            exactly to fp64).  A value is MISSING when it is NaN or equals one of the n_fill <= 2 fill values, compared in the
+ *            field's own type (the remap's rule).
+ *   weights  the list of ogg_xgrid between the target edges (as the atmosphere) and the model cells, same threshold, optional uint8
+ *            wet mask, in list order (the canonical order Supergrid.exchange_grid gathers).
+ *   transpose  the entries of target cell k in ASCENDING list position (the keys (k << 32) | position are unique, so any correct
+ *            sort gives this permutation).
+ *   static   W0_k = sum A_e over every entry of k, left to right from +0.0 in fp64, no FMA (what np.bincount(k, weights=area) gives);
+ *            ocean_frac_k = W0_k / A_atm; n_entries_k.
+ *   records  W = sum A_e and S = sum (A_e * g_e) over the entries whose value is not missing, left to right from +0.0, each product
+ *            rounded before it is added.  OGG_REGRID_AREA: value S / W when W > 0, else OGG_REMAP_FILL (the mean over the part of
+ *            the cell with valid values).  OGG_REGRID_CELL: value S / A_atm, 0 where W = 0 (conserves a flux over the whole cell).
+ *            cover (optional) = W / A_atm.
+ * Every output is a fixed function of the list, the field and a_atm: BIT-IDENTICAL for any launch geometry (the OGG_REGRID_* knobs),
+ * run and, on the gathered list, rank count.  Output layout: values and cover (nrec, NB, NA) fp64, record-major; frac (NB, NA) fp64 and
+ * n_entries (NB, NA) int32.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { OGG_REGRID_AREA = 0, OGG_REGRID_CELL = 1 };
+enum { OGG_REGRID_PARAMS = 0, OGG_REGRID_COUNTS = 1 };
+/* ny * nx < 2^31, NA * NB < 2^31, nrec * NB * NA < 2^32; list length < 2^31 (the calls) */
+typedef struct ogg_regrid_params {
+    long ny, nx;               /* model cells */
+    long NA, NB, nrec;         /* target cells and records */
+    int dtype;                 /* OGG_REMAP_FLOAT32 / FLOAT64 */
+    int n_fill;                /* 0 .. OGG_REMAP_MAX_FILLS */
+    double fill[2];            /* the values that mark missing */
+    int normalize;             /* OGG_REGRID_AREA / OGG_REGRID_CELL */
+} ogg_regrid_params;
+typedef struct ogg_regrid_counts {
+    long long entries;         /* list entries transposed (transpose step) */
+    long long bad_entries;     /* list entries outside the cells or the target (a list of other edges or rows): refuse the result */
+    long long cells;           /* target cells with entries (regrid step) */
+    long long max_entries;     /* the largest n_entries (regrid step) */
+    long long valid;           /* (record, cell) pairs with W > 0 (regrid step) */
+    long long empty;           /* (record, cell) pairs with W = 0 (regrid step) */
+} ogg_regrid_counts;
+long ogg_regrid_struct_bytes(int which);                                    /* sizeof of OGG_REGRID_PARAMS / COUNTS, -1 otherwise */
+long ogg_regrid_workspace_bytes(const ogg_regrid_params* p, long n_entries); /* of both steps, -1 on a bad *p or length */
+/* the checks of *p (sizes, dtype, n_fill, normalize): OGG_EARG with the reason, before any device work */
+int ogg_regrid_check(const ogg_regrid_params* p);
+/* transpose step, device pointers, on a stream: the list (atm_ij, ocn_ij, area; n_entries entries as ogg_xgrid_write_dev writes
+ * them) grouped by target cell in ascending list position, into the workspace; *counts (device memory) is zeroed and gets entries and
+ * bad_entries. */
+int ogg_regrid_transpose_dev(const ogg_regrid_params* p, const int* atm_ij, const int* ocn_ij, const double* area, long n_entries,
+                             void* workspace, long workspace_bytes, ogg_regrid_counts* counts, void* stream);
+/* regrid step, after the transpose step on the same workspace and list length n_list: f the field (nrec * ny * nx values of dtype;
+ * NULL with values NULL), a_atm (NB * NA); values, cover, frac, n_entries each NULL or as above (values NULL: no record is read, the
+ * static sums only).  Every call sets cells and max_entries in *counts, and valid and empty (0 without values), from zero; entries and
+ * bad_entries stay the transpose step's.  The workspace keeps the transpose; the step also writes its list of long cells there. */
+int ogg_regrid_dev(const ogg_regrid_params* p, const void* f, const double* a_atm, long n_list, void* workspace, long workspace_bytes,
+                   double* values, double* cover, double* frac, int* n_entries, ogg_regrid_counts* counts, void* stream);
+/* HOST pointers throughout, staged through device memory: both steps on the list atm_ij / ocn_ij / area of n_entries entries; f and
+ * values NULL together (the static sums only), cover / frac / n_out NULL to skip. */
+int ogg_regrid(const ogg_regrid_params* p, const void* f, const int* atm_ij, const int* ocn_ij, const double* area, long n_entries,
+               const double* a_atm, double* values, double* cover, double* frac, int* n_out, ogg_regrid_counts* counts);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

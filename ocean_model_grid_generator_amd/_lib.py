@@ -173,6 +173,24 @@ RUNOFF_PARAMS, RUNOFF_COUNTS = 0, 1                                    # OGG_RUN
 RUNOFF_MAX_BINS = 160                                                  # OGG_RUNOFF_MAX_BINS
 
 
+class RegridParams(ctypes.Structure):
+    """ogg_regrid_params of include/ogg_hip.h"""
+    _fields_ = [("ny", c_long), ("nx", c_long), ("NA", c_long), ("NB", c_long), ("nrec", c_long), ("dtype", c_int), ("n_fill", c_int),
+                ("fill", c_double * 2), ("normalize", c_int)]
+
+
+REGRID_COUNT_FIELDS = ("entries", "bad_entries", "cells", "max_entries", "valid", "empty")
+
+
+class RegridCounts(ctypes.Structure):
+    """ogg_regrid_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in REGRID_COUNT_FIELDS]
+
+
+REGRID_AREA, REGRID_CELL = 0, 1                                        # OGG_REGRID_AREA, OGG_REGRID_CELL
+REGRID_PARAMS, REGRID_COUNTS = 0, 1                                    # OGG_REGRID_PARAMS, OGG_REGRID_COUNTS
+
+
 # name -> argtypes; every function returns int except the two string getters.  Must list EVERY symbol of ogg_hip.h
 # (tests/test_abi.py checks this list against the header).
 SIGNATURES = {
@@ -316,6 +334,12 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p],
     "ogg_runoff": [ctypes.POINTER(RunoffParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                    c_void_p, c_void_p, c_void_p, ctypes.POINTER(RunoffCounts)],
+    "ogg_regrid_check": [ctypes.POINTER(RegridParams)],
+    "ogg_regrid_transpose_dev": [ctypes.POINTER(RegridParams), c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p],
+    "ogg_regrid_dev": [ctypes.POINTER(RegridParams), c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
+                       c_void_p, c_void_p],
+    "ogg_regrid": [ctypes.POINTER(RegridParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
+                   c_void_p, ctypes.POINTER(RegridCounts)],
     "ogg_event_create": [ctypes.POINTER(c_void_p)],
     "ogg_event_destroy": [c_void_p],
     "ogg_event_record": [c_void_p, c_void_p],
@@ -346,7 +370,9 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_remap_struct_bytes": [c_int],
                 "ogg_remap_workspace_bytes": [ctypes.POINTER(RemapParams)],
                 "ogg_runoff_struct_bytes": [c_int],
-                "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)]}
+                "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],
+                "ogg_regrid_struct_bytes": [c_int],
+                "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long]}
 
 _lib = None
 

@@ -1,0 +1,631 @@
+// Conservative regrid of model-cell fields onto a lat-lon grid (include/ogg_hip.h, "Conservative regrid to a lat-lon grid"): the
+// exchange list transposed from model-cell order to target-cell order, then a segmented, masked, weighted sum per target cell.
+//
+// transpose          count_kernel counts the entries of every target cell (atomicAdd) and a three-kernel exclusive scan turns the
+//                    counts into segment starts.  The entries themselves are ordered by their keys (k << 32) | position with the
+//                    shared key sort (ogg_keysort.h): key_block_kernel sorts runs of 256 keys in LDS, keysort_merge_kernel merges runs
+//                    in pairs, O(n log n) whatever the lengths of the segments (a zonal or one-cell target puts the whole list in a
+//                    few).  The keys are unique and sort by cell, then position, so every segment comes out in ascending list
+//                    position; entries outside the cells or the target take k = NA * NB and sort last.  pairs_kernel writes the
+//                    sorted (model cell, area) pairs.
+// regrid_kernel<T,R> one lane per target cell of at most OGG_REGRID_LONG entries, 64 consecutive cells per wavefront; a lane walks its
+//                    own segment left to right for R records at once (OGG_REGRID_RECORDS): each entry's (cell, area) is read once
+//                    for the R records, whose R gathers are independent loads in flight together.
+// regrid_long_kernel one wavefront per longer target cell and group of R records (blockIdx.y), the cells taken from a list the static
+//                    step builds: 64 entries at a time, every lane gathers one entry's R values, and the sums take them in list order
+//                    through shuffles (the remap's long path), so no lane walks a long cell alone.
+// static_kernel      one lane per target cell: n_entries, the long-cell list, and for the other cells W0 (every entry, in order) and
+//                    ocean_frac = W0 / A_atm; static_long_kernel the same sum for the long cells by whole wavefronts.
+//
+// Every value is a fixed function of the list, the field and A_atm: the in-order sums are the definition's on either path, so nothing
+// depends on the launch geometry, the knobs or the order in which the atomics land (the long-cell list's order decides only which
+// wavefront takes a cell).
+#include <algorithm>
+#include <climits>
+#include <cstddef>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "ogg_common.h"
+#include "ogg_keysort.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int NT = 256;                 // threads per workgroup of the list passes (four wavefronts)
+constexpr int PER = 8;                  // items per thread of the scan
+constexpr int CH = NT * PER;            // items per scan block
+constexpr int LONG_DEFAULT = 512;       // cells with more entries are walked by whole wavefronts (OGG_REGRID_LONG)
+constexpr int LONG_WAVES = 4096;        // wavefronts of the long-cell kernels (per record group)
+constexpr int RECORDS_DEFAULT = 4;      // records a lane sums at once (OGG_REGRID_RECORDS)
+constexpr long HEAD = 256;              // workspace head: the length of the long-cell list (int64)
+
+static_assert(sizeof(ogg_regrid_params) == 72, "ogg_regrid_params layout");
+static_assert(sizeof(ogg_regrid_counts) == 48, "ogg_regrid_counts layout");
+
+__device__ inline unsigned long long* ull(long long* p) { return reinterpret_cast<unsigned long long*>(p); }
+
+template <int K>
+__device__ inline void block_add(long long (&v)[K], long long* const (&dst)[K]) {
+    __shared__ long long part[NT / 64][K];
+    for (int k = 0; k < K; ++k)
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < K; ++k) part[threadIdx.x / 64][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x < K) {
+        long long t = 0;
+        for (int w = 0; w < NT / 64; ++w) t += part[w][threadIdx.x];
+        if (t) atomicAdd(ull(dst[threadIdx.x]), (unsigned long long)t);
+    }
+}
+
+// exclusive prefix of v over the workgroup; *total the sum
+__device__ inline long long block_scan(long long v, long long* total) {
+    __shared__ long long wsum[NT / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x / 64;
+    long long incl = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    long long base = 0, tot = 0;
+    for (int k = 0; k < NT / 64; ++k) {
+        if (k < w) base += wsum[k];
+        tot += wsum[k];
+    }
+    __syncthreads();
+    *total = tot;
+    return base + incl - v;
+}
+
+// ---- transpose -----------------------------------------------------------------------------------------------------
+struct List {
+    long n, ny, nx, NA, NB;
+};
+
+// the target cell of entry e, -1 when the entry lies outside the cells or the target
+__device__ inline long target_of(const List& l, const int* atm, const int* ocn, long e) {
+    const long I = atm[2 * e], J = atm[2 * e + 1], i = ocn[2 * e], m = ocn[2 * e + 1];
+    if (I < 0 || I >= l.NA || J < 0 || J >= l.NB || i < 0 || i >= l.nx || m < 0 || m >= l.ny) return -1;
+    return J * l.NA + I;
+}
+
+__global__ __launch_bounds__(NT) void count_kernel(List l, const int* __restrict__ atm, const int* __restrict__ ocn, int* __restrict__ cnt,
+                                                   ogg_regrid_counts* counts) {
+    long long v[2] = {0, 0};
+    for (long e = (long)blockIdx.x * NT + threadIdx.x; e < l.n; e += (long)gridDim.x * NT) {
+        const long k = target_of(l, atm, ocn, e);
+        if (k < 0) {
+            ++v[1];
+            continue;
+        }
+        atomicAdd(&cnt[k], 1);
+        ++v[0];
+    }
+    long long* const dst[2] = {&counts->entries, &counts->bad_entries};
+    block_add<2>(v, dst);
+}
+
+// bsum[b] = the sum of cnt over block b (CH items)
+__global__ __launch_bounds__(NT) void scan_count_kernel(const int* __restrict__ in, long n, long long* __restrict__ bsum) {
+    const long b0 = (long)blockIdx.x * CH;
+    long long v = 0;
+    for (int k = 0; k < PER; ++k) {
+        const long i = b0 + k * NT + threadIdx.x;
+        if (i < n) v += in[i];
+    }
+    long long tot;
+    (void)block_scan(v, &tot);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+// exclusive scan of the nb block sums in place (one workgroup)
+__global__ __launch_bounds__(NT) void scan_blocks_kernel(long long* bsum, long nb) {
+    long long carry = 0;
+    for (long base = 0; base < nb; base += NT) {
+        const long i = base + threadIdx.x;
+        const long long v = i < nb ? bsum[i] : 0;
+        long long tot;
+        const long long ex = block_scan(v, &tot);
+        if (i < nb) bsum[i] = carry + ex;
+        carry += tot;
+    }
+}
+
+// seg[i] = the sum of cnt[i'] for i' < i, i <= n (seg[n]: the total); PER consecutive items per thread
+__global__ __launch_bounds__(NT) void scan_write_kernel(const int* __restrict__ in, long n, const long long* __restrict__ bsum,
+                                                        int* __restrict__ seg) {
+    const long i0 = (long)blockIdx.x * CH + (long)threadIdx.x * PER;
+    long long v[PER], s = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        v[k] = i0 + k < n ? in[i0 + k] : 0;
+        s += v[k];
+    }
+    long long tot;
+    long long run = bsum[blockIdx.x] + block_scan(s, &tot);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        if (i0 + k <= n) seg[i0 + k] = (int)run;
+        run += v[k];
+    }
+}
+
+// keys (k << 32) | position of KEYSORT_NT consecutive entries sorted in LDS by rank (the keys are unique)
+__global__ __launch_bounds__(KEYSORT_NT) void key_block_kernel(List l, long nk, const int* __restrict__ atm, const int* __restrict__ ocn,
+                                                               unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long lk[KEYSORT_NT];
+    const long e = (long)blockIdx.x * KEYSORT_NT + threadIdx.x;
+    unsigned long long key = ULLONG_MAX;
+    if (e < l.n) {
+        const long k = target_of(l, atm, ocn, e);
+        key = ((unsigned long long)(k < 0 ? nk : k) << 32) | (unsigned long long)e;
+    }
+    lk[threadIdx.x] = key;
+    __syncthreads();
+    int rank = 0;
+    for (int q = 0; q < KEYSORT_NT; ++q) rank += lk[q] < key;
+    if (e < l.n) out[(long)blockIdx.x * KEYSORT_NT + rank] = key;
+}
+
+// the (model cell, area) pair of every sorted key of the cells and the target (they come first: the others have k = nk)
+__global__ __launch_bounds__(NT) void pairs_kernel(long n, long nk, long nx, const unsigned long long* __restrict__ key,
+                                                   const int* __restrict__ ocn, const double* __restrict__ area, int* __restrict__ pc,
+                                                   double* __restrict__ pa) {
+    for (long t = (long)blockIdx.x * NT + threadIdx.x; t < n; t += (long)gridDim.x * NT) {
+        const unsigned long long kt = key[t];
+        if ((long)(kt >> 32) >= nk) continue;
+        const long e = (long)(kt & 0xFFFFFFFFull);
+        pc[t] = ocn[2 * e + 1] * (int)nx + ocn[2 * e];
+        pa[t] = area[e];
+    }
+}
+
+// ---- regrid --------------------------------------------------------------------------------------------------------
+struct Geo {
+    long nk, ncell, nrec;
+    int n_fill, cell_norm, long_n;
+    double fill0, fill1;
+};
+
+template <typename T>
+__device__ inline bool missing(T v, T f0, T f1, int nf) {
+    return v != v || (nf > 0 && v == f0) || (nf > 1 && v == f1);
+}
+
+template <typename T, int R>
+__global__ __launch_bounds__(NT) void regrid_kernel(Geo g, const T* __restrict__ f, const int* __restrict__ seg, const int* __restrict__ pc,
+                                                    const double* __restrict__ pa, const double* __restrict__ a_atm,
+                                                    double* __restrict__ out, double* __restrict__ cover, ogg_regrid_counts* counts) {
+    const long k = (long)blockIdx.x * NT + threadIdx.x;
+    const bool inb = k < g.nk;
+    const T f0 = static_cast<T>(g.fill0), f1 = static_cast<T>(g.fill1);
+    int s = 0, e = 0;
+    double A = 1.0;
+    bool mine = false;   // not a long cell: regrid_long_kernel takes those
+    if (inb) {
+        s = seg[k];
+        e = seg[k + 1];
+        A = a_atm[k];
+        mine = e - s <= g.long_n;
+        if (!mine) e = s;
+    }
+    long long v_ok = 0, v_empty = 0;
+    for (long r0 = 0; r0 < g.nrec; r0 += R) {
+        const int nr = g.nrec - r0 < R ? (int)(g.nrec - r0) : R;
+        double W[R], S[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) W[q] = 0.0, S[q] = 0.0;
+        const T* fr = f + r0 * g.ncell;
+        for (int t = s; t < e; ++t) {
+            const long c = pc[t];
+            const double a = pa[t];
+            T v[R];
+#pragma unroll
+            for (int q = 0; q < R; ++q) v[q] = q < nr ? fr[q * g.ncell + c] : T(0);
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                if (!missing(v[q], f0, f1, g.n_fill)) {
+                    W[q] += a;
+                    S[q] += a * (double)v[q];
+                }
+            }
+        }
+        if (mine) {
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                if (q >= nr) break;
+                const long o = (r0 + q) * g.nk + k;
+                double val;
+                if (g.cell_norm) val = W[q] > 0.0 ? S[q] / A : 0.0;
+                else val = W[q] > 0.0 ? S[q] / W[q] : OGG_REMAP_FILL;
+                out[o] = val;
+                if (cover) cover[o] = W[q] / A;
+                if (W[q] > 0.0) ++v_ok;
+                else ++v_empty;
+            }
+        }
+    }
+    long long v[2] = {v_ok, v_empty};
+    long long* const dst[2] = {&counts->valid, &counts->empty};
+    block_add<2>(v, dst);
+}
+
+// one wavefront per long cell and group of R records: the entries 64 at a time, the sums in list order through shuffles
+template <typename T, int R>
+__global__ __launch_bounds__(64) void regrid_long_kernel(Geo g, const T* __restrict__ f, const int* __restrict__ seg, const int* __restrict__ pc,
+                                                         const double* __restrict__ pa, const double* __restrict__ a_atm,
+                                                         const int* __restrict__ longs, const long long* __restrict__ n_long,
+                                                         double* __restrict__ out, double* __restrict__ cover, ogg_regrid_counts* counts) {
+    const int lane = threadIdx.x;
+    const T f0 = static_cast<T>(g.fill0), f1 = static_cast<T>(g.fill1);
+    const long nl = *n_long;
+    long long v_ok = 0, v_empty = 0;
+    for (long r0 = (long)blockIdx.y * R; r0 < g.nrec; r0 += (long)gridDim.y * R)
+    for (long i = blockIdx.x; i < nl; i += gridDim.x) {
+        const int nr = g.nrec - r0 < R ? (int)(g.nrec - r0) : R;
+        const T* fr = f + r0 * g.ncell;
+        const long k = longs[i];
+        const int s = seg[k], n = seg[k + 1] - s;
+        double W[R], S[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) W[q] = 0.0, S[q] = 0.0;
+        for (int base = 0; base < n; base += 64) {
+            double a = 0.0, p[R];
+            unsigned ok = 0;
+#pragma unroll
+            for (int q = 0; q < R; ++q) p[q] = 0.0;
+            if (base + lane < n) {
+                const long c = pc[s + base + lane];
+                a = pa[s + base + lane];
+#pragma unroll
+                for (int q = 0; q < R; ++q) {
+                    if (q < nr) {
+                        const T v = fr[q * g.ncell + c];
+                        if (!missing(v, f0, f1, g.n_fill)) ok |= 1u << q;
+                        p[q] = a * (double)v;
+                    }
+                }
+            }
+            const int cnt = n - base < 64 ? n - base : 64;
+            for (int t = 0; t < cnt; ++t) {
+                const double at = __shfl(a, t, 64);
+                const unsigned ot = __shfl(ok, t, 64);
+#pragma unroll
+                for (int q = 0; q < R; ++q) {
+                    const double pt = __shfl(p[q], t, 64);
+                    if ((ot >> q) & 1u) {
+                        W[q] += at;
+                        S[q] += pt;
+                    }
+                }
+            }
+        }
+        if (lane == 0) {
+            const double A = a_atm[k];
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                if (q >= nr) break;
+                const long o = (r0 + q) * g.nk + k;
+                double val;
+                if (g.cell_norm) val = W[q] > 0.0 ? S[q] / A : 0.0;
+                else val = W[q] > 0.0 ? S[q] / W[q] : OGG_REMAP_FILL;
+                out[o] = val;
+                if (cover) cover[o] = W[q] / A;
+                if (W[q] > 0.0) ++v_ok;
+                else ++v_empty;
+            }
+        }
+    }
+    if (lane == 0) {
+        if (v_ok) atomicAdd(ull(&counts->valid), (unsigned long long)v_ok);
+        if (v_empty) atomicAdd(ull(&counts->empty), (unsigned long long)v_empty);
+    }
+}
+
+// one lane per target cell: n_entries, the counts, the long cells into the list, W0 and ocean_frac of the others
+__global__ __launch_bounds__(NT) void static_kernel(long nk, int long_n, const int* __restrict__ seg, const double* __restrict__ pa,
+                                                    const double* __restrict__ a_atm, double* __restrict__ frac, int* __restrict__ nent,
+                                                    int* __restrict__ longs, long long* __restrict__ n_long, ogg_regrid_counts* counts) {
+    const long k = (long)blockIdx.x * NT + threadIdx.x;
+    long long n = 0;
+    if (k < nk) {
+        const int s = seg[k], e = seg[k + 1];
+        n = e - s;
+        if (n > long_n) {
+            longs[atomicAdd(ull(n_long), 1ull)] = (int)k;
+        } else if (frac) {
+            double w = 0.0;
+            for (int t = s; t < e; ++t) w += pa[t];
+            frac[k] = w / a_atm[k];
+        }
+        if (nent) nent[k] = (int)n;
+    }
+    long long mx = n;
+    for (int off = 32; off > 0; off >>= 1) {
+        const long long t = __shfl_xor(mx, off, 64);
+        mx = t > mx ? t : mx;
+    }
+    if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(ull(&counts->max_entries), (unsigned long long)mx);
+    long long v[1] = {n > 0 ? 1 : 0};
+    long long* const dst[1] = {&counts->cells};
+    block_add<1>(v, dst);
+}
+
+// W0 and ocean_frac of the long cells: one wavefront per cell, 64 areas at a time added in list order through shuffles
+__global__ __launch_bounds__(64) void static_long_kernel(const int* __restrict__ seg, const double* __restrict__ pa,
+                                                         const double* __restrict__ a_atm, const int* __restrict__ longs,
+                                                         const long long* __restrict__ n_long, double* __restrict__ frac) {
+    const int lane = threadIdx.x;
+    const long nl = *n_long;
+    for (long i = blockIdx.x; i < nl; i += gridDim.x) {
+        const long k = longs[i];
+        const int s = seg[k], n = seg[k + 1] - s;
+        double w = 0.0;
+        for (int base = 0; base < n; base += 64) {
+            const double a = base + lane < n ? pa[s + base + lane] : 0.0;
+            const int cnt = n - base < 64 ? n - base : 64;
+            for (int t = 0; t < cnt; ++t) w += __shfl(a, t, 64);
+        }
+        if (lane == 0) frac[k] = w / a_atm[k];
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+long round256(long v) { return (v + 255) / 256 * 256; }
+
+int check_params(const ogg_regrid_params* p) {
+    OGG_REQUIRE(p, OGG_EARG, "regrid: null parameters");
+    OGG_REQUIRE(p->ny >= 1 && p->nx >= 1 && p->ny <= (long)INT_MAX && p->nx <= (long)INT_MAX && p->ny * p->nx < (1L << 31), OGG_EARG,
+                "regrid: %ld x %ld model cells: ny, nx >= 1 and ny * nx < 2^31", p->ny, p->nx);
+    OGG_REQUIRE(p->NA >= 1 && p->NB >= 1 && p->NA <= (long)INT_MAX && p->NB <= (long)INT_MAX && p->NA * p->NB < (1L << 31), OGG_EARG,
+                "regrid: %ld x %ld target cells: NA, NB >= 1 and NA * NB < 2^31", p->NA, p->NB);
+    OGG_REQUIRE(p->nrec >= 1 && p->nrec <= (long)INT_MAX && p->nrec * p->NA * p->NB < (1L << 32), OGG_EARG,
+                "regrid: %ld records of %ld x %ld target cells: nrec >= 1 and nrec * NB * NA < 2^32", p->nrec, p->NB, p->NA);
+    OGG_REQUIRE(p->dtype == OGG_REMAP_FLOAT32 || p->dtype == OGG_REMAP_FLOAT64, OGG_EARG, "regrid: field dtype %d (0: float32, 1: float64)",
+                p->dtype);
+    OGG_REQUIRE(p->n_fill >= 0 && p->n_fill <= OGG_REMAP_MAX_FILLS, OGG_EARG, "regrid: %d fill values (at most %d)", p->n_fill,
+                OGG_REMAP_MAX_FILLS);
+    OGG_REQUIRE(p->normalize == OGG_REGRID_AREA || p->normalize == OGG_REGRID_CELL, OGG_EARG, "regrid: normalize %d (0: area, 1: cell)",
+                p->normalize);
+    return OGG_OK;
+}
+
+// workspace: head | counts (nk ints) | segments (nk + 1 ints) | scan block sums | long cells (nk ints) | keys (two buffers of n) |
+// cells (n ints) | areas (n doubles)
+struct Layout {
+    long cur, seg, bsum, longs, key0, key1, pc, pa, total;
+};
+
+Layout layout(const ogg_regrid_params& p, long n) {
+    Layout l;
+    const long nk = p.NA * p.NB;
+    l.cur = HEAD;
+    l.seg = l.cur + round256(nk * 4);
+    l.bsum = l.seg + round256((nk + 1) * 4);
+    l.longs = l.bsum + round256(((nk + 1) / CH + 2) * 8);
+    l.key0 = l.longs + round256(nk * 4);
+    l.key1 = l.key0 + round256(n * 8);
+    l.pc = l.key1 + round256(n * 8);
+    l.pa = l.pc + round256(n * 4);
+    l.total = l.pa + round256(n * 8);
+    return l;
+}
+
+template <typename P>
+P* at(void* ws, long off) { return reinterpret_cast<P*>(static_cast<char*>(ws) + off); }
+template <typename P>
+const P* at(const void* ws, long off) { return reinterpret_cast<const P*>(static_cast<const char*>(ws) + off); }
+
+int knob(const char* name, int def, int lo, int hi, int* out) {
+    *out = def;
+    if (const char* e = getenv(name)) {
+        const long v = atol(e);
+        OGG_REQUIRE(v >= lo && v <= hi, OGG_EARG, "%s=%s: %d .. %d", name, e, lo, hi);
+        *out = (int)v;
+    }
+    return OGG_OK;
+}
+
+unsigned grid_for(long n, long cap) { return (unsigned)std::min<long>(std::max<long>((n + NT - 1) / NT, 1), cap); }
+
+struct Bufs {
+    const int *seg, *pc, *longs;
+    const double *pa, *a_atm;
+    const long long* n_long;
+    double *out, *cover;
+    ogg_regrid_counts* counts;
+};
+
+template <typename T, int R>
+void launch_regrid(hipStream_t st, const Geo& g, const void* f, const Bufs& b) {
+    const T* ft = static_cast<const T*>(f);
+    regrid_kernel<T, R><<<(unsigned)((g.nk + NT - 1) / NT), NT, 0, st>>>(g, ft, b.seg, b.pc, b.pa, b.a_atm, b.out, b.cover, b.counts);
+    const dim3 grid((unsigned)std::min<long>(g.nk, LONG_WAVES), (unsigned)std::min<long>((g.nrec + R - 1) / R, 65535));
+    regrid_long_kernel<T, R><<<grid, 64, 0, st>>>(g, ft, b.seg, b.pc, b.pa, b.a_atm, b.longs, b.n_long, b.out, b.cover, b.counts);
+}
+
+template <typename T>
+int launch_regrid_r(int rec, hipStream_t st, const Geo& g, const void* f, const Bufs& b) {
+    switch (rec) {
+        case 1: launch_regrid<T, 1>(st, g, f, b); break;
+        case 2: launch_regrid<T, 2>(st, g, f, b); break;
+        case 4: launch_regrid<T, 4>(st, g, f, b); break;
+        case 8: launch_regrid<T, 8>(st, g, f, b); break;
+        default: return ogg::set_error(OGG_EARG, "OGG_REGRID_RECORDS=%d: 1, 2, 4 or 8", rec);
+    }
+    return OGG_OK;
+}
+
+}  // namespace
+
+extern "C" long ogg_regrid_struct_bytes(int which) {
+    return which == OGG_REGRID_PARAMS ? (long)sizeof(ogg_regrid_params) : (which == OGG_REGRID_COUNTS ? (long)sizeof(ogg_regrid_counts) : -1L);
+}
+
+extern "C" long ogg_regrid_workspace_bytes(const ogg_regrid_params* p, long n_entries) {
+    if (!p || check_params(p) != OGG_OK || n_entries < 0 || n_entries >= (long)INT_MAX) return -1;
+    return layout(*p, n_entries).total;
+}
+
+extern "C" int ogg_regrid_check(const ogg_regrid_params* p) { return check_params(p); }
+
+extern "C" int ogg_regrid_transpose_dev(const ogg_regrid_params* p, const int* atm_ij, const int* ocn_ij, const double* area, long n_entries,
+                                        void* workspace, long workspace_bytes, ogg_regrid_counts* counts, void* stream) {
+    if (int e = check_params(p)) return e;
+    OGG_REQUIRE(n_entries >= 0 && n_entries < (long)INT_MAX, OGG_EARG, "ogg_regrid_transpose: %ld entries (< 2^31)", n_entries);
+    OGG_REQUIRE((atm_ij && ocn_ij && area) || n_entries == 0, OGG_EARG, "ogg_regrid_transpose: null atm_ij / ocn_ij / area");
+    OGG_REQUIRE(counts, OGG_EARG, "ogg_regrid_transpose: null counts");
+    const Layout l = layout(*p, n_entries);
+    OGG_REQUIRE(workspace && workspace_bytes >= l.total, OGG_EARG, "ogg_regrid_transpose: workspace of %ld bytes, %ld needed",
+                workspace_bytes, l.total);
+    hipStream_t st = ogg::as_stream(stream);
+    const long nk = p->NA * p->NB;
+    OGG_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(ogg_regrid_counts), st));
+    int* cur = at<int>(workspace, l.cur);
+    int* seg = at<int>(workspace, l.seg);
+    long long* bsum = at<long long>(workspace, l.bsum);
+    OGG_HIP_CHECK(hipMemsetAsync(cur, 0, (size_t)nk * 4, st));
+    const List li{n_entries, p->ny, p->nx, p->NA, p->NB};
+    if (n_entries > 0) {
+        count_kernel<<<grid_for(n_entries, 8192), NT, 0, st>>>(li, atm_ij, ocn_ij, cur, counts);
+        OGG_LAUNCH_CHECK();
+    }
+    const long nb = (nk + 1 + CH - 1) / CH;
+    scan_count_kernel<<<(unsigned)nb, NT, 0, st>>>(cur, nk, bsum);
+    OGG_LAUNCH_CHECK();
+    scan_blocks_kernel<<<1, NT, 0, st>>>(bsum, nb);
+    OGG_LAUNCH_CHECK();
+    scan_write_kernel<<<(unsigned)nb, NT, 0, st>>>(cur, nk, bsum, seg);
+    OGG_LAUNCH_CHECK();
+    if (n_entries == 0) return OGG_OK;
+    unsigned long long* key[2] = {at<unsigned long long>(workspace, l.key0), at<unsigned long long>(workspace, l.key1)};
+    key_block_kernel<<<(unsigned)((n_entries + KEYSORT_NT - 1) / KEYSORT_NT), KEYSORT_NT, 0, st>>>(li, nk, atm_ij, ocn_ij, key[0]);
+    OGG_LAUNCH_CHECK();
+    int k = 0;
+    for (long w = KEYSORT_NT; w < n_entries; w *= 2, ++k) {
+        keysort_merge_kernel<<<grid_for(n_entries, 1L << 20), KEYSORT_NT, 0, st>>>(key[k & 1], n_entries, w, key[(k + 1) & 1]);
+        OGG_LAUNCH_CHECK();
+    }
+    pairs_kernel<<<grid_for(n_entries, 8192), NT, 0, st>>>(n_entries, nk, p->nx, key[keysort_passes(n_entries) & 1], ocn_ij, area,
+                                                           at<int>(workspace, l.pc), at<double>(workspace, l.pa));
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+extern "C" int ogg_regrid_dev(const ogg_regrid_params* p, const void* f, const double* a_atm, long n_list, void* workspace,
+                              long workspace_bytes, double* values, double* cover, double* frac, int* n_entries, ogg_regrid_counts* counts,
+                              void* stream) {
+    if (int e = check_params(p)) return e;
+    OGG_REQUIRE(a_atm && counts, OGG_EARG, "ogg_regrid: null a_atm / counts");
+    OGG_REQUIRE((f == nullptr) == (values == nullptr), OGG_EARG, "ogg_regrid: f and values are given together or not at all");
+    OGG_REQUIRE(values || !cover, OGG_EARG, "ogg_regrid: cover needs values");
+    OGG_REQUIRE(n_list >= 0 && n_list < (long)INT_MAX, OGG_EARG, "ogg_regrid: %ld entries (< 2^31)", n_list);
+    const Layout l = layout(*p, n_list);
+    OGG_REQUIRE(workspace && workspace_bytes >= l.total, OGG_EARG, "ogg_regrid: workspace of %ld bytes, %ld needed", workspace_bytes, l.total);
+    // OGG_REGRID_RECORDS: records a lane sums at once.  Their gathers are independent loads, so more records keep more of them in
+    // flight per lane.  Measured at 1/8 degree (profiles/r12_regrid_time.json, ms for 1, 2, 4, 8): 57 levels onto 1 degree 21.3, 14.4,
+    // 11.8, 10.5; onto 0.25 degree 18.0, 11.0, 8.5, 7.0; 12 records onto 1 degree 5.2, 3.5, 3.2, 4.2.
+    int rec = 0, long_n = 0;
+    if (int e = knob("OGG_REGRID_RECORDS", RECORDS_DEFAULT, 1, 8, &rec)) return e;
+    // OGG_REGRID_LONG: cells of more entries are walked by whole wavefronts (a lane's walk costs its entry count, a wavefront's about
+    // as much in shuffles but with the gathers 64 at a time and no other lane waiting).  Measured as above (ms for 128, 512, 4096): 57
+    // levels onto 1 degree 8.9, 11.8, 30.7; onto 0.25 degree 5.5, 8.4, 15.6; 12 records onto 1 degree 2.9, 3.2, 6.8.
+    if (int e = knob("OGG_REGRID_LONG", LONG_DEFAULT, 0, INT_MAX, &long_n)) return e;
+    hipStream_t st = ogg::as_stream(stream);
+    const long nk = p->NA * p->NB;
+    const int* seg = at<int>(workspace, l.seg);
+    const int* pc = at<int>(workspace, l.pc);
+    const double* pa = at<double>(workspace, l.pa);
+    int* longs = at<int>(workspace, l.longs);
+    long long* n_long = at<long long>(workspace, 0);
+    // this step's counts start from zero on every call (entries and bad_entries are the transpose step's)
+    OGG_HIP_CHECK(hipMemsetAsync(&counts->cells, 0, sizeof(ogg_regrid_counts) - offsetof(ogg_regrid_counts, cells), st));
+    OGG_HIP_CHECK(hipMemsetAsync(n_long, 0, sizeof(long long), st));
+    const unsigned blocks = (unsigned)((nk + NT - 1) / NT);
+    static_kernel<<<blocks, NT, 0, st>>>(nk, long_n, seg, pa, a_atm, frac, n_entries, longs, n_long, counts);
+    OGG_LAUNCH_CHECK();
+    if (frac) {
+        static_long_kernel<<<(unsigned)std::min<long>(nk, LONG_WAVES), 64, 0, st>>>(seg, pa, a_atm, longs, n_long, frac);
+        OGG_LAUNCH_CHECK();
+    }
+    if (!values) return OGG_OK;
+    const Geo g{nk, p->ny * p->nx, p->nrec, p->n_fill, p->normalize == OGG_REGRID_CELL ? 1 : 0, long_n, p->fill[0], p->fill[1]};
+    const Bufs b{seg, pc, longs, pa, a_atm, n_long, values, cover, counts};
+    int e = p->dtype == OGG_REMAP_FLOAT32 ? launch_regrid_r<float>(rec, st, g, f, b) : launch_regrid_r<double>(rec, st, g, f, b);
+    if (e) return e;
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+// the host-pointer form: field, list and areas copied to device memory, both steps, the results copied back (synchronous)
+extern "C" int ogg_regrid(const ogg_regrid_params* p, const void* f, const int* atm_ij, const int* ocn_ij, const double* area, long n_entries,
+                          const double* a_atm, double* values, double* cover, double* frac, int* n_out, ogg_regrid_counts* counts) {
+    if (int e = check_params(p)) return e;
+    OGG_REQUIRE(n_entries >= 0 && n_entries < (long)INT_MAX, OGG_EARG, "ogg_regrid: %ld entries (< 2^31)", n_entries);
+    OGG_REQUIRE(a_atm && counts && ((atm_ij && ocn_ij && area) || n_entries == 0), OGG_EARG,
+                "ogg_regrid: null a_atm / atm_ij / ocn_ij / area / counts");
+    OGG_REQUIRE((f == nullptr) == (values == nullptr), OGG_EARG, "ogg_regrid: f and values are given together or not at all");
+    OGG_REQUIRE(values || !cover, OGG_EARG, "ogg_regrid: cover needs values");
+    struct Buffers {   // freed on every exit path
+        std::vector<void*> p;
+        ~Buffers() {
+            for (void* q : p) (void)hipFree(q);
+        }
+        int alloc(void** out, size_t bytes) {
+            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
+            if (e != hipSuccess)
+                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
+                                      hipGetErrorString(e));
+            p.push_back(*out);
+            return OGG_OK;
+        }
+    } bufs;
+    const size_t nk = (size_t)p->NA * p->NB, nout = (size_t)p->nrec * nk;
+    const size_t fbytes = (size_t)p->nrec * p->ny * p->nx * (p->dtype == OGG_REMAP_FLOAT32 ? 4 : 8);
+    const long wsb = layout(*p, n_entries).total;
+    void *df = nullptr, *da = nullptr, *dox = nullptr, *dar = nullptr, *daa = nullptr, *ws = nullptr, *dv = nullptr, *dc = nullptr,
+         *dfr = nullptr, *dn = nullptr, *ct = nullptr;
+    if (int e = bufs.alloc(&da, (size_t)n_entries * 8)) return e;
+    if (int e = bufs.alloc(&dox, (size_t)n_entries * 8)) return e;
+    if (int e = bufs.alloc(&dar, (size_t)n_entries * 8)) return e;
+    if (int e = bufs.alloc(&daa, nk * 8)) return e;
+    if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
+    if (int e = bufs.alloc(&ct, sizeof(ogg_regrid_counts))) return e;
+    if (values) {
+        if (int e = bufs.alloc(&df, fbytes)) return e;
+        if (int e = bufs.alloc(&dv, nout * 8)) return e;
+        OGG_HIP_CHECK(hipMemcpy(df, f, fbytes, hipMemcpyHostToDevice));
+    }
+    if (cover)
+        if (int e = bufs.alloc(&dc, nout * 8)) return e;
+    if (frac)
+        if (int e = bufs.alloc(&dfr, nk * 8)) return e;
+    if (n_out)
+        if (int e = bufs.alloc(&dn, nk * 4)) return e;
+    if (n_entries > 0) {
+        OGG_HIP_CHECK(hipMemcpy(da, atm_ij, (size_t)n_entries * 8, hipMemcpyHostToDevice));
+        OGG_HIP_CHECK(hipMemcpy(dox, ocn_ij, (size_t)n_entries * 8, hipMemcpyHostToDevice));
+        OGG_HIP_CHECK(hipMemcpy(dar, area, (size_t)n_entries * 8, hipMemcpyHostToDevice));
+    }
+    OGG_HIP_CHECK(hipMemcpy(daa, a_atm, nk * 8, hipMemcpyHostToDevice));
+    ogg_regrid_counts* dct = static_cast<ogg_regrid_counts*>(ct);
+    if (int e = ogg_regrid_transpose_dev(p, static_cast<const int*>(da), static_cast<const int*>(dox), static_cast<const double*>(dar),
+                                         n_entries, ws, wsb, dct, nullptr))
+        return e;
+    if (int e = ogg_regrid_dev(p, df, static_cast<const double*>(daa), n_entries, ws, wsb, static_cast<double*>(dv), static_cast<double*>(dc),
+                               static_cast<double*>(dfr), static_cast<int*>(dn), dct, nullptr))
+        return e;
+    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_regrid_counts), hipMemcpyDeviceToHost));
+    if (values) OGG_HIP_CHECK(hipMemcpy(values, dv, nout * 8, hipMemcpyDeviceToHost));
+    if (cover) OGG_HIP_CHECK(hipMemcpy(cover, dc, nout * 8, hipMemcpyDeviceToHost));
+    if (frac) OGG_HIP_CHECK(hipMemcpy(frac, dfr, nk * 8, hipMemcpyDeviceToHost));
+    if (n_out) OGG_HIP_CHECK(hipMemcpy(n_out, dn, nk * 4, hipMemcpyDeviceToHost));
+    return OGG_OK;
+}

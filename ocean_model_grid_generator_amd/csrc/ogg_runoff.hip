@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "ogg_common.h"
+#include "ogg_keysort.h"
 
 #pragma clang fp contract(off)
 
@@ -45,6 +46,7 @@ constexpr double MARGIN = 1.0 + 1e-12;  // covers the rounding of a computed d2
 
 static_assert(sizeof(ogg_runoff_params) == 80, "ogg_runoff_params layout");
 static_assert(sizeof(ogg_runoff_counts) == 64, "ogg_runoff_counts layout");
+static_assert(NT == KEYSORT_NT, "the block sort makes the runs the merge passes take");
 
 struct Head {
     long long total;                    // the last scan's total
@@ -414,24 +416,6 @@ __global__ __launch_bounds__(NT) void sort_block_kernel(const int* __restrict__ 
     if (i < n) out[(long)blockIdx.x * NT + rank] = key;
 }
 
-// runs of w sorted keys merged in pairs: a key's slot is its place in its run plus the keys of the partner run below it
-__global__ __launch_bounds__(NT) void merge_kernel(const unsigned long long* __restrict__ in, long n, long w, unsigned long long* __restrict__ out) {
-    for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
-        const unsigned long long key = in[i];
-        const long r = i / w, rs = r * w;
-        long lo = (r & 1) ? rs - w : rs + w;
-        long hi = (r & 1) ? rs : (rs + 2 * w < n ? rs + 2 * w : n);
-        const long p0 = lo;
-        if (lo > n) lo = hi = n;
-        while (lo < hi) {
-            const long m = lo + (hi - lo) / 2;
-            if (in[m] < key) lo = m + 1;
-            else hi = m;
-        }
-        out[(r & ~1L) * w + (i - rs) + (lo - (p0 > n ? n : p0))] = key;
-    }
-}
-
 __global__ __launch_bounds__(NT) void seg_kernel(const unsigned long long* __restrict__ key, long n, long ncell, int2* __restrict__ seg) {
     for (long k = (long)blockIdx.x * NT + threadIdx.x; k < n; k += (long)gridDim.x * NT) {
         const unsigned c = (unsigned)(key[k] >> 32);
@@ -636,13 +620,6 @@ int scan_write(const T* in, long n, int* out, void* ws, const Layout& l, hipStre
     return OGG_OK;
 }
 
-// the number of merge passes after the block sort, so which key buffer holds the sorted keys
-int merge_passes(long n) {
-    int k = 0;
-    for (long w = NT; w < n; w *= 2) ++k;
-    return k;
-}
-
 }  // namespace
 
 extern "C" long ogg_runoff_struct_bytes(int which) {
@@ -781,7 +758,7 @@ extern "C" int ogg_runoff_segments_dev(const ogg_runoff_params* p, const int* sr
     OGG_LAUNCH_CHECK();
     int k = 0;
     for (long w = NT; w < n_mapped; w *= 2, ++k) {
-        merge_kernel<<<grid_for(n_mapped, 1L << 20), NT, 0, st>>>(buf[k & 1], n_mapped, w, buf[(k + 1) & 1]);
+        keysort_merge_kernel<<<grid_for(n_mapped, 1L << 20), NT, 0, st>>>(buf[k & 1], n_mapped, w, buf[(k + 1) & 1]);
         OGG_LAUNCH_CHECK();
     }
     seg_kernel<<<grid_for(n_mapped, 1L << 20), NT, 0, st>>>(buf[k & 1], n_mapped, ncell_of(*p), seg);
@@ -801,7 +778,7 @@ extern "C" int ogg_runoff_accumulate_dev(const ogg_runoff_params* p, const void*
     OGG_REQUIRE(lda >= 2 * p->nx, OGG_EARG, "ogg_runoff_accumulate: area row stride %ld < 2 nx", lda);
     hipStream_t st = ogg::as_stream(stream);
     const Layout l = layout(*p);
-    const unsigned long long* key = at<unsigned long long>(workspace, (merge_passes(n_mapped) & 1) ? l.key1 : l.key0);
+    const unsigned long long* key = at<unsigned long long>(workspace, (keysort_passes(n_mapped) & 1) ? l.key1 : l.key0);
     const Geo g{p->ny, p->nx, nsrc_of(*p), p->nrec, lda, p->n_fill, p->fill[0], p->fill[1]};
     const long waves = p->ny * ((p->nx + 63) / 64);
     const unsigned grid = (unsigned)((waves + NT / 64 - 1) / (NT / 64));

@@ -63,13 +63,19 @@ def counts_dict(c):
 
 
 # ---- results ---------------------------------------------------------------------------------------------------
+def atm_area(lon, lat, Re):
+    """A_atm of every atmosphere cell (NB x NA): Re^2 dlam (sin b_J+1 - sin b_J), formed as the definition's keep step has it.  The
+    lat-lon regrid takes these bits as its cell areas, so its fractions and ocean_frac's are one number."""
+    D = np.pi / 180.0
+    b1, b2 = lat[:-1] * D, lat[1:] * D
+    return (Re * Re) * (lon[1:] * D - lon[:-1] * D)[None, :] * (2.0 * np.cos((b1 + b2) / 2.0) * np.sin((b2 - b1) / 2.0))[:, None]
+
+
 def ocean_frac(atm, area, lon, lat, Re):
     """The fraction of every atmosphere cell (NB x NA) covered by the list's exchange cells: their areas summed per atmosphere cell
     with np.bincount in list order, over the cell's area (Re^2 dlam (sin b_J+1 - sin b_J), formed as the definition has it)."""
     NA, NB = lon.size - 1, lat.size - 1
-    D = np.pi / 180.0
-    b1, b2 = lat[:-1] * D, lat[1:] * D
-    a_atm = (Re * Re) * (lon[1:] * D - lon[:-1] * D)[None, :] * (2.0 * np.cos((b1 + b2) / 2.0) * np.sin((b2 - b1) / 2.0))[:, None]
+    a_atm = atm_area(lon, lat, Re)
     s = np.bincount(atm[:, 1].astype(np.int64) * NA + atm[:, 0], weights=area, minlength=NA * NB).reshape(NB, NA)
     return s / a_atm, a_atm
 

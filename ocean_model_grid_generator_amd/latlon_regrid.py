@@ -1,0 +1,421 @@
+"""Conservative regrid to a lat-lon grid: fields on the model cells of a supergrid (model output, a mask, the ocean fraction itself)
+aggregated first-order conservatively onto the cells of a global rectilinear grid, the direction opposite to remap.py.
+include/ogg_hip.h, "Conservative regrid to a lat-lon grid", gives the definition; the reference has no such step.
+
+The weights are the exchange list of exchange_grid.py between the target's cell edges and the model cells.  The list is transposed
+to target-cell order and summed per target cell on the device (ogg_regrid_transpose_dev / ogg_regrid_dev, or the host-pointer
+ogg_regrid); every value is a fixed function of the list, the field and the target's cell areas, so the result is bit-identical for
+any launch geometry and any number of ranks.  The same steps without a field give every target cell's ocean fraction (main()'s
+--xgrid_frac_file).
+
+    python -m ocean_model_grid_generator_amd.latlon_regrid ocean_hgrid.nc FIELDS.nc --var V [--var V2 ...] --atm NLON NLAT
+        [--topog topog.nc | --mask ocean_mask.nc] [--normalize area|cell] [--cover] -o out.nc [--json summary.json]
+
+FIELDS.nc is a NetCDF classic / 64-bit-offset file; a variable qualifies when its last two dimensions have the lengths of the grid's
+model cells (ny, nx); every dimension ahead of them is a record dimension.
+"""
+import argparse
+import ctypes
+import json
+import sys
+
+import numpy as np
+
+from . import _lib as L
+from . import exchange_grid as X
+from . import netcdf3
+
+FILL = L.REMAP_FILL
+NORMALIZE = {"area": L.REGRID_AREA, "cell": L.REGRID_CELL}
+_DTYPES = {np.dtype(np.float32): L.REMAP_FLOAT32, np.dtype(np.float64): L.REMAP_FLOAT64}
+
+
+# ---- fields --------------------------------------------------------------------------------------------------
+class Field(object):
+    """A field on the model cells: data (..., ny, nx), float32 or float64; the values that mark missing (``fill``, at most two, in the
+    data's type; NaN is always missing); the leading dimensions [(name, length)] and their coordinate variables [(name, nc type,
+    attributes, values)] for the writer; ``record_dim`` the unlimited dimension of the file it came from (None: none)."""
+
+    def __init__(self, data, fill=(), name="field", lead_dims=None, coords=(), atts=(), note="", record_dim=None):
+        data = np.asarray(data)
+        if data.ndim < 2 or data.dtype.newbyteorder("=") not in _DTYPES:
+            raise ValueError("regrid field: a float32 or float64 array of two or more dimensions is needed, not %s %s" % (data.dtype, data.shape))
+        self.data = np.ascontiguousarray(data, dtype=data.dtype.newbyteorder("="))
+        self.fill = tuple(self.data.dtype.type(f) for f in fill)
+        if len(self.fill) > L.REMAP_MAX_FILLS:
+            raise ValueError("regrid field: at most %d fill values" % L.REMAP_MAX_FILLS)
+        self.name = name
+        lead = self.data.shape[:-2]
+        self.lead_dims = list(lead_dims) if lead_dims is not None else [("record%d" % k, n) for k, n in enumerate(lead)]
+        self.coords, self.atts, self.note, self.record_dim = list(coords), list(atts), note, record_dim
+
+    @property
+    def nrec(self):
+        return int(np.prod(self.data.shape[:-2], dtype=np.int64))
+
+    @property
+    def records(self):
+        """the data as (nrec, ny, nx)"""
+        return self.data.reshape((self.nrec,) + self.data.shape[-2:])
+
+
+def _num(atts, key):
+    v = atts.get(key)
+    return None if v is None or isinstance(v, str) else float(np.asarray(v).reshape(-1)[0])
+
+
+def read_field(path, var, shape):
+    """A Field from a NetCDF classic (CDF-1) or 64-bit-offset (CDF-2) file: the byte / short / float / double variable ``var`` whose
+    last two dimensions have the lengths ``shape`` = (ny, nx) of the model cells (their names do not matter); every dimension ahead of
+    them is a record dimension, the unlimited one included.  A byte or short variable is unpacked to float64 as raw * scale_factor +
+    add_offset, with missing values (_FillValue, missing_value, tested on the raw values) as NaN; float and double keep their type and
+    their fill values.  CDF-5 and NetCDF-4 / HDF5 files are refused."""
+    from . import topography as T
+    try:
+        h = netcdf3.read_header(path)
+    except ValueError as e:
+        if "CDF-5" in str(e) or "HDF5" in str(e):
+            raise ValueError("%s: only NetCDF classic / 64-bit-offset fields are read; %s" % (str(e).split(";")[0], T._NCCOPY))
+        raise
+    if var not in h.vars:
+        raise KeyError("%s: no variable %r (variables: %s); choose one with --var" % (path, var, ", ".join(sorted(h.vars))))
+    v = h.vars[var]
+    if v.nc_type not in (netcdf3.NC_BYTE, netcdf3.NC_SHORT, netcdf3.NC_FLOAT, netcdf3.NC_DOUBLE) or len(v.shape) < 2:
+        raise ValueError("%s: %s must be a byte, short, float or double variable of two or more dimensions (type %d, shape %s)"
+                         % (path, var, v.nc_type, v.shape))
+    if tuple(v.shape[-2:]) != tuple(shape):
+        raise ValueError("%s: %s ends in %s, the grid has %d x %d model cells (ny, nx)" % (path, var, tuple(v.shape[-2:]), shape[0], shape[1]))
+
+    def raw_bytes(name, u):
+        return (netcdf3.read_record_var_bytes if u.is_record else netcdf3.read_var_bytes)(path, h, name, dtype=u.nc_type)
+    data = np.frombuffer(raw_bytes(var, v), dtype=netcdf3.NUMPY_DTYPE[v.nc_type]).reshape(v.shape)
+    data = data.astype(data.dtype.newbyteorder("="))
+    fills = []
+    for k in ("_FillValue", "missing_value"):
+        fv = _num(v.atts, k)
+        if fv is not None and fv not in fills:
+            fills.append(fv)
+    if v.nc_type in (netcdf3.NC_BYTE, netcdf3.NC_SHORT):
+        scale, offset = _num(v.atts, "scale_factor"), _num(v.atts, "add_offset")
+        miss = np.zeros(data.shape, dtype=bool)
+        for fv in fills:
+            miss |= data == data.dtype.type(fv)
+        out = data.astype(np.float64) * (1.0 if scale is None else scale) + (0.0 if offset is None else offset)
+        out[miss] = np.nan
+        data, fills = out, []
+    lead = [(d, n) for d, n in zip(v.dims[:-2], v.shape[:-2])]
+    coords = []
+    for d, _ in lead:
+        cv = h.vars.get(d)
+        if cv is not None and len(cv.shape) == 1 and cv.nc_type != netcdf3.NC_CHAR:
+            vals = np.frombuffer(raw_bytes(d, cv), dtype=netcdf3.NUMPY_DTYPE[cv.nc_type])
+            atts = [(k, a if isinstance(a, str) else np.asarray(a).reshape(-1)[0].item()) for k, a in cv.atts.items()
+                    if isinstance(a, str) or np.asarray(a).size == 1]
+            coords.append((d, cv.nc_type, atts, vals))
+    keep = [(k, a) for k, a in v.atts.items() if k in ("units", "long_name") and isinstance(a, str)]
+    note = "%s: %s %s, %d records of %d x %d model cells" % (path, var, tuple(v.dims), int(np.prod(v.shape[:-2], dtype=np.int64)),
+                                                            shape[0], shape[1])
+    return Field(data, fill=fills, name=var, lead_dims=lead, coords=coords, atts=keep, note=note,
+                 record_dim=v.dims[0] if v.is_record else None)
+
+
+# ---- arguments -----------------------------------------------------------------------------------------------
+def params(shape, lon, lat, field=None, normalize="area"):
+    """an ogg_regrid_params, checked by the library (OGG_EARG -> ValueError); without a field, one float64 record (the static sums)"""
+    if normalize not in NORMALIZE:
+        raise ValueError("regrid: normalize must be area or cell, not %r" % (normalize,))
+    p = L.RegridParams(ny=int(shape[0]), nx=int(shape[1]), NA=lon.size - 1, NB=lat.size - 1, nrec=1 if field is None else field.nrec,
+                       dtype=L.REMAP_FLOAT64 if field is None else _DTYPES[field.data.dtype],
+                       n_fill=0 if field is None else len(field.fill), normalize=NORMALIZE[normalize])
+    for k, f in enumerate(() if field is None else field.fill):
+        p.fill[k] = float(f)
+    if field is not None and tuple(field.data.shape[-2:]) != tuple(shape):
+        raise ValueError("regrid: the field is %s, the model cells %s" % (field.data.shape[-2:], tuple(shape)))
+    if L.load().ogg_regrid_check(ctypes.byref(p)) != L.OGG_OK:
+        raise ValueError(L.load().ogg_last_error().decode())
+    return p
+
+
+def _mask(mask, shape):
+    if mask is None:
+        return None
+    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    if m.shape != shape:
+        raise ValueError("regrid: the mask is %s, the model cells %s" % (m.shape, shape))
+    return m
+
+
+def counts_dict(c):
+    return {f: int(c[k]) for k, f in enumerate(L.REGRID_COUNT_FIELDS)}
+
+
+def result(values, cover, frac, n_entries, counts, field, lon, lat, a_atm, normalize, masked, cell_weight=None):
+    """What regrid_to_latlon() returns: values and cover (the field's leading dimensions, NB, NA; None without a field), ocean_frac,
+    n_entries and cell_area (NB, NA), the edges, the counts and a summary.  ``cell_weight``: sum_{e in c} A_e per model cell (ny, nx),
+    for the conservation lines of the summary."""
+    if counts["bad_entries"]:
+        raise ValueError("regrid: %d list entries lie outside the cells or the target: the list belongs to other edges or rows"
+                         % counts["bad_entries"])
+    NB, NA = a_atm.shape
+    frac = frac.reshape(NB, NA)
+    summary = dict(counts, n_lon=int(NA), n_lat=int(NB), normalize=normalize, masked=bool(masked),
+                   frac_excess=float(np.max(frac - 1.0)) if frac.size else 0.0)
+    del summary["bad_entries"]
+    out = {"ocean_frac": frac, "n_entries": n_entries.reshape(NB, NA), "cell_area": a_atm, "lon_edges": lon, "lat_edges": lat,
+           "counts": counts, "summary": summary, "values": None, "cover": None}
+    if field is not None:
+        shape = tuple(field.data.shape[:-2]) + (NB, NA)
+        v, cv = values.reshape(field.nrec, NB, NA), cover.reshape(field.nrec, NB, NA)
+        summary.update(var=field.name, records=field.nrec, shape=list(field.data.shape[-2:]))
+        if cell_weight is not None:   # sum_k S_k against sum_c g_c sum_{e in c} A_e, per record
+            g = field.records.astype(np.float64)
+            ok = ~np.isnan(g)
+            for f in field.fill:
+                ok &= field.records != f
+            summary["integral_model"] = [float(np.sum(np.where(ok[r], g[r], 0.0) * cell_weight)) for r in range(field.nrec)]
+            w = np.broadcast_to(a_atm, cv.shape) if normalize == "cell" else cv * a_atm
+            summary["integral_latlon"] = [float(np.sum(np.where(cv[r] > 0, v[r] * w[r], 0.0))) for r in range(field.nrec)]
+        out["values"], out["cover"] = v.reshape(shape), cv.reshape(shape)
+    return out
+
+
+def _cell_weight(ocn, area, shape):
+    return np.bincount(ocn[:, 1].astype(np.int64) * shape[1] + ocn[:, 0], weights=area, minlength=shape[0] * shape[1]).reshape(shape)
+
+
+# ---- host arrays -----------------------------------------------------------------------------------------------
+def regrid_to_latlon(x, y, field, lon_edges, lat_edges, mask=None, normalize="area", cover=False, fill_values=(), Re=X.DEFAULT_RE,
+                     threshold=X.DEFAULT_THRESHOLD, lists=None):
+    """The conservative regrid of ``field`` on the model cells of a stitched supergrid x, y ((ny + 1) x (nx + 1), degrees; nx, ny
+    even) onto the global lat-lon cells of edges lon_edges, lat_edges, on one GPU through the host-pointer entries (ogg_xgrid for the
+    list, ogg_regrid for the rest).  ``field``: a Field, an array (..., ny / 2, nx / 2) with fill_values, or None (the static sums
+    only).  mask: None or one value per model cell (0: the cell takes no part).  normalize: "area" (the mean over the valid part of
+    the cell) or "cell" (S / A_atm).  A dict (result()); cover is always formed and kept in it only when ``cover``.  ``lists``: the
+    exchange_grid() result of the same grid, edges, mask, Re and threshold, used instead of building the list again."""
+    x, y = L.as_f64(x), L.as_f64(y)
+    lon, lat = X.atm_edges(lon_edges, lat_edges)
+    X.check_args(threshold, Re)
+    if lists is None:
+        lists = X.exchange_grid(x, y, lon, lat, mask=mask, Re=Re, threshold=threshold)
+    shape = lists["a_poly"].shape
+    if field is not None and not isinstance(field, Field):
+        field = Field(field, fill=fill_values)
+    p = params(shape, lon, lat, field, normalize)
+    a_atm = np.ascontiguousarray(X.atm_area(lon, lat, Re))
+    nk = a_atm.size
+    frac = np.empty(nk)
+    nent = np.empty(nk, dtype=np.int32)
+    values = cv = None
+    if field is not None:
+        values = np.empty(field.nrec * nk)
+        cv = np.empty(field.nrec * nk)
+    counts = L.RegridCounts()
+    atm, ocn, area = (np.ascontiguousarray(lists[k]) for k in ("atm", "ocn", "area"))
+    L.call("ogg_regrid", ctypes.byref(p), None if field is None else field.records.ctypes.data, atm.ctypes.data, ocn.ctypes.data,
+           area.ctypes.data, area.size, a_atm.ctypes.data, None if values is None else values.ctypes.data,
+           None if cv is None else cv.ctypes.data, frac.ctypes.data, nent.ctypes.data, ctypes.byref(counts))
+    c = {f: int(getattr(counts, f)) for f in L.REGRID_COUNT_FIELDS}
+    res = result(values, cv, frac, nent, c, field, lon, lat, a_atm, normalize, mask is not None,
+                 None if field is None else _cell_weight(ocn, area, shape))
+    if not cover:
+        res["cover"] = None
+    return res
+
+
+def latlon_fraction(x, y, lon_edges, lat_edges, mask=None, Re=X.DEFAULT_RE, threshold=X.DEFAULT_THRESHOLD, lists=None):
+    """ocean_frac, n_entries and cell_area of every target cell (regrid_to_latlon without a field)"""
+    return regrid_to_latlon(x, y, None, lon_edges, lat_edges, mask=mask, Re=Re, threshold=threshold, lists=lists)
+
+
+# ---- device arrays ---------------------------------------------------------------------------------------------
+def lists_dev(p, atm, ocn, area, a_atm, f, stream, device):
+    """Both steps on a list and a field in device memory (f (nrec, ny, nx) or None): values and cover (nrec, NB, NA) float64 or None,
+    frac (NB, NA) float64, n_entries (NB, NA) int32, counts (int64 device tensor of 6)."""
+    import torch
+    lib = L.load()
+    n = int(area.numel())
+    wsb = int(lib.ogg_regrid_workspace_bytes(ctypes.byref(p), n))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=device)
+    counts = torch.zeros(len(L.REGRID_COUNT_FIELDS), dtype=torch.int64, device=device)
+    frac = torch.empty((p.NB, p.NA), dtype=torch.float64, device=device)
+    nent = torch.empty((p.NB, p.NA), dtype=torch.int32, device=device)
+    values = cover = None
+    if f is not None:
+        values = torch.empty((p.nrec, p.NB, p.NA), dtype=torch.float64, device=device)
+        cover = torch.empty((p.nrec, p.NB, p.NA), dtype=torch.float64, device=device)
+    L.call("ogg_regrid_transpose_dev", ctypes.byref(p), atm.data_ptr() if n else None, ocn.data_ptr() if n else None,
+           area.data_ptr() if n else None, n, ws.data_ptr(), wsb, counts.data_ptr(), stream)
+    L.call("ogg_regrid_dev", ctypes.byref(p), None if f is None else f.data_ptr(), a_atm.data_ptr(), n, ws.data_ptr(), wsb,
+           None if values is None else values.data_ptr(), None if cover is None else cover.data_ptr(), frac.data_ptr(), nent.data_ptr(),
+           counts.data_ptr(), stream)
+    return values, cover, frac, nent, counts
+
+
+def finish_dev(p, atm, ocn, area, field, lon, lat, a_atm, normalize, cover, masked, shape, stream, device):
+    """lists_dev on a gathered list, then result() with host arrays"""
+    import torch
+    f = None if field is None else torch.from_numpy(field.records).to(device)
+    values, cv, frac, nent, counts = lists_dev(p, atm, ocn, area, torch.from_numpy(a_atm).to(device), f, stream, device)
+    host = lambda t: None if t is None else t.cpu().numpy()   # noqa: E731
+    cw = None if field is None else _cell_weight(host(ocn), host(area), shape)
+    res = result(host(values), host(cv), host(frac), host(nent), counts_dict(host(counts)), field, lon, lat, a_atm, normalize, masked, cw)
+    if not cover:
+        res["cover"] = None
+    return res
+
+
+def regrid_to_latlon_dev(x, y, field, lon_edges, lat_edges, mask=None, normalize="area", cover=False, fill_values=(), Re=X.DEFAULT_RE,
+                         threshold=X.DEFAULT_THRESHOLD):
+    """regrid_to_latlon() on one GPU with the grid x, y as float64 device tensors ((ny + 1) x (nx + 1), contiguous rows): the list,
+    the transpose and the sums all on the device, on its current stream.  The same dict as regrid_to_latlon(), with host arrays."""
+    import torch
+    dev = x.device
+    x, y = x.contiguous(), y.contiguous()
+    nyp, nxp = x.shape
+    X.check_grid(nyp, nxp)
+    X.check_args(threshold, Re)
+    lon, lat = X.atm_edges(lon_edges, lat_edges)
+    shape = ((nyp - 1) // 2, (nxp - 1) // 2)
+    if field is not None and not isinstance(field, Field):
+        field = Field(field, fill=fill_values)
+    p = params(shape, lon, lat, field, normalize)
+    m = _mask(mask, shape)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    lt, bt = torch.from_numpy(lon).to(dev), torch.from_numpy(lat).to(dev)
+    desc = L.XgridAtm(lon=lt.data_ptr(), lat=bt.data_ptr(), NA=lon.size - 1, NB=lat.size - 1)
+    band = L.XgridBand(nx=nxp - 1, ny=nyp - 1, j0=0, n_cell_rows=nyp - 1, Re=float(Re), threshold=float(threshold))
+    band.x, band.y = x.data_ptr(), y.data_ptr()
+    band.x_next, band.y_next = x[nyp - 1:].data_ptr(), y[nyp - 1:].data_ptr()
+    mt = None if m is None else torch.from_numpy(m).to(dev)
+    band.mask = None if mt is None else mt.data_ptr()
+    _, _, _, atm, ocn, area = X.band_lists_dev(band, desc, st, dev)
+    return finish_dev(p, atm, ocn, area, field, lon, lat, np.ascontiguousarray(X.atm_area(lon, lat, Re)), normalize, cover, m is not None,
+                      shape, st, dev)
+
+
+# ---- files -----------------------------------------------------------------------------------------------------
+def _latlon_vars(ds, res):
+    lon, lat = res["lon_edges"], res["lat_edges"]
+    ds.def_var("lat", netcdf3.NC_DOUBLE, ("lat",), [("units", "degrees_north"), ("bounds", "lat_bnds")], 0.5 * (lat[:-1] + lat[1:]))
+    ds.def_var("lon", netcdf3.NC_DOUBLE, ("lon",), [("units", "degrees_east"), ("bounds", "lon_bnds")], 0.5 * (lon[:-1] + lon[1:]))
+    ds.def_var("lat_bnds", netcdf3.NC_DOUBLE, ("lat", "bnds"), [], np.stack([lat[:-1], lat[1:]], axis=1))
+    ds.def_var("lon_bnds", netcdf3.NC_DOUBLE, ("lon", "bnds"), [], np.stack([lon[:-1], lon[1:]], axis=1))
+    ds.def_var("cell_area", netcdf3.NC_DOUBLE, ("lat", "lon"), [("units", "m2"), ("long_name", "lat-lon cell area")], res["cell_area"])
+    ds.def_var("ocean_frac", netcdf3.NC_DOUBLE, ("lat", "lon"), [("long_name", "fraction of the cell covered by exchanging model cells")],
+               res["ocean_frac"])
+
+
+def write_regridded(path, results, title="conservative regrid of model-cell fields onto a lat-lon grid"):
+    """One float64 variable per field (its leading dimensions, then lat, lon; _FillValue FILL; units and long_name copied) and
+    <var>_cover when the result holds a cover, the cell centres, bounds and areas, ocean_frac and n_entries, the leading coordinate
+    variables copied from the field (the record dimension kept unlimited), as a NetCDF 64-bit-offset file.  ``results``: [(Field,
+    regrid_to_latlon() result)], all on one target grid."""
+    from . import remap as R
+    dims, coords, seen, record_dim = [], [], set(), None
+    for fld, res in results:
+        rd = fld.record_dim
+        if rd is not None:
+            if record_dim not in (None, rd):
+                raise ValueError("regrid: two record dimensions, %s and %s" % (record_dim, rd))
+            record_dim = rd
+        for d, n in fld.lead_dims:
+            if d in seen:
+                if dict(dims)[d] != n:
+                    raise ValueError("regrid: dimension %s has length %d in one variable and %d in another" % (d, dict(dims)[d], n))
+                continue
+            seen.add(d)
+            dims.append((d, n))
+            coords += [c for c in fld.coords if c[0] == d]
+        nbytes = int(np.prod(res["values"].shape[1 if rd else 0:], dtype=np.int64)) * 8
+        if nbytes > R.CDF2_VAR_LIMIT:
+            raise ValueError("regrid: %s takes %d bytes, more than one variable of a NetCDF 64-bit-offset file can hold (%d); regrid "
+                             "fewer records at a time" % (fld.name, nbytes, R.CDF2_VAR_LIMIT))
+    for fld, _ in results:
+        if record_dim is not None and record_dim in dict(fld.lead_dims) and fld.lead_dims[0][0] != record_dim:
+            raise ValueError("regrid: %s has the record dimension %s but not first" % (fld.name, record_dim))
+    if record_dim is not None:   # the record dimension first, as the format wants it
+        dims.sort(key=lambda d: d[0] != record_dim)
+    res0 = results[0][1]
+    NB, NA = res0["cell_area"].shape
+    dims += [("lat", NB), ("lon", NA), ("bnds", 2)]
+    ds = netcdf3.Dataset(path, dims, global_atts=[("title", title), ("normalize", res0["summary"]["normalize"])], record_dim=record_dim)
+    for name, nc_type, atts, vals in coords:
+        ds.def_var(name, nc_type, (name,), atts, vals)
+    _latlon_vars(ds, res0)
+    ds.def_var("n_entries", netcdf3.NC_INT, ("lat", "lon"), [("long_name", "exchange cells of the cell")], res0["n_entries"])
+    for fld, res in results:
+        lead = tuple(d for d, _ in fld.lead_dims)
+        ds.def_var(fld.name, netcdf3.NC_DOUBLE, lead + ("lat", "lon"), list(fld.atts) + [("_FillValue", FILL)], res["values"])
+        if res["cover"] is not None:
+            ds.def_var(fld.name + "_cover", netcdf3.NC_DOUBLE, lead + ("lat", "lon"),
+                       [("long_name", "fraction of the cell covered by valid values of " + fld.name)], res["cover"])
+    ds.write()
+
+
+def write_fraction(path, res, title="ocean and land fractions of the lat-lon cells"):
+    """ocean_frac, land_frac = 1 - min(ocean_frac, 1), cell_area and n_entries on the lat-lon grid of ``res`` (latlon_fraction()),
+    with the cell centres and bounds, as a NetCDF 64-bit-offset file."""
+    NB, NA = res["cell_area"].shape
+    ds = netcdf3.Dataset(path, [("lat", NB), ("lon", NA), ("bnds", 2)], global_atts=[("title", title)])
+    _latlon_vars(ds, res)
+    ds.def_var("land_frac", netcdf3.NC_DOUBLE, ("lat", "lon"), [("long_name", "1 - min(ocean_frac, 1)")],
+               1.0 - np.minimum(res["ocean_frac"], 1.0))
+    ds.def_var("n_entries", netcdf3.NC_INT, ("lat", "lon"), [("long_name", "exchange cells of the cell")], res["n_entries"])
+    ds.write()
+
+
+def summary_lines(res):
+    s = res["summary"]
+    out = []
+    if "var" in s:
+        out.append("   latlon regrid: %s, %d records of %d x %d model cells onto %d x %d lat-lon cells%s (normalize %s): %d (record, cell) "
+                   "pairs with values, %d without" % (s["var"], s["records"], s["shape"][1], s["shape"][0], s["n_lon"], s["n_lat"],
+                                                      " (masked)" if s["masked"] else "", s["normalize"], s["valid"], s["empty"]))
+        if "integral_model" in s:
+            m, ll = np.array(s["integral_model"]), np.array(s["integral_latlon"])
+            rel = float(np.max(np.abs(ll - m) / np.maximum(np.abs(m), 1e-300))) if m.size else 0.0
+            out.append("   latlon regrid: sum S %.15g against sum g A %.15g (record 0), largest relative difference %.3g"
+                       % (ll[0], m[0], rel))
+    out.append("   latlon regrid: %d of %d lat-lon cells with exchange cells (%d entries, at most %d in one cell); largest ocean_frac - 1 "
+               "%.3g" % (s["cells"], s["n_lon"] * s["n_lat"], s["entries"], s["max_entries"], s["frac_excess"]))
+    return out
+
+
+def main(argv=None):
+    from . import remap as R
+    p = argparse.ArgumentParser(prog="python -m ocean_model_grid_generator_amd.latlon_regrid",
+                                description="conservative regrid of model-cell fields of a supergrid file onto a regular lat-lon grid")
+    p.add_argument("grid", help="ocean_hgrid.nc (NetCDF classic / 64-bit offset)")
+    p.add_argument("fields", help="fields on the model cells (NetCDF classic / 64-bit offset)")
+    p.add_argument("--var", action="append", required=True, help="a variable of the fields file (repeatable)")
+    p.add_argument("--atm", type=int, nargs=2, required=True, metavar=("NLON", "NLAT"), help="a regular global target of NLON x NLAT cells")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--topog", default=None, help="topog.nc: only cells with depth > 0 exchange")
+    g.add_argument("--mask", default=None, help="ocean_mask.nc: only cells with mask != 0 exchange")
+    p.add_argument("--normalize", choices=("area", "cell"), default="area", help="area: S / W (default); cell: S / A_atm")
+    p.add_argument("--cover", action="store_true", help="also write <var>_cover = W / A_atm")
+    p.add_argument("-o", "--output", default="regridded.nc")
+    p.add_argument("--json", default=None, help="write the summaries as JSON to this file")
+    a = p.parse_args(argv)
+    grid = netcdf3.read_doubles(a.grid, names=("x", "y"))
+    shape = ((grid["x"].shape[0] - 1) // 2, (grid["x"].shape[1] - 1) // 2)
+    mask = R.mask_from_file(a.topog or a.mask) if (a.topog or a.mask) else None
+    lon, lat = X.regular_atm(*a.atm)
+    out = []
+    for var in a.var:
+        fld = read_field(a.fields, var, shape)
+        print(fld.note)
+        res = regrid_to_latlon(grid["x"], grid["y"], fld, lon, lat, mask=mask, normalize=a.normalize, cover=a.cover)
+        for line in summary_lines(res):
+            print(line)
+        out.append((fld, res))
+    write_regridded(a.output, out)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump([r["summary"] for _, r in out], fh, indent=1)
+    return out
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)

@@ -645,7 +645,7 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          topog_file="topog.nc", topog_refine=None, xgrid_atm=None, xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc",
          ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False, mask_seed=None, mask_keep_cells=0,
          remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None,
-         runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast"):
+         runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -671,7 +671,9 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     and depth_sampled, and the exchange grid uses the edited wet set; also an addition.  ``remap_source`` (--remap_source FILE): the
     variables ``remap_var`` of that lat-lon file remapped conservatively onto the model cells (remap.py; wet cells only when
     ``topog_source`` is given, the exchange grid's wet set; the wet cells the source leaves empty filled unless ``remap_no_fill``, at
-    most ``remap_fill_max`` cells away), written to ``remap_file``; also an addition."""
+    most ``remap_fill_max`` cells away), written to ``remap_file``; also an addition.  ``xgrid_frac_file`` (--xgrid_frac_file FILE,
+    needs ``xgrid_atm``): the ocean fraction, land fraction, area and exchange-cell count of every atmosphere cell (latlon_regrid.py;
+    wet cells only, as for the exchange grid), written to FILE; also an addition."""
     import time
 
     path = path or os.environ.get("OGG_MAIN_PATH", "pass")
@@ -684,13 +686,14 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
                                    cap_symmetry, quality_report, topog_source, topog_var, topog_file, topog_refine, xgrid_atm,
                                    xgrid_file, ocean_mask_file, mask_min_depth, mask_deepen, mask_seed, mask_keep_cells,
                                    remap_source, remap_var, remap_file, remap_no_fill, remap_fill_max, runoff_source, runoff_var,
-                                   runoff_file, runoff_targets)
+                                   runoff_file, runoff_targets, xgrid_frac_file)
     from . import supergrid as SG
 
     _validate_flags(match_dy, r_dp, lat_dp)
     _validate_mask_flags(ocean_mask_file, topog_source)
     _validate_remap_flags(remap_source, remap_var)
     _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targets, skip_metrics)
+    _validate_frac_flags(xgrid_frac_file, xgrid_atm)
     hist, source, desc = _meta_strings(inverse_resolution, no_changing_meta)
     start_time = time.time()
     plan = SG.SupergridPlan(inverse_resolution, r_dp=r_dp, lon_dp=lon_dp, lat_dp=lat_dp, exfracdp=exfracdp, south_cutoff_row=south_cutoff_row,
@@ -728,7 +731,10 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
         topo = _write_topog_and_mask(topo, mask, topog_file, ocean_mask_file)
     if xgrid_atm is not None:
         from . import exchange_grid as X
-        _write_xgrid(g.exchange_grid(cut, X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo)), xgrid_file)
+        xres = g.exchange_grid(cut, X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo))
+        _write_xgrid(xres, xgrid_file)
+        if xgrid_frac_file and xres is not None:   # rank 0's gathered list, not built a second time
+            _write_frac(g.regrid_to_latlon(cut, None, X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo), lists=xres), xgrid_frac_file)
     if remap_source is not None:
         _write_remap([(src, g.remap(cut, src, mask=_xgrid_mask(topo), fill=not remap_no_fill, fill_max=remap_fill_max))
                       for src in _remap_sources(remap_source, remap_var)], remap_file)
@@ -805,7 +811,7 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
                         xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0,
                         mask_deepen=False, mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None,
                         remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None, runoff_source=None, runoff_var=None,
-                        runoff_file="runoff.nc", runoff_targets="coast"):
+                        runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None):
     """The reference's own sequence of calls (OGG:855-1449), every callee a host-array function of this module (numpy in, numpy
     out, one staged device call each) and the stitching on the host: what a user gets who swaps the reference's module for this
     one function by function.  main() produces the same bits from one device-resident pass."""
@@ -814,6 +820,7 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
     _validate_mask_flags(ocean_mask_file, topog_source)
     _validate_remap_flags(remap_source, remap_var)
     _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targets, skip_metrics)
+    _validate_frac_flags(xgrid_frac_file, xgrid_atm)
     known_options = ["bp", "so", "p125sc", ""]
     unknown = list(set(match_dy).difference(known_options))
     if len(unknown) != 0:
@@ -1041,7 +1048,12 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
         topo = _write_topog_and_mask(topo, mask, topog_file, ocean_mask_file)
     if xgrid_atm is not None:   # the same list as the device pass gives, through the host-pointer entry
         from . import exchange_grid as X
-        _write_xgrid(X.exchange_grid(x3, y3, *X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo), Re=_default_Re), xgrid_file)
+        xres = X.exchange_grid(x3, y3, *X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo), Re=_default_Re)
+        _write_xgrid(xres, xgrid_file)
+        if xgrid_frac_file:   # the same fractions as the device pass gives, through the host-pointer entry, on the same list
+            from . import latlon_regrid as G
+            _write_frac(G.latlon_fraction(x3, y3, *X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo), Re=_default_Re, lists=xres),
+                        xgrid_frac_file)
     if remap_source is not None:   # the same values as the device pass gives, through the host-pointer entries
         from . import remap as R
         _write_remap([(src, R.remap(x3, y3, src, mask=_xgrid_mask(topo), fill=not remap_no_fill, fill_max=remap_fill_max, Re=_default_Re))
@@ -1177,6 +1189,18 @@ def _xgrid_mask(topo):
     return X.wet_mask(topo["depth"])
 
 
+def _validate_frac_flags(xgrid_frac_file, xgrid_atm):
+    if xgrid_frac_file and xgrid_atm is None:
+        raise ValueError("--xgrid_frac_file needs --xgrid_atm: the fractions are of that atmosphere's cells")
+
+
+def _write_frac(res, fnam):
+    from . import latlon_regrid as G
+    for line in G.summary_lines(res):
+        print(line)
+    G.write_fraction(str(fnam), res)
+
+
 def _write_xgrid(res, fnam):
     from . import exchange_grid as X
     for line in X.summary_lines(res):
@@ -1302,6 +1326,9 @@ def build_parser():
     parser.add_argument("--runoff_file", type=str, required=False, default="runoff.nc", help="runoff output file, default runoff.nc")
     parser.add_argument("--runoff_targets", type=str, choices=["coast", "wet"], required=False, default="coast",
                         help="coast (default): wet cells next to land; wet: every wet cell")
+    parser.add_argument("--xgrid_frac_file", type=str, required=False, default=None,
+                        help="write the ocean / land fraction, area and exchange-cell count of every --xgrid_atm atmosphere cell to this "
+                             "file (wet cells only when --topog_source is given)")
     return parser
 
 

@@ -1395,6 +1395,35 @@ class Supergrid(object):
         self.torch.cuda.synchronize(self.device)
         return out
 
+    def _gather_xgrid(self, cut, lon, lat, hm, threshold):
+        """Every rank's xgrid_lists on rank 0 in piece order, the canonical order of the list (None on the other ranks): [(piece index,
+        first model row, counts, a_poly, atm, ocn, area)], on the device or, under gloo, the CPU.  ``hm``: None or a uint8 host
+        array of every model cell."""
+        torch = self.torch
+        ncol = self.plan.Ni // 2
+
+        def records(g):
+            to = lambda a: torch.from_numpy(a).to(g.device)   # noqa: E731
+            return g.xgrid_lists(cut, (to(lon), to(lat)), None if hm is None else to(hm), threshold)
+
+        def send(e):   # counts first, then the arrays (when there are any), then a_poly
+            _, _, counts, a_poly, atm_ij, ocn_ij, area = e
+            return (counts,) + ((atm_ij, ocn_ij, area) if atm_ij.shape[0] else ()) + (a_poly,)
+
+        def recv(k, q, take):
+            m0, rows, _ = self._xgrid_rows(q)
+            if rows == 0:
+                return None
+            counts = take(len(L.XGRID_COUNT_FIELDS), torch.int64)
+            n = int(counts[L.XGRID_COUNT_FIELDS.index("kept")])
+            lists = [take(s, d) if n else torch.empty(s, dtype=d, device=counts.device)
+                     for s, d in (((n, 2), torch.int32), ((n, 2), torch.int32), (n, torch.float64))]
+            return (k, m0, counts, take((rows, ncol), torch.float64), *lists)
+        got = self._gather(self.quality_pieces(cut), records, send, recv)
+        if got is not None:
+            got.sort(key=lambda e: e[0])
+        return got
+
     def exchange_grid(self, cut, atm, mask=None, threshold=1e-6):
         """The atmosphere x ocean exchange grid of the stitched grid of every rank (exchange_grid.result on rank 0, None on the other
         ranks).  ``atm``: (lon_edges, lat_edges) of a global rectilinear atmosphere; ``mask``: None or one value per model cell (0:
@@ -1413,27 +1442,9 @@ class Supergrid(object):
             if hm.shape != shape:
                 raise ValueError("exchange grid: the mask is %s, the model cells %s" % (hm.shape, shape))
 
-        def records(g):
-            to = lambda a: torch.from_numpy(a).to(g.device)   # noqa: E731
-            return g.xgrid_lists(cut, (to(lon), to(lat)), None if hm is None else to(hm), threshold)
-
-        def send(e):   # counts first, then the arrays (when there are any), then a_poly
-            _, _, counts, a_poly, atm_ij, ocn_ij, area = e
-            return (counts,) + ((atm_ij, ocn_ij, area) if atm_ij.shape[0] else ()) + (a_poly,)
-
-        def recv(k, q, take):
-            m0, rows, _ = self._xgrid_rows(q)
-            if rows == 0:
-                return None
-            counts = take(len(L.XGRID_COUNT_FIELDS), torch.int64)
-            n = int(counts[L.XGRID_COUNT_FIELDS.index("kept")])
-            lists = [take(s, d) if n else torch.empty(s, dtype=d, device=counts.device)
-                     for s, d in (((n, 2), torch.int32), ((n, 2), torch.int32), (n, torch.float64))]
-            return (k, m0, counts, take((rows, shape[1]), torch.float64), *lists)
-        got = self._gather(self.quality_pieces(cut), records, send, recv)
+        got = self._gather_xgrid(cut, lon, lat, hm, threshold)
         if got is None:
             return None
-        got.sort(key=lambda e: e[0])   # piece order: the canonical order of the list
         hostp = [(m0,) + tuple(t.cpu().numpy() for t in ts) for _, m0, *ts in got]
         return X.assemble(hostp, shape, lon, lat, float(self.plan.Re), threshold, mask is not None)
 
@@ -1548,6 +1559,39 @@ class Supergrid(object):
             R.fill_dev(p, values, flags, counts, self._stream(), self.device)
         return R.result(values.cpu().numpy(), flags.cpu().numpy(), R.counts_dict(counts.cpu().numpy()), source, periodic, fold, fill,
                         fill_max, hm is not None)
+
+    # -- conservative regrid to a lat-lon grid ------------------------------------------------------------------------
+    def regrid_to_latlon(self, cut, field, atm, mask=None, normalize="area", cover=False, threshold=1e-6, lists=None):
+        """The conservative regrid (latlon_regrid.result on rank 0, None on the other ranks) of ``field`` (a latlon_regrid.Field, an
+        array (..., ny, nx) of the stitched grid's model cells, or None for the static sums alone) onto the lat-lon cells of ``atm``
+        = (lon_edges, lat_edges).  ``mask``: None or one value per model cell (0: the cell takes no part).  Every rank builds the
+        lists of its own pieces (xgrid_lists); rank 0 gathers them in piece order (_gather), then transposes and sums on its GPU: the
+        list is the canonical one whatever the rank count, and per-rank partial sums could not be combined bit-identically.  ``lists``:
+        rank 0's exchange_grid() result for the same atm, mask and threshold, whose list is used instead of building and gathering it
+        again (the call then runs on this rank alone)."""
+        from . import exchange_grid as X
+        from . import latlon_regrid as G
+        torch = self.torch
+        nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
+        X.check_grid(nyp, nxp)
+        X.check_args(threshold, self.plan.Re)
+        lon, lat = X.atm_edges(*atm)
+        shape = ((nyp - 1) // 2, (nxp - 1) // 2)
+        if field is not None and not isinstance(field, G.Field):
+            field = G.Field(field)
+        p = G.params(shape, lon, lat, field, normalize)   # the checks, before any device work
+        hm = G._mask(mask, shape)
+        if lists is not None:
+            atm_ij, ocn_ij, area = (torch.from_numpy(np.ascontiguousarray(lists[k])).to(self.device) for k in ("atm", "ocn", "area"))
+        else:
+            got = self._gather_xgrid(cut, lon, lat, hm, threshold)
+            if got is None:
+                return None
+            cat = lambda i, s, d: torch.cat([e[i].to(self.device) for e in got]) if got else torch.empty(s, dtype=d, device=self.device)   # noqa: E731
+            atm_ij, ocn_ij, area = cat(4, (0, 2), torch.int32), cat(5, (0, 2), torch.int32), cat(6, (0,), torch.float64)
+        a_atm = np.ascontiguousarray(X.atm_area(lon, lat, float(self.plan.Re)))
+        return G.finish_dev(p, atm_ij.contiguous(), ocn_ij.contiguous(), area.contiguous(), field, lon, lat, a_atm, normalize, cover,
+                            hm is not None, shape, self._stream(), self.device)
 
     # -- runoff mapping -----------------------------------------------------------------------------------------------
     def runoff(self, cut, source, wet, targets="coast"):
