@@ -926,6 +926,76 @@ int ogg_regrid_dev(const ogg_regrid_params* p, const void* f, const double* a_at
 int ogg_regrid(const ogg_regrid_params* p, const void* f, const int* atm_ij, const int* ocn_ij, const double* area, long n_entries,
                const double* a_atm, double* values, double* cover, double* frac, int* n_out, ogg_regrid_counts* counts);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Bilinear interpolation (an addition: the reference has none).  Scalar and vector fields on a global rectilinear (lat-lon) source
+ * interpolated between the source's cell centres at the h, u or v points of the grid, and vectors turned from (east, north) to the
+ * grid's own x and y directions with angle_dx.
+ *   source   as for the remap: edges lon (NA + 1, spanning 360 degrees) and lat (NB + 1, increasing), values f[r][J][I], float32 or
+ *            fp64 (float32 converted exactly), MISSING when NaN or equal to one of n_fill <= 2 fill values in the source's own type.
+ *            The nodes are the centres lonc[I] = (lon[I] + lon[I+1]) / 2 and latc[J] = (lat[J] + lat[J+1]) / 2.
+ *   points   of a supergrid of (2 ny + 1) x (2 nx + 1) points: OGG_BILINEAR_H (2j+1, 2i+1), ny x nx; OGG_BILINEAR_U (2j+1, 2i),
+ *            ny x (nx + 1); OGG_BILINEAR_V (2j, 2i+1), (ny + 1) x nx; OGG_BILINEAR_C (vectors only): the first component at the U
+ *            points, the second at the V points.
+ *   locate   point (x, y), all in fp64, no FMA.  c[I] = lonc[I] - lonc[0]; t = x - lonc[0]; t = t - 360 * floor(t / 360); t = 0
+ *            unless 0 <= t < 360.  I: the last index with c[I] <= t; I1 = (I + 1) mod NA; c1 = c[I + 1], or c[0] + 360 after the last
+ *            node; wx = (t - c[I]) / (c1 - c[I]).  y <= latc[0]: J = J1 = 0, wy = 0; y >= latc[NB-1]: J = J1 = NB - 1, wy = 0 (the
+ *            clamps beyond the first and last centres); otherwise J the last index with latc[J] <= y, J1 = J + 1,
+ *            wy = (y - latc[J]) / (latc[J1] - latc[J]).
+ *   value    weights (1-wx)(1-wy), wx(1-wy), (1-wx)wy, wx wy of the corners (J,I), (J,I1), (J1,I), (J1,I1), in that order.  S = sum
+ *            (w * f) and W = sum w over the corners that are not missing, left to right from +0.0, each product rounded before it is
+ *            added.  All four corners valid: value S; some valid and W > 0: S / W; both flag OGG_REMAP_REMAPPED.  Otherwise value
+ *            OGG_REMAP_FILL and flag OGG_REMAP_UNFILLED.  With a mask (H points only), dry cells: OGG_REMAP_DRY and OGG_REMAP_FILL.
+ *   vectors  a corner is valid only where both components are; both are interpolated with the same weights, so they have the same
+ *            flags (two copies, one per component: the fill changes flags in place).
+ *   fill     H points only: ogg_remap_fill_dev on each component's values and flags (same codes, fill_max and topology), while the
+ *            components are still eastward and northward.  U, V and C points have no mask and no fill: a point with no valid corner
+ *            stays OGG_REMAP_UNFILLED.
+ *   rotate   last.  a = angle_dx at the point (degrees); (sa, ca) = sincospi(a / 180); ug = U * ca + V * sa, vg = V * ca - U * sa,
+ *            products rounded, one addition each; points flagged OGG_REMAP_DRY or OGG_REMAP_UNFILLED keep OGG_REMAP_FILL.  ca and sa of
+ *            every point are returned (rot_cos, rot_sin), so everything downstream of them is bit for bit.  At C points ug is formed
+ *            at the U points and vg at the V points, each from both components interpolated there.
+ * Every value is a function of one point, the source and the angle there: BIT-IDENTICAL for any launch geometry (the OGG_BILINEAR_*
+ * environment knobs), run and rank count.  Output layout: values (fp64) and flags (uint8), (nrec, rows, columns), record-major.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { OGG_BILINEAR_H = 0, OGG_BILINEAR_U = 1, OGG_BILINEAR_V = 2, OGG_BILINEAR_C = 3 };
+/* ny * nx model cells, the supergrid rows given starting at model row m0 of the stitched grid (the fill needs m0 = 0);
+ * (ny + 1) * (nx + 1) < 2^31, nrec * (ny + 1) * (nx + 1) < 2^32, NA * NB < 2^31 */
+typedef struct ogg_bilinear_params {
+    long ny, nx, m0;
+    long NA, NB, nrec;
+    int dtype;                 /* OGG_REMAP_FLOAT32 / FLOAT64 */
+    int n_fill;                /* 0 .. OGG_REMAP_MAX_FILLS */
+    double fill[2];            /* the values that mark missing */
+    int points;                /* OGG_BILINEAR_H / U / V / C */
+    int ncomp;                 /* 1: a scalar, 2: a vector (eastward, northward) */
+    int topology;              /* fill step: OGG_MASK_PERIODIC | OGG_MASK_FOLD */
+    int fill_max;              /* fill step: the largest distance filled, < 0 for no limit */
+} ogg_bilinear_params;
+long ogg_bilinear_struct_bytes(void);                        /* sizeof(ogg_bilinear_params) */
+/* the checks of *p (sizes, dtype, n_fill, points, ncomp, C for a scalar, topology) and of a mask away from the H points: OGG_EARG
+ * with the reason, before any device work */
+int ogg_bilinear_check(const ogg_bilinear_params* p, int has_mask);
+/* locate and interpolate, device pointers, on a stream.  x, y: the supergrid points (2 ny + 1 rows of ld doubles); lon, lat: the
+ * source's edges; f (and f2 for a vector): nrec * NB * NA values of dtype; mask: NULL or one byte per model cell (H points only).
+ * values / flags: the scalar, or the first component; values2 / flags2: the second component (at C points on the V points' shape).
+ * cross / cross2 (C points only, NULL to skip, needed by the rotation): the second component at the U points and the first at the V
+ * points.  flags, flags2: allocations rounded up to a multiple of 4 bytes when the fill step follows. */
+int ogg_bilinear_dev(const ogg_bilinear_params* p, const double* x, const double* y, long ld, const double* lon, const double* lat,
+                     const void* f, const void* f2, const unsigned char* mask, double* values, unsigned char* flags, double* values2,
+                     unsigned char* flags2, double* cross, double* cross2, void* stream);
+/* the rotation of a vector's components (ncomp = 2) in place, after ogg_bilinear_dev (and the fill): angle the supergrid's angle_dx
+ * (2 ny + 1 rows of ld doubles); rot_cos / rot_sin one value per point (at C points: of the U points, and rot_cos2 / rot_sin2 of the V
+ * points; NULL otherwise).  rotate = 0: the cosines and sines only, the components stay eastward and northward. */
+int ogg_bilinear_rotate_dev(const ogg_bilinear_params* p, const double* angle, long ld, double* values, const unsigned char* flags,
+                            double* values2, const unsigned char* flags2, const double* cross, const double* cross2, double* rot_cos,
+                            double* rot_sin, double* rot_cos2, double* rot_sin2, int rotate, void* stream);
+/* HOST pointers throughout, staged through device memory: interpolate, the fill when do_fill != 0 (H points), the rotation for a
+ * vector (angle NULL: no rotation and no rot_cos / rot_sin).  Arrays of a scalar's second component are NULL. */
+int ogg_bilinear(const ogg_bilinear_params* p, const double* x, const double* y, const double* angle, const double* lon,
+                 const double* lat, const void* f, const void* f2, const unsigned char* mask, int do_fill, int rotate, double* values,
+                 unsigned char* flags, double* values2, unsigned char* flags2, double* rot_cos, double* rot_sin, double* rot_cos2,
+                 double* rot_sin2);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

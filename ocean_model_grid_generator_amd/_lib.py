@@ -191,6 +191,16 @@ REGRID_AREA, REGRID_CELL = 0, 1                                        # OGG_REG
 REGRID_PARAMS, REGRID_COUNTS = 0, 1                                    # OGG_REGRID_PARAMS, OGG_REGRID_COUNTS
 
 
+class BilinearParams(ctypes.Structure):
+    """ogg_bilinear_params of include/ogg_hip.h"""
+    _fields_ = [("ny", c_long), ("nx", c_long), ("m0", c_long), ("NA", c_long), ("NB", c_long), ("nrec", c_long), ("dtype", c_int),
+                ("n_fill", c_int), ("fill", c_double * 2), ("points", c_int), ("ncomp", c_int), ("topology", c_int), ("fill_max", c_int)]
+
+
+BILINEAR_H, BILINEAR_U, BILINEAR_V, BILINEAR_C = 0, 1, 2, 3            # OGG_BILINEAR_H ... OGG_BILINEAR_C
+BILINEAR_POINTS = {"h": BILINEAR_H, "u": BILINEAR_U, "v": BILINEAR_V, "c": BILINEAR_C}
+
+
 # name -> argtypes; every function returns int except the two string getters.  Must list EVERY symbol of ogg_hip.h
 # (tests/test_abi.py checks this list against the header).
 SIGNATURES = {
@@ -340,6 +350,13 @@ SIGNATURES = {
                        c_void_p, c_void_p],
     "ogg_regrid": [ctypes.POINTER(RegridParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
                    c_void_p, ctypes.POINTER(RegridCounts)],
+    "ogg_bilinear_check": [ctypes.POINTER(BilinearParams), c_int],
+    "ogg_bilinear_dev": [ctypes.POINTER(BilinearParams), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_bilinear_rotate_dev": [ctypes.POINTER(BilinearParams), c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "ogg_bilinear": [ctypes.POINTER(BilinearParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                     c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_event_create": [ctypes.POINTER(c_void_p)],
     "ogg_event_destroy": [c_void_p],
     "ogg_event_record": [c_void_p, c_void_p],
@@ -372,7 +389,8 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_runoff_struct_bytes": [c_int],
                 "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],
                 "ogg_regrid_struct_bytes": [c_int],
-                "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long]}
+                "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long],
+                "ogg_bilinear_struct_bytes": []}
 
 _lib = None
 

@@ -645,7 +645,9 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          topog_file="topog.nc", topog_refine=None, xgrid_atm=None, xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc",
          ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False, mask_seed=None, mask_keep_cells=0,
          remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None,
-         runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None):
+         runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None,
+         interp_source=None, interp_var=None, interp_vector=None, interp_points="h", interp_file="interp.nc", interp_no_fill=False,
+         interp_fill_max=None, interp_no_rotate=False):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -673,7 +675,12 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     ``topog_source`` is given, the exchange grid's wet set; the wet cells the source leaves empty filled unless ``remap_no_fill``, at
     most ``remap_fill_max`` cells away), written to ``remap_file``; also an addition.  ``xgrid_frac_file`` (--xgrid_frac_file FILE,
     needs ``xgrid_atm``): the ocean fraction, land fraction, area and exchange-cell count of every atmosphere cell (latlon_regrid.py;
-    wet cells only, as for the exchange grid), written to FILE; also an addition."""
+    wet cells only, as for the exchange grid), written to FILE; also an addition.  ``interp_source`` (--interp_source FILE): the
+    scalars ``interp_var`` and the vectors ``interp_vector`` ((eastward, northward) pairs) of that lat-lon file interpolated
+    bilinearly between the source's cell centres at the ``interp_points`` of the grid (bilinear.py; h, u, v, or c: a vector's first
+    component at u and its second at v), vectors turned to the grid's directions with angle_dx unless ``interp_no_rotate``; at the h
+    points the wet set is the remap's and the wet points the source leaves empty are filled unless ``interp_no_fill``, at most
+    ``interp_fill_max`` cells away; written to ``interp_file``; also an addition."""
     import time
 
     path = path or os.environ.get("OGG_MAIN_PATH", "pass")
@@ -686,7 +693,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
                                    cap_symmetry, quality_report, topog_source, topog_var, topog_file, topog_refine, xgrid_atm,
                                    xgrid_file, ocean_mask_file, mask_min_depth, mask_deepen, mask_seed, mask_keep_cells,
                                    remap_source, remap_var, remap_file, remap_no_fill, remap_fill_max, runoff_source, runoff_var,
-                                   runoff_file, runoff_targets, xgrid_frac_file)
+                                   runoff_file, runoff_targets, xgrid_frac_file, interp_source, interp_var, interp_vector,
+                                   interp_points, interp_file, interp_no_fill, interp_fill_max, interp_no_rotate)
     from . import supergrid as SG
 
     _validate_flags(match_dy, r_dp, lat_dp)
@@ -694,6 +702,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     _validate_remap_flags(remap_source, remap_var)
     _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targets, skip_metrics)
     _validate_frac_flags(xgrid_frac_file, xgrid_atm)
+    _validate_interp_flags(interp_source, interp_var, interp_vector, interp_points, skip_metrics, interp_no_fill, interp_fill_max,
+                           interp_no_rotate)
     hist, source, desc = _meta_strings(inverse_resolution, no_changing_meta)
     start_time = time.time()
     plan = SG.SupergridPlan(inverse_resolution, r_dp=r_dp, lon_dp=lon_dp, lat_dp=lat_dp, exfracdp=exfracdp, south_cutoff_row=south_cutoff_row,
@@ -741,6 +751,10 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     if runoff_source is not None:
         _write_runoff([(src, g.runoff(cut, src, _xgrid_mask(topo), targets=runoff_targets))
                        for src in _runoff_sources(runoff_source, runoff_var)], runoff_file)
+    if interp_source is not None:
+        _write_interp(_interp_results(interp_source, interp_var, interp_vector, interp_points, lambda s1, s2: g.bilinear(
+            cut, s1, s2, points=interp_points, mask=_xgrid_mask(topo) if interp_points == "h" else None, fill=not interp_no_fill,
+            fill_max=interp_fill_max, rotate=not interp_no_rotate)), interp_file)
     print("Stitching the grids together...")
     SG.check_guards(g.stitched_column("y", plan.Ni // 4, cut), any(s.name == "BP" for s in plan.subs))
     names = [s.name for s in plan.subs if not (s.name == "SC" and cut[2])]
@@ -811,7 +825,9 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
                         xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0,
                         mask_deepen=False, mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None,
                         remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None, runoff_source=None, runoff_var=None,
-                        runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None):
+                        runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None, interp_source=None, interp_var=None,
+                        interp_vector=None, interp_points="h", interp_file="interp.nc", interp_no_fill=False, interp_fill_max=None,
+                        interp_no_rotate=False):
     """The reference's own sequence of calls (OGG:855-1449), every callee a host-array function of this module (numpy in, numpy
     out, one staged device call each) and the stitching on the host: what a user gets who swaps the reference's module for this
     one function by function.  main() produces the same bits from one device-resident pass."""
@@ -821,6 +837,8 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
     _validate_remap_flags(remap_source, remap_var)
     _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targets, skip_metrics)
     _validate_frac_flags(xgrid_frac_file, xgrid_atm)
+    _validate_interp_flags(interp_source, interp_var, interp_vector, interp_points, skip_metrics, interp_no_fill, interp_fill_max,
+                           interp_no_rotate)
     known_options = ["bp", "so", "p125sc", ""]
     unknown = list(set(match_dy).difference(known_options))
     if len(unknown) != 0:
@@ -1062,6 +1080,12 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
         from . import runoff as RO
         _write_runoff([(src, RO.runoff(x3, y3, area3, src, _xgrid_mask(topo), targets=runoff_targets, Re=_default_Re))
                        for src in _runoff_sources(runoff_source, runoff_var)], runoff_file)
+    if interp_source is not None:   # the same values as the device pass gives, through the host-pointer entry
+        from . import bilinear as B
+        _write_interp(_interp_results(interp_source, interp_var, interp_vector, interp_points, lambda s1, s2: B.bilinear(
+            x3, y3, s1, s2, angle_dx=angle3 if s2 is not None else None, points=interp_points,
+            mask=_xgrid_mask(topo) if interp_points == "h" else None, fill=not interp_no_fill, fill_max=interp_fill_max,
+            rotate=not interp_no_rotate)), interp_file)
 
     if write_subgrid_files:
         if "SC" in sub:
@@ -1161,6 +1185,41 @@ def _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targe
         raise ValueError("--runoff_source needs --topog_source: the runoff goes to the wet cells of the topography")
     if runoff_targets not in ("coast", "wet"):
         raise ValueError("--runoff_targets must be coast or wet, not %r" % (runoff_targets,))
+
+
+def _validate_interp_flags(interp_source, interp_var, interp_vector, interp_points, skip_metrics, no_fill=False, fill_max=None,
+                           no_rotate=False):
+    if interp_source is None:
+        if interp_var or interp_vector or no_fill or fill_max is not None or no_rotate or interp_points != "h":
+            raise ValueError("--interp_var, --interp_vector, --interp_points, --interp_no_fill, --interp_fill_max and --interp_no_rotate "
+                             "need --interp_source")
+        return
+    from . import bilinear as B
+    for pair in interp_vector or ():
+        if len(pair) != 2:
+            raise ValueError("--interp_vector takes the eastward and the northward component: two names, not %r" % (pair,))
+    B.requests(interp_var, interp_vector, interp_points)
+    if interp_vector and skip_metrics:
+        raise ValueError("--interp_vector needs angle_dx: drop --skip_metrics")
+    if fill_max is not None and int(fill_max) < 0:
+        raise ValueError("--interp_fill_max must be >= 0 (%r)" % (fill_max,))
+
+
+def _interp_results(path, variables, vectors, points, interpolate):
+    from . import bilinear as B
+
+    def read(name):
+        src = B.R.read_source(str(path), name)
+        print(src.note)
+        return src
+    return B.run_requests(B.requests(variables, vectors, points), read, interpolate)
+
+
+def _write_interp(results, fnam):
+    from . import bilinear as B
+    if any(res is None for _, res in results):   # not rank 0
+        return
+    B.write_bilinear(str(fnam), results)
 
 
 def _mask_args(min_depth, deepen, seeds, keep_cells):
@@ -1329,6 +1388,21 @@ def build_parser():
     parser.add_argument("--xgrid_frac_file", type=str, required=False, default=None,
                         help="write the ocean / land fraction, area and exchange-cell count of every --xgrid_atm atmosphere cell to this "
                              "file (wet cells only when --topog_source is given)")
+    parser.add_argument("--interp_source", type=str, required=False, default=None,
+                        help="a global lat-lon file (NetCDF classic / 64-bit offset) whose --interp_var scalars and --interp_vector "
+                             "vectors are interpolated bilinearly at the grid's points into --interp_file")
+    parser.add_argument("--interp_var", type=str, action="append", required=False, default=None,
+                        help="a scalar variable of --interp_source (repeatable)")
+    parser.add_argument("--interp_vector", type=str, nargs=2, action="append", required=False, default=None, metavar=("U", "V"),
+                        help="the eastward and northward components of a vector of --interp_source (repeatable); turned to the "
+                             "grid's x and y directions with angle_dx unless --interp_no_rotate")
+    parser.add_argument("--interp_points", type=str, choices=["h", "u", "v", "c"], required=False, default="h",
+                        help="h (default): cell centres; u, v: cell faces; c: a vector's first component at u, its second at v")
+    parser.add_argument("--interp_file", type=str, required=False, default="interp.nc", help="interpolation output file, default interp.nc")
+    parser.add_argument("--interp_no_fill", action="store_true", help="leave wet h points the source does not cover unfilled")
+    parser.add_argument("--interp_fill_max", type=int, required=False, default=None,
+                        help="fill wet h points at most N cells away from an interpolated point (default: no limit)")
+    parser.add_argument("--interp_no_rotate", action="store_true", help="leave vectors as eastward and northward components")
     return parser
 
 

@@ -1605,6 +1605,44 @@ class Supergrid(object):
             return None
         return RO.runoff_dev(xy[0], xy[1], area, source, wet, targets=targets, Re=float(self.plan.Re))
 
+    # -- bilinear interpolation ---------------------------------------------------------------------------------------
+    def stitched_angle(self, cut):
+        """The stitched angle_dx ((nyp, nxp) float64 device tensor) on rank 0's device, None on the other ranks: every piece's point
+        rows gathered in piece order (_gather), as stitched_xy gathers the points."""
+        torch, nxp = self.torch, self.plan.Ni + 1
+        if self.plan.skip_metrics:
+            raise ValueError("angle_dx is not computed with --skip_metrics")
+
+        def records(g):
+            out = []
+            for k, q in enumerate(g.quality_pieces(cut)):
+                if q["rank"] == g.rank:
+                    out.append((k, g.buf[q["sub"].name]["angle_dx"][q["row"]:q["row"] + q["n_pt"]].to(self.device)))
+            return out
+
+        def recv(k, q, take):
+            return k, take((q["n_pt"], nxp), torch.float64)
+        got = self._gather(self.quality_pieces(cut), records, lambda e: (e[1].contiguous(),), recv)
+        if got is None:
+            return None
+        got.sort(key=lambda e: e[0])
+        return torch.cat([e[1].to(self.device) for e in got]).contiguous()
+
+    def bilinear(self, cut, source, source2=None, points="h", mask=None, fill=True, fill_max=None, rotate=True):
+        """The bilinear interpolation (bilinear.result on rank 0, None on the other ranks) of ``source`` (a remap.Source; with
+        ``source2`` the eastward and northward components of a vector) at the h, u, v or c points of the stitched grid, on rank 0's
+        GPU with the stitched points (and angle_dx for a vector) gathered there, as runoff does.  Every value is a function of one
+        point only, so the bits are the same for any number of ranks.  A vector needs angle_dx: ValueError with --skip_metrics."""
+        from . import bilinear as B
+        if source2 is not None and self.plan.skip_metrics:
+            raise ValueError("a vector needs angle_dx, which is not computed with --skip_metrics")
+        xy = self.stitched_xy(cut)
+        angle = self.stitched_angle(cut) if source2 is not None else None
+        if xy is None:
+            return None
+        return B.bilinear_dev(xy[0], xy[1], source, source2, angle_dx=angle, points=points, mask=mask, fill=fill, fill_max=fill_max,
+                              rotate=rotate)
+
     def bands_to_host(self):
         """This rank's bands as numpy arrays (halo rows dropped): {sub: {field: array}}."""
         out = {}
