@@ -16,13 +16,13 @@ second at the v points.  angle_dx comes from the grid file.
 """
 import argparse
 import ctypes
-import json
 import sys
 
 import numpy as np
 
 from . import _lib as L
 from . import exchange_grid as X
+from . import fields as F
 from . import netcdf3
 from . import remap as R
 
@@ -79,15 +79,6 @@ def _pair(source, source2):
         raise ValueError("bilinear: the two components have different fill values (%s, %s)" % (source.fill, source2.fill))
 
 
-def _mask(mask, shape):
-    if mask is None:
-        return None
-    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-    if m.shape != shape:
-        raise ValueError("bilinear: the mask is %s, the model cells %s" % (m.shape, shape))
-    return m
-
-
 def result(arrays, source, source2, points, periodic, fold, fill, fill_max, masked, rotated):
     """What bilinear() returns: values and flags (the source's leading dimensions, then the points' rows and columns); for a vector
     also values2 and flags2, and rot_cos / rot_sin (rot_cos2 / rot_sin2 at c points: the v points') when there was an angle; the counts
@@ -126,7 +117,7 @@ def bilinear(x, y, source, source2=None, angle_dx=None, points="h", mask=None, f
     X.check_grid(nyp, nxp)
     ny, nx = (nyp - 1) // 2, (nxp - 1) // 2
     vector = source2 is not None
-    m = _mask(mask, (ny, nx))
+    m = F.cell_mask(mask, (ny, nx), "bilinear: the mask")
     fill = bool(fill) and points == "h"
     periodic, fold = M.detect_topology(x, y, 2) if fill else (False, False)
     p = params(ny, nx, source, points, 2 if vector else 1, 0, periodic, fold, fill_max, m is not None)
@@ -182,13 +173,11 @@ def bilinear_dev(x, y, source, source2=None, angle_dx=None, points="h", mask=Non
     X.check_grid(nyp, nxp)
     ny, nx = (nyp - 1) // 2, (nxp - 1) // 2
     vector = source2 is not None
-    m = _mask(mask, (ny, nx))
+    m = F.cell_mask(mask, (ny, nx), "bilinear: the mask")
     fill = bool(fill) and points == "h"
     periodic, fold = False, False
     if fill:
-        xs, ys = x[::2, ::2], y[::2, ::2]
-        periodic, fold = M.topology_of_edges(*[(xs[sl].cpu().numpy(), ys[sl].cpu().numpy())
-                                              for sl in ((slice(None), 0), (slice(None), -1), (-1, slice(None)))])
+        periodic, fold = M.topology_of_device_grid(x, y)
     p = params(ny, nx, source, points, 2 if vector else 1, 0, periodic, fold, fill_max, m is not None)
     if vector and angle_dx is None and rotate:
         raise ValueError("bilinear: a vector is turned to the grid's directions with angle_dx; pass it, or rotate=False")
@@ -238,24 +227,12 @@ def write_bilinear(path, results, title="bilinear interpolation at the grid's po
     interpolated, 2 filled, 3 unfilled), the leading coordinate variables copied from the source, as a NetCDF 64-bit-offset file.  A
     vector's components carry the attributes vector_component, vector_partner and grid_relative ("true": along the grid's x and y;
     "false": eastward and northward).  ``results``: [((Source,) or (Source, Source), bilinear() result)]."""
-    dims, coords, seen, names = [], [], set(), set()
-    for srcs, res in results:
-        for d, n in srcs[0].lead_dims:
-            if d in seen:
-                if dict(dims)[d] != n:
-                    raise ValueError("bilinear: dimension %s has length %d in one variable and %d in another" % (d, dict(dims)[d], n))
-                continue
-            seen.add(d)
-            dims.append((d, n))
-            coords += [c for c in srcs[0].coords if c[0] == d]
-        for s, key in zip(srcs, ("values", "values2")):
-            if s.name in names:
-                raise ValueError("bilinear: the variable %s is asked for twice" % s.name)
-            names.add(s.name)
-            nbytes = int(np.prod(res[key].shape, dtype=np.int64)) * 8
-            if nbytes > R.CDF2_VAR_LIMIT:
-                raise ValueError("bilinear: %s takes %d bytes, more than one variable of a NetCDF 64-bit-offset file can hold (%d); "
-                                 "interpolate fewer records at a time" % (s.name, nbytes, R.CDF2_VAR_LIMIT))
+    names = [s.name for srcs, _ in results for s in srcs]
+    for n in names:
+        if names.count(n) > 1:
+            raise ValueError("bilinear: the variable %s is asked for twice" % n)
+    dims, coords, _ = F.writer_dims("bilinear", [(srcs[0], [(s.name, res[key]) for s, key in zip(srcs, ("values", "values2"))])
+                                                 for srcs, res in results], "; interpolate fewer records at a time")
     kinds = [k for _, res in results for k in _kinds(res["summary"]["points"], res["summary"]["vector"])]
     s0 = results[0][1]["summary"]
     ny, nx = s0["shape"][0] - (s0["points"] == "v"), s0["shape"][1] - (s0["points"] in ("u", "c"))
@@ -346,9 +323,7 @@ def main(argv=None):
                                                           points=a.points, mask=mask, fill=not a.no_fill, fill_max=a.fill_max,
                                                           rotate=not a.no_rotate))
     write_bilinear(a.output, out)
-    if a.json:
-        with open(a.json, "w") as fh:
-            json.dump([r["summary"] for _, r in out], fh, indent=1)
+    F.dump_summaries(a.json, out)
     return out
 
 

@@ -23,11 +23,14 @@
 #include <cstring>
 #include <vector>
 
+#include "ogg_blocks.h"
 #include "ogg_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+
+using ogg::knob;
 
 constexpr int NT = 256;                 // threads per workgroup (four wavefronts)
 constexpr int UNR = 4;                  // records whose gathers are in flight together
@@ -54,11 +57,6 @@ struct Geo {
     int n_fill, lds;
     double fill0, fill1;
 };
-
-template <typename T>
-__device__ inline bool missing(T v, T f0, T f1, int nf) {
-    return v != v || (nf > 0 && v == f0) || (nf > 1 && v == f1);
-}
 
 // the nodes: from LDS, or from the edges by the operations that filled the LDS
 struct Nodes {
@@ -230,17 +228,6 @@ int check_params(const ogg_bilinear_params* p, int has_mask) {
     return OGG_OK;
 }
 
-int knob(const char* name, int def, int lo, int hi, int* out) {
-    *out = def;
-    if (const char* e = getenv(name)) {
-        char* end = nullptr;
-        const long v = strtol(e, &end, 10);
-        OGG_REQUIRE(end != e && *end == '\0' && v >= lo && v <= hi, OGG_EARG, "%s=%s: an integer %d .. %d", name, e, lo, hi);
-        *out = (int)v;
-    }
-    return OGG_OK;
-}
-
 struct Launch {
     dim3 grid;
     size_t lds_bytes;
@@ -359,25 +346,7 @@ extern "C" int ogg_bilinear(const ogg_bilinear_params* p, const double* x, const
                 "ogg_bilinear: the fill is for the h points of the whole grid (points %d, m0 = %ld)", p->points, p->m0);
     const bool rot = vec && angle;
     OGG_REQUIRE(!rot || (rot_cos && rot_sin && (!c || (rot_cos2 && rot_sin2))), OGG_EARG, "ogg_bilinear: null rot_cos / rot_sin");
-    struct Buffers {   // freed on every exit path
-        std::vector<void*> p;
-        ~Buffers() {
-            for (void* q : p) (void)hipFree(q);
-        }
-        int alloc(void** out, size_t bytes) {
-            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
-            if (e != hipSuccess)
-                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
-                                      hipGetErrorString(e));
-            p.push_back(*out);
-            return OGG_OK;
-        }
-        int put(void** out, const void* src, size_t bytes) {
-            if (int e = alloc(out, bytes)) return e;
-            OGG_HIP_CHECK(hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice));
-            return OGG_OK;
-        }
-    } bufs;
+    ogg::Buffers bufs;   // freed on every exit path
     const long ld = 2 * p->nx + 1;
     const size_t gbytes = (size_t)(2 * p->ny + 1) * ld * 8;
     const size_t fbytes = (size_t)p->nrec * p->NA * p->NB * (p->dtype == OGG_REMAP_FLOAT32 ? 4 : 8);

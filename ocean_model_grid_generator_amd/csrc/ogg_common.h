@@ -2,8 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <vector>
 
 #include "../../include/ogg_hip.h"
 
@@ -55,3 +58,60 @@ class AsyncScratch {
     do {                                                  \
         if (!(cond)) return ogg::set_error(code, __VA_ARGS__); \
     } while (0)
+
+namespace ogg {
+
+// hipMalloc'd buffers of a host-pointer entry, freed on EVERY exit path of the call (the synchronous sibling of AsyncScratch).
+class Buffers {
+   public:
+    Buffers() = default;
+    Buffers(const Buffers&) = delete;
+    Buffers& operator=(const Buffers&) = delete;
+    ~Buffers() {
+        for (void* q : p_) (void)hipFree(q);
+    }
+    int alloc(void** out, size_t bytes) {
+        hipError_t e = hipMalloc(out, bytes ? bytes : 8);
+        if (e != hipSuccess)
+            return set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        p_.push_back(*out);
+        return OGG_OK;
+    }
+    // a buffer holding a copy of bytes of host memory
+    int put(void** out, const void* src, size_t bytes) {
+        if (int e = alloc(out, bytes)) return e;
+        OGG_HIP_CHECK(hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice));
+        return OGG_OK;
+    }
+
+   private:
+    std::vector<void*> p_;
+};
+
+// workspace sections start on 256-byte boundaries
+inline long round256(long v) { return (v + 255) / 256 * 256; }
+
+// a typed pointer into a workspace
+template <typename P>
+P* at(void* ws, long off) { return reinterpret_cast<P*>(static_cast<char*>(ws) + off); }
+template <typename P>
+const P* at(const void* ws, long off) { return reinterpret_cast<const P*>(static_cast<const char*>(ws) + off); }
+
+// workgroups of NT threads for n items of a grid-stride loop: at least one, at most cap
+template <int NT>
+unsigned grid_for(long n, long cap) { return (unsigned)std::min<long>(std::max<long>((n + NT - 1) / NT, 1), cap); }
+
+// an environment knob: def when unset, else the whole string must be an integer in lo .. hi (a pure host read, done when a call is
+// set up, before any device work)
+inline int knob(const char* name, int def, int lo, int hi, int* out) {
+    *out = def;
+    if (const char* e = getenv(name)) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        OGG_REQUIRE(end != e && *end == '\0' && v >= lo && v <= hi, OGG_EARG, "%s=%s: an integer %d .. %d", name, e, lo, hi);
+        *out = (int)v;
+    }
+    return OGG_OK;
+}
+
+}  // namespace ogg

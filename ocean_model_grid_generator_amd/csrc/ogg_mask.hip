@@ -29,9 +29,15 @@
 #include <cstring>
 #include <vector>
 
+#include "ogg_blocks.h"
 #include "ogg_common.h"
 
 namespace {
+
+using ogg::at;
+using ogg::grid_for;
+using ogg::knob;
+using ogg::round256;
 
 constexpr int TW = 64;       // tile width: one wavefront across a tile row
 constexpr int NT = 256;      // threads per workgroup
@@ -40,6 +46,7 @@ constexpr int TH_MAX = 64;
 constexpr long LIST_BLOCKS = 1024;   // blocks of the list and apply kernels: each block adds once to a shared counter word
 constexpr long APPLY_BLOCKS = 1024;
 
+static_assert(NT == BLOCKS_NT, "block_add sums over a workgroup of BLOCKS_NT threads");
 static_assert(sizeof(ogg_mask_params) == 48, "ogg_mask_params layout");
 static_assert(sizeof(ogg_mask_counts) == 64, "ogg_mask_counts layout");
 
@@ -50,25 +57,6 @@ struct Geo {
     double fill, min_depth;
     int mode;
 };
-
-__device__ inline unsigned long long* ull(long long* p) { return reinterpret_cast<unsigned long long*>(p); }
-
-// block sums of K counters: wavefront shuffles, then LDS, then one atomicAdd per block and non-zero counter (a counter word takes
-// every block's add, so the adds per word are as few as the blocks)
-template <int K>
-__device__ inline void block_add(long long (&v)[K], long long* const (&dst)[K]) {
-    __shared__ long long part[NT / 64][K];
-    for (int k = 0; k < K; ++k)
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < K; ++k) part[threadIdx.x / 64][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < K) {
-        long long t = 0;
-        for (int w = 0; w < NT / 64; ++w) t += part[w][threadIdx.x];
-        if (t) atomicAdd(ull(dst[threadIdx.x]), (unsigned long long)t);
-    }
-}
 
 // ---- tile-local labelling in LDS ---------------------------------------------------------------------------------
 __device__ inline int lds_find(int* lab, int x) {
@@ -368,8 +356,6 @@ __global__ __launch_bounds__(NT) void mask_seed_kernel(long ny, long nx, const d
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-long round256(long v) { return (v + 255) / 256 * 256; }
-
 int check_params(const ogg_mask_params* p) {
     OGG_REQUIRE(p, OGG_EARG, "ocean mask: null parameters");
     OGG_REQUIRE(p->ny >= 1 && p->nx >= 1, OGG_EARG, "ocean mask: %ld x %ld cells", p->ny, p->nx);
@@ -385,21 +371,9 @@ int check_params(const ogg_mask_params* p) {
 
 long ws_bytes(const ogg_mask_params& p) { return 2 * round256(p.ny * p.nx * 4); }
 
-int tile_rows(int* th) {
-    *th = TH_DEFAULT;
-    if (const char* e = getenv("OGG_MASK_TILE_ROWS")) {
-        const long v = atol(e);
-        OGG_REQUIRE(v >= 1 && v <= TH_MAX, OGG_EARG, "OGG_MASK_TILE_ROWS=%s: 1 .. %d", e, TH_MAX);
-        *th = (int)v;
-    }
-    return OGG_OK;
-}
-
 Geo make_geo(const ogg_mask_params& p, const double* depth, int th) {
     return Geo{depth, p.ny, p.nx, th, (int)((p.nx + TW - 1) / TW), p.fill, p.min_depth, p.mode};
 }
-
-unsigned grid_for(long n, long cap = 4096) { return (unsigned)std::min<long>(std::max<long>((n + NT - 1) / NT, 1), cap); }
 
 }  // namespace
 
@@ -421,10 +395,10 @@ extern "C" int ogg_mask_label_dev(const ogg_mask_params* p, const double* depth,
     OGG_REQUIRE(workspace && workspace_bytes >= ws_bytes(*p), OGG_EARG, "ogg_mask_label: workspace of %ld bytes, %ld needed",
                 workspace_bytes, ws_bytes(*p));
     int th = 0;
-    if (int e = tile_rows(&th)) return e;
+    if (int e = knob("OGG_MASK_TILE_ROWS", TH_DEFAULT, 1, TH_MAX, &th)) return e;
     const long n = p->ny * p->nx;
     int* par = static_cast<int*>(workspace);
-    int* size = reinterpret_cast<int*>(static_cast<char*>(workspace) + round256(n * 4));
+    int* size = at<int>(workspace, round256(n * 4));
     hipStream_t st = ogg::as_stream(stream);
     const Geo g = make_geo(*p, depth, th);
     const long nby = (p->ny + th - 1) / th;
@@ -438,12 +412,12 @@ extern "C" int ogg_mask_label_dev(const ogg_mask_params* p, const double* depth,
     if (p->topology & OGG_MASK_FOLD) f.n_f = p->nx / 2;
     const long faces = f.n_v + f.n_h + f.n_p + f.n_f;
     if (faces > 0) {
-        mask_merge_kernel<<<grid_for(faces), NT, 0, st>>>(f, par);
+        mask_merge_kernel<<<grid_for<NT>(faces, 4096), NT, 0, st>>>(f, par);
         OGG_LAUNCH_CHECK();
     }
     mask_flatten_kernel<<<(unsigned)tiles, NT, 3 * TW * th * sizeof(int), st>>>(g, par, root, size);
     OGG_LAUNCH_CHECK();
-    const long blocks = grid_for(n, LIST_BLOCKS), chunk = (n + blocks - 1) / blocks;
+    const long blocks = grid_for<NT>(n, LIST_BLOCKS), chunk = (n + blocks - 1) / blocks;
     mask_list_kernel<<<(unsigned)blocks, NT, 0, st>>>(n, chunk, root, size, components, counts);
     OGG_LAUNCH_CHECK();
     return OGG_OK;
@@ -460,9 +434,9 @@ extern "C" int ogg_mask_seed_dev(const ogg_mask_params* p, const double* x, cons
     const long n = p->ny * p->nx;
     OGG_HIP_CHECK(hipMemsetAsync(out, 0xFF, (size_t)n_seeds * 16, st));
     unsigned long long* o = reinterpret_cast<unsigned long long*>(out);
-    mask_seed_kernel<false><<<grid_for(n), NT, 0, st>>>(p->ny, p->nx, x, y, ld, n_seeds, lonlat, o);
+    mask_seed_kernel<false><<<grid_for<NT>(n, 4096), NT, 0, st>>>(p->ny, p->nx, x, y, ld, n_seeds, lonlat, o);
     OGG_LAUNCH_CHECK();
-    mask_seed_kernel<true><<<grid_for(n), NT, 0, st>>>(p->ny, p->nx, x, y, ld, n_seeds, lonlat, o);
+    mask_seed_kernel<true><<<grid_for<NT>(n, 4096), NT, 0, st>>>(p->ny, p->nx, x, y, ld, n_seeds, lonlat, o);
     OGG_LAUNCH_CHECK();
     return OGG_OK;
 }
@@ -476,11 +450,11 @@ extern "C" int ogg_mask_apply_dev(const ogg_mask_params* p, const double* depth,
     OGG_REQUIRE(workspace && workspace_bytes >= ws_bytes(*p), OGG_EARG, "ogg_mask_apply: workspace of %ld bytes, %ld needed",
                 workspace_bytes, ws_bytes(*p));
     const long n = p->ny * p->nx;
-    const int* size = reinterpret_cast<const int*>(static_cast<const char*>(workspace) + round256(n * 4));
+    const int* size = at<int>(workspace, round256(n * 4));
     hipStream_t st = ogg::as_stream(stream);
     OGG_HIP_CHECK(hipMemsetAsync(&counts->wet_in, 0, 3 * sizeof(long long), st));
     OGG_HIP_CHECK(hipMemsetAsync(&counts->kept, 0, 3 * sizeof(long long), st));
-    mask_apply_kernel<<<grid_for(n, APPLY_BLOCKS), NT, 0, st>>>(make_geo(*p, depth, 1), root, size, kept, n_kept, p->keep_min_cells, depth_out, wet,
+    mask_apply_kernel<<<grid_for<NT>(n, APPLY_BLOCKS), NT, 0, st>>>(make_geo(*p, depth, 1), root, size, kept, n_kept, p->keep_min_cells, depth_out, wet,
                                                   counts);
     OGG_LAUNCH_CHECK();
     return OGG_OK;
@@ -499,21 +473,8 @@ extern "C" int ogg_ocean_mask(const ogg_mask_params* p, const double* depth, con
                     "ocean mask: seed %d (%g, %g) is not a point on the sphere", s, lonlat[2 * s], lonlat[2 * s + 1]);
     OGG_REQUIRE(capacity >= 0 && (components || capacity == 0), OGG_EARG, "ogg_ocean_mask: component capacity %ld", capacity);
     int th = 0;
-    if (int e = tile_rows(&th)) return e;
-    struct Buffers {   // freed on every exit path
-        std::vector<void*> p;
-        ~Buffers() {
-            for (void* q : p) (void)hipFree(q);
-        }
-        int alloc(void** out, size_t bytes) {
-            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
-            if (e != hipSuccess)
-                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
-                                      hipGetErrorString(e));
-            p.push_back(*out);
-            return OGG_OK;
-        }
-    } bufs;
+    if (int e = knob("OGG_MASK_TILE_ROWS", TH_DEFAULT, 1, TH_MAX, &th)) return e;
+    ogg::Buffers bufs;   // freed on every exit path
     const long n = p->ny * p->nx, wsb = ws_bytes(*p);
     void *dd = nullptr, *ws = nullptr, *dr = nullptr, *dc = nullptr, *ct = nullptr, *dout = nullptr, *dwet = nullptr, *dk = nullptr;
     if (int e = bufs.alloc(&dd, (size_t)n * 8)) return e;

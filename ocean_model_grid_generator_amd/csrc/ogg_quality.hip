@@ -354,20 +354,7 @@ extern "C" int ogg_grid_quality(const ogg_quality_band* band, ogg_grid_quality_r
     OGG_REQUIRE(band && out, OGG_EARG, "ogg_grid_quality: null pointer");
     const ogg_quality_band& h = *band;
     OGG_REQUIRE(h.nx >= 1 && h.n_pt_rows >= 0 && h.n_cell_rows >= 0, OGG_EARG, "ogg_grid_quality: bad size");
-    struct Buffers {   // freed on every exit path
-        std::vector<void*> p;
-        ~Buffers() {
-            for (void* q : p) (void)hipFree(q);
-        }
-        int alloc(void** out, size_t bytes) {
-            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
-            if (e != hipSuccess)
-                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
-                                      hipGetErrorString(e));
-            p.push_back(*out);
-            return OGG_OK;
-        }
-    } bufs;
+    ogg::Buffers bufs;   // freed on every exit path
     const long nxp = h.nx + 1, np = h.n_pt_rows, nc = h.n_cell_rows;
     ogg_quality_band d = h;   // the same descriptor with device copies of every array it names
     auto up = [&bufs](const double* src, long n, const double** dst) -> int {

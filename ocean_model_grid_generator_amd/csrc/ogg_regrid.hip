@@ -28,6 +28,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ogg_blocks.h"
 #include "ogg_common.h"
 #include "ogg_keysort.h"
 
@@ -35,54 +36,20 @@
 
 namespace {
 
+using ogg::at;
+using ogg::grid_for;
+using ogg::knob;
+using ogg::round256;
+
 constexpr int NT = 256;                 // threads per workgroup of the list passes (four wavefronts)
-constexpr int PER = 8;                  // items per thread of the scan
-constexpr int CH = NT * PER;            // items per scan block
 constexpr int LONG_DEFAULT = 512;       // cells with more entries are walked by whole wavefronts (OGG_REGRID_LONG)
 constexpr int LONG_WAVES = 4096;        // wavefronts of the long-cell kernels (per record group)
 constexpr int RECORDS_DEFAULT = 4;      // records a lane sums at once (OGG_REGRID_RECORDS)
 constexpr long HEAD = 256;              // workspace head: the length of the long-cell list (int64)
 
+static_assert(NT == BLOCKS_NT, "block_add and block_scan work over a workgroup of BLOCKS_NT threads");
 static_assert(sizeof(ogg_regrid_params) == 72, "ogg_regrid_params layout");
 static_assert(sizeof(ogg_regrid_counts) == 48, "ogg_regrid_counts layout");
-
-__device__ inline unsigned long long* ull(long long* p) { return reinterpret_cast<unsigned long long*>(p); }
-
-template <int K>
-__device__ inline void block_add(long long (&v)[K], long long* const (&dst)[K]) {
-    __shared__ long long part[NT / 64][K];
-    for (int k = 0; k < K; ++k)
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < K; ++k) part[threadIdx.x / 64][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < K) {
-        long long t = 0;
-        for (int w = 0; w < NT / 64; ++w) t += part[w][threadIdx.x];
-        if (t) atomicAdd(ull(dst[threadIdx.x]), (unsigned long long)t);
-    }
-}
-
-// exclusive prefix of v over the workgroup; *total the sum
-__device__ inline long long block_scan(long long v, long long* total) {
-    __shared__ long long wsum[NT / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x / 64;
-    long long incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    long long base = 0, tot = 0;
-    for (int k = 0; k < NT / 64; ++k) {
-        if (k < w) base += wsum[k];
-        tot += wsum[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - v;
-}
 
 // ---- transpose -----------------------------------------------------------------------------------------------------
 struct List {
@@ -110,51 +77,6 @@ __global__ __launch_bounds__(NT) void count_kernel(List l, const int* __restrict
     }
     long long* const dst[2] = {&counts->entries, &counts->bad_entries};
     block_add<2>(v, dst);
-}
-
-// bsum[b] = the sum of cnt over block b (CH items)
-__global__ __launch_bounds__(NT) void scan_count_kernel(const int* __restrict__ in, long n, long long* __restrict__ bsum) {
-    const long b0 = (long)blockIdx.x * CH;
-    long long v = 0;
-    for (int k = 0; k < PER; ++k) {
-        const long i = b0 + k * NT + threadIdx.x;
-        if (i < n) v += in[i];
-    }
-    long long tot;
-    (void)block_scan(v, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-// exclusive scan of the nb block sums in place (one workgroup)
-__global__ __launch_bounds__(NT) void scan_blocks_kernel(long long* bsum, long nb) {
-    long long carry = 0;
-    for (long base = 0; base < nb; base += NT) {
-        const long i = base + threadIdx.x;
-        const long long v = i < nb ? bsum[i] : 0;
-        long long tot;
-        const long long ex = block_scan(v, &tot);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += tot;
-    }
-}
-
-// seg[i] = the sum of cnt[i'] for i' < i, i <= n (seg[n]: the total); PER consecutive items per thread
-__global__ __launch_bounds__(NT) void scan_write_kernel(const int* __restrict__ in, long n, const long long* __restrict__ bsum,
-                                                        int* __restrict__ seg) {
-    const long i0 = (long)blockIdx.x * CH + (long)threadIdx.x * PER;
-    long long v[PER], s = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        v[k] = i0 + k < n ? in[i0 + k] : 0;
-        s += v[k];
-    }
-    long long tot;
-    long long run = bsum[blockIdx.x] + block_scan(s, &tot);
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        if (i0 + k <= n) seg[i0 + k] = (int)run;
-        run += v[k];
-    }
 }
 
 // keys (k << 32) | position of KEYSORT_NT consecutive entries sorted in LDS by rank (the keys are unique)
@@ -193,11 +115,6 @@ struct Geo {
     int n_fill, cell_norm, long_n;
     double fill0, fill1;
 };
-
-template <typename T>
-__device__ inline bool missing(T v, T f0, T f1, int nf) {
-    return v != v || (nf > 0 && v == f0) || (nf > 1 && v == f1);
-}
 
 template <typename T, int R>
 __global__ __launch_bounds__(NT) void regrid_kernel(Geo g, const T* __restrict__ f, const int* __restrict__ seg, const int* __restrict__ pc,
@@ -378,8 +295,6 @@ __global__ __launch_bounds__(64) void static_long_kernel(const int* __restrict__
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-long round256(long v) { return (v + 255) / 256 * 256; }
-
 int check_params(const ogg_regrid_params* p) {
     OGG_REQUIRE(p, OGG_EARG, "regrid: null parameters");
     OGG_REQUIRE(p->ny >= 1 && p->nx >= 1 && p->ny <= (long)INT_MAX && p->nx <= (long)INT_MAX && p->ny * p->nx < (1L << 31), OGG_EARG,
@@ -409,7 +324,7 @@ Layout layout(const ogg_regrid_params& p, long n) {
     l.cur = HEAD;
     l.seg = l.cur + round256(nk * 4);
     l.bsum = l.seg + round256((nk + 1) * 4);
-    l.longs = l.bsum + round256(((nk + 1) / CH + 2) * 8);
+    l.longs = l.bsum + round256(((nk + 1) / SCAN_CH + 2) * 8);
     l.key0 = l.longs + round256(nk * 4);
     l.key1 = l.key0 + round256(n * 8);
     l.pc = l.key1 + round256(n * 8);
@@ -417,23 +332,6 @@ Layout layout(const ogg_regrid_params& p, long n) {
     l.total = l.pa + round256(n * 8);
     return l;
 }
-
-template <typename P>
-P* at(void* ws, long off) { return reinterpret_cast<P*>(static_cast<char*>(ws) + off); }
-template <typename P>
-const P* at(const void* ws, long off) { return reinterpret_cast<const P*>(static_cast<const char*>(ws) + off); }
-
-int knob(const char* name, int def, int lo, int hi, int* out) {
-    *out = def;
-    if (const char* e = getenv(name)) {
-        const long v = atol(e);
-        OGG_REQUIRE(v >= lo && v <= hi, OGG_EARG, "%s=%s: %d .. %d", name, e, lo, hi);
-        *out = (int)v;
-    }
-    return OGG_OK;
-}
-
-unsigned grid_for(long n, long cap) { return (unsigned)std::min<long>(std::max<long>((n + NT - 1) / NT, 1), cap); }
 
 struct Bufs {
     const int *seg, *pc, *longs;
@@ -494,26 +392,20 @@ extern "C" int ogg_regrid_transpose_dev(const ogg_regrid_params* p, const int* a
     OGG_HIP_CHECK(hipMemsetAsync(cur, 0, (size_t)nk * 4, st));
     const List li{n_entries, p->ny, p->nx, p->NA, p->NB};
     if (n_entries > 0) {
-        count_kernel<<<grid_for(n_entries, 8192), NT, 0, st>>>(li, atm_ij, ocn_ij, cur, counts);
+        count_kernel<<<grid_for<NT>(n_entries, 8192), NT, 0, st>>>(li, atm_ij, ocn_ij, cur, counts);
         OGG_LAUNCH_CHECK();
     }
-    const long nb = (nk + 1 + CH - 1) / CH;
-    scan_count_kernel<<<(unsigned)nb, NT, 0, st>>>(cur, nk, bsum);
-    OGG_LAUNCH_CHECK();
-    scan_blocks_kernel<<<1, NT, 0, st>>>(bsum, nb);
-    OGG_LAUNCH_CHECK();
-    scan_write_kernel<<<(unsigned)nb, NT, 0, st>>>(cur, nk, bsum, seg);
-    OGG_LAUNCH_CHECK();
+    if (int e = exclusive_scan<true>(cur, nk, bsum, nullptr, seg, st)) return e;   // seg[nk]: the total
     if (n_entries == 0) return OGG_OK;
     unsigned long long* key[2] = {at<unsigned long long>(workspace, l.key0), at<unsigned long long>(workspace, l.key1)};
     key_block_kernel<<<(unsigned)((n_entries + KEYSORT_NT - 1) / KEYSORT_NT), KEYSORT_NT, 0, st>>>(li, nk, atm_ij, ocn_ij, key[0]);
     OGG_LAUNCH_CHECK();
     int k = 0;
     for (long w = KEYSORT_NT; w < n_entries; w *= 2, ++k) {
-        keysort_merge_kernel<<<grid_for(n_entries, 1L << 20), KEYSORT_NT, 0, st>>>(key[k & 1], n_entries, w, key[(k + 1) & 1]);
+        keysort_merge_kernel<<<grid_for<NT>(n_entries, 1L << 20), KEYSORT_NT, 0, st>>>(key[k & 1], n_entries, w, key[(k + 1) & 1]);
         OGG_LAUNCH_CHECK();
     }
-    pairs_kernel<<<grid_for(n_entries, 8192), NT, 0, st>>>(n_entries, nk, p->nx, key[keysort_passes(n_entries) & 1], ocn_ij, area,
+    pairs_kernel<<<grid_for<NT>(n_entries, 8192), NT, 0, st>>>(n_entries, nk, p->nx, key[keysort_passes(n_entries) & 1], ocn_ij, area,
                                                            at<int>(workspace, l.pc), at<double>(workspace, l.pa));
     OGG_LAUNCH_CHECK();
     return OGG_OK;
@@ -573,20 +465,7 @@ extern "C" int ogg_regrid(const ogg_regrid_params* p, const void* f, const int* 
                 "ogg_regrid: null a_atm / atm_ij / ocn_ij / area / counts");
     OGG_REQUIRE((f == nullptr) == (values == nullptr), OGG_EARG, "ogg_regrid: f and values are given together or not at all");
     OGG_REQUIRE(values || !cover, OGG_EARG, "ogg_regrid: cover needs values");
-    struct Buffers {   // freed on every exit path
-        std::vector<void*> p;
-        ~Buffers() {
-            for (void* q : p) (void)hipFree(q);
-        }
-        int alloc(void** out, size_t bytes) {
-            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
-            if (e != hipSuccess)
-                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
-                                      hipGetErrorString(e));
-            p.push_back(*out);
-            return OGG_OK;
-        }
-    } bufs;
+    ogg::Buffers bufs;   // freed on every exit path
     const size_t nk = (size_t)p->NA * p->NB, nout = (size_t)p->nrec * nk;
     const size_t fbytes = (size_t)p->nrec * p->ny * p->nx * (p->dtype == OGG_REMAP_FLOAT32 ? 4 : 8);
     const long wsb = layout(*p, n_entries).total;

@@ -29,11 +29,17 @@
 #include <cstring>
 #include <vector>
 
+#include "ogg_blocks.h"
 #include "ogg_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+
+using ogg::at;
+using ogg::grid_for;
+using ogg::knob;
+using ogg::round256;
 
 constexpr int NT = 256;                 // threads per workgroup (four wavefronts)
 constexpr int REG = 8;                  // entries a lane keeps in registers across records
@@ -43,6 +49,7 @@ constexpr int FILL_BLOCKS_DEFAULT = 1024;
 constexpr long HEAD = 256;              // workspace: Head, then the segments, then the queue
 constexpr unsigned char Q0 = 4;         // a queued pair at distance d holds Q0 + d % 3
 
+static_assert(NT == BLOCKS_NT, "block_add sums over a workgroup of BLOCKS_NT threads");
 static_assert(sizeof(ogg_remap_params) == 80, "ogg_remap_params layout");
 static_assert(sizeof(ogg_remap_counts) == 64, "ogg_remap_counts layout");
 
@@ -55,23 +62,6 @@ struct Head {
     unsigned long long seg_bad;         // entries of the segment step outside the cells
 };
 static_assert(sizeof(Head) <= HEAD, "workspace head");
-
-__device__ inline unsigned long long* ull(long long* p) { return reinterpret_cast<unsigned long long*>(p); }
-
-template <int K>
-__device__ inline void block_add(long long (&v)[K], long long* const (&dst)[K]) {
-    __shared__ long long part[NT / 64][K];
-    for (int k = 0; k < K; ++k)
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < K; ++k) part[threadIdx.x / 64][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < K) {
-        long long t = 0;
-        for (int w = 0; w < NT / 64; ++w) t += part[w][threadIdx.x];
-        if (t) atomicAdd(ull(dst[threadIdx.x]), (unsigned long long)t);
-    }
-}
 
 // ---- segments ----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT) void remap_seg_kernel(long n, const int* __restrict__ ocn, long m0, long ny, long nx, int2* seg,
@@ -97,11 +87,6 @@ struct Geo {
     double fill0, fill1;
     const unsigned long long* seg_bad;
 };
-
-template <typename T>
-__device__ inline bool missing(T v, T f0, T f1, int nf) {
-    return v != v || (nf > 0 && v == f0) || (nf > 1 && v == f1);
-}
 
 template <typename T, bool CACHE>
 __global__ __launch_bounds__(NT) void remap_kernel(Geo g, const T* __restrict__ f, const int2* __restrict__ seg,
@@ -367,8 +352,6 @@ __global__ __launch_bounds__(NT) void remap_fill_last_kernel(unsigned long long 
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-long round256(long v) { return (v + 255) / 256 * 256; }
-
 int check_params(const ogg_remap_params* p) {
     OGG_REQUIRE(p, OGG_EARG, "remap: null parameters");
     OGG_REQUIRE(p->ny >= 1 && p->nx >= 1 && p->ny <= (long)INT_MAX && p->nx <= (long)INT_MAX && p->ny * p->nx < (1L << 31), OGG_EARG,
@@ -389,22 +372,10 @@ int check_params(const ogg_remap_params* p) {
 long seg_bytes(const ogg_remap_params& p) { return round256(p.ny * p.nx * 8); }
 long ws_bytes(const ogg_remap_params& p) { return HEAD + seg_bytes(p) + round256(p.nrec * p.ny * p.nx * 4); }
 
-int knob(const char* name, int def, int lo, int hi, int* out) {
-    *out = def;
-    if (const char* e = getenv(name)) {
-        const long v = atol(e);
-        OGG_REQUIRE(v >= lo && v <= hi, OGG_EARG, "%s=%s: %d .. %d", name, e, lo, hi);
-        *out = (int)v;
-    }
-    return OGG_OK;
-}
-
 int check_ws(const ogg_remap_params& p, const void* ws, long wsb, const char* who) {
     OGG_REQUIRE(ws && wsb >= ws_bytes(p), OGG_EARG, "%s: workspace of %ld bytes, %ld needed", who, wsb, ws_bytes(p));
     return OGG_OK;
 }
-
-unsigned grid_for(long n, long cap) { return (unsigned)std::min<long>(std::max<long>((n + NT - 1) / NT, 1), cap); }
 
 template <typename T, bool C>
 void launch_remap(dim3 grid, hipStream_t st, const Geo& g, const void* f, const int2* seg, const int* atm_ij, const double* area,
@@ -433,11 +404,11 @@ extern "C" int ogg_remap_segments_dev(const ogg_remap_params* p, const int* ocn_
     OGG_REQUIRE(ocn_ij || n_entries == 0, OGG_EARG, "ogg_remap_segments: null ocn_ij");
     hipStream_t st = ogg::as_stream(stream);
     Head* h = static_cast<Head*>(workspace);
-    int2* seg = reinterpret_cast<int2*>(static_cast<char*>(workspace) + HEAD);
+    int2* seg = at<int2>(workspace, HEAD);
     OGG_HIP_CHECK(hipMemsetAsync(&h->seg_bad, 0, sizeof(h->seg_bad), st));
     OGG_HIP_CHECK(hipMemsetAsync(seg, 0, (size_t)p->ny * p->nx * 8, st));
     if (n_entries == 0) return OGG_OK;
-    remap_seg_kernel<<<grid_for(n_entries, 4096), NT, 0, st>>>(n_entries, ocn_ij, p->m0, p->ny, p->nx, seg, &h->seg_bad);
+    remap_seg_kernel<<<grid_for<NT>(n_entries, 4096), NT, 0, st>>>(n_entries, ocn_ij, p->m0, p->ny, p->nx, seg, &h->seg_bad);
     OGG_LAUNCH_CHECK();
     return OGG_OK;
 }
@@ -460,7 +431,7 @@ extern "C" int ogg_remap_dev(const ogg_remap_params* p, const void* f, const int
     OGG_REQUIRE(nchunk <= 65535, OGG_EARG, "ogg_remap: %ld record chunks (OGG_REMAP_RECORDS=%d): at most 65535", nchunk, rec);
     hipStream_t st = ogg::as_stream(stream);
     const Head* h = static_cast<const Head*>(workspace);
-    const int2* seg = reinterpret_cast<const int2*>(static_cast<const char*>(workspace) + HEAD);
+    const int2* seg = at<int2>(workspace, HEAD);
     OGG_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(ogg_remap_counts), st));
     const Geo g{p->ny, p->nx, p->NA, p->NB, p->nrec, rchunk, p->n_fill, long_n, p->fill[0], p->fill[1], &h->seg_bad};
     const long waves = p->ny * ((p->nx + 63) / 64);
@@ -485,11 +456,11 @@ extern "C" int ogg_remap_fill_dev(const ogg_remap_params* p, void* workspace, lo
     if (int e = knob("OGG_REMAP_FILL_BLOCKS", FILL_BLOCKS_DEFAULT, 1, 1 << 16, &blocks)) return e;
     hipStream_t st = ogg::as_stream(stream);
     Head* h = static_cast<Head*>(workspace);
-    unsigned* queue = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + HEAD + seg_bytes(*p));
+    unsigned* queue = at<unsigned>(workspace, HEAD + seg_bytes(*p));
     const Topo t{p->ny, p->nx, p->ny * p->nx, (unsigned long long)(p->nrec * p->ny * p->nx), (p->topology & OGG_MASK_PERIODIC) ? 1 : 0,
                  (p->topology & OGG_MASK_FOLD) ? 1 : 0};
     OGG_HIP_CHECK(hipMemsetAsync(h, 0, sizeof(Slot) * 3 + sizeof(long long), st));
-    remap_fill_first_kernel<<<grid_for((long)((t.total + 3) / 4), blocks), NT, 0, st>>>(t, flags, queue, h);
+    remap_fill_first_kernel<<<grid_for<NT>((long)((t.total + 3) / 4), blocks), NT, 0, st>>>(t, flags, queue, h);
     OGG_LAUNCH_CHECK();
     int k = 1;
     long long launches = 0;
@@ -504,7 +475,7 @@ extern "C" int ogg_remap_fill_dev(const ogg_remap_params* p, void* workspace, lo
         if (hh.slot[k % 3].count == 0 || (p->fill_max >= 0 && k > p->fill_max)) break;
     }
     const unsigned long long n_done = hh.slot[k % 3].lo, n_total = n_done + hh.slot[k % 3].count;
-    remap_fill_last_kernel<<<grid_for((long)std::max<unsigned long long>(n_total, 1), blocks), NT, 0, st>>>(
+    remap_fill_last_kernel<<<grid_for<NT>((long)std::max<unsigned long long>(n_total, 1), blocks), NT, 0, st>>>(
         n_done, n_total, queue, flags, counts, hh.max_distance, launches);
     OGG_LAUNCH_CHECK();
     return OGG_OK;
@@ -518,20 +489,7 @@ extern "C" int ogg_remap(const ogg_remap_params* p, const void* f, const int* at
     OGG_REQUIRE(f && values && flags && counts && ((atm_ij && ocn_ij && area) || n_entries == 0), OGG_EARG,
                 "ogg_remap: null f / atm_ij / ocn_ij / area / values / flags / counts");
     OGG_REQUIRE(!do_fill || p->m0 == 0, OGG_EARG, "ogg_remap: the fill needs the whole grid (m0 = %ld)", p->m0);
-    struct Buffers {   // freed on every exit path
-        std::vector<void*> p;
-        ~Buffers() {
-            for (void* q : p) (void)hipFree(q);
-        }
-        int alloc(void** out, size_t bytes) {
-            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
-            if (e != hipSuccess)
-                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
-                                      hipGetErrorString(e));
-            p.push_back(*out);
-            return OGG_OK;
-        }
-    } bufs;
+    ogg::Buffers bufs;   // freed on every exit path
     const size_t ncell = (size_t)p->ny * p->nx, npair = (size_t)p->nrec * ncell;
     const size_t fbytes = (size_t)p->nrec * p->NA * p->NB * (p->dtype == OGG_REMAP_FLOAT32 ? 4 : 8);
     const long wsb = ws_bytes(*p);

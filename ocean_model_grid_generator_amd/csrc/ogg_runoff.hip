@@ -27,6 +27,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ogg_blocks.h"
 #include "ogg_common.h"
 #include "ogg_keysort.h"
 
@@ -34,9 +35,12 @@
 
 namespace {
 
+using ogg::at;
+using ogg::grid_for;
+using ogg::knob;
+using ogg::round256;
+
 constexpr int NT = 256;                 // threads per workgroup (four wavefronts)
-constexpr int PER = 8;                  // items per thread of the scan
-constexpr int CH = NT * PER;            // items per scan block
 constexpr int REG = 8;                  // sources a lane keeps in registers across records
 constexpr int LONG_N = 32;              // cells with more sources are walked by the whole wavefront
 constexpr long HEAD = 256;
@@ -46,50 +50,13 @@ constexpr double MARGIN = 1.0 + 1e-12;  // covers the rounding of a computed d2
 
 static_assert(sizeof(ogg_runoff_params) == 80, "ogg_runoff_params layout");
 static_assert(sizeof(ogg_runoff_counts) == 64, "ogg_runoff_counts layout");
+static_assert(NT == BLOCKS_NT, "block_add and block_scan work over a workgroup of BLOCKS_NT threads");
 static_assert(NT == KEYSORT_NT, "the block sort makes the runs the merge passes take");
 
 struct Head {
     long long total;                    // the last scan's total
 };
 static_assert(sizeof(Head) <= HEAD, "workspace head");
-
-__device__ inline unsigned long long* ull(long long* p) { return reinterpret_cast<unsigned long long*>(p); }
-
-template <int K>
-__device__ inline void block_add(long long (&v)[K], long long* const (&dst)[K]) {
-    __shared__ long long part[NT / 64][K];
-    for (int k = 0; k < K; ++k)
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < K; ++k) part[threadIdx.x / 64][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < K) {
-        long long t = 0;
-        for (int w = 0; w < NT / 64; ++w) t += part[w][threadIdx.x];
-        if (t) atomicAdd(ull(dst[threadIdx.x]), (unsigned long long)t);
-    }
-}
-
-// exclusive prefix of v over the workgroup; *total the sum
-__device__ inline long long block_scan(long long v, long long* total) {
-    __shared__ long long wsum[NT / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x / 64;
-    long long incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    long long base = 0, tot = 0;
-    for (int k = 0; k < NT / 64; ++k) {
-        if (k < w) base += wsum[k];
-        tot += wsum[k];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - v;
-}
 
 __device__ inline void unit(double lon, double lat, double* u) {
     const double cl = cos(lat * D);
@@ -107,55 +74,6 @@ __device__ inline unsigned long long bits_of(double v) {
     unsigned long long b;
     memcpy(&b, &v, 8);
     return b;
-}
-
-// ---- ordered compaction --------------------------------------------------------------------------------------------
-// bsum[b] = the number of items of block b (CH items) that are non-zero
-template <typename T>
-__global__ __launch_bounds__(NT) void scan_count_kernel(const T* __restrict__ in, long n, long long* __restrict__ bsum) {
-    const long b0 = (long)blockIdx.x * CH;
-    long long v = 0;
-    for (int k = 0; k < PER; ++k) {
-        const long i = b0 + k * NT + threadIdx.x;
-        if (i < n) v += (long long)in[i];
-    }
-    long long tot;
-    (void)block_scan(v, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-// exclusive scan of the nb block counts in place (one workgroup); head->total the sum
-__global__ __launch_bounds__(NT) void scan_blocks_kernel(long long* bsum, long nb, Head* head) {
-    long long carry = 0;
-    for (long base = 0; base < nb; base += NT) {
-        const long i = base + threadIdx.x;
-        const long long v = i < nb ? bsum[i] : 0;
-        long long tot;
-        const long long ex = block_scan(v, &tot);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) head->total = carry;
-}
-
-// every item's exclusive prefix (in[i] summed over i' < i): PER consecutive items per thread, so the order is the index order
-template <typename T>
-__global__ __launch_bounds__(NT) void scan_write_kernel(const T* __restrict__ in, long n, const long long* __restrict__ bsum,
-                                                        int* __restrict__ out) {
-    const long i0 = (long)blockIdx.x * CH + (long)threadIdx.x * PER;
-    long long v[PER], s = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        v[k] = i0 + k < n ? (long long)in[i0 + k] : 0;
-        s += v[k];
-    }
-    long long tot;
-    long long run = bsum[blockIdx.x] + block_scan(s, &tot);
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        if (i0 + k < n) out[i0 + k] = (int)run;
-        run += v[k];
-    }
 }
 
 // ---- targets -------------------------------------------------------------------------------------------------------
@@ -207,11 +125,6 @@ __global__ __launch_bounds__(NT) void target_list_kernel(long ny, long nx, const
 }
 
 // ---- sources -------------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ inline bool missing(T v, T f0, T f1, int nf) {
-    return v != v || (nf > 0 && v == f0) || (nf > 1 && v == f1);
-}
-
 template <typename T>
 __global__ __launch_bounds__(NT) void source_flag_kernel(const T* __restrict__ f, long nsrc, long nrec, int nf, double fill0, double fill1,
                                                          unsigned char* __restrict__ flag, ogg_runoff_counts* counts) {
@@ -526,8 +439,6 @@ __global__ __launch_bounds__(NT) void accumulate_kernel(Geo g, const T* __restri
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-long round256(long v) { return (v + 255) / 256 * 256; }
-
 int check_params(const ogg_runoff_params* p) {
     OGG_REQUIRE(p, OGG_EARG, "runoff: null parameters");
     OGG_REQUIRE(p->ny >= 1 && p->nx >= 1 && p->ny <= (long)INT_MAX && p->nx <= (long)INT_MAX && p->ny * p->nx < (1L << 31), OGG_EARG,
@@ -565,7 +476,7 @@ Layout layout(const ogg_runoff_params& p) {
     l.flag = HEAD;
     l.pos = l.flag + round256(ni);
     l.bsum = l.pos + round256(ni * 4);
-    l.As = l.bsum + round256((std::max(ni, nb) / CH + 2) * 8);
+    l.As = l.bsum + round256((std::max(ni, nb) / SCAN_CH + 2) * 8);
     l.cnt = l.As + round256(ns * 8);
     l.start = l.cnt + round256(nb * 4);
     l.bin = l.start + round256(nb * 4);
@@ -578,45 +489,9 @@ Layout layout(const ogg_runoff_params& p) {
     return l;
 }
 
-template <typename P>
-P* at(void* ws, long off) { return reinterpret_cast<P*>(static_cast<char*>(ws) + off); }
-template <typename P>
-const P* at(const void* ws, long off) { return reinterpret_cast<const P*>(static_cast<const char*>(ws) + off); }
-
-int knob(const char* name, int def, int lo, int hi, int* out) {
-    *out = def;
-    if (const char* e = getenv(name)) {
-        const long v = atol(e);
-        OGG_REQUIRE(v >= lo && v <= hi, OGG_EARG, "%s=%s: %d .. %d", name, e, lo, hi);
-        *out = (int)v;
-    }
-    return OGG_OK;
-}
-
 int check_ws(const ogg_runoff_params& p, const void* ws, long wsb, const char* who) {
     const long need = layout(p).total;
     OGG_REQUIRE(ws && wsb >= need, OGG_EARG, "%s: workspace of %ld bytes, %ld needed", who, wsb, need);
-    return OGG_OK;
-}
-
-unsigned grid_for(long n, long cap) { return (unsigned)std::min<long>(std::max<long>((n + NT - 1) / NT, 1), cap); }
-
-// pos[i] = the number of non-zero in[i'] for i' < i, for i < n; head->total their sum
-template <typename T>
-int scan(const T* in, long n, void* ws, const Layout& l, hipStream_t st) {
-    const long nb = (n + CH - 1) / CH;
-    scan_count_kernel<T><<<(unsigned)nb, NT, 0, st>>>(in, n, at<long long>(ws, l.bsum));
-    OGG_LAUNCH_CHECK();
-    scan_blocks_kernel<<<1, NT, 0, st>>>(at<long long>(ws, l.bsum), nb, at<Head>(ws, 0));
-    OGG_LAUNCH_CHECK();
-    return OGG_OK;
-}
-
-template <typename T>
-int scan_write(const T* in, long n, int* out, void* ws, const Layout& l, hipStream_t st) {
-    const long nb = (n + CH - 1) / CH;
-    scan_write_kernel<T><<<(unsigned)nb, NT, 0, st>>>(in, n, at<long long>(ws, l.bsum), out);
-    OGG_LAUNCH_CHECK();
     return OGG_OK;
 }
 
@@ -648,11 +523,10 @@ extern "C" int ogg_runoff_targets_dev(const ogg_runoff_params* p, const double* 
                   p->targets == OGG_RUNOFF_COAST ? 1 : 0};
     unsigned char* flag = at<unsigned char>(workspace, l.flag);
     int* pos = at<int>(workspace, l.pos);
-    target_flag_kernel<<<grid_for(nc, 4096), NT, 0, st>>>(g, wet, flag, counts);
+    target_flag_kernel<<<grid_for<NT>(nc, 4096), NT, 0, st>>>(g, wet, flag, counts);
     OGG_LAUNCH_CHECK();
-    if (int e = scan<unsigned char>(flag, nc, workspace, l, st)) return e;
-    if (int e = scan_write<unsigned char>(flag, nc, pos, workspace, l, st)) return e;
-    target_list_kernel<<<grid_for(nc, 4096), NT, 0, st>>>(p->ny, p->nx, flag, pos, x, y, ld, tgt_cell, tgt_u);
+    if (int e = exclusive_scan<false>(flag, nc, at<long long>(workspace, l.bsum), &at<Head>(workspace, 0)->total, pos, st)) return e;
+    target_list_kernel<<<grid_for<NT>(nc, 4096), NT, 0, st>>>(p->ny, p->nx, flag, pos, x, y, ld, tgt_cell, tgt_u);
     OGG_LAUNCH_CHECK();
     return OGG_OK;
 }
@@ -670,17 +544,16 @@ extern "C" int ogg_runoff_sources_dev(const ogg_runoff_params* p, const void* f,
     unsigned char* flag = at<unsigned char>(workspace, l.flag);
     int* pos = at<int>(workspace, l.pos);
     if (p->dtype == OGG_REMAP_FLOAT32)
-        source_flag_kernel<float><<<grid_for(ns, 4096), NT, 0, st>>>(static_cast<const float*>(f), ns, p->nrec, p->n_fill, p->fill[0],
+        source_flag_kernel<float><<<grid_for<NT>(ns, 4096), NT, 0, st>>>(static_cast<const float*>(f), ns, p->nrec, p->n_fill, p->fill[0],
                                                                     p->fill[1], flag, counts);
     else
-        source_flag_kernel<double><<<grid_for(ns, 4096), NT, 0, st>>>(static_cast<const double*>(f), ns, p->nrec, p->n_fill, p->fill[0],
+        source_flag_kernel<double><<<grid_for<NT>(ns, 4096), NT, 0, st>>>(static_cast<const double*>(f), ns, p->nrec, p->n_fill, p->fill[0],
                                                                      p->fill[1], flag, counts);
     OGG_LAUNCH_CHECK();
-    source_ds_kernel<<<grid_for(p->NB, 64), NT, 0, st>>>(lat, p->NB, ds);
+    source_ds_kernel<<<grid_for<NT>(p->NB, 64), NT, 0, st>>>(lat, p->NB, ds);
     OGG_LAUNCH_CHECK();
-    if (int e = scan<unsigned char>(flag, ns, workspace, l, st)) return e;
-    if (int e = scan_write<unsigned char>(flag, ns, pos, workspace, l, st)) return e;
-    source_list_kernel<<<grid_for(ns, 4096), NT, 0, st>>>(p->NA, p->NB, flag, pos, lon, lat, ds, p->Re, src_cell, src_u,
+    if (int e = exclusive_scan<false>(flag, ns, at<long long>(workspace, l.bsum), &at<Head>(workspace, 0)->total, pos, st)) return e;
+    source_list_kernel<<<grid_for<NT>(ns, 4096), NT, 0, st>>>(p->NA, p->NB, flag, pos, lon, lat, ds, p->Re, src_cell, src_u,
                                                           at<double>(workspace, l.As));
     OGG_LAUNCH_CHECK();
     return OGG_OK;
@@ -720,23 +593,18 @@ extern "C" int ogg_runoff_search_dev(const ogg_runoff_params* p, const int* tgt_
     int* start = at<int>(workspace, l.start);
     int* bin = at<int>(workspace, l.bin);
     OGG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)(nb + 1) * 4, st));
-    bin_count_kernel<<<grid_for(n_targets, 4096), NT, 0, st>>>(tgt_u, n_targets, (int)G, cnt, bin);
+    bin_count_kernel<<<grid_for<NT>(n_targets, 4096), NT, 0, st>>>(tgt_u, n_targets, (int)G, cnt, bin);
     OGG_LAUNCH_CHECK();
     // starts: the exclusive prefix of the counts over nb + 1 cubes (cnt[nb] = 0, so start[nb] = n_targets)
-    const long nb1 = nb + 1, nblk = (nb1 + CH - 1) / CH;
-    scan_count_kernel<int><<<(unsigned)nblk, NT, 0, st>>>(cnt, nb1, at<long long>(workspace, l.bsum));
-    OGG_LAUNCH_CHECK();
-    scan_blocks_kernel<<<1, NT, 0, st>>>(at<long long>(workspace, l.bsum), nblk, at<Head>(workspace, 0));
-    OGG_LAUNCH_CHECK();
-    scan_write_kernel<int><<<(unsigned)nblk, NT, 0, st>>>(cnt, nb1, at<long long>(workspace, l.bsum), start);
-    OGG_LAUNCH_CHECK();
+    const long nb1 = nb + 1;
+    if (int e = exclusive_scan<false>(cnt, nb1, at<long long>(workspace, l.bsum), &at<Head>(workspace, 0)->total, start, st)) return e;
     OGG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)nb1 * 4, st));   // the cursors of the fill
     double* bu = at<double>(workspace, l.bu);
     int* bc = at<int>(workspace, l.bc);
-    bin_fill_kernel<<<grid_for(n_targets, 4096), NT, 0, st>>>(tgt_u, tgt_cell, n_targets, bin, start, cnt, bu, bc);
+    bin_fill_kernel<<<grid_for<NT>(n_targets, 4096), NT, 0, st>>>(tgt_u, tgt_cell, n_targets, bin, start, cnt, bu, bc);
     OGG_LAUNCH_CHECK();
     const Index ix{(int)G, 2.0 / (double)G, start, bu, bc};
-    search_kernel<<<grid_for(n_mapped, 1L << 20), NT, 0, st>>>(ix, src_u, n_mapped, src_target, src_d2, counts);
+    search_kernel<<<grid_for<NT>(n_mapped, 1L << 20), NT, 0, st>>>(ix, src_u, n_mapped, src_target, src_d2, counts);
     OGG_LAUNCH_CHECK();
     return OGG_OK;
 }
@@ -758,10 +626,10 @@ extern "C" int ogg_runoff_segments_dev(const ogg_runoff_params* p, const int* sr
     OGG_LAUNCH_CHECK();
     int k = 0;
     for (long w = NT; w < n_mapped; w *= 2, ++k) {
-        keysort_merge_kernel<<<grid_for(n_mapped, 1L << 20), NT, 0, st>>>(buf[k & 1], n_mapped, w, buf[(k + 1) & 1]);
+        keysort_merge_kernel<<<grid_for<NT>(n_mapped, 1L << 20), NT, 0, st>>>(buf[k & 1], n_mapped, w, buf[(k + 1) & 1]);
         OGG_LAUNCH_CHECK();
     }
-    seg_kernel<<<grid_for(n_mapped, 1L << 20), NT, 0, st>>>(buf[k & 1], n_mapped, ncell_of(*p), seg);
+    seg_kernel<<<grid_for<NT>(n_mapped, 1L << 20), NT, 0, st>>>(buf[k & 1], n_mapped, ncell_of(*p), seg);
     OGG_LAUNCH_CHECK();
     return OGG_OK;
 }
@@ -800,20 +668,7 @@ extern "C" int ogg_runoff(const ogg_runoff_params* p, const double* x, const dou
     if (int e = check_params(p)) return e;
     OGG_REQUIRE(x && y && area && wet && f && lon && lat && values && n_sources && src_cell && src_target && src_d2 && counts, OGG_EARG,
                 "ogg_runoff: null argument");
-    struct Buffers {   // freed on every exit path
-        std::vector<void*> p;
-        ~Buffers() {
-            for (void* q : p) (void)hipFree(q);
-        }
-        int alloc(void** out, size_t bytes) {
-            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
-            if (e != hipSuccess)
-                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
-                                      hipGetErrorString(e));
-            p.push_back(*out);
-            return OGG_OK;
-        }
-    } bufs;
+    ogg::Buffers bufs;   // freed on every exit path
     const size_t nc = (size_t)ncell_of(*p), ns = (size_t)nsrc_of(*p), npt = (size_t)(2 * p->ny + 1) * (2 * p->nx + 1);
     const size_t fbytes = (size_t)p->nrec * ns * (p->dtype == OGG_REMAP_FLOAT32 ? 4 : 8);
     const long wsb = layout(*p).total;

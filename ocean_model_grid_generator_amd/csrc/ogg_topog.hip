@@ -393,20 +393,7 @@ extern "C" int ogg_topog(const ogg_topog_band* band, const ogg_topog_source* src
     OGG_REQUIRE(h.x && h.y, OGG_EARG, "ogg_topog: null x / y");
     const long rows = out_rows(h);
     if (rows == 0) return OGG_OK;
-    struct Buffers {   // freed on every exit path
-        std::vector<void*> p;
-        ~Buffers() {
-            for (void* q : p) (void)hipFree(q);
-        }
-        int alloc(void** out, size_t bytes) {
-            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
-            if (e != hipSuccess)
-                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
-                                      hipGetErrorString(e));
-            p.push_back(*out);
-            return OGG_OK;
-        }
-    } bufs;
+    ogg::Buffers bufs;   // freed on every exit path
     const long nxp = h.nx + 1, n = h.n_cell_rows;
     ogg_topog_band d = h;
     void *px = nullptr, *py = nullptr;

@@ -541,20 +541,7 @@ extern "C" int ogg_xgrid(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, l
     *counts = ogg_xgrid_counts{};
     if (rows == 0) return OGG_OK;
     OGG_REQUIRE(h.x && h.y && a_poly, OGG_EARG, "ogg_xgrid: null x / y / a_poly");
-    struct Buffers {   // freed on every exit path
-        std::vector<void*> p;
-        ~Buffers() {
-            for (void* q : p) (void)hipFree(q);
-        }
-        int alloc(void** out, size_t bytes) {
-            hipError_t e = hipMalloc(out, bytes ? bytes : 8);
-            if (e != hipSuccess)
-                return ogg::set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes,
-                                      hipGetErrorString(e));
-            p.push_back(*out);
-            return OGG_OK;
-        }
-    } bufs;
+    ogg::Buffers bufs;   // freed on every exit path
     const long nxp = h.nx + 1, n = h.n_cell_rows, nn = next_rows(h);
     const size_t body = (size_t)n * nxp * sizeof(double), tail = (size_t)nn * nxp * sizeof(double);
     void *px = nullptr, *py = nullptr, *pm = nullptr, *pa = nullptr, *pb = nullptr, *ws = nullptr, *ap = nullptr, *ct = nullptr;

@@ -158,6 +158,23 @@ def band_lists_dev(band, atm_desc, stream, device):
     return m0, counts, a_poly, atm, ocn, area
 
 
+def whole_grid_lists_dev(x, y, lon, lat, mask, Re, threshold, stream, device):
+    """band_lists_dev of the whole stitched grid as one band: x, y float64 device tensors ((ny + 1) x (nx + 1), contiguous rows), the
+    atmosphere's edges lon, lat and the mask (None or one byte per model cell) as host arrays.  (atm, ocn, area, the mask on the
+    device or None)."""
+    import torch
+    nyp, nxp = x.shape
+    lt, bt = torch.from_numpy(lon).to(device), torch.from_numpy(lat).to(device)
+    desc = L.XgridAtm(lon=lt.data_ptr(), lat=bt.data_ptr(), NA=lon.size - 1, NB=lat.size - 1)
+    band = L.XgridBand(nx=nxp - 1, ny=nyp - 1, j0=0, n_cell_rows=nyp - 1, Re=float(Re), threshold=float(threshold))
+    band.x, band.y = x.data_ptr(), y.data_ptr()
+    band.x_next, band.y_next = x[nyp - 1:].data_ptr(), y[nyp - 1:].data_ptr()
+    mt = None if mask is None else torch.from_numpy(mask).to(device)
+    band.mask = None if mt is None else mt.data_ptr()
+    _, _, _, atm, ocn, area = band_lists_dev(band, desc, stream, device)
+    return atm, ocn, area, mt
+
+
 def assemble(pieces, shape, lon, lat, Re, threshold, masked):
     """The result of the whole grid from [(first model row, counts, a_poly, atm, ocn, area)] as host arrays, in piece order."""
     a_poly = np.full(shape, np.nan)

@@ -16,52 +16,22 @@ model cells (ny, nx); every dimension ahead of them is a record dimension.
 """
 import argparse
 import ctypes
-import json
 import sys
 
 import numpy as np
 
 from . import _lib as L
 from . import exchange_grid as X
+from . import fields as F
 from . import netcdf3
 
 FILL = L.REMAP_FILL
 NORMALIZE = {"area": L.REGRID_AREA, "cell": L.REGRID_CELL}
-_DTYPES = {np.dtype(np.float32): L.REMAP_FLOAT32, np.dtype(np.float64): L.REMAP_FLOAT64}
+_DTYPES = F.DTYPES
 
 
 # ---- fields --------------------------------------------------------------------------------------------------
-class Field(object):
-    """A field on the model cells: data (..., ny, nx), float32 or float64; the values that mark missing (``fill``, at most two, in the
-    data's type; NaN is always missing); the leading dimensions [(name, length)] and their coordinate variables [(name, nc type,
-    attributes, values)] for the writer; ``record_dim`` the unlimited dimension of the file it came from (None: none)."""
-
-    def __init__(self, data, fill=(), name="field", lead_dims=None, coords=(), atts=(), note="", record_dim=None):
-        data = np.asarray(data)
-        if data.ndim < 2 or data.dtype.newbyteorder("=") not in _DTYPES:
-            raise ValueError("regrid field: a float32 or float64 array of two or more dimensions is needed, not %s %s" % (data.dtype, data.shape))
-        self.data = np.ascontiguousarray(data, dtype=data.dtype.newbyteorder("="))
-        self.fill = tuple(self.data.dtype.type(f) for f in fill)
-        if len(self.fill) > L.REMAP_MAX_FILLS:
-            raise ValueError("regrid field: at most %d fill values" % L.REMAP_MAX_FILLS)
-        self.name = name
-        lead = self.data.shape[:-2]
-        self.lead_dims = list(lead_dims) if lead_dims is not None else [("record%d" % k, n) for k, n in enumerate(lead)]
-        self.coords, self.atts, self.note, self.record_dim = list(coords), list(atts), note, record_dim
-
-    @property
-    def nrec(self):
-        return int(np.prod(self.data.shape[:-2], dtype=np.int64))
-
-    @property
-    def records(self):
-        """the data as (nrec, ny, nx)"""
-        return self.data.reshape((self.nrec,) + self.data.shape[-2:])
-
-
-def _num(atts, key):
-    v = atts.get(key)
-    return None if v is None or isinstance(v, str) else float(np.asarray(v).reshape(-1)[0])
+Field = F.Field   # a field on the model cells: data (..., ny, nx)
 
 
 def read_field(path, var, shape):
@@ -70,49 +40,10 @@ def read_field(path, var, shape):
     them is a record dimension, the unlimited one included.  A byte or short variable is unpacked to float64 as raw * scale_factor +
     add_offset, with missing values (_FillValue, missing_value, tested on the raw values) as NaN; float and double keep their type and
     their fill values.  CDF-5 and NetCDF-4 / HDF5 files are refused."""
-    from . import topography as T
-    try:
-        h = netcdf3.read_header(path)
-    except ValueError as e:
-        if "CDF-5" in str(e) or "HDF5" in str(e):
-            raise ValueError("%s: only NetCDF classic / 64-bit-offset fields are read; %s" % (str(e).split(";")[0], T._NCCOPY))
-        raise
-    if var not in h.vars:
-        raise KeyError("%s: no variable %r (variables: %s); choose one with --var" % (path, var, ", ".join(sorted(h.vars))))
-    v = h.vars[var]
-    if v.nc_type not in (netcdf3.NC_BYTE, netcdf3.NC_SHORT, netcdf3.NC_FLOAT, netcdf3.NC_DOUBLE) or len(v.shape) < 2:
-        raise ValueError("%s: %s must be a byte, short, float or double variable of two or more dimensions (type %d, shape %s)"
-                         % (path, var, v.nc_type, v.shape))
+    h, v = F.open_variable(path, var, "fields")
     if tuple(v.shape[-2:]) != tuple(shape):
         raise ValueError("%s: %s ends in %s, the grid has %d x %d model cells (ny, nx)" % (path, var, tuple(v.shape[-2:]), shape[0], shape[1]))
-
-    def raw_bytes(name, u):
-        return (netcdf3.read_record_var_bytes if u.is_record else netcdf3.read_var_bytes)(path, h, name, dtype=u.nc_type)
-    data = np.frombuffer(raw_bytes(var, v), dtype=netcdf3.NUMPY_DTYPE[v.nc_type]).reshape(v.shape)
-    data = data.astype(data.dtype.newbyteorder("="))
-    fills = []
-    for k in ("_FillValue", "missing_value"):
-        fv = _num(v.atts, k)
-        if fv is not None and fv not in fills:
-            fills.append(fv)
-    if v.nc_type in (netcdf3.NC_BYTE, netcdf3.NC_SHORT):
-        scale, offset = _num(v.atts, "scale_factor"), _num(v.atts, "add_offset")
-        miss = np.zeros(data.shape, dtype=bool)
-        for fv in fills:
-            miss |= data == data.dtype.type(fv)
-        out = data.astype(np.float64) * (1.0 if scale is None else scale) + (0.0 if offset is None else offset)
-        out[miss] = np.nan
-        data, fills = out, []
-    lead = [(d, n) for d, n in zip(v.dims[:-2], v.shape[:-2])]
-    coords = []
-    for d, _ in lead:
-        cv = h.vars.get(d)
-        if cv is not None and len(cv.shape) == 1 and cv.nc_type != netcdf3.NC_CHAR:
-            vals = np.frombuffer(raw_bytes(d, cv), dtype=netcdf3.NUMPY_DTYPE[cv.nc_type])
-            atts = [(k, a if isinstance(a, str) else np.asarray(a).reshape(-1)[0].item()) for k, a in cv.atts.items()
-                    if isinstance(a, str) or np.asarray(a).size == 1]
-            coords.append((d, cv.nc_type, atts, vals))
-    keep = [(k, a) for k, a in v.atts.items() if k in ("units", "long_name") and isinstance(a, str)]
+    data, fills, lead, coords, keep = F.read_values(path, h, v)
     note = "%s: %s %s, %d records of %d x %d model cells" % (path, var, tuple(v.dims), int(np.prod(v.shape[:-2], dtype=np.int64)),
                                                             shape[0], shape[1])
     return Field(data, fill=fills, name=var, lead_dims=lead, coords=coords, atts=keep, note=note,
@@ -134,15 +65,6 @@ def params(shape, lon, lat, field=None, normalize="area"):
     if L.load().ogg_regrid_check(ctypes.byref(p)) != L.OGG_OK:
         raise ValueError(L.load().ogg_last_error().decode())
     return p
-
-
-def _mask(mask, shape):
-    if mask is None:
-        return None
-    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-    if m.shape != shape:
-        raise ValueError("regrid: the mask is %s, the model cells %s" % (m.shape, shape))
-    return m
 
 
 def counts_dict(c):
@@ -279,16 +201,9 @@ def regrid_to_latlon_dev(x, y, field, lon_edges, lat_edges, mask=None, normalize
     if field is not None and not isinstance(field, Field):
         field = Field(field, fill=fill_values)
     p = params(shape, lon, lat, field, normalize)
-    m = _mask(mask, shape)
+    m = F.cell_mask(mask, shape, "regrid: the mask")
     st = torch.cuda.current_stream(dev).cuda_stream
-    lt, bt = torch.from_numpy(lon).to(dev), torch.from_numpy(lat).to(dev)
-    desc = L.XgridAtm(lon=lt.data_ptr(), lat=bt.data_ptr(), NA=lon.size - 1, NB=lat.size - 1)
-    band = L.XgridBand(nx=nxp - 1, ny=nyp - 1, j0=0, n_cell_rows=nyp - 1, Re=float(Re), threshold=float(threshold))
-    band.x, band.y = x.data_ptr(), y.data_ptr()
-    band.x_next, band.y_next = x[nyp - 1:].data_ptr(), y[nyp - 1:].data_ptr()
-    mt = None if m is None else torch.from_numpy(m).to(dev)
-    band.mask = None if mt is None else mt.data_ptr()
-    _, _, _, atm, ocn, area = X.band_lists_dev(band, desc, st, dev)
+    atm, ocn, area, _ = X.whole_grid_lists_dev(x, y, lon, lat, m, Re, threshold, st, dev)
     return finish_dev(p, atm, ocn, area, field, lon, lat, np.ascontiguousarray(X.atm_area(lon, lat, Re)), normalize, cover, m is not None,
                       shape, st, dev)
 
@@ -310,31 +225,8 @@ def write_regridded(path, results, title="conservative regrid of model-cell fiel
     <var>_cover when the result holds a cover, the cell centres, bounds and areas, ocean_frac and n_entries, the leading coordinate
     variables copied from the field (the record dimension kept unlimited), as a NetCDF 64-bit-offset file.  ``results``: [(Field,
     regrid_to_latlon() result)], all on one target grid."""
-    from . import remap as R
-    dims, coords, seen, record_dim = [], [], set(), None
-    for fld, res in results:
-        rd = fld.record_dim
-        if rd is not None:
-            if record_dim not in (None, rd):
-                raise ValueError("regrid: two record dimensions, %s and %s" % (record_dim, rd))
-            record_dim = rd
-        for d, n in fld.lead_dims:
-            if d in seen:
-                if dict(dims)[d] != n:
-                    raise ValueError("regrid: dimension %s has length %d in one variable and %d in another" % (d, dict(dims)[d], n))
-                continue
-            seen.add(d)
-            dims.append((d, n))
-            coords += [c for c in fld.coords if c[0] == d]
-        nbytes = int(np.prod(res["values"].shape[1 if rd else 0:], dtype=np.int64)) * 8
-        if nbytes > R.CDF2_VAR_LIMIT:
-            raise ValueError("regrid: %s takes %d bytes, more than one variable of a NetCDF 64-bit-offset file can hold (%d); regrid "
-                             "fewer records at a time" % (fld.name, nbytes, R.CDF2_VAR_LIMIT))
-    for fld, _ in results:
-        if record_dim is not None and record_dim in dict(fld.lead_dims) and fld.lead_dims[0][0] != record_dim:
-            raise ValueError("regrid: %s has the record dimension %s but not first" % (fld.name, record_dim))
-    if record_dim is not None:   # the record dimension first, as the format wants it
-        dims.sort(key=lambda d: d[0] != record_dim)
+    dims, coords, record_dim = F.writer_dims("regrid", [(fld, [(fld.name, res["values"])]) for fld, res in results],
+                                             "; regrid fewer records at a time", record_dims=True)
     res0 = results[0][1]
     NB, NA = res0["cell_area"].shape
     dims += [("lat", NB), ("lon", NA), ("bnds", 2)]
@@ -401,19 +293,9 @@ def main(argv=None):
     shape = ((grid["x"].shape[0] - 1) // 2, (grid["x"].shape[1] - 1) // 2)
     mask = R.mask_from_file(a.topog or a.mask) if (a.topog or a.mask) else None
     lon, lat = X.regular_atm(*a.atm)
-    out = []
-    for var in a.var:
-        fld = read_field(a.fields, var, shape)
-        print(fld.note)
-        res = regrid_to_latlon(grid["x"], grid["y"], fld, lon, lat, mask=mask, normalize=a.normalize, cover=a.cover)
-        for line in summary_lines(res):
-            print(line)
-        out.append((fld, res))
-    write_regridded(a.output, out)
-    if a.json:
-        with open(a.json, "w") as fh:
-            json.dump([r["summary"] for _, r in out], fh, indent=1)
-    return out
+    return F.run_variables(a.var, lambda var: read_field(a.fields, var, shape),
+                           lambda fld: regrid_to_latlon(grid["x"], grid["y"], fld, lon, lat, mask=mask, normalize=a.normalize, cover=a.cover),
+                           summary_lines, write_regridded, a.output, a.json)
 
 
 if __name__ == "__main__":

@@ -60,6 +60,13 @@ def topology_of_edges(first, last, top):
     return periodic, fold
 
 
+def topology_of_device_grid(x, y, stride=2):
+    """detect_topology of a supergrid held as device tensors: only the corner columns and the top row are copied to the host"""
+    xs, ys = x[::stride, ::stride], y[::stride, ::stride]
+    return topology_of_edges(*[(xs[sl].cpu().numpy(), ys[sl].cpu().numpy())
+                               for sl in ((slice(None), 0), (slice(None), -1), (-1, slice(None)))])
+
+
 def topology_flags(periodic, fold):
     return (L.MASK_PERIODIC if periodic else 0) | (L.MASK_FOLD if fold else 0)
 
@@ -180,9 +187,7 @@ def ocean_mask_dev(depth, x, y, min_depth=0.0, mode="mask", seeds=(), keep_min_c
     s = _seeds(seeds)
     if s.shape[0] and stride != 2:
         raise ValueError("ocean mask: seeds need model cells (a seed picks the cell whose centre, supergrid point (2j+1, 2i+1), is nearest)")
-    xs, ys = x[::stride, ::stride], y[::stride, ::stride]   # (views: only the corner columns and the top row are copied)
-    periodic, fold = topology_of_edges(*[(xs[sl].cpu().numpy(), ys[sl].cpu().numpy())
-                                         for sl in ((slice(None), 0), (slice(None), -1), (-1, slice(None)))])
+    periodic, fold = topology_of_device_grid(x, y, stride)
     p = params(ny, nx, periodic, fold, min_depth, mode, keep_min_cells, fill)
     st = torch.cuda.current_stream(dev).cuda_stream
     lib = L.load()

@@ -15,61 +15,36 @@ uniform 1-D coordinates spanning 360 degrees of longitude; every dimension ahead
 """
 import argparse
 import ctypes
-import json
 import sys
 
 import numpy as np
 
 from . import _lib as L
 from . import exchange_grid as X
+from . import fields as F
 from . import netcdf3
 
 FILL = L.REMAP_FILL
 FLAG_NAMES = ("dry", "remapped", "filled", "unfilled")
-CDF2_VAR_LIMIT = (1 << 32) - 4      # bytes of one fixed-size variable of a 64-bit-offset file
-_DTYPES = {np.dtype(np.float32): L.REMAP_FLOAT32, np.dtype(np.float64): L.REMAP_FLOAT64}
+CDF2_VAR_LIMIT = F.CDF2_VAR_LIMIT
+_DTYPES = F.DTYPES
 
 
 # ---- sources -------------------------------------------------------------------------------------------------
-class Source(object):
-    """A field on a global rectilinear grid: data (..., NB, NA), float32 or float64, row 0 southmost; its cell edges lon (NA + 1,
-    spanning 360 degrees) and lat (NB + 1, increasing, inside [-90, 90]); the values that mark missing (``fill``, at most two, in
-    the data's type; NaN is always missing); the leading dimensions [(name, length)] and their coordinate variables [(name, nc type,
-    attributes, values)] for the writer; ``note`` says how the grid was read."""
+class Source(F.Field):
+    """A field on a global rectilinear grid: a fields.Field with data (..., NB, NA), row 0 southmost, and its cell edges lon (NA + 1,
+    spanning 360 degrees) and lat (NB + 1, increasing, inside [-90, 90])."""
+    _who = "remap source"
 
-    def __init__(self, data, lon_edges, lat_edges, fill=(), name="field", lead_dims=None, coords=(), atts=(), note=""):
-        data = np.asarray(data)
-        if data.ndim < 2 or data.dtype.newbyteorder("=") not in _DTYPES:
-            raise ValueError("remap source: a float32 or float64 array of two or more dimensions is needed, not %s %s" % (data.dtype, data.shape))
-        self.data = np.ascontiguousarray(data, dtype=data.dtype.newbyteorder("="))
+    def __init__(self, data, lon_edges, lat_edges, fill=(), name="field", lead_dims=None, coords=(), atts=(), note="", record_dim=None):
+        F.Field.__init__(self, data, fill, name, lead_dims, coords, atts, note, record_dim)
         self.lon, self.lat = X.atm_edges(lon_edges, lat_edges)
         if self.data.shape[-2:] != (self.lat.size - 1, self.lon.size - 1):
             raise ValueError("remap source: data %s and %d x %d cells (lat x lon edges - 1)" % (self.data.shape, self.lat.size - 1, self.lon.size - 1))
-        self.fill = tuple(self.data.dtype.type(f) for f in fill)
-        if len(self.fill) > L.REMAP_MAX_FILLS:
-            raise ValueError("remap source: at most %d fill values" % L.REMAP_MAX_FILLS)
-        self.name = name
-        lead = self.data.shape[:-2]
-        self.lead_dims = list(lead_dims) if lead_dims is not None else [("record%d" % k, n) for k, n in enumerate(lead)]
-        self.coords, self.atts, self.note = list(coords), list(atts), note
-
-    @property
-    def nrec(self):
-        return int(np.prod(self.data.shape[:-2], dtype=np.int64))
-
-    @property
-    def records(self):
-        """the data as (nrec, NB, NA)"""
-        return self.data.reshape((self.nrec,) + self.data.shape[-2:])
-
-
-def _num(atts, key):
-    v = atts.get(key)
-    return None if v is None or isinstance(v, str) else float(np.asarray(v).reshape(-1)[0])
 
 
 class _Last2(object):
-    """the last two dimensions of a variable, as topography's dimension helper reads them"""
+    """the last two dimensions of a variable, as fields.lat_lon_dims reads them"""
 
     def __init__(self, v):
         self.name, self.dims = v.name, v.dims[-2:]
@@ -88,34 +63,16 @@ def _read_source(path, var, records=False):
     with missing values (_FillValue, missing_value, tested on the raw values) as NaN; float and double keep their type and their fill
     values.  CDF-5 and NetCDF-4 / HDF5 files are refused.  ``records`` (opt-in): a record (unlimited) variable is read too, its
     record dimension the first leading dimension (the Source's ``record_dim``), and so is the coordinate variable of that dimension."""
-    from . import topography as T
-    try:
-        h = netcdf3.read_header(path)
-    except ValueError as e:
-        if "CDF-5" in str(e) or "HDF5" in str(e):
-            raise ValueError("%s: only NetCDF classic / 64-bit-offset sources are read; %s" % (str(e).split(";")[0], T._NCCOPY))
-        raise
-    if var not in h.vars:
-        raise KeyError("%s: no variable %r (variables: %s); choose one with --var" % (path, var, ", ".join(sorted(h.vars))))
-    v = h.vars[var]
-    if v.nc_type not in (netcdf3.NC_BYTE, netcdf3.NC_SHORT, netcdf3.NC_FLOAT, netcdf3.NC_DOUBLE) or len(v.shape) < 2:
-        raise ValueError("%s: %s must be a byte, short, float or double variable of two or more dimensions (type %d, shape %s)"
-                         % (path, var, v.nc_type, v.shape))
-    if v.is_record and not records:
-        raise ValueError("%s: %s is a record (unlimited) variable; only fixed-size variables are read" % (path, var))
-
-    def raw_bytes(name, u):
-        return (netcdf3.read_record_var_bytes if u.is_record else netcdf3.read_var_bytes)(path, h, name, dtype=u.nc_type)
-    lat_name, lon_name = T._lat_lon_dims(path, h, _Last2(v))
+    h, v = F.open_variable(path, var, "sources", records)
+    lat_name, lon_name = F.lat_lon_dims(path, h, _Last2(v))
     axes = {}
     for dname in (lat_name, lon_name):
         if dname not in h.vars:
             raise ValueError("%s: no coordinate variable for dimension %s of %s" % (path, dname, var))
         cv = h.vars[dname]
         raw = netcdf3.read_var_bytes(path, h, dname, dtype=cv.nc_type)
-        axes[dname] = T._uniform_axis(path, dname, np.frombuffer(raw, dtype=netcdf3.NUMPY_DTYPE[cv.nc_type]))
-    data = np.frombuffer(raw_bytes(var, v), dtype=netcdf3.NUMPY_DTYPE[v.nc_type]).reshape(v.shape)
-    data = data.astype(data.dtype.newbyteorder("="))
+        axes[dname] = F.uniform_axis(path, dname, np.frombuffer(raw, dtype=netcdf3.NUMPY_DTYPE[cv.nc_type]))
+    data, fills, lead, coords, keep = F.read_values(path, h, v, records, keep=("units", "long_name", "standard_name"))
     if v.dims[-2] == lon_name:   # stored (..., lon, lat)
         data = np.swapaxes(data, -1, -2)
     (lat, dlat), (lon, dlon) = axes[lat_name], axes[lon_name]
@@ -127,45 +84,21 @@ def _read_source(path, var, records=False):
     if abs(NA * dlon - 360.0) > 1e-9 * 360.0:
         raise ValueError("%s: %s covers %.10g degrees of longitude (%d x %.10g); the remap needs a global source (360 degrees)"
                          % (path, var, NA * dlon, NA, dlon))
-    lon0, kind_lon = T._edges(lon[0], dlon)
+    lon0, kind_lon = F.axis_edges(lon[0], dlon)
     if min(abs(lat[0] - 0.5 * dlat + 90.0), abs(lat[-1] + 0.5 * dlat - 90.0)) <= 1e-6 * dlat:
         lat0, kind_lat = lat[0] - 0.5 * dlat, "centres"   # centres whose half-step edges reach a pole
     else:
-        lat0, kind_lat = T._edges(lat[0], dlat)
+        lat0, kind_lat = F.axis_edges(lat[0], dlat)
     lon_edges = lon0 + dlon * np.arange(NA + 1)
     lon_edges[-1] = lon_edges[0] + 360.0
     lat_edges = np.clip(lat0 + dlat * np.arange(NB + 1), -90.0, 90.0)
     for k, pole in ((0, -90.0), (NB, 90.0)):   # an edge within rounding of a pole is the pole
         if abs(lat_edges[k] - pole) <= 1e-6 * dlat:
             lat_edges[k] = pole
-    fills = []
-    for k in ("_FillValue", "missing_value"):
-        fv = _num(v.atts, k)
-        if fv is not None and fv not in fills:
-            fills.append(fv)
-    if v.nc_type in (netcdf3.NC_BYTE, netcdf3.NC_SHORT):
-        scale, offset = _num(v.atts, "scale_factor"), _num(v.atts, "add_offset")
-        miss = np.zeros(data.shape, dtype=bool)
-        for fv in fills:
-            miss |= data == data.dtype.type(fv)
-        out = data.astype(np.float64) * (1.0 if scale is None else scale) + (0.0 if offset is None else offset)
-        out[miss] = np.nan
-        data, fills = out, []
-    lead = [(d, n) for d, n in zip(v.dims[:-2], v.shape[:-2])]
-    coords = []
-    for d, _ in lead:
-        cv = h.vars.get(d)
-        if cv is not None and len(cv.shape) == 1 and (records or not cv.is_record) and cv.nc_type != netcdf3.NC_CHAR:
-            vals = np.frombuffer(raw_bytes(d, cv), dtype=netcdf3.NUMPY_DTYPE[cv.nc_type])
-            atts = [(k, a if isinstance(a, str) else np.asarray(a).reshape(-1)[0].item()) for k, a in cv.atts.items()
-                    if isinstance(a, str) or np.asarray(a).size == 1]
-            coords.append((d, cv.nc_type, atts, vals))
-    keep = [(k, a) for k, a in v.atts.items() if k in ("units", "long_name", "standard_name") and isinstance(a, str)]
     note = "%s: %s %s, %d records of %d x %d cells, longitude coordinates taken as cell %s, latitude as cell %s" % (
         path, var, tuple(v.dims), int(np.prod(v.shape[:-2], dtype=np.int64)), NB, NA, kind_lon, kind_lat)
-    src = Source(data, lon_edges, lat_edges, fill=fills, name=var, lead_dims=lead, coords=coords, atts=keep, note=note)
-    src.record_dim = v.dims[0] if v.is_record else None
-    return src
+    return Source(data, lon_edges, lat_edges, fill=fills, name=var, lead_dims=lead, coords=coords, atts=keep, note=note,
+                  record_dim=v.dims[0] if v.is_record else None)
 
 
 # ---- arguments -----------------------------------------------------------------------------------------------
@@ -182,15 +115,6 @@ def params(ny, nx, source, m0=0, periodic=False, fold=False, fill_max=None):
     if L.load().ogg_remap_check(ctypes.byref(p)) != L.OGG_OK:
         raise ValueError(L.load().ogg_last_error().decode())
     return p
-
-
-def _mask(mask, shape):
-    if mask is None:
-        return None
-    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-    if m.shape != shape:
-        raise ValueError("remap: the mask is %s, the model cells %s" % (m.shape, shape))
-    return m
 
 
 def counts_dict(c):
@@ -224,7 +148,7 @@ def remap(x, y, source, lon_edges=None, lat_edges=None, mask=None, fill=True, fi
     x, y = L.as_f64(x), L.as_f64(y)
     lists = X.exchange_grid(x, y, source.lon, source.lat, mask=mask, Re=Re, threshold=threshold)
     shape = lists["a_poly"].shape
-    m = _mask(mask, shape)
+    m = F.cell_mask(mask, shape, "remap: the mask")
     periodic, fold = M.detect_topology(x, y, 2)
     p = params(shape[0], shape[1], source, 0, periodic, fold, fill_max)
     npair = source.nrec * shape[0] * shape[1]
@@ -282,20 +206,11 @@ def remap_dev(x, y, source, mask=None, fill=True, fill_max=None, threshold=X.DEF
     nyp, nxp = x.shape
     X.check_grid(nyp, nxp)
     shape = ((nyp - 1) // 2, (nxp - 1) // 2)
-    m = _mask(mask, shape)
-    xs, ys = x[::2, ::2], y[::2, ::2]
-    periodic, fold = M.topology_of_edges(*[(xs[sl].cpu().numpy(), ys[sl].cpu().numpy())
-                                          for sl in ((slice(None), 0), (slice(None), -1), (-1, slice(None)))])
+    m = F.cell_mask(mask, shape, "remap: the mask")
+    periodic, fold = M.topology_of_device_grid(x, y)
     p = params(shape[0], shape[1], source, 0, periodic, fold, fill_max)
     st = torch.cuda.current_stream(dev).cuda_stream
-    lon, lat = torch.from_numpy(source.lon).to(dev), torch.from_numpy(source.lat).to(dev)
-    desc = L.XgridAtm(lon=lon.data_ptr(), lat=lat.data_ptr(), NA=lon.numel() - 1, NB=lat.numel() - 1)
-    band = L.XgridBand(nx=nxp - 1, ny=nyp - 1, j0=0, n_cell_rows=nyp - 1, Re=float(Re), threshold=float(threshold))
-    band.x, band.y = x.data_ptr(), y.data_ptr()
-    band.x_next, band.y_next = x[nyp - 1:].data_ptr(), y[nyp - 1:].data_ptr()
-    mt = None if m is None else torch.from_numpy(m).to(dev)
-    band.mask = None if mt is None else mt.data_ptr()
-    _, _, _, atm, ocn, area = X.band_lists_dev(band, desc, st, dev)
+    atm, ocn, area, mt = X.whole_grid_lists_dev(x, y, source.lon, source.lat, m, Re, threshold, st, dev)
     f = torch.from_numpy(source.records).to(dev)
     values, flags, counts = piece_dev(p, f, atm, ocn, area, mt, st, dev)
     if fill:
@@ -309,20 +224,8 @@ def write_remapped(path, results, title="conservative remap onto the model cells
     """One float64 variable per remapped field (its source's leading dimensions, then ny, nx; _FillValue FILL) and a byte variable
     <var>_remap_flag (0 dry, 1 remapped, 2 filled, 3 unfilled), the leading coordinate variables copied from the source, as a
     NetCDF 64-bit-offset file.  ``results``: [(Source, remap() result)]."""
-    dims, coords, seen = [], [], set()
-    for src, res in results:
-        for d, n in src.lead_dims:
-            if d in seen:
-                if dict(dims)[d] != n:
-                    raise ValueError("remap: dimension %s has length %d in one variable and %d in another" % (d, dict(dims)[d], n))
-                continue
-            seen.add(d)
-            dims.append((d, n))
-            coords += [c for c in src.coords if c[0] == d]
-        nbytes = int(np.prod(res["values"].shape, dtype=np.int64)) * 8
-        if nbytes > CDF2_VAR_LIMIT:
-            raise ValueError("remap: %s takes %d bytes, more than one variable of a NetCDF 64-bit-offset file can hold (%d); remap "
-                             "fewer records at a time" % (src.name, nbytes, CDF2_VAR_LIMIT))
+    dims, coords, _ = F.writer_dims("remap", [(src, [(src.name, res["values"])]) for src, res in results],
+                                    "; remap fewer records at a time")
     ny, nx = results[0][1]["values"].shape[-2:]
     dims += [("ny", ny), ("nx", nx)]
     ds = netcdf3.Dataset(path, dims, global_atts=[("title", title), ("cells", "MOM6 model (h) cells: 2 x 2 supergrid cells"),
@@ -371,19 +274,9 @@ def main(argv=None):
     a = p.parse_args(argv)
     grid = netcdf3.read_doubles(a.grid, names=("x", "y"))
     mask = mask_from_file(a.topog or a.mask) if (a.topog or a.mask) else None
-    out = []
-    for var in a.var:
-        src = read_source(a.source, var)
-        print(src.note)
-        res = remap(grid["x"], grid["y"], src, mask=mask, fill=not a.no_fill, fill_max=a.fill_max)
-        for line in summary_lines(res):
-            print(line)
-        out.append((src, res))
-    write_remapped(a.output, out)
-    if a.json:
-        with open(a.json, "w") as fh:
-            json.dump([r["summary"] for _, r in out], fh, indent=1)
-    return out
+    return F.run_variables(a.var, lambda var: read_source(a.source, var),
+                           lambda src: remap(grid["x"], grid["y"], src, mask=mask, fill=not a.no_fill, fill_max=a.fill_max),
+                           summary_lines, write_remapped, a.output, a.json)
 
 
 if __name__ == "__main__":

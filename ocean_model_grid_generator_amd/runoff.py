@@ -15,7 +15,6 @@ SOURCE is a NetCDF classic / 64-bit-offset file read as remap.py reads its sourc
 """
 import argparse
 import ctypes
-import json
 import math
 import sys
 
@@ -23,6 +22,7 @@ import numpy as np
 
 from . import _lib as L
 from . import exchange_grid as X
+from . import fields as F
 from . import netcdf3
 from . import remap as R
 
@@ -55,10 +55,7 @@ def params(ny, nx, source, targets="coast", periodic=False, fold=False, Re=X.DEF
 def _wet(wet, shape):
     if wet is None:
         raise ValueError("runoff: a wet mask is needed (depth > 0 of a topography or mask != 0 of an ocean mask)")
-    m = np.ascontiguousarray(np.asarray(wet) != 0, dtype=np.uint8)
-    if m.shape != shape:
-        raise ValueError("runoff: the wet mask is %s, the model cells %s" % (m.shape, shape))
-    return m
+    return F.cell_mask(wet, shape, "runoff: the wet mask")
 
 
 def cell_area(area):
@@ -168,9 +165,7 @@ def runoff_dev(x, y, area, source, wet, targets="coast", Re=X.DEFAULT_RE, keep_l
     if tuple(area.shape) != (nyp - 1, nxp - 1):
         raise ValueError("runoff: area %s for a supergrid of %s points" % (tuple(area.shape), tuple(x.shape)))
     m = _wet(wet.cpu().numpy() if hasattr(wet, "cpu") else wet, shape)
-    xs, ys = x[::2, ::2], y[::2, ::2]
-    periodic, fold = M.topology_of_edges(*[(xs[sl].cpu().numpy(), ys[sl].cpu().numpy())
-                                          for sl in ((slice(None), 0), (slice(None), -1), (-1, slice(None)))])
+    periodic, fold = M.topology_of_device_grid(x, y)
     p = params(shape[0], shape[1], source, targets, periodic, fold, Re)
     st = torch.cuda.current_stream(dev).cuda_stream
     lib = L.load()
@@ -215,30 +210,7 @@ def write_runoff(path, results, title="runoff mapped onto the nearest coastal mo
     variables copied from the source (the first leading dimension written as the record dimension when the source's was), the cell
     area (m2) and n_sources (int, the number of source cells mapped to each cell), as a NetCDF 64-bit-offset file.  ``results``:
     [(Source, runoff() result)]."""
-    dims, coords, seen, record_dim = [], [], set(), None
-    for src, res in results:
-        rd = getattr(src, "record_dim", None)
-        if rd is not None:
-            if record_dim not in (None, rd):
-                raise ValueError("runoff: two record dimensions, %s and %s" % (record_dim, rd))
-            record_dim = rd
-        for d, n in src.lead_dims:
-            if d in seen:
-                if dict(dims)[d] != n:
-                    raise ValueError("runoff: dimension %s has length %d in one variable and %d in another" % (d, dict(dims)[d], n))
-                continue
-            seen.add(d)
-            dims.append((d, n))
-            coords += [c for c in src.coords if c[0] == d]
-        nbytes = int(np.prod(res["values"].shape[1 if rd else 0:], dtype=np.int64)) * 8
-        if nbytes > R.CDF2_VAR_LIMIT:
-            raise ValueError("runoff: %s takes %d bytes, more than one variable of a NetCDF 64-bit-offset file can hold (%d)"
-                             % (src.name, nbytes, R.CDF2_VAR_LIMIT))
-    for src, _ in results:
-        if record_dim is not None and record_dim in dict(src.lead_dims) and src.lead_dims[0][0] != record_dim:
-            raise ValueError("runoff: %s has the record dimension %s but not first" % (src.name, record_dim))
-    if record_dim is not None:   # the record dimension first, as the format wants it
-        dims.sort(key=lambda d: d[0] != record_dim)
+    dims, coords, record_dim = F.writer_dims("runoff", [(src, [(src.name, res["values"])]) for src, res in results], record_dims=True)
     ny, nx = results[0][1]["n_sources"].shape
     dims += [("ny", ny), ("nx", nx)]
     ds = netcdf3.Dataset(path, dims, global_atts=[("title", title), ("cells", "MOM6 model (h) cells: 2 x 2 supergrid cells")],
@@ -283,19 +255,9 @@ def main(argv=None):
     a = p.parse_args(argv)
     grid = netcdf3.read_doubles(a.grid, names=("x", "y", "area"))
     wet = R.mask_from_file(a.topog or a.mask)
-    out = []
-    for var in a.var:
-        src = read_source(a.source, var)
-        print(src.note)
-        res = runoff(grid["x"], grid["y"], grid["area"], src, wet, targets=a.targets)
-        for line in summary_lines(res):
-            print(line)
-        out.append((src, res))
-    write_runoff(a.output, out)
-    if a.json:
-        with open(a.json, "w") as fh:
-            json.dump([r["summary"] for _, r in out], fh, indent=1)
-    return out
+    return F.run_variables(a.var, lambda var: read_source(a.source, var),
+                           lambda src: runoff(grid["x"], grid["y"], grid["area"], src, wet, targets=a.targets),
+                           summary_lines, write_runoff, a.output, a.json)
 
 
 if __name__ == "__main__":

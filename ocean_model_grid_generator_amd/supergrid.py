@@ -1514,13 +1514,14 @@ class Supergrid(object):
         counts in piece order (_gather) and fills on its GPU with the topology of the stitched grid, as ocean_mask does.  Nothing is
         summed across pieces, so the result is bit-identical for any number of ranks."""
         from . import exchange_grid as X
+        from . import fields as F
         from . import ocean_mask as M
         from . import remap as R
         torch = self.torch
         nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
         X.check_grid(nyp, nxp)
         shape = ((nyp - 1) // 2, (nxp - 1) // 2)
-        hm = R._mask(mask, shape)
+        hm = F.cell_mask(mask, shape, "remap: the mask")
         R.params(shape[0], shape[1], source, 0, False, False, fill_max)   # the checks, before any device work
         nrec = source.nrec
 
@@ -1551,9 +1552,7 @@ class Supergrid(object):
         flags = R.flags_buffer(torch, values.numel(), self.device).view(values.shape)
         flags.copy_(torch.cat([e[2].to(self.device) for e in got], dim=1))
         counts = torch.stack([e[3].to(self.device) for e in got]).sum(dim=0)
-        xs, ys = xy[0][::2, ::2], xy[1][::2, ::2]
-        periodic, fold = M.topology_of_edges(*[(xs[sl].cpu().numpy(), ys[sl].cpu().numpy())
-                                              for sl in ((slice(None), 0), (slice(None), -1), (-1, slice(None)))])
+        periodic, fold = M.topology_of_device_grid(*xy)
         if fill:
             p = R.params(shape[0], shape[1], source, 0, periodic, fold, fill_max)
             R.fill_dev(p, values, flags, counts, self._stream(), self.device)
@@ -1570,6 +1569,7 @@ class Supergrid(object):
         rank 0's exchange_grid() result for the same atm, mask and threshold, whose list is used instead of building and gathering it
         again (the call then runs on this rank alone)."""
         from . import exchange_grid as X
+        from . import fields as F
         from . import latlon_regrid as G
         torch = self.torch
         nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
@@ -1580,7 +1580,7 @@ class Supergrid(object):
         if field is not None and not isinstance(field, G.Field):
             field = G.Field(field)
         p = G.params(shape, lon, lat, field, normalize)   # the checks, before any device work
-        hm = G._mask(mask, shape)
+        hm = F.cell_mask(mask, shape, "regrid: the mask")
         if lists is not None:
             atm_ij, ocn_ij, area = (torch.from_numpy(np.ascontiguousarray(lists[k])).to(self.device) for k in ("atm", "ocn", "area"))
         else:

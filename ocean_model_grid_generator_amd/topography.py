@@ -20,10 +20,10 @@ import numpy as np
 
 from . import _lib as L
 from . import netcdf3
+from .fields import NCCOPY as _NCCOPY, axis_edges as _edges, lat_lon_dims as _lat_lon_dims, uniform_axis as _uniform_axis
 
 FILL = 1.0e20                 # _FillValue of the floating outputs (cells without a valid sample)
 DEFAULT_QUANTUM = 0.01        # float sources: q = rint(v / quantum)
-_NCCOPY = "convert it with `nccopy -k 64-bit-offset IN OUT`"
 _EMPTY = (0, 0, 0, 0, 0, np.iinfo(np.int32).max, np.iinfo(np.int32).min, 0, 0, 0)   # a record with no sample
 _DTYPES = {np.dtype(np.int16): L.TOPOG_INT16, np.dtype(np.float32): L.TOPOG_FLOAT32, np.dtype(np.float64): L.TOPOG_FLOAT64}
 
@@ -92,51 +92,6 @@ class DeviceSource(object):
             d.dtype, d.n_fill = L.TOPOG_INT32, 0
         d.data = self.tensor.data_ptr()
         self.desc = d
-
-
-def _uniform_axis(path, name, c):
-    c = np.asarray(c, dtype=np.float64).reshape(-1)
-    if c.size < 2:
-        raise ValueError("%s: coordinate %s has %d values; two or more are needed" % (path, name, c.size))
-    step = (c[-1] - c[0]) / (c.size - 1)
-    if step == 0 or np.max(np.abs(np.diff(c) - step)) > 1e-9 * abs(step):
-        raise ValueError("%s: coordinate %s is not uniform within 1e-9 of its step %r" % (path, name, step))
-    return c, step
-
-
-def _edges(c0, step):
-    """(first edge, note): coordinates at half-steps of the lattice k * step are cell centres, any others are taken as edges."""
-    r = c0 / abs(step) - 0.5
-    if abs(r - round(r)) <= 1e-6:
-        return c0 - 0.5 * abs(step), "centres"
-    return c0, "edges"
-
-
-_LAT_NAMES, _LON_NAMES = ("lat", "latitude", "y", "nlat"), ("lon", "longitude", "x", "nlon")
-
-
-def _lat_lon_dims(path, h, v):
-    """(latitude dimension, longitude dimension) of a 2-D variable, from its coordinate variables' units (degrees_north /
-    degrees_east, as CF has them) or, without units, their names; a file where neither decides is refused."""
-    kinds = []
-    for d in v.dims:
-        cv = h.vars.get(d)
-        units = cv.atts.get("units", "") if cv is not None else ""
-        units = units.strip().lower() if isinstance(units, str) else ""
-        if units in ("degrees_north", "degree_north", "degrees_n", "degree_n"):
-            kinds.append("lat")
-        elif units in ("degrees_east", "degree_east", "degrees_e", "degree_e"):
-            kinds.append("lon")
-        elif d.lower() in _LAT_NAMES:
-            kinds.append("lat")
-        elif d.lower() in _LON_NAMES:
-            kinds.append("lon")
-        else:
-            kinds.append(None)
-    if sorted(k for k in kinds if k) != ["lat", "lon"]:
-        raise ValueError("%s: cannot tell the latitude and longitude dimensions of %s%s: give the coordinate variables units "
-                         "degrees_north / degrees_east" % (path, v.name, tuple(v.dims)))
-    return (v.dims[0], v.dims[1]) if kinds[0] == "lat" else (v.dims[1], v.dims[0])
 
 
 def read_source_nc(path, var="elevation", quantum=None):

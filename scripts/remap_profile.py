@@ -76,9 +76,7 @@ def time_case(g, cut, case, reps):
     pieces = g.xgrid_lists(cut, edges, mt, halo=halo)   # piece order: the concatenation is the whole grid's list
     atm, ocn, area = (torch.cat([e[i] for e in pieces]).contiguous() for i in (4, 5, 6))
     counts = torch.stack([e[2] for e in pieces]).sum(dim=0)
-    xs, ys = x[::2, ::2], y[::2, ::2]
-    periodic, fold = M.topology_of_edges(*[(xs[sl].cpu().numpy(), ys[sl].cpu().numpy())
-                                          for sl in ((slice(None), 0), (slice(None), -1), (-1, slice(None)))])
+    periodic, fold = M.topology_of_device_grid(x, y)
     p = R.params(ny, nx, src, 0, periodic, fold)
     st = torch.cuda.current_stream(dev).cuda_stream
     lib = L.load()

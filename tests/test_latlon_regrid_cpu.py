@@ -218,6 +218,21 @@ def test_struct_sizes_and_refusals():
     assert b"cover" in lib.ogg_last_error()
 
 
+def test_knobs_must_be_integers_in_range(monkeypatch):
+    """the knobs are read when a call is set up, before any device work: a value that is no integer in range is refused, not read as 0
+    or as its numeric prefix"""
+    from ocean_model_grid_generator_amd import _lib as L
+    lib = L.load()
+    p = L.RegridParams(ny=4, nx=6, NA=8, NB=4, nrec=2, dtype=L.REMAP_FLOAT32, n_fill=1, normalize=L.REGRID_AREA)
+    args = (ctypes.byref(p), 8, 8, 1, 8, 1 << 30, 8, None, None, None, 8, None)   # never dereferenced
+    for knob, val in (("OGG_REGRID_LONG", "abc"), ("OGG_REGRID_LONG", "7x"), ("OGG_REGRID_RECORDS", ""), ("OGG_REGRID_RECORDS", "9"),
+                      ("OGG_REGRID_LONG", "-1")):
+        monkeypatch.setenv(knob, val)
+        assert lib.ogg_regrid_dev(*args) == L.OGG_EARG, (knob, val)
+        assert (knob + "=" + val).encode() in lib.ogg_last_error() and b"an integer" in lib.ogg_last_error()
+        monkeypatch.delenv(knob)
+
+
 def test_python_arguments_are_checked():
     from ocean_model_grid_generator_amd import latlon_regrid as G
     lon, lat = np.array([0.0, 120.0, 240.0, 360.0]), np.array([-90.0, 0.0, 90.0])

@@ -160,6 +160,19 @@ def test_argument_errors_without_a_device(hip_lib):
         M.params(1 << 16, 1 << 15, False, False)
 
 
+def test_knobs_must_be_integers_in_range(hip_lib, monkeypatch):
+    """the knobs are read when a call is set up, before any device work: a value that is no integer in range is refused, not read as 0
+    or as its numeric prefix"""
+    L, lib = hip_lib
+    p = L.MaskParams(ny=10, nx=10)
+    args = (ctypes.byref(p), 8, 8, 1024, 8, 8, 8, None)   # never dereferenced
+    for val in ("abc", "32x", "", "65", "0"):
+        monkeypatch.setenv("OGG_MASK_TILE_ROWS", val)
+        assert lib.ogg_mask_label_dev(*args) == L.OGG_EARG, val
+        assert ("OGG_MASK_TILE_ROWS=" + val).encode() in lib.ogg_last_error() and b"an integer" in lib.ogg_last_error()
+        monkeypatch.delenv("OGG_MASK_TILE_ROWS")
+
+
 def test_struct_sizes_equal_the_ctypes_mirrors(hip_lib):
     L, lib = hip_lib
     assert lib.ogg_mask_struct_bytes(L.MASK_PARAMS) == ctypes.sizeof(L.MaskParams)

@@ -218,6 +218,23 @@ def test_struct_sizes_and_refusals():
     assert b"whole grid" in lib.ogg_last_error()
 
 
+def test_knobs_must_be_integers_in_range(monkeypatch):
+    """the knobs are read when a call is set up, before any device work: a value that is no integer in range is refused, not read as 0
+    or as its numeric prefix"""
+    from ocean_model_grid_generator_amd import _lib as L
+    lib = L.load()
+    p = L.RemapParams(ny=4, nx=6, m0=0, NA=8, NB=4, nrec=2, dtype=L.REMAP_FLOAT64, n_fill=1, topology=3, fill_max=-1)
+    steps = {"remap": lambda: lib.ogg_remap_dev(ctypes.byref(p), 8, 8, 8, 1, None, 8, 1 << 30, 8, 8, 8, None),   # never dereferenced
+             "fill": lambda: lib.ogg_remap_fill_dev(ctypes.byref(p), 8, 1 << 30, 8, 8, 8, None)}
+    for step, knob, val in (("remap", "OGG_REMAP_LONG", "abc"), ("remap", "OGG_REMAP_CACHE", "1x"), ("remap", "OGG_REMAP_RECORDS", ""),
+                            ("remap", "OGG_REMAP_LONG", "0"), ("remap", "OGG_REMAP_CACHE", "2"), ("fill", "OGG_REMAP_FILL_BLOCKS", "abc"),
+                            ("fill", "OGG_REMAP_FRONTS_PER_READ", "8 "), ("fill", "OGG_REMAP_FILL_BLOCKS", "0")):
+        monkeypatch.setenv(knob, val)
+        assert steps[step]() == L.OGG_EARG, (knob, val)
+        assert (knob + "=" + val).encode() in lib.ogg_last_error() and b"an integer" in lib.ogg_last_error()
+        monkeypatch.delenv(knob)
+
+
 def test_python_arguments_are_checked():
     from ocean_model_grid_generator_amd import remap as R
     with pytest.raises(ValueError, match="spanning|360|lon edges"):

@@ -193,6 +193,21 @@ def test_struct_sizes_and_refusals():
         assert lib.ogg_runoff_workspace_bytes(ctypes.byref(q)) == -1
 
 
+def test_knobs_must_be_integers_in_range(monkeypatch):
+    """the knobs are read when a call is set up, before any device work: a value that is no integer in range is refused, not read as 0
+    or as its numeric prefix"""
+    from ocean_model_grid_generator_amd import _lib as L
+    lib = L.load()
+    p = L.RunoffParams(ny=10, nx=20, NA=36, NB=18, nrec=2, dtype=L.REMAP_FLOAT32, n_fill=1, topology=3, targets=L.RUNOFF_COAST, Re=6371e3)
+    args = (ctypes.byref(p), 8, 8, 1, 8, 1, 8, 1 << 40, 8, 8, 8, None)   # never dereferenced
+    for knob, val in (("OGG_RUNOFF_BINS", "abc"), ("OGG_RUNOFF_BINS", "4x"), ("OGG_RUNOFF_BRUTE", ""), ("OGG_RUNOFF_BRUTE", "2"),
+                      ("OGG_RUNOFF_BINS", "-1")):
+        monkeypatch.setenv(knob, val)
+        assert lib.ogg_runoff_search_dev(*args) == L.OGG_EARG, (knob, val)
+        assert (knob + "=" + val).encode() in lib.ogg_last_error() and b"an integer" in lib.ogg_last_error()
+        monkeypatch.delenv(knob)
+
+
 def test_python_arguments_are_checked():
     from ocean_model_grid_generator_amd import remap as R
     from ocean_model_grid_generator_amd import runoff as RO
