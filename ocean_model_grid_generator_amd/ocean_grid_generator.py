@@ -636,6 +636,54 @@ def _meta_strings(inverse_resolution, no_changing_meta):
     return hist, source, desc
 
 
+def _description(head, names, merc_span, latUp_SO, lat0_SO, displaced_pole, south_cutoff_ang, south_cutoff_row):
+    """The description of OGG:1403-1423: ``head`` (_meta_strings), then a clause for every sub-grid of ``names`` that is in the grid
+    (``merc_span``: the Mercator sub-grid's first and last latitude; ``displaced_pole``: the southern cap is one, whether --r_dp or
+    --lat_dp asked for it), then the south cuts."""
+    desc = head + "It consists of; "
+    if "Merc" in names:
+        desc = desc + "a Mercator grid spanning " + str(merc_span[0]) + " to " + str(merc_span[1]) + " degrees; "
+        if "BP" in names:
+            desc = desc + "a bipolar northern cap north of " + str(merc_span[1]) + " degrees; "
+    if "SO" in names:
+        desc = desc + "a regular lat-lon grid spanning " + str(latUp_SO) + " to " + str(lat0_SO) + " degrees; "
+    if "SC" in names:
+        desc = desc + "a " + ("displaced pole " if displaced_pole else "regular ") + "southern cap south of " + str(lat0_SO) + " degrees."
+    if south_cutoff_ang > -90:
+        desc = desc + " It is cut south of " + str(south_cutoff_ang) + " degrees."
+    if south_cutoff_row > 0:
+        desc = desc + " The first " + str(south_cutoff_row) + " rows at south are deleted."
+    return desc
+
+
+class AnalysisFlags(object):
+    """main()'s flags of the analyses that follow the grid (its docstring describes them), with main()'s defaults: what main() hands
+    to either of its paths.  An unknown name is a TypeError."""
+    DEFAULTS = dict(quality_report=None, topog_source=None, topog_var="elevation", topog_file="topog.nc", topog_refine=None, xgrid_atm=None,
+                    xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False,
+                    mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False,
+                    remap_fill_max=None, runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast",
+                    xgrid_frac_file=None, interp_source=None, interp_var=None, interp_vector=None, interp_points="h",
+                    interp_file="interp.nc", interp_no_fill=False, interp_fill_max=None, interp_no_rotate=False)
+
+    def __init__(self, **flags):
+        unknown = sorted(set(flags) - set(self.DEFAULTS))
+        if unknown:
+            raise TypeError("unknown analysis flags: %s" % ", ".join(unknown))
+        vars(self).update(self.DEFAULTS, **flags)
+
+
+def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
+    """Every refusal of the flags, on both of main()'s paths: before any device work and before any source file is opened."""
+    _validate_flags(match_dy, r_dp, lat_dp)
+    _validate_mask_flags(a.ocean_mask_file, a.topog_source)
+    _validate_remap_flags(a.remap_source, a.remap_var)
+    _validate_runoff_flags(a.runoff_source, a.runoff_var, a.topog_source, a.runoff_targets, skip_metrics)
+    _validate_frac_flags(a.xgrid_frac_file, a.xgrid_atm)
+    _validate_interp_flags(a.interp_source, a.interp_var, a.interp_vector, a.interp_points, skip_metrics, a.interp_no_fill,
+                           a.interp_fill_max, a.interp_no_rotate)
+
+
 def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.0, lat_dp=-99.0, exfracdp=None,
          south_cutoff_row=0, south_cutoff_ang=-90.0, reproduce_MIDAS_grids=False, write_subgrid_files=False, plotem=False,
          no_changing_meta=False, enhanced_equatorial=0, debug=False, grids="all", match_dy=(), skip_metrics=False,
@@ -681,29 +729,17 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     component at u and its second at v), vectors turned to the grid's directions with angle_dx unless ``interp_no_rotate``; at the h
     points the wet set is the remap's and the wet points the source leaves empty are filled unless ``interp_no_fill``, at most
     ``interp_fill_max`` cells away; written to ``interp_file``; also an addition."""
+    flags = dict(locals())   # the arguments, by name: taken before anything else is bound
     import time
 
-    path = path or os.environ.get("OGG_MAIN_PATH", "pass")
-    dp_arc = dp_arc or default_dp_arc()
+    a = AnalysisFlags(**{k: flags.pop(k) for k in AnalysisFlags.DEFAULTS})
+    path = flags.pop("path") or os.environ.get("OGG_MAIN_PATH", "pass")
+    dp_arc = flags["dp_arc"] = dp_arc or default_dp_arc()
     if path == "functions":
-        return main_function_level(inverse_resolution, gridfilename, r_dp, lon_dp, lat_dp, exfracdp, south_cutoff_row, south_cutoff_ang,
-                                   reproduce_MIDAS_grids, write_subgrid_files, plotem, no_changing_meta, enhanced_equatorial, debug, grids,
-                                   match_dy, skip_metrics, ensure_nj_even, shift_equator_to_u_point, bipolar_lower_lat, mercator_lower_lat,
-                                   mercator_upper_lat, south_ocean_lower_lat, south_ocean_upper_lat, no_south_cap, return_arrays, dp_arc,
-                                   cap_symmetry, quality_report, topog_source, topog_var, topog_file, topog_refine, xgrid_atm,
-                                   xgrid_file, ocean_mask_file, mask_min_depth, mask_deepen, mask_seed, mask_keep_cells,
-                                   remap_source, remap_var, remap_file, remap_no_fill, remap_fill_max, runoff_source, runoff_var,
-                                   runoff_file, runoff_targets, xgrid_frac_file, interp_source, interp_var, interp_vector,
-                                   interp_points, interp_file, interp_no_fill, interp_fill_max, interp_no_rotate)
+        return main_function_level(analyses=a, **flags)
     from . import supergrid as SG
 
-    _validate_flags(match_dy, r_dp, lat_dp)
-    _validate_mask_flags(ocean_mask_file, topog_source)
-    _validate_remap_flags(remap_source, remap_var)
-    _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targets, skip_metrics)
-    _validate_frac_flags(xgrid_frac_file, xgrid_atm)
-    _validate_interp_flags(interp_source, interp_var, interp_vector, interp_points, skip_metrics, interp_no_fill, interp_fill_max,
-                           interp_no_rotate)
+    _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a)
     hist, source, desc = _meta_strings(inverse_resolution, no_changing_meta)
     start_time = time.time()
     plan = SG.SupergridPlan(inverse_resolution, r_dp=r_dp, lon_dp=lon_dp, lat_dp=lat_dp, exfracdp=exfracdp, south_cutoff_row=south_cutoff_row,
@@ -728,51 +764,14 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
                 print("   " + labels.get(name, "CHECK_metrics_hquad: % errors in (area, lat arc, lon arc)" if sc_dp else labels["SO"]), errs[name])
     # south cuts (OGG:1268-1313) and the final guards (OGG:1371-1375, 1425-1436) need two columns of y only
     cut = g.south_cut()
-    if quality_report:
-        _write_quality_report(g.quality(cut), quality_report)
-    topo = None
-    if topog_source is not None:
-        from . import topography as T
-        src = _topog_source(topog_source, topog_var)
-        topo = g.topography(cut, T.DeviceSource(src, g.device), refine=topog_refine)
-        mask = None
-        if ocean_mask_file:
-            mask = g.ocean_mask(cut, topo, **_mask_args(mask_min_depth, mask_deepen, mask_seed, mask_keep_cells))
-        topo = _write_topog_and_mask(topo, mask, topog_file, ocean_mask_file)
-    if xgrid_atm is not None:
-        from . import exchange_grid as X
-        xres = g.exchange_grid(cut, X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo))
-        _write_xgrid(xres, xgrid_file)
-        if xgrid_frac_file and xres is not None:   # rank 0's gathered list, not built a second time
-            _write_frac(g.regrid_to_latlon(cut, None, X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo), lists=xres), xgrid_frac_file)
-    if remap_source is not None:
-        _write_remap([(src, g.remap(cut, src, mask=_xgrid_mask(topo), fill=not remap_no_fill, fill_max=remap_fill_max))
-                      for src in _remap_sources(remap_source, remap_var)], remap_file)
-    if runoff_source is not None:
-        _write_runoff([(src, g.runoff(cut, src, _xgrid_mask(topo), targets=runoff_targets))
-                       for src in _runoff_sources(runoff_source, runoff_var)], runoff_file)
-    if interp_source is not None:
-        _write_interp(_interp_results(interp_source, interp_var, interp_vector, interp_points, lambda s1, s2: g.bilinear(
-            cut, s1, s2, points=interp_points, mask=_xgrid_mask(topo) if interp_points == "h" else None, fill=not interp_no_fill,
-            fill_max=interp_fill_max, rotate=not interp_no_rotate)), interp_file)
+    _run_analyses(a, g, cut)
     print("Stitching the grids together...")
     SG.check_guards(g.stitched_column("y", plan.Ni // 4, cut), any(s.name == "BP" for s in plan.subs))
     names = [s.name for s in plan.subs if not (s.name == "SC" and cut[2])]
-    desc = desc + "It consists of; "
-    merc = next((s for s in plan.subs if s.name == "Merc"), None)
-    if merc is not None:
-        ym = g.stitched_column("y", 0, (0, 0, False), only="Merc")
-        desc = desc + "a Mercator grid spanning " + str(ym[0]) + " to " + str(ym[-1]) + " degrees; "
-        if "BP" in names:
-            desc = desc + "a bipolar northern cap north of " + str(ym[-1]) + " degrees; "
-    if "SO" in names:
-        desc = desc + "a regular lat-lon grid spanning " + str(plan.latUp_SO) + " to " + str(plan.lat0_SO) + " degrees; "
-    if "SC" in names:
-        desc = desc + "a " + ("displaced pole " if r_dp != 0.0 else "regular ") + "southern cap south of " + str(plan.lat0_SO) + " degrees."
-    if south_cutoff_ang > -90:
-        desc = desc + " It is cut south of " + str(south_cutoff_ang) + " degrees."
-    if south_cutoff_row > 0:
-        desc = desc + " The first " + str(south_cutoff_row) + " rows at south are deleted."
+    ym = g.stitched_column("y", 0, (0, 0, False), only="Merc") if "Merc" in names else None
+    # (a displaced pole as the reference decides it, OGG:1160: --lat_dp makes one as --r_dp does)
+    desc = _description(desc, names, None if ym is None else (ym[0], ym[-1]), plan.latUp_SO, plan.lat0_SO, plan.subs[0].kind == "dpole",
+                        south_cutoff_ang, south_cutoff_row)
     nyp = g.stitched_rows(cut)
     print("shapes: ", (nyp, plan.Ni + 1), (nyp, plan.Ni + 1), (nyp, plan.Ni), (nyp - 1, plan.Ni + 1), (nyp - 1, plan.Ni), (nyp, plan.Ni + 1))
     out = None
@@ -820,48 +819,18 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
                         no_changing_meta=False, enhanced_equatorial=0, debug=False, grids="all", match_dy=(), skip_metrics=False,
                         ensure_nj_even=False, shift_equator_to_u_point=True, bipolar_lower_lat=-99.0, mercator_lower_lat=-99.0,
                         mercator_upper_lat=-99.0, south_ocean_lower_lat=-99.0, south_ocean_upper_lat=-99.0, no_south_cap=False,
-                        return_arrays=False, dp_arc=None, cap_symmetry=None, quality_report=None, topog_source=None,
-                        topog_var="elevation", topog_file="topog.nc", topog_refine=None, xgrid_atm=None,
-                        xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0,
-                        mask_deepen=False, mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None,
-                        remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None, runoff_source=None, runoff_var=None,
-                        runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None, interp_source=None, interp_var=None,
-                        interp_vector=None, interp_points="h", interp_file="interp.nc", interp_no_fill=False, interp_fill_max=None,
-                        interp_no_rotate=False):
+                        return_arrays=False, dp_arc=None, cap_symmetry=None, analyses=None):
     """The reference's own sequence of calls (OGG:855-1449), every callee a host-array function of this module (numpy in, numpy
     out, one staged device call each) and the stitching on the host: what a user gets who swaps the reference's module for this
     one function by function.  main() produces the same bits from one device-resident pass."""
     import time
 
-    _validate_mask_flags(ocean_mask_file, topog_source)
-    _validate_remap_flags(remap_source, remap_var)
-    _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targets, skip_metrics)
-    _validate_frac_flags(xgrid_frac_file, xgrid_atm)
-    _validate_interp_flags(interp_source, interp_var, interp_vector, interp_points, skip_metrics, interp_no_fill, interp_fill_max,
-                           interp_no_rotate)
-    known_options = ["bp", "so", "p125sc", ""]
-    unknown = list(set(match_dy).difference(known_options))
-    if len(unknown) != 0:
-        print("Unknown options in match_dy: ", unknown)
-        print("Known options are one or more of ", known_options)
-        sys.exit(2)
+    a = analyses or AnalysisFlags()
+    _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a)
     doughnut = 0.28 * 7 / 4
     doughnut = exfracdp if (exfracdp is not None) else doughnut
     calculate_metrics = not skip_metrics
-    if r_dp != 0.0 and lat_dp > -90.0:
-        print("Cannot specify both --rdp and --latdp for the displaced pole!")
-        usage()
-        sys.exit(2)
-
-    hist = "This grid file was generated via command " + " ".join(sys.argv)
-    source = ""
-    if not no_changing_meta:
-        host, scriptpath, githash, gitmod = _script_metadata()
-        hist = hist + " on " + str(datetime.date.today()) + " on platform " + host
-        source = scriptpath + " had git hash " + githash + gitmod
-        source = source + ". To obtain the grid generating code do: git clone  https://github.com/nikizadehgfdl/grid_generation.git ; cd grid_generation;  git checkout " + githash
-    desc = ("This is an orthogonal coordinate grid for the Earth with a nominal resoution of " + str(1 / inverse_resolution)
-            + " degrees along the equator. ")
+    hist, source, desc = _meta_strings(inverse_resolution, no_changing_meta)
 
     start_time = time.time()
     refineS = 2  # supergrid
@@ -1048,44 +1017,7 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
         if np.any((np.roll(ycol, shift=-1, axis=0) - ycol) == 0):
             raise Exception("lattitude array has repeated values along symmetry meridian!")
     x3, y3, dx3, dy3, area3, angle3 = g
-    if quality_report:   # the same report as the device pass gives, from the stitched host arrays
-        names = [n for n in ("SC", "SO", "Merc", "BP") if n in sub]
-        starts = list(np.cumsum([0] + [sub[n][0].shape[0] - 1 for n in names[:-1]]))
-        seams = [(sub[n][0][-1], sub[n][1][-1]) for n in names[:-1]]
-        metric_fields = (dx3, dy3, area3) if calculate_metrics else (None, None, None)
-        _write_quality_report(grid_quality(x3, y3, *metric_fields, Re=_default_Re, sections=list(zip(names, starts)), seams=seams),
-                              quality_report)
-    topo = None
-    if topog_source is not None:   # the same topography as the device pass gives, from the stitched host arrays
-        from . import topography as T
-        topo = T.topography(x3, y3, _topog_source(topog_source, topog_var), refine=topog_refine)
-        mask = None
-        if ocean_mask_file:   # the same mask as the device pass gives, through the host-pointer entry
-            from . import ocean_mask as M
-            mask = M.ocean_mask(topo["depth"], x3, y3, fill=T.FILL, **_mask_args(mask_min_depth, mask_deepen, mask_seed, mask_keep_cells))
-        topo = _write_topog_and_mask(topo, mask, topog_file, ocean_mask_file)
-    if xgrid_atm is not None:   # the same list as the device pass gives, through the host-pointer entry
-        from . import exchange_grid as X
-        xres = X.exchange_grid(x3, y3, *X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo), Re=_default_Re)
-        _write_xgrid(xres, xgrid_file)
-        if xgrid_frac_file:   # the same fractions as the device pass gives, through the host-pointer entry, on the same list
-            from . import latlon_regrid as G
-            _write_frac(G.latlon_fraction(x3, y3, *X.regular_atm(*xgrid_atm), mask=_xgrid_mask(topo), Re=_default_Re, lists=xres),
-                        xgrid_frac_file)
-    if remap_source is not None:   # the same values as the device pass gives, through the host-pointer entries
-        from . import remap as R
-        _write_remap([(src, R.remap(x3, y3, src, mask=_xgrid_mask(topo), fill=not remap_no_fill, fill_max=remap_fill_max, Re=_default_Re))
-                      for src in _remap_sources(remap_source, remap_var)], remap_file)
-    if runoff_source is not None:   # the same values as the device pass gives, through the host-pointer entry
-        from . import runoff as RO
-        _write_runoff([(src, RO.runoff(x3, y3, area3, src, _xgrid_mask(topo), targets=runoff_targets, Re=_default_Re))
-                       for src in _runoff_sources(runoff_source, runoff_var)], runoff_file)
-    if interp_source is not None:   # the same values as the device pass gives, through the host-pointer entry
-        from . import bilinear as B
-        _write_interp(_interp_results(interp_source, interp_var, interp_vector, interp_points, lambda s1, s2: B.bilinear(
-            x3, y3, s1, s2, angle_dx=angle3 if s2 is not None else None, points=interp_points,
-            mask=_xgrid_mask(topo) if interp_points == "h" else None, fill=not interp_no_fill, fill_max=interp_fill_max,
-            rotate=not interp_no_rotate)), interp_file)
+    _run_analyses(a, _StitchedArrays(x3, y3, (dx3, dy3, area3) if calculate_metrics else (None, None, None), angle3, sub))
 
     if write_subgrid_files:
         if "SC" in sub:
@@ -1094,19 +1026,8 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
             print("There remained no South Pole cap grid because of the number of rows cut= ", jcut, sc_rows_before_cut)
 
     # ---- description (OGG:1403-1423)
-    desc = desc + "It consists of; "
-    if "Merc" in sub:
-        desc = desc + "a Mercator grid spanning " + str(phiMerc[0, 0]) + " to " + str(phiMerc[-1, 0]) + " degrees; "
-    if "BP" in sub:
-        desc = desc + "a bipolar northern cap north of " + str(phiMerc[-1, 0]) + " degrees; "
-    if "SO" in sub:
-        desc = desc + "a regular lat-lon grid spanning " + str(latUp_SO) + " to " + str(lat0_SO) + " degrees; "
-    if "SC" in sub:
-        desc = desc + "a " + ("displaced pole " if r_dp != 0.0 else "regular ") + "southern cap south of " + str(lat0_SO) + " degrees."
-    if south_cutoff_ang > -90:
-        desc = desc + " It is cut south of " + str(south_cutoff_ang) + " degrees."
-    if south_cutoff_row > 0:
-        desc = desc + " The first " + str(south_cutoff_row) + " rows at south are deleted."
+    desc = _description(desc, sub, (phiMerc[0, 0], phiMerc[-1, 0]) if "Merc" in sub else None, latUp_SO, lat0_SO, r_dp != 0.0,
+                        south_cutoff_ang, south_cutoff_row)
 
     # ---- guards (OGG:1425-1436)
     equator_index = np.searchsorted(y3[:, q], 0.0)
@@ -1128,6 +1049,84 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
     print("runtime(secs)  %s" % (time.time() - start_time))
     if return_arrays:
         return {"x": x3, "y": y3, "dx": dx3, "dy": dy3, "area": area3, "angle_dx": angle3, "sub": sub}
+
+
+def _run_analyses(a, g, cut=None):
+    """The analyses that follow the grid (``a``: AnalysisFlags), each printed and written as it is done, in their one order: quality
+    report, topography and ocean mask, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
+    Supergrid with its ``cut`` (main) or the _StitchedArrays of main_function_level."""
+    if a.quality_report:
+        _write_quality_report(g.quality(cut), a.quality_report)
+    topo = None
+    if a.topog_source is not None:
+        topo = g.topography(cut, _topog_source(a.topog_source, a.topog_var), refine=a.topog_refine)
+        mask = None
+        if a.ocean_mask_file:
+            mask = g.ocean_mask(cut, topo, **_mask_args(a.mask_min_depth, a.mask_deepen, a.mask_seed, a.mask_keep_cells))
+        topo = _write_topog_and_mask(topo, mask, a.topog_file, a.ocean_mask_file)
+    wet = _xgrid_mask(topo)   # of the topography as written: the wet set of everything below
+    if a.xgrid_atm is not None:
+        from . import exchange_grid as X
+        xres = g.exchange_grid(cut, X.regular_atm(*a.xgrid_atm), mask=wet)
+        _write_xgrid(xres, a.xgrid_file)
+        if a.xgrid_frac_file and xres is not None:   # rank 0's list, not built a second time
+            _write_frac(g.regrid_to_latlon(cut, None, X.regular_atm(*a.xgrid_atm), mask=wet, lists=xres), a.xgrid_frac_file)
+    if a.remap_source is not None:
+        from . import remap as R
+        _write_results(R, R.write_remapped, [(src, g.remap(cut, src, mask=wet, fill=not a.remap_no_fill, fill_max=a.remap_fill_max))
+                                             for src in _read_sources(R, a.remap_source, a.remap_var)], a.remap_file)
+    if a.runoff_source is not None:
+        from . import runoff as RO
+        _write_results(RO, RO.write_runoff, [(src, g.runoff(cut, src, wet, targets=a.runoff_targets))
+                                             for src in _read_sources(RO, a.runoff_source, a.runoff_var)], a.runoff_file)
+    if a.interp_source is not None:
+        _write_interp(_interp_results(a.interp_source, a.interp_var, a.interp_vector, a.interp_points, lambda s1, s2: g.bilinear(
+            cut, s1, s2, points=a.interp_points, mask=wet if a.interp_points == "h" else None, fill=not a.interp_no_fill,
+            fill_max=a.interp_fill_max, rotate=not a.interp_no_rotate)), a.interp_file)
+
+
+class _StitchedArrays(object):
+    """The analyses of a Supergrid, under its names and arguments (``cut`` unused: the arrays are cut already), on the stitched host
+    arrays and the pieces ``sub`` of main_function_level: each the host-pointer entry of its module, which gives the same result as the
+    device pass."""
+
+    def __init__(self, x, y, metrics, angle_dx, sub):
+        self.x, self.y, self.metrics, self.angle_dx, self.sub = x, y, metrics, angle_dx, sub
+
+    def quality(self, cut):
+        sub = self.sub   # the pieces as stitched: where each starts, and the row of each that stitching dropped
+        names = [n for n in ("SC", "SO", "Merc", "BP") if n in sub]
+        starts = list(np.cumsum([0] + [sub[n][0].shape[0] - 1 for n in names[:-1]]))
+        seams = [(sub[n][0][-1], sub[n][1][-1]) for n in names[:-1]]
+        return grid_quality(self.x, self.y, *self.metrics, Re=_default_Re, sections=list(zip(names, starts)), seams=seams)
+
+    def topography(self, cut, source, refine=None):
+        from . import topography as T
+        return T.topography(self.x, self.y, source, refine=refine)
+
+    def ocean_mask(self, cut, topo, **args):
+        from . import ocean_mask as M, topography as T
+        return M.ocean_mask(topo["depth"], self.x, self.y, fill=T.FILL, **args)
+
+    def exchange_grid(self, cut, atm, mask=None):
+        from . import exchange_grid as X
+        return X.exchange_grid(self.x, self.y, *atm, mask=mask, Re=_default_Re)
+
+    def regrid_to_latlon(self, cut, field, atm, mask=None, lists=None):
+        from . import latlon_regrid as G
+        return G.latlon_fraction(self.x, self.y, *atm, mask=mask, Re=_default_Re, lists=lists)
+
+    def remap(self, cut, source, **args):
+        from . import remap as R
+        return R.remap(self.x, self.y, source, Re=_default_Re, **args)
+
+    def runoff(self, cut, source, wet, targets="coast"):
+        from . import runoff as RO
+        return RO.runoff(self.x, self.y, self.metrics[2], source, wet, targets=targets, Re=_default_Re)
+
+    def bilinear(self, cut, source, source2=None, **args):
+        from . import bilinear as B
+        return B.bilinear(self.x, self.y, source, source2, angle_dx=self.angle_dx if source2 is not None else None, **args)
 
 
 def grid_quality(x, y, dx=None, dy=None, area=None, Re=_default_Re, sections=None, seams=None):
@@ -1267,40 +1266,22 @@ def _write_xgrid(res, fnam):
     X.write_xgrid(str(fnam), res)
 
 
-def _remap_sources(path, names):
-    from . import remap as R
+def _read_sources(module, path, names):
+    """The variables ``names`` of the lat-lon file ``path`` as the Sources of remap or runoff (``module``), each announced."""
     out = []
     for name in names:
-        src = R.read_source(str(path), name)
+        src = module.read_source(str(path), name)
         print(src.note)
         out.append(src)
     return out
 
 
-def _write_remap(results, fnam):
-    from . import remap as R
+def _write_results(module, write, results, fnam):
+    """The summaries of the (source, result) pairs of remap or runoff (``module``), then its file through ``write``."""
     for _, res in results:
-        for line in R.summary_lines(res):
+        for line in module.summary_lines(res):
             print(line)
-    R.write_remapped(str(fnam), results)
-
-
-def _runoff_sources(path, names):
-    from . import runoff as RO
-    out = []
-    for name in names:
-        src = RO.read_source(str(path), name)
-        print(src.note)
-        out.append(src)
-    return out
-
-
-def _write_runoff(results, fnam):
-    from . import runoff as RO
-    for _, res in results:
-        for line in RO.summary_lines(res):
-            print(line)
-    RO.write_runoff(str(fnam), results)
+    write(str(fnam), results)
 
 
 def build_parser():

@@ -1329,9 +1329,11 @@ class Supergrid(object):
 
     def topography(self, cut, source, refine=None, oversample=2.0, cells="model"):
         """Topography of the stitched grid of every rank (topography.result on rank 0, None on the other ranks): ``source`` a
-        topography.DeviceSource on this rank's GPU.  Every piece is sampled by the rank that holds it; rank 0 gathers the integer records
+        topography.DeviceSource on this rank's GPU, or a topography.Source to upload there.  Every piece is sampled by the rank that holds it; rank 0 gathers the integer records
         (_gather) and combines them exactly, so the result is bit-identical for any number of ranks."""
         from . import topography as T
+        if isinstance(source, T.Source):
+            source = T.DeviceSource(source, self.device)
         nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
         T.check_args(nyp, nxp, cells, refine, oversample)
         sh = 1 if cells == "model" else 0
@@ -1449,49 +1451,40 @@ class Supergrid(object):
         return X.assemble(hostp, shape, lon, lat, float(self.plan.Re), threshold, mask is not None)
 
     # -- ocean mask ---------------------------------------------------------------------------------------------------
-    def stitched_xy(self, cut):
-        """The stitched x and y ((nyp, nxp) float64 device tensors) on rank 0's device, None on the other ranks: every piece's point rows
-        gathered in piece order (_gather)."""
-        torch, nxp = self.torch, self.plan.Ni + 1
+    def _stitched(self, cut, fields, point_rows):
+        """The stitched ``fields`` (float64 device tensors, contiguous) on rank 0's device, None on the other ranks: the point rows
+        (x, y, angle_dx) or the cell rows (area) of every piece gathered in piece order, all the fields in one _gather."""
+        torch, n = self.torch, "n_pt" if point_rows else "n_cell"
 
         def records(g):
             out = []
             for k, q in enumerate(g.quality_pieces(cut)):
-                if q["rank"] == g.rank:
+                if q["rank"] == g.rank and q[n] > 0:
                     b = g.buf[q["sub"].name]
-                    out.append((k, b["x"][q["row"]:q["row"] + q["n_pt"]].to(self.device), b["y"][q["row"]:q["row"] + q["n_pt"]].to(self.device)))
+                    out.append((k,) + tuple(b[f][q["row"]:q["row"] + q[n]].to(self.device) for f in fields))
             return out
 
         def recv(k, q, take):
-            return k, take((q["n_pt"], nxp), torch.float64), take((q["n_pt"], nxp), torch.float64)
-        got = self._gather(self.quality_pieces(cut), records, lambda e: (e[1], e[2]), recv)
+            if q[n] == 0:
+                return None
+            return (k,) + tuple(take((q[n], self.plan.Ni + (0 if f in ("dx", "area") else 1)), torch.float64) for f in fields)
+        got = self._gather(self.quality_pieces(cut), records, lambda e: e[1:], recv)
         if got is None:
             return None
         got.sort(key=lambda e: e[0])
-        return (torch.cat([e[1].to(self.device) for e in got]).contiguous(), torch.cat([e[2].to(self.device) for e in got]).contiguous())
+        return tuple(torch.cat([e[i].to(self.device) for e in got]).contiguous() for i in range(1, len(fields) + 1))
+
+    def stitched_xy(self, cut):
+        """The stitched x and y ((nyp, nxp) float64 device tensors) on rank 0's device, None on the other ranks (_stitched)."""
+        return self._stitched(cut, ("x", "y"), True)
 
     def stitched_area(self, cut):
-        """The stitched supergrid area ((nyp - 1, nxp - 1) float64 device tensor) on rank 0's device, None on the other ranks: every
-        piece's cell rows gathered in piece order (_gather), as stitched_xy gathers the points."""
-        torch, nx = self.torch, self.plan.Ni
+        """The stitched supergrid area ((nyp - 1, nxp - 1) float64 device tensor) on rank 0's device, None on the other ranks
+        (_stitched, cell rows)."""
         if self.plan.skip_metrics:
             raise ValueError("the supergrid area is not computed with --skip_metrics")
-
-        def records(g):
-            out = []
-            for k, q in enumerate(g.quality_pieces(cut)):
-                if q["rank"] == g.rank and q["n_cell"] > 0:
-                    b = g.buf[q["sub"].name]
-                    out.append((k, b["area"][q["row"]:q["row"] + q["n_cell"]].to(self.device)))
-            return out
-
-        def recv(k, q, take):
-            return (k, take((q["n_cell"], nx), torch.float64)) if q["n_cell"] > 0 else None
-        got = self._gather(self.quality_pieces(cut), records, lambda e: (e[1].contiguous(),), recv)
-        if got is None:
-            return None
-        got.sort(key=lambda e: e[0])
-        return torch.cat([e[1].to(self.device) for e in got]).contiguous()
+        got = self._stitched(cut, ("area",), False)
+        return None if got is None else got[0]
 
     def ocean_mask(self, cut, topo, min_depth=0.0, mode="mask", seeds=(), keep_min_cells=0):
         """The ocean mask (ocean_mask.result on rank 0, None on the other ranks) of the topography ``topo`` that topography() gathered on
@@ -1607,26 +1600,11 @@ class Supergrid(object):
 
     # -- bilinear interpolation ---------------------------------------------------------------------------------------
     def stitched_angle(self, cut):
-        """The stitched angle_dx ((nyp, nxp) float64 device tensor) on rank 0's device, None on the other ranks: every piece's point
-        rows gathered in piece order (_gather), as stitched_xy gathers the points."""
-        torch, nxp = self.torch, self.plan.Ni + 1
+        """The stitched angle_dx ((nyp, nxp) float64 device tensor) on rank 0's device, None on the other ranks (_stitched)."""
         if self.plan.skip_metrics:
             raise ValueError("angle_dx is not computed with --skip_metrics")
-
-        def records(g):
-            out = []
-            for k, q in enumerate(g.quality_pieces(cut)):
-                if q["rank"] == g.rank:
-                    out.append((k, g.buf[q["sub"].name]["angle_dx"][q["row"]:q["row"] + q["n_pt"]].to(self.device)))
-            return out
-
-        def recv(k, q, take):
-            return k, take((q["n_pt"], nxp), torch.float64)
-        got = self._gather(self.quality_pieces(cut), records, lambda e: (e[1].contiguous(),), recv)
-        if got is None:
-            return None
-        got.sort(key=lambda e: e[0])
-        return torch.cat([e[1].to(self.device) for e in got]).contiguous()
+        got = self._stitched(cut, ("angle_dx",), True)
+        return None if got is None else got[0]
 
     def bilinear(self, cut, source, source2=None, points="h", mask=None, fill=True, fill_max=None, rotate=True):
         """The bilinear interpolation (bilinear.result on rank 0, None on the other ranks) of ``source`` (a remap.Source; with

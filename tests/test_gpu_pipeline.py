@@ -583,6 +583,23 @@ def test_main_pass_path_matches_function_level_path(hip, name, tmp_path):
     nc.close()
 
 
+def test_both_main_paths_write_the_same_description(hip, tmp_path):
+    """The grid file's ``description`` attribute of main() and of main(path="functions") on r0.5_latdp is one string, and it names
+    the cap as the reference does (OGG:1160: --lat_dp makes a displaced pole).  The global attributes are only written without
+    no_changing_meta, so this test runs without it; the description itself holds nothing that changes from run to run."""
+    import ocean_model_grid_generator_amd.ocean_grid_generator as ogg
+    from scipy.io import netcdf_file
+    texts = []
+    for path in ("pass", "functions"):
+        out = str(tmp_path / (path + ".nc"))
+        ogg.main(gridfilename=out, path=path, **CONFIGS["r0.5_latdp"])
+        nc = netcdf_file(out, "r", mmap=False)
+        texts.append(nc.description.decode())
+        nc.close()
+    assert texts[0] == texts[1], texts
+    assert "a displaced pole southern cap south of" in texts[0], texts[0]
+
+
 @pytest.mark.parametrize("seed", range(40))
 def test_both_orchestrators_agree_on_random_flag_sets(hip, seed):
     """main() drives the device-resident pass from SupergridPlan's restatement of the reference's size logic (OGG:969-1313);

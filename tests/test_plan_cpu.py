@@ -106,3 +106,68 @@ def test_plot_helpers_and_row_cuts_are_back():
         import pytest
         with pytest.raises(Exception, match="matplotlib"):     # asked for a plot without matplotlib: an error, not silence
             ogg.plot_mesh_in_latlon(lam, phi)
+
+
+def _description_of(flags, names, cut_ang=-90.0, cut_row=0):
+    """_description as main()'s pass path calls it: whether the cap is a displaced pole is the PLAN's decision (OGG:1160 replaces r_dp
+    when --lat_dp is given, before the text is built), everything else literal."""
+    import ocean_model_grid_generator_amd.ocean_grid_generator as ogg
+    import ocean_model_grid_generator_amd.supergrid as SG
+    y0, y1 = orc.mercator_y_star(360, -66.85954725, 64.05895973, True, True)
+    plan = SG.SupergridPlan(0.5, ensure_nj_even=True, mercator_axis=(y0, orc.phi_mercator(360, np.arange(y0, y1 + 1))), **flags)
+    return ogg._description("Head. ", names, (-66.5, 64.25), -66.5, -78.0, plan.subs[0].kind == "dpole", cut_ang, cut_row)
+
+
+def test_description_of_the_grid_file():
+    """The one description tail of both main() paths against literal strings.  The second case is the reason it is one function: with
+    --lat_dp (r_dp left 0) the cap IS a displaced pole, as the reference and the function-level path say; the pass path used to test
+    its untouched r_dp argument and wrote "a regular southern cap"."""
+    merc = "Head. It consists of; a Mercator grid spanning -66.5 to 64.25 degrees; a bipolar northern cap north of 64.25 degrees; "
+    so = "a regular lat-lon grid spanning -66.5 to -78.0 degrees; "
+    dp = "a displaced pole southern cap south of -78.0 degrees."
+    every = ["SC", "SO", "Merc", "BP"]
+    assert _description_of(dict(r_dp=0.2), every) == merc + so + dp
+    assert _description_of(dict(lat_dp=-85.85), every) == merc + so + dp
+    assert _description_of({}, ["SO", "Merc", "BP"], cut_row=30) == merc + so + " The first 30 rows at south are deleted."
+    assert _description_of({}, every, cut_ang=-88.5, cut_row=2) == (
+        merc + so + "a regular southern cap south of -78.0 degrees. It is cut south of -88.5 degrees. The first 2 rows at south are deleted.")
+
+
+_REFUSALS = [
+    (dict(match_dy=["xx"]), SystemExit, "2"),
+    (dict(r_dp=0.2, lat_dp=-85.0), SystemExit, "2"),
+    (dict(ocean_mask_file="m.nc"), ValueError, "--ocean_mask_file needs --topog_source"),
+    (dict(remap_source="s.nc"), ValueError, "--remap_source needs at least one --remap_var"),
+    (dict(runoff_source="r.nc", runoff_var=["f"], topog_source="t.nc", skip_metrics=True), ValueError, "--runoff_source needs the cell areas"),
+    (dict(runoff_source="r.nc", topog_source="t.nc"), ValueError, "--runoff_source needs at least one --runoff_var"),
+    (dict(runoff_source="r.nc", runoff_var=["f"]), ValueError, "--runoff_source needs --topog_source"),
+    (dict(runoff_source="r.nc", runoff_var=["f"], topog_source="t.nc", runoff_targets="ocean"), ValueError, "--runoff_targets must be coast or wet"),
+    (dict(xgrid_frac_file="f.nc"), ValueError, "--xgrid_frac_file needs --xgrid_atm"),
+    (dict(interp_var=["t"]), ValueError, "need --interp_source"),
+    (dict(interp_no_rotate=True), ValueError, "need --interp_source"),
+    (dict(interp_source="s.nc"), ValueError, "nothing to interpolate"),
+    (dict(interp_source="s.nc", interp_vector=[("u",)]), ValueError, "two names"),
+    (dict(interp_source="s.nc", interp_var=["t"], interp_points="c"), ValueError, "c points are for vectors"),
+    (dict(interp_source="s.nc", interp_vector=[("u", "v")], skip_metrics=True), ValueError, "--interp_vector needs angle_dx"),
+    (dict(interp_source="s.nc", interp_var=["t"], interp_fill_max=-1), ValueError, "--interp_fill_max must be >= 0"),
+]
+
+
+@pytest.mark.parametrize("path", ["pass", "functions"])
+@pytest.mark.parametrize("flags,exc,text", _REFUSALS, ids=[",".join(sorted(f)) + ":" + t[-12:] for f, _, t in _REFUSALS])
+def test_main_refuses_on_both_paths_before_any_work(flags, exc, text, path):
+    """Every refusal of the flags, with its type and text, on both of main()'s paths and without a GPU or any of the files named: it
+    comes before any device work and before a source is opened."""
+    import re
+    import ocean_model_grid_generator_amd.ocean_grid_generator as ogg
+    with pytest.raises(exc, match=re.escape(text)):
+        ogg.main(1.0, gridfilename=None, path=path, **flags)
+
+
+def test_main_refuses_an_unknown_flag():
+    import ocean_model_grid_generator_amd.ocean_grid_generator as ogg
+    with pytest.raises(TypeError):
+        ogg.main(1.0, gridfilename=None, no_such_flag=1)
+    with pytest.raises(TypeError, match="no_such_flag"):
+        ogg.AnalysisFlags(no_such_flag=1)
+    assert ogg.AnalysisFlags(topog_var="z").topog_var == "z" and ogg.AnalysisFlags().interp_points == "h"
