@@ -940,7 +940,9 @@ int ogg_regrid(const ogg_regrid_params* p, const void* f, const int* atm_ij, con
  *            unless 0 <= t < 360.  I: the last index with c[I] <= t; I1 = (I + 1) mod NA; c1 = c[I + 1], or c[0] + 360 after the last
  *            node; wx = (t - c[I]) / (c1 - c[I]).  y <= latc[0]: J = J1 = 0, wy = 0; y >= latc[NB-1]: J = J1 = NB - 1, wy = 0 (the
  *            clamps beyond the first and last centres); otherwise J the last index with latc[J] <= y, J1 = J + 1,
- *            wy = (y - latc[J]) / (latc[J1] - latc[J]).
+ *            wy = (y - latc[J]) / (latc[J1] - latc[J]).  A NaN latitude lies between no two nodes: the point has no corners (value
+ *            OGG_REMAP_FILL, flag OGG_REMAP_UNFILLED, or OGG_REMAP_DRY under a dry mask cell), whatever the source holds; at the H
+ *            points the fill treats it as any other unfilled point.  A NaN or infinite longitude is t = 0 by the rule above.
  *   value    weights (1-wx)(1-wy), wx(1-wy), (1-wx)wy, wx wy of the corners (J,I), (J,I1), (J1,I), (J1,I1), in that order.  S = sum
  *            (w * f) and W = sum w over the corners that are not missing, left to right from +0.0, each product rounded before it is
  *            added.  All four corners valid: value S; some valid and W > 0: S / W; both flag OGG_REMAP_REMAPPED.  Otherwise value

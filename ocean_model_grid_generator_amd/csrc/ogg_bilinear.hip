@@ -92,11 +92,12 @@ __global__ __launch_bounds__(NT) void bilinear_kernel(Geo g, const double* __res
         const long pidx = row * g.pt.C + i;
         double w[4] = {0.0, 0.0, 0.0, 0.0};
         int o[4] = {0, 0, 0, 0};
-        bool wet = true;
+        bool wet = true, nolat = false;
         if (inb) {
             const long gi = (2 * row + g.pt.oy) * g.ld + 2 * i + g.pt.ox;
             const double px = x[gi], py = y[gi];
             if (mask) wet = mask[pidx] != 0;
+            nolat = py != py;   // a NaN latitude lies between no two nodes: the point is unfilled whatever the corners hold
             double t = px - nd.lonc0;
             t = t - 360.0 * floor(t / 360.0);
             if (!(t >= 0.0 && t < 360.0)) t = 0.0;
@@ -121,7 +122,8 @@ __global__ __launch_bounds__(NT) void bilinear_kernel(Geo g, const double* __res
                     if (nd.l(mid) <= py) lo = mid + 1; else hi = mid;
                 }
                 J = lo - 1;
-                if (J < 0) J = 0;                       // (only a NaN latitude gets here or below: the reads stay inside the source)
+                if (J < 0) J = 0;                       // (only a NaN latitude gets here or below: the reads stay inside the source,
+                                                        //  and nolat keeps their values out of the result)
                 if (J > g.NB - 2) J = g.NB - 2;
                 if (J < 0) J = 0;
                 J1 = J + 1 < g.NB ? J + 1 : J;
@@ -161,6 +163,8 @@ __global__ __launch_bounds__(NT) void bilinear_kernel(Geo g, const double* __res
                 double a = OGG_REMAP_FILL, b = OGG_REMAP_FILL;
                 unsigned char fl = OGG_REMAP_DRY;
                 if (!wet) {
+                } else if (nolat) {
+                    fl = OGG_REMAP_UNFILLED;
                 } else if (n == 4) {
                     a = Sa, b = Sb, fl = OGG_REMAP_REMAPPED;
                 } else if (n > 0 && W > 0.0) {

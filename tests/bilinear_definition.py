@@ -73,7 +73,8 @@ def interpolate(x, y, lon_edges, lat_edges, f, f2=None, fills=(), mask=None):
             with np.errstate(invalid="ignore", over="ignore"):
                 S[k] = np.where(ok, S[k] + wb * v.astype(np.float64), S[k])
         n += ok
-    full, part = n == 4, (n > 0) & (n < 4) & (W > 0)
+    nolat = np.broadcast_to(np.isnan(np.asarray(y, dtype=np.float64)), shape)   # a NaN latitude: no corners, whatever locate() clipped to
+    full, part = (n == 4) & ~nolat, (n > 0) & (n < 4) & (W > 0) & ~nolat
     flags = np.where(full | part, REMAPPED, UNFILLED).astype(np.uint8)
     out = []
     for s in S:
