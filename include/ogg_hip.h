@@ -507,8 +507,15 @@ int ogg_grid_quality(const ogg_quality_band* band, ogg_grid_quality_result* out)
  *   samples   a, b = 0 .. R-1; s = (a + 0.5) / R, t = (b + 0.5) / R, u = 1 - s, v = 1 - t;
  *             lon = (u * v) * L00 + (s * v) * L01 + (u * t) * L10 + (s * t) * L11 (left to right), lat the same of y00 .. y11;
  *             a pole-enclosing cell samples the polar raster row instead: lon = L00 + 360 * s, js = 0 (south) or Ny - 1 (north)
- *   index     is = floor((lon - lon0) * inv_dlon), js = floor((lat - lat0) * inv_dlat), inv_d = 1.0 / d once in fp64.  Periodic:
- *             is mod Nx, js clamped to [0, Ny - 1].  Regional: an index outside the raster makes the sample MISSING
+ *   index     js = floor((lat - lat0) * inv_dlat), inv_d = 1.0 / d once in fp64.  Periodic: is = floor((lon - lon0) * inv_dlon)
+ *             mod Nx, js clamped to [0, Ny - 1].  Regional: the sample is met on the raster's own longitude branch, whatever
+ *             multiple of 360 the grid or lon0 is stated at: d = lon - lon0, d' = d mod 360 (numpy's % semantics, as for unwrap:
+ *             m = fmod(d, 360), m + 360 when m < 0, +0 when m = 0; d' is d itself, bit for bit, when 0 <= d < 360),
+ *             is = floor(d' * inv_dlon); an index outside the raster (is outside [0, Nx - 1], d' = 360 included, or js outside
+ *             [0, Ny - 1]) makes the sample MISSING.  A sample whose lon or lat is not finite (NaN or +-infinity, from a grid point
+ *             that is not finite) is MISSING for periodic and regional sources alike: no index is formed from it, and an infinite
+ *             latitude is not clamped to a polar row (a periodic source also refuses |floor((lon - lon0) * inv_dlon)| >= 4e15).
+ *             Such a cell has no spans: its R is CLAMPED as above.  A pole-enclosing cell's samples have no lat; only lon counts
  *   record    n (samples that are not missing), n_missing, n_wet ((double)q < wet_below, wet_below = sea_level / quantum), sum q and
  *             sum q^2 (int64), min q, max q (INT32_MAX / INT32_MIN when n = 0), R
  * A MODEL cell (a MOM6 h-cell) is the 2 x 2 block of supergrid cells (2 jm + dj, 2 im + di): its record is the exact integer

@@ -86,7 +86,9 @@ OGG_DEV Cell setup_cell(const Geo& g, const Src& s, long j, long i) {
     } else {
         const double span_l = fmax(fmax(c.L00, c.L01), fmax(c.L10, c.L11)) - fmin(fmin(c.L00, c.L01), fmin(c.L10, c.L11));
         const double span_y = fmax(fmax(c.y00, c.y01), fmax(c.y10, c.y11)) - fmin(fmin(c.y00, c.y01), fmin(c.y10, c.y11));
-        const double v = ceil(g.oversample * fmax(span_l / s.dlon, span_y / s.dlat));
+        // fmax / fmin drop a NaN operand; a cell with a NaN corner has no span, and its R is clamped
+        const double any = (c.L00 + c.L01) + (c.L10 + c.L11) + (c.y00 + c.y01) + (c.y10 + c.y11);
+        const double v = any != any ? any : ceil(g.oversample * fmax(span_l / s.dlon, span_y / s.dlat));
         if (!(v <= (double)RMAX)) {
             c.R = RMAX, c.clamped = 1;
         } else {
@@ -124,26 +126,32 @@ OGG_DEV void sample_cell(const Src& s, const Cell& c, const double* S, const dou
         } else {
             lon = c.L00 + 360.0 * sa;
         }
-        double fi = floor((lon - s.lon0) * s.inv_dlon);
         bool miss = false;
         int is, js;
         if (s.periodic) {
+            const double fi = floor((lon - s.lon0) * s.inv_dlon);
             // fi mod Nx without an integer division: fi is an integral double (|fi| < 2^52 below), so fi - Nx * floor(fi / Nx),
             // taken with the reciprocal and set right by one step either way, is exact
-            miss = !(fabs(fi) < 4.0e15);   // not a number (a grid without NaN never gets here): no index is formed from it
+            miss = !(fabs(fi) < 4.0e15);   // a longitude that is not finite (or beyond any grid): no index is formed from it
             double r = miss ? 0.0 : fi - dNx * floor(fi * inv_Nx);
             r = r < 0.0 ? r + dNx : r;
             r = r >= dNx ? r - dNx : r;
             is = (int)r;
         } else {
-            miss = !(fi >= 0.0 && fi < dNx);
+            // a regional raster is met on its own longitude branch: d = (lon - lon0) mod 360 before the range test.  A d already in
+            // [0, 360) is left as it is; one turn below or above, mod360(d) is d + 360 or d - 360 bit for bit (fmod(d, 360) = d for
+            // |d| < 360 and = d - 360, exactly, for 360 <= d < 720), so only a grid stated further away pays the fmod
+            double d = lon - s.lon0;
+            if (!(d >= 0.0 && d < 360.0)) d = (d < 0.0 && d >= -360.0) ? d + 360.0 : ((d >= 360.0 && d < 720.0) ? d - 360.0 : mod360(d));
+            const double fi = floor(d * s.inv_dlon);
+            miss = !(fi >= 0.0 && fi < dNx);   // NaN (a longitude that is not finite) included
             is = miss ? 0 : (int)fi;
         }
         if (c.pole != 0) {
             js = c.pole < 0 ? 0 : (int)(Ny - 1);
         } else {
             double fj = floor((lat - s.lat0) * s.inv_dlat);
-            if (s.periodic && fj == fj) {
+            if (s.periodic && fabs(fj) < INFINITY) {   // a latitude that is not finite is MISSING, not clamped
                 fj = fj < 0.0 ? 0.0 : (fj > dNy - 1.0 ? dNy - 1.0 : fj);
             } else if (!(fj >= 0.0 && fj < dNy)) {
                 miss = true, fj = 0.0;

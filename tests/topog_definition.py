@@ -81,18 +81,23 @@ def sample_values(q, lon0, dlon, lat0, dlat, lon, lat, pole):
     Ny, Nx = q.shape
     periodic = abs(Nx * dlon - 360.0) <= 1e-9
     inv_dlon, inv_dlat = 1.0 / dlon, 1.0 / dlat
-    fi = np.floor((lon - lon0) * inv_dlon)
-    fj = np.floor((lat - lat0) * inv_dlat)
-    miss = np.zeros(lon.shape, dtype=bool)
-    if periodic:
-        is_ = fi.astype(np.int64) % Nx
-        fj = np.clip(fj, 0.0, Ny - 1.0)
-    else:
-        miss |= ~((fi >= 0) & (fi < Nx))
-        is_ = np.where(miss, 0, fi).astype(np.int64)
     pj = pole[:, None, None]
-    if not periodic:
-        miss |= (pj == 0) & ~((fj >= 0) & (fj < Ny))
+    miss = np.zeros(lon.shape, dtype=bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        fj = np.floor((lat - lat0) * inv_dlat)
+        if periodic:
+            fi = np.floor((lon - lon0) * inv_dlon)
+            miss |= ~(np.abs(fi) < 4.0e15)            # a longitude that is not finite (or beyond any grid): no index is formed
+            is_ = np.where(miss, 0.0, fi).astype(np.int64) % Nx
+            finite = np.abs(fj) < np.inf
+            miss |= (pj == 0) & ~finite                # a latitude that is not finite is MISSING, not clamped
+            fj = np.clip(np.where(finite, fj, 0.0), 0.0, Ny - 1.0)
+        else:
+            d = (lon - lon0) % 360.0                   # onto the raster's own branch; d itself when 0 <= d < 360 (fmod is exact)
+            fi = np.floor(d * inv_dlon)
+            miss |= ~((fi >= 0) & (fi < Nx))
+            is_ = np.where(miss, 0.0, fi).astype(np.int64)
+            miss |= (pj == 0) & ~((fj >= 0) & (fj < Ny))
     js = np.where(pj < 0, 0, np.where(pj > 0, Ny - 1, np.where(miss, 0, fj))).astype(np.int64)   # a pole cell: the polar row
     v = q[js, np.where(miss, 0, is_)]
     miss |= v == MISSING
@@ -102,7 +107,8 @@ def sample_values(q, lon0, dlon, lat0, dlat, lon, lat, pole):
 def supergrid_records(x, y, q, lon0, dlon, lat0, dlat, refine=None, oversample=2.0, wet_below=0.0):
     """Records of every supergrid cell (a dict of arrays ny x nx, RECORD_FIELDS)."""
     x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
-    c = cells(x, y, dlon, dlat, refine, oversample)
+    with np.errstate(invalid="ignore"):   # a grid point that is not finite
+        c = cells(x, y, dlon, dlat, refine, oversample)
     shape = c["R"].shape
     out = {f: np.zeros(shape, dtype=np.int64) for f in RECORD_FIELDS}
     out["min"][:] = np.iinfo(np.int32).max
@@ -117,7 +123,8 @@ def supergrid_records(x, y, q, lon0, dlon, lat0, dlat, refine=None, oversample=2
         chunk = max(1, 4_000_000 // int(R * R))
         for s0 in range(0, all_idx.size, chunk):
             idx = all_idx[s0:s0 + chunk]
-            lon, lat = sample_positions(flat, int(R), idx)
+            with np.errstate(invalid="ignore"):
+                lon, lat = sample_positions(flat, int(R), idx)
             v, miss = sample_values(q, lon0, dlon, lat0, dlat, lon, lat, flat["pole"][idx])
             ok = ~miss
             v64 = v.astype(np.int64)
