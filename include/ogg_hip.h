@@ -573,6 +573,59 @@ int ogg_topog_quantize_dev(const ogg_topog_source* src, int* q, int* n_bad, void
  * host memory.  A float source is quantised on the device first (OGG_EARG when |q| > OGG_TOPOG_MAX_Q). */
 int ogg_topog(const ogg_topog_band* band, const ogg_topog_source* src, ogg_topog_record* out);
 
+/* Plane-fit topography (opt-in; without it every record, output and file above is what it was): the least-squares plane
+ * q ~ c + a * dI + b * dJ over the valid samples of every output cell, fitted in the raster's INDEX space: dI counts raster columns
+ * and dJ raster rows from a per-cell origin.  The sub-grid roughness about that plane is h2, its slope the resolved bottom slope
+ * (h_std is the spread about the MEAN: on a slope it is mostly resolved slope).  Samples, indices, missing values, R, the pole test and
+ * the quantisation are exactly as above; the accumulation is in integers, so a plane record too is exact and bit-identical for any
+ * split into bands or ranks.  The fit is a plane in (lon, lat); within a cell that is a plane in distance to first order in the
+ * cell's size over its distance to the pole.  Cells that enclose a pole are refused.
+ *   origin    O of an output cell: for a model cell (jm, im) the supergrid point (2 jm + 1, 2 im + 1), its centre; for a supergrid
+ *             cell its P00.  A band that holds only one of a model row's two supergrid rows still holds this point (in its own rows or
+ *             in x_next / y_next), so two partial records use the same origin and add up.
+ *             Periodic raster: fI0 = floor((xO - lon0) * inv_dlon), fJ0 = floor((yO - lat0) * inv_dlat) clamped to [0, Ny - 1].
+ *             Regional raster: fI0 = floor(((xO - lon0) mod 360) * inv_dlon) (numpy's % semantics and the branch rule of the
+ *             samples), fJ0 = floor((yO - lat0) * inv_dlat), unclamped; neither index is range-tested.
+ *             NO ORIGIN: xO or yO is not finite, or a periodic source has |fI0| >= 4e15 (or an index is not a number); every valid
+ *             sample of the record is then FAR
+ *   offsets   of a sample that is not missing, with its unreduced column index fi (before mod Nx on a periodic source, after the
+ *             branch mapping on a regional one) and its row index fj (after the clamp on a periodic source):
+ *             periodic dI = ((fi - fI0 + hN) mod Nx) - hN, hN = Nx div 2, a non-negative mod; regional dI = fi - fI0, with NO wrap: a
+ *             cell whose origin and samples lie on either side of the raster's branch cut at lon0 has offsets of nearly a turn, and
+ *             ends up FAR wherever a turn is more than OGG_TOPOG_PLANE_MAX_OFFSET columns (on a coarser raster the offsets are
+ *             within the limit, all shifted alike, which the fit does not see); dJ = fj - fJ0.  All are integral doubles, exact.
+ *             (The kernel forms the same values as int32 differences of the reduced indices and tests those: with Nx, Ny < 2^30 and
+ *             a regional origin admitted only within 2^16 of the raster nothing overflows; csrc/ogg_topog.hip, at the far test.)
+ *   far       a valid sample is FAR (counted in n_far) when |dI| > OGG_TOPOG_PLANE_MAX_OFFSET or |dJ| > OGG_TOPOG_PLANE_MAX_OFFSET,
+ *             when it belongs to a pole-enclosing supergrid cell (which has no latitude), or when the cell has no origin.  Far samples
+ *             enter n, sum, sumsq, min and max as above, but not the moments
+ *   moments   int64, over the valid samples that are not far: sx = sum dI, sy = sum dJ, sxx = sum dI^2, sxy = sum dI dJ,
+ *             syy = sum dJ^2, sxq = sum dI q, syq = sum dJ q.  n <= 4 * 256^2 = 2^18, |d| <= 2^15, |q| <= 2^21, so sxx <= 2^48 and
+ *             |sxq| <= 2^54: nothing overflows.  Partial records combine by adding the eight new fields
+ * Outputs (host side, from the integers): the centred moments Cxx = n sxx - sx^2, Cxy = n sxy - sx sy, Cyy = n syy - sy^2,
+ * Cxq = n sxq - sx sum, Cyq = n syq - sy sum, Cqq = n sumsq - sum^2, each formed exactly in 128 bits and rounded once to fp64; then
+ * in fp64, in this order: d = Cxx * Cyy - Cxy * Cxy, a = (Cxq * Cyy - Cyq * Cxy) / d, b = (Cyq * Cxx - Cxq * Cxy) / d,
+ * r = Cqq - a * Cxq - b * Cyq (left to right).
+ *   plane_flag (byte)  0: n = 0, every float output is the fill value; 1: fitted; 2: degenerate, n < 3 or d <= 0 (one raster column
+ *             or row, collinear samples); 3: refused, n_far > 0
+ *   h2        flag 1: max(0, r) / (n * n) * quantum^2; flags 2 and 3: Cqq / (n * n) * quantum^2, the variance about the mean
+ *   plane_a, plane_b   flag 1: a, b in quanta per raster column / row; otherwise the fill value
+ *   slope_east = a * quantum / (dlon * pi / 180 * Re * cos(latC * pi / 180)), slope_north = b * quantum / (dlat * pi / 180 * Re),
+ *             Re the library's Earth radius (ogg_math.h); latC is yO for model cells and the mean of the four corner latitudes
+ *             ((y00 + y01 + y10 + y11) / 4, summed left to right) for supergrid cells; slope_east is the fill value where
+ *             |latC| >= 90 - OGG_TOPOG_POLE_EPS */
+#define OGG_TOPOG_PLANE_MAX_OFFSET (1 << 15)
+typedef struct ogg_topog_plane_record {
+    ogg_topog_record base;
+    long long sx, sy, sxx, sxy, syy, sxq, syq, n_far;
+} ogg_topog_plane_record;
+long ogg_topog_plane_record_bytes(void);                   /* sizeof(ogg_topog_plane_record): 120 */
+/* ogg_topog_band_dev with the plane moments: the same band, source and workspace contracts; out holds plane records */
+int ogg_topog_plane_band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* workspace, long workspace_bytes,
+                             ogg_topog_plane_record* out, void* stream);
+/* ogg_topog with the plane moments (HOST pointers, the same staging); out holds plane records */
+int ogg_topog_plane(const ogg_topog_band* band, const ogg_topog_source* src, ogg_topog_plane_record* out);
+
 /* ------------------------------------------------------------------------------------------------------
  * Atmosphere x ocean exchange grid (an addition: the reference has none).  First-order conservative overlaps of a rectilinear global
  * atmosphere with the MOM6 h-cells of the STITCHED supergrid x, y ((ny + 1) x (nx + 1), degrees; nx and ny even), as FMS's

@@ -89,6 +89,10 @@ TOPOG_POLE_EPS = 1.0e-10                                               # OGG_TOP
 # ogg_topog_record as a numpy record (56 bytes)
 TOPOG_RECORD = np.dtype([("n", "<i8"), ("n_missing", "<i8"), ("n_wet", "<i8"), ("sum", "<i8"), ("sumsq", "<i8"), ("min", "<i4"),
                          ("max", "<i4"), ("R", "<i4"), ("n_pole", "<i2"), ("n_clamped", "<i2")])
+TOPOG_PLANE_MAX_OFFSET = 1 << 15                                       # OGG_TOPOG_PLANE_MAX_OFFSET
+TOPOG_MOMENT_FIELDS = ("sx", "sy", "sxx", "sxy", "syy", "sxq", "syq", "n_far")
+# ogg_topog_plane_record as a numpy record (120 bytes): the fields of ogg_topog_record (its ``base``), then the moments
+TOPOG_PLANE_RECORD = np.dtype(TOPOG_RECORD.descr + [(f, "<i8") for f in TOPOG_MOMENT_FIELDS])
 
 
 class XgridAtm(ctypes.Structure):
@@ -312,6 +316,8 @@ SIGNATURES = {
     "ogg_topog_band_dev": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p, c_long, c_void_p, c_void_p],
     "ogg_topog_quantize_dev": [ctypes.POINTER(TopogSource), c_void_p, c_void_p, c_void_p],
     "ogg_topog": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p],
+    "ogg_topog_plane_band_dev": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p, c_long, c_void_p, c_void_p],
+    "ogg_topog_plane": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p],
     "ogg_xgrid_check_atm": [ctypes.POINTER(XgridAtm)],
     "ogg_xgrid_count_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_void_p, c_long, c_void_p, c_void_p, c_void_p],
     "ogg_xgrid_write_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_void_p, c_long, c_void_p, c_void_p, c_void_p,
@@ -375,6 +381,7 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_grid_quality_result_bytes": [],
                 "ogg_grid_quality_workspace_bytes": [c_long, c_long],
                 "ogg_topog_record_bytes": [],
+                "ogg_topog_plane_record_bytes": [],
                 "ogg_topog_band_out_rows": [ctypes.POINTER(TopogBand)],
                 "ogg_topog_workspace_bytes": [],
                 "ogg_xgrid_struct_bytes": [c_int],
@@ -431,6 +438,8 @@ def load():
         getattr(lib, name).restype = ctypes.c_char_p
         getattr(lib, name).argtypes = []
     for name, argtypes in LONG_GETTERS.items():
+        if os.environ.get("OGG_LIB_PATH") and not hasattr(lib, name):
+            continue   # as above
         getattr(lib, name).restype = c_long
         getattr(lib, name).argtypes = argtypes
     _lib = lib

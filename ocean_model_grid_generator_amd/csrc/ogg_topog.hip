@@ -10,9 +10,16 @@
 // and 1 - s come from a per-wavefront LDS table rebuilt when R changes (two fp64 divisions per sample would otherwise dominate).
 // Each lane keeps its own counts, sums and extremes in registers; the wavefront reduces them with shuffles (integers: exact, in any
 // order) and lane 0 stores the record.  No atomics touch a result; the only atomic is the work counter.
+//
+// PLANE (ogg_topog_plane_band_dev): the same walk also keeps the integer moments of the least-squares plane of "Plane-fit
+// topography".  Lane 0 sets up the output cell's origin (its raster column and row) into LDS next to cells[]; a sample's offsets
+// from it are int32 differences of the indices the loop already has (the periodic column offset folded into [-Nx/2, Nx/2) with two
+// conditional steps: the same residue as the definition's fold of the unreduced index), tested against the limit, and accumulated
+// as int32 sums and 32 x 32 + 64-bit multiply-adds per lane.  The PLANE = false instantiations are the code they were.
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "ogg_common.h"
@@ -24,7 +31,10 @@ constexpr int TT = 64;        // threads per workgroup: one wavefront
 constexpr int TR = 4;         // output cells per take from the counter
 constexpr int RMAX = OGG_TOPOG_MAX_REFINE;
 
+constexpr int MAXO = OGG_TOPOG_PLANE_MAX_OFFSET;
+
 static_assert(sizeof(ogg_topog_record) == 56, "ogg_topog_record layout");
+static_assert(sizeof(ogg_topog_plane_record) == 120, "ogg_topog_plane_record layout");
 
 struct Src {
     const void* data;
@@ -100,13 +110,65 @@ OGG_DEV Cell setup_cell(const Geo& g, const Src& s, long j, long i) {
     return c;
 }
 
+// the origin of an output cell's plane fit, set up once per output cell.  valid = 0: the cell has no origin, or one so far outside
+// a regional raster that every sample of it is far (the offsets below then stay within int32 whenever valid = 1)
+struct Origin {
+    int oI;      // periodic: (fI0 mod Nx) - (Nx div 2); regional: fI0
+    int J0;      // fJ0
+    int valid;
+};
+
+OGG_DEV Origin setup_origin(const Geo& g, const Src& s, long m, long io) {
+    Origin o{0, 0, 0};
+    const long jp = g.shift ? 2 * m + 1 : m, ip = g.shift ? 2 * io + 1 : io;   // a model cell's centre, a supergrid cell's P00
+    const long r = jp - g.j0;                                                  // 0 .. n: n is the row that follows the band
+    const double xO = (r < g.n ? g.x + r * g.nxp : g.x_next)[ip], yO = (r < g.n ? g.y + r * g.nxp : g.y_next)[ip];
+    if (!(fabs(xO) < INFINITY && fabs(yO) < INFINITY)) return o;
+    double fJ0 = floor((yO - s.lat0) * s.inv_dlat);
+    const double dNx = (double)s.Nx, dNy = (double)s.Ny;
+    if (s.periodic) {
+        const double fI0 = floor((xO - s.lon0) * s.inv_dlon);
+        if (!(fabs(fI0) < 4.0e15)) return o;
+        double rI = fI0 - dNx * floor(fI0 * (1.0 / dNx));   // fI0 mod Nx, as the samples' fold
+        rI = rI < 0.0 ? rI + dNx : rI;
+        rI = rI >= dNx ? rI - dNx : rI;
+        fJ0 = fJ0 < 0.0 ? 0.0 : (fJ0 > dNy - 1.0 ? dNy - 1.0 : fJ0);
+        o.oI = (int)rI - (int)(s.Nx >> 1);
+    } else {
+        // a sample's indices lie in [0, 2^30): an origin index outside [-2^16, 2^30 + 2^16) puts every one of them beyond the limit
+        const double fI0 = floor(mod360(xO - s.lon0) * s.inv_dlon);
+        const double lo = -65536.0, hi = 1073741824.0 + 65536.0;
+        if (!(fI0 >= lo && fI0 < hi && fJ0 >= lo && fJ0 < hi)) return o;
+        o.oI = (int)fI0;
+    }
+    o.J0 = (int)fJ0;
+    o.valid = 1;
+    return o;
+}
+
 struct Acc {
     int n, nm, nw, mn, mx;
     long long sum, sumsq;
 };
 
-template <int DT>
-OGG_DEV void sample_cell(const Src& s, const Cell& c, const double* S, const double* U, int lane, Acc& acc) {
+// the moments of the plane fit: a lane sees at most 4 * 256 * 256 / 64 = 4096 samples of a record, |offset| <= 2^15, |q| <= 2^21
+struct PAcc {
+    int sx, sy, nfar;
+    long long sxx, sxy, syy, sxq, syq;
+};
+
+// what a lane carries for the plane fit through the supergrid cells of one output cell.  PLANE = false: nothing -- no origin, no
+// moments, no LDS behind it -- so the sampling without the plane cannot touch any of it
+template <bool PLANE>
+struct PlaneLane {};
+template <>
+struct PlaneLane<true> {
+    PAcc acc;
+    Origin o;   // the output cell's origin, read from LDS once
+};
+
+template <int DT, bool PLANE>
+OGG_DEV void sample_cell(const Src& s, const Cell& c, const double* S, const double* U, int lane, Acc& acc, PlaneLane<PLANE>& pl) {
     const int R = c.R;
     const int RR = R * R;
     int f = lane;
@@ -115,6 +177,8 @@ OGG_DEV void sample_cell(const Src& s, const Cell& c, const double* S, const dou
     const int step_b = TT / R, step_a = TT % R;
     const long Nx = s.Nx, Ny = s.Ny;
     const double dNx = (double)Nx, dNy = (double)Ny, inv_Nx = 1.0 / dNx;
+    [[maybe_unused]] bool far_cell = false;   // PLANE only: no origin, or a pole-enclosing cell (no latitude): every valid sample is far
+    if constexpr (PLANE) far_cell = !pl.o.valid || c.pole != 0;
     for (; f < RR; f += TT) {
         const double sa = S[a], ua = U[a];
         double lon, lat = 0.0;
@@ -175,6 +239,29 @@ OGG_DEV void sample_cell(const Src& s, const Cell& c, const double* S, const dou
                 acc.sumsq += (long long)q * q;
                 acc.mn = q < acc.mn ? q : acc.mn;
                 acc.mx = q > acc.mx ? q : acc.mx;
+                if constexpr (PLANE) {
+                    // The definition forms the offsets as integral doubles and tests them against the limit before any cast.  Here
+                    // they are int32 differences, which is the same test: is, js and Nx, Ny lie in [0, 2^30) (check_source), a
+                    // periodic origin is a residue in [0, Nx) less Nx div 2 and its row is clamped to [0, Ny), and a regional origin
+                    // is admitted (valid) only in [-2^16, 2^30 + 2^16), so every difference and every step of the fold below stays
+                    // within +-(2^31 - 1); an origin outside that gate is more than 2^15 from every sample, which far_cell says.
+                    // With |dI|, |dJ| < 2^31 - 2^15 the unsigned compare of d + 2^15 against 2^16 is |d| > 2^15.
+                    const Origin& o = pl.o;
+                    PAcc& pacc = pl.acc;
+                    int dI = is - o.oI;
+                    if (s.periodic) {   // ((fi - fI0 + hN) mod Nx) - hN from the two residues
+                        dI += dI < 0 ? (int)Nx : 0;
+                        dI -= dI >= (int)Nx ? (int)Nx : 0;
+                        dI -= (int)(Nx >> 1);
+                    }
+                    const int dJ = js - o.J0;
+                    const bool far = far_cell || (unsigned)(dI + MAXO) > 2u * MAXO || (unsigned)(dJ + MAXO) > 2u * MAXO;
+                    const int eI = far ? 0 : dI, eJ = far ? 0 : dJ, eq = far ? 0 : q;
+                    pacc.nfar += far ? 1 : 0;
+                    pacc.sx += eI, pacc.sy += eJ;
+                    pacc.sxx += (long long)eI * eI, pacc.sxy += (long long)eI * eJ, pacc.syy += (long long)eJ * eJ;
+                    pacc.sxq += (long long)eI * eq, pacc.syq += (long long)eJ * eq;
+                }
             }
         }
         if (miss) acc.nm += 1;
@@ -200,11 +287,17 @@ OGG_DEV int wave_max(int v) {
     return v;
 }
 
-template <int DT>
-__global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned long long* counter, ogg_topog_record* out) {
+template <int DT, bool PLANE>
+__global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned long long* counter, void* records) {
+    auto* out = static_cast<std::conditional_t<PLANE, ogg_topog_plane_record, ogg_topog_record>*>(records);
     __shared__ double S[RMAX], U[RMAX];
     __shared__ Cell cells[4];
     __shared__ long long take;
+    [[maybe_unused]] Origin* org = nullptr;   // PLANE only: the output cell's origin in LDS, next to cells[]
+    if constexpr (PLANE) {
+        __shared__ Origin origin;
+        org = &origin;
+    }
     const int lane = threadIdx.x;
     int table_R = 0;
     const int side = 1 << g.shift;
@@ -227,8 +320,13 @@ __global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned l
                 }
                 cells[lane] = cl;
             }
+            if constexpr (PLANE) {
+                if (lane == 0) *org = setup_origin(g, s, m, io);
+            }
             __syncthreads();
             Acc acc{0, 0, 0, INT_MAX, INT_MIN, 0, 0};
+            PlaneLane<PLANE> pl;
+            if constexpr (PLANE) pl.acc = PAcc{0, 0, 0, 0, 0, 0, 0, 0}, pl.o = *org;
             int Rmax = 0, n_pole = 0, n_clamped = 0;
             for (int k = 0; k < side * side; ++k) {
                 const Cell cl = cells[k];
@@ -245,16 +343,24 @@ __global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned l
                     __syncthreads();
                     table_R = cl.R;
                 }
-                sample_cell<DT>(s, cl, S, U, lane, acc);
+                sample_cell<DT, PLANE>(s, cl, S, U, lane, acc, pl);
             }
             const int n = wave_sum(acc.n), nm = wave_sum(acc.nm), nw = wave_sum(acc.nw);
             const long long sum = wave_sum(acc.sum), sumsq = wave_sum(acc.sumsq);
             const int mn = wave_min(acc.mn), mx = wave_max(acc.mx);
-            if (lane == 0) {
-                ogg_topog_record r;
-                r.n = n, r.n_missing = nm, r.n_wet = nw, r.sum = sum, r.sumsq = sumsq;
-                r.min = mn, r.max = mx, r.R = Rmax, r.n_pole = (short)n_pole, r.n_clamped = (short)n_clamped;
-                out[c] = r;
+            ogg_topog_record r;
+            r.n = n, r.n_missing = nm, r.n_wet = nw, r.sum = sum, r.sumsq = sumsq;
+            r.min = mn, r.max = mx, r.R = Rmax, r.n_pole = (short)n_pole, r.n_clamped = (short)n_clamped;
+            if constexpr (PLANE) {
+                const PAcc& a = pl.acc;
+                ogg_topog_plane_record p;   // the wavefront's moments; a lane's sums of offsets fit int32, the wavefront's need not
+                p.base = r;
+                p.sx = wave_sum((long long)a.sx), p.sy = wave_sum((long long)a.sy), p.n_far = wave_sum(a.nfar);
+                p.sxx = wave_sum(a.sxx), p.sxy = wave_sum(a.sxy), p.syy = wave_sum(a.syy);
+                p.sxq = wave_sum(a.sxq), p.syq = wave_sum(a.syq);
+                if (lane == 0) out[c] = p;
+            } else {
+                if (lane == 0) out[c] = r;
             }
             __syncthreads();   // cells[] is rewritten for the next output cell
         }
@@ -331,6 +437,8 @@ long out_rows(const ogg_topog_band& b) {
 
 extern "C" long ogg_topog_record_bytes(void) { return (long)sizeof(ogg_topog_record); }
 
+extern "C" long ogg_topog_plane_record_bytes(void) { return (long)sizeof(ogg_topog_plane_record); }
+
 extern "C" long ogg_topog_workspace_bytes(void) { return 256; }
 
 extern "C" long ogg_topog_band_out_rows(const ogg_topog_band* band) {
@@ -338,8 +446,11 @@ extern "C" long ogg_topog_band_out_rows(const ogg_topog_band* band) {
     return out_rows(*band);
 }
 
-extern "C" int ogg_topog_band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* workspace, long workspace_bytes,
-                                  ogg_topog_record* out, void* stream) {
+namespace {
+
+// ogg_topog_band_dev (out: ogg_topog_record) and ogg_topog_plane_band_dev (plane: out holds ogg_topog_plane_record)
+int band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* workspace, long workspace_bytes, void* out, void* stream,
+             bool plane) {
     OGG_REQUIRE(band && src, OGG_EARG, "ogg_topog_band: null pointer");
     if (int e = check_band(*band)) return e;
     if (int e = check_source(*src, true)) return e;
@@ -364,12 +475,31 @@ extern "C" int ogg_topog_band_dev(const ogg_topog_band* band, const ogg_topog_so
     const long takes = (g.total + TR - 1) / TR;
     const long wgs = std::min(takes, (long)(n_cu > 0 ? n_cu : 256) * 32);   // 32 one-wave workgroups per CU, persistent
     auto* counter = static_cast<unsigned long long*>(workspace);
-    if (q.dtype == OGG_TOPOG_INT16)
-        topog_band_kernel<OGG_TOPOG_INT16><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
-    else
-        topog_band_kernel<OGG_TOPOG_INT32><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+    if (plane) {
+        if (q.dtype == OGG_TOPOG_INT16)
+            topog_band_kernel<OGG_TOPOG_INT16, true><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+        else
+            topog_band_kernel<OGG_TOPOG_INT32, true><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+    } else {
+        if (q.dtype == OGG_TOPOG_INT16)
+            topog_band_kernel<OGG_TOPOG_INT16, false><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+        else
+            topog_band_kernel<OGG_TOPOG_INT32, false><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+    }
     OGG_LAUNCH_CHECK();
     return OGG_OK;
+}
+
+}  // namespace
+
+extern "C" int ogg_topog_band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* workspace, long workspace_bytes,
+                                  ogg_topog_record* out, void* stream) {
+    return band_dev(band, src, workspace, workspace_bytes, out, stream, false);
+}
+
+extern "C" int ogg_topog_plane_band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* workspace, long workspace_bytes,
+                                        ogg_topog_plane_record* out, void* stream) {
+    return band_dev(band, src, workspace, workspace_bytes, out, stream, true);
 }
 
 extern "C" int ogg_topog_quantize_dev(const ogg_topog_source* src, int* q, int* n_bad, void* stream) {
@@ -392,8 +522,11 @@ extern "C" int ogg_topog_quantize_dev(const ogg_topog_source* src, int* q, int* 
     return OGG_OK;
 }
 
-// the host-pointer form: grid rows and raster copied to device memory, one band, the records copied back (synchronous)
-extern "C" int ogg_topog(const ogg_topog_band* band, const ogg_topog_source* src, ogg_topog_record* out) {
+namespace {
+
+// the host-pointer forms: grid rows and raster copied to device memory, one band, the records (plane records when ``plane``) copied
+// back (synchronous)
+int topog_host(const ogg_topog_band* band, const ogg_topog_source* src, void* out, bool plane) {
     OGG_REQUIRE(band && src && out, OGG_EARG, "ogg_topog: null pointer");
     if (int e = check_band(*band)) return e;
     if (int e = check_source(*src, false)) return e;
@@ -436,8 +569,19 @@ extern "C" int ogg_topog(const ogg_topog_band* band, const ogg_topog_source* src
     const long nrec = rows * (h.nx >> (h.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0));
     void *ws = nullptr, *res = nullptr;
     if (int e = bufs.alloc(&ws, (size_t)ogg_topog_workspace_bytes())) return e;
-    if (int e = bufs.alloc(&res, (size_t)nrec * sizeof(ogg_topog_record))) return e;
-    if (int e = ogg_topog_band_dev(&d, &ds, ws, ogg_topog_workspace_bytes(), static_cast<ogg_topog_record*>(res), nullptr)) return e;
-    OGG_HIP_CHECK(hipMemcpy(out, res, (size_t)nrec * sizeof(ogg_topog_record), hipMemcpyDeviceToHost));
+    const size_t rec_bytes = plane ? sizeof(ogg_topog_plane_record) : sizeof(ogg_topog_record);
+    if (int e = bufs.alloc(&res, (size_t)nrec * rec_bytes)) return e;
+    if (int e = band_dev(&d, &ds, ws, ogg_topog_workspace_bytes(), res, nullptr, plane)) return e;
+    OGG_HIP_CHECK(hipMemcpy(out, res, (size_t)nrec * rec_bytes, hipMemcpyDeviceToHost));
     return OGG_OK;
+}
+
+}  // namespace
+
+extern "C" int ogg_topog(const ogg_topog_band* band, const ogg_topog_source* src, ogg_topog_record* out) {
+    return topog_host(band, src, out, false);
+}
+
+extern "C" int ogg_topog_plane(const ogg_topog_band* band, const ogg_topog_source* src, ogg_topog_plane_record* out) {
+    return topog_host(band, src, out, true);
 }

@@ -659,7 +659,8 @@ def _description(head, names, merc_span, latUp_SO, lat0_SO, displaced_pole, sout
 class AnalysisFlags(object):
     """main()'s flags of the analyses that follow the grid (its docstring describes them), with main()'s defaults: what main() hands
     to either of its paths.  An unknown name is a TypeError."""
-    DEFAULTS = dict(quality_report=None, topog_source=None, topog_var="elevation", topog_file="topog.nc", topog_refine=None, xgrid_atm=None,
+    DEFAULTS = dict(quality_report=None, topog_source=None, topog_var="elevation", topog_file="topog.nc", topog_refine=None,
+                    topog_roughness=False, xgrid_atm=None,
                     xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False,
                     mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False,
                     remap_fill_max=None, runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast",
@@ -677,6 +678,7 @@ def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
     """Every refusal of the flags, on both of main()'s paths: before any device work and before any source file is opened."""
     _validate_flags(match_dy, r_dp, lat_dp)
     _validate_mask_flags(a.ocean_mask_file, a.topog_source)
+    _validate_roughness_flags(a.topog_roughness, a.topog_source)
     _validate_remap_flags(a.remap_source, a.remap_var)
     _validate_runoff_flags(a.runoff_source, a.runoff_var, a.topog_source, a.runoff_targets, skip_metrics)
     _validate_frac_flags(a.xgrid_frac_file, a.xgrid_atm)
@@ -695,7 +697,7 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None,
          runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None,
          interp_source=None, interp_var=None, interp_vector=None, interp_points="h", interp_file="interp.nc", interp_no_fill=False,
-         interp_fill_max=None, interp_no_rotate=False):
+         interp_fill_max=None, interp_no_rotate=False, topog_roughness=False):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -712,7 +714,9 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     write the grid-quality report of the stitched grid (grid_quality.py) to that file as JSON and print a summary of it after the
     CHECK_metrics lines; an addition the reference does not have.  ``topog_source`` (--topog_source FILE, or a topography.Source):
     sample that raster (variable ``topog_var``) on the model cells of the stitched grid straight from HBM and write ``topog_file``
-    (topography.py; ``topog_refine``: R x R samples per supergrid cell instead of R from the cell's size); also an addition.
+    (topography.py; ``topog_refine``: R x R samples per supergrid cell instead of R from the cell's size; ``topog_roughness``
+    (--topog_roughness): also fit a plane to every cell's samples and write the roughness h2 about it, the bottom slopes slope_east and
+    slope_north, and plane_flag); also an addition.
     ``xgrid_atm`` (--xgrid_atm NLON NLAT): write the exchange grid of the model cells with a regular global NLON x NLAT atmosphere to
     ``xgrid_file`` (exchange_grid.py; only cells with depth > 0 when ``topog_source`` is given too); also an addition.
     ``ocean_mask_file`` (--ocean_mask_file FILE, needs ``topog_source``): the ocean mask of that topography (ocean_mask.py: cells
@@ -1059,7 +1063,7 @@ def _run_analyses(a, g, cut=None):
         _write_quality_report(g.quality(cut), a.quality_report)
     topo = None
     if a.topog_source is not None:
-        topo = g.topography(cut, _topog_source(a.topog_source, a.topog_var), refine=a.topog_refine)
+        topo = g.topography(cut, _topog_source(a.topog_source, a.topog_var), refine=a.topog_refine, plane=bool(a.topog_roughness))
         mask = None
         if a.ocean_mask_file:
             mask = g.ocean_mask(cut, topo, **_mask_args(a.mask_min_depth, a.mask_deepen, a.mask_seed, a.mask_keep_cells))
@@ -1100,9 +1104,9 @@ class _StitchedArrays(object):
         seams = [(sub[n][0][-1], sub[n][1][-1]) for n in names[:-1]]
         return grid_quality(self.x, self.y, *self.metrics, Re=_default_Re, sections=list(zip(names, starts)), seams=seams)
 
-    def topography(self, cut, source, refine=None):
+    def topography(self, cut, source, refine=None, plane=False):
         from . import topography as T
-        return T.topography(self.x, self.y, source, refine=refine)
+        return T.topography(self.x, self.y, source, refine=refine, plane=plane)
 
     def ocean_mask(self, cut, topo, **args):
         from . import ocean_mask as M, topography as T
@@ -1166,6 +1170,11 @@ def _write_topog(res, fnam):
 def _validate_mask_flags(ocean_mask_file, topog_source):
     if ocean_mask_file and topog_source is None:
         raise ValueError("--ocean_mask_file needs --topog_source: the ocean mask is made from the topography")
+
+
+def _validate_roughness_flags(topog_roughness, topog_source):
+    if topog_roughness and topog_source is None:
+        raise ValueError("--topog_roughness needs --topog_source: the roughness and the bottom slopes come from the topography's samples")
 
 
 def _validate_remap_flags(remap_source, remap_var):
@@ -1335,6 +1344,9 @@ def build_parser():
     parser.add_argument("--topog_file", type=str, required=False, default="topog.nc", help="topography output file, default topog.nc")
     parser.add_argument("--topog_refine", type=int, required=False, default=None,
                         help="R x R samples in every supergrid cell (default: from each cell's size, twice the raster's resolution)")
+    parser.add_argument("--topog_roughness", action="store_true",
+                        help="also fit a plane to every cell's samples of --topog_source and write the roughness h2 about it, the bottom "
+                             "slopes slope_east and slope_north, and plane_flag into --topog_file")
     parser.add_argument("--xgrid_atm", type=int, nargs=2, required=False, default=None, metavar=("NLON", "NLAT"),
                         help="write the atmosphere x ocean exchange grid of a regular global NLON x NLAT atmosphere into --xgrid_file "
                              "(wet cells only when --topog_source is given)")

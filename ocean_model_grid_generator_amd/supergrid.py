@@ -1304,10 +1304,11 @@ class Supergrid(object):
         return Q.report(recs, self.plan.Re, self.stitched_rows(cut), self.plan.Ni, not self.plan.skip_metrics)
 
     # -- topography by refined sampling -------------------------------------------------------------------------
-    def topography_records(self, cut, source, refine=None, oversample=2.0, cells="model", halo=None):
+    def topography_records(self, cut, source, refine=None, oversample=2.0, cells="model", halo=None, plane=False):
         """[(piece index, first output row, int64 device tensor of records)] of THIS rank's pieces of the stitched grid, sampled on the
         buffers the pass left in HBM.  A piece's last cell row takes its upper point row from the next piece (quality_halo); a model
-        row whose two supergrid rows lie in two pieces gets a partial record from each, combined exactly by the caller."""
+        row whose two supergrid rows lie in two pieces gets a partial record from each, combined exactly by the caller.  ``plane``:
+        plane records (ogg_topog_plane_band_dev)."""
         from . import topography as T
         p, st = self.plan, self._stream()
         halo = self.quality_halo(cut) if halo is None else halo   # (held until the kernels have run: the bands point into it)
@@ -1321,35 +1322,38 @@ class Supergrid(object):
                 band.x_next, band.y_next = nxt["x"].data_ptr(), nxt["y"].data_ptr()
             else:   # the piece that ends the grid holds its own last point row
                 band.x_next, band.y_next = self._p(b["x"], q["row"] + q["n_cell"]), self._p(b["y"], q["row"] + q["n_cell"])
-            m0, rec, ws = T.band_records_dev(band, source.desc, st, self.device)
+            m0, rec, ws = T.band_records_dev(band, source.desc, st, self.device, plane)
             out.append((k, m0, rec))
             keep.append(ws)
         self.torch.cuda.synchronize(self.device)
         return out
 
-    def topography(self, cut, source, refine=None, oversample=2.0, cells="model"):
+    def topography(self, cut, source, refine=None, oversample=2.0, cells="model", plane=False):
         """Topography of the stitched grid of every rank (topography.result on rank 0, None on the other ranks): ``source`` a
         topography.DeviceSource on this rank's GPU, or a topography.Source to upload there.  Every piece is sampled by the rank that holds it; rank 0 gathers the integer records
-        (_gather) and combines them exactly, so the result is bit-identical for any number of ranks."""
+        (_gather) and combines them exactly, so the result is bit-identical for any number of ranks.  ``plane``: plane records through
+        the same gather, and the stitched latitudes gathered on rank 0 (_stitched) for the slopes of the plane."""
         from . import topography as T
         if isinstance(source, T.Source):
             source = T.DeviceSource(source, self.device)
         nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
         T.check_args(nyp, nxp, cells, refine, oversample)
         sh = 1 if cells == "model" else 0
-        words = L.TOPOG_RECORD.itemsize // 8
+        words = T.record_words(plane)
 
         def recv(k, q, take):
             if q["n_cell"] == 0:
                 return None
             rows = ((q["j0"] + q["n_cell"] - 1) >> sh) - (q["j0"] >> sh) + 1
             return k, q["j0"] >> sh, take((rows, self.plan.Ni >> sh, words), self.torch.int64)
-        got = self._gather(self.quality_pieces(cut), lambda g: g.topography_records(cut, source, refine, oversample, cells),
+        got = self._gather(self.quality_pieces(cut), lambda g: g.topography_records(cut, source, refine, oversample, cells, plane=plane),
                            lambda e: (e[2],), recv)
+        lat = self._stitched(cut, ("y",), True) if plane else None   # every rank takes part
         if got is None:
             return None
-        recs = T.assemble([(m0, T.records_to_host(t)) for _, m0, t in got], (nyp - 1) >> sh, (nxp - 1) >> sh)
-        return T.result(recs, source.source.quantum, source.sea_level, cells, refine, oversample, source.source)
+        recs = T.assemble([(m0, T.records_to_host(t)) for _, m0, t in got], (nyp - 1) >> sh, (nxp - 1) >> sh, plane)
+        lat_c = T.cell_latitudes(lat[0].cpu().numpy(), cells) if plane else None
+        return T.result(recs, source.source.quantum, source.sea_level, cells, refine, oversample, source.source, lat_c)
 
     # -- atmosphere x ocean exchange grid --------------------------------------------------------------------------
     @staticmethod

@@ -1,11 +1,16 @@
 """Time topography by refined sampling (csrc/ogg_topog.hip) on generated grids against a synthetic int16 raster of GEBCO size built
 on the device (a smooth analytic field plus a seeded hash: nothing is downloaded).
 
-    python scripts/topog_profile.py [--res 8] [--arcsec 30 15] [--dp 0 0.2] [--reps 3] [--json OUT] [--baseline]
+    python scripts/topog_profile.py [--res 8] [--arcsec 30 15] [--dp 0 0.2] [--reps 3] [--json OUT] [--baseline] [--plane] [--int32]
 
 For every (raster, grid) pair: HIP-event times of the sampling of the whole stitched grid (Supergrid.topography_records: every
 band's ogg_topog_band_dev; the halo rows are fetched once before the timed runs and are not timed), samples, samples/s.  --baseline adds the numpy definition's samples/s on one host
 core (tests/topog_definition.py, on a small grid against the same kind of raster).  One warm-up run precedes the timed ones.
+--plane times the plane-fit kernel (ogg_topog_plane_band_dev) as well, in the same process: after a warm-up of each, every repetition
+runs the base sampling and then the plane sampling, so that both see the same box at the same time; it reports both lists of times,
+the ratio of the best and of the median times, and checks that the base half of the plane records is the base records.
+--int32 widens the raster to int32 quanta on the device (what a float source becomes once quantised), so that the int32 instantiations
+of both kernels are the ones timed.
 """
 import argparse
 import json
@@ -40,19 +45,22 @@ def synthetic_raster(arcsec, device):
 class _DeviceRaster(object):
     """A topography.DeviceSource over a raster that already lives on the device."""
 
-    def __init__(self, tensor, box):
+    def __init__(self, tensor, box, int32=False):
         import numpy as np
+        import torch
 
         from ocean_model_grid_generator_amd import _lib as L
         from ocean_model_grid_generator_amd import topography as T
+        if int32:
+            tensor = tensor.to(torch.int32)
         self.tensor, self.sea_level = tensor, 0.0
         self.source = T.Source(np.zeros((1, 1), dtype=np.int16), *box)
         Ny, Nx = tensor.shape
-        self.desc = L.TopogSource(data=tensor.data_ptr(), dtype=L.TOPOG_INT16, n_fill=0, Nx=Nx, Ny=Ny, lon0=box[0], dlon=box[1],
+        self.desc = L.TopogSource(data=tensor.data_ptr(), dtype=L.TOPOG_INT32 if int32 else L.TOPOG_INT16, n_fill=0, Nx=Nx, Ny=Ny, lon0=box[0], dlon=box[1],
                                   lat0=box[2], dlat=box[3], quantum=1.0, wet_below=0.0)
 
 
-def time_grid(res, r_dp, src, reps):
+def time_grid(res, r_dp, src, reps, plane=False):
     import torch
 
     from ocean_model_grid_generator_amd import supergrid as SG
@@ -75,8 +83,27 @@ def time_grid(res, r_dp, src, reps):
         times.append(e0.elapsed_time(e1))
         del recs
     best = min(times)
-    return {"res": res, "r_dp": r_dp, "nyp": g.stitched_rows(cut), "nxp": plan.Ni + 1, "samples": samples, "R_max": r_max,
-            "ms": times, "ms_best": best, "samples_per_s": samples / (best * 1e-3)}
+    out = {"res": res, "r_dp": r_dp, "nyp": g.stitched_rows(cut), "nxp": plan.Ni + 1, "samples": samples, "R_max": r_max,
+           "ms": times, "ms_best": best, "samples_per_s": samples / (best * 1e-3)}
+    if plane:
+        base = g.topography_records(cut, src, halo=halo)
+        recs = g.topography_records(cut, src, halo=halo, plane=True)   # warm-up of the plane kernel
+        out["base_half_equal"] = all(bool((b == p[..., :7]).all()) for (_, _, b), (_, _, p) in zip(base, recs))
+        out["n_far"] = sum(int(t[..., 14].sum()) for _, _, t in recs)
+        del base, recs
+        tb, tp = [], []
+        for _ in range(reps):
+            for flag, times in ((False, tb), (True, tp)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                recs = g.topography_records(cut, src, halo=halo, plane=flag)
+                e1.record()
+                torch.cuda.synchronize()
+                times.append(e0.elapsed_time(e1))
+                del recs
+        med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
+        out.update(ms_base_alternating=tb, ms_plane=tp, ms_plane_best=min(tp), ratio_best=min(tp) / min(tb), ratio_median=med(tp) / med(tb))
+    return out
 
 
 def baseline(arcsec_like=30):
@@ -102,17 +129,20 @@ def main(argv=None):
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--json", default=None)
     p.add_argument("--baseline", action="store_true")
+    p.add_argument("--plane", action="store_true", help="also time the plane-fit kernel, alternating with the base kernel")
+    p.add_argument("--int32", action="store_true", help="sample the raster as int32 quanta (the kernels of a quantised float source)")
     a = p.parse_args(argv)
     import torch
     out = []
     for arcsec in a.arcsec:
         t, box = synthetic_raster(arcsec, "cuda:0")
         torch.cuda.synchronize()
-        src = _DeviceRaster(t, box)
+        src = _DeviceRaster(t, box, a.int32)
         for res in a.res:
             for dp in a.dp:
-                r = time_grid(res, dp, src, a.reps)
+                r = time_grid(res, dp, src, a.reps, a.plane)
                 r["arcsec"] = arcsec
+                r["dtype"] = "int32" if a.int32 else "int16"
                 r["raster"] = list(t.shape)
                 print(json.dumps(r))
                 out.append(r)
