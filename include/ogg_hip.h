@@ -1058,6 +1058,68 @@ int ogg_bilinear(const ogg_bilinear_params* p, const double* x, const double* y,
                  unsigned char* flags, double* values2, unsigned char* flags2, double* rot_cos, double* rot_sin, double* rot_cos2,
                  double* rot_sin2);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Distance to the coast (an addition: the reference has none).  For every model cell the nearest cell across the coast, as MOM6
+ * set-ups need it to taper salinity restoring near land, to spread runoff and to build sponges.
+ *   cells    the ny x nx model cells, c = j * nx + i, one wet byte per cell (0: land) and the centre at supergrid point (2j+1, 2i+1),
+ *            as for the runoff mapping.  A cell is VALID when its centre's longitude and latitude are both finite.
+ *   nearest  unit vectors and d2 = (dx * dx + dy * dy) + dz * dz exactly as "Runoff mapping" forms them (the same D, no FMA; one
+ *            shared implementation), and nearest by the key (d2, c'): ties to the smaller cell.
+ *   face neighbours  the ocean mask's: i +- 1 (with OGG_MASK_PERIODIC, (j, nx-1) ~ (j, 0)), j +- 1, and on the top row with
+ *            OGG_MASK_FOLD the partner (ny-1, nx-1-i).  A neighbour that does not exist is NOT a neighbour: the grid's edge is no
+ *            coast.  (This differs from OGG_RUNOFF_COAST, which counts a missing neighbour as land.)  On a fold of odd width the
+ *            middle cell is its own partner and is not thereby coastal.
+ *   coastal  a cell with at least one face neighbour of the other wetness.  Wetness alone decides this: an invalid neighbour still
+ *            makes its neighbour coastal through its wet byte.  L: the VALID coastal land cells; W: the VALID coastal wet cells; both
+ *            lists in ascending c.
+ *   answer   a valid wet cell gets the member of L with the smallest (d2, c'), a valid land cell the member of W with the smallest
+ *            (d2, c').  sides (OGG_COAST_WET | OGG_COAST_LAND) selects which cells are queried.  A cell that is not queried, is
+ *            invalid, or whose opposite set is empty gets nearest = -1 and d2 = +inf.  A cell is never its own answer.
+ *   flags    one byte per cell: bit 0 wet, bit 1 coastal, bit 2 valid.
+ * nearest and d2 are a function of the unit vectors and the wet bytes alone: no search index, tile shape, launch geometry or knob
+ * (OGG_COAST_BRUTE, OGG_COAST_CUBES, OGG_COAST_TILE_X, OGG_COAST_TILE_Y, OGG_COAST_CHUNK) changes a bit, and neither does the rank
+ * count on the gathered grid.  The distance in metres is not a device output: coast_distance.py forms
+ * Re * (2 * arcsin(minimum(1, 0.5 * sqrt(d2)))) with numpy from d2, and writes 1e20 where nearest = -1.
+ * Output layout: nearest (ny, nx) int32; d2 (ny, nx) fp64.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { OGG_COAST_WET = 1, OGG_COAST_LAND = 2 };
+enum { OGG_COAST_PARAMS = 0, OGG_COAST_COUNTS = 1 };
+#define OGG_COAST_MAX_CUBES 128   /* the largest OGG_COAST_CUBES: cubes per axis of the search index */
+/* ny * nx < 2^31 */
+typedef struct ogg_coast_params {
+    long ny, nx;               /* model cells */
+    int topology;              /* OGG_MASK_PERIODIC | OGG_MASK_FOLD */
+    int sides;                 /* OGG_COAST_WET | OGG_COAST_LAND: the cells that are queried */
+} ogg_coast_params;
+typedef struct ogg_coast_counts {
+    long long coast_wet;       /* members of W (sets step) */
+    long long coast_land;      /* members of L (sets step) */
+    long long queries;         /* valid cells of the selected sides (sets step) */
+    long long answered;        /* queries with an answer (search step) */
+    long long tests;           /* distance tests (search step) */
+    long long tiles;           /* tiles of cells, one workgroup each (search step) */
+    long long cubes;           /* cubes per axis of the search index, 0 for brute force (search step) */
+} ogg_coast_counts;
+long ogg_coast_struct_bytes(int which);                      /* sizeof of OGG_COAST_PARAMS / COUNTS, -1 otherwise */
+long ogg_coast_workspace_bytes(const ogg_coast_params* p);   /* of both steps, -1 on a bad *p */
+/* the checks of *p (sizes, topology, sides): OGG_EARG with the reason, before any device work */
+int ogg_coast_check(const ogg_coast_params* p);
+/* sets step, device pointers, on a stream: x, y the supergrid points (2 ny + 1 rows of ld doubles), wet one byte per cell; flags
+ * (ny * nx bytes) and u (3 doubles per cell) of every cell; the lists land_cell / wet_cell (room for ny * nx each) in ascending c with
+ * their unit vectors land_u / wet_u (3 per member); *counts (device memory) is zeroed and gets coast_wet, coast_land and queries. */
+int ogg_coast_sets_dev(const ogg_coast_params* p, const double* x, const double* y, long ld, const unsigned char* wet, void* workspace,
+                       long workspace_bytes, unsigned char* flags, double* u, int* land_cell, double* land_u, int* wet_cell,
+                       double* wet_u, ogg_coast_counts* counts, void* stream);
+/* search step, after the sets step (n_land, n_wet its counts): nearest and the bits of d2 for every cell as above; answered, tests,
+ * tiles and cubes into *counts, from zero. */
+int ogg_coast_search_dev(const ogg_coast_params* p, const unsigned char* flags, const double* u, const int* land_cell,
+                         const double* land_u, long n_land, const int* wet_cell, const double* wet_u, long n_wet, void* workspace,
+                         long workspace_bytes, int* nearest, double* d2, ogg_coast_counts* counts, void* stream);
+/* HOST pointers throughout, staged through device memory: both steps on the supergrid x, y ((2 ny + 1) x (2 nx + 1)); nearest, d2 and
+ * flags one value per cell. */
+int ogg_coast_distance(const ogg_coast_params* p, const double* x, const double* y, const unsigned char* wet, int* nearest, double* d2,
+                       unsigned char* flags, ogg_coast_counts* counts);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

@@ -177,6 +177,25 @@ RUNOFF_PARAMS, RUNOFF_COUNTS = 0, 1                                    # OGG_RUN
 RUNOFF_MAX_BINS = 160                                                  # OGG_RUNOFF_MAX_BINS
 
 
+class CoastParams(ctypes.Structure):
+    """ogg_coast_params of include/ogg_hip.h"""
+    _fields_ = [("ny", c_long), ("nx", c_long), ("topology", c_int), ("sides", c_int)]
+
+
+COAST_COUNT_FIELDS = ("coast_wet", "coast_land", "queries", "answered", "tests", "tiles", "cubes")
+
+
+class CoastCounts(ctypes.Structure):
+    """ogg_coast_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in COAST_COUNT_FIELDS]
+
+
+COAST_WET, COAST_LAND = 1, 2                                           # OGG_COAST_WET, OGG_COAST_LAND
+COAST_PARAMS, COAST_COUNTS = 0, 1                                      # OGG_COAST_PARAMS, OGG_COAST_COUNTS
+COAST_F_WET, COAST_F_COAST, COAST_F_VALID = 1, 2, 4                    # the bits of a flag byte
+COAST_MAX_CUBES = 128                                                  # OGG_COAST_MAX_CUBES
+
+
 class RegridParams(ctypes.Structure):
     """ogg_regrid_params of include/ogg_hip.h"""
     _fields_ = [("ny", c_long), ("nx", c_long), ("NA", c_long), ("NB", c_long), ("nrec", c_long), ("dtype", c_int), ("n_fill", c_int),
@@ -350,6 +369,13 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p],
     "ogg_runoff": [ctypes.POINTER(RunoffParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                    c_void_p, c_void_p, c_void_p, ctypes.POINTER(RunoffCounts)],
+    "ogg_coast_check": [ctypes.POINTER(CoastParams)],
+    "ogg_coast_sets_dev": [ctypes.POINTER(CoastParams), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_coast_search_dev": [ctypes.POINTER(CoastParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long,
+                             c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_coast_distance": [ctypes.POINTER(CoastParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           ctypes.POINTER(CoastCounts)],
     "ogg_regrid_check": [ctypes.POINTER(RegridParams)],
     "ogg_regrid_transpose_dev": [ctypes.POINTER(RegridParams), c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p],
     "ogg_regrid_dev": [ctypes.POINTER(RegridParams), c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -395,6 +421,8 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_remap_workspace_bytes": [ctypes.POINTER(RemapParams)],
                 "ogg_runoff_struct_bytes": [c_int],
                 "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],
+                "ogg_coast_struct_bytes": [c_int],
+                "ogg_coast_workspace_bytes": [ctypes.POINTER(CoastParams)],
                 "ogg_regrid_struct_bytes": [c_int],
                 "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long],
                 "ogg_bilinear_struct_bytes": []}

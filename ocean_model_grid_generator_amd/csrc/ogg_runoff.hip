@@ -30,6 +30,7 @@
 #include "ogg_blocks.h"
 #include "ogg_common.h"
 #include "ogg_keysort.h"
+#include "ogg_sphere.h"
 
 #pragma clang fp contract(off)
 
@@ -44,7 +45,7 @@ constexpr int NT = 256;                 // threads per workgroup (four wavefront
 constexpr int REG = 8;                  // sources a lane keeps in registers across records
 constexpr int LONG_N = 32;              // cells with more sources are walked by the whole wavefront
 constexpr long HEAD = 256;
-constexpr double D = 0.017453292519943295;   // pi / 180
+constexpr double D = SPHERE_D;
 constexpr double PAD = 1e-9;            // cubes widened by this much: covers the rounding of a point's cube index
 constexpr double MARGIN = 1.0 + 1e-12;  // covers the rounding of a computed d2
 
@@ -57,24 +58,6 @@ struct Head {
     long long total;                    // the last scan's total
 };
 static_assert(sizeof(Head) <= HEAD, "workspace head");
-
-__device__ inline void unit(double lon, double lat, double* u) {
-    const double cl = cos(lat * D);
-    u[0] = cl * cos(lon * D);
-    u[1] = cl * sin(lon * D);
-    u[2] = sin(lat * D);
-}
-
-__device__ inline double dist2(double ax, double ay, double az, double bx, double by, double bz) {
-    const double dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-__device__ inline unsigned long long bits_of(double v) {
-    unsigned long long b;
-    memcpy(&b, &v, 8);
-    return b;
-}
 
 // ---- targets -------------------------------------------------------------------------------------------------------
 struct Cells {
@@ -175,34 +158,6 @@ __global__ __launch_bounds__(NT) void source_list_kernel(long NA, long NB, const
 }
 
 // ---- search --------------------------------------------------------------------------------------------------------
-__device__ inline int cube_of(double v, int G) {
-    const int k = (int)floor((v + 1.0) * (0.5 * (double)G));
-    return k < 0 ? 0 : (k >= G ? G - 1 : k);
-}
-
-__global__ __launch_bounds__(NT) void bin_count_kernel(const double* __restrict__ u, long n, int G, int* __restrict__ cnt,
-                                                       int* __restrict__ bin) {
-    for (long k = (long)blockIdx.x * NT + threadIdx.x; k < n; k += (long)gridDim.x * NT) {
-        const int b = cube_of(u[3 * k], G) + G * (cube_of(u[3 * k + 1], G) + G * cube_of(u[3 * k + 2], G));
-        bin[k] = b;
-        atomicAdd(&cnt[b], 1);
-    }
-}
-
-// every target copied into its cube's range (the order inside a cube does not matter: the key breaks ties)
-__global__ __launch_bounds__(NT) void bin_fill_kernel(const double* __restrict__ u, const int* __restrict__ cell, long n,
-                                                      const int* __restrict__ bin, const int* __restrict__ start, int* __restrict__ cursor,
-                                                      double* __restrict__ bu, int* __restrict__ bc) {
-    for (long k = (long)blockIdx.x * NT + threadIdx.x; k < n; k += (long)gridDim.x * NT) {
-        const int b = bin[k];
-        const long q = (long)start[b] + atomicAdd(&cursor[b], 1);
-        bu[3 * q] = u[3 * k];
-        bu[3 * q + 1] = u[3 * k + 1];
-        bu[3 * q + 2] = u[3 * k + 2];
-        bc[q] = cell[k];
-    }
-}
-
 struct Index {
     int G;
     double h;

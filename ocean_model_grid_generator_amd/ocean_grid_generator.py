@@ -664,7 +664,7 @@ class AnalysisFlags(object):
                     xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False,
                     mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False,
                     remap_fill_max=None, runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast",
-                    xgrid_frac_file=None, interp_source=None, interp_var=None, interp_vector=None, interp_points="h",
+                    coast_distance_file=None, coast_distance_sides="both", xgrid_frac_file=None, interp_source=None, interp_var=None, interp_vector=None, interp_points="h",
                     interp_file="interp.nc", interp_no_fill=False, interp_fill_max=None, interp_no_rotate=False)
 
     def __init__(self, **flags):
@@ -681,6 +681,7 @@ def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
     _validate_roughness_flags(a.topog_roughness, a.topog_source)
     _validate_remap_flags(a.remap_source, a.remap_var)
     _validate_runoff_flags(a.runoff_source, a.runoff_var, a.topog_source, a.runoff_targets, skip_metrics)
+    _validate_coast_distance_flags(a.coast_distance_file, a.coast_distance_sides, a.topog_source)
     _validate_frac_flags(a.xgrid_frac_file, a.xgrid_atm)
     _validate_interp_flags(a.interp_source, a.interp_var, a.interp_vector, a.interp_points, skip_metrics, a.interp_no_fill,
                            a.interp_fill_max, a.interp_no_rotate)
@@ -697,7 +698,7 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None,
          runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None,
          interp_source=None, interp_var=None, interp_vector=None, interp_points="h", interp_file="interp.nc", interp_no_fill=False,
-         interp_fill_max=None, interp_no_rotate=False, topog_roughness=False):
+         interp_fill_max=None, interp_no_rotate=False, topog_roughness=False, coast_distance_file=None, coast_distance_sides="both"):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -732,7 +733,10 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     bilinearly between the source's cell centres at the ``interp_points`` of the grid (bilinear.py; h, u, v, or c: a vector's first
     component at u and its second at v), vectors turned to the grid's directions with angle_dx unless ``interp_no_rotate``; at the h
     points the wet set is the remap's and the wet points the source leaves empty are filled unless ``interp_no_fill``, at most
-    ``interp_fill_max`` cells away; written to ``interp_file``; also an addition."""
+    ``interp_fill_max`` cells away; written to ``interp_file``; also an addition.  ``coast_distance_file`` (--coast_distance_file FILE,
+    needs ``topog_source``): for every wet cell of the topography the distance to the nearest coastal land cell, and for every land
+    cell to the nearest coastal wet cell (coast_distance.py; ``coast_distance_sides``: wet, land or both; the edited wet set with
+    ``ocean_mask_file``), written to FILE; also an addition."""
     flags = dict(locals())   # the arguments, by name: taken before anything else is bound
     import time
 
@@ -1057,7 +1061,7 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
 
 def _run_analyses(a, g, cut=None):
     """The analyses that follow the grid (``a``: AnalysisFlags), each printed and written as it is done, in their one order: quality
-    report, topography and ocean mask, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
+    report, topography and ocean mask, distance to the coast, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
     Supergrid with its ``cut`` (main) or the _StitchedArrays of main_function_level."""
     if a.quality_report:
         _write_quality_report(g.quality(cut), a.quality_report)
@@ -1069,6 +1073,8 @@ def _run_analyses(a, g, cut=None):
             mask = g.ocean_mask(cut, topo, **_mask_args(a.mask_min_depth, a.mask_deepen, a.mask_seed, a.mask_keep_cells))
         topo = _write_topog_and_mask(topo, mask, a.topog_file, a.ocean_mask_file)
     wet = _xgrid_mask(topo)   # of the topography as written: the wet set of everything below
+    if a.coast_distance_file:
+        _write_coast_distance(g.coast_distance(cut, wet, sides=a.coast_distance_sides), a.coast_distance_file)
     if a.xgrid_atm is not None:
         from . import exchange_grid as X
         xres = g.exchange_grid(cut, X.regular_atm(*a.xgrid_atm), mask=wet)
@@ -1127,6 +1133,10 @@ class _StitchedArrays(object):
     def runoff(self, cut, source, wet, targets="coast"):
         from . import runoff as RO
         return RO.runoff(self.x, self.y, self.metrics[2], source, wet, targets=targets, Re=_default_Re)
+
+    def coast_distance(self, cut, wet, sides="both"):
+        from . import coast_distance as CD
+        return CD.coast_distance(self.x, self.y, wet, sides=sides, Re=_default_Re)
 
     def bilinear(self, cut, source, source2=None, **args):
         from . import bilinear as B
@@ -1193,6 +1203,26 @@ def _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targe
         raise ValueError("--runoff_source needs --topog_source: the runoff goes to the wet cells of the topography")
     if runoff_targets not in ("coast", "wet"):
         raise ValueError("--runoff_targets must be coast or wet, not %r" % (runoff_targets,))
+
+
+def _validate_coast_distance_flags(coast_distance_file, coast_distance_sides, topog_source):
+    if coast_distance_sides not in ("wet", "land", "both"):
+        raise ValueError("--coast_distance_sides must be wet, land or both, not %r" % (coast_distance_sides,))
+    if not coast_distance_file:
+        if coast_distance_sides != "both":
+            raise ValueError("--coast_distance_sides needs --coast_distance_file")
+        return
+    if topog_source is None:
+        raise ValueError("--coast_distance_file needs --topog_source: the coast is that of the topography's wet cells")
+
+
+def _write_coast_distance(res, fnam):
+    if res is None:   # not rank 0
+        return
+    from . import coast_distance as CD
+    for line in CD.summary_lines(res):
+        print(line)
+    CD.write_coast_distance(str(fnam), res)
 
 
 def _validate_interp_flags(interp_source, interp_var, interp_vector, interp_points, skip_metrics, no_fill=False, fill_max=None,
@@ -1378,6 +1408,11 @@ def build_parser():
     parser.add_argument("--runoff_file", type=str, required=False, default="runoff.nc", help="runoff output file, default runoff.nc")
     parser.add_argument("--runoff_targets", type=str, choices=["coast", "wet"], required=False, default="coast",
                         help="coast (default): wet cells next to land; wet: every wet cell")
+    parser.add_argument("--coast_distance_file", type=str, required=False, default=None,
+                        help="write the distance of every model cell to the nearest cell across the coast of the --topog_source "
+                             "topography (the --ocean_mask_file mask when given) to this file")
+    parser.add_argument("--coast_distance_sides", type=str, choices=["wet", "land", "both"], required=False, default="both",
+                        help="the cells that get a distance: wet, land or both (default)")
     parser.add_argument("--xgrid_frac_file", type=str, required=False, default=None,
                         help="write the ocean / land fraction, area and exchange-cell count of every --xgrid_atm atmosphere cell to this "
                              "file (wet cells only when --topog_source is given)")

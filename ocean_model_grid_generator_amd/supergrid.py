@@ -1602,6 +1602,17 @@ class Supergrid(object):
             return None
         return RO.runoff_dev(xy[0], xy[1], area, source, wet, targets=targets, Re=float(self.plan.Re))
 
+    # -- distance to the coast ----------------------------------------------------------------------------------------
+    def coast_distance(self, cut, wet, sides="both"):
+        """The distance to the coast (coast_distance.result on rank 0, None on the other ranks) of the model cells of the stitched grid
+        with the wet set ``wet`` (one value per model cell, 0: land), on rank 0's GPU with the stitched points gathered there, as
+        runoff does: the same bits for any number of ranks by construction."""
+        from . import coast_distance as CD
+        xy = self.stitched_xy(cut)
+        if xy is None:
+            return None
+        return CD.coast_distance_dev(xy[0], xy[1], wet, sides=sides, Re=float(self.plan.Re))
+
     # -- bilinear interpolation ---------------------------------------------------------------------------------------
     def stitched_angle(self, cut):
         """The stitched angle_dx ((nyp, nxp) float64 device tensor) on rank 0's device, None on the other ranks (_stitched)."""
