@@ -1120,6 +1120,89 @@ int ogg_coast_search_dev(const ogg_coast_params* p, const unsigned char* flags, 
 int ogg_coast_distance(const ogg_coast_params* p, const double* x, const double* y, const unsigned char* wet, int* nearest, double* d2,
                        unsigned char* flags, ogg_coast_counts* counts);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Basin codes (an addition: the reference has none).  The integer basin of every wet model cell (Southern Ocean, Atlantic, Pacific,
+ * ...), as MOM6 set-ups keep it in basin_codes.nc for transports by basin, regional restoring and analysis masks: an ordered list
+ * of seeded floods, each confined to a longitude / latitude box, later floods taking only what earlier ones left.
+ *   cells    the ocean mask's: ny x nx model cells, c = j * nx + i, ny * nx < 2^31; faces (j, i) ~ (j, i+1) and (j, i) ~ (j+1, i),
+ *            with OGG_MASK_PERIODIC (j, nx-1) ~ (j, 0), with OGG_MASK_FOLD (ny-1, i) ~ (ny-1, nx-1-i); diagonal neighbours are not
+ *            connected.  The centre of a cell is supergrid point (2j+1, 2i+1); a cell is VALID when both centre coordinates are
+ *            finite.  wet: one byte per cell, non-zero wet.
+ *   rules    K of them in order, 1 <= K <= OGG_BASIN_MAX_RULES; rule k = (code, seed_lon, seed_lat, lon_w, lon_e, lat_s, lat_n) with
+ *            1 <= code <= 255 (several rules may share a code: an ocean usually needs several floods), -90 <= lat_s <= lat_n <= 90,
+ *            0 < lon_e - lon_w <= 360, every value finite, and the seed in its own box by the predicate below (OGG_EARG names the
+ *            rule otherwise).
+ *   in the box  a valid centre (lon, lat) is in box k when lat_s <= lat <= lat_n and, with W = lon_e - lon_w, t = lon - lon_w and
+ *            t = t - 360.0 * floor(t / 360.0): W == 360 or t <= W.  The operations are evaluated in exactly this order, each rounded
+ *            on its own (no FMA), so the same bits come out of numpy.  Both edges belong to the box, and so does a centre stated any
+ *            number of whole turns away.  A t that rounds to exactly 360.0 (lon a hair west of lon_w) is in the box only when
+ *            W == 360.
+ *   seed cell  of rule k: the valid cell whose centre is nearest to the seed by the key (bits of d2, c), d2 = dist2(u_c, u_seed) of
+ *            "Runoff mapping" (unit vectors (cos lat cos lon, cos lat sin lon, sin lat), lon, lat * (pi / 180); d2 = (dx * dx + dy *
+ *            dy) + dz * dz): ties to the smaller index.  It is the cell ogg_mask_seed_dev names, with the same d2 bits.  Invalid
+ *            cells are no candidates.  A seed whose d2 is larger than seed_max_d2 (+inf: off) is OFF THE GRID.
+ *   order    before rule k, code[c] = 0 for every cell that no earlier rule took.  E_k: the cells that are wet, valid, uncoded and in
+ *            box k.  If the seed cell is in E_k, its connected component inside E_k through the faces above gets code_k and rule[c]
+ *            = k.  Otherwise the rule takes nothing, which is no error (a coarse or regional grid may have no Black Sea), and its
+ *            status says why, the first of these that holds: OGG_BASIN_SEED_INVALID (5) the grid has no valid cell, so there is no
+ *            seed cell (seed_cell -1, d2 +inf); OGG_BASIN_SEED_OFF_GRID (4); OGG_BASIN_SEED_LAND (1) the seed cell is not wet;
+ *            OGG_BASIN_SEED_OUTSIDE (2) its centre is outside box k; OGG_BASIN_SEED_CODED (3) rule blocking_rule took it before.
+ *            OGG_BASIN_TOOK (0): the rule took cells.
+ *   outputs  code (ny, nx) uint8, 0 for land and for wet cells no rule took; rule (ny, nx) int16, -1 where code is 0; one record per
+ *            rule; the counts.
+ * Everything is an integer: no launch geometry or knob changes a bit.  Consecutive rules whose boxes are pairwise disjoint run as one
+ * pass of at most OGG_BASIN_MAX_PASS_RULES rules; two boxes count as disjoint only when their latitude intervals or their longitude
+ * arcs are separated by more than 1e-9 degrees.  OGG_BASIN_BATCH=0 gives one rule per pass; OGG_BASIN_TILE_ROWS (1 .. 64, default 32)
+ * the rows of a labelling tile.
+ * ---------------------------------------------------------------------------------------------------- */
+#define OGG_BASIN_MAX_RULES 4096
+#define OGG_BASIN_MAX_PASS_RULES 255
+enum { OGG_BASIN_PARAMS = 0, OGG_BASIN_RULE = 1, OGG_BASIN_RECORD = 2, OGG_BASIN_COUNTS = 3 };
+enum { OGG_BASIN_TOOK = 0, OGG_BASIN_SEED_LAND = 1, OGG_BASIN_SEED_OUTSIDE = 2, OGG_BASIN_SEED_CODED = 3, OGG_BASIN_SEED_OFF_GRID = 4,
+       OGG_BASIN_SEED_INVALID = 5 };
+typedef struct ogg_basin_params {
+    long ny, nx;               /* model cells */
+    int topology;              /* OGG_MASK_PERIODIC | OGG_MASK_FOLD */
+    int n_rules;               /* K */
+    double seed_max_d2;        /* squared chord beyond which a seed is off the grid; +inf: off */
+} ogg_basin_params;
+typedef struct ogg_basin_rule {
+    int code;                  /* 1 .. 255 */
+    int reserved;              /* not read */
+    double seed_lon, seed_lat; /* degrees */
+    double lon_w, lon_e;       /* 0 < lon_e - lon_w <= 360 */
+    double lat_s, lat_n;
+} ogg_basin_rule;
+typedef struct ogg_basin_rule_record {
+    long long seed_cell;       /* -1 when the grid has no valid cell */
+    long long d2_bits;         /* the bits of the squared chord from the seed to the seed cell's centre */
+    int status;                /* OGG_BASIN_TOOK ... OGG_BASIN_SEED_INVALID */
+    int blocking_rule;         /* with OGG_BASIN_SEED_CODED the rule that took the seed cell, else -1 */
+    long long cells;           /* cells taken */
+} ogg_basin_rule_record;
+typedef struct ogg_basin_counts {
+    long long wet;             /* cells with a non-zero wet byte */
+    long long coded;           /* cells some rule took */
+    long long uncoded;         /* wet - coded */
+    long long passes;          /* passes run */
+} ogg_basin_counts;
+long ogg_basin_struct_bytes(int which);                      /* sizeof of OGG_BASIN_PARAMS / RULE / RECORD / COUNTS, -1 otherwise */
+long ogg_basin_workspace_bytes(const ogg_basin_params* p);   /* -1 on a bad *p */
+/* the checks of *p and of the n_rules rules (HOST memory): OGG_EARG with the reason, before any device work */
+int ogg_basin_check(const ogg_basin_params* p, const ogg_basin_rule* rules);
+/* the passes the call would run (host only): pass q holds the rules pass_start[q] .. pass_start[q + 1] - 1; pass_start has room for
+ * n_rules + 1 entries */
+int ogg_basin_plan(const ogg_basin_params* p, const ogg_basin_rule* rules, int* pass_start, int* n_passes);
+/* device pointers, on a stream, without a host round trip between the passes: rules in HOST memory (checked and planned there) and
+ * rules_dev the same n_rules rules in device memory; x, y the supergrid points (2 ny + 1 rows of ld doubles); wet, code (ny * nx
+ * bytes), rule (ny * nx int16), records (n_rules) and *counts in device memory. */
+int ogg_basin_codes_dev(const ogg_basin_params* p, const ogg_basin_rule* rules, const ogg_basin_rule* rules_dev, const double* x,
+                        const double* y, long ld, const unsigned char* wet, void* workspace, long workspace_bytes, unsigned char* code,
+                        short* rule, ogg_basin_rule_record* records, ogg_basin_counts* counts, void* stream);
+/* HOST pointers throughout, staged through device memory: x, y (2 ny + 1) x (2 nx + 1) */
+int ogg_basin_codes(const ogg_basin_params* p, const ogg_basin_rule* rules, const double* x, const double* y, const unsigned char* wet,
+                    unsigned char* code, short* rule, ogg_basin_rule_record* records, ogg_basin_counts* counts);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

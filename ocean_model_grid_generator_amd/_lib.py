@@ -196,6 +196,28 @@ COAST_F_WET, COAST_F_COAST, COAST_F_VALID = 1, 2, 4                    # the bit
 COAST_MAX_CUBES = 128                                                  # OGG_COAST_MAX_CUBES
 
 
+class BasinParams(ctypes.Structure):
+    """ogg_basin_params of include/ogg_hip.h"""
+    _fields_ = [("ny", c_long), ("nx", c_long), ("topology", c_int), ("n_rules", c_int), ("seed_max_d2", c_double)]
+
+
+BASIN_COUNT_FIELDS = ("wet", "coded", "uncoded", "passes")
+
+
+class BasinCounts(ctypes.Structure):
+    """ogg_basin_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in BASIN_COUNT_FIELDS]
+
+
+# ogg_basin_rule and ogg_basin_rule_record as numpy records (56 and 32 bytes)
+BASIN_RULE = np.dtype([("code", "<i4"), ("reserved", "<i4"), ("seed_lon", "<f8"), ("seed_lat", "<f8"), ("lon_w", "<f8"), ("lon_e", "<f8"),
+                       ("lat_s", "<f8"), ("lat_n", "<f8")])
+BASIN_RECORD = np.dtype([("seed_cell", "<i8"), ("d2_bits", "<i8"), ("status", "<i4"), ("blocking_rule", "<i4"), ("cells", "<i8")])
+BASIN_PARAMS, BASIN_RULE_STRUCT, BASIN_RECORD_STRUCT, BASIN_COUNTS = 0, 1, 2, 3   # OGG_BASIN_PARAMS ... OGG_BASIN_COUNTS
+BASIN_MAX_RULES, BASIN_MAX_PASS_RULES = 4096, 255                      # OGG_BASIN_MAX_RULES, OGG_BASIN_MAX_PASS_RULES
+BASIN_TOOK, BASIN_SEED_LAND, BASIN_SEED_OUTSIDE, BASIN_SEED_CODED, BASIN_SEED_OFF_GRID, BASIN_SEED_INVALID = range(6)   # OGG_BASIN_TOOK ...
+
+
 class RegridParams(ctypes.Structure):
     """ogg_regrid_params of include/ogg_hip.h"""
     _fields_ = [("ny", c_long), ("nx", c_long), ("NA", c_long), ("NB", c_long), ("nrec", c_long), ("dtype", c_int), ("n_fill", c_int),
@@ -376,6 +398,12 @@ SIGNATURES = {
                              c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_coast_distance": [ctypes.POINTER(CoastParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            ctypes.POINTER(CoastCounts)],
+    "ogg_basin_check": [ctypes.POINTER(BasinParams), c_void_p],
+    "ogg_basin_plan": [ctypes.POINTER(BasinParams), c_void_p, c_void_p, ctypes.POINTER(c_int)],
+    "ogg_basin_codes_dev": [ctypes.POINTER(BasinParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_basin_codes": [ctypes.POINTER(BasinParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                        ctypes.POINTER(BasinCounts)],
     "ogg_regrid_check": [ctypes.POINTER(RegridParams)],
     "ogg_regrid_transpose_dev": [ctypes.POINTER(RegridParams), c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p],
     "ogg_regrid_dev": [ctypes.POINTER(RegridParams), c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -423,6 +451,8 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],
                 "ogg_coast_struct_bytes": [c_int],
                 "ogg_coast_workspace_bytes": [ctypes.POINTER(CoastParams)],
+                "ogg_basin_struct_bytes": [c_int],
+                "ogg_basin_workspace_bytes": [ctypes.POINTER(BasinParams)],
                 "ogg_regrid_struct_bytes": [c_int],
                 "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long],
                 "ogg_bilinear_struct_bytes": []}

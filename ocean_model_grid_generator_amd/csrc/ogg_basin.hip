@@ -1,0 +1,583 @@
+// Basin codes: ordered seeded floods of the wet cells (include/ogg_hip.h, "Basin codes").  Rule k floods, from its seed cell, the
+// cells that are wet, valid, not yet coded and inside its longitude / latitude box.  A flood is a connected component under a per-cell
+// class, so the floods run on the ocean mask's union-find (ogg_unionfind.h) and the launches of a call do not grow with a basin's
+// diameter.  Consecutive rules whose boxes are pairwise disjoint cannot see each other's cells and run as ONE pass (planned on the
+// host); every pass is five launches on the caller's stream, and nothing comes back to the host between passes:
+//
+// basin_unit_kernel      once: the unit vector of every cell centre (NaN for an invalid centre), code = 0 and rule = -1 everywhere,
+//                        and the wet count.
+// basin_seed_kernel      once: the seed cell of every rule, the valid cell with the smallest (bits of dist2, cell).  A wavefront lane
+//                        is a rule, the cells stream through LDS, every lane tests every cell: three subtractions and three products
+//                        per test, no sin / cos beyond the seed's own.  One partial result per (block, rule), reduced by
+// basin_seed_reduce_kernel  into the rule records.
+// basin_tile_kernel      per pass, one workgroup per tile of TW x th cells: the class byte of every cell (the index inside the pass of
+//                        the rule whose box holds it if the cell is wet, valid and uncoded; 255 otherwise), then the union-find in LDS
+//                        over the faces inside the tile between cells of EQUAL class; a tile without an eligible cell leaves after
+//                        writing its parents.
+// basin_merge_kernel     one thread per face across a tile edge, the seam or the fold: the same union on the global parents.
+// basin_flatten_kernel   root[c] = find(c), the smallest index of the cell's component.
+// basin_seedroot_kernel  one thread per rule of the pass: the status of the rule, and the root of its seed cell if it floods.
+// basin_assign_kernel    every cell whose root is the kept root of its class's rule gets that rule's code and index; the cells taken
+//                        are counted per wavefront and class, then in LDS, then one atomicAdd per block and rule.
+//
+// Every result is an integer, and the key of the seed search is total, so nothing depends on the launch geometry.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "ogg_blocks.h"
+#include "ogg_common.h"
+#include "ogg_sphere.h"
+#include "ogg_unionfind.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using ogg::at;
+using ogg::grid_for;
+using ogg::knob;
+using ogg::round256;
+
+constexpr int TW = 64;             // tile width: one wavefront across a tile row
+constexpr int NT = 256;            // threads per workgroup
+constexpr int TH_DEFAULT = 32;     // tile rows (OGG_BASIN_TILE_ROWS), the ocean mask's
+constexpr int TH_MAX = 64;
+constexpr int NONE = 255;          // the class of a cell that no rule of the pass can take
+constexpr int PASS_MAX = OGG_BASIN_MAX_PASS_RULES;
+constexpr long SEED_BLOCKS = 1024; // workgroups of the seed search, over cells and groups of 64 rules
+constexpr double SEPARATION = 1.0e-9;   // degrees: two boxes closer than this are not disjoint for the planner
+
+static_assert(NT == BLOCKS_NT, "block_add sums over a workgroup of BLOCKS_NT threads");
+static_assert(PASS_MAX < NONE + 1 && PASS_MAX <= NT, "a class is a byte, and a thread per rule of a pass");
+static_assert(sizeof(ogg_basin_params) == 32, "ogg_basin_params layout");
+static_assert(sizeof(ogg_basin_rule) == 56, "ogg_basin_rule layout");
+static_assert(sizeof(ogg_basin_rule_record) == 32, "ogg_basin_rule_record layout");
+static_assert(sizeof(ogg_basin_counts) == 32, "ogg_basin_counts layout");
+
+// ---- the box predicate: host and device, one rounding order --------------------------------------------------------
+__host__ __device__ inline bool in_box(double lon, double lat, double lon_w, double W, double lat_s, double lat_n) {
+    if (!(lat_s <= lat && lat <= lat_n)) return false;
+    double t = lon - lon_w;
+    t = t - 360.0 * floor(t / 360.0);
+    return W == 360.0 || t <= W;
+}
+
+struct Grid {
+    long ny, nx;
+    int th, nbx;
+};
+
+struct Pass {
+    int r0, nr;   // the rules r0 .. r0 + nr - 1
+};
+
+// ---- once per call ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NT) void basin_unit_kernel(long ny, long nx, const double* __restrict__ x, const double* __restrict__ y,
+                                                        long ld, const unsigned char* __restrict__ wet, double* __restrict__ u,
+                                                        unsigned char* __restrict__ code, short* __restrict__ rule,
+                                                        ogg_basin_counts* counts) {
+    const long n = ny * nx;
+    long long v[1] = {0};
+    for (long c = (long)blockIdx.x * NT + threadIdx.x; c < n; c += (long)gridDim.x * NT) {
+        const long j = c / nx, i = c % nx, k = (2 * j + 1) * ld + 2 * i + 1;
+        const double lon = x[k], lat = y[k];
+        double t[3] = {NAN, NAN, NAN};
+        if (isfinite(lon) && isfinite(lat)) unit(lon, lat, t);
+        u[3 * c] = t[0];
+        u[3 * c + 1] = t[1];
+        u[3 * c + 2] = t[2];
+        code[c] = 0;
+        rule[c] = -1;
+        v[0] += wet[c] != 0;
+    }
+    long long* const dst[1] = {&counts->wet};
+    block_add<1>(v, dst);
+}
+
+// part[(b * K + s) * 2 ..]: the smallest (d2 bits, cell) of rule s over the cells of block column b
+__global__ __launch_bounds__(NT) void basin_seed_kernel(long n, const double* __restrict__ u, int K, const ogg_basin_rule* __restrict__ rules,
+                                                        unsigned long long* __restrict__ part) {
+    __shared__ double cu[3][NT];
+    __shared__ unsigned long long wb[NT / 64][64];
+    __shared__ int wc[NT / 64][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x / 64;
+    const int s = blockIdx.y * 64 + lane;
+    double su[3] = {0.0, 0.0, 0.0};
+    if (s < K) unit(rules[s].seed_lon, rules[s].seed_lat, su);
+    unsigned long long best = ULLONG_MAX;
+    int bc = INT_MAX;
+    for (long base = (long)blockIdx.x * NT; base < n; base += (long)gridDim.x * NT) {
+        __syncthreads();   // the chunk before this one has been read
+        const long c = base + threadIdx.x;
+        cu[0][threadIdx.x] = c < n ? u[3 * c] : NAN;
+        cu[1][threadIdx.x] = c < n ? u[3 * c + 1] : NAN;
+        cu[2][threadIdx.x] = c < n ? u[3 * c + 2] : NAN;
+        __syncthreads();
+        for (int k = 0; k < 64; ++k) {   // this wavefront's 64 cells of the chunk, in ascending order
+            const int q = w * 64 + k;
+            const double ax = cu[0][q];
+            if (ax != ax) continue;   // an invalid centre (or past the end) is no candidate; the same for every lane
+            const unsigned long long b = bits_of(dist2(ax, cu[1][q], cu[2][q], su[0], su[1], su[2]));
+            const int cc = (int)(base + q);
+            if (b < best || (b == best && cc < bc)) best = b, bc = cc;
+        }
+    }
+    wb[w][lane] = best;
+    wc[w][lane] = bc;
+    __syncthreads();
+    if (w == 0 && s < K) {
+        for (int v = 1; v < NT / 64; ++v)
+            if (wb[v][lane] < best || (wb[v][lane] == best && wc[v][lane] < bc)) best = wb[v][lane], bc = wc[v][lane];
+        part[((long)blockIdx.x * K + s) * 2] = best;
+        part[((long)blockIdx.x * K + s) * 2 + 1] = (unsigned long long)(unsigned)bc;
+    }
+}
+
+__global__ __launch_bounds__(NT) void basin_seed_reduce_kernel(int K, int nparts, const unsigned long long* __restrict__ part,
+                                                               ogg_basin_rule_record* __restrict__ rec) {
+    const int s = blockIdx.x * NT + threadIdx.x;
+    if (s >= K) return;
+    unsigned long long best = ULLONG_MAX;
+    int bc = INT_MAX;
+    for (int b = 0; b < nparts; ++b) {
+        const unsigned long long v = part[((long)b * K + s) * 2];
+        const int cc = (int)(unsigned)part[((long)b * K + s) * 2 + 1];
+        if (v < best || (v == best && cc < bc)) best = v, bc = cc;
+    }
+    const bool found = bc != INT_MAX;
+    rec[s].seed_cell = found ? bc : -1;
+    rec[s].d2_bits = found ? (long long)best : (long long)bits_of(INFINITY);
+    rec[s].status = OGG_BASIN_TOOK;
+    rec[s].blocking_rule = -1;
+    rec[s].cells = 0;
+}
+
+// ---- per pass: classes and the tile-local labelling ----------------------------------------------------------------
+// the boxes of the pass's rules in LDS: lon_w, W = lon_e - lon_w, lat_s, lat_n
+__device__ inline void load_boxes(const Pass& ps, const ogg_basin_rule* __restrict__ rules, double (*box)[4]) {
+    for (int r = threadIdx.x; r < ps.nr; r += NT) {
+        const ogg_basin_rule q = rules[ps.r0 + r];
+        box[r][0] = q.lon_w;
+        box[r][1] = q.lon_e - q.lon_w;
+        box[r][2] = q.lat_s;
+        box[r][3] = q.lat_n;
+    }
+}
+
+__global__ __launch_bounds__(NT) void basin_tile_kernel(Grid g, Pass ps, const ogg_basin_rule* __restrict__ rules,
+                                                        const double* __restrict__ x, const double* __restrict__ y, long ld,
+                                                        const unsigned char* __restrict__ wet, const unsigned char* __restrict__ code,
+                                                        unsigned char* __restrict__ cls, int* par) {
+    extern __shared__ int lab[];                 // TW * th parents, then TW * th class bytes
+    __shared__ double box[PASS_MAX][4];
+    const int n = TW * g.th;
+    unsigned char* lc = reinterpret_cast<unsigned char*>(lab + n);
+    const long i0 = (long)(blockIdx.x % g.nbx) * TW, j0 = (long)(blockIdx.x / g.nbx) * g.th;
+    load_boxes(ps, rules, box);
+    __syncthreads();
+    int any = 0;
+    for (int l = threadIdx.x; l < n; l += NT) {
+        const long j = j0 + l / TW, i = i0 + l % TW;
+        int k = NONE;
+        if (j < g.ny && i < g.nx) {
+            const long c = j * g.nx + i;
+            if (wet[c] != 0 && code[c] == 0) {
+                const long q = (2 * j + 1) * ld + 2 * i + 1;
+                const double lon = x[q], lat = y[q];
+                if (isfinite(lon) && isfinite(lat))
+                    for (int r = 0; r < ps.nr; ++r)
+                        if (in_box(lon, lat, box[r][0], box[r][1], box[r][2], box[r][3])) {
+                            k = r;   // the first rule of the pass whose box holds the cell
+                            break;
+                        }
+            }
+            cls[c] = (unsigned char)k;
+        }
+        lc[l] = (unsigned char)k;
+        lab[l] = k != NONE ? l : -1;
+        any |= k != NONE;
+    }
+    if (__syncthreads_or(any) == 0) {   // nothing to flood in this tile
+        for (int l = threadIdx.x; l < n; l += NT) {
+            const long j = j0 + l / TW, i = i0 + l % TW;
+            if (j < g.ny && i < g.nx) par[j * g.nx + i] = -1;
+        }
+        return;
+    }
+    for (int l = threadIdx.x; l < n; l += NT) {
+        const int k = lc[l];
+        if (k == NONE) continue;
+        const int tx = l % TW, ty = l / TW;
+        if (tx + 1 < TW && lc[l + 1] == k) lds_unite(lab, l, l + 1);
+        if (ty + 1 < g.th && lc[l + TW] == k) lds_unite(lab, l, l + TW);
+    }
+    __syncthreads();
+    for (int l = threadIdx.x; l < n; l += NT) {
+        const long j = j0 + l / TW, i = i0 + l % TW;
+        if (j >= g.ny || i >= g.nx) continue;
+        int p = -1;
+        if (lc[l] != NONE) {
+            const int r = lds_find(lab, l);
+            p = (int)((j0 + r / TW) * g.nx + i0 + r % TW);
+        }
+        par[j * g.nx + i] = p;
+    }
+}
+
+// ---- merge across tile edges, the seam and the fold ----------------------------------------------------------------
+struct Faces {
+    long ny, nx;
+    int th;
+    long n_v, n_h, n_p, n_f;   // faces across vertical tile edges, horizontal tile edges, the seam, the fold
+};
+
+__global__ __launch_bounds__(NT) void basin_merge_kernel(Faces f, const unsigned char* __restrict__ cls, int* par) {
+    const long total = f.n_v + f.n_h + f.n_p + f.n_f;
+    for (long t = (long)blockIdx.x * NT + threadIdx.x; t < total; t += (long)gridDim.x * NT) {
+        long a, b, u = t;
+        if (u < f.n_v) {   // (j, i - 1) ~ (j, i), i = (k + 1) * TW
+            const long k = u / f.ny, j = u % f.ny;
+            a = j * f.nx + (k + 1) * TW - 1;
+            b = a + 1;
+        } else if ((u -= f.n_v) < f.n_h) {   // (j - 1, i) ~ (j, i), j = (k + 1) * th
+            const long k = u / f.nx, i = u % f.nx;
+            a = ((k + 1) * f.th - 1) * f.nx + i;
+            b = a + f.nx;
+        } else if ((u -= f.n_h) < f.n_p) {   // (j, nx - 1) ~ (j, 0)
+            a = u * f.nx + f.nx - 1;
+            b = u * f.nx;
+        } else {   // (ny - 1, i) ~ (ny - 1, nx - 1 - i), i < nx - 1 - i
+            u -= f.n_p;
+            a = (f.ny - 1) * f.nx + u;
+            b = (f.ny - 1) * f.nx + f.nx - 1 - u;
+        }
+        const int k = cls[a];
+        if (k != NONE && k == cls[b]) glb_unite(par, (int)a, (int)b);   // equal classes only
+    }
+}
+
+// ---- flatten -------------------------------------------------------------------------------------------------------
+// As the ocean mask's, without the cells per root: the tile's parents go to LDS, every cell follows them inside the tile to its
+// representative, and only the representatives walk the global chains.
+__global__ __launch_bounds__(NT) void basin_flatten_kernel(Grid g, int* par, int* __restrict__ root) {
+    extern __shared__ int sh[];
+    const int n = TW * g.th;
+    int* lp = sh;       // the parent of each tile cell as a tile-local index, -1 outside the tile, -2 for no class / off the grid
+    int* rt = sh + n;   // the root of each representative
+    const long i0 = (long)(blockIdx.x % g.nbx) * TW, j0 = (long)(blockIdx.x / g.nbx) * g.th;
+    int any = 0;
+    for (int l = threadIdx.x; l < n; l += NT) {
+        const long j = j0 + l / TW, i = i0 + l % TW;
+        int v = -2;
+        if (j < g.ny && i < g.nx) {
+            const int p = glb_load(&par[j * g.nx + i]);   // (another tile's walk may halve it: any value read is an ancestor)
+            if (p >= 0) {
+                const long pj = p / g.nx, pi = p % g.nx;
+                v = (pj >= j0 && pj < j0 + g.th && pi >= i0 && pi < i0 + TW) ? (int)((pj - j0) * TW + (pi - i0)) : -1;
+                if (v == l) v = -1;   // a root: its own representative
+            }
+        }
+        lp[l] = v;
+        any |= v != -2;
+    }
+    if (__syncthreads_or(any) == 0) {
+        for (int l = threadIdx.x; l < n; l += NT) {
+            const long j = j0 + l / TW, i = i0 + l % TW;
+            if (j < g.ny && i < g.nx) root[j * g.nx + i] = -1;
+        }
+        return;
+    }
+    for (int l = threadIdx.x; l < n; l += NT)
+        if (lp[l] == -1) rt[l] = glb_find_halving(par, (int)((j0 + l / TW) * g.nx + i0 + l % TW));
+    __syncthreads();
+    for (int l = threadIdx.x; l < n; l += NT) {
+        const long j = j0 + l / TW, i = i0 + l % TW;
+        if (j >= g.ny || i >= g.nx) continue;
+        int r = -1;
+        if (lp[l] != -2) {
+            int q = l;
+            while (lp[q] >= 0) q = lp[q];   // in-tile parents have smaller local indices: this ends
+            r = rt[q];
+        }
+        root[j * g.nx + i] = r;
+    }
+}
+
+// ---- seed roots and the assignment ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(NT) void basin_seedroot_kernel(long nx, Pass ps, double seed_max_d2, const ogg_basin_rule* __restrict__ rules,
+                                                            const double* __restrict__ x, const double* __restrict__ y, long ld,
+                                                            const unsigned char* __restrict__ wet, const unsigned char* __restrict__ code,
+                                                            const short* __restrict__ rule, const int* __restrict__ root,
+                                                            ogg_basin_rule_record* __restrict__ rec, int* __restrict__ keep) {
+    const int r = threadIdx.x;
+    if (r >= ps.nr) return;
+    const int k = ps.r0 + r;
+    const long long sc = rec[k].seed_cell;
+    int status = OGG_BASIN_TOOK, blocking = -1, kept = -1;
+    if (sc < 0) {
+        status = OGG_BASIN_SEED_INVALID;
+    } else {
+        double d2;
+        const long long b = rec[k].d2_bits;
+        memcpy(&d2, &b, 8);
+        const long j = sc / nx, i = sc % nx, q = (2 * j + 1) * ld + 2 * i + 1;
+        const ogg_basin_rule w = rules[k];
+        if (d2 > seed_max_d2)
+            status = OGG_BASIN_SEED_OFF_GRID;
+        else if (wet[sc] == 0)
+            status = OGG_BASIN_SEED_LAND;
+        else if (!in_box(x[q], y[q], w.lon_w, w.lon_e - w.lon_w, w.lat_s, w.lat_n))
+            status = OGG_BASIN_SEED_OUTSIDE;
+        else if (code[sc] != 0)
+            status = OGG_BASIN_SEED_CODED, blocking = rule[sc];
+        else
+            kept = root[sc];
+    }
+    rec[k].status = status;
+    rec[k].blocking_rule = blocking;
+    keep[r] = kept;
+}
+
+__global__ __launch_bounds__(NT) void basin_assign_kernel(long n, Pass ps, const ogg_basin_rule* __restrict__ rules,
+                                                          const unsigned char* __restrict__ cls, const int* __restrict__ root,
+                                                          const int* __restrict__ keep, unsigned char* __restrict__ code,
+                                                          short* __restrict__ rule, ogg_basin_rule_record* rec, ogg_basin_counts* counts) {
+    __shared__ int kp[NT], kc[NT], cnt[NT];
+    kp[threadIdx.x] = (int)threadIdx.x < ps.nr ? keep[threadIdx.x] : -1;
+    kc[threadIdx.x] = (int)threadIdx.x < ps.nr ? rules[ps.r0 + threadIdx.x].code : 0;
+    cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    long long v[1] = {0};
+    for (long base = (long)blockIdx.x * NT; base < n; base += (long)gridDim.x * NT) {   // the same trip count for every thread
+        const long c = base + threadIdx.x;
+        const int k = c < n ? cls[c] : NONE;
+        const bool take = k != NONE && kp[k] >= 0 && root[c] == kp[k];
+        if (take) {
+            code[c] = (unsigned char)kc[k];
+            rule[c] = (short)(ps.r0 + k);
+        }
+        v[0] += take;
+        unsigned long long m = __ballot(take);
+        while (m) {   // one LDS add per wavefront and class met
+            const int lead = __ffsll((long long)m) - 1;
+            const int kl = __shfl(k, lead, 64);
+            const unsigned long long same = __ballot(take && k == kl);
+            if (lane == lead) atomicAdd(&cnt[kl], __popcll(same));
+            m &= ~same;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < ps.nr && cnt[threadIdx.x] > 0)
+        atomicAdd(ull(&rec[ps.r0 + threadIdx.x].cells), (unsigned long long)cnt[threadIdx.x]);   // one add per block and rule
+    long long* const dst[1] = {&counts->coded};
+    block_add<1>(v, dst);
+}
+
+__global__ void basin_finish_kernel(ogg_basin_counts* counts, long long passes) {
+    counts->uncoded = counts->wet - counts->coded;
+    counts->passes = passes;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+int check_params(const ogg_basin_params* p) {
+    OGG_REQUIRE(p, OGG_EARG, "basin codes: null parameters");
+    OGG_REQUIRE(p->ny >= 1 && p->nx >= 1 && p->ny <= (long)INT_MAX && p->nx <= (long)INT_MAX && p->ny * p->nx < (1L << 31), OGG_EARG,
+                "basin codes: %ld x %ld cells: ny, nx >= 1 and ny * nx < 2^31", p->ny, p->nx);
+    OGG_REQUIRE((p->topology & ~(OGG_MASK_PERIODIC | OGG_MASK_FOLD)) == 0, OGG_EARG, "basin codes: topology flags %d", p->topology);
+    OGG_REQUIRE(p->n_rules >= 1 && p->n_rules <= OGG_BASIN_MAX_RULES, OGG_EARG, "basin codes: %d rules (1 .. %d)", p->n_rules,
+                OGG_BASIN_MAX_RULES);
+    OGG_REQUIRE(!std::isnan(p->seed_max_d2) && p->seed_max_d2 >= 0.0, OGG_EARG, "basin codes: seed_max_d2 must be >= 0 or +inf (%g)",
+                p->seed_max_d2);
+    return OGG_OK;
+}
+
+int check_rules(const ogg_basin_params* p, const ogg_basin_rule* rules) {
+    if (int e = check_params(p)) return e;
+    OGG_REQUIRE(rules, OGG_EARG, "basin codes: null rules");
+    for (int k = 0; k < p->n_rules; ++k) {
+        const ogg_basin_rule& r = rules[k];
+        OGG_REQUIRE(std::isfinite(r.seed_lon) && std::isfinite(r.seed_lat) && std::isfinite(r.lon_w) && std::isfinite(r.lon_e) &&
+                        std::isfinite(r.lat_s) && std::isfinite(r.lat_n),
+                    OGG_EARG, "basin codes: rule %d holds a value that is not finite", k);
+        OGG_REQUIRE(r.code >= 1 && r.code <= 255, OGG_EARG, "basin codes: rule %d has code %d (1 .. 255)", k, r.code);
+        OGG_REQUIRE(-90.0 <= r.lat_s && r.lat_s <= r.lat_n && r.lat_n <= 90.0, OGG_EARG,
+                    "basin codes: rule %d: -90 <= lat_s <= lat_n <= 90 (%.17g, %.17g)", k, r.lat_s, r.lat_n);
+        const double W = r.lon_e - r.lon_w;
+        OGG_REQUIRE(W > 0.0 && W <= 360.0, OGG_EARG, "basin codes: rule %d: 0 < lon_e - lon_w <= 360 (%.17g, %.17g)", k, r.lon_w, r.lon_e);
+        OGG_REQUIRE(in_box(r.seed_lon, r.seed_lat, r.lon_w, W, r.lat_s, r.lat_n), OGG_EARG,
+                    "basin codes: rule %d: the seed (%.17g, %.17g) lies outside its box", k, r.seed_lon, r.seed_lat);
+    }
+    return OGG_OK;
+}
+
+// Two boxes are disjoint for the planner only when their latitude intervals or their longitude arcs are separated by more than
+// SEPARATION degrees: far more than the rounding of the predicate's t (a few 1e-14 degrees), so no cell centre is in both.
+bool disjoint(const ogg_basin_rule& a, const ogg_basin_rule& b) {
+    if (a.lat_n + SEPARATION < b.lat_s || b.lat_n + SEPARATION < a.lat_s) return true;
+    const double WA = a.lon_e - a.lon_w, WB = b.lon_e - b.lon_w;
+    if (WA >= 360.0 || WB >= 360.0) return false;
+    double d = fmod(b.lon_w - a.lon_w, 360.0);   // b's west edge, degrees east of a's
+    if (d < 0.0) d += 360.0;
+    return d > WA + SEPARATION && d + WB + SEPARATION < 360.0;
+}
+
+// start[q] .. start[q + 1] - 1 are the rules of pass q: consecutive, pairwise disjoint, at most PASS_MAX
+void plan_passes(const ogg_basin_rule* rules, int K, int batch, std::vector<int>* start) {
+    start->assign(1, 0);
+    for (int k = 1; k <= K; ++k) {
+        bool cut = k == K || !batch || k - start->back() >= PASS_MAX;
+        for (int q = start->back(); !cut && q < k; ++q) cut = !disjoint(rules[q], rules[k]);
+        if (cut) start->push_back(k);
+    }
+}
+
+// workspace: unit vectors | parents | roots | classes | kept roots of a pass | partial results of the seed search
+struct Layout {
+    long u, par, root, cls, keep, part, total;
+    unsigned seed_bx, seed_by;
+};
+
+Layout layout(const ogg_basin_params& p) {
+    Layout l;
+    const long n = p.ny * p.nx;
+    l.seed_by = (unsigned)((p.n_rules + 63) / 64);
+    l.seed_bx = (unsigned)std::max<long>(1, std::min<long>((n + NT - 1) / NT, SEED_BLOCKS / l.seed_by));
+    l.u = 0;
+    l.par = l.u + round256(n * 24);
+    l.root = l.par + round256(n * 4);
+    l.cls = l.root + round256(n * 4);
+    l.keep = l.cls + round256(n);
+    l.part = l.keep + round256(NT * 4);
+    l.total = l.part + round256((long)l.seed_bx * p.n_rules * 16);
+    return l;
+}
+
+int read_knobs(int* th, int* batch) {
+    // OGG_BASIN_TILE_ROWS: rows of a labelling tile; OGG_BASIN_BATCH=0: one rule per pass (the cross-check of the planner)
+    if (int e = knob("OGG_BASIN_TILE_ROWS", TH_DEFAULT, 1, TH_MAX, th)) return e;
+    return knob("OGG_BASIN_BATCH", 1, 0, 1, batch);
+}
+
+}  // namespace
+
+extern "C" long ogg_basin_struct_bytes(int which) {
+    switch (which) {
+        case OGG_BASIN_PARAMS: return (long)sizeof(ogg_basin_params);
+        case OGG_BASIN_RULE: return (long)sizeof(ogg_basin_rule);
+        case OGG_BASIN_RECORD: return (long)sizeof(ogg_basin_rule_record);
+        case OGG_BASIN_COUNTS: return (long)sizeof(ogg_basin_counts);
+    }
+    return -1;
+}
+
+extern "C" long ogg_basin_workspace_bytes(const ogg_basin_params* p) {
+    if (!p || check_params(p) != OGG_OK) return -1;
+    return layout(*p).total;
+}
+
+extern "C" int ogg_basin_check(const ogg_basin_params* p, const ogg_basin_rule* rules) { return check_rules(p, rules); }
+
+extern "C" int ogg_basin_plan(const ogg_basin_params* p, const ogg_basin_rule* rules, int* pass_start, int* n_passes) {
+    if (int e = check_rules(p, rules)) return e;
+    OGG_REQUIRE(pass_start && n_passes, OGG_EARG, "ogg_basin_plan: null pass_start / n_passes");
+    int th = 0, batch = 1;
+    if (int e = read_knobs(&th, &batch)) return e;
+    std::vector<int> start;
+    plan_passes(rules, p->n_rules, batch, &start);
+    std::copy(start.begin(), start.end(), pass_start);
+    *n_passes = (int)start.size() - 1;
+    return OGG_OK;
+}
+
+extern "C" int ogg_basin_codes_dev(const ogg_basin_params* p, const ogg_basin_rule* rules, const ogg_basin_rule* rules_dev,
+                                   const double* x, const double* y, long ld, const unsigned char* wet, void* workspace,
+                                   long workspace_bytes, unsigned char* code, short* rule, ogg_basin_rule_record* records,
+                                   ogg_basin_counts* counts, void* stream) {
+    if (int e = check_rules(p, rules)) return e;
+    OGG_REQUIRE(rules_dev && x && y && wet && code && rule && records && counts, OGG_EARG,
+                "ogg_basin_codes: null rules_dev / x / y / wet / code / rule / records / counts");
+    OGG_REQUIRE(ld >= 2 * p->nx + 1, OGG_EARG, "ogg_basin_codes: point rows of %ld, %ld needed", ld, 2 * p->nx + 1);
+    const Layout l = layout(*p);
+    OGG_REQUIRE(workspace && workspace_bytes >= l.total, OGG_EARG, "ogg_basin_codes: workspace of %ld bytes, %ld needed", workspace_bytes,
+                l.total);
+    int th = 0, batch = 1;
+    if (int e = read_knobs(&th, &batch)) return e;
+    std::vector<int> start;
+    plan_passes(rules, p->n_rules, batch, &start);
+    hipStream_t st = ogg::as_stream(stream);
+    const long n = p->ny * p->nx;
+    const int K = p->n_rules;
+    double* u = at<double>(workspace, l.u);
+    int* par = at<int>(workspace, l.par);
+    int* root = at<int>(workspace, l.root);
+    unsigned char* cls = at<unsigned char>(workspace, l.cls);
+    int* keep = at<int>(workspace, l.keep);
+    unsigned long long* part = at<unsigned long long>(workspace, l.part);
+    OGG_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(ogg_basin_counts), st));
+    basin_unit_kernel<<<grid_for<NT>(n, 4096), NT, 0, st>>>(p->ny, p->nx, x, y, ld, wet, u, code, rule, counts);
+    OGG_LAUNCH_CHECK();
+    basin_seed_kernel<<<dim3(l.seed_bx, l.seed_by), NT, 0, st>>>(n, u, K, rules_dev, part);
+    OGG_LAUNCH_CHECK();
+    basin_seed_reduce_kernel<<<grid_for<NT>(K, 4096), NT, 0, st>>>(K, (int)l.seed_bx, part, records);
+    OGG_LAUNCH_CHECK();
+    const Grid g{p->ny, p->nx, th, (int)((p->nx + TW - 1) / TW)};
+    const long nby = (p->ny + th - 1) / th, tiles = (long)g.nbx * nby;
+    Faces f{p->ny, p->nx, th, (long)(g.nbx - 1) * p->ny, (nby - 1) * p->nx, 0, 0};
+    if ((p->topology & OGG_MASK_PERIODIC) && p->nx > 2) f.n_p = p->ny;
+    if (p->topology & OGG_MASK_FOLD) f.n_f = p->nx / 2;
+    const long faces = f.n_v + f.n_h + f.n_p + f.n_f;
+    for (size_t q = 0; q + 1 < start.size(); ++q) {
+        const Pass ps{start[q], start[q + 1] - start[q]};
+        basin_tile_kernel<<<(unsigned)tiles, NT, TW * th * (sizeof(int) + 1), st>>>(g, ps, rules_dev, x, y, ld, wet, code, cls, par);
+        OGG_LAUNCH_CHECK();
+        if (faces > 0) {
+            basin_merge_kernel<<<grid_for<NT>(faces, 4096), NT, 0, st>>>(f, cls, par);
+            OGG_LAUNCH_CHECK();
+        }
+        basin_flatten_kernel<<<(unsigned)tiles, NT, 2 * TW * th * sizeof(int), st>>>(g, par, root);
+        OGG_LAUNCH_CHECK();
+        basin_seedroot_kernel<<<1, NT, 0, st>>>(p->nx, ps, p->seed_max_d2, rules_dev, x, y, ld, wet, code, rule, root, records, keep);
+        OGG_LAUNCH_CHECK();
+        basin_assign_kernel<<<grid_for<NT>(n, 1024), NT, 0, st>>>(n, ps, rules_dev, cls, root, keep, code, rule, records, counts);
+        OGG_LAUNCH_CHECK();
+    }
+    basin_finish_kernel<<<1, 1, 0, st>>>(counts, (long long)start.size() - 1);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+// the host-pointer form: everything copied to device memory, the call, the results copied back (synchronous)
+extern "C" int ogg_basin_codes(const ogg_basin_params* p, const ogg_basin_rule* rules, const double* x, const double* y,
+                               const unsigned char* wet, unsigned char* code, short* rule, ogg_basin_rule_record* records,
+                               ogg_basin_counts* counts) {
+    if (int e = check_rules(p, rules)) return e;
+    OGG_REQUIRE(x && y && wet && code && rule && records && counts, OGG_EARG, "ogg_basin_codes: null argument");
+    ogg::Buffers bufs;   // freed on every exit path
+    const size_t nc = (size_t)(p->ny * p->nx), npt = (size_t)(2 * p->ny + 1) * (2 * p->nx + 1), K = (size_t)p->n_rules;
+    const long wsb = layout(*p).total;
+    void *dx, *dy, *dw, *dr, *ws, *dc, *du, *dk, *ct;
+    if (int e = bufs.put(&dx, x, npt * 8)) return e;
+    if (int e = bufs.put(&dy, y, npt * 8)) return e;
+    if (int e = bufs.put(&dw, wet, nc)) return e;
+    if (int e = bufs.put(&dr, rules, K * sizeof(ogg_basin_rule))) return e;
+    if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
+    if (int e = bufs.alloc(&dc, nc)) return e;
+    if (int e = bufs.alloc(&du, nc * 2)) return e;
+    if (int e = bufs.alloc(&dk, K * sizeof(ogg_basin_rule_record))) return e;
+    if (int e = bufs.alloc(&ct, sizeof(ogg_basin_counts))) return e;
+    if (int e = ogg_basin_codes_dev(p, rules, static_cast<ogg_basin_rule*>(dr), static_cast<double*>(dx), static_cast<double*>(dy),
+                                    2 * p->nx + 1, static_cast<unsigned char*>(dw), ws, wsb, static_cast<unsigned char*>(dc),
+                                    static_cast<short*>(du), static_cast<ogg_basin_rule_record*>(dk),
+                                    static_cast<ogg_basin_counts*>(ct), nullptr))
+        return e;
+    OGG_HIP_CHECK(hipMemcpy(code, dc, nc, hipMemcpyDeviceToHost));
+    OGG_HIP_CHECK(hipMemcpy(rule, du, nc * 2, hipMemcpyDeviceToHost));
+    OGG_HIP_CHECK(hipMemcpy(records, dk, K * sizeof(ogg_basin_rule_record), hipMemcpyDeviceToHost));
+    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_basin_counts), hipMemcpyDeviceToHost));
+    return OGG_OK;
+}

@@ -31,6 +31,7 @@
 
 #include "ogg_blocks.h"
 #include "ogg_common.h"
+#include "ogg_unionfind.h"
 
 namespace {
 
@@ -58,31 +59,7 @@ struct Geo {
     int mode;
 };
 
-// ---- tile-local labelling in LDS ---------------------------------------------------------------------------------
-__device__ inline int lds_find(int* lab, int x) {
-    for (;;) {
-        const int p = __hip_atomic_load(&lab[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-__device__ inline void lds_unite(int* lab, int a, int b) {
-    a = lds_find(lab, a);
-    b = lds_find(lab, b);
-    while (a != b) {
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = __hip_atomic_fetch_min(&lab[a], b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (old == a) return;   // a linked under b
-        a = lds_find(lab, old);   // a was linked elsewhere meanwhile (now under min(old, b)): join old's set and b's
-        b = lds_find(lab, b);
-    }
-}
-
+// ---- tile-local labelling in LDS (lds_find, lds_unite: ogg_unionfind.h) ----------------------------------------------
 __global__ __launch_bounds__(NT) void mask_tile_kernel(Geo g, int* par) {
     extern __shared__ int lab[];
     const int n = TW * g.th;
@@ -118,46 +95,7 @@ __global__ __launch_bounds__(NT) void mask_tile_kernel(Geo g, int* par) {
 }
 
 // ---- merge across tile edges, the seam and the fold --------------------------------------------------------------
-__device__ inline int glb_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ inline int glb_find(const int* par, int x) {
-    for (;;) {
-        const int p = glb_load(&par[x]);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-// find with path halving: x's parent becomes its grandparent (an ancestor in the same set, of a smaller index: parents keep
-// decreasing along every chain, so no cycle can form).  Used by the flatten launch, where only one thread per tile-local component
-// walks: halving by every cell would put millions of atomics on the few words near a large component's root.
-__device__ inline int glb_find_halving(int* par, int x) {
-    for (;;) {
-        const int p = glb_load(&par[x]);
-        if (p == x) return x;
-        const int gp = glb_load(&par[p]);
-        if (gp == p) return p;
-        __hip_atomic_fetch_min(&par[x], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = gp;
-    }
-}
-
-__device__ inline void glb_unite(int* par, int a, int b) {
-    a = glb_find(par, a);
-    b = glb_find(par, b);
-    while (a != b) {
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = __hip_atomic_fetch_min(&par[a], b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == a) return;
-        a = glb_find(par, old);
-        b = glb_find(par, b);
-    }
-}
-
+// (glb_load, glb_find, glb_find_halving, glb_unite: ogg_unionfind.h)
 struct Faces {
     long ny, nx;
     int th;

@@ -34,6 +34,11 @@ def _att_list(atts):
             b = np.array([v], dtype=_NUMPY_TYPE[t]).tobytes()
             out += _name(k) + struct.pack(">ii", t, 1) + b + b"\0" * _pad4(len(b))
             continue
+        if isinstance(v, np.ndarray):   # several numbers (CF's flag_values): int32 or float64
+            t = NC_DOUBLE if v.dtype.kind == "f" else NC_INT
+            b = v.reshape(-1).astype(_NUMPY_TYPE[t]).tobytes()
+            out += _name(k) + struct.pack(">ii", t, v.size) + b + b"\0" * _pad4(len(b))
+            continue
         b = v if isinstance(v, bytes) else str(v).encode("utf-8")
         out += _name(k) + struct.pack(">ii", NC_CHAR, len(b)) + b + b"\0" * _pad4(len(b))
     return out

@@ -664,7 +664,8 @@ class AnalysisFlags(object):
                     xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False,
                     mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False,
                     remap_fill_max=None, runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast",
-                    coast_distance_file=None, coast_distance_sides="both", xgrid_frac_file=None, interp_source=None, interp_var=None, interp_vector=None, interp_points="h",
+                    coast_distance_file=None, coast_distance_sides="both", basin_codes_file=None, basin_rules=None, basin_seed_max_km=None,
+                    xgrid_frac_file=None, interp_source=None, interp_var=None, interp_vector=None, interp_points="h",
                     interp_file="interp.nc", interp_no_fill=False, interp_fill_max=None, interp_no_rotate=False)
 
     def __init__(self, **flags):
@@ -682,6 +683,7 @@ def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
     _validate_remap_flags(a.remap_source, a.remap_var)
     _validate_runoff_flags(a.runoff_source, a.runoff_var, a.topog_source, a.runoff_targets, skip_metrics)
     _validate_coast_distance_flags(a.coast_distance_file, a.coast_distance_sides, a.topog_source)
+    _validate_basin_flags(a.basin_codes_file, a.basin_rules, a.basin_seed_max_km, a.topog_source)
     _validate_frac_flags(a.xgrid_frac_file, a.xgrid_atm)
     _validate_interp_flags(a.interp_source, a.interp_var, a.interp_vector, a.interp_points, skip_metrics, a.interp_no_fill,
                            a.interp_fill_max, a.interp_no_rotate)
@@ -698,7 +700,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False, remap_fill_max=None,
          runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None,
          interp_source=None, interp_var=None, interp_vector=None, interp_points="h", interp_file="interp.nc", interp_no_fill=False,
-         interp_fill_max=None, interp_no_rotate=False, topog_roughness=False, coast_distance_file=None, coast_distance_sides="both"):
+         interp_fill_max=None, interp_no_rotate=False, topog_roughness=False, coast_distance_file=None, coast_distance_sides="both",
+         basin_codes_file=None, basin_rules=None, basin_seed_max_km=None):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -736,7 +739,10 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     ``interp_fill_max`` cells away; written to ``interp_file``; also an addition.  ``coast_distance_file`` (--coast_distance_file FILE,
     needs ``topog_source``): for every wet cell of the topography the distance to the nearest coastal land cell, and for every land
     cell to the nearest coastal wet cell (coast_distance.py; ``coast_distance_sides``: wet, land or both; the edited wet set with
-    ``ocean_mask_file``), written to FILE; also an addition."""
+    ``ocean_mask_file``), written to FILE; also an addition.  ``basin_codes_file`` (--basin_codes_file FILE, needs ``topog_source`` and
+    ``basin_rules``, --basin_rules FILE): the integer basin of every wet cell of the topography by the ordered seeded floods of the
+    rule file (basin_codes.py; a seed farther than ``basin_seed_max_km`` from every cell centre is off the grid; the edited wet set
+    with ``ocean_mask_file``), written to FILE; also an addition."""
     flags = dict(locals())   # the arguments, by name: taken before anything else is bound
     import time
 
@@ -1061,7 +1067,7 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
 
 def _run_analyses(a, g, cut=None):
     """The analyses that follow the grid (``a``: AnalysisFlags), each printed and written as it is done, in their one order: quality
-    report, topography and ocean mask, distance to the coast, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
+    report, topography and ocean mask, distance to the coast, basin codes, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
     Supergrid with its ``cut`` (main) or the _StitchedArrays of main_function_level."""
     if a.quality_report:
         _write_quality_report(g.quality(cut), a.quality_report)
@@ -1075,6 +1081,9 @@ def _run_analyses(a, g, cut=None):
     wet = _xgrid_mask(topo)   # of the topography as written: the wet set of everything below
     if a.coast_distance_file:
         _write_coast_distance(g.coast_distance(cut, wet, sides=a.coast_distance_sides), a.coast_distance_file)
+    if a.basin_codes_file:
+        from . import basin_codes as BC
+        _write_basin_codes(g.basin_codes(cut, wet, BC.read_rules(str(a.basin_rules)), seed_max_km=a.basin_seed_max_km), a.basin_codes_file)
     if a.xgrid_atm is not None:
         from . import exchange_grid as X
         xres = g.exchange_grid(cut, X.regular_atm(*a.xgrid_atm), mask=wet)
@@ -1137,6 +1146,12 @@ class _StitchedArrays(object):
     def coast_distance(self, cut, wet, sides="both"):
         from . import coast_distance as CD
         return CD.coast_distance(self.x, self.y, wet, sides=sides, Re=_default_Re)
+
+    def basin_codes(self, cut, wet, rules, seed_max_km=None):
+        from . import basin_codes as BC
+        from . import runoff as RO
+        return BC.basin_codes(self.x, self.y, wet, rules, seed_max_distance=None if seed_max_km is None else 1000.0 * seed_max_km,
+                              Re=_default_Re, area=None if self.metrics[2] is None else RO.cell_area(self.metrics[2]))
 
     def bilinear(self, cut, source, source2=None, **args):
         from . import bilinear as B
@@ -1223,6 +1238,28 @@ def _write_coast_distance(res, fnam):
     for line in CD.summary_lines(res):
         print(line)
     CD.write_coast_distance(str(fnam), res)
+
+
+def _validate_basin_flags(basin_codes_file, basin_rules, basin_seed_max_km, topog_source):
+    if not basin_codes_file:
+        if basin_rules or basin_seed_max_km is not None:
+            raise ValueError("--basin_rules and --basin_seed_max_km need --basin_codes_file")
+        return
+    if not basin_rules:
+        raise ValueError("--basin_codes_file needs --basin_rules: the basins are the ordered floods of a rule file")
+    if topog_source is None:
+        raise ValueError("--basin_codes_file needs --topog_source: the basins are those of the topography's wet cells")
+    if basin_seed_max_km is not None and not (float(basin_seed_max_km) >= 0.0):
+        raise ValueError("--basin_seed_max_km must be >= 0, not %r" % (basin_seed_max_km,))
+
+
+def _write_basin_codes(res, fnam):
+    if res is None:   # not rank 0
+        return
+    from . import basin_codes as BC
+    for line in BC.summary_lines(res):
+        print(line)
+    BC.write_basin_codes(str(fnam), res)
 
 
 def _validate_interp_flags(interp_source, interp_var, interp_vector, interp_points, skip_metrics, no_fill=False, fill_max=None,
@@ -1413,6 +1450,13 @@ def build_parser():
                              "topography (the --ocean_mask_file mask when given) to this file")
     parser.add_argument("--coast_distance_sides", type=str, choices=["wet", "land", "both"], required=False, default="both",
                         help="the cells that get a distance: wet, land or both (default)")
+    parser.add_argument("--basin_codes_file", type=str, required=False, default=None,
+                        help="write the integer basin of every wet model cell of the --topog_source topography (the --ocean_mask_file "
+                             "mask when given), by the ordered seeded floods of --basin_rules, to this file")
+    parser.add_argument("--basin_rules", type=str, required=False, default=None,
+                        help="the rule file of --basin_codes_file: code seed_lon seed_lat lon_w lon_e lat_s lat_n [name] per line")
+    parser.add_argument("--basin_seed_max_km", type=float, required=False, default=None,
+                        help="a seed farther than this from every cell centre is off the grid (default: any distance)")
     parser.add_argument("--xgrid_frac_file", type=str, required=False, default=None,
                         help="write the ocean / land fraction, area and exchange-cell count of every --xgrid_atm atmosphere cell to this "
                              "file (wet cells only when --topog_source is given)")

@@ -1613,6 +1613,21 @@ class Supergrid(object):
             return None
         return CD.coast_distance_dev(xy[0], xy[1], wet, sides=sides, Re=float(self.plan.Re))
 
+    # -- basin codes --------------------------------------------------------------------------------------------------
+    def basin_codes(self, cut, wet, rules, seed_max_km=None):
+        """The basin codes (basin_codes.result on rank 0, None on the other ranks) of the model cells of the stitched grid with the wet
+        set ``wet`` (one value per model cell, 0: land) under ``rules`` (a basin_codes.Rules or rows), on rank 0's GPU with the stitched
+        points gathered there, as coast_distance does: the same bits for any number of ranks by construction.  The area per code of
+        the summary comes from the stitched area unless the plan skips the metrics."""
+        from . import basin_codes as BC
+        from . import runoff as RO
+        xy = self.stitched_xy(cut)
+        area = None if self.plan.skip_metrics else self.stitched_area(cut)
+        if xy is None:
+            return None
+        return BC.basin_codes_dev(xy[0], xy[1], wet, rules, seed_max_distance=None if seed_max_km is None else 1000.0 * seed_max_km,
+                                  Re=float(self.plan.Re), area=None if area is None else RO.cell_area(area.cpu().numpy()))
+
     # -- bilinear interpolation ---------------------------------------------------------------------------------------
     def stitched_angle(self, cut):
         """The stitched angle_dx ((nyp, nxp) float64 device tensor) on rank 0's device, None on the other ranks (_stitched)."""
