@@ -1139,8 +1139,9 @@ int ogg_coast_distance(const ogg_coast_params* p, const double* x, const double*
  *            W == 360.
  *   seed cell  of rule k: the valid cell whose centre is nearest to the seed by the key (bits of d2, c), d2 = dist2(u_c, u_seed) of
  *            "Runoff mapping" (unit vectors (cos lat cos lon, cos lat sin lon, sin lat), lon, lat * (pi / 180); d2 = (dx * dx + dy *
- *            dy) + dz * dz): ties to the smaller index.  It is the cell ogg_mask_seed_dev names, with the same d2 bits.  Invalid
- *            cells are no candidates.  A seed whose d2 is larger than seed_max_d2 (+inf: off) is OFF THE GRID.
+ *            dy) + dz * dz): ties to the smaller index.  It is the cell ogg_mask_seed_dev names, with the same d2 bits: the two
+ *            searches share one definition of d2.  Invalid cells are no candidates.  A seed whose d2 is larger than seed_max_d2
+ *            (+inf: off) is OFF THE GRID.
  *   order    before rule k, code[c] = 0 for every cell that no earlier rule took.  E_k: the cells that are wet, valid, uncoded and in
  *            box k.  If the seed cell is in E_k, its connected component inside E_k through the faces above gets code_k and rule[c]
  *            = k.  Otherwise the rule takes nothing, which is no error (a coarse or regional grid may have no Black Sea), and its

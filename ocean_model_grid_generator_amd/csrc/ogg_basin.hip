@@ -1,8 +1,9 @@
 // Basin codes: ordered seeded floods of the wet cells (include/ogg_hip.h, "Basin codes").  Rule k floods, from its seed cell, the
 // cells that are wet, valid, not yet coded and inside its longitude / latitude box.  A flood is a connected component under a per-cell
-// class, so the floods run on the ocean mask's union-find (ogg_unionfind.h) and the launches of a call do not grow with a basin's
-// diameter.  Consecutive rules whose boxes are pairwise disjoint cannot see each other's cells and run as ONE pass (planned on the
-// host); every pass is five launches on the caller's stream, and nothing comes back to the host between passes:
+// class, so the floods are the components of ogg_label.h (its tile, merge and flatten launches, the ocean mask's) and the launches of a
+// call do not grow with a basin's diameter.  Consecutive rules whose boxes are pairwise disjoint cannot see each other's cells and run
+// as ONE pass (planned on the host); every pass is five launches on the caller's stream, and nothing comes back to the host between
+// passes:
 //
 // basin_unit_kernel      once: the unit vector of every cell centre (NaN for an invalid centre), code = 0 and rule = -1 everywhere,
 //                        and the wet count.
@@ -10,12 +11,8 @@
 //                        is a rule, the cells stream through LDS, every lane tests every cell: three subtractions and three products
 //                        per test, no sin / cos beyond the seed's own.  One partial result per (block, rule), reduced by
 // basin_seed_reduce_kernel  into the rule records.
-// basin_tile_kernel      per pass, one workgroup per tile of TW x th cells: the class byte of every cell (the index inside the pass of
-//                        the rule whose box holds it if the cell is wet, valid and uncoded; 255 otherwise), then the union-find in LDS
-//                        over the faces inside the tile between cells of EQUAL class; a tile without an eligible cell leaves after
-//                        writing its parents.
-// basin_merge_kernel     one thread per face across a tile edge, the seam or the fold: the same union on the global parents.
-// basin_flatten_kernel   root[c] = find(c), the smallest index of the cell's component.
+// basin_tile_kernel      per pass: the class byte of every cell of a tile (the index inside the pass of the rule whose box holds it if
+//                        the cell is wet, valid and uncoded; NONE = 255 otherwise), kept in cls[], then label_tile.
 // basin_seedroot_kernel  one thread per rule of the pass: the status of the rule, and the root of its seed cell if it floods.
 // basin_assign_kernel    every cell whose root is the kept root of its class's rule gets that rule's code and index; the cells taken
 //                        are counted per wavefront and class, then in LDS, then one atomicAdd per block and rule.
@@ -30,8 +27,8 @@
 
 #include "ogg_blocks.h"
 #include "ogg_common.h"
+#include "ogg_label.h"
 #include "ogg_sphere.h"
-#include "ogg_unionfind.h"
 
 #pragma clang fp contract(off)
 
@@ -42,16 +39,10 @@ using ogg::grid_for;
 using ogg::knob;
 using ogg::round256;
 
-constexpr int TW = 64;             // tile width: one wavefront across a tile row
-constexpr int NT = 256;            // threads per workgroup
-constexpr int TH_DEFAULT = 32;     // tile rows (OGG_BASIN_TILE_ROWS), the ocean mask's
-constexpr int TH_MAX = 64;
-constexpr int NONE = 255;          // the class of a cell that no rule of the pass can take
 constexpr int PASS_MAX = OGG_BASIN_MAX_PASS_RULES;
 constexpr long SEED_BLOCKS = 1024; // workgroups of the seed search, over cells and groups of 64 rules
 constexpr double SEPARATION = 1.0e-9;   // degrees: two boxes closer than this are not disjoint for the planner
 
-static_assert(NT == BLOCKS_NT, "block_add sums over a workgroup of BLOCKS_NT threads");
 static_assert(PASS_MAX < NONE + 1 && PASS_MAX <= NT, "a class is a byte, and a thread per rule of a pass");
 static_assert(sizeof(ogg_basin_params) == 32, "ogg_basin_params layout");
 static_assert(sizeof(ogg_basin_rule) == 56, "ogg_basin_rule layout");
@@ -65,11 +56,6 @@ __host__ __device__ inline bool in_box(double lon, double lat, double lon_w, dou
     t = t - 360.0 * floor(t / 360.0);
     return W == 360.0 || t <= W;
 }
-
-struct Grid {
-    long ny, nx;
-    int th, nbx;
-};
 
 struct Pass {
     int r0, nr;   // the rules r0 .. r0 + nr - 1
@@ -156,9 +142,16 @@ __global__ __launch_bounds__(NT) void basin_seed_reduce_kernel(int K, int nparts
     rec[s].cells = 0;
 }
 
-// ---- per pass: classes and the tile-local labelling ----------------------------------------------------------------
-// the boxes of the pass's rules in LDS: lon_w, W = lon_e - lon_w, lat_s, lat_n
-__device__ inline void load_boxes(const Pass& ps, const ogg_basin_rule* __restrict__ rules, double (*box)[4]) {
+// ---- per pass: the classes and the tile-local labelling (ogg_label.h) -----------------------------------------------
+__global__ __launch_bounds__(NT) void basin_tile_kernel(Grid g, Pass ps, const ogg_basin_rule* __restrict__ rules,
+                                                        const double* __restrict__ x, const double* __restrict__ y, long ld,
+                                                        const unsigned char* __restrict__ wet, const unsigned char* __restrict__ code,
+                                                        unsigned char* __restrict__ cls, int* par) {
+    extern __shared__ int lab[];                 // TW * th parents, then TW * th class bytes
+    __shared__ double box[PASS_MAX][4];          // the boxes of the pass's rules: lon_w, W = lon_e - lon_w, lat_s, lat_n
+    const int n = TW * g.th;
+    unsigned char* lc = reinterpret_cast<unsigned char*>(lab + n);
+    const long i0 = (long)(blockIdx.x % g.nbx) * TW, j0 = (long)(blockIdx.x / g.nbx) * g.th;
     for (int r = threadIdx.x; r < ps.nr; r += NT) {
         const ogg_basin_rule q = rules[ps.r0 + r];
         box[r][0] = q.lon_w;
@@ -166,18 +159,6 @@ __device__ inline void load_boxes(const Pass& ps, const ogg_basin_rule* __restri
         box[r][2] = q.lat_s;
         box[r][3] = q.lat_n;
     }
-}
-
-__global__ __launch_bounds__(NT) void basin_tile_kernel(Grid g, Pass ps, const ogg_basin_rule* __restrict__ rules,
-                                                        const double* __restrict__ x, const double* __restrict__ y, long ld,
-                                                        const unsigned char* __restrict__ wet, const unsigned char* __restrict__ code,
-                                                        unsigned char* __restrict__ cls, int* par) {
-    extern __shared__ int lab[];                 // TW * th parents, then TW * th class bytes
-    __shared__ double box[PASS_MAX][4];
-    const int n = TW * g.th;
-    unsigned char* lc = reinterpret_cast<unsigned char*>(lab + n);
-    const long i0 = (long)(blockIdx.x % g.nbx) * TW, j0 = (long)(blockIdx.x / g.nbx) * g.th;
-    load_boxes(ps, rules, box);
     __syncthreads();
     int any = 0;
     for (int l = threadIdx.x; l < n; l += NT) {
@@ -201,111 +182,13 @@ __global__ __launch_bounds__(NT) void basin_tile_kernel(Grid g, Pass ps, const o
         lab[l] = k != NONE ? l : -1;
         any |= k != NONE;
     }
-    if (__syncthreads_or(any) == 0) {   // nothing to flood in this tile
-        for (int l = threadIdx.x; l < n; l += NT) {
-            const long j = j0 + l / TW, i = i0 + l % TW;
-            if (j < g.ny && i < g.nx) par[j * g.nx + i] = -1;
-        }
-        return;
-    }
-    for (int l = threadIdx.x; l < n; l += NT) {
-        const int k = lc[l];
-        if (k == NONE) continue;
-        const int tx = l % TW, ty = l / TW;
-        if (tx + 1 < TW && lc[l + 1] == k) lds_unite(lab, l, l + 1);
-        if (ty + 1 < g.th && lc[l + TW] == k) lds_unite(lab, l, l + TW);
-    }
-    __syncthreads();
-    for (int l = threadIdx.x; l < n; l += NT) {
-        const long j = j0 + l / TW, i = i0 + l % TW;
-        if (j >= g.ny || i >= g.nx) continue;
-        int p = -1;
-        if (lc[l] != NONE) {
-            const int r = lds_find(lab, l);
-            p = (int)((j0 + r / TW) * g.nx + i0 + r % TW);
-        }
-        par[j * g.nx + i] = p;
-    }
+    label_tile<true>(g, j0, i0, lab, any, par);
 }
 
-// ---- merge across tile edges, the seam and the fold ----------------------------------------------------------------
-struct Faces {
-    long ny, nx;
-    int th;
-    long n_v, n_h, n_p, n_f;   // faces across vertical tile edges, horizontal tile edges, the seam, the fold
+struct SameClass {   // the merge predicate: equal classes only
+    const unsigned char* __restrict__ cls;
+    __device__ bool operator()(const int*, long a, long b) const { return cls[a] != NONE && cls[a] == cls[b]; }
 };
-
-__global__ __launch_bounds__(NT) void basin_merge_kernel(Faces f, const unsigned char* __restrict__ cls, int* par) {
-    const long total = f.n_v + f.n_h + f.n_p + f.n_f;
-    for (long t = (long)blockIdx.x * NT + threadIdx.x; t < total; t += (long)gridDim.x * NT) {
-        long a, b, u = t;
-        if (u < f.n_v) {   // (j, i - 1) ~ (j, i), i = (k + 1) * TW
-            const long k = u / f.ny, j = u % f.ny;
-            a = j * f.nx + (k + 1) * TW - 1;
-            b = a + 1;
-        } else if ((u -= f.n_v) < f.n_h) {   // (j - 1, i) ~ (j, i), j = (k + 1) * th
-            const long k = u / f.nx, i = u % f.nx;
-            a = ((k + 1) * f.th - 1) * f.nx + i;
-            b = a + f.nx;
-        } else if ((u -= f.n_h) < f.n_p) {   // (j, nx - 1) ~ (j, 0)
-            a = u * f.nx + f.nx - 1;
-            b = u * f.nx;
-        } else {   // (ny - 1, i) ~ (ny - 1, nx - 1 - i), i < nx - 1 - i
-            u -= f.n_p;
-            a = (f.ny - 1) * f.nx + u;
-            b = (f.ny - 1) * f.nx + f.nx - 1 - u;
-        }
-        const int k = cls[a];
-        if (k != NONE && k == cls[b]) glb_unite(par, (int)a, (int)b);   // equal classes only
-    }
-}
-
-// ---- flatten -------------------------------------------------------------------------------------------------------
-// As the ocean mask's, without the cells per root: the tile's parents go to LDS, every cell follows them inside the tile to its
-// representative, and only the representatives walk the global chains.
-__global__ __launch_bounds__(NT) void basin_flatten_kernel(Grid g, int* par, int* __restrict__ root) {
-    extern __shared__ int sh[];
-    const int n = TW * g.th;
-    int* lp = sh;       // the parent of each tile cell as a tile-local index, -1 outside the tile, -2 for no class / off the grid
-    int* rt = sh + n;   // the root of each representative
-    const long i0 = (long)(blockIdx.x % g.nbx) * TW, j0 = (long)(blockIdx.x / g.nbx) * g.th;
-    int any = 0;
-    for (int l = threadIdx.x; l < n; l += NT) {
-        const long j = j0 + l / TW, i = i0 + l % TW;
-        int v = -2;
-        if (j < g.ny && i < g.nx) {
-            const int p = glb_load(&par[j * g.nx + i]);   // (another tile's walk may halve it: any value read is an ancestor)
-            if (p >= 0) {
-                const long pj = p / g.nx, pi = p % g.nx;
-                v = (pj >= j0 && pj < j0 + g.th && pi >= i0 && pi < i0 + TW) ? (int)((pj - j0) * TW + (pi - i0)) : -1;
-                if (v == l) v = -1;   // a root: its own representative
-            }
-        }
-        lp[l] = v;
-        any |= v != -2;
-    }
-    if (__syncthreads_or(any) == 0) {
-        for (int l = threadIdx.x; l < n; l += NT) {
-            const long j = j0 + l / TW, i = i0 + l % TW;
-            if (j < g.ny && i < g.nx) root[j * g.nx + i] = -1;
-        }
-        return;
-    }
-    for (int l = threadIdx.x; l < n; l += NT)
-        if (lp[l] == -1) rt[l] = glb_find_halving(par, (int)((j0 + l / TW) * g.nx + i0 + l % TW));
-    __syncthreads();
-    for (int l = threadIdx.x; l < n; l += NT) {
-        const long j = j0 + l / TW, i = i0 + l % TW;
-        if (j >= g.ny || i >= g.nx) continue;
-        int r = -1;
-        if (lp[l] != -2) {
-            int q = l;
-            while (lp[q] >= 0) q = lp[q];   // in-tile parents have smaller local indices: this ends
-            r = rt[q];
-        }
-        root[j * g.nx + i] = r;
-    }
-}
 
 // ---- seed roots and the assignment ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT) void basin_seedroot_kernel(long nx, Pass ps, double seed_max_d2, const ogg_basin_rule* __restrict__ rules,
@@ -525,22 +408,12 @@ extern "C" int ogg_basin_codes_dev(const ogg_basin_params* p, const ogg_basin_ru
     OGG_LAUNCH_CHECK();
     basin_seed_reduce_kernel<<<grid_for<NT>(K, 4096), NT, 0, st>>>(K, (int)l.seed_bx, part, records);
     OGG_LAUNCH_CHECK();
-    const Grid g{p->ny, p->nx, th, (int)((p->nx + TW - 1) / TW)};
-    const long nby = (p->ny + th - 1) / th, tiles = (long)g.nbx * nby;
-    Faces f{p->ny, p->nx, th, (long)(g.nbx - 1) * p->ny, (nby - 1) * p->nx, 0, 0};
-    if ((p->topology & OGG_MASK_PERIODIC) && p->nx > 2) f.n_p = p->ny;
-    if (p->topology & OGG_MASK_FOLD) f.n_f = p->nx / 2;
-    const long faces = f.n_v + f.n_h + f.n_p + f.n_f;
     for (size_t q = 0; q + 1 < start.size(); ++q) {
         const Pass ps{start[q], start[q + 1] - start[q]};
-        basin_tile_kernel<<<(unsigned)tiles, NT, TW * th * (sizeof(int) + 1), st>>>(g, ps, rules_dev, x, y, ld, wet, code, cls, par);
-        OGG_LAUNCH_CHECK();
-        if (faces > 0) {
-            basin_merge_kernel<<<grid_for<NT>(faces, 4096), NT, 0, st>>>(f, cls, par);
-            OGG_LAUNCH_CHECK();
-        }
-        basin_flatten_kernel<<<(unsigned)tiles, NT, 2 * TW * th * sizeof(int), st>>>(g, par, root);
-        OGG_LAUNCH_CHECK();
+        const auto tile = [&](const Grid& g, unsigned tiles) {
+            basin_tile_kernel<<<tiles, NT, TW * th * (sizeof(int) + 1), st>>>(g, ps, rules_dev, x, y, ld, wet, code, cls, par);
+        };
+        if (int e = label_components<false>(p->ny, p->nx, th, p->topology, tile, SameClass{cls}, par, root, nullptr, st)) return e;
         basin_seedroot_kernel<<<1, NT, 0, st>>>(p->nx, ps, p->seed_max_d2, rules_dev, x, y, ld, wet, code, rule, root, records, keep);
         OGG_LAUNCH_CHECK();
         basin_assign_kernel<<<grid_for<NT>(n, 1024), NT, 0, st>>>(n, ps, rules_dev, cls, root, keep, code, rule, records, counts);

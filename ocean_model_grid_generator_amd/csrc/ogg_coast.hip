@@ -4,7 +4,7 @@
 // sets      one flag byte (wet, coastal, valid) and the unit vector of every cell, then the two coastal lists by the ordered
 //           compaction of ogg_blocks.h (a membership byte, one exclusive scan, a list kernel), as the runoff targets step.
 // search    every cell is a query, and index-space neighbours are usually neighbours on the sphere, so one workgroup takes a tile of
-//           TY x TX cells and does the pruning once for all of them.  The targets are sorted into G^3 cubes (ogg_sphere.h); a
+//           TY x TX cells and does the pruning once for all of them.  The targets are sorted into G^3 cubes (ogg_sphere_bins.h); a
 //           coastline is one-dimensional, so only the non-empty cubes are kept, as a compact list in ascending cube order with the
 //           TIGHT box of each cube's contents (the exact minimum and maximum of the coordinates held: no rounding enters a box).
 //           The tile's queries lie in a ball: centre m (the middle of their bounding box), radius r (the largest |p - m|).
@@ -31,7 +31,7 @@
 
 #include "ogg_blocks.h"
 #include "ogg_common.h"
-#include "ogg_sphere.h"
+#include "ogg_sphere_bins.h"
 
 #pragma clang fp contract(off)
 

@@ -1,25 +1,14 @@
-// Ocean mask: minimum depth and connected basins (include/ogg_hip.h, "Ocean mask").  Connected components of the wet cells by
-// union-find, in three launches, so the number of launches does not grow with a component's diameter (a serpentine channel is one
-// component of millions of cells):
+// Ocean mask: minimum depth and connected basins (include/ogg_hip.h, "Ocean mask").  The connected components of the wet cells are
+// those of ogg_label.h under one class, with the cells per root; what is left here:
 //
-// mask_tile_kernel     one workgroup per tile of TW x th cells: the wet rule, then a union-find in LDS over the faces inside the tile
-//                      (link the larger root under the smaller by an LDS atomicMin, retried); every cell's parent becomes the GLOBAL
-//                      index of its tile-local root.  Row-major local indices map monotonically to global ones, so that root is the
-//                      smallest global index of the tile-local component.
-// mask_merge_kernel    one thread per face that crosses a tile edge, the periodic seam or the fold: the same union on the global
-//                      parents, with agent-scope atomicMin links.  Other workgroups write parent words in this launch, so every read
-//                      of one is an agent-scope relaxed atomic load (a plain load may return a stale line of another XCD's L2).
-//                      Parents only ever decrease, so there is no cycle; the retry is lock-free and no workgroup waits on another.
-// mask_flatten_kernel  its own launch (every link is in place): root[c] = find(c) and the cells per root.  Inside a tile the cells
-//                      follow their parents in LDS to a representative; only representatives walk the global chains (halving them
-//                      as they go), and the cells are counted per representative in LDS, then one atomicAdd per (tile,
-//                      representative), so the world ocean does not serialise millions of atomics on one word.
+// mask_tile_kernel     the wet rule of a tile's cells, then label_tile.
 // mask_list_kernel     the component list ((cells << 32) | (INT32_MAX - root) of every root) and the largest entry: each block owns a
 //                      contiguous chunk, reduces its count and maximum, and adds to each shared word once.
 // mask_apply_kernel    the edited depth and the final wet mask from the roots kept (a short sorted list chosen on the host, and
 //                      keep_min_cells against the per-root counts), and the wet-rule and selection counts, one add per block.
-// mask_seed_kernel     the nearest model-cell centre of each seed: the smallest squared chordal distance (its bits: positive doubles
-//                      order as integers), then the smallest index at that distance; both reduced per wavefront first.
+// mask_seed_kernel     the nearest model-cell centre of each seed: the smallest squared chordal distance (unit, dist2 and bits_of of
+//                      ogg_sphere.h, the basin codes' own; positive doubles order as integers), then the smallest index at that
+//                      distance; both reduced per wavefront first.
 //
 // Every result is an integer or a copy, so nothing depends on the order in which the atomics land.
 #include <algorithm>
@@ -31,7 +20,8 @@
 
 #include "ogg_blocks.h"
 #include "ogg_common.h"
-#include "ogg_unionfind.h"
+#include "ogg_label.h"
+#include "ogg_sphere.h"
 
 namespace {
 
@@ -40,137 +30,38 @@ using ogg::grid_for;
 using ogg::knob;
 using ogg::round256;
 
-constexpr int TW = 64;       // tile width: one wavefront across a tile row
-constexpr int NT = 256;      // threads per workgroup
-constexpr int TH_DEFAULT = 32;   // tile rows (OGG_MASK_TILE_ROWS)
-constexpr int TH_MAX = 64;
 constexpr long LIST_BLOCKS = 1024;   // blocks of the list and apply kernels: each block adds once to a shared counter word
 constexpr long APPLY_BLOCKS = 1024;
 
-static_assert(NT == BLOCKS_NT, "block_add sums over a workgroup of BLOCKS_NT threads");
 static_assert(sizeof(ogg_mask_params) == 48, "ogg_mask_params layout");
 static_assert(sizeof(ogg_mask_counts) == 64, "ogg_mask_counts layout");
 
 struct Geo {
     const double* depth;
-    long ny, nx;
-    int th, nbx;
     double fill, min_depth;
     int mode;
 };
 
-// ---- tile-local labelling in LDS (lds_find, lds_unite: ogg_unionfind.h) ----------------------------------------------
-__global__ __launch_bounds__(NT) void mask_tile_kernel(Geo g, int* par) {
+// ---- the wet rule and the tile-local labelling (ogg_label.h) -------------------------------------------------------
+__global__ __launch_bounds__(NT) void mask_tile_kernel(Grid t, Geo g, int* par) {
     extern __shared__ int lab[];
-    const int n = TW * g.th;
-    const long i0 = (long)(blockIdx.x % g.nbx) * TW, j0 = (long)(blockIdx.x / g.nbx) * g.th;
+    const int n = TW * t.th;
+    const long i0 = (long)(blockIdx.x % t.nbx) * TW, j0 = (long)(blockIdx.x / t.nbx) * t.th;
     for (int l = threadIdx.x; l < n; l += NT) {
         const long j = j0 + l / TW, i = i0 + l % TW;
         int v = -1;
-        if (j < g.ny && i < g.nx) {
-            const double d = g.depth[j * g.nx + i];
+        if (j < t.ny && i < t.nx) {
+            const double d = g.depth[j * t.nx + i];
             if (d > 0.0 && d != g.fill && !(d < g.min_depth && g.mode == OGG_MASK_MASK)) v = l;
         }
         lab[l] = v;
     }
-    __syncthreads();
-    for (int l = threadIdx.x; l < n; l += NT) {
-        if (__hip_atomic_load(&lab[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 0) continue;   // land stays -1
-        const int tx = l % TW, ty = l / TW;
-        if (tx + 1 < TW && __hip_atomic_load(&lab[l + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= 0) lds_unite(lab, l, l + 1);
-        if (ty + 1 < g.th && __hip_atomic_load(&lab[l + TW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= 0)
-            lds_unite(lab, l, l + TW);
-    }
-    __syncthreads();
-    for (int l = threadIdx.x; l < n; l += NT) {
-        const long j = j0 + l / TW, i = i0 + l % TW;
-        if (j >= g.ny || i >= g.nx) continue;
-        int p = -1;
-        if (lab[l] >= 0) {
-            const int r = lds_find(lab, l);
-            p = (int)((j0 + r / TW) * g.nx + i0 + r % TW);
-        }
-        par[j * g.nx + i] = p;
-    }
+    label_tile<false>(t, j0, i0, lab, 1, par);
 }
 
-// ---- merge across tile edges, the seam and the fold --------------------------------------------------------------
-// (glb_load, glb_find, glb_find_halving, glb_unite: ogg_unionfind.h)
-struct Faces {
-    long ny, nx;
-    int th;
-    long n_v, n_h, n_p, n_f;   // faces across vertical tile edges, horizontal tile edges, the seam, the fold
+struct BothWet {   // the merge predicate of one class: land stays -1
+    __device__ bool operator()(const int* par, long a, long b) const { return glb_load(&par[a]) >= 0 && glb_load(&par[b]) >= 0; }
 };
-
-__global__ __launch_bounds__(NT) void mask_merge_kernel(Faces f, int* par) {
-    const long total = f.n_v + f.n_h + f.n_p + f.n_f;
-    for (long t = (long)blockIdx.x * NT + threadIdx.x; t < total; t += (long)gridDim.x * NT) {
-        long a, b, u = t;
-        if (u < f.n_v) {   // (j, i - 1) ~ (j, i), i = (k + 1) * TW
-            const long k = u / f.ny, j = u % f.ny;
-            a = j * f.nx + (k + 1) * TW - 1;
-            b = a + 1;
-        } else if ((u -= f.n_v) < f.n_h) {   // (j - 1, i) ~ (j, i), j = (k + 1) * th
-            const long k = u / f.nx, i = u % f.nx;
-            a = ((k + 1) * f.th - 1) * f.nx + i;
-            b = a + f.nx;
-        } else if ((u -= f.n_h) < f.n_p) {   // (j, nx - 1) ~ (j, 0)
-            a = u * f.nx + f.nx - 1;
-            b = u * f.nx;
-        } else {   // (ny - 1, i) ~ (ny - 1, nx - 1 - i), i < nx - 1 - i
-            u -= f.n_p;
-            a = (f.ny - 1) * f.nx + u;
-            b = (f.ny - 1) * f.nx + f.nx - 1 - u;
-        }
-        if (glb_load(&par[a]) >= 0 && glb_load(&par[b]) >= 0) glb_unite(par, (int)a, (int)b);   // land stays -1
-    }
-}
-
-// ---- flatten, cells per root ---------------------------------------------------------------------------------------
-// The tile's parents go to LDS; every cell follows them inside the tile to its representative (the first cell whose parent is
-// itself or lies outside the tile).  Only the representatives walk the global chains; the other cells take their representative's
-// root from LDS.
-__global__ __launch_bounds__(NT) void mask_flatten_kernel(Geo g, int* par, int* root, int* size) {
-    extern __shared__ int sh[];
-    const int n = TW * g.th;
-    int* lp = sh;          // the parent of each tile cell as a tile-local index, -1 outside the tile, -2 for land / off the grid
-    int* rt = sh + n;      // the root of each representative
-    int* cnt = sh + 2 * n; // cells per representative
-    const long i0 = (long)(blockIdx.x % g.nbx) * TW, j0 = (long)(blockIdx.x / g.nbx) * g.th;
-    for (int l = threadIdx.x; l < n; l += NT) {
-        const long j = j0 + l / TW, i = i0 + l % TW;
-        int v = -2;
-        if (j < g.ny && i < g.nx) {
-            const int p = glb_load(&par[j * g.nx + i]);   // (another tile's walk may halve it: any value read is an ancestor)
-            if (p >= 0) {
-                const long pj = p / g.nx, pi = p % g.nx;
-                v = (pj >= j0 && pj < j0 + g.th && pi >= i0 && pi < i0 + TW) ? (int)((pj - j0) * TW + (pi - i0)) : -1;
-                if (v == l) v = -1;   // a root: its own representative
-            }
-        }
-        lp[l] = v;
-        cnt[l] = 0;
-    }
-    __syncthreads();
-    for (int l = threadIdx.x; l < n; l += NT)
-        if (lp[l] == -1) rt[l] = glb_find_halving(par, (int)((j0 + l / TW) * g.nx + i0 + l % TW));
-    __syncthreads();
-    for (int l = threadIdx.x; l < n; l += NT) {
-        const long j = j0 + l / TW, i = i0 + l % TW;
-        if (j >= g.ny || i >= g.nx) continue;
-        if (lp[l] == -2) {
-            root[j * g.nx + i] = -1;
-            continue;
-        }
-        int x = l;
-        while (lp[x] >= 0) x = lp[x];   // in-tile parents have smaller local indices: this ends
-        root[j * g.nx + i] = rt[x];
-        atomicAdd(&cnt[x], 1);
-    }
-    __syncthreads();
-    for (int l = threadIdx.x; l < n; l += NT)
-        if (cnt[l] > 0) atomicAdd(&size[rt[l]], cnt[l]);
-}
 
 // ---- component list and the largest ------------------------------------------------------------------------------
 // Each block owns one contiguous chunk of cells: it counts its roots and takes their room in the list with ONE atomicAdd, then writes
@@ -222,9 +113,8 @@ __global__ __launch_bounds__(NT) void mask_list_kernel(long n, long chunk, const
 }
 
 // ---- apply ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT) void mask_apply_kernel(Geo g, const int* root, const int* size, const int* kept, int n_kept,
+__global__ __launch_bounds__(NT) void mask_apply_kernel(Geo g, long n, const int* root, const int* size, const int* kept, int n_kept,
                                                         long long kmin, double* out, unsigned char* wet, ogg_mask_counts* counts) {
-    const long n = g.ny * g.nx;
     long long v[6] = {0, 0, 0, 0, 0, 0};   // wet_in, masked, deepened, kept, removed, wet_out
     for (long c = (long)blockIdx.x * NT + threadIdx.x; c < n; c += (long)gridDim.x * NT) {
         const double d = g.depth[c];
@@ -258,30 +148,21 @@ __global__ __launch_bounds__(NT) void mask_apply_kernel(Geo g, const int* root, 
 }
 
 // ---- seeds ---------------------------------------------------------------------------------------------------------
-__device__ inline double chord2(double lon, double lat, double sx, double sy, double sz) {
-    const double D = 0.017453292519943295;   // pi / 180
-    const double cl = cos(lat * D);
-    const double dx = cl * cos(lon * D) - sx, dy = cl * sin(lon * D) - sy, dz = sin(lat * D) - sz;
-    return dx * dx + dy * dy + dz * dz;
-}
-
 template <bool SECOND>
 __global__ __launch_bounds__(NT) void mask_seed_kernel(long ny, long nx, const double* x, const double* y, long ld, int ns,
                                                        const double* lonlat, unsigned long long* out) {
     const long n = ny * nx;
-    const double D = 0.017453292519943295;
     for (int s = 0; s < ns; ++s) {
-        const double slon = lonlat[2 * s] * D, slat = lonlat[2 * s + 1] * D;
-        const double sx = cos(slat) * cos(slon), sy = cos(slat) * sin(slon), sz = sin(slat);
+        double su[3], cu[3];
+        unit(lonlat[2 * s], lonlat[2 * s + 1], su);
         const unsigned long long want = SECOND ? out[2 * s] : 0ull;   // written by the first launch
         unsigned long long best = ULLONG_MAX;
         for (long base = (long)blockIdx.x * NT; base < n; base += (long)gridDim.x * NT) {
             const long c = base + threadIdx.x;
             if (c >= n) continue;
             const long j = c / nx, i = c % nx, k = (2 * j + 1) * ld + 2 * i + 1;
-            double d2 = chord2(x[k], y[k], sx, sy, sz);
-            unsigned long long bits;
-            memcpy(&bits, &d2, 8);
+            unit(x[k], y[k], cu);
+            const unsigned long long bits = bits_of(dist2(cu[0], cu[1], cu[2], su[0], su[1], su[2]));
             const unsigned long long v = SECOND ? (bits == want ? (unsigned long long)c : ULLONG_MAX) : bits;
             best = v < best ? v : best;
         }
@@ -309,10 +190,6 @@ int check_params(const ogg_mask_params* p) {
 
 long ws_bytes(const ogg_mask_params& p) { return 2 * round256(p.ny * p.nx * 4); }
 
-Geo make_geo(const ogg_mask_params& p, const double* depth, int th) {
-    return Geo{depth, p.ny, p.nx, th, (int)((p.nx + TW - 1) / TW), p.fill, p.min_depth, p.mode};
-}
-
 }  // namespace
 
 extern "C" long ogg_mask_struct_bytes(int which) {
@@ -338,23 +215,11 @@ extern "C" int ogg_mask_label_dev(const ogg_mask_params* p, const double* depth,
     int* par = static_cast<int*>(workspace);
     int* size = at<int>(workspace, round256(n * 4));
     hipStream_t st = ogg::as_stream(stream);
-    const Geo g = make_geo(*p, depth, th);
-    const long nby = (p->ny + th - 1) / th;
-    const long tiles = (long)g.nbx * nby;
     OGG_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(ogg_mask_counts), st));
     OGG_HIP_CHECK(hipMemsetAsync(size, 0, (size_t)n * 4, st));
-    mask_tile_kernel<<<(unsigned)tiles, NT, TW * th * sizeof(int), st>>>(g, par);
-    OGG_LAUNCH_CHECK();
-    Faces f{p->ny, p->nx, th, (long)(g.nbx - 1) * p->ny, (nby - 1) * p->nx, 0, 0};
-    if ((p->topology & OGG_MASK_PERIODIC) && p->nx > 2) f.n_p = p->ny;
-    if (p->topology & OGG_MASK_FOLD) f.n_f = p->nx / 2;
-    const long faces = f.n_v + f.n_h + f.n_p + f.n_f;
-    if (faces > 0) {
-        mask_merge_kernel<<<grid_for<NT>(faces, 4096), NT, 0, st>>>(f, par);
-        OGG_LAUNCH_CHECK();
-    }
-    mask_flatten_kernel<<<(unsigned)tiles, NT, 3 * TW * th * sizeof(int), st>>>(g, par, root, size);
-    OGG_LAUNCH_CHECK();
+    const Geo geo{depth, p->fill, p->min_depth, p->mode};
+    const auto tile = [&](const Grid& g, unsigned tiles) { mask_tile_kernel<<<tiles, NT, TW * th * sizeof(int), st>>>(g, geo, par); };
+    if (int e = label_components<true>(p->ny, p->nx, th, p->topology, tile, BothWet{}, par, root, size, st)) return e;
     const long blocks = grid_for<NT>(n, LIST_BLOCKS), chunk = (n + blocks - 1) / blocks;
     mask_list_kernel<<<(unsigned)blocks, NT, 0, st>>>(n, chunk, root, size, components, counts);
     OGG_LAUNCH_CHECK();
@@ -392,8 +257,8 @@ extern "C" int ogg_mask_apply_dev(const ogg_mask_params* p, const double* depth,
     hipStream_t st = ogg::as_stream(stream);
     OGG_HIP_CHECK(hipMemsetAsync(&counts->wet_in, 0, 3 * sizeof(long long), st));
     OGG_HIP_CHECK(hipMemsetAsync(&counts->kept, 0, 3 * sizeof(long long), st));
-    mask_apply_kernel<<<grid_for<NT>(n, APPLY_BLOCKS), NT, 0, st>>>(make_geo(*p, depth, 1), root, size, kept, n_kept, p->keep_min_cells, depth_out, wet,
-                                                  counts);
+    mask_apply_kernel<<<grid_for<NT>(n, APPLY_BLOCKS), NT, 0, st>>>(Geo{depth, p->fill, p->min_depth, p->mode}, n, root, size, kept, n_kept,
+                                                                    p->keep_min_cells, depth_out, wet, counts);
     OGG_LAUNCH_CHECK();
     return OGG_OK;
 }

@@ -30,7 +30,7 @@
 #include "ogg_blocks.h"
 #include "ogg_common.h"
 #include "ogg_keysort.h"
-#include "ogg_sphere.h"
+#include "ogg_sphere_bins.h"
 
 #pragma clang fp contract(off)
 

@@ -1,8 +1,9 @@
 """GPU tests of the basin codes (csrc/ogg_basin.hip, basin_codes.py, Supergrid.basin_codes): code, rule and the rule records bit for
 bit against the sequential floods of tests/basin_definition.py run on the device's own unit vectors: regular grids around the 64 x 32
 tile, a serpentine channel through every tile, diagonal contact, longitudes stated a turn away, invalid centres, every status, the
-rule limits, random masks under random overlapping rules, the knobs, the seed cell against the ocean mask's seed lookup, and main(),
-the function-level path, the file command and Supergrid.basin_codes writing the same bytes."""
+rule limits, random masks under random overlapping rules, the knobs, a rule over the whole sphere against the ocean mask's component
+of its seed cell, the seed cell against the ocean mask's seed lookup, and main(), the function-level path, the file command and
+Supergrid.basin_codes writing the same bytes."""
 import ctypes
 import os
 import subprocess
@@ -256,6 +257,31 @@ def test_knobs_change_no_bit(BC, monkeypatch):
     monkeypatch.setenv("OGG_BASIN_TILE_ROWS", "65")
     with pytest.raises(Exception, match="OGG_BASIN_TILE_ROWS=65"):
         BC.basin_codes_dev(to(cases[0][0]["x"]), to(cases[0][0]["y"]), cases[0][1], cases[0][2], periodic=True, fold=False)
+
+
+# ---- the ocean mask's components ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows", [None, "1"])
+@pytest.mark.parametrize("periodic,fold", [(False, False), (True, False), (False, True), (True, True)])
+@pytest.mark.parametrize("shape", [(33, 129), (1, 65), (5, 7)])   # (5, 7): an odd fold narrower than a tile
+def test_one_rule_over_the_sphere_floods_a_component_of_the_ocean_mask(BC, monkeypatch, shape, periodic, fold, rows):
+    """both callers of the shared labelling agree: the flood of a rule whose box is the sphere is the ocean mask's component of the
+    seed cell, cell for cell, with the size the mask's component list gives it"""
+    from test_gpu_ocean_mask import lib_mask
+    if rows:
+        monkeypatch.setenv("OGG_MASK_TILE_ROWS", rows)
+        monkeypatch.setenv("OGG_BASIN_TILE_ROWS", rows)
+    ny, nx = shape
+    g = sm.latlon_grid(ny, nx, lon0=-33.0, lat0=-21.0, dlon=1.0, dlat=1.0)
+    wet = (np.random.default_rng(1000 * ny + nx).random(shape) < 0.5927).astype(np.uint8)
+    cells = np.flatnonzero(wet)
+    j, i = divmod(int(cells[cells.size // 2]), nx)   # the seed: the centre of the middle wet cell
+    res = run(BC, g["x"], g["y"], wet, [(1,) + centre(g, j, i) + FULL], periodic, fold)
+    comps = np.zeros(ny * nx, np.int64)
+    root, _, _, counts = lib_mask(np.where(wet != 0, 100.0, 0.0), periodic, fold, components=comps)
+    assert res["records"]["seed_cell"][0] == j * nx + i and root[j, i] >= 0
+    assert np.array_equal(res["code"], (root == root[j, i]).astype(np.uint8))
+    size = {2**31 - 1 - int(e & 0xFFFFFFFF): int(e >> 32) for e in comps[:counts["components"]]}
+    assert res["records"]["cells"][0] == size[int(root[j, i])]
 
 
 # ---- the seed cell --------------------------------------------------------------------------------------------------

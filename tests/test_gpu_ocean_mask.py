@@ -1,7 +1,7 @@
 """GPU tests of the ocean mask (csrc/ogg_mask.hip, ocean_mask.py, Supergrid.ocean_mask): every root bit-identical to the numpy
-definition in tests/ocean_mask_definition.py on random wet sets around the percolation threshold, on edge shapes, under every
-combination of seam and fold, on a serpentine channel that fills a 1/8 degree grid, and under every setting of the tile knob; main()'s
---ocean_mask_file at 1 degree with a lake, a sea behind a sill and an open ocean, against the definition, the function path, the
+definition in tests/ocean_mask_definition.py on random wet sets around the percolation threshold, on edge shapes, on shapes around the
+64 x 32 tile, under every combination of seam and fold, on a serpentine channel that fills a 1/8 degree grid, and under every setting
+of the tile knob; main()'s --ocean_mask_file at 1 degree with a lake, a sea behind a sill and an open ocean, against the definition, the function path, the
 file-based command and the virtual ranks."""
 import ctypes
 import os
@@ -17,8 +17,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def lib_mask(depth, periodic=False, fold=False, min_depth=0.0, mode="mask", keep_min_cells=0):
-    """ogg_ocean_mask with the topology given (no seeds): (root, depth, wet, counts)"""
+def lib_mask(depth, periodic=False, fold=False, min_depth=0.0, mode="mask", keep_min_cells=0, components=None):
+    """ogg_ocean_mask with the topology given (no seeds): (root, depth, wet, counts); components: an int64 array that takes the
+    component list, (cells << 32) | (INT32_MAX - root), largest first"""
     from ocean_model_grid_generator_amd import _lib as L
     from ocean_model_grid_generator_amd import ocean_mask as M
     d = np.ascontiguousarray(depth, dtype=np.float64)
@@ -28,7 +29,7 @@ def lib_mask(depth, periodic=False, fold=False, min_depth=0.0, mode="mask", keep
     wet = np.empty(d.shape, np.uint8)
     c = L.MaskCounts()
     L.call("ogg_ocean_mask", ctypes.byref(p), d.ctypes.data, None, None, 0, None, out.ctypes.data, wet.ctypes.data, root.ctypes.data,
-           None, None, 0, ctypes.byref(c))
+           None, None if components is None else components.ctypes.data, 0 if components is None else components.size, ctypes.byref(c))
     return root, out, wet, {f: int(getattr(c, f)) for f in L.MASK_COUNT_FIELDS}
 
 
@@ -63,6 +64,15 @@ def test_shapes_match_definition(hip, shape):
     rng = np.random.default_rng(shape[0] * 7 + shape[1])
     for periodic, fold in ((False, False), (True, True)):
         check(rng.random(shape) < 0.5927, periodic, fold)
+
+
+@pytest.mark.parametrize("ny", [1, 31, 32, 33, 65])
+@pytest.mark.parametrize("nx", [1, 2, 63, 64, 65, 129])
+def test_shapes_around_the_tile_match_definition(hip, ny, nx):
+    """one tile and the first cells of a second one in each direction; bands one and two cells wide, where the seam adds no face"""
+    rng = np.random.default_rng(1000 * ny + nx)
+    for periodic, fold in ((False, False), (True, True)):
+        check(rng.random((ny, nx)) < 0.5927, periodic, fold)
 
 
 @pytest.mark.parametrize("periodic,fold", [(False, False), (True, True)])
