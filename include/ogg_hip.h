@@ -412,6 +412,40 @@ int ogg_bswap64_dev(long n, const void* src, void* dst, void* stream);
  * one reduction (the generic stencil kernel's form) / from two, against numpy.mod's own fmod form.  (8, 10, 11, 12 -- restatements that no kernel uses any more -- were removed with them in round 4: OGG_EARG.)  The number of k < n for which the
  * restatement differs IN ANY BIT from the library's own function is ADDED to *n_diff (device memory, 8 bytes, zeroed by the caller). */
 int ogg_libm_check_dev(int which, long n, const double* x, const double* y, unsigned long long* n_diff, void* stream);
+/* Test-only evaluation of the scalar device helpers that DEPART from the library on purpose (ogg_math.h, ogg_bipolar_dev.h,
+ * ogg_dpole_dev.h), and of the library functions they fall back to: out[k] = helper(x[k] [, y[k]]), the helper's VALUE, so that a test can
+ * hold it against an extended-precision truth (tests/test_gpu_math_helpers.py).  Element k is computed by thread k of 256-thread
+ * workgroups: the 64 consecutive elements 64 w .. 64 w + 63 share wave w, so the caller decides what every wave sees -- several helpers
+ * choose between their own form and the library's by one ballot per wave.  The threads behind n of the last wave recompute element n - 1
+ * (they take part in the ballots and the lane shifts with a value the wave already holds); only OGG_MATH_WAVE_PREV_TAIL / _NEXT_TAIL let
+ * them return first.  x, y, out: device memory, n doubles each (y may be NULL for the one-argument codes).
+ *   OGG_MATH_XCD_CONTIGUOUS: b = x[k], n = y[k] (integers held in doubles); the result is an integer held in a double.
+ *   OGG_MATH_HOM_ARC / _HOM_TAN: s = x[k], w = y[k], a power of two of either sign: homogeneous_arc (its tangent) of a = (0, 0, |w|) and
+ *   b = (s |w|, 0, |w|) for w > 0, (0, s |w|, |w|) for w < 0 -- the family whose cross products are exact, tan(theta) = |s|. */
+#define OGG_MATH_DIV_PI180 0
+#define OGG_MATH_RCP_C3 1
+#define OGG_MATH_RSQRT_C3 2
+#define OGG_MATH_ATAN_SERIES14 3
+#define OGG_MATH_ATAN_SERIES17 4
+#define OGG_MATH_ATAN_CAP 5
+#define OGG_MATH_ATAN2_ANGLE 6      /* atan2_angle(y[k], x[k]) */
+#define OGG_MATH_WAVE_PREV 7
+#define OGG_MATH_WAVE_NEXT 8
+#define OGG_MATH_WAVE_PREV_TAIL 9   /* the threads behind n have returned before the shift */
+#define OGG_MATH_WAVE_NEXT_TAIL 10
+#define OGG_MATH_XCD_CONTIGUOUS 11
+#define OGG_MATH_LIB_ATAN 12        /* the device library's atan */
+#define OGG_MATH_ATAN_LIB 13        /* atan_lib, its restatement */
+#define OGG_MATH_WAVE_NEXT_INT 14   /* the int overload of wave_next on (int)x[k] */
+#define OGG_MATH_SIN_TINY 32
+#define OGG_MATH_ASIN_TINY 33
+#define OGG_MATH_COS_CAP 34
+#define OGG_MATH_HOM_ARC 35
+#define OGG_MATH_HOM_TAN 36         /* homogeneous_tan, the tangent homogeneous_arc forms */
+#define OGG_MATH_LIB_SIN 37         /* the device library's sin, asin, cos (the out-of-line copies the helpers fall back to) */
+#define OGG_MATH_LIB_ASIN 38
+#define OGG_MATH_LIB_COS 39
+int ogg_math_eval_dev(int which, long n, const double* x, const double* y, double* out, void* stream);
 /* The five sums behind metrics_error (OGG:732-770) of one sub-grid band, on the device and deterministic:
  * out5 = { sum(area), sum(dy[:, col_a]), sum(dy[:, col_b]) (0 when col_b < 0), sum(dx[0, :]) if want_first_row,
  * sum(dx[n_dx_rows-1, :]) if want_last_row }.  dx: n_dx_rows x ni, dy: n_cell_rows x (ni+1), area: n_cell_rows x ni; out5 is a

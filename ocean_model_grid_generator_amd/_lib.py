@@ -16,6 +16,11 @@ OGG_OK, OGG_EORDER, OGG_ESHAPE, OGG_EHIP, OGG_ENOMEM, OGG_EARG = 0, 1, 2, 3, 4, 
 DP_ARC_LITERAL, DP_ARC_CHORD = 0, 1   # OGG_DP_ARC_* of include/ogg_hip.h
 SYM_DEFAULT, SYM_MIRROR, SYM_NONE = 0, 1, 2   # OGG_SYM_* of include/ogg_hip.h
 
+# OGG_MATH_* of include/ogg_hip.h: the codes of ogg_math_eval_dev (test-only)
+MATH = {"div_pi180": 0, "rcp_c3": 1, "rsqrt_c3": 2, "atan_series14": 3, "atan_series17": 4, "atan_cap": 5, "atan2_angle": 6,
+        "wave_prev": 7, "wave_next": 8, "wave_prev_tail": 9, "wave_next_tail": 10, "xcd_contiguous": 11, "lib_atan": 12, "atan_lib": 13, "wave_next_int": 14,
+        "sin_tiny": 32, "asin_tiny": 33, "cos_cap": 34, "hom_arc": 35, "hom_tan": 36, "lib_sin": 37, "lib_asin": 38, "lib_cos": 39}
+
 c_long, c_int, c_double, c_void_p, c_longlong = ctypes.c_long, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_longlong
 _dp = ctypes.POINTER(ctypes.c_double)
 _llp = ctypes.POINTER(ctypes.c_longlong)
@@ -351,6 +356,7 @@ SIGNATURES = {
     "ogg_fill_dev": [c_long, c_double, c_void_p, c_void_p],
     "ogg_bswap64_dev": [c_long, c_void_p, c_void_p, c_void_p],
     "ogg_libm_check_dev": [c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_math_eval_dev": [c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_metrics_sums_dev": [c_long, c_long, c_long, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_void_p],
     "ogg_grid_quality_band_dev": [ctypes.POINTER(QualityBand), c_void_p, c_long, c_void_p, c_void_p],
     "ogg_grid_quality": [ctypes.POINTER(QualityBand), ctypes.POINTER(QualityResult)],

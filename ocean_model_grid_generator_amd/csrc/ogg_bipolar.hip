@@ -47,9 +47,54 @@ __global__ void libm_check_kernel(int which, long n, const double* __restrict__ 
     const unsigned long long m = __ballot(diff);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(n_diff, (unsigned long long)__popcll(m));
 }
+
+// ogg_math_eval_dev: the VALUE of a helper of ogg_math.h / of this unit's device header, one element per thread.  The threads behind n
+// recompute element n - 1 (clamped index, no early return: the ballots and lane shifts see a full wave), except for the two _TAIL codes.
+__global__ __launch_bounds__(256) void math_eval_kernel(int which, long n, const double* __restrict__ x, const double* __restrict__ y,
+                                                         double* __restrict__ out) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if ((which == OGG_MATH_WAVE_PREV_TAIL || which == OGG_MATH_WAVE_NEXT_TAIL) && k >= n) return;
+    const long kc = (k < n) ? k : n - 1;
+    const double a = x[kc], b = y ? y[kc] : 0.0;
+    double r = 0.0;
+    switch (which) {   // wave-uniform
+        case OGG_MATH_DIV_PI180: r = div_pi180(a); break;
+        case OGG_MATH_RCP_C3: r = rcp_c3(a); break;
+        case OGG_MATH_RSQRT_C3: r = rsqrt_c3(a); break;
+        case OGG_MATH_ATAN_SERIES14: r = atan_series<14>(a); break;
+        case OGG_MATH_ATAN_SERIES17: r = atan_series<17>(a); break;
+        case OGG_MATH_ATAN_CAP: r = atan_cap(a); break;
+        case OGG_MATH_ATAN2_ANGLE: r = atan2_angle(b, a); break;
+        case OGG_MATH_WAVE_PREV:
+        case OGG_MATH_WAVE_PREV_TAIL: r = wave_prev(a); break;
+        case OGG_MATH_WAVE_NEXT:
+        case OGG_MATH_WAVE_NEXT_TAIL: r = wave_next(a); break;
+        case OGG_MATH_XCD_CONTIGUOUS: r = (double)xcd_contiguous((long)a, (long)b); break;
+        case OGG_MATH_LIB_ATAN: r = atan(a); break;
+        case OGG_MATH_ATAN_LIB: r = atan_lib(a); break;
+        case OGG_MATH_WAVE_NEXT_INT: r = (double)wave_next((int)a); break;
+        default: break;
+    }
+    if (k < n) out[k] = r;
+}
 }  // namespace
 
+namespace ogg {
+int math_eval_dpole(int which, long n, const double* x, const double* y, double* out, hipStream_t stream);   // ogg_dpole.hip
+}
+
 extern "C" {
+
+int ogg_math_eval_dev(int which, long n, const double* x, const double* y, double* out, void* stream) {
+    const bool here = which >= OGG_MATH_DIV_PI180 && which <= OGG_MATH_WAVE_NEXT_INT, there = which >= OGG_MATH_SIN_TINY && which <= OGG_MATH_LIB_COS;
+    const bool two = which == OGG_MATH_ATAN2_ANGLE || which == OGG_MATH_XCD_CONTIGUOUS || which == OGG_MATH_HOM_ARC || which == OGG_MATH_HOM_TAN;
+    OGG_REQUIRE((here || there) && n >= 0 && x && out && (!two || y), OGG_EARG, "ogg_math_eval: bad argument");
+    if (n == 0) return OGG_OK;
+    if (there) return ogg::math_eval_dpole(which, n, x, y, out, ogg::as_stream(stream));
+    math_eval_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ogg::as_stream(stream)>>>(which, n, x, y, out);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
 
 int ogg_libm_check_dev(int which, long n, const double* x, const double* y, unsigned long long* n_diff, void* stream) {
     OGG_REQUIRE(which >= 0 && which <= 14 && which != 8 && !(which >= 10 && which <= 12) && n >= 0 && x && n_diff &&

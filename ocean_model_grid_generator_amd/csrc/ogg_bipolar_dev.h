@@ -249,7 +249,9 @@ OGG_DEV double atan_series(double r) {
 // atan(u) for 0 <= u <= 0.3 -- u = rp tan(chi/2) <= rp = tan(13 degrees) = 0.23 for every cap main() builds -- from 14 terms of the odd
 // Taylor series in Horner form (the first omitted term is below 5e-18 relative): 0.57 ulp at worst (validated on the host against
 // atanl on 3e7 arguments; glibc: 0.52).  A wave with any larger argument (a cap that starts south of 56.6 degrees) takes ocml's atan,
-// behind one ballot.
+// behind one ballot.  Both are tests on the device (tests/test_gpu_math_helpers.py, against a 50-digit truth): 0.550 ulp at worst over
+// 2.6e5 uniform arguments of [0, 0.3], 0.4997 log-uniformly down to the subnormals, bound 0.57; a wave with one lane above 0.3 (its upper
+// neighbour, an infinity, a NaN) has ocml's bits in all 64 lanes.
 OGG_DEV double atan_cap(double u) {
     if (__builtin_expect(__ballot(!(u <= 0.3)) != 0ull, 0)) return atan(u);
     return atan_series<14>(u);
@@ -258,7 +260,11 @@ OGG_DEV double atan_cap(double u) {
 // atan2(y, x) for the fused angle_x (finite arguments): octant reduction with ONE reciprocal -- r = (mn - mx) / (mn + mx) when
 // mn / mx > tan(pi/8), mn / mx otherwise, so |r| <= tan(pi/8) -- and 17 terms of the odd series: 6e-16 rad at worst (host, 3e7
 // arguments), which is 3e-14 degrees where the fused angle is held to 1e-10 (it already takes cos(phi) algebraically).  atan2(0, 0) = 0
-// like numpy's arctan2(+0, +0).
+// like numpy's arctan2(+0, +0), with the sign of y.  On the device (tests/test_gpu_math_helpers.py, 50-digit truth): 5.4e-16 rad at worst
+// over 2.6e5 pairs of either sign with magnitudes 2^-300 .. 2^300 (|y| = |x|, the neighbours of mn = tan(pi/8) mx, the axes and the four
+// signed-zero pairs among them), bound 6e-16; the sign bit is that of y; and for x > 0, |y| <= 0.4 x the angle is good to 1.82 ulp OF
+// ITSELF (bound 4: one reciprocal of <= 1 ulp, one product, one fma), so small angles do not drown in the absolute figure.  The series
+// alone: 1.9e-16 rad (3.4 ulp at the end of its range, where the first omitted term is r^37 / 37).
 OGG_DEV double atan2_angle(double y, double x) {
     const double ax = fabs(x), ay = fabs(y);
     const double mx = fmax(ax, ay), mn = fmin(ax, ay);
@@ -410,7 +416,9 @@ OGG_DEV void bipolar_mesh_body(const MeshParams& m, BpRow* s_row, long bx, long 
             a = div_pi180(a);
             double* __restrict__ ra = angle + jl * ni1;
             if (out) ra[i] = a;
-            if (img) ra[h2 - i] = -a, ra[h2 + i] = a, ra[Ni - i] = -a;
+            // (0 - a, not -a: on the row j = 0, where every column has the same latitude, the angle is +0.0 at every column of the reference and
+            // the mirror image of +0.0 is +0.0)
+            if (img) ra[h2 - i] = 0.0 - a, ra[h2 + i] = a, ra[Ni - i] = 0.0 - a;
         }
     }
 }

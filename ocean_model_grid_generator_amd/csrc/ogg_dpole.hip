@@ -400,7 +400,42 @@ int check_cap(long ni, long nj) {
     return OGG_OK;
 }
 
+// ogg_math_eval_dev, the helpers of ogg_dpole_dev.h (the same launch shape and tail handling as its sibling in ogg_bipolar.hip)
+__global__ __launch_bounds__(256) void math_eval_dpole_kernel(int which, long n, const double* __restrict__ x, const double* __restrict__ y,
+                                                               double* __restrict__ out) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long kc = (k < n) ? k : n - 1;
+    const double a = x[kc], b = y ? y[kc] : 0.0;
+    double r = 0.0;
+    switch (which) {   // wave-uniform
+        case OGG_MATH_SIN_TINY: r = sin_tiny(a); break;
+        case OGG_MATH_ASIN_TINY: r = asin_tiny(a); break;
+        case OGG_MATH_COS_CAP: r = cos_cap(a); break;
+        case OGG_MATH_HOM_ARC:
+        case OGG_MATH_HOM_TAN: {
+            const double w = fabs(b), sw = a * w;   // w a power of two: exact
+            const Hom ha = {0.0, 0.0, w};
+            const Hom hb = {(b > 0.0) ? sw : 0.0, (b > 0.0) ? 0.0 : sw, w};
+            r = (which == OGG_MATH_HOM_ARC) ? homogeneous_arc(ha, hb) : homogeneous_tan(ha, hb);
+            break;
+        }
+        case OGG_MATH_LIB_SIN: r = lib_sin(a); break;
+        case OGG_MATH_LIB_ASIN: r = lib_asin(a); break;
+        case OGG_MATH_LIB_COS: r = lib_cos(a); break;
+        default: break;
+    }
+    if (k < n) out[k] = r;
+}
+
 }  // namespace
+
+namespace ogg {
+int math_eval_dpole(int which, long n, const double* x, const double* y, double* out, hipStream_t stream) {
+    math_eval_dpole_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(which, n, x, y, out);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+}  // namespace ogg
 
 extern "C" {
 

@@ -135,8 +135,11 @@ OGG_DEV double qavg_1d(const double* y) {  // OGG:207-222
 
 // sin(x) and asin(x) for |x| < 2^-13 from three terms of their series: the truncation error is below 2^-80 relative, so the
 // result is the correctly rounded value up to the rounding of the last fma (<= 0.5000001 ulp) -- inside the <1 ulp band of
-// any libm, at 5 instructions instead of ocml's range-reduced sin / table-free asin.  The haversine of two probes that are
-// 2e-6 rad apart only ever sees such arguments; anything larger goes to ocml.
+// any libm, at 5 instructions instead of ocml's range-reduced sin / table-free asin (sin_tiny: 6, the copysign that keeps -0.0).  The
+// haversine of two probes that are 2e-6 rad apart only ever sees such arguments; anything larger goes to ocml, lane by lane.  On the
+// device (tests/test_gpu_math_helpers.py, 50-digit truth, 2.6e5 arguments of either sign log-uniform from 2^-13 down to the subnormals):
+// sin_tiny 0.49953 ulp, asin_tiny 0.499986 ulp (bound 0.5001), a zero keeps its sign, and 2^-13, its lower neighbour and everything
+// larger have ocml's bits.
 // the library functions behind the range-specialised forms below, out of line: inlined, the literals of their polynomials (a few dozen
 // doubles) are hoisted out of the quadrature's loop into vector registers for branches that a fine grid never takes
 __device__ __attribute__((noinline)) double lib_sin(double x) { return sin(x); }
@@ -146,7 +149,7 @@ __device__ __attribute__((noinline)) double lib_cos(double x) { return cos(x); }
 OGG_DEV double sin_tiny(double x) {
     if (fabs(x) < 0x1p-13) {
         const double x2 = x * x;
-        return fma(x * x2, fma(x2, 1.0 / 120.0, -1.0 / 6.0), x);
+        return copysign(fma(x * x2, fma(x2, 1.0 / 120.0, -1.0 / 6.0), x), x);   // (-0.0: the correction term is +0.0 there, and +0 + -0 = +0)
     }
     return lib_sin(x);
 }
@@ -160,7 +163,9 @@ OGG_DEV double asin_tiny(double x) {
 
 // cos(x) for the latitudes of a southern cap: x in (-3 pi/4, -pi/4) and not within 2^-20 of -pi/2.  cos x = sin(x + pi/2): the 33-bit head
 // of pi/2 is added exactly, its tail in double-double, and the sum goes through the fdlibm sine kernel with tail -- 0.73 ulp at worst
-// (validated on the host against cosl on 2.7e7 arguments; glibc: 0.52, and the two differ in 2 % of the arguments, as ocml and glibc do),
+// (validated on the host against cosl on 2.7e7 arguments; on the device, against a 50-digit truth, 0.699 ulp over 2.6e5 arguments of the
+// range -- a quarter of them log-uniformly towards -pi/2 -- and the neighbours of its four limits, tests/test_gpu_math_helpers.py, where a
+// wave with one lane outside has ocml's bits in all 64; glibc: 0.52, and the two differ in 2 % of the arguments, as ocml and glibc do),
 // 20 instructions instead of ocml's range-reduced cosine.  Taken only when the WHOLE wave is in range (one ballot): a cap row always is,
 // except next to the pole itself; everything else goes to ocml.
 OGG_DEV double cos_cap(double x) {
@@ -571,11 +576,9 @@ OGG_DEV Hom dp_homogeneous(double r, cplx ep, const DpConst& c, double inv_rj) {
     return h;
 }
 
-// Great-arc distance of two nearby points a, b given along (P, Q, -D): tan(theta) = |a x b| / (a . b); theta = atan(tan theta)
-// from three terms of the series (the probes of the eps = 1e-3 stencil are ~1e-6 rad apart; exact to 1e-30 below 1e-3).  One
-// reciprocal square root per arc, seed + one Newton step (2^-50: the cross product itself carries 1e-10 of cancellation):
-// tan theta = |a x b|^2 / sqrt(|a x b|^2 (a . b)^2).
-OGG_DEV double homogeneous_arc(const Hom& a, const Hom& b) {
+// tan(theta) of the arc between two nearby points a, b given along (P, Q, -D): |a x b| / (a . b) = |a x b|^2 / sqrt(|a x b|^2 (a . b)^2),
+// one reciprocal square root per arc, from the hardware seed and one third-order step (rsqrt_c3, <= 1 ulp).  0 for parallel vectors.
+OGG_DEV double homogeneous_tan(const Hom& a, const Hom& b) {
     const double c1 = fma(a.D, b.Q, -(a.Q * b.D));
     const double c2 = fma(a.P, b.D, -(a.D * b.P));
     const double c3 = fma(a.P, b.Q, -(a.Q * b.P));
@@ -583,9 +586,17 @@ OGG_DEV double homogeneous_arc(const Hom& a, const Hom& b) {
     if (cc == 0.0) return 0.0;
     const double dot = fma(a.P, b.P, fma(a.Q, b.Q, a.D * b.D));
     const double x = cc * (dot * dot);
-    double y = __builtin_amdgcn_rsq(x);
-    y = y * fma(-0.5 * x * y, y, 1.5);
-    const double t = cc * y;                   // tan(theta)
+    return cc * rsqrt_c3(x);
+}
+
+// Great-arc distance of two nearby points: theta = atan(tan theta) from three terms of the series (the probes of the eps = 1e-3 stencil
+// are ~1e-6 rad apart; exact to 1e-30 below 1e-3).  Measured on the device on the family of arguments whose cross products are exact (a
+// along the axis, b = (s, 0, 1) or (0, s, 1), scaled by powers of two: tan theta = |s|; tests/test_gpu_math_helpers.py): theta within
+// 3.7e-16 relative of atan|s| (the tangent within 2.2e-16 of |s|; bound 2^-49) for |s| from 2^-40 to 1, on either side of the switch
+// below; a lane at or above the switch has the bits of atan_lib of its tangent.
+OGG_DEV double homogeneous_arc(const Hom& a, const Hom& b) {
+    const double t = homogeneous_tan(a, b);
+    if (t == 0.0) return 0.0;
     const double q = t * t;
     double th = t * fma(q, fma(q, 1.0 / 5.0, -1.0 / 3.0), 1.0);
     // grids so coarse that two probes are more than 1e-3 rad apart (a few dozen columns): the whole wave takes the library atan, behind a

@@ -45,13 +45,24 @@ OGG_DEV double pymod360(double a) {
     return (r == 0.0) ? 0.0 : r;
 }
 
-// a / PI_180 for finite a, correctly rounded -- the same bits as the IEEE division a / kPi180 -- in 3 instructions instead
-// of the 11 of a full fp64 divide (division by a constant: q = a rc, then one residual correction; checked against the
-// divide instruction on 3e8 random operands over 40 binades).
+// a / PI_180, correctly rounded -- the same bits as the IEEE division a / kPi180, the sign of a zero included -- for 2^-1000 <= |a| <=
+// 2^1000 and for +-0.0, in 3 instructions instead of the 11 of a full fp64 divide (division by a constant: q = a rc, then one residual
+// correction).  Bit-identity is a test on the device (tests/test_gpu_math_helpers.py: both zeros, 2^20 operands of either sign over those
+// 2000 binades, the radians range +-2 pi densely, every value numpy.arctan2 takes on a table of signed zeros, equal magnitudes and axis
+// points).
+//
+// The residual is formed NEGATED, nr = fma(q, kPi180, -a), and applied as fma(-nr, rc, q): for a = -+0.0 nr is +0.0 and the result is
+// -0 rc + q = q, the zero of a (the sign numpy's arctan2(-0.0, positive) / PI_180 has, which ogg_angle_x must return for a caller's
+// arrays); for every other a it is the residual's exact negative, so the bits do not depend on the form.
+//
+// Outside that domain it is NOT the division: |a| above about 3.1e306, and the infinities, give NaN (q overflows and the residual is inf -
+// inf) where the division gives an infinity, and quotients in the subnormal range (|a| below about 2^-1016) can differ by one ulp (the
+// residual is no longer exact).  No caller comes near either: the arguments are angles in radians.
 OGG_DEV double div_pi180(double a) {
     constexpr double rc = 1.0 / kPi180;
     const double q = a * rc;
-    return fma(fma(-q, kPi180, a), rc, q);
+    const double nr = fma(q, kPi180, -a);   // -(a - q PI_180)
+    return fma(-nr, rc, q);
 }
 
 // OGG:682-684 mdist: positive distance modulo 360.
@@ -150,8 +161,10 @@ OGG_DEV double cabs_np(cplx w) {
 // 1/x and 1/sqrt(x) for NORMAL, positive x from the hardware seed (v_rcp_f64 / v_rsq_f64, relative error e <= 2^-24 measured,
 // scripts/microbench/rcp_rsq_accuracy.hip) and ONE third-order step -- 1/x = y (1 + e + e^2 + ...), x^(-1/2) = y (1 + e/2 + 3 e^2/8 + ...)
 // with e = 1 - x y (resp. 1 - x y^2) exact from the fma -- which leaves e^3 = 2^-72 of truncation: 0.5 / 1.0 ulp at worst over 1.7e7
-// operands of 680 binades (two Newton steps: 0.5 / 1.75 ulp and one / two more instructions; that micro-benchmark keeps them for
-// comparison).  No denormal scaling, no fix-up.  Only used where a kernel documents that it departs from the reference's literal
+// operands of 680 binades in that micro-benchmark (two Newton steps: 0.5 / 1.75 ulp and one / two more instructions; it keeps them for
+// comparison), and as a test on the device against a 50-digit truth (tests/test_gpu_math_helpers.py, ogg_math_eval_dev; 5.2e5 operands of
+// 2^-340 .. 2^340 and every power of two there with its neighbours): rcp_c3 0.4999997 ulp (bound 0.501: the last fma's 0.5 plus e^3),
+// rsqrt_c3 0.9913 ulp (bound 1.0).  No denormal scaling, no fix-up.  Only used where a kernel documents that it departs from the reference's literal
 // operation sequence (bp_point_fast, the mesh's tan(acos(A)/2), atan2_angle); everything else uses IEEE division and sqrt.
 OGG_DEV double rcp_c3(double x) {
     const double y = __builtin_amdgcn_rcp(x);
@@ -345,7 +358,11 @@ OGG_DEV double atan2_lib_any(double y, double x) {
 
 // Neighbour lanes of a wave64 through DPP wave shifts (gfx9: wave_shr:1 = 0x138, wave_shl:1 = 0x130): two VALU moves per
 // double instead of two ds_bpermute round trips through the LDS crossbar.  The end lanes keep their own value, like
-// __shfl_up / __shfl_down with delta 1.
+// __shfl_up / __shfl_down with delta 1, and both words of the double travel together.  Called in uniform control flow (every kernel
+// clamps its index instead of returning early).  Where the upper lanes of a wave HAVE returned, a lane whose source lane is inactive
+// is not written (bound_ctrl is off) and keeps its own value too: wave_next at the last active lane -- the left neighbour of the first
+// returned lane -- returns that lane's own x, exactly as lane 63 does in a full wave; wave_prev is unaffected, its source lanes lie below.
+// Both cases are tests on the device (tests/test_gpu_math_helpers.py).
 OGG_DEV double wave_prev(double x) {  // lane l gets the value of lane l-1
     int lo = __double2loint(x), hi = __double2hiint(x);
     lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false);
