@@ -28,7 +28,7 @@ extern "C" {
 #define OGG_ENOMEM 4 /* device allocation failed */
 #define OGG_EARG 5   /* null pointer / invalid scalar */
 
-#define OGG_DP_ARC_LITERAL 0 /* arc form of the displaced-pole quadrature: see ogg_displaced_pole_metrics_quad_form_ws_dev */
+#define OGG_DP_ARC_LITERAL 0 /* arc form of the displaced-pole quadrature: see ogg_displaced_pole_metrics_quad_form_sym_ws_dev */
 #define OGG_DP_ARC_CHORD 1
 
 /* Mirror symmetry of the two caps (the `symmetry` field of ogg_bipolar_band / ogg_dpole_band, the *_sym_* entry points).
@@ -48,8 +48,37 @@ const char* ogg_last_error(void);
 /* "ogg_hip <version> (gfx950) src <hash>": <hash> = first 12 hex digits of the sha256 over the kernel sources the library was built
  * from (csrc/build.py source_hash()); profiles/valu_counters.json and hbm_traffic.json record the hash they were collected with */
 const char* ogg_version(void);
-/* sizeof(ogg_latlon_band) for which = 0, sizeof(ogg_bipolar_band) for which = 1, sizeof(ogg_dpole_band) for which = 2 (-1
- * otherwise): lets a binding verify its layout */
+/* sizeof of every struct this header defines, so that a binding can verify its layout: OGG_ABI_<NAME> is the code of ogg_<name>,
+ * OGG_ABI_N one past the last; any other value gives -1.  A struct added to this header takes the next code. */
+#define OGG_ABI_LATLON_BAND 0
+#define OGG_ABI_BIPOLAR_BAND 1
+#define OGG_ABI_DPOLE_BAND 2
+#define OGG_ABI_QUALITY_EXTREMUM 3
+#define OGG_ABI_GRID_QUALITY_RESULT 4
+#define OGG_ABI_QUALITY_BAND 5
+#define OGG_ABI_TOPOG_SOURCE 6
+#define OGG_ABI_TOPOG_BAND 7
+#define OGG_ABI_TOPOG_RECORD 8
+#define OGG_ABI_TOPOG_PLANE_RECORD 9
+#define OGG_ABI_XGRID_ATM 10
+#define OGG_ABI_XGRID_BAND 11
+#define OGG_ABI_XGRID_COUNTS 12
+#define OGG_ABI_MASK_PARAMS 13
+#define OGG_ABI_MASK_COUNTS 14
+#define OGG_ABI_REMAP_PARAMS 15
+#define OGG_ABI_REMAP_COUNTS 16
+#define OGG_ABI_RUNOFF_PARAMS 17
+#define OGG_ABI_RUNOFF_COUNTS 18
+#define OGG_ABI_REGRID_PARAMS 19
+#define OGG_ABI_REGRID_COUNTS 20
+#define OGG_ABI_BILINEAR_PARAMS 21
+#define OGG_ABI_COAST_PARAMS 22
+#define OGG_ABI_COAST_COUNTS 23
+#define OGG_ABI_BASIN_PARAMS 24
+#define OGG_ABI_BASIN_RULE 25
+#define OGG_ABI_BASIN_RULE_RECORD 26
+#define OGG_ABI_BASIN_COUNTS 27
+#define OGG_ABI_N 28
 long ogg_abi_sizeof(int which);
 int ogg_device_count(int* count);
 int ogg_set_device(int device);
@@ -141,9 +170,6 @@ int ogg_latlon_supergrid_multi_dev(int n_bands, const ogg_latlon_band* bands, lo
 long ogg_latlon_rows_workspace_bytes(int n_bands, const ogg_latlon_band* bands, long ni1);
 int ogg_latlon_supergrid_rows_ws_dev(int n_bands, const ogg_latlon_band* bands, long ni1, double lon0, double lenlon, double Re,
                                      int metrics, void* workspace, long workspace_bytes, void* stream);
-int ogg_latlon_supergrid_dev(long n_pt_rows, long n_cell_rows, long ni1, const double* lat1d, const double* lon1d, double Re,
-                             int metrics, double* x, double* y, double* dx, double* dy, double* area, double* angle,
-                             void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Murray bipolar Arctic cap
@@ -156,19 +182,18 @@ int ogg_bipolar_projection_dev(long n, const double* lamg, const double* phig, d
                                int metrics_only, double* lams, double* phis, double* h_i_inv, double* h_j_inv,
                                void* stream);
 
-/* generate_bipolar_cap_mesh (OGG:103-122), rows j0..j0+nrows-1 of the (Nj+1) x (Ni+1) mesh.
- * lams, phis: nrows x (Ni+1).  h_i_inv: nrows x Ni and h_j_inv: nrows x (Ni+1), already scaled as OGG:119-120
- * (h_j_inv row Nj is computed but dropped by the reference; rows >= Nj are not written); either may be NULL. */
-int ogg_bipolar_cap_mesh_dev(long Ni, long Nj, double lat0_bp, double lon_bp, long j0, long nrows, double* lams,
-                             double* phis, double* h_i_inv, double* h_j_inv, void* stream);
-/* same, also writing angle_dx = angle_x(lams, phis) (nrows x (Ni+1); NULL to skip) without reading the mesh back */
-int ogg_bipolar_cap_mesh_angle_dev(long Ni, long Nj, double lat0_bp, double lon_bp, long j0, long nrows, double* lams,
-                                   double* phis, double* h_i_inv, double* h_j_inv, double* angle_dx, void* stream);
-/* same with the column symmetry stated by the caller (OGG_SYM_*; the forms above ask for OGG_SYM_DEFAULT): mirrored, the columns
- * [0, Ni/4] (+ 2 degrees beyond the pole meridian) are evaluated and written to their three images, the columns next to the fold lines
- * and within 2 degrees of the pole meridians at their own positions */
+/* generate_bipolar_cap_mesh (OGG:103-122), rows j0..j0+nrows-1 of the (Nj+1) x (Ni+1) mesh, one launch.
+ *   lams, phis   nrows x (Ni+1)
+ *   h_i_inv      nrows x Ni, h_j_inv: nrows x (Ni+1), already scaled as OGG:119-120 (h_j_inv row Nj is computed but dropped by the
+ *                reference; rows >= Nj are not written); either may be NULL
+ *   angle_dx     angle_x(lams, phis) (OGG:719-729) of the same rows, nrows x (Ni+1), without reading the mesh back; NULL to skip
+ *   symmetry     OGG_SYM_* (top of this file).  Mirrored, the columns [0, Ni/4] (+ 2 degrees beyond the pole meridian) are evaluated and
+ *                written to their three images, the columns next to the fold lines and within 2 degrees of the pole meridians at their
+ *                own positions
+ * No workspace, no allocation. */
 int ogg_bipolar_cap_mesh_angle_sym_dev(long Ni, long Nj, double lat0_bp, double lon_bp, long j0, long nrows, int symmetry, double* lams,
                                        double* phis, double* h_i_inv, double* h_j_inv, double* angle_dx, void* stream);
+/* the whole mesh into host arrays, under the reference's own name (symmetry = OGG_SYM_DEFAULT) and with the symmetry stated */
 int ogg_bipolar_cap_mesh(long Ni, long Nj, double lat0_bp, double lon_bp, double* lams, double* phis,
                          double* h_i_inv, double* h_j_inv);
 int ogg_bipolar_cap_mesh_sym(long Ni, long Nj, double lat0_bp, double lon_bp, int symmetry, double* lams, double* phis,
@@ -181,36 +206,29 @@ int ogg_bipolar_cap_ij_array(long n_i, const double* i, long n_j, const double* 
 int ogg_bipolar_cap_ij_array_dev(long n_i, const double* i, long n_j, const double* j, long Ni, long Nj, double lat0_bp,
                                  double lon_bp, double rp, double* h_i_inv, double* h_j_inv, void* stream);
 
-/* bipolar_cap_metrics_quad_fast (OGG:136-188): Gauss-Lobatto quadrature (order 2..5) of the analytic scale
- * factors.  Band form: dxq rows j0..j0+n_dx_rows-1 of (ny+1) x nx; dyq rows j0..j0+n_cell_rows-1 of ny x (nx+1);
- * daq rows j0..j0+n_cell_rows-1 of ny x nx. */
-int ogg_bipolar_cap_metrics_quad_dev(int order, long nx, long ny, double lat0_bp, double lon_bp, double rp,
-                                     double Re, long j0, long n_dx_rows, long n_cell_rows, double* dxq, double* dyq,
-                                     double* daq, void* stream);
+/* bipolar_cap_metrics_quad_fast (OGG:136-188): Gauss-Lobatto quadrature (order 2..5) of the analytic scale factors of an
+ * (ny+1) x (nx+1) cap.
+ *   rows         a band: dxq rows j0..j0+n_dx_rows-1 of (ny+1) x nx; dyq rows j0..j0+n_cell_rows-1 of ny x (nx+1); daq rows
+ *                j0..j0+n_cell_rows-1 of ny x nx.  n_dx_rows = n_cell_rows, or n_cell_rows + 1 on the band that holds row ny.  The whole
+ *                cap is j0 = 0, n_dx_rows = ny + 1, n_cell_rows = ny
+ *   workspace    device memory for the row / column tables, at least ogg_bipolar_quad_workspace_bytes bytes: no allocation of any kind
+ *                inside the call, so it can be captured into a HIP graph.  workspace = NULL, workspace_bytes = 0: the tables come from
+ *                the stream-ordered allocator (hipMallocAsync / hipFreeAsync)
+ *   symmetry     OGG_SYM_* (top of this file).  Mirrored, the rows below 88.2 degrees are evaluated on the cells [0, nx/4) and next to
+ *                the fold lines (6 degrees either side of the columns 0 and nx/2) and written to their images; replaces the column
+ *                loop of OGG:168-172 for those rows */
+long ogg_bipolar_quad_workspace_bytes(int order, long nx, long ny);
+int ogg_bipolar_cap_metrics_quad_sym_ws_dev(int order, long nx, long ny, double lat0_bp, double lon_bp, double rp, double Re,
+                                            long j0, long n_dx_rows, long n_cell_rows, int symmetry, double* dxq, double* dyq, double* daq,
+                                            void* workspace, long workspace_bytes, void* stream);
+/* the whole cap into host arrays, under the reference's own name (symmetry = OGG_SYM_DEFAULT) and with the symmetry stated */
 int ogg_bipolar_cap_metrics_quad(int order, long nx, long ny, double lat0_bp, double lon_bp, double rp, double Re,
                                  double* dxq, double* dyq, double* daq);
 int ogg_bipolar_cap_metrics_quad_sym(int order, long nx, long ny, double lat0_bp, double lon_bp, double rp, double Re, int symmetry,
                                      double* dxq, double* dyq, double* daq);
-/* Same with a caller-provided device workspace for the row/column tables (at least ogg_bipolar_quad_workspace_bytes
- * bytes): no allocation of any kind inside the call, so it can be captured into a HIP graph.  The plain _dev form takes
- * the tables from the stream-ordered allocator (hipMallocAsync / hipFreeAsync). */
-long ogg_bipolar_quad_workspace_bytes(int order, long nx, long ny);
-int ogg_bipolar_cap_metrics_quad_ws_dev(int order, long nx, long ny, double lat0_bp, double lon_bp, double rp, double Re,
-                                        long j0, long n_dx_rows, long n_cell_rows, double* dxq, double* dyq, double* daq,
-                                        void* workspace, long workspace_bytes, void* stream);
-/* Same with the column symmetry stated by the caller (OGG_SYM_*, top of this file); the forms above ask for OGG_SYM_DEFAULT.  Mirrored,
- * the rows below 88.2 degrees are evaluated on the cells [0, nx/4) and next to the fold lines (6 degrees either side of the columns
- * 0 and nx/2) and written to their images; replaces the column loop of OGG:168-172 for those rows. */
-int ogg_bipolar_cap_metrics_quad_sym_ws_dev(int order, long nx, long ny, double lat0_bp, double lon_bp, double rp, double Re,
-                                            long j0, long n_dx_rows, long n_cell_rows, int symmetry, double* dxq, double* dyq, double* daq,
-                                            void* workspace, long workspace_bytes, void* stream);
 
-/* One rank's share of a tripolar supergrid -- the lat-lon sub-grids and the bipolar cap generated by the sub-grid loop of
- * main() (OGG:1100-1313: generate_mercator_grid / generate_latlon_grid / generate_bipolar_cap_mesh + angle_x +
- * bipolar_cap_metrics_quad_fast) -- in three launches on one stream: the HBM-bound lat-lon row strips and the VALU-bound
- * cap workgroups share each launch, so nothing waits on a cross-stream dependency.  Results are bit-identical to
- * ogg_latlon_supergrid_multi_dev + ogg_bipolar_cap_mesh_angle_dev + ogg_bipolar_cap_metrics_quad_ws_dev on the same bands.
- * cap may be NULL (no cap rows on this rank); metrics == 0 writes coordinates and angle_dx only. */
+/* The band of a bipolar cap in a pass (ogg_tripolar_pass_dev, ogg_supergrid_pass_dev below): mesh, angle_dx and quadrature of its
+ * rows.  Results are bit-identical to ogg_bipolar_cap_mesh_angle_sym_dev + ogg_bipolar_cap_metrics_quad_sym_ws_dev on the same band. */
 typedef struct ogg_bipolar_band {
     long Ni, Nj;             /* the cap is (Nj+1) x (Ni+1) points */
     double lat0_bp, lon_bp;  /* OGG:103 */
@@ -226,13 +244,6 @@ typedef struct ogg_bipolar_band {
                                 fix-up list, claim counters of the lat-lon strips; one pass at a time per workspace */
     long workspace_bytes;
 } ogg_bipolar_band;
-int ogg_tripolar_pass_dev(int n_latlon, const ogg_latlon_band* latlon, long ni1, double lon0, double lenlon, double Re,
-                          int metrics, const ogg_bipolar_band* cap, void* stream);
-/* same; events4 (NULL, or 4 events from ogg_event_create) are recorded on the stream before the first launch and after each
- * of the three launches, so that the caller can time them (ogg_event_elapsed_ms); alg_bytes3 (NULL, or 3 doubles on the host)
- * receives the bytes each launch writes (its share of the 48 B per cell) */
-int ogg_tripolar_pass_events_dev(int n_latlon, const ogg_latlon_band* latlon, long ni1, double lon0, double lenlon, double Re,
-                                 int metrics, const ogg_bipolar_band* cap, void** events4, double* alg_bytes3, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Displaced-pole Southern cap
@@ -259,13 +270,14 @@ int ogg_haversine(long n, const double* lam0, const double* phi0, const double* 
 int ogg_haversine_dev(long n, const double* lam0, const double* phi0, const double* lam1, const double* phi1, double* out,
                       void* stream);
 
-/* generate_displaced_pole_grid (OGG:509-518), rows j0..j0+nrows-1 of (Nj+1) x (Ni+1): projection, the sequential unwrap of
- * monotonic_bounding (a look-back scan over the column strips of a row) and, when angle_dx != NULL, angle_x (OGG:719-729) of
- * the same rows (nrows x (Ni+1)) without reading the mesh back -- one launch.  The _ws form takes a caller-provided device
- * workspace (>= ogg_displaced_pole_grid_workspace_bytes; its first two 32-bit words are the work counter and an error flag,
- * see ogg_workspace_error_flag_dev) and allocates nothing; the plain form uses the stream-ordered allocator. */
-int ogg_displaced_pole_grid_dev(long Ni, long Nj, double lon0, double lat0, double lon_dp, double r_dp, long j0,
-                                long nrows, double* x, double* y, void* stream);
+/* generate_displaced_pole_grid (OGG:509-518), rows j0..j0+nrows-1 of (Nj+1) x (Ni+1), one launch after a small reset: projection and
+ * the sequential unwrap of monotonic_bounding (a look-back scan over the column strips of a row).
+ *   x, y         nrows x (Ni+1)
+ *   angle_dx     angle_x (OGG:719-729) of the same rows, nrows x (Ni+1), without reading the mesh back; NULL to skip
+ *   workspace    device memory, at least ogg_displaced_pole_grid_workspace_bytes bytes (its first two 32-bit words are the work counter
+ *                and an error flag, see ogg_workspace_error_flag_dev): nothing is allocated.  workspace = NULL, workspace_bytes = 0: the
+ *                stream-ordered allocator, and the call waits for the stream to check the flag itself
+ * Every column is evaluated: the mesh has no mirrored form. */
 long ogg_displaced_pole_grid_workspace_bytes(long Ni, long nrows);
 int ogg_displaced_pole_grid_angle_ws_dev(long Ni, long Nj, double lon0, double lat0, double lon_dp, double r_dp, long j0,
                                          long nrows, double* x, double* y, double* angle_dx, void* workspace,
@@ -283,17 +295,26 @@ int ogg_displaced_pole_numerical_h(long n_i, const double* i, long n_j, const do
                                    double lon0, double lat0, double lon_dp, double r_dp, double eps, int fd_order,
                                    double* h_i, double* h_j);
 
-/* displacedPoleCap_metrics_quad (OGG:565-601): quadrature order (2..5) is also the finite-difference order, as in
- * the reference (OGG:583-584), so only orders 2 and 4 are valid.  Band form as for the bipolar cap; cell rows
- * below j0 are simply not evaluated (main() discards the doughnut rows, OGG:1177-1186).
+/* displacedPoleCap_metrics_quad (OGG:565-601) of an (ny+1) x (nx+1) cap: quadrature order (2..5) is also the finite-difference order,
+ * as in the reference (OGG:583-584), so only orders 2 and 4 are valid.
+ *   rows         a band, as for the bipolar cap: dxq rows j0..j0+n_dx_rows-1 of (ny+1) x nx; dyq rows j0..j0+n_cell_rows-1 of
+ *                ny x (nx+1); daq rows j0..j0+n_cell_rows-1 of ny x nx; n_dx_rows = n_cell_rows, or n_cell_rows + 1 on the band that
+ *                holds row ny.  Cell rows below j0 are simply not evaluated (main() discards the doughnut rows, OGG:1177-1186)
+ *   workspace    device memory for the row / column tables and the look-back words, at least
+ *                ogg_displaced_pole_quad_workspace_bytes(order, nx, n_cell_rows) bytes (a few MB -- the lattice itself is never
+ *                stored): no allocation inside the call; one call at a time per workspace.  workspace = NULL, workspace_bytes = 0: the
+ *                stream-ordered allocator; the literal form then waits for the stream to check the error flag itself
+ *   symmetry     OGG_SYM_* (top of this file).  Mirrored (chord form only, when the meridian of the displaced pole is a node column,
+ *                (lon_dp - lon0) nx / 360 an integer, and nx is even): the half of the columns on one side of that meridian is
+ *                evaluated and written to its mirror images (OGG:583-584 evaluate every column)
  * arc_form selects how the great-arc distance between two probes of the finite-difference stencil is taken:
  *   OGG_DP_ARC_CHORD    the finite-difference stencil of the reference, distance of two probes from their positions on the sphere (no
  *                       atan2, no unwrap): ~6x less arithmetic than the literal form, and closer to what the reference's formula means
- *                       (below).  Since round 4 THE default: what the entry points without an arc_form argument run, and what the
+ *                       (below).  Since round 4 THE default: what ogg_displaced_pole_metrics_quad runs, and what the
  *                       Python host (main(), displacedPoleCap_metrics_quad, SupergridPlan, bench.py) asks for unless OGG_DP_ARC /
  *                       dp_arc / arc_form says literal;
  *   OGG_DP_ARC_LITERAL  the reference's operation sequence (haversine of the projected, unwrapped longitudes and latitudes,
- *                       OGG:522-532): opt-in through the *_form entry points and the band descriptor of the pass.
+ *                       OGG:522-532): opt-in through the arc_form argument and the band descriptor of the pass.
  * Measured on the 5760 x 560 cap of BASELINE config 4 (1/8 degree), max relative difference of dx / dy / area
  *   from the numpy oracle (profiles/dp_parity.json):             literal 1.3e-9 / 1.2e-9 / 7.6e-10   chord 1.5e-9 / 1.3e-9 / 9.8e-10
  *   from a 50-digit evaluation of the reference's own formula on 10 500 cells (tests/golden/truth_table.npz, tests/test_gpu_truth.py,
@@ -303,43 +324,22 @@ int ogg_displaced_pole_numerical_h(long n_i, const double* i, long n_j, const do
  * atan2 is amplified by ~Ni / (4e-3 pi); the fp64 reference is itself that far from the exact value of its formula, and the chord form,
  * which never forms a longitude, is the closest of the three.  The literal form is not bit-identical to a CPU run either, because the
  * transcendental functions are not (the restatements of atan / atan2 used here reproduce the bits of the ROCm 7.2 device library,
- * ogg_libm_check_dev). */
-/* (OGG_DP_ARC_LITERAL = 0, OGG_DP_ARC_CHORD = 1: defined next to the error codes at the top of this file) */
-int ogg_displaced_pole_metrics_quad_dev(int order, long nx, long ny, double lon0, double lat0, double lon_dp,
-                                        double r_dp, double Re, long j0, long n_dx_rows, long n_cell_rows,
-                                        double* dxq, double* dyq, double* daq, void* stream);
-/* Same with a caller-provided workspace for the row / column tables and the look-back words (at least
- * ogg_displaced_pole_quad_workspace_bytes(order, nx, n_cell_rows) bytes; a few MB -- the lattice itself is never stored): no
- * allocation inside the call.  One call at a time per workspace. */
+ * ogg_libm_check_dev).
+ * (OGG_DP_ARC_LITERAL = 0, OGG_DP_ARC_CHORD = 1: defined next to the error codes at the top of this file) */
 long ogg_displaced_pole_quad_workspace_bytes(int order, long nx, long n_cell_rows);
-int ogg_displaced_pole_metrics_quad_ws_dev(int order, long nx, long ny, double lon0, double lat0, double lon_dp,
-                                           double r_dp, double Re, long j0, long n_dx_rows, long n_cell_rows, double* dxq,
-                                           double* dyq, double* daq, void* workspace, long workspace_bytes, void* stream);
-int ogg_displaced_pole_metrics_quad_form_ws_dev(int arc_form, int order, long nx, long ny, double lon0, double lat0,
-                                                double lon_dp, double r_dp, double Re, long j0, long n_dx_rows,
-                                                long n_cell_rows, double* dxq, double* dyq, double* daq, void* workspace,
-                                                long workspace_bytes, void* stream);
-/* same with the column symmetry stated by the caller (OGG_SYM_*; the form above asks for OGG_SYM_DEFAULT).  Mirrored (chord form only, when
- * the meridian of the displaced pole is a node column, (lon_dp - lon0) nx / 360 an integer, and nx is even): the half of the columns on
- * one side of that meridian is evaluated and written to its mirror images (OGG:583-584 evaluate every column) */
 int ogg_displaced_pole_metrics_quad_form_sym_ws_dev(int arc_form, int symmetry, int order, long nx, long ny, double lon0, double lat0,
                                                     double lon_dp, double r_dp, double Re, long j0, long n_dx_rows, long n_cell_rows,
                                                     double* dxq, double* dyq, double* daq, void* workspace, long workspace_bytes,
                                                     void* stream);
+/* the whole cap into host arrays, under the reference's own name (arc_form = OGG_DP_ARC_CHORD, symmetry = OGG_SYM_DEFAULT) and with both
+ * stated */
 int ogg_displaced_pole_metrics_quad(int order, long nx, long ny, double lon0, double lat0, double lon_dp, double r_dp,
                                     double Re, double* dxq, double* dyq, double* daq);
-int ogg_displaced_pole_metrics_quad_form(int arc_form, int order, long nx, long ny, double lon0, double lat0, double lon_dp,
-                                         double r_dp, double Re, double* dxq, double* dyq, double* daq);
 int ogg_displaced_pole_metrics_quad_form_sym(int arc_form, int symmetry, int order, long nx, long ny, double lon0, double lat0, double lon_dp,
                                              double r_dp, double Re, double* dxq, double* dyq, double* daq);
 
-/* One rank's share of a whole supergrid: ogg_tripolar_pass_dev plus the band of a displaced-pole southern cap (the SC branch of
- * the same sub-grid loop, OGG:1158-1197: generate_displaced_pole_grid + angle_x + displacedPoleCap_metrics_quad) in the SAME
- * launches: its tables and the reset of its look-back words join launch A, its mesh + angle workgroups and -- in the chord form --
- * its quadrature strips join launch B; the literal form of the quadrature is a fourth launch (D) on the same stream.  Results are
- * bit-identical to ogg_displaced_pole_grid_angle_ws_dev + ogg_displaced_pole_metrics_quad_form_ws_dev on the same band.
- * south_cap may be NULL.  events5 (NULL, or 5 events, entries may be NULL): before A, after A, B, C, D; alg_bytes4: bytes each
- * launch writes. */
+/* The band of a displaced-pole southern cap in a pass (ogg_supergrid_pass_dev below): mesh, angle_dx and quadrature of its rows.
+ * Results are bit-identical to ogg_displaced_pole_grid_angle_ws_dev + ogg_displaced_pole_metrics_quad_form_sym_ws_dev on the same band. */
 typedef struct ogg_dpole_band {
     long Ni, Nj;                 /* the cap is (Nj+1) x (Ni+1) points (OGG:509) */
     double lon0, lat0;           /* OGG:478: first longitude, latitude of the joint with the Southern Ocean sub-grid */
@@ -363,10 +363,26 @@ long ogg_dpole_band_workspace_bytes(int order, long Ni, long n_pt_rows);
  * (col_writes[n + 1]) is written, and how many are evaluated.  Every count must be 1 whatever `symmetry` (OGG_SYM_*). */
 int ogg_symmetry_coverage(int which, int order, long n, double lon0, double lon_dp, int symmetry, int* cell_writes, int* col_writes,
                           long* evaluated);
+
+/* The pass: one rank's share of a whole supergrid -- the lat-lon sub-grids, the bipolar cap and the displaced-pole southern cap generated
+ * by the sub-grid loop of main() (OGG:1100-1313: generate_mercator_grid / generate_latlon_grid; generate_bipolar_cap_mesh + angle_x +
+ * bipolar_cap_metrics_quad_fast; the SC branch, OGG:1158-1197: generate_displaced_pole_grid + angle_x + displacedPoleCap_metrics_quad)
+ * -- in three launches on one stream: the HBM-bound lat-lon row strips and the VALU-bound cap workgroups share each launch, so nothing
+ * waits on a cross-stream dependency.  The southern cap's tables and the reset of its look-back words join launch A, its mesh + angle
+ * workgroups and -- in the chord form -- its quadrature strips join launch B; the literal form of its quadrature is a fourth launch (D).
+ * Results are bit-identical to ogg_latlon_supergrid_multi_dev and the caps' own entry points (above each band struct) on the same bands.
+ *   cap, south_cap  either may be NULL: no rows of that cap on this rank
+ *   metrics         0 writes coordinates and angle_dx only
+ *   events5         NULL, or 5 events from ogg_event_create (entries may be NULL), recorded on the stream before A and after A, B, C, D,
+ *                   so that the caller can time the launches (ogg_event_elapsed_ms)
+ *   alg_bytes4      NULL, or 4 doubles on the host: the bytes each launch writes (its share of the 48 B per cell) */
 int ogg_supergrid_pass_dev(int n_latlon, const ogg_latlon_band* latlon, long ni1, double lon0, double lenlon, double Re, int metrics,
                            const ogg_bipolar_band* cap, const ogg_dpole_band* south_cap, void** events5, double* alg_bytes4,
                            void* stream);
-/* The same in two steps, for a caller that runs the pass of one set of bands many times (a rank's step loop): the plan holds the kernel
+/* the pass without a southern cap: ogg_supergrid_pass_dev with south_cap, events5 and alg_bytes4 NULL */
+int ogg_tripolar_pass_dev(int n_latlon, const ogg_latlon_band* latlon, long ni1, double lon0, double lenlon, double Re,
+                          int metrics, const ogg_bipolar_band* cap, void* stream);
+/* ogg_supergrid_pass_dev in two steps, for a caller that runs the pass of one set of bands many times (a rank's step loop): the plan holds the kernel
  * parameters of the launches, their grid sizes and the tiling knobs (the OGG_* environment variables are read when the plan is BUILT), so
  * that a run costs the host its launches and nothing else -- no validation, no planning, no getenv.  The band descriptors are copied:
  * they may be freed after ogg_supergrid_pass_plan_dev returns; the buffers and workspaces they point to must stay.  The runs of a plan
@@ -513,7 +529,6 @@ typedef struct ogg_quality_band {
     double Re;
     int metrics;
 } ogg_quality_band;
-long ogg_grid_quality_result_bytes(void); /* sizeof(ogg_grid_quality_result) (lets a binding verify its layout) */
 long ogg_grid_quality_workspace_bytes(long nx, long n_pt_rows);
 /* device pointers throughout: the band's result into *out (device memory); the workspace (device memory, at least
  * ogg_grid_quality_workspace_bytes) holds one record per workgroup, merged in workgroup order by a second kernel */
@@ -592,7 +607,6 @@ typedef struct ogg_topog_record {
     int min, max, R;
     short n_pole, n_clamped;   /* supergrid cells of this record that enclose a pole / whose R was clamped */
 } ogg_topog_record;
-long ogg_topog_record_bytes(void);                         /* sizeof(ogg_topog_record) */
 long ogg_topog_band_out_rows(const ogg_topog_band* band);  /* m1 - m0 + 1 (0 for an empty band), -1 on a bad band */
 long ogg_topog_workspace_bytes(void);                      /* the work counter of ogg_topog_band_dev */
 /* device pointers throughout: the band's records, row-major (m - m0, i_out), into out (device memory, out_rows * (nx >> shift)
@@ -653,7 +667,6 @@ typedef struct ogg_topog_plane_record {
     ogg_topog_record base;
     long long sx, sy, sxx, sxy, syy, sxq, syq, n_far;
 } ogg_topog_plane_record;
-long ogg_topog_plane_record_bytes(void);                   /* sizeof(ogg_topog_plane_record): 120 */
 /* ogg_topog_band_dev with the plane moments: the same band, source and workspace contracts; out holds plane records */
 int ogg_topog_plane_band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* workspace, long workspace_bytes,
                              ogg_topog_plane_record* out, void* stream);
@@ -694,7 +707,6 @@ int ogg_topog_plane(const ogg_topog_band* band, const ogg_topog_source* src, ogg
  * Order: ocean cells row-major (m, n), then J ascending, then a_I + s ascending.  Nothing is summed across cells, so the list is
  * bit-identical for any band split.  The integer counts are over the band's cells; the first four ignore the mask.
  * ---------------------------------------------------------------------------------------------------- */
-enum { OGG_XGRID_BAND = 0, OGG_XGRID_ATM = 1, OGG_XGRID_COUNTS = 2 };
 typedef struct ogg_xgrid_atm {
     const double *lon, *lat;   /* NA + 1 and NB + 1 edges */
     long NA, NB;
@@ -714,7 +726,6 @@ typedef struct ogg_xgrid_band {
 typedef struct ogg_xgrid_counts {
     long long cells, pole_cells, pole_enclosing, inverted, degenerate, masked, candidates, kept;
 } ogg_xgrid_counts;
-long ogg_xgrid_struct_bytes(int which);                    /* sizeof of OGG_XGRID_BAND / ATM / COUNTS, -1 otherwise */
 long ogg_xgrid_band_first_row(const ogg_xgrid_band* band); /* m0, -1 on a bad band */
 long ogg_xgrid_band_out_rows(const ogg_xgrid_band* band);  /* m1 - m0 (0 for a band without a model row), -1 on a bad band */
 long ogg_xgrid_band_next_rows(const ogg_xgrid_band* band); /* point rows needed after the band: 0, 1 or 2; -1 on a bad band */
@@ -764,7 +775,6 @@ enum { OGG_MASK_MASK = 0, OGG_MASK_DEEPEN = 1 };
 #define OGG_MASK_PERIODIC 1
 #define OGG_MASK_FOLD 2
 #define OGG_MASK_MAX_SEEDS 1024
-enum { OGG_MASK_PARAMS = 0, OGG_MASK_COUNTS = 1 };
 typedef struct ogg_mask_params {
     long ny, nx;
     int topology;             /* OGG_MASK_PERIODIC | OGG_MASK_FOLD */
@@ -782,7 +792,6 @@ typedef struct ogg_mask_counts {
     long long removed;        /* wet cells made land by the selection (apply step) */
     long long wet_out;        /* wet cells of the final mask (apply step) */
 } ogg_mask_counts;
-long ogg_mask_struct_bytes(int which);                        /* sizeof of OGG_MASK_PARAMS / COUNTS, -1 otherwise */
 long ogg_mask_workspace_bytes(const ogg_mask_params* p);      /* of the label and apply steps, -1 on bad sizes */
 /* the checks of *p (sizes, mode, min_depth, fill, keep_min_cells): OGG_EARG with the reason, before any device work */
 int ogg_mask_check(const ogg_mask_params* p);
@@ -833,7 +842,6 @@ enum { OGG_REMAP_FLOAT32 = 0, OGG_REMAP_FLOAT64 = 1 };
 enum { OGG_REMAP_DRY = 0, OGG_REMAP_REMAPPED = 1, OGG_REMAP_FILLED = 2, OGG_REMAP_UNFILLED = 3 };
 #define OGG_REMAP_FILL 1.0e20
 #define OGG_REMAP_MAX_FILLS 2
-enum { OGG_REMAP_PARAMS = 0, OGG_REMAP_COUNTS = 1 };
 /* the cells are model rows m0 .. m0 + ny - 1 of a grid nx cells wide (the list's m are counted in the whole grid); the fill step
  * needs the whole grid (m0 = 0).  ny * nx < 2^31, nrec * ny * nx < 2^32, NA * NB < 2^31. */
 typedef struct ogg_remap_params {
@@ -853,7 +861,6 @@ typedef struct ogg_remap_counts {
     long long fronts;          /* fill fronts with cells (= max_distance) */
     long long launches;        /* fill launches, those on an empty frontier included */
 } ogg_remap_counts;
-long ogg_remap_struct_bytes(int which);                     /* sizeof of OGG_REMAP_PARAMS / COUNTS, -1 otherwise */
 long ogg_remap_workspace_bytes(const ogg_remap_params* p);  /* of the segment, remap and fill steps, -1 on a bad *p */
 /* the checks of *p (sizes, dtype, n_fill, topology): OGG_EARG with the reason, before any device work */
 int ogg_remap_check(const ogg_remap_params* p);
@@ -903,7 +910,6 @@ int ogg_remap(const ogg_remap_params* p, const void* f, const int* atm_ij, const
  * on the gathered grid, for any rank count.  Output layout: values (nrec, ny, nx) fp64, record-major; n_sources (ny, nx) int32.
  * ---------------------------------------------------------------------------------------------------- */
 enum { OGG_RUNOFF_COAST = 0, OGG_RUNOFF_WET = 1 };
-enum { OGG_RUNOFF_PARAMS = 0, OGG_RUNOFF_COUNTS = 1 };
 #define OGG_RUNOFF_MAX_BINS 160   /* the largest OGG_RUNOFF_BINS: cubes per axis of the search index */
 /* ny * nx < 2^31, NA * NB < 2^31, nrec * ny * nx < 2^32, nrec * NA * NB < 2^40 */
 typedef struct ogg_runoff_params {
@@ -924,7 +930,6 @@ typedef struct ogg_runoff_counts {
     long long tests;           /* distance tests of the search (search step) */
     long long bins;            /* cubes per axis of the search index, 0 for brute force (search step) */
 } ogg_runoff_counts;
-long ogg_runoff_struct_bytes(int which);                     /* sizeof of OGG_RUNOFF_PARAMS / COUNTS, -1 otherwise */
 long ogg_runoff_workspace_bytes(const ogg_runoff_params* p); /* of every step, -1 on a bad *p */
 /* the checks of *p (sizes, dtype, n_fill, topology, targets, Re): OGG_EARG with the reason, before any device work */
 int ogg_runoff_check(const ogg_runoff_params* p);
@@ -982,7 +987,6 @@ int ogg_runoff(const ogg_runoff_params* p, const double* x, const double* y, con
  * n_entries (NB, NA) int32.
  * ---------------------------------------------------------------------------------------------------- */
 enum { OGG_REGRID_AREA = 0, OGG_REGRID_CELL = 1 };
-enum { OGG_REGRID_PARAMS = 0, OGG_REGRID_COUNTS = 1 };
 /* ny * nx < 2^31, NA * NB < 2^31, nrec * NB * NA < 2^32; list length < 2^31 (the calls) */
 typedef struct ogg_regrid_params {
     long ny, nx;               /* model cells */
@@ -1000,7 +1004,6 @@ typedef struct ogg_regrid_counts {
     long long valid;           /* (record, cell) pairs with W > 0 (regrid step) */
     long long empty;           /* (record, cell) pairs with W = 0 (regrid step) */
 } ogg_regrid_counts;
-long ogg_regrid_struct_bytes(int which);                                    /* sizeof of OGG_REGRID_PARAMS / COUNTS, -1 otherwise */
 long ogg_regrid_workspace_bytes(const ogg_regrid_params* p, long n_entries); /* of both steps, -1 on a bad *p or length */
 /* the checks of *p (sizes, dtype, n_fill, normalize): OGG_EARG with the reason, before any device work */
 int ogg_regrid_check(const ogg_regrid_params* p);
@@ -1067,7 +1070,6 @@ typedef struct ogg_bilinear_params {
     int topology;              /* fill step: OGG_MASK_PERIODIC | OGG_MASK_FOLD */
     int fill_max;              /* fill step: the largest distance filled, < 0 for no limit */
 } ogg_bilinear_params;
-long ogg_bilinear_struct_bytes(void);                        /* sizeof(ogg_bilinear_params) */
 /* the checks of *p (sizes, dtype, n_fill, points, ncomp, C for a scalar, topology) and of a mask away from the H points: OGG_EARG
  * with the reason, before any device work */
 int ogg_bilinear_check(const ogg_bilinear_params* p, int has_mask);
@@ -1117,7 +1119,6 @@ int ogg_bilinear(const ogg_bilinear_params* p, const double* x, const double* y,
  * Output layout: nearest (ny, nx) int32; d2 (ny, nx) fp64.
  * ---------------------------------------------------------------------------------------------------- */
 enum { OGG_COAST_WET = 1, OGG_COAST_LAND = 2 };
-enum { OGG_COAST_PARAMS = 0, OGG_COAST_COUNTS = 1 };
 #define OGG_COAST_MAX_CUBES 128   /* the largest OGG_COAST_CUBES: cubes per axis of the search index */
 /* ny * nx < 2^31 */
 typedef struct ogg_coast_params {
@@ -1134,7 +1135,6 @@ typedef struct ogg_coast_counts {
     long long tiles;           /* tiles of cells, one workgroup each (search step) */
     long long cubes;           /* cubes per axis of the search index, 0 for brute force (search step) */
 } ogg_coast_counts;
-long ogg_coast_struct_bytes(int which);                      /* sizeof of OGG_COAST_PARAMS / COUNTS, -1 otherwise */
 long ogg_coast_workspace_bytes(const ogg_coast_params* p);   /* of both steps, -1 on a bad *p */
 /* the checks of *p (sizes, topology, sides): OGG_EARG with the reason, before any device work */
 int ogg_coast_check(const ogg_coast_params* p);
@@ -1192,7 +1192,6 @@ int ogg_coast_distance(const ogg_coast_params* p, const double* x, const double*
  * ---------------------------------------------------------------------------------------------------- */
 #define OGG_BASIN_MAX_RULES 4096
 #define OGG_BASIN_MAX_PASS_RULES 255
-enum { OGG_BASIN_PARAMS = 0, OGG_BASIN_RULE = 1, OGG_BASIN_RECORD = 2, OGG_BASIN_COUNTS = 3 };
 enum { OGG_BASIN_TOOK = 0, OGG_BASIN_SEED_LAND = 1, OGG_BASIN_SEED_OUTSIDE = 2, OGG_BASIN_SEED_CODED = 3, OGG_BASIN_SEED_OFF_GRID = 4,
        OGG_BASIN_SEED_INVALID = 5 };
 typedef struct ogg_basin_params {
@@ -1221,7 +1220,6 @@ typedef struct ogg_basin_counts {
     long long uncoded;         /* wet - coded */
     long long passes;          /* passes run */
 } ogg_basin_counts;
-long ogg_basin_struct_bytes(int which);                      /* sizeof of OGG_BASIN_PARAMS / RULE / RECORD / COUNTS, -1 otherwise */
 long ogg_basin_workspace_bytes(const ogg_basin_params* p);   /* -1 on a bad *p */
 /* the checks of *p and of the n_rules rules (HOST memory): OGG_EARG with the reason, before any device work */
 int ogg_basin_check(const ogg_basin_params* p, const ogg_basin_rule* rules);

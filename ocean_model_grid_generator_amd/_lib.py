@@ -119,9 +119,6 @@ class XgridCounts(ctypes.Structure):
     _fields_ = [(f, c_longlong) for f in XGRID_COUNT_FIELDS]
 
 
-XGRID_BAND, XGRID_ATM, XGRID_COUNTS = 0, 1, 2                          # OGG_XGRID_BAND ... of include/ogg_hip.h
-
-
 class MaskParams(ctypes.Structure):
     """ogg_mask_params of include/ogg_hip.h"""
     _fields_ = [("ny", c_long), ("nx", c_long), ("topology", c_int), ("mode", c_int), ("fill", c_double), ("min_depth", c_double),
@@ -139,7 +136,6 @@ class MaskCounts(ctypes.Structure):
 MASK_MASK, MASK_DEEPEN = 0, 1                                          # OGG_MASK_MASK, OGG_MASK_DEEPEN
 MASK_PERIODIC, MASK_FOLD = 1, 2                                        # OGG_MASK_PERIODIC, OGG_MASK_FOLD
 MASK_MAX_SEEDS = 1024                                                  # OGG_MASK_MAX_SEEDS
-MASK_PARAMS, MASK_COUNTS = 0, 1                                        # OGG_MASK_PARAMS, OGG_MASK_COUNTS
 
 
 class RemapParams(ctypes.Structure):
@@ -160,7 +156,6 @@ REMAP_FLOAT32, REMAP_FLOAT64 = 0, 1                                    # OGG_REM
 REMAP_DRY, REMAP_REMAPPED, REMAP_FILLED, REMAP_UNFILLED = 0, 1, 2, 3   # OGG_REMAP_DRY ... OGG_REMAP_UNFILLED
 REMAP_FILL = 1.0e20                                                    # OGG_REMAP_FILL
 REMAP_MAX_FILLS = 2                                                    # OGG_REMAP_MAX_FILLS
-REMAP_PARAMS, REMAP_COUNTS = 0, 1                                      # OGG_REMAP_PARAMS, OGG_REMAP_COUNTS
 
 
 class RunoffParams(ctypes.Structure):
@@ -178,7 +173,6 @@ class RunoffCounts(ctypes.Structure):
 
 
 RUNOFF_COAST, RUNOFF_WET = 0, 1                                        # OGG_RUNOFF_COAST, OGG_RUNOFF_WET
-RUNOFF_PARAMS, RUNOFF_COUNTS = 0, 1                                    # OGG_RUNOFF_PARAMS, OGG_RUNOFF_COUNTS
 RUNOFF_MAX_BINS = 160                                                  # OGG_RUNOFF_MAX_BINS
 
 
@@ -196,7 +190,6 @@ class CoastCounts(ctypes.Structure):
 
 
 COAST_WET, COAST_LAND = 1, 2                                           # OGG_COAST_WET, OGG_COAST_LAND
-COAST_PARAMS, COAST_COUNTS = 0, 1                                      # OGG_COAST_PARAMS, OGG_COAST_COUNTS
 COAST_F_WET, COAST_F_COAST, COAST_F_VALID = 1, 2, 4                    # the bits of a flag byte
 COAST_MAX_CUBES = 128                                                  # OGG_COAST_MAX_CUBES
 
@@ -218,7 +211,6 @@ class BasinCounts(ctypes.Structure):
 BASIN_RULE = np.dtype([("code", "<i4"), ("reserved", "<i4"), ("seed_lon", "<f8"), ("seed_lat", "<f8"), ("lon_w", "<f8"), ("lon_e", "<f8"),
                        ("lat_s", "<f8"), ("lat_n", "<f8")])
 BASIN_RECORD = np.dtype([("seed_cell", "<i8"), ("d2_bits", "<i8"), ("status", "<i4"), ("blocking_rule", "<i4"), ("cells", "<i8")])
-BASIN_PARAMS, BASIN_RULE_STRUCT, BASIN_RECORD_STRUCT, BASIN_COUNTS = 0, 1, 2, 3   # OGG_BASIN_PARAMS ... OGG_BASIN_COUNTS
 BASIN_MAX_RULES, BASIN_MAX_PASS_RULES = 4096, 255                      # OGG_BASIN_MAX_RULES, OGG_BASIN_MAX_PASS_RULES
 BASIN_TOOK, BASIN_SEED_LAND, BASIN_SEED_OUTSIDE, BASIN_SEED_CODED, BASIN_SEED_OFF_GRID, BASIN_SEED_INVALID = range(6)   # OGG_BASIN_TOOK ...
 
@@ -238,7 +230,6 @@ class RegridCounts(ctypes.Structure):
 
 
 REGRID_AREA, REGRID_CELL = 0, 1                                        # OGG_REGRID_AREA, OGG_REGRID_CELL
-REGRID_PARAMS, REGRID_COUNTS = 0, 1                                    # OGG_REGRID_PARAMS, OGG_REGRID_COUNTS
 
 
 class BilinearParams(ctypes.Structure):
@@ -249,6 +240,17 @@ class BilinearParams(ctypes.Structure):
 
 BILINEAR_H, BILINEAR_U, BILINEAR_V, BILINEAR_C = 0, 1, 2, 3            # OGG_BILINEAR_H ... OGG_BILINEAR_C
 BILINEAR_POINTS = {"h": BILINEAR_H, "u": BILINEAR_U, "v": BILINEAR_V, "c": BILINEAR_C}
+
+# OGG_ABI_* of include/ogg_hip.h, in code order: name -> the mirror of ogg_<name> (a ctypes.Structure or a numpy record), whose size
+# ogg_abi_sizeof(code) must give (tests/test_abi.py)
+ABI_MIRRORS = {"LATLON_BAND": LatlonBand, "BIPOLAR_BAND": BipolarBand, "DPOLE_BAND": DpoleBand, "QUALITY_EXTREMUM": QualityExtremum,
+               "GRID_QUALITY_RESULT": QualityResult, "QUALITY_BAND": QualityBand, "TOPOG_SOURCE": TopogSource, "TOPOG_BAND": TopogBand,
+               "TOPOG_RECORD": TOPOG_RECORD, "TOPOG_PLANE_RECORD": TOPOG_PLANE_RECORD, "XGRID_ATM": XgridAtm, "XGRID_BAND": XgridBand,
+               "XGRID_COUNTS": XgridCounts, "MASK_PARAMS": MaskParams, "MASK_COUNTS": MaskCounts, "REMAP_PARAMS": RemapParams,
+               "REMAP_COUNTS": RemapCounts, "RUNOFF_PARAMS": RunoffParams, "RUNOFF_COUNTS": RunoffCounts, "REGRID_PARAMS": RegridParams,
+               "REGRID_COUNTS": RegridCounts, "BILINEAR_PARAMS": BilinearParams, "COAST_PARAMS": CoastParams, "COAST_COUNTS": CoastCounts,
+               "BASIN_PARAMS": BasinParams, "BASIN_RULE": BASIN_RULE, "BASIN_RULE_RECORD": BASIN_RECORD, "BASIN_COUNTS": BasinCounts}
+ABI = {name: code for code, name in enumerate(ABI_MIRRORS)}
 
 
 # name -> argtypes; every function returns int except the two string getters.  Must list EVERY symbol of ogg_hip.h
@@ -273,10 +275,6 @@ SIGNATURES = {
     "ogg_bipolar_projection": [c_long, c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_bipolar_projection_dev": [c_long, c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p],
-    "ogg_bipolar_cap_mesh_dev": [c_long, c_long, c_double, c_double, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p],
-    "ogg_bipolar_cap_mesh_angle_dev": [c_long, c_long, c_double, c_double, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p],
     "ogg_bipolar_cap_mesh_sym": [c_long, c_long, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_bipolar_cap_metrics_quad_sym": [c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p],
     "ogg_displaced_pole_metrics_quad_form_sym": [c_int, c_int, c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_double, c_void_p,
@@ -285,10 +283,6 @@ SIGNATURES = {
     "ogg_bipolar_cap_mesh_angle_sym_dev": [c_long, c_long, c_double, c_double, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p],
     "ogg_bipolar_cap_mesh": [c_long, c_long, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p],
-    "ogg_bipolar_cap_metrics_quad_dev": [c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_long, c_long, c_long,
-                                         c_void_p, c_void_p, c_void_p, c_void_p],
-    "ogg_bipolar_cap_metrics_quad_ws_dev": [c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_long, c_long, c_long,
-                                            c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
     "ogg_bipolar_cap_metrics_quad_sym_ws_dev": [c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_long, c_long, c_long, c_int,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
     "ogg_bipolar_cap_metrics_quad": [c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
@@ -297,22 +291,12 @@ SIGNATURES = {
                                     c_double, c_void_p, c_void_p, c_void_p],
     "ogg_displaced_pole_mesh": [c_long, c_void_p, c_long, c_void_p, c_long, c_long, c_double, c_double, c_double, c_double,
                                 c_void_p, c_void_p],
-    "ogg_displaced_pole_grid_dev": [c_long, c_long, c_double, c_double, c_double, c_double, c_long, c_long, c_void_p,
-                                    c_void_p, c_void_p],
     "ogg_displaced_pole_numerical_h_dev": [c_long, c_void_p, c_long, c_void_p, c_long, c_long, c_double, c_double, c_double,
                                            c_double, c_double, c_int, c_void_p, c_void_p, c_void_p],
     "ogg_displaced_pole_numerical_h": [c_long, c_void_p, c_long, c_void_p, c_long, c_long, c_double, c_double, c_double,
                                        c_double, c_double, c_int, c_void_p, c_void_p],
-    "ogg_displaced_pole_metrics_quad_dev": [c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_double, c_long,
-                                            c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
-    "ogg_displaced_pole_metrics_quad_ws_dev": [c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_double, c_long,
-                                               c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
     "ogg_displaced_pole_metrics_quad": [c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_double, c_void_p,
                                         c_void_p, c_void_p],
-    "ogg_displaced_pole_metrics_quad_form": [c_int, c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_double, c_void_p,
-                                             c_void_p, c_void_p],
-    "ogg_displaced_pole_metrics_quad_form_ws_dev": [c_int, c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_double,
-                                                    c_long, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
     "ogg_displaced_pole_metrics_quad_form_sym_ws_dev": [c_int, c_int, c_int, c_long, c_long, c_double, c_double, c_double, c_double, c_double,
                                                         c_long, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
     "ogg_displaced_pole_grid_angle_ws_dev": [c_long, c_long, c_double, c_double, c_double, c_double, c_long, c_long, c_void_p,
@@ -341,8 +325,6 @@ SIGNATURES = {
                                          c_void_p],
     "ogg_tripolar_pass_dev": [c_int, ctypes.POINTER(LatlonBand), c_long, c_double, c_double, c_double, c_int,
                               ctypes.POINTER(BipolarBand), c_void_p],
-    "ogg_tripolar_pass_events_dev": [c_int, ctypes.POINTER(LatlonBand), c_long, c_double, c_double, c_double, c_int,
-                                     ctypes.POINTER(BipolarBand), ctypes.POINTER(c_void_p), ctypes.POINTER(c_double), c_void_p],
     "ogg_supergrid_pass_dev": [c_int, ctypes.POINTER(LatlonBand), c_long, c_double, c_double, c_double, c_int,
                                ctypes.POINTER(BipolarBand), ctypes.POINTER(DpoleBand), ctypes.POINTER(c_void_p), ctypes.POINTER(c_double),
                                c_void_p],
@@ -351,8 +333,6 @@ SIGNATURES = {
     "ogg_supergrid_pass_run_dev": [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_double), c_void_p],
     "ogg_supergrid_pass_plan_destroy": [c_void_p],
     "ogg_supergrid_pass_plan_flags_dev": [c_void_p, ctypes.POINTER(c_int), c_void_p],
-    "ogg_latlon_supergrid_dev": [c_long, c_long, c_long, c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_fill_dev": [c_long, c_double, c_void_p, c_void_p],
     "ogg_bswap64_dev": [c_long, c_void_p, c_void_p, c_void_p],
     "ogg_libm_check_dev": [c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
@@ -438,30 +418,19 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_latlon_rows_workspace_bytes": [c_int, ctypes.POINTER(LatlonBand), c_long],
                 "ogg_supergrid_pass_plan_slots": [c_void_p],
                 "ogg_supergrid_pass_plan_carried_runs": [c_void_p],
-                "ogg_grid_quality_result_bytes": [],
                 "ogg_grid_quality_workspace_bytes": [c_long, c_long],
-                "ogg_topog_record_bytes": [],
-                "ogg_topog_plane_record_bytes": [],
                 "ogg_topog_band_out_rows": [ctypes.POINTER(TopogBand)],
                 "ogg_topog_workspace_bytes": [],
-                "ogg_xgrid_struct_bytes": [c_int],
                 "ogg_xgrid_band_first_row": [ctypes.POINTER(XgridBand)],
                 "ogg_xgrid_band_out_rows": [ctypes.POINTER(XgridBand)],
                 "ogg_xgrid_band_next_rows": [ctypes.POINTER(XgridBand)],
                 "ogg_xgrid_workspace_bytes": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm)],
-                "ogg_mask_struct_bytes": [c_int],
                 "ogg_mask_workspace_bytes": [ctypes.POINTER(MaskParams)],
-                "ogg_remap_struct_bytes": [c_int],
                 "ogg_remap_workspace_bytes": [ctypes.POINTER(RemapParams)],
-                "ogg_runoff_struct_bytes": [c_int],
                 "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],
-                "ogg_coast_struct_bytes": [c_int],
                 "ogg_coast_workspace_bytes": [ctypes.POINTER(CoastParams)],
-                "ogg_basin_struct_bytes": [c_int],
                 "ogg_basin_workspace_bytes": [ctypes.POINTER(BasinParams)],
-                "ogg_regrid_struct_bytes": [c_int],
-                "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long],
-                "ogg_bilinear_struct_bytes": []}
+                "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long]}
 
 _lib = None
 

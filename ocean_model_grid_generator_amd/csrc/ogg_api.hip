@@ -192,13 +192,42 @@ const char* ogg_last_error(void) { return ogg::g_err; }
 #define OGG_STR2(x) #x
 #define OGG_STR(x) OGG_STR2(x)
 const char* ogg_version(void) {
-    return "ogg_hip 0.5 (gfx950; cap columns mirrored by default, OGG_SYM_*; libm restatements read from ROCm 7.2.0 ocml, built with HIP " OGG_STR(HIP_VERSION_MAJOR) "." OGG_STR(HIP_VERSION_MINOR) "." OGG_STR(
+    return "ogg_hip 0.6 (gfx950; cap columns mirrored by default, OGG_SYM_*; libm restatements read from ROCm 7.2.0 ocml, built with HIP " OGG_STR(HIP_VERSION_MAJOR) "." OGG_STR(HIP_VERSION_MINOR) "." OGG_STR(
         HIP_VERSION_PATCH) ") src " OGG_SRC_HASH;
 }
-// sizeof of the descriptor structs of the ABI (0: ogg_latlon_band, 1: ogg_bipolar_band), so that a binding can check its layout
+// sizeof of every struct of the ABI, by its OGG_ABI_* code, so that a binding can check its layout
 long ogg_abi_sizeof(int which) {
-    return which == 0 ? (long)sizeof(ogg_latlon_band)
-                      : (which == 1 ? (long)sizeof(ogg_bipolar_band) : (which == 2 ? (long)sizeof(ogg_dpole_band) : -1L));
+    switch (which) {
+        case OGG_ABI_LATLON_BAND: return (long)sizeof(ogg_latlon_band);
+        case OGG_ABI_BIPOLAR_BAND: return (long)sizeof(ogg_bipolar_band);
+        case OGG_ABI_DPOLE_BAND: return (long)sizeof(ogg_dpole_band);
+        case OGG_ABI_QUALITY_EXTREMUM: return (long)sizeof(ogg_quality_extremum);
+        case OGG_ABI_GRID_QUALITY_RESULT: return (long)sizeof(ogg_grid_quality_result);
+        case OGG_ABI_QUALITY_BAND: return (long)sizeof(ogg_quality_band);
+        case OGG_ABI_TOPOG_SOURCE: return (long)sizeof(ogg_topog_source);
+        case OGG_ABI_TOPOG_BAND: return (long)sizeof(ogg_topog_band);
+        case OGG_ABI_TOPOG_RECORD: return (long)sizeof(ogg_topog_record);
+        case OGG_ABI_TOPOG_PLANE_RECORD: return (long)sizeof(ogg_topog_plane_record);
+        case OGG_ABI_XGRID_ATM: return (long)sizeof(ogg_xgrid_atm);
+        case OGG_ABI_XGRID_BAND: return (long)sizeof(ogg_xgrid_band);
+        case OGG_ABI_XGRID_COUNTS: return (long)sizeof(ogg_xgrid_counts);
+        case OGG_ABI_MASK_PARAMS: return (long)sizeof(ogg_mask_params);
+        case OGG_ABI_MASK_COUNTS: return (long)sizeof(ogg_mask_counts);
+        case OGG_ABI_REMAP_PARAMS: return (long)sizeof(ogg_remap_params);
+        case OGG_ABI_REMAP_COUNTS: return (long)sizeof(ogg_remap_counts);
+        case OGG_ABI_RUNOFF_PARAMS: return (long)sizeof(ogg_runoff_params);
+        case OGG_ABI_RUNOFF_COUNTS: return (long)sizeof(ogg_runoff_counts);
+        case OGG_ABI_REGRID_PARAMS: return (long)sizeof(ogg_regrid_params);
+        case OGG_ABI_REGRID_COUNTS: return (long)sizeof(ogg_regrid_counts);
+        case OGG_ABI_BILINEAR_PARAMS: return (long)sizeof(ogg_bilinear_params);
+        case OGG_ABI_COAST_PARAMS: return (long)sizeof(ogg_coast_params);
+        case OGG_ABI_COAST_COUNTS: return (long)sizeof(ogg_coast_counts);
+        case OGG_ABI_BASIN_PARAMS: return (long)sizeof(ogg_basin_params);
+        case OGG_ABI_BASIN_RULE: return (long)sizeof(ogg_basin_rule);
+        case OGG_ABI_BASIN_RULE_RECORD: return (long)sizeof(ogg_basin_rule_record);
+        case OGG_ABI_BASIN_COUNTS: return (long)sizeof(ogg_basin_counts);
+        default: return -1L;
+    }
 }
 
 int ogg_device_count(int* count) {
@@ -450,14 +479,9 @@ int ogg_displaced_pole_metrics_quad_form_sym(int arc_form, int symmetry, int ord
     return OGG_OK;
 }
 
-int ogg_displaced_pole_metrics_quad_form(int arc_form, int order, long nx, long ny, double lon0, double lat0, double lon_dp, double r_dp,
-                                         double Re, double* dxq, double* dyq, double* daq) {
-    return ogg_displaced_pole_metrics_quad_form_sym(arc_form, OGG_SYM_DEFAULT, order, nx, ny, lon0, lat0, lon_dp, r_dp, Re, dxq, dyq, daq);
-}
-
 int ogg_displaced_pole_metrics_quad(int order, long nx, long ny, double lon0, double lat0, double lon_dp, double r_dp, double Re,
                                     double* dxq, double* dyq, double* daq) {
-    return ogg_displaced_pole_metrics_quad_form(OGG_DP_ARC_CHORD, order, nx, ny, lon0, lat0, lon_dp, r_dp, Re, dxq, dyq, daq);
+    return ogg_displaced_pole_metrics_quad_form_sym(OGG_DP_ARC_CHORD, OGG_SYM_DEFAULT, order, nx, ny, lon0, lat0, lon_dp, r_dp, Re, dxq, dyq, daq);
 }
 
 // ---- small element-wise entry points -----------------------------------------------------------------------

@@ -348,16 +348,6 @@ int read_knobs(int* th, int* batch) {
 
 }  // namespace
 
-extern "C" long ogg_basin_struct_bytes(int which) {
-    switch (which) {
-        case OGG_BASIN_PARAMS: return (long)sizeof(ogg_basin_params);
-        case OGG_BASIN_RULE: return (long)sizeof(ogg_basin_rule);
-        case OGG_BASIN_RECORD: return (long)sizeof(ogg_basin_rule_record);
-        case OGG_BASIN_COUNTS: return (long)sizeof(ogg_basin_counts);
-    }
-    return -1;
-}
-
 extern "C" long ogg_basin_workspace_bytes(const ogg_basin_params* p) {
     if (!p || check_params(p) != OGG_OK) return -1;
     return layout(*p).total;

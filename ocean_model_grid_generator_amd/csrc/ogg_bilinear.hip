@@ -278,8 +278,6 @@ ogg_remap_params fill_params(const ogg_bilinear_params& p) {
 
 }  // namespace
 
-extern "C" long ogg_bilinear_struct_bytes(void) { return (long)sizeof(ogg_bilinear_params); }
-
 extern "C" int ogg_bilinear_check(const ogg_bilinear_params* p, int has_mask) { return check_params(p, has_mask); }
 
 extern "C" int ogg_bilinear_dev(const ogg_bilinear_params* p, const double* x, const double* y, long ld, const double* lon, const double* lat,

@@ -133,16 +133,6 @@ int ogg_bipolar_cap_mesh_angle_sym_dev(long Ni, long Nj, double lat0_bp, double 
     return OGG_OK;
 }
 
-int ogg_bipolar_cap_mesh_angle_dev(long Ni, long Nj, double lat0_bp, double lon_bp, long j0, long nrows, double* lams,
-                                   double* phis, double* h_i_inv, double* h_j_inv, double* angle_dx, void* stream) {
-    return ogg_bipolar_cap_mesh_angle_sym_dev(Ni, Nj, lat0_bp, lon_bp, j0, nrows, OGG_SYM_DEFAULT, lams, phis, h_i_inv, h_j_inv, angle_dx, stream);
-}
-
-int ogg_bipolar_cap_mesh_dev(long Ni, long Nj, double lat0_bp, double lon_bp, long j0, long nrows, double* lams,
-                             double* phis, double* h_i_inv, double* h_j_inv, void* stream) {
-    return ogg_bipolar_cap_mesh_angle_dev(Ni, Nj, lat0_bp, lon_bp, j0, nrows, lams, phis, h_i_inv, h_j_inv, nullptr, stream);
-}
-
 int ogg_bipolar_cap_ij_array_dev(long n_i, const double* i, long n_j, const double* j, long Ni, long Nj, double lat0_bp,
                                  double lon_bp, double rp, double* h_i_inv, double* h_j_inv, void* stream) {
     OGG_REQUIRE(n_i > 0 && n_j >= 0 && i && j && h_i_inv && h_j_inv && Ni > 0 && Nj > 0, OGG_EARG,
@@ -188,20 +178,6 @@ int ogg_bipolar_cap_metrics_quad_sym_ws_dev(int order, long nx, long ny, double 
         case 4: return launch_quad<4>(p, n_dx_rows, n_cell_rows, gap, sym, workspace, workspace_bytes, s);
         default: return launch_quad<5>(p, n_dx_rows, n_cell_rows, gap, sym, workspace, workspace_bytes, s);
     }
-}
-
-int ogg_bipolar_cap_metrics_quad_ws_dev(int order, long nx, long ny, double lat0_bp, double lon_bp, double rp, double Re,
-                                        long j0, long n_dx_rows, long n_cell_rows, double* dxq, double* dyq, double* daq,
-                                        void* workspace, long workspace_bytes, void* stream) {
-    return ogg_bipolar_cap_metrics_quad_sym_ws_dev(order, nx, ny, lat0_bp, lon_bp, rp, Re, j0, n_dx_rows, n_cell_rows, OGG_SYM_DEFAULT, dxq,
-                                                   dyq, daq, workspace, workspace_bytes, stream);
-}
-
-int ogg_bipolar_cap_metrics_quad_dev(int order, long nx, long ny, double lat0_bp, double lon_bp, double rp, double Re,
-                                     long j0, long n_dx_rows, long n_cell_rows, double* dxq, double* dyq, double* daq,
-                                     void* stream) {
-    return ogg_bipolar_cap_metrics_quad_ws_dev(order, nx, ny, lat0_bp, lon_bp, rp, Re, j0, n_dx_rows, n_cell_rows, dxq, dyq, daq,
-                                               nullptr, 0, stream);
 }
 
 }  // extern "C"

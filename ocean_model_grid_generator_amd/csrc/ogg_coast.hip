@@ -436,10 +436,6 @@ int search_side(const ogg_coast_params& p, const Knobs& kn, int G, int wet, cons
 
 }  // namespace
 
-extern "C" long ogg_coast_struct_bytes(int which) {
-    return which == OGG_COAST_PARAMS ? (long)sizeof(ogg_coast_params) : (which == OGG_COAST_COUNTS ? (long)sizeof(ogg_coast_counts) : -1L);
-}
-
 extern "C" long ogg_coast_workspace_bytes(const ogg_coast_params* p) {
     if (!p || check_params(p) != OGG_OK) return -1;
     return layout(*p).total;

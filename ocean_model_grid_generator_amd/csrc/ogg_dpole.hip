@@ -498,11 +498,6 @@ int ogg_displaced_pole_grid_angle_ws_dev(long Ni, long Nj, double lon0, double l
     return OGG_OK;
 }
 
-int ogg_displaced_pole_grid_dev(long Ni, long Nj, double lon0, double lat0, double lon_dp, double r_dp, long j0, long nrows,
-                                double* x, double* y, void* stream) {
-    return ogg_displaced_pole_grid_angle_ws_dev(Ni, Nj, lon0, lat0, lon_dp, r_dp, j0, nrows, x, y, nullptr, nullptr, 0, stream);
-}
-
 int ogg_displaced_pole_numerical_h_dev(long n_i, const double* i, long n_j, const double* j, long nx, long ny, double lon0,
                                        double lat0, double lon_dp, double r_dp, double eps, int fd_order, double* h_i,
                                        double* h_j, void* stream) {
@@ -595,27 +590,6 @@ int ogg_displaced_pole_metrics_quad_form_sym_ws_dev(int arc_form, int symmetry, 
     OGG_LAUNCH_CHECK();
     if (!workspace && arc_form == OGG_DP_ARC_LITERAL) return check_own_workspace(ws, s, "ogg_displaced_pole_metrics_quad");
     return OGG_OK;
-}
-
-int ogg_displaced_pole_metrics_quad_form_ws_dev(int arc_form, int order, long nx, long ny, double lon0, double lat0, double lon_dp,
-                                                double r_dp, double Re, long j0, long n_dx_rows, long n_cell_rows, double* dxq,
-                                                double* dyq, double* daq, void* workspace, long workspace_bytes, void* stream) {
-    return ogg_displaced_pole_metrics_quad_form_sym_ws_dev(arc_form, OGG_SYM_DEFAULT, order, nx, ny, lon0, lat0, lon_dp, r_dp, Re, j0,
-                                                           n_dx_rows, n_cell_rows, dxq, dyq, daq, workspace, workspace_bytes, stream);
-}
-
-int ogg_displaced_pole_metrics_quad_ws_dev(int order, long nx, long ny, double lon0, double lat0, double lon_dp, double r_dp,
-                                           double Re, long j0, long n_dx_rows, long n_cell_rows, double* dxq, double* dyq,
-                                           double* daq, void* workspace, long workspace_bytes, void* stream) {
-    return ogg_displaced_pole_metrics_quad_form_ws_dev(OGG_DP_ARC_CHORD, order, nx, ny, lon0, lat0, lon_dp, r_dp, Re, j0, n_dx_rows,
-                                                       n_cell_rows, dxq, dyq, daq, workspace, workspace_bytes, stream);
-}
-
-int ogg_displaced_pole_metrics_quad_dev(int order, long nx, long ny, double lon0, double lat0, double lon_dp, double r_dp,
-                                        double Re, long j0, long n_dx_rows, long n_cell_rows, double* dxq, double* dyq,
-                                        double* daq, void* stream) {
-    return ogg_displaced_pole_metrics_quad_form_ws_dev(OGG_DP_ARC_CHORD, order, nx, ny, lon0, lat0, lon_dp, r_dp, Re, j0, n_dx_rows,
-                                                       n_cell_rows, dxq, dyq, daq, nullptr, 0, stream);
 }
 
 }  // extern "C"

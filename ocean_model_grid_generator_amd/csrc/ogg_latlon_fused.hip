@@ -149,18 +149,3 @@ extern "C" int ogg_latlon_supergrid_multi_dev(int n_bands, const ogg_latlon_band
     OGG_LAUNCH_CHECK();
     return OGG_OK;
 }
-
-extern "C" int ogg_latlon_supergrid_dev(long n_pt_rows, long n_cell_rows, long ni1, const double* lat1d, const double* lon1d,
-                                        double Re, int metrics, double* x, double* y, double* dx, double* dy, double* area,
-                                        double* angle, void* stream) {
-    OGG_REQUIRE(lat1d && lon1d, OGG_EARG, "ogg_latlon_supergrid: null axis");
-    // the longitude axis of every caller is lon0 + (i*len)/Ni; recover its two scalars from the device array
-    double ends[2];
-    OGG_HIP_CHECK(hipMemcpyAsync(&ends[0], lon1d, sizeof(double), hipMemcpyDeviceToHost, ogg::as_stream(stream)));
-    OGG_HIP_CHECK(hipMemcpyAsync(&ends[1], lon1d + (ni1 - 1), sizeof(double), hipMemcpyDeviceToHost, ogg::as_stream(stream)));
-    OGG_HIP_CHECK(hipStreamSynchronize(ogg::as_stream(stream)));
-    ogg_latlon_band b{};
-    b.axis_kind = 2, b.lat1d = lat1d, b.k0 = 0, b.n_pt_rows = n_pt_rows, b.n_cell_rows = n_cell_rows;
-    b.x = x, b.y = y, b.dx = dx, b.dy = dy, b.area = area, b.angle = angle;
-    return ogg_latlon_supergrid_multi_dev(1, &b, ni1, ends[0], ends[1] - ends[0], Re, metrics, stream);
-}

@@ -192,10 +192,6 @@ long ws_bytes(const ogg_mask_params& p) { return 2 * round256(p.ny * p.nx * 4); 
 
 }  // namespace
 
-extern "C" long ogg_mask_struct_bytes(int which) {
-    return which == OGG_MASK_PARAMS ? (long)sizeof(ogg_mask_params) : (which == OGG_MASK_COUNTS ? (long)sizeof(ogg_mask_counts) : -1L);
-}
-
 extern "C" long ogg_mask_workspace_bytes(const ogg_mask_params* p) {
     if (!p || p->ny < 1 || p->nx < 1 || p->ny > (long)INT_MAX || p->nx > (long)INT_MAX || p->ny * p->nx >= (1L << 31)) return -1;
     return ws_bytes(*p);

@@ -880,19 +880,6 @@ extern "C" int ogg_supergrid_pass_plan_flags_dev(const void* plan, int* flags, v
     return OGG_OK;
 }
 
-extern "C" int ogg_tripolar_pass_events_dev(int n_latlon, const ogg_latlon_band* latlon, long ni1, double lon0, double lenlon, double Re,
-                                            int metrics, const ogg_bipolar_band* cap, void** events4, double* alg_bytes3, void* stream) {
-    void* ev5[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    double by4[4] = {0.0, 0.0, 0.0, 0.0};
-    if (events4)
-        for (int k = 0; k < 4; ++k) ev5[k] = events4[k];
-    const int rc = ogg_supergrid_pass_dev(n_latlon, latlon, ni1, lon0, lenlon, Re, metrics, cap, nullptr, events4 ? ev5 : nullptr,
-                                          alg_bytes3 ? by4 : nullptr, stream);
-    if (alg_bytes3)
-        for (int k = 0; k < 3; ++k) alg_bytes3[k] = by4[k];
-    return rc;
-}
-
 extern "C" int ogg_tripolar_pass_dev(int n_latlon, const ogg_latlon_band* latlon, long ni1, double lon0, double lenlon, double Re,
                                      int metrics, const ogg_bipolar_band* cap, void* stream) {
     return ogg_supergrid_pass_dev(n_latlon, latlon, ni1, lon0, lenlon, Re, metrics, cap, nullptr, nullptr, nullptr, stream);

@@ -312,8 +312,6 @@ long band_blocks(long nx, long n_pt) { return ((nx + 1 + QW - 1) / QW) * ((n_pt 
 
 }  // namespace
 
-extern "C" long ogg_grid_quality_result_bytes(void) { return (long)sizeof(ogg_grid_quality_result); }
-
 extern "C" long ogg_grid_quality_workspace_bytes(long nx, long n_pt_rows) {
     if (nx < 1 || n_pt_rows < 0) return -1;
     return band_blocks(nx, n_pt_rows) * (long)sizeof(ogg_grid_quality_result);

@@ -363,10 +363,6 @@ int launch_regrid_r(int rec, hipStream_t st, const Geo& g, const void* f, const 
 
 }  // namespace
 
-extern "C" long ogg_regrid_struct_bytes(int which) {
-    return which == OGG_REGRID_PARAMS ? (long)sizeof(ogg_regrid_params) : (which == OGG_REGRID_COUNTS ? (long)sizeof(ogg_regrid_counts) : -1L);
-}
-
 extern "C" long ogg_regrid_workspace_bytes(const ogg_regrid_params* p, long n_entries) {
     if (!p || check_params(p) != OGG_OK || n_entries < 0 || n_entries >= (long)INT_MAX) return -1;
     return layout(*p, n_entries).total;

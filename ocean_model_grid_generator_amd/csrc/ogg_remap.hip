@@ -385,10 +385,6 @@ void launch_remap(dim3 grid, hipStream_t st, const Geo& g, const void* f, const 
 
 }  // namespace
 
-extern "C" long ogg_remap_struct_bytes(int which) {
-    return which == OGG_REMAP_PARAMS ? (long)sizeof(ogg_remap_params) : (which == OGG_REMAP_COUNTS ? (long)sizeof(ogg_remap_counts) : -1L);
-}
-
 extern "C" long ogg_remap_workspace_bytes(const ogg_remap_params* p) {
     if (!p || check_params(p) != OGG_OK) return -1;
     return ws_bytes(*p);

@@ -452,10 +452,6 @@ int check_ws(const ogg_runoff_params& p, const void* ws, long wsb, const char* w
 
 }  // namespace
 
-extern "C" long ogg_runoff_struct_bytes(int which) {
-    return which == OGG_RUNOFF_PARAMS ? (long)sizeof(ogg_runoff_params) : (which == OGG_RUNOFF_COUNTS ? (long)sizeof(ogg_runoff_counts) : -1L);
-}
-
 extern "C" long ogg_runoff_workspace_bytes(const ogg_runoff_params* p) {
     if (!p || check_params(p) != OGG_OK) return -1;
     return layout(*p).total;

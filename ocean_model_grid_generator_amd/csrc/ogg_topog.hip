@@ -435,10 +435,6 @@ long out_rows(const ogg_topog_band& b) {
 
 }  // namespace
 
-extern "C" long ogg_topog_record_bytes(void) { return (long)sizeof(ogg_topog_record); }
-
-extern "C" long ogg_topog_plane_record_bytes(void) { return (long)sizeof(ogg_topog_plane_record); }
-
 extern "C" long ogg_topog_workspace_bytes(void) { return 256; }
 
 extern "C" long ogg_topog_band_out_rows(const ogg_topog_band* band) {

@@ -462,12 +462,6 @@ Geo make_geo(const ogg_xgrid_band& b) {
 
 }  // namespace
 
-extern "C" long ogg_xgrid_struct_bytes(int which) {
-    return which == OGG_XGRID_BAND ? (long)sizeof(ogg_xgrid_band)
-                                   : (which == OGG_XGRID_ATM ? (long)sizeof(ogg_xgrid_atm)
-                                                             : (which == OGG_XGRID_COUNTS ? (long)sizeof(ogg_xgrid_counts) : -1L));
-}
-
 extern "C" long ogg_xgrid_band_first_row(const ogg_xgrid_band* band) {
     if (!band || band->j0 < 0 || band->n_cell_rows < 0) return -1;
     return first_row(*band);

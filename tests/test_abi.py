@@ -49,6 +49,53 @@ def test_math_eval_codes_match_the_header():
     assert {k.lower(): int(v) for k, v in defines.items()} == _lib.MATH
 
 
+def test_every_struct_has_a_size_code_and_a_mirror():
+    """Every struct of the header has an OGG_ABI_* code, _lib restates the codes (the same names, the same numbers) and holds a mirror of
+    each struct, and every mirror has the size the compiler gives the struct: a silent mismatch would shift every pointer behind it."""
+    import numpy as np
+    from ocean_model_grid_generator_amd import _lib
+    text = open(HEADER).read()
+    structs = set(re.findall(r"^\}\s*ogg_([a-z0-9_]+);", text, flags=re.M))
+    assert len(structs) == len(re.findall(r"\btypedef struct\b", text)) >= 28
+    defines = {k: int(v) for k, v in re.findall(r"^#define OGG_ABI_([A-Z0-9_]+)\s+(\d+)", text, flags=re.M)}
+    n = defines.pop("N")
+    assert {k.lower() for k in defines} == structs
+    assert sorted(defines.values()) == list(range(n))
+    assert defines == _lib.ABI and set(_lib.ABI_MIRRORS) == set(_lib.ABI)
+    lib = _lib.load()
+    for name, code in _lib.ABI.items():
+        mirror = _lib.ABI_MIRRORS[name]
+        size = mirror.itemsize if isinstance(mirror, np.dtype) else ctypes.sizeof(mirror)
+        assert lib.ogg_abi_sizeof(code) == size, name
+    assert lib.ogg_abi_sizeof(-1) == lib.ogg_abi_sizeof(n) == -1
+
+
+def exported_symbols(path):
+    """The defined dynamic symbols of a shared library that begin with ogg_, or None when no tool that lists them is installed."""
+    import shutil
+    import subprocess
+    nm = shutil.which("nm")
+    readelf = shutil.which("llvm-readelf", path=os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin"))
+    if nm:
+        out = subprocess.run([nm, "-D", "--defined-only", path], check=True, stdout=subprocess.PIPE, text=True).stdout
+        names = [line.split()[-1] for line in out.splitlines() if line.split()]
+    elif readelf:
+        out = subprocess.run([readelf, "--dyn-syms", "-W", path], check=True, stdout=subprocess.PIPE, text=True).stdout
+        names = [f[7] for f in (line.split() for line in out.splitlines()) if len(f) == 8 and f[6] != "UND"]
+    else:
+        return None
+    return sorted({n.split("@")[0] for n in names if n.startswith("ogg_")})
+
+
+def test_library_exports_nothing_the_header_does_not_declare():
+    """The other direction of test_library_exports_every_declared_symbol: an entry point that left the header has left the library."""
+    from ocean_model_grid_generator_amd import _lib
+    exported = exported_symbols(_lib.LIB_PATH)
+    if exported is None:
+        pytest.skip("neither nm nor llvm-readelf is installed")
+    assert exported == declared_symbols()
+
+
 def test_descriptor_structs_have_the_c_layout():
     """The ctypes mirrors of the three descriptor structs must have the size the compiler gives them (a silent mismatch would
     shift every pointer), and the pass validates its arguments before any device work."""
@@ -57,7 +104,7 @@ def test_descriptor_structs_have_the_c_layout():
     assert lib.ogg_abi_sizeof(0) == ctypes.sizeof(_lib.LatlonBand)
     assert lib.ogg_abi_sizeof(1) == ctypes.sizeof(_lib.BipolarBand)
     assert lib.ogg_abi_sizeof(2) == ctypes.sizeof(_lib.DpoleBand)
-    assert lib.ogg_abi_sizeof(3) == -1
+    assert lib.ogg_abi_sizeof(-1) == lib.ogg_abi_sizeof(len(_lib.ABI)) == -1     # len(_lib.ABI) == OGG_ABI_N, checked below
     bands = (_lib.LatlonBand * 5)()
     rc = lib.ogg_tripolar_pass_dev(5, bands, 1441, -300.0, 360.0, 6371e3, 1, None, None)     # more than 4 lat-lon bands
     assert rc == _lib.OGG_EARG and b"at most 4 bands" in lib.ogg_last_error()

@@ -152,7 +152,7 @@ def test_struct_size_and_check_refusals():
     from ocean_model_grid_generator_amd import _lib as L
     from ocean_model_grid_generator_amd import bilinear as B
     lib = L.load()
-    assert lib.ogg_bilinear_struct_bytes() == ctypes.sizeof(L.BilinearParams)
+    assert lib.ogg_abi_sizeof(L.ABI["BILINEAR_PARAMS"]) == ctypes.sizeof(L.BilinearParams)
     B.check(good_params(L))
     B.check(good_params(L, points=L.BILINEAR_C, ncomp=2))
     B.check(good_params(L, points=L.BILINEAR_H, ncomp=2), has_mask=True)

@@ -178,8 +178,8 @@ def test_abi_refuses_bad_parameters_and_knobs(monkeypatch):
     from ocean_model_grid_generator_amd import _lib as L
     from ocean_model_grid_generator_amd import coast_distance as CD
     lib = L.load()
-    assert lib.ogg_coast_struct_bytes(L.COAST_PARAMS) == ctypes.sizeof(L.CoastParams)
-    assert lib.ogg_coast_struct_bytes(L.COAST_COUNTS) == ctypes.sizeof(L.CoastCounts) and lib.ogg_coast_struct_bytes(2) == -1
+    assert lib.ogg_abi_sizeof(L.ABI["COAST_PARAMS"]) == ctypes.sizeof(L.CoastParams)
+    assert lib.ogg_abi_sizeof(L.ABI["COAST_COUNTS"]) == ctypes.sizeof(L.CoastCounts)
     with pytest.raises(ValueError, match="sides"):
         CD.params(4, 8, sides="ocean")
     for bad in (dict(ny=0, nx=4, topology=0, sides=3), dict(ny=1 << 16, nx=1 << 15, topology=0, sides=3), dict(ny=4, nx=4, topology=4, sides=3),

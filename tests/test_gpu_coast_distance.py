@@ -194,8 +194,8 @@ def test_main_function_level_and_file_command_write_the_same_bytes(hip, tmp_path
 def test_struct_layout(hip):
     L = hip
     lib = L.load()
-    assert lib.ogg_coast_struct_bytes(L.COAST_PARAMS) == ctypes.sizeof(L.CoastParams) == 24
-    assert lib.ogg_coast_struct_bytes(L.COAST_COUNTS) == ctypes.sizeof(L.CoastCounts) == 8 * len(L.COAST_COUNT_FIELDS)
+    assert lib.ogg_abi_sizeof(L.ABI["COAST_PARAMS"]) == ctypes.sizeof(L.CoastParams) == 24
+    assert lib.ogg_abi_sizeof(L.ABI["COAST_COUNTS"]) == ctypes.sizeof(L.CoastCounts) == 8 * len(L.COAST_COUNT_FIELDS)
     assert [L.CoastParams.ny.offset, L.CoastParams.nx.offset, L.CoastParams.topology.offset, L.CoastParams.sides.offset] == [0, 8, 16, 20]
     # the host-pointer entry fills the ctypes counts in the header's order
     from ocean_model_grid_generator_amd import coast_distance as CD

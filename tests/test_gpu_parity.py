@@ -623,7 +623,7 @@ def test_displaced_pole_quad_bands_are_bit_identical(hip):
         wsb = int(lib.ogg_displaced_pole_quad_workspace_bytes(order, Ni, n_cell))
         ws = torch.empty(wsb, dtype=torch.uint8, device="cuda:0")
         out = [torch.full(shp, float("nan"), dtype=torch.float64, device="cuda:0") for shp in ((n_dx, Ni), (n_cell, Ni + 1), (n_cell, Ni))]
-        L.call("ogg_displaced_pole_metrics_quad_form_ws_dev", form, order, Ni, Nj, -300.0, -78.0, 80.0, 0.3, 6371.0e3, j0, n_dx, n_cell,
+        L.call("ogg_displaced_pole_metrics_quad_form_sym_ws_dev", form, L.SYM_DEFAULT, order, Ni, Nj, -300.0, -78.0, 80.0, 0.3, 6371.0e3, j0, n_dx, n_cell,
                out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(), wsb, st)
         flag = ctypes.c_int(-1)
         L.call("ogg_workspace_error_flag_dev", ws.data_ptr(), ctypes.byref(flag), st)

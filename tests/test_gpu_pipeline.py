@@ -363,7 +363,7 @@ def test_pass_does_not_depend_on_tiling_knobs(sg, name, dp_arc, monkeypatch):
 def test_supergrid_pass_southern_cap_alone_matches_function_level(hip, order, arc):
     """ogg_supergrid_pass_dev with nothing but a displaced-pole band (no lat-lon bands, no bipolar cap), both quadrature orders and
     both arc forms, band in the middle of the cap: the same bits as ogg_displaced_pole_grid_angle_ws_dev +
-    ogg_displaced_pole_metrics_quad_form_ws_dev."""
+    ogg_displaced_pole_metrics_quad_form_sym_ws_dev."""
     import ctypes
     import torch
     from ocean_model_grid_generator_amd import _lib as L
@@ -393,7 +393,7 @@ def test_supergrid_pass_southern_cap_alone_matches_function_level(hip, order, ar
     w2 = torch.zeros(qws, dtype=torch.uint8, device="cuda:0")
     L.call("ogg_displaced_pole_grid_angle_ws_dev", Ni, Nj, geo[0], geo[1], geo[2], geo[3], j0, n, b["x"].data_ptr(), b["y"].data_ptr(),
            b["angle"].data_ptr(), w1.data_ptr(), mws, st)
-    L.call("ogg_displaced_pole_metrics_quad_form_ws_dev", form, order, Ni, Nj, geo[0], geo[1], geo[2], geo[3], 6371.0e3, j0, n, n,
+    L.call("ogg_displaced_pole_metrics_quad_form_sym_ws_dev", form, L.SYM_DEFAULT, order, Ni, Nj, geo[0], geo[1], geo[2], geo[3], 6371.0e3, j0, n, n,
            b["dx"].data_ptr(), b["dy"].data_ptr(), b["area"].data_ptr(), w2.data_ptr(), qws, st)
     torch.cuda.synchronize()
     for f in a:

@@ -64,8 +64,8 @@ def test_bipolar_quadrature_random_bands(ogg, hip, seed):
         dx = torch.full((n_dx, nx), float("nan"), dtype=torch.float64, device="cuda")
         dy = torch.full((max(n_cell, 0), nx + 1), float("nan"), dtype=torch.float64, device="cuda")
         da = torch.full((max(n_cell, 0), nx), float("nan"), dtype=torch.float64, device="cuda")
-        L.call("ogg_bipolar_cap_metrics_quad_ws_dev", 5, nx, ny, lat0, -300.0, rp, orc.RE_DEFAULT, lo, n_dx, max(n_cell, 0), dx.data_ptr(),
-               dy.data_ptr() if n_cell > 0 else None, da.data_ptr() if n_cell > 0 else None, ws.data_ptr(), wsb, st)
+        L.call("ogg_bipolar_cap_metrics_quad_sym_ws_dev", 5, nx, ny, lat0, -300.0, rp, orc.RE_DEFAULT, lo, n_dx, max(n_cell, 0), L.SYM_DEFAULT,
+               dx.data_ptr(), dy.data_ptr() if n_cell > 0 else None, da.data_ptr() if n_cell > 0 else None, ws.data_ptr(), wsb, st)
         torch.cuda.synchronize()
         assert np.array_equal(dx.cpu().numpy(), whole[0][lo:hi]), (lo, hi)
         if n_cell > 0:

@@ -186,9 +186,8 @@ def test_writers_read_back_through_scipy(tmp_path):
 def test_struct_sizes_and_refusals():
     from ocean_model_grid_generator_amd import _lib as L
     lib = L.load()
-    assert lib.ogg_regrid_struct_bytes(L.REGRID_PARAMS) == ctypes.sizeof(L.RegridParams) == 72
-    assert lib.ogg_regrid_struct_bytes(L.REGRID_COUNTS) == ctypes.sizeof(L.RegridCounts) == 48
-    assert lib.ogg_regrid_struct_bytes(5) == -1
+    assert lib.ogg_abi_sizeof(L.ABI["REGRID_PARAMS"]) == ctypes.sizeof(L.RegridParams) == 72
+    assert lib.ogg_abi_sizeof(L.ABI["REGRID_COUNTS"]) == ctypes.sizeof(L.RegridCounts) == 48
 
     def p(**kw):
         d = dict(ny=4, nx=6, NA=8, NB=4, nrec=2, dtype=L.REMAP_FLOAT32, n_fill=1, normalize=L.REGRID_AREA)

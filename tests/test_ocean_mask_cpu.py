@@ -175,9 +175,8 @@ def test_knobs_must_be_integers_in_range(hip_lib, monkeypatch):
 
 def test_struct_sizes_equal_the_ctypes_mirrors(hip_lib):
     L, lib = hip_lib
-    assert lib.ogg_mask_struct_bytes(L.MASK_PARAMS) == ctypes.sizeof(L.MaskParams)
-    assert lib.ogg_mask_struct_bytes(L.MASK_COUNTS) == ctypes.sizeof(L.MaskCounts)
-    assert lib.ogg_mask_struct_bytes(2) == -1
+    assert lib.ogg_abi_sizeof(L.ABI["MASK_PARAMS"]) == ctypes.sizeof(L.MaskParams)
+    assert lib.ogg_abi_sizeof(L.ABI["MASK_COUNTS"]) == ctypes.sizeof(L.MaskCounts)
 
 
 def test_main_flags():

@@ -97,7 +97,7 @@ def test_host_merge_is_order_free():
     for _ in range(5):
         perm = rng.permutation(len(recs))
         assert Q.merge([recs[k] for k in perm]) == want
-    assert L.load().ogg_grid_quality_result_bytes() == __import__("ctypes").sizeof(L.QualityResult)
+    assert L.load().ogg_abi_sizeof(L.ABI["GRID_QUALITY_RESULT"]) == __import__("ctypes").sizeof(L.QualityResult)
 
 
 # ---- NetCDF classic reader -----------------------------------------------------------------------------------

@@ -191,9 +191,8 @@ def test_unreachable_wet_cell_stays_unfilled():
 def test_struct_sizes_and_refusals():
     from ocean_model_grid_generator_amd import _lib as L
     lib = L.load()
-    assert lib.ogg_remap_struct_bytes(L.REMAP_PARAMS) == ctypes.sizeof(L.RemapParams) == 80
-    assert lib.ogg_remap_struct_bytes(L.REMAP_COUNTS) == ctypes.sizeof(L.RemapCounts) == 64
-    assert lib.ogg_remap_struct_bytes(7) == -1
+    assert lib.ogg_abi_sizeof(L.ABI["REMAP_PARAMS"]) == ctypes.sizeof(L.RemapParams) == 80
+    assert lib.ogg_abi_sizeof(L.ABI["REMAP_COUNTS"]) == ctypes.sizeof(L.RemapCounts) == 64
 
     def p(**kw):
         d = dict(ny=4, nx=6, m0=0, NA=8, NB=4, nrec=2, dtype=L.REMAP_FLOAT64, n_fill=1, topology=3, fill_max=-1)

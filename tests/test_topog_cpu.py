@@ -264,6 +264,6 @@ def test_argument_errors():
     band.refine, src.dtype = 0, L.TOPOG_FLOAT32
     assert lib.ogg_topog_band_dev(ctypes.byref(band), ctypes.byref(src), 8, 256, 8, None) == L.OGG_EARG
     assert b"quantise" in lib.ogg_last_error()
-    assert lib.ogg_topog_record_bytes() == L.TOPOG_RECORD.itemsize
+    assert lib.ogg_abi_sizeof(L.ABI["TOPOG_RECORD"]) == L.TOPOG_RECORD.itemsize
     band.j0, band.n_cell_rows = 3, 4
     assert lib.ogg_topog_band_out_rows(ctypes.byref(band)) == 3    # model rows 1, 2, 3

@@ -307,7 +307,7 @@ def test_exact_centred_moment_against_python_integers():
 
 # ---- interfaces ------------------------------------------------------------------------------------------------
 def test_record_layout_constants_and_the_flag_that_needs_a_source():
-    assert L.TOPOG_PLANE_RECORD.itemsize == 120 and L.load().ogg_topog_plane_record_bytes() == 120
+    assert L.TOPOG_PLANE_RECORD.itemsize == 120 and L.load().ogg_abi_sizeof(L.ABI["TOPOG_PLANE_RECORD"]) == 120
     assert L.TOPOG_PLANE_RECORD.names[:len(L.TOPOG_RECORD.names)] == L.TOPOG_RECORD.names
     assert all(L.TOPOG_PLANE_RECORD.fields[f][1] == L.TOPOG_RECORD.fields[f][1] for f in L.TOPOG_RECORD.names)
     assert L.TOPOG_PLANE_RECORD.names[len(L.TOPOG_RECORD.names):] == tp.MOMENTS and L.TOPOG_PLANE_MAX_OFFSET == tp.MAX_OFFSET == 2 ** 15

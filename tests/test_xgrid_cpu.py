@@ -136,10 +136,9 @@ def test_xgrid_file_layout(tmp_path):
 
 def test_structs_and_argument_checks_before_device_work():
     lib = L.load()
-    assert lib.ogg_xgrid_struct_bytes(L.XGRID_BAND) == ctypes.sizeof(L.XgridBand)
-    assert lib.ogg_xgrid_struct_bytes(L.XGRID_ATM) == ctypes.sizeof(L.XgridAtm)
-    assert lib.ogg_xgrid_struct_bytes(L.XGRID_COUNTS) == ctypes.sizeof(L.XgridCounts) == 64
-    assert lib.ogg_xgrid_struct_bytes(3) == -1
+    assert lib.ogg_abi_sizeof(L.ABI["XGRID_BAND"]) == ctypes.sizeof(L.XgridBand)
+    assert lib.ogg_abi_sizeof(L.ABI["XGRID_ATM"]) == ctypes.sizeof(L.XgridAtm)
+    assert lib.ogg_abi_sizeof(L.ABI["XGRID_COUNTS"]) == ctypes.sizeof(L.XgridCounts) == 64
     x, y = latlon_supergrid(0.0, -10.0, 1.0, 1.0, 8, 4)
     counts = L.XgridCounts()
     out = np.zeros(64)
