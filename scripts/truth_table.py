@@ -35,13 +35,19 @@ Three groups ("next round" item 1):
                     rows (the joint, mid-cap, the ten rows under the pole incl. the j = ny - 0.001 row) x every 37th column and the ten
                     columns around each symmetry meridian (the cells that touch the two pole points).
 
+  small             every point of four SMALL caps (x, y, angle_x over the exact mesh), into a fixture of its own:
+
+    python scripts/truth_table.py --groups small             ->  tests/golden/truth_small_caps.npz   (truth_table.npz is left alone)
+
 Stored per value: hi = fp64(truth), lo = fp64(truth - hi)  (so that v - truth = (v - hi) - lo to 1e-32 relative), and
 the oracle's distance from the truth as measured when the fixture was made (`*_eref`), which the tests use as the unit
-of their tolerances.
+of their tolerances.  The `small` fixture holds every point of its caps, so it stores each value as ONE 64-bit integer k,
+truth = k * 2^-54 degrees (rounded to 5.6e-17 degrees; the test rebuilds exact hi / lo pairs from k): half the bytes.
 """
 import argparse
 import os
 import sys
+import tempfile
 import time
 from multiprocessing import Pool
 
@@ -632,17 +638,139 @@ def mdso_group(pool, quick):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# small: WHOLE small caps -- every point of the bipolar caps of the plans at inverse resolution 0.25 (Ni = 180: Ni/4 odd) and 0.5 and of the
+# kept rows of two displaced-pole caps at inverse resolution 0.5: exact x, y (OGG:41-70 / OGG:447-467) and angle_x over the exact mesh
+# (OGG:719-729).  Its own fixture, tests/golden/truth_small_caps.npz (tests/test_gpu_small_caps_truth.py)
+# ---------------------------------------------------------------------------------------------------------------
+SMALL_OUT = os.path.join(ROOT, "tests", "golden", "truth_small_caps.npz")
+FIX_BITS = 54                                    # values are stored as integers k with truth = k * 2^-54 degrees (5.6e-17) +- half a unit
+SMALL_CAPS = (("sbp180_", "bipolar", dict(inverse_resolution=0.25, ensure_nj_even=True)),
+              ("sbp360_", "bipolar", dict(inverse_resolution=0.5, ensure_nj_even=True)),
+              ("sdp_rdp_", "dpole", dict(inverse_resolution=0.5, r_dp=0.2, ensure_nj_even=True)),
+              ("sdp_latdp_", "dpole", dict(inverse_resolution=0.5, lat_dp=-85.85, lon_dp=80.0, ensure_nj_even=True)))
+
+
+def fix(pair):
+    """(hi, lo) -> the integer nearest to truth * 2^FIX_BITS (|truth| < 512 degrees: fits 64 bits)."""
+    return int(mp.nint((M(pair[0]) + M(pair[1])) * 2 ** FIX_BITS))
+
+
+def unfix(k):
+    """int64 array -> (..., 2) hi / lo pairs: hi = fp64(k 2^-54), lo = k 2^-54 - hi (exact)."""
+    k = np.asarray(k, dtype=np.int64)
+    hi = np.ldexp(k.astype(np.float64), -FIX_BITS)
+    rest = k - np.ldexp(hi, FIX_BITS).astype(np.int64)
+    return np.stack([hi, np.ldexp(rest.astype(np.float64), -FIX_BITS)], axis=-1)
+
+
+def small_bp_point(args):
+    par, j, i, lon3, lat = args
+    x, y, guard = bp_point((lon3[1], lat, par[3], par[4]))
+    _, _, a = ax_bp_point(args)
+    return fix(x), fix(y), fix(a), guard
+
+
+def small_dp_point(args):
+    _, _, a, x, y = ax_dp_point(args)
+    return fix(x), fix(y), fix(a), False
+
+
+def save_npz_reproducibly(path, arrays):
+    """numpy.savez_compressed with the members in sorted order and a fixed time stamp: the same arrays give the same bytes."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for name in sorted(arrays):
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with z.open(info, "w") as f:
+                np.lib.format.write_array(f, np.ascontiguousarray(arrays[name]), allow_pickle=False)
+
+
+def small_group(pool, quick):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import angle_bounds                                                                  # the stencil's shape 1 / hypot(N, D)
+    out = {"dps": np.array(mp.mp.dps), "fix_bits": np.array(FIX_BITS)}
+    for tag, kind, flags in (SMALL_CAPS[:1] if quick else SMALL_CAPS):
+        f = dict(flags)
+        r = f.pop("inverse_resolution")
+        w = orc.make_supergrid(r, skip_metrics=True, skip_doughnut_rows=True, **f)
+        Ni, q = w["Ni"], w["Ni"] // 4
+        if kind == "bipolar":
+            ox, oy = w["sub"]["BP"][0], w["sub"]["BP"][1]
+            Nj, lat0, lon_bp = ox.shape[0] - 1, float(w["sub"]["Merc"][1][-1, q]), -300.0
+            rp = float(np.tan(0.5 * (90 - lat0) * orc.PI_180))
+            lon_g = lon_bp + np.arange(Ni + 1) * 360.0 / float(Ni)                       # OGG:108-115, fp64 as the reference forms them
+            latg0 = lat0 + np.arange(Nj + 1) * (90 - lat0) / float(Nj)
+            par = (Ni, Nj, lat0, lon_bp, rp)
+            jobs = [(par, j, i, [lon_g[min(max(c, 0), Ni)] for c in (i - 1, i, i + 1)], latg0[j]) for j in range(Nj + 1) for i in range(Ni + 1)]
+            worker, params, rows = small_bp_point, np.array(par), Nj + 1
+        else:
+            ox, oy = w["sub"]["SC"][0], w["sub"]["SC"][1]                                # the rows main() keeps (OGG:1177-1186)
+            ny = int(r * 40) * 7 // 4
+            row0, lat0 = ny + 1 - ox.shape[0], float(w["sub"]["SO"][1][0, q])
+            r_dp = f.get("r_dp", 0.0)
+            if f.get("lat_dp", -99.0) > -90:
+                r_dp = float(np.tan((90 + f["lat_dp"]) * orc.PI_180) / np.tan((90 + lat0) * orc.PI_180))   # OGG:1160 (main's fp64 value: an INPUT)
+            par = (Ni, ny, -300.0, lat0, f.get("lon_dp", 80.0), r_dp)
+            jobs = [(par, row0 + j, i, [ox[j, min(max(c, 0), Ni)] for c in (i - 1, i, i + 1)]) for j in range(ox.shape[0]) for i in range(Ni + 1)]
+            worker, params, rows = small_dp_point, np.array(par + (row0, ox.shape[0])), ox.shape[0]
+        t0 = time.time()
+        res = pool.map(worker, jobs, chunksize=32)
+        print("small %s: %d points in %.0f s" % (tag, len(jobs), time.time() - t0), flush=True)
+        k = np.array([p[:3] for p in res], dtype=np.int64).reshape(rows, Ni + 1, 3)
+        out.update({tag + "params": params, tag + "x": k[..., 0].copy(), tag + "y": k[..., 1].copy(), tag + "angle": k[..., 2].copy()})
+        # the oracle's own distances from the truth, per class
+        top = np.zeros(ox.shape, bool)
+        ill = np.zeros(ox.shape, bool)
+        if kind == "bipolar":
+            guard = np.array([p[3] for p in res]).reshape(rows, Ni + 1)
+            ph2 = 90 - 2 * np.arctan(np.tan(0.5 * (90 - np.tile(latg0[:, None], (1, Ni + 1))) * orc.PI_180) / rp) / orc.PI_180
+            assert np.array_equal(np.abs(np.tan(ph2 * orc.PI_180) ** 2) > 1e30, guard)      # fp64 and exact arithmetic take the same branch of OGG:52
+            top[-1, :] = True
+            for c in (q, 3 * q):
+                ill[:-1, c - 2:c + 3] = True
+        for fld, o, col in (("x", ox, 0), ("y", oy, 1)):
+            t = unfix(k[..., col])
+            e = np.abs((o - t[..., 0]) - t[..., 1])
+            for nm, m in (("regular", ~top & ~ill), ("ill_columns", ill), ("top_row", top)):
+                if m.any():
+                    out[tag + fld + "_eref_" + nm] = np.array(e[m].max())
+                    print("small %s oracle vs truth %s %s: %.3e deg" % (tag, fld, nm, e[m].max()))
+        t = unfix(k[..., 2])
+        e = np.abs((orc.angle_x(ox, oy) - t[..., 0]) - t[..., 1])
+        e = np.minimum(e, np.abs(e - 360.0))
+        shp = angle_bounds.shape(ox, oy)
+        fin = np.isfinite(shp)
+        c = np.where(fin, e / np.where(fin, shp, 1.0), 0.0)
+        out[tag + "angle_c_ref"] = np.array(c.max())
+        jw, iw = np.unravel_index(c.argmax(), c.shape)
+        print("small %s oracle vs truth angle: c_ref %.3e deg (row %d column %d), max error %.3e deg, %d points without a stencil" %
+              (tag, c.max(), jw, iw, e[fin].max(), int((~fin).sum())))
+    return out
+
+
 GROUPS = {"md": md_group, "bq": bq_group, "bp": bp_group, "dp": dp_group, "dp4": lambda pool, quick: dp_group(pool, quick, "dp4"),
           "ax": ax_group, "dm": dm_group, "bq16": bq16_group, "mdso": mdso_group}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--groups", nargs="+", default=list(GROUPS), help="which groups to (re)compute; the others are kept from the existing fixture")
+    ap.add_argument("--groups", nargs="+", default=list(GROUPS), help="which groups to (re)compute; the others are kept from the existing fixture (`small` writes tests/golden/truth_small_caps.npz and leaves truth_table.npz alone)")
     ap.add_argument("--procs", type=int, default=8)
     ap.add_argument("--quick", action="store_true", help="a thin sample (smoke run of this script; does not overwrite the fixture)")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "truth_table.npz"))
     a = ap.parse_args()
+    if "small" in a.groups:                                                    # its own fixture; truth_table.npz is not rewritten
+        with Pool(a.procs) as pool:
+            small = small_group(pool, a.quick)
+        path = SMALL_OUT if not a.quick else os.path.join(tempfile.gettempdir(), "truth_small_caps_quick.npz")
+        save_npz_reproducibly(path, small)
+        print("wrote", path, os.path.getsize(path), "bytes")
+        a.groups = [g for g in a.groups if g != "small"]
+        if not a.groups:
+            return
     out = {"dps": np.array(mp.mp.dps)}
     if not a.quick and os.path.exists(a.out) and set(a.groups) != set(GROUPS):
         out.update({k: v for k, v in np.load(a.out).items()})              # keep the groups that are not recomputed

@@ -15,7 +15,10 @@ field was measured (DESIGN.md "Parity"); the bounds below are tho
   bipolar quadrature dx, dy, area       rel 5e-14
   displaced-pole quadrature dx, dy,     rel 2e-12 * Ni  (10x the measured difference, which grows with the resolution: finite
                      area                             differences of an arc of 2e-3 * 360/Ni degrees; see dp_quad_rel_tol)
-  angle_dx                              1e-10 deg away from singular points (pole rows)
+  angle_dx                              EVERY point: equal on lat-lon rows; elsewhere within the first-order change of atan2(N, D) under
+                                        the coordinate bounds above, x 1.5 (tests/angle_bounds.py); nothing at the three points of the
+                                        bipolar cap's top row where the stencil vanishes (columns Ni/4, Ni/2, 3Ni/4), whose number is
+                                        counted on the oracle's mesh; and 99.9 % of a grid within 1e-9 deg
 """
 import json
 import os
@@ -23,6 +26,7 @@ import os
 import numpy as np
 import pytest
 
+import angle_bounds
 from oracle import ogg_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -30,6 +34,7 @@ pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 TOL_COORD = 1e-12
 TOL_COORD_ILL = 2e-11
+BP_POLE_POINT_TOL_Y = 1e-6
 REPORT = {}
 
 
@@ -674,7 +679,8 @@ def dp_quad_rel_tol(Ni):
 SUB_TOL = {
     "latlon": {"x": (1e-13, 0.0), "y": (1e-13, 0.0), "dx": (1e-10, 5e-14), "dy": (2e-8, 5e-14), "area": (1e-6, 1.2e-11)},   # area: 10 x the measured 1.2e-12
     # (area: 6.5e-14 in the four cells that touch the pole points at 1/2 degree, <= 1e-14 elsewhere)
-    "bipolar": {"x": (TOL_COORD_ILL, 0.0), "y": (1e-6, 0.0), "dx": (1e-9, 5e-14), "dy": (1e-9, 5e-14), "area": (1e-6, 2e-13)},
+    # (x, y: the bound of the REGULAR points of the cap; the ill-conditioned ones keep TOL_COORD_ILL / 1e-6 by the masks of _row_tolerances)
+    "bipolar": {"x": (TOL_COORD, 0.0), "y": (TOL_COORD, 0.0), "dx": (1e-9, 5e-14), "dy": (1e-9, 5e-14), "area": (1e-6, 2e-13)},
     # displaced-pole cap: metrics purely RELATIVE, dp_quad_rel_tol(Ni) (None below) -- at 1/8 degree that is 1.15e-8 of a 7 km cell: the
     # measured differences from the oracle are 1.3e-6 m (dx), 1.8e-6 m (dy) and 2e-3 m^2 (area), i.e. north_star's 1e-6 m^2 is NOT met
     # here, and cannot be: the fp64 reference itself is 1.2e-9 relative = 3e-3 m^2 away from the exact value of its own formula
@@ -690,12 +696,21 @@ def _piece(sub, name, k):
     return v[("x", "y", "dx", "dy", "area", "angle_dx")[k]] if isinstance(v, dict) else v[k]
 
 
+def _bipolar_rows(got):
+    """(lo, hi): the stitched point rows that come from the bipolar cap (it is the northernmost piece and keeps all its rows); (n, n) without one."""
+    n = got["x"].shape[0]
+    return (n - _piece(got["sub"], "BP", 0).shape[0], n) if "BP" in got["sub"] else (n, n)
+
+
 def _row_tolerances(got, field):
-    """Per-row (abs, rel) of a stitched field from the sub-grids `got` was stitched from, counted from the NORTH end (south cuts
-    remove rows at the south end only): x, y, dx, angle_dx drop the southern piece's last row at every joint, dy and area do not."""
+    """Per-POINT (abs, rel) arrays of a stitched field from the sub-grids `got` was stitched from, rows counted from the NORTH end (south
+    cuts remove rows at the south end only): x, y, dx, angle_dx drop the southern piece's last row at every joint, dy and area do not.
+    The bipolar cap's coordinates are held to TOL_COORD at every point but the ill-conditioned ones, by masks: x keeps TOL_COORD_ILL on the
+    top (fold) row and within 2 columns of the two symmetry meridians Ni/4, 3Ni/4 (the `ill` mask of test_bipolar_cap_mesh); y keeps 1e-6 at
+    the three points of the top row where the stencil of the angle vanishes (columns Ni/4, Ni/2, 3Ni/4), nowhere else."""
     k = ("x", "y", "dx", "dy", "area").index(field)
-    n = got[field].shape[0]
-    a, r = np.zeros(n), np.zeros(n)
+    n, ncol = got[field].shape
+    a, r = np.zeros((n, ncol)), np.zeros((n, ncol))
     hi = n
     Ni = got["x"].shape[1] - 1
     names = [s for s in ("BP", "Merc", "SO", "SC") if s in got["sub"]]
@@ -709,14 +724,20 @@ def _row_tolerances(got, field):
         ta, tr = SUB_TOL[kind][field]
         lo = max(hi - rows, 0)
         a[lo:hi], r[lo:hi] = ta, (dp_quad_rel_tol(Ni) if tr is None else tr)
+        if kind == "bipolar" and field == "x" and hi > lo:
+            for c in (Ni // 4, 3 * Ni // 4):
+                a[lo:hi, max(c - 2, 0):c + 3] = TOL_COORD_ILL
+            a[hi - 1, :] = TOL_COORD_ILL
+        if kind == "bipolar" and field == "y" and hi > lo:
+            a[hi - 1, [Ni // 4, Ni // 2, 3 * Ni // 4]] = BP_POLE_POINT_TOL_Y
         hi = lo
     assert hi == 0, (field, hi)
-    return a[:, None], r[:, None]
+    return a, r
 
 
 def _check_supergrid(got, want, name):
-    """Every element of every stitched field against the oracle / the golden arrays, each row held to the bound of the sub-grid it
-    came from (SUB_TOL)."""
+    """Every element of every stitched field against the oracle / the golden arrays, each point held to the bound of the sub-grid it
+    came from (SUB_TOL); angle_dx to the bound that follows from the coordinate bounds enforced here (tests/angle_bounds.py)."""
     rep = {}
     for f in ("x", "y", "dx", "dy", "area"):
         assert got[f].shape == want[f].shape, (f, got[f].shape, want[f].shape)
@@ -731,6 +752,12 @@ def _check_supergrid(got, want, name):
     d = np.minimum(d, np.abs(d - 360.0))
     rep["angle_dx_p999"] = float(np.quantile(d, 0.999))
     assert rep["angle_dx_p999"] < 1e-9, (name, rep)
+    # ... and EVERY point: equal on the lat-lon rows, within the conditioned bound at every regular point, and no more singular points in
+    # the reference mesh than the bipolar cap's three
+    lo, hi = _bipolar_rows(got)
+    ang = angle_bounds.check_angle(got["angle_dx"], want["x"], want["y"], want["angle_dx"], _row_tolerances(got, "x")[0],
+                                   _row_tolerances(got, "y")[0], angle_bounds.MAX_SINGULAR_WITH_CAP if hi > lo else 0, name)
+    rep["angle_dx_worst_d_over_bound"], rep["angle_dx_singular_points"] = ang["worst_ratio"], ang["n_singular"]
     record("supergrid_" + name, **rep)
 
 

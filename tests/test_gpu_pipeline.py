@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from oracle import ogg_oracle as orc
-from test_gpu_parity import _check_supergrid, FIELD_TOL  # noqa: F401
+import angle_bounds
+from test_gpu_parity import _check_supergrid, record, FIELD_TOL, TOL_COORD  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -541,7 +542,8 @@ def test_more_ranks_than_rows(sg):
 def _same_as_function_level(got, ref, name):
     """Bit identity of the pass path with the function-level path, field by field; angle_dx on the bipolar cap excepted: the
     function-level path applies the generic angle_x kernel to the stored mesh, the pass takes the cap's angle inside the mesh kernel
-    with cos(phi) in its algebraic form 2u/(1+u^2) -- < 1e-10 degrees apart away from the two pole points."""
+    with cos(phi) in its algebraic form 2u/(1+u^2) -- < 1e-10 degrees apart away from the two pole points, and at EVERY point of the cap
+    within the conditioned bound of tests/angle_bounds.py."""
     for f in FIELDS:
         assert got[f].shape == ref[f].shape, (name, f, got[f].shape, ref[f].shape)
         if f != "angle_dx":
@@ -553,6 +555,12 @@ def _same_as_function_level(got, ref, name):
         d = np.abs(got["angle_dx"][n - nbp:] - ref["angle_dx"][n - nbp:])
         d = np.minimum(d, np.abs(d - 360.0))
         assert np.quantile(d, 0.999) < 1e-10 and np.median(d) < 1e-12, (name, float(np.quantile(d, 0.999)), float(d.max()))
+        # ... and EVERY point of the cap: both paths hold the same x, y bits (asserted above), each within TOL_COORD of the exact mesh
+        # wherever it is well-conditioned, so their angles agree to the conditioned bound of that eps (tests/angle_bounds.py; stencil and
+        # classes from the function-level mesh); only the three points of the top row where the stencil vanishes are exempt
+        rep = angle_bounds.check_angle(got["angle_dx"][n - nbp:], ref["x"][n - nbp:], ref["y"][n - nbp:], ref["angle_dx"][n - nbp:],
+                                       TOL_COORD, TOL_COORD, angle_bounds.MAX_SINGULAR_WITH_CAP, "pass vs functions, " + name)
+        record("pass_vs_functions_" + name, angle_dx_worst_d_over_bound=rep["worst_ratio"], angle_dx_singular_points=rep["n_singular"])
 
 
 _GOLDEN_CONFIGS = sorted(json.load(open(os.path.join(GOLD, "ref_hashes.json")))["configs"])

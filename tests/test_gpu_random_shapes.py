@@ -151,14 +151,9 @@ def test_tripolar_pass_random_plans(hip, seed):
     _check_supergrid(ga, want, "random_plan_%d" % seed)
 
 
-@pytest.mark.parametrize("seed", range(40))
-def test_main_random_flags_pass_path_vs_function_level_and_oracle(hip, seed):
-    """main() with randomly drawn flag sets -- resolution, --ensure_nj_even, displaced pole by radius or by latitude (or none),
-    south cuts by row or by angle, --match_dy, --no_south_cap, --exfracdp, latitude overrides, --skip_metrics -- through the
-    device-resident pass against the function-level path (bitwise, bipolar angle_dx excepted) and against the oracle; flag sets
-    the reference's own guards reject must be rejected with the same text."""
-    import ocean_model_grid_generator_amd.ocean_grid_generator as ogg
-    from test_gpu_pipeline import _same_as_function_level, FIELDS
+def _random_flags(seed):
+    """The flag set of test_main_random_flags_pass_path_vs_function_level_and_oracle[seed] (also drawn, on the CPU, by the census of
+    tests/test_angle_bounds_cpu.py)."""
     rng = np.random.default_rng(7000 + seed)
     flags = dict(inverse_resolution=float(rng.choice([0.25, 0.5, 0.75, 1.0])), ensure_nj_even=bool(rng.integers(0, 2)))
     pole = int(rng.integers(0, 3))
@@ -199,6 +194,18 @@ def test_main_random_flags_pass_path_vs_function_level_and_oracle(hip, seed):
             flags.pop("south_cutoff_ang", None)
         elif extra == 5:
             flags["shift_equator_to_u_point"] = False
+    return flags
+
+
+@pytest.mark.parametrize("seed", range(40))
+def test_main_random_flags_pass_path_vs_function_level_and_oracle(hip, seed):
+    """main() with randomly drawn flag sets -- resolution, --ensure_nj_even, displaced pole by radius or by latitude (or none),
+    south cuts by row or by angle, --match_dy, --no_south_cap, --exfracdp, latitude overrides, --skip_metrics -- through the
+    device-resident pass against the function-level path (bitwise, bipolar angle_dx excepted) and against the oracle; flag sets
+    the reference's own guards reject must be rejected with the same text."""
+    import ocean_model_grid_generator_amd.ocean_grid_generator as ogg
+    from test_gpu_pipeline import _same_as_function_level, FIELDS
+    flags = _random_flags(seed)
     r = flags["inverse_resolution"]
     oflags = {k: v for k, v in flags.items() if k != "inverse_resolution"}
     try:
