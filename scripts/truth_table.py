@@ -39,12 +39,17 @@ Three groups ("next round" item 1):
 
     python scripts/truth_table.py --groups small             ->  tests/golden/truth_small_caps.npz   (truth_table.npz is left alone)
 
+  small_metrics     every dx, dy and area of the same four caps (orders 5 / 4; reduced row sets of the other coded orders), one fixture per cap:
+
+    python scripts/truth_table.py --groups small_metrics     ->  tests/golden/truth_small_caps_metrics*.npz   (two minutes on 8 processes)
+
 Stored per value: hi = fp64(truth), lo = fp64(truth - hi)  (so that v - truth = (v - hi) - lo to 1e-32 relative), and
 the oracle's distance from the truth as measured when the fixture was made (`*_eref`), which the tests use as the unit
 of their tolerances.  The `small` fixture holds every point of its caps, so it stores each value as ONE 64-bit integer k,
 truth = k * 2^-54 degrees (rounded to 5.6e-17 degrees; the test rebuilds exact hi / lo pairs from k): half the bytes.
 """
 import argparse
+import functools
 import os
 import sys
 import tempfile
@@ -123,33 +128,72 @@ def probes(node, exact):
     return M(node + EPS64), M(node - EPS64), M(node + 2.0 * EPS64), M(node - 2.0 * EPS64)
 
 
-def h_pair(cap, jn, inn, exact):
-    """numerical_hi, numerical_hj (order 4) at lattice node (jn, inn) (fp64 values).  OGG:535-562."""
+def h_pair(cap, jn, inn, exact, order=4, want=(True, True)):
+    """numerical_hi, numerical_hj (central differences of order 4, or 2) at lattice node (jn, inn) (fp64 values).  OGG:535-562.
+    `want`: which of the two to evaluate (the other is None)."""
     reps = 1 / M(EPS64)
     ip1, im1, ip2, im2 = probes(inn, exact)
     jp1, jm1, jp2, jm2 = probes(jn, exact)
     jm, im = M(jn), M(inn)
-    hi = (8 * cap.arc(ip1, jm, im1, jm) - cap.arc(ip2, jm, im2, jm)) * (M(1.0) / 12) * reps
-    hj = (8 * cap.arc(im, jp1, im, jm1) - cap.arc(im, jp2, im, jm2)) * (M(1.0) / 12) * reps
+    hi = hj = None
+    if order == 4:
+        if want[0]:
+            hi = (8 * cap.arc(ip1, jm, im1, jm) - cap.arc(ip2, jm, im2, jm)) * (M(1.0) / 12) * reps
+        if want[1]:
+            hj = (8 * cap.arc(im, jp1, im, jm1) - cap.arc(im, jp2, im, jm2)) * (M(1.0) / 12) * reps
+    elif order == 2:
+        if want[0]:
+            hi = M(0.5) * cap.arc(ip1, jm, im1, jm) * reps                                          # OGG:542
+        if want[1]:
+            hj = M(0.5) * cap.arc(im, jp1, im, jm1) * reps
+    else:
+        raise ValueError("finite-difference order %d has no truth here" % order)
     return hi, hj
 
 
+@functools.lru_cache(maxsize=None)
+def quad_weights(n):
+    """The Lobatto mean of order n as the oracle codes it (OGG:207-255): integer weights w and the integer D with mean = sum(w y) / D,
+    read off orc.quad_average itself; the 2-D mean is checked to be its tensor product."""
+    D = int(round(1.0 / orc._D1D[n]))
+    w = [int(round(float(orc.quad_average(np.eye(n)[k])) * D)) for k in range(n)]
+    assert sum(w) == D and all(abs(float(orc.quad_average(np.eye(n)[k])) * D - w[k]) < 1e-12 for k in range(n)), (n, w, D)
+    for a in range(n):
+        for b in range(n):
+            e = np.zeros((n, n))
+            e[a, b] = 1.0
+            assert abs(float(orc.quad_average_2d(e)) * D * D - w[a] * w[b]) < 1e-9, (n, a, b)
+    return w, D
+
+
+def lobatto_means(hi, hj, n, with_dx=True, with_dy=True, with_area=True):
+    """dx (the cell's bottom edge, OGG:217-220), dy (its left edge) and area (OGG:239-252) from the n x n node values hi[a][b], hj[a][b]
+    (a along j, b along i), in radians; None for what is not asked for."""
+    w, D = quad_weights(n)
+    d = M(1.0) / D
+    dx = d * sum(w[b] * hi[0][b] for b in range(n)) if with_dx else None
+    dy = d * sum(w[a] * hj[a][0] for a in range(n)) if with_dy else None
+    area = d * d * sum(w[a] * w[b] * hi[a][b] * hj[a][b] for a in range(n) for b in range(n)) if with_area else None
+    return dx, dy, area
+
+
 def dp_cell(args):
+    """One cell (j, i) of the displaced-pole quadrature from its n fp64 lattice nodes per direction (n = len(jn): 4, or 2; the central
+    differences have the same order, OGG:585-590): truths A and B of dx, dy, area.  The lattice row j = ny has a dx only (its first node
+    row), the lattice column i = nx a dy only: what is not defined comes back as None."""
     (nx, ny, lon0, lat0, lon_dp, r_dp), j, i, jn, inn = args
     cap = Cap(nx, ny, lon0, lat0, lon_dp, r_dp)
-    w = [1, 5, 5, 1]
+    n = len(jn)
+    na, nb = (n if j < ny else 1), (n if i < nx else 1)
     out = []
     for exact in (True, False):
-        hi = [[None] * 4 for _ in range(4)]
-        hj = [[None] * 4 for _ in range(4)]
-        for a in range(4):
-            for b in range(4):
-                hi[a][b], hj[a][b] = h_pair(cap, jn[a], inn[b], exact)
-        d = M(1.0) / 12
-        area = d * d * sum(w[a] * w[b] * hi[a][b] * hj[a][b] for a in range(4) for b in range(4))      # OGG:239-245
-        dx = d * (5 * (hi[0][1] + hi[0][2]) + (hi[0][0] + hi[0][3]))                                   # OGG:217-218
-        dy = d * (5 * (hj[1][0] + hj[2][0]) + (hj[0][0] + hj[3][0]))
-        out += [split(dx * RE), split(dy * RE), split(area * RE * RE)]
+        hi = [[None] * n for _ in range(n)]
+        hj = [[None] * n for _ in range(n)]
+        for a in range(na):
+            for b in range(nb):
+                hi[a][b], hj[a][b] = h_pair(cap, jn[a], inn[b], exact, order=n, want=(i < nx, j < ny))
+        dx, dy, area = lobatto_means(hi, hj, n, i < nx, j < ny, i < nx and j < ny)
+        out += [None if dx is None else split(dx * RE), None if dy is None else split(dy * RE), None if area is None else split(area * RE * RE)]
     return j, i, out
 
 
@@ -368,23 +412,22 @@ def bq_metrics(lamg, phig, lon_bp, rp):
 
 
 def bq_cell(args):
+    """One cell (j, i) of the bipolar quadrature from its n fp64 lattice nodes per direction (n = len(jn): 2 .. 5).  The top edge row j = ny
+    has a dx only (its first node row), the last column i = nx a dy only: what is not defined comes back as None."""
     (nx, ny, lat0, lon_bp, rp), j, i, jn, inn = args
     lat0m, lonm, rpm = M(lat0), M(lon_bp), M(rp)
-    hi = [[None] * 5 for _ in range(5)]
-    hj = [[None] * 5 for _ in range(5)]
-    for a in range(5):
+    n = len(jn)
+    hi = [[None] * n for _ in range(n)]
+    hj = [[None] * n for _ in range(n)]
+    for a in range(n if j < ny else 1):
         latg = lat0m + M(jn[a]) * (90 - lat0m) / ny                                    # OGG:127
-        for b in range(5):
+        for b in range(n if i < nx else 1):
             long = lonm + M(inn[b]) * 360 / nx                                         # OGG:126
             x, y = bq_metrics(long, latg, lonm, rpm)
             hi[a][b] = x * 2 * M(np.pi) / nx                                           # OGG:131-132
             hj[a][b] = y * (90 - lat0m) * PI180 / ny
-    w = [9, 49, 64, 49, 9]
-    d = M(1.0) / 180
-    area = d * d * sum(w[a] * w[b] * hi[a][b] * hj[a][b] for a in range(5) for b in range(5))
-    dx = d * (64 * hi[0][2] + 49 * (hi[0][1] + hi[0][3]) + 9 * (hi[0][0] + hi[0][4]))   # OGG:219-220
-    dy = d * (64 * hj[2][0] + 49 * (hj[1][0] + hj[3][0]) + 9 * (hj[0][0] + hj[4][0]))
-    return j, i, [split(dx * RE), split(dy * RE), split(area * RE * RE)]
+    dx, dy, area = lobatto_means(hi, hj, n, i < nx, j < ny, i < nx and j < ny)
+    return j, i, [None if dx is None else split(dx * RE), None if dy is None else split(dy * RE), None if area is None else split(area * RE * RE)]
 
 
 def bq_group(pool, quick):
@@ -751,6 +794,144 @@ def small_group(pool, quick):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# small_metrics: EVERY dx, dy and area of the four SMALL caps -- the bipolar quadrature of order 5 (OGG:125-188) with the top edge row of dx
+# and the last column of dy, the displaced-pole quadrature of order 4 (OGG:522-601, truths A and B) on the rows main() keeps -- plus reduced
+# row sets of the other coded orders (bipolar 2, 3, 4 on sbp180_: the bottom row, a mid-cap row, every row from the guard's first row - 1 up;
+# displaced pole 2 on sdp_rdp_: the first, a middle and the last kept row).  One fixture per cap, tests/golden/truth_small_caps_metrics*.npz
+# (names, classes and bounds: tests/quad_bounds.py; tests/test_quad_bounds_cpu.py, tests/test_gpu_small_caps_metrics_truth.py).
+#
+# Stored per set (prefix = the cap's tag, + "o<n>_" for a reduced set): `order`, `rows` (the cell rows held, as row indices of the cap's
+# arrays), `dx_rows` (= rows + the top edge row), and per field ONE int64 k per value, truth = k * 2^-bits with `<field>_bits` chosen so
+# that max |k| < 2^62; per field and class the oracle's distance from the truth as measured here, relative (`_eref_rel_<class>`) and in
+# metres (`_eref_abs_<class>`), and the class census.  Classes are those of bq_group (tests/quad_bounds.classes) from the element's own
+# (row, column) and `fold` = |truth| <= 1e-6 max |truth| from the truth alone; the displaced pole has one class per field and truth.  No
+# class was split further.  The oracle's error is flat over the rows of every class (the printed per-row maxima).  Along a row the one
+# structure inside a class is in dy next to the fold lines: 1.2e-13 one column away (`edge`), 3.7e-14 two and 2.5e-14 three columns away at
+# Ni = 360 (`regular`, whose other columns stay under 2e-14; at Ni = 180 the same columns are under the 2e-14 floor).  Widening `edge` by two
+# columns would take the regular bound of dy at Ni = 360 from 5.6e-14 to the floor's 3e-14: not worth a class rule of its own.
+# ---------------------------------------------------------------------------------------------------------------
+def metrics_cap_params(tag, kind, flags):
+    """(par, row0, oracle arrays (dx, dy, area) of the order main() uses) of a small cap, exactly as small_group forms its parameters."""
+    f = dict(flags)
+    r = f.pop("inverse_resolution")
+    w = orc.make_supergrid(r, skip_doughnut_rows=True, **f)
+    Ni, q = w["Ni"], w["Ni"] // 4
+    if kind == "bipolar":
+        ox = w["sub"]["BP"][0]
+        Nj, lat0, lon_bp = ox.shape[0] - 1, float(w["sub"]["Merc"][1][-1, q]), -300.0
+        rp = float(np.tan(0.5 * (90 - lat0) * orc.PI_180))
+        return (Ni, Nj, lat0, lon_bp, rp), 0, w["sub"]["BP"][2:5]
+    ox = w["sub"]["SC"][0]
+    ny = int(r * 40) * 7 // 4
+    row0, lat0 = ny + 1 - ox.shape[0], float(w["sub"]["SO"][1][0, q])
+    r_dp = f.get("r_dp", 0.0)
+    if f.get("lat_dp", -99.0) > -90:
+        r_dp = float(np.tan((90 + f["lat_dp"]) * orc.PI_180) / np.tan((90 + lat0) * orc.PI_180))   # OGG:1160 (main's fp64 value: an INPUT)
+    return (Ni, ny, -300.0, lat0, f.get("lon_dp", 80.0), r_dp, row0, ox.shape[0]), row0, w["sub"]["SC"][2:5]
+
+
+def metrics_oracle(kind, par, order):
+    """The oracle's whole arrays of the cap (the rows main() keeps)."""
+    if kind == "bipolar":
+        return orc.bipolar_cap_metrics_quad_fast(order, par[0], par[1], par[2], par[3], par[4])
+    row0 = par[6]
+    o = orc.displacedPoleCap_metrics_quad(order, par[0], par[1], par[2], par[3], par[4], par[5], j_first=row0)
+    return tuple(a[row0:] for a in o)
+
+
+def metrics_set(pool, qb, prefix, kind, par, order, rows, main_arrays=None):
+    """The truth of one (cap, order, cell rows) set and the oracle's distance from it: {fixture key: array}."""
+    Ni, ny = par[0], par[1]
+    row0 = 0 if kind == "bipolar" else par[6]
+    nrow = ny + 1 - row0
+    rows = sorted(rows)
+    dx_rows = rows + [nrow - 1]
+    jn = orc._lattice_1d(ny, order).reshape(ny + 1, order)
+    if kind == "bipolar":
+        jn[:, -1] = np.where(jn[:, -1] == ny, ny - 0.001, jn[:, -1])                      # OGG:146-147
+    i1d = orc._lattice_1d(Ni, order).reshape(Ni + 1, order)
+    cpar = tuple(par[:5]) if kind == "bipolar" else tuple(par[:6])
+    jobs = [(cpar, row0 + r, i, jn[row0 + r], i1d[i]) for r in rows for i in range(Ni + 1)] + [(cpar, ny, i, jn[ny], i1d[i]) for i in range(Ni)]
+    t0 = time.time()
+    res = pool.map(bq_cell if kind == "bipolar" else dp_cell, jobs, chunksize=8)
+    print("small_metrics %sorder %d: %d cells in %.0f s" % (prefix, order, len(jobs), time.time() - t0), flush=True)
+    Ts = ("",) if kind == "bipolar" else ("A", "B")
+    val = {(T, f): {} for T in Ts for f in qb.FIELDS}
+    for j, i, v in res:
+        for k, (T, f) in enumerate((T, f) for T in Ts for f in qb.FIELDS):
+            if v[k] is not None:
+                val[T, f][j - row0, i] = M(v[k][0]) + M(v[k][1])
+    shp = qb.shapes(kind, par)
+    out = {prefix + "order": np.array(order), prefix + "rows": np.array(rows), prefix + "dx_rows": np.array(dx_rows)}
+    oracle = metrics_oracle(kind, par, order)
+    if main_arrays is not None:                                                          # what main() stitches: the same bits, the same shapes
+        assert all(np.array_equal(a, b) for a, b in zip(oracle, main_arrays))
+    for k, f in enumerate(qb.FIELDS):
+        held = dx_rows if f == "dx" else rows
+        assert oracle[k].shape == shp[f], (f, oracle[k].shape, shp[f])
+        assert sorted(val[Ts[0], f]) == [(r, i) for r in held for i in range(shp[f][1])], (prefix, f)      # every element of the held rows, no other
+        big = max(abs(v) for T in Ts for v in val[T, f].values())
+        bits = 62 - int(mp.ceil(mp.log(big, 2)))
+        out[prefix + f + "_bits"] = np.array(bits)
+        cl = {nm: m[held] for nm, m in qb.classes(kind, shp[f], Ni, shp["area"][0]).items()}
+        for T in Ts:
+            kk = np.array([[int(mp.nint(val[T, f][r, i] * 2 ** bits)) for i in range(shp[f][1])] for r in held], dtype=np.int64)
+            out[prefix + (T + "_" if T else "") + f] = kk
+            t = qb.pairs(kk, bits)
+            e = qb.err(oracle[k][held], t)
+            fm = qb.fold(t[..., 0])
+            assert np.all(np.abs(oracle[k][held][fm]) < qb.FOLD_ABS) and e[fm].max(initial=0.0) < qb.FOLD_ABS
+            for nm, m in list(cl.items()) + [("fold", None)]:
+                m = fm if m is None else m & ~fm
+                if T == Ts[0]:
+                    out["%s%s_census_%s" % (prefix, f, nm)] = np.array(int(m.sum()))
+                if not m.any():
+                    continue
+                key = prefix + (T + "_" if T else "") + f
+                out[key + "_eref_abs_" + nm] = np.array(e[m].max())
+                if nm != "fold":
+                    rel = e / np.where(fm, 1.0, np.abs(t[..., 0]))
+                    out[key + "_eref_rel_" + nm] = np.array(rel[m].max())
+                    jw, iw = np.unravel_index(np.where(m, rel, -1.0).argmax(), rel.shape)
+                    print("small_metrics %s oracle vs truth %s: rel %.3e (row %d column %d; per-row maxima %s) abs %.3e, %d elements" % (
+                        key, nm, rel[m].max(), held[jw], iw, " ".join("%.1e" % np.where(m, rel, 0.0)[a].max() for a in range(len(held))), e[m].max(), m.sum()))
+                else:
+                    print("small_metrics %s oracle vs truth fold: abs %.3e m, %d elements" % (key, e[m].max(), m.sum()))
+    return out
+
+
+def small_metrics_group(pool, quick):
+    """{fixture file name: {key: array}}, one file per cap."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import quad_bounds as qb                                                             # the class masks and the integer <-> hi / lo pairs
+    files = {}
+    for tag, kind, flags in SMALL_CAPS:
+        reduced = qb.REDUCED_ORDERS.get(tag, ())
+        if quick and not reduced:
+            continue
+        par, row0, main_arrays = metrics_cap_params(tag, kind, flags)
+        assert kind == qb.KIND[tag]
+        out = {"dps": np.array(mp.mp.dps), tag + "params": np.array(par, dtype=np.float64)}
+        n_cell = par[1] - row0
+        if kind == "bipolar":
+            jg = qb.guard_row(par[1], par[2])
+            assert 0 < jg - 1 and jg < n_cell
+            some = [0, n_cell // 2] + list(range(jg - 1, n_cell))
+            out[tag + "guard_row"] = np.array(jg)
+        else:
+            some = [0, n_cell // 2, n_cell - 1]
+        if quick:                                                                        # a thin sample: two rows at the order main() uses, one at a reduced one
+            out.update(metrics_set(pool, qb, tag, kind, par, qb.MAIN_ORDER[kind], [0] if kind == "dpole" else [0, n_cell - 1]))
+            out.update(metrics_set(pool, qb, "%so%d_" % (tag, reduced[0]), kind, par, reduced[0], some[-1:]))
+        else:
+            out.update(metrics_set(pool, qb, tag, kind, par, qb.MAIN_ORDER[kind], range(n_cell), main_arrays))
+            for n in reduced:
+                out.update(metrics_set(pool, qb, "%so%d_" % (tag, n), kind, par, n, some))
+        files[qb.FILES[tag]] = out
+    return files
+
+
 GROUPS = {"md": md_group, "bq": bq_group, "bp": bp_group, "dp": dp_group, "dp4": lambda pool, quick: dp_group(pool, quick, "dp4"),
           "ax": ax_group, "dm": dm_group, "bq16": bq16_group, "mdso": mdso_group}
 
@@ -761,6 +942,7 @@ def main():
     ap.add_argument("--procs", type=int, default=8)
     ap.add_argument("--quick", action="store_true", help="a thin sample (smoke run of this script; does not overwrite the fixture)")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "truth_table.npz"))
+    ap.add_argument("--metrics-dir", default=None, help="where `small_metrics` writes its files (default: tests/golden, or the temp directory with --quick)")
     a = ap.parse_args()
     if "small" in a.groups:                                                    # its own fixture; truth_table.npz is not rewritten
         with Pool(a.procs) as pool:
@@ -769,6 +951,17 @@ def main():
         save_npz_reproducibly(path, small)
         print("wrote", path, os.path.getsize(path), "bytes")
         a.groups = [g for g in a.groups if g != "small"]
+        if not a.groups:
+            return
+    if "small_metrics" in a.groups:                                            # one fixture per cap; truth_table.npz is not rewritten
+        with Pool(a.procs) as pool:
+            files = small_metrics_group(pool, a.quick)
+        where = a.metrics_dir or (os.path.dirname(SMALL_OUT) if not a.quick else tempfile.gettempdir())
+        for name, arrays in sorted(files.items()):
+            path = os.path.join(where, name if not a.quick else name.replace(".npz", "_quick.npz"))
+            save_npz_reproducibly(path, arrays)
+            print("wrote", path, os.path.getsize(path), "bytes")
+        a.groups = [g for g in a.groups if g != "small_metrics"]
         if not a.groups:
             return
     out = {"dps": np.array(mp.mp.dps)}
