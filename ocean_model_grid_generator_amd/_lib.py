@@ -494,6 +494,21 @@ def call(name, *args):
     check(getattr(load(), name)(*args))
 
 
+def checked(name, p, *args):
+    """p after the library's ogg_*_check ``name`` took it; the reason of a refusal as a ValueError (no device is needed)"""
+    lib = load()
+    if getattr(lib, name)(ctypes.byref(p), *args) != OGG_OK:
+        raise ValueError(lib.ogg_last_error().decode())
+    return p
+
+
+def counts_dict(fields, c):
+    """{field: int} of a counts struct, or of the counts in the fields' order (a numpy array or a device tensor)"""
+    if isinstance(c, ctypes.Structure):
+        return {f: int(getattr(c, f)) for f in fields}
+    return {f: int(v) for f, v in zip(fields, c.cpu().numpy() if hasattr(c, "cpu") else c)}
+
+
 def ptr(a):
     """Host pointer of a C-contiguous float64/int64 numpy array (or None)."""
     if a is None:

@@ -103,9 +103,7 @@ def params(ny, nx, rules, periodic=False, fold=False, seed_max_distance=None, Re
     from . import ocean_mask as M
     p = L.BasinParams(ny=int(ny), nx=int(nx), topology=M.topology_flags(periodic, fold), n_rules=len(rules),
                       seed_max_d2=seed_max_d2(seed_max_distance, Re))
-    if L.load().ogg_basin_check(ctypes.byref(p), rules.table.ctypes.data) != L.OGG_OK:
-        raise ValueError(L.load().ogg_last_error().decode())
-    return p
+    return L.checked("ogg_basin_check", p, rules.table.ctypes.data)
 
 
 def plan(rules):
@@ -119,19 +117,6 @@ def plan(rules):
 
 
 # ---- the result ------------------------------------------------------------------------------------------------
-def _wet(wet, shape):
-    if wet is None:
-        raise ValueError("basin codes: a wet mask is needed (depth > 0 of a topography or mask != 0 of an ocean mask)")
-    return F.cell_mask(wet, shape, "basin codes: the wet mask")
-
-
-def _topology(periodic, fold, detect):
-    if periodic is None or fold is None:
-        p, f = detect()
-        periodic, fold = (p if periodic is None else periodic), (f if fold is None else fold)
-    return bool(periodic), bool(fold)
-
-
 def uncoded_bodies(plane, periodic, fold):
     """the connected bodies of a plane (1.0: wet and uncoded) by the ocean mask's label step on the current device: (number of
     bodies, [(cells, root)] of the N_LISTED largest)"""
@@ -148,7 +133,7 @@ def uncoded_bodies(plane, periodic, fold):
     counts = torch.zeros(len(L.MASK_COUNT_FIELDS), dtype=torch.int64, device=dev)
     L.call("ogg_mask_label_dev", ctypes.byref(p), d.data_ptr(), ws.data_ptr(), wsb, root.data_ptr(), comps.data_ptr(), counts.data_ptr(),
            torch.cuda.current_stream(dev).cuda_stream)
-    n = int(counts.cpu().numpy()[L.MASK_COUNT_FIELDS.index("components")])
+    n = L.counts_dict(L.MASK_COUNT_FIELDS, counts)["components"]
     top = np.sort(comps[:n].cpu().numpy())[::-1][:N_LISTED]
     return n, [(int(c >> 32), int(np.iinfo(np.int32).max - (c & 0xFFFFFFFF))) for c in top]
 
@@ -195,9 +180,9 @@ def basin_codes(x, y, wet, rules, periodic=None, fold=None, seed_max_distance=No
     nyp, nxp = x.shape
     X.check_grid(nyp, nxp)
     shape = ((nyp - 1) // 2, (nxp - 1) // 2)
-    m = _wet(wet, shape)
+    m = F.wet_mask(wet, shape, "basin codes")
     p = params(shape[0], shape[1], rules, False, False, seed_max_distance, Re)   # the rules' refusals come before the grid's
-    periodic, fold = _topology(periodic, fold, lambda: M.detect_topology(x, y, 2))
+    periodic, fold = F.resolve_topology(periodic, fold, lambda: M.detect_topology(x, y, 2))
     p = params(shape[0], shape[1], rules, periodic, fold, seed_max_distance, Re)
     code = np.empty(shape, np.uint8)
     rule = np.empty(shape, np.int16)
@@ -205,7 +190,7 @@ def basin_codes(x, y, wet, rules, periodic=None, fold=None, seed_max_distance=No
     c = L.BasinCounts()
     L.call("ogg_basin_codes", ctypes.byref(p), rules.table.ctypes.data, x.ctypes.data, y.ctypes.data, m.ctypes.data, code.ctypes.data,
            rule.ctypes.data, rec.ctypes.data, ctypes.byref(c))
-    counts = {f: int(getattr(c, f)) for f in L.BASIN_COUNT_FIELDS}
+    counts = L.counts_dict(L.BASIN_COUNT_FIELDS, c)
     return result(code, rule, rec, counts, m, rules, x, y, periodic, fold, seed_max_distance, Re, area)
 
 
@@ -221,9 +206,9 @@ def basin_codes_dev(x, y, wet, rules, periodic=None, fold=None, seed_max_distanc
     nyp, nxp = x.shape
     X.check_grid(nyp, nxp)
     shape = ((nyp - 1) // 2, (nxp - 1) // 2)
-    m = _wet(wet.cpu().numpy() if hasattr(wet, "cpu") else wet, shape)
+    m = F.wet_mask(wet.cpu().numpy() if hasattr(wet, "cpu") else wet, shape, "basin codes")
     p = params(shape[0], shape[1], rules, False, False, seed_max_distance, Re)
-    periodic, fold = _topology(periodic, fold, lambda: M.topology_of_device_grid(x, y))
+    periodic, fold = F.resolve_topology(periodic, fold, lambda: M.topology_of_device_grid(x, y))
     p = params(shape[0], shape[1], rules, periodic, fold, seed_max_distance, Re)
     st = torch.cuda.current_stream(dev).cuda_stream
     wsb = int(L.load().ogg_basin_workspace_bytes(ctypes.byref(p)))
@@ -236,7 +221,7 @@ def basin_codes_dev(x, y, wet, rules, periodic=None, fold=None, seed_max_distanc
     counts = torch.zeros(len(L.BASIN_COUNT_FIELDS), dtype=torch.int64, device=dev)
     L.call("ogg_basin_codes_dev", ctypes.byref(p), rules.table.ctypes.data, rt.data_ptr(), x.data_ptr(), y.data_ptr(), nxp, wt.data_ptr(),
            ws.data_ptr(), wsb, code.data_ptr(), rule.data_ptr(), rec.data_ptr(), counts.data_ptr(), st)
-    cd = {k: int(v) for k, v in zip(L.BASIN_COUNT_FIELDS, counts.cpu().numpy())}
+    cd = L.counts_dict(L.BASIN_COUNT_FIELDS, counts)
     records = rec.cpu().numpy().view(L.BASIN_RECORD).copy()
     if area is not None and hasattr(area, "cpu"):
         area = area.cpu().numpy()

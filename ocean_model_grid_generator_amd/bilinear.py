@@ -61,9 +61,7 @@ def params(ny, nx, source, points="h", ncomp=1, m0=0, periodic=False, fold=False
 
 def check(p, has_mask=False):
     """ogg_bilinear_check: the reason of a refusal as a ValueError (no device is needed)"""
-    lib = L.load()
-    if lib.ogg_bilinear_check(ctypes.byref(p), 1 if has_mask else 0) != L.OGG_OK:
-        raise ValueError(lib.ogg_last_error().decode())
+    L.checked("ogg_bilinear_check", p, 1 if has_mask else 0)
 
 
 def _pair(source, source2):

@@ -34,23 +34,11 @@ def params(ny, nx, sides="both", periodic=False, fold=False):
     from . import ocean_mask as M
     if sides not in SIDES:
         raise ValueError("coast distance: sides must be one of %s, not %r" % (", ".join(sorted(SIDES)), sides))
-    p = L.CoastParams(ny=int(ny), nx=int(nx), topology=M.topology_flags(periodic, fold), sides=SIDES[sides])
-    if L.load().ogg_coast_check(ctypes.byref(p)) != L.OGG_OK:
-        raise ValueError(L.load().ogg_last_error().decode())
-    return p
+    return L.checked("ogg_coast_check", L.CoastParams(ny=int(ny), nx=int(nx), topology=M.topology_flags(periodic, fold), sides=SIDES[sides]))
 
 
 def _wet(wet, shape):
-    if wet is None:
-        raise ValueError("coast distance: a wet mask is needed (depth > 0 of a topography or mask != 0 of an ocean mask)")
-    return F.cell_mask(wet, shape, "coast distance: the wet mask")
-
-
-def _topology(periodic, fold, detect):
-    if periodic is None or fold is None:
-        p, f = detect()
-        periodic, fold = (p if periodic is None else periodic), (f if fold is None else fold)
-    return bool(periodic), bool(fold)
+    return F.wet_mask(wet, shape, "coast distance")
 
 
 def distance_of(d2, nearest, Re=X.DEFAULT_RE):
@@ -96,7 +84,7 @@ def coast_distance(x, y, wet, sides="both", periodic=None, fold=None, Re=X.DEFAU
     X.check_grid(nyp, nxp)
     shape = ((nyp - 1) // 2, (nxp - 1) // 2)
     m = _wet(wet, shape)
-    periodic, fold = _topology(periodic, fold, lambda: M.detect_topology(x, y, 2))
+    periodic, fold = F.resolve_topology(periodic, fold, lambda: M.detect_topology(x, y, 2))
     p = params(shape[0], shape[1], sides, periodic, fold)
     nearest = np.empty(shape, np.int32)
     d2 = np.empty(shape, np.float64)
@@ -104,7 +92,7 @@ def coast_distance(x, y, wet, sides="both", periodic=None, fold=None, Re=X.DEFAU
     c = L.CoastCounts()
     L.call("ogg_coast_distance", ctypes.byref(p), x.ctypes.data, y.ctypes.data, m.ctypes.data, nearest.ctypes.data, d2.ctypes.data,
            flags.ctypes.data, ctypes.byref(c))
-    counts = {f: int(getattr(c, f)) for f in L.COAST_COUNT_FIELDS}
+    counts = L.counts_dict(L.COAST_COUNT_FIELDS, c)
     return result(nearest, d2, flags, counts, x, y, sides, periodic, fold, Re)
 
 
@@ -122,7 +110,7 @@ def coast_distance_dev(x, y, wet, sides="both", periodic=None, fold=None, Re=X.D
     X.check_grid(nyp, nxp)
     shape = ((nyp - 1) // 2, (nxp - 1) // 2)
     m = _wet(wet.cpu().numpy() if hasattr(wet, "cpu") else wet, shape)
-    periodic, fold = _topology(periodic, fold, lambda: M.topology_of_device_grid(x, y))
+    periodic, fold = F.resolve_topology(periodic, fold, lambda: M.topology_of_device_grid(x, y))
     p = params(shape[0], shape[1], sides, periodic, fold)
     st = torch.cuda.current_stream(dev).cuda_stream
     wsb = int(L.load().ogg_coast_workspace_bytes(ctypes.byref(p)))
@@ -142,7 +130,7 @@ def coast_distance_dev(x, y, wet, sides="both", periodic=None, fold=None, Re=X.D
     nw, nl = int(c[0]), int(c[1])
     L.call("ogg_coast_search_dev", ctypes.byref(p), flags.data_ptr(), u.data_ptr(), lc.data_ptr(), lu.data_ptr(), nl, wc.data_ptr(),
            wu.data_ptr(), nw, ws.data_ptr(), wsb, nearest.data_ptr(), d2.data_ptr(), counts.data_ptr(), st)
-    cd = {k: int(v) for k, v in zip(L.COAST_COUNT_FIELDS, counts.cpu().numpy())}
+    cd = L.counts_dict(L.COAST_COUNT_FIELDS, counts)
     lists = None
     if keep_lists:
         lists = {"u": u.cpu().numpy(), "land_cell": lc[:nl].cpu().numpy(), "land_u": lu[:nl].cpu().numpy(),

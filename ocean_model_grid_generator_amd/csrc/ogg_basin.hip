@@ -22,7 +22,6 @@
 #include <climits>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "ogg_blocks.h"
@@ -37,7 +36,6 @@ namespace {
 using ogg::at;
 using ogg::grid_for;
 using ogg::knob;
-using ogg::round256;
 
 constexpr int PASS_MAX = OGG_BASIN_MAX_PASS_RULES;
 constexpr long SEED_BLOCKS = 1024; // workgroups of the seed search, over cells and groups of 64 rules
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(NT) void basin_unit_kernel(long ny, long nx, const 
     const long n = ny * nx;
     long long v[1] = {0};
     for (long c = (long)blockIdx.x * NT + threadIdx.x; c < n; c += (long)gridDim.x * NT) {
-        const long j = c / nx, i = c % nx, k = (2 * j + 1) * ld + 2 * i + 1;
+        const long k = centre_point(c, nx, ld);
         const double lon = x[k], lat = y[k];
         double t[3] = {NAN, NAN, NAN};
         if (isfinite(lon) && isfinite(lat)) unit(lon, lat, t);
@@ -94,8 +92,7 @@ __global__ __launch_bounds__(NT) void basin_seed_kernel(long n, const double* __
     const int s = blockIdx.y * 64 + lane;
     double su[3] = {0.0, 0.0, 0.0};
     if (s < K) unit(rules[s].seed_lon, rules[s].seed_lat, su);
-    unsigned long long best = ULLONG_MAX;
-    int bc = INT_MAX;
+    Nearest best{ULLONG_MAX, INT_MAX};
     for (long base = (long)blockIdx.x * NT; base < n; base += (long)gridDim.x * NT) {
         __syncthreads();   // the chunk before this one has been read
         const long c = base + threadIdx.x;
@@ -107,19 +104,16 @@ __global__ __launch_bounds__(NT) void basin_seed_kernel(long n, const double* __
             const int q = w * 64 + k;
             const double ax = cu[0][q];
             if (ax != ax) continue;   // an invalid centre (or past the end) is no candidate; the same for every lane
-            const unsigned long long b = bits_of(dist2(ax, cu[1][q], cu[2][q], su[0], su[1], su[2]));
-            const int cc = (int)(base + q);
-            if (b < best || (b == best && cc < bc)) best = b, bc = cc;
+            best.offer(bits_of(dist2(ax, cu[1][q], cu[2][q], su[0], su[1], su[2])), (int)(base + q));
         }
     }
-    wb[w][lane] = best;
-    wc[w][lane] = bc;
+    wb[w][lane] = best.bits;
+    wc[w][lane] = best.cell;
     __syncthreads();
     if (w == 0 && s < K) {
-        for (int v = 1; v < NT / 64; ++v)
-            if (wb[v][lane] < best || (wb[v][lane] == best && wc[v][lane] < bc)) best = wb[v][lane], bc = wc[v][lane];
-        part[((long)blockIdx.x * K + s) * 2] = best;
-        part[((long)blockIdx.x * K + s) * 2 + 1] = (unsigned long long)(unsigned)bc;
+        for (int v = 1; v < NT / 64; ++v) best.offer(wb[v][lane], wc[v][lane]);
+        part[((long)blockIdx.x * K + s) * 2] = best.bits;
+        part[((long)blockIdx.x * K + s) * 2 + 1] = (unsigned long long)(unsigned)best.cell;
     }
 }
 
@@ -127,16 +121,10 @@ __global__ __launch_bounds__(NT) void basin_seed_reduce_kernel(int K, int nparts
                                                                ogg_basin_rule_record* __restrict__ rec) {
     const int s = blockIdx.x * NT + threadIdx.x;
     if (s >= K) return;
-    unsigned long long best = ULLONG_MAX;
-    int bc = INT_MAX;
-    for (int b = 0; b < nparts; ++b) {
-        const unsigned long long v = part[((long)b * K + s) * 2];
-        const int cc = (int)(unsigned)part[((long)b * K + s) * 2 + 1];
-        if (v < best || (v == best && cc < bc)) best = v, bc = cc;
-    }
-    const bool found = bc != INT_MAX;
-    rec[s].seed_cell = found ? bc : -1;
-    rec[s].d2_bits = found ? (long long)best : (long long)bits_of(INFINITY);
+    Nearest best{ULLONG_MAX, INT_MAX};
+    for (int b = 0; b < nparts; ++b) best.offer(part[((long)b * K + s) * 2], (int)(unsigned)part[((long)b * K + s) * 2 + 1]);
+    rec[s].seed_cell = best.found() ? best.cell : -1;
+    rec[s].d2_bits = best.found() ? (long long)best.bits : (long long)bits_of(INFINITY);
     rec[s].status = OGG_BASIN_TOOK;
     rec[s].blocking_rule = -1;
     rec[s].cells = 0;
@@ -167,7 +155,7 @@ __global__ __launch_bounds__(NT) void basin_tile_kernel(Grid g, Pass ps, const o
         if (j < g.ny && i < g.nx) {
             const long c = j * g.nx + i;
             if (wet[c] != 0 && code[c] == 0) {
-                const long q = (2 * j + 1) * ld + 2 * i + 1;
+                const long q = centre_ji(j, i, ld);
                 const double lon = x[q], lat = y[q];
                 if (isfinite(lon) && isfinite(lat))
                     for (int r = 0; r < ps.nr; ++r)
@@ -204,10 +192,8 @@ __global__ __launch_bounds__(NT) void basin_seedroot_kernel(long nx, Pass ps, do
     if (sc < 0) {
         status = OGG_BASIN_SEED_INVALID;
     } else {
-        double d2;
-        const long long b = rec[k].d2_bits;
-        memcpy(&d2, &b, 8);
-        const long j = sc / nx, i = sc % nx, q = (2 * j + 1) * ld + 2 * i + 1;
+        const double d2 = __longlong_as_double(rec[k].d2_bits);
+        const long q = centre_point(sc, nx, ld);
         const ogg_basin_rule w = rules[k];
         if (d2 > seed_max_d2)
             status = OGG_BASIN_SEED_OFF_GRID;
@@ -330,13 +316,14 @@ Layout layout(const ogg_basin_params& p) {
     const long n = p.ny * p.nx;
     l.seed_by = (unsigned)((p.n_rules + 63) / 64);
     l.seed_bx = (unsigned)std::max<long>(1, std::min<long>((n + NT - 1) / NT, SEED_BLOCKS / l.seed_by));
-    l.u = 0;
-    l.par = l.u + round256(n * 24);
-    l.root = l.par + round256(n * 4);
-    l.cls = l.root + round256(n * 4);
-    l.keep = l.cls + round256(n);
-    l.part = l.keep + round256(NT * 4);
-    l.total = l.part + round256((long)l.seed_bx * p.n_rules * 16);
+    ogg::Sections s{0};
+    l.u = s.take(n * 24);
+    l.par = s.take(n * 4);
+    l.root = s.take(n * 4);
+    l.cls = s.take(n);
+    l.keep = s.take(NT * 4);
+    l.part = s.take((long)l.seed_bx * p.n_rules * 16);
+    l.total = s.off;
     return l;
 }
 
@@ -376,8 +363,7 @@ extern "C" int ogg_basin_codes_dev(const ogg_basin_params* p, const ogg_basin_ru
                 "ogg_basin_codes: null rules_dev / x / y / wet / code / rule / records / counts");
     OGG_REQUIRE(ld >= 2 * p->nx + 1, OGG_EARG, "ogg_basin_codes: point rows of %ld, %ld needed", ld, 2 * p->nx + 1);
     const Layout l = layout(*p);
-    OGG_REQUIRE(workspace && workspace_bytes >= l.total, OGG_EARG, "ogg_basin_codes: workspace of %ld bytes, %ld needed", workspace_bytes,
-                l.total);
+    if (int e = ogg::check_workspace("ogg_basin_codes", workspace, workspace_bytes, l.total)) return e;
     int th = 0, batch = 1;
     if (int e = read_knobs(&th, &batch)) return e;
     std::vector<int> start;
@@ -423,24 +409,26 @@ extern "C" int ogg_basin_codes(const ogg_basin_params* p, const ogg_basin_rule* 
     ogg::Buffers bufs;   // freed on every exit path
     const size_t nc = (size_t)(p->ny * p->nx), npt = (size_t)(2 * p->ny + 1) * (2 * p->nx + 1), K = (size_t)p->n_rules;
     const long wsb = layout(*p).total;
-    void *dx, *dy, *dw, *dr, *ws, *dc, *du, *dk, *ct;
-    if (int e = bufs.put(&dx, x, npt * 8)) return e;
-    if (int e = bufs.put(&dy, y, npt * 8)) return e;
+    double *dx, *dy;
+    unsigned char *dw, *dc;
+    ogg_basin_rule* dr;
+    char* ws;
+    short* du;
+    ogg_basin_rule_record* dk;
+    ogg_basin_counts* ct;
+    if (int e = bufs.put(&dx, x, npt)) return e;
+    if (int e = bufs.put(&dy, y, npt)) return e;
     if (int e = bufs.put(&dw, wet, nc)) return e;
-    if (int e = bufs.put(&dr, rules, K * sizeof(ogg_basin_rule))) return e;
+    if (int e = bufs.put(&dr, rules, K)) return e;
     if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
     if (int e = bufs.alloc(&dc, nc)) return e;
-    if (int e = bufs.alloc(&du, nc * 2)) return e;
-    if (int e = bufs.alloc(&dk, K * sizeof(ogg_basin_rule_record))) return e;
-    if (int e = bufs.alloc(&ct, sizeof(ogg_basin_counts))) return e;
-    if (int e = ogg_basin_codes_dev(p, rules, static_cast<ogg_basin_rule*>(dr), static_cast<double*>(dx), static_cast<double*>(dy),
-                                    2 * p->nx + 1, static_cast<unsigned char*>(dw), ws, wsb, static_cast<unsigned char*>(dc),
-                                    static_cast<short*>(du), static_cast<ogg_basin_rule_record*>(dk),
-                                    static_cast<ogg_basin_counts*>(ct), nullptr))
-        return e;
-    OGG_HIP_CHECK(hipMemcpy(code, dc, nc, hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(rule, du, nc * 2, hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(records, dk, K * sizeof(ogg_basin_rule_record), hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_basin_counts), hipMemcpyDeviceToHost));
+    if (int e = bufs.alloc(&du, nc)) return e;
+    if (int e = bufs.alloc(&dk, K)) return e;
+    if (int e = bufs.alloc(&ct, 1)) return e;
+    if (int e = ogg_basin_codes_dev(p, rules, dr, dx, dy, 2 * p->nx + 1, dw, ws, wsb, dc, du, dk, ct, nullptr)) return e;
+    if (int e = bufs.get(code, dc, nc)) return e;
+    if (int e = bufs.get(rule, du, nc)) return e;
+    if (int e = bufs.get(records, dk, K)) return e;
+    if (int e = bufs.get(counts, ct, 1)) return e;
     return OGG_OK;
 }

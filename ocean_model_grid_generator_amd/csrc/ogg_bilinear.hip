@@ -350,74 +350,71 @@ extern "C" int ogg_bilinear(const ogg_bilinear_params* p, const double* x, const
     OGG_REQUIRE(!rot || (rot_cos && rot_sin && (!c || (rot_cos2 && rot_sin2))), OGG_EARG, "ogg_bilinear: null rot_cos / rot_sin");
     ogg::Buffers bufs;   // freed on every exit path
     const long ld = 2 * p->nx + 1;
-    const size_t gbytes = (size_t)(2 * p->ny + 1) * ld * 8;
+    const size_t npt = (size_t)(2 * p->ny + 1) * ld;
     const size_t fbytes = (size_t)p->nrec * p->NA * p->NB * (p->dtype == OGG_REMAP_FLOAT32 ? 4 : 8);
     const Pts p1 = points_of(*p, c ? OGG_BILINEAR_U : p->points), p2 = points_of(*p, c ? OGG_BILINEAR_V : p->points);
     const size_t n1 = (size_t)p1.R * p1.C, n2 = (size_t)p2.R * p2.C, m1 = n1 * p->nrec, m2 = n2 * p->nrec;
-    void *dx = nullptr, *dy = nullptr, *da = nullptr, *dlon = nullptr, *dlat = nullptr, *df = nullptr, *df2 = nullptr, *dm = nullptr;
-    void *dv = nullptr, *dfl = nullptr, *dv2 = nullptr, *dfl2 = nullptr, *dc = nullptr, *dc2 = nullptr, *rc = nullptr, *rs = nullptr,
-         *rc2 = nullptr, *rs2 = nullptr;
-    if (int e = bufs.put(&dx, x, gbytes)) return e;
-    if (int e = bufs.put(&dy, y, gbytes)) return e;
-    if (int e = bufs.put(&dlon, lon, (size_t)(p->NA + 1) * 8)) return e;
-    if (int e = bufs.put(&dlat, lat, (size_t)(p->NB + 1) * 8)) return e;
-    if (int e = bufs.put(&df, f, fbytes)) return e;
+    double *dx, *dy, *da = nullptr, *dlon, *dlat, *dv, *dv2 = nullptr, *dc = nullptr, *dc2 = nullptr;
+    double *rc = nullptr, *rs = nullptr, *rc2 = nullptr, *rs2 = nullptr;
+    char *df, *df2 = nullptr;
+    unsigned char *dm = nullptr, *dfl, *dfl2 = nullptr;
+    if (int e = bufs.put(&dx, x, npt)) return e;
+    if (int e = bufs.put(&dy, y, npt)) return e;
+    if (int e = bufs.put(&dlon, lon, (size_t)p->NA + 1)) return e;
+    if (int e = bufs.put(&dlat, lat, (size_t)p->NB + 1)) return e;
+    if (int e = bufs.put(&df, static_cast<const char*>(f), fbytes)) return e;
     if (vec)
-        if (int e = bufs.put(&df2, f2, fbytes)) return e;
+        if (int e = bufs.put(&df2, static_cast<const char*>(f2), fbytes)) return e;
     if (mask)
         if (int e = bufs.put(&dm, mask, (size_t)p->ny * p->nx)) return e;
-    if (int e = bufs.alloc(&dv, m1 * 8)) return e;
+    if (int e = bufs.alloc(&dv, m1)) return e;
     if (int e = bufs.alloc(&dfl, (m1 + 3) / 4 * 4)) return e;
     if (vec) {
-        if (int e = bufs.alloc(&dv2, m2 * 8)) return e;
+        if (int e = bufs.alloc(&dv2, m2)) return e;
         if (int e = bufs.alloc(&dfl2, (m2 + 3) / 4 * 4)) return e;
     }
     if (rot) {
-        if (int e = bufs.put(&da, angle, gbytes)) return e;
-        if (int e = bufs.alloc(&rc, n1 * 8)) return e;
-        if (int e = bufs.alloc(&rs, n1 * 8)) return e;
+        if (int e = bufs.put(&da, angle, npt)) return e;
+        if (int e = bufs.alloc(&rc, n1)) return e;
+        if (int e = bufs.alloc(&rs, n1)) return e;
         if (c) {
-            if (int e = bufs.alloc(&rc2, n2 * 8)) return e;
-            if (int e = bufs.alloc(&rs2, n2 * 8)) return e;
+            if (int e = bufs.alloc(&rc2, n2)) return e;
+            if (int e = bufs.alloc(&rs2, n2)) return e;
             if (rotate) {
-                if (int e = bufs.alloc(&dc, m1 * 8)) return e;
-                if (int e = bufs.alloc(&dc2, m2 * 8)) return e;
+                if (int e = bufs.alloc(&dc, m1)) return e;
+                if (int e = bufs.alloc(&dc2, m2)) return e;
             }
         }
     }
-    auto D = [](void* q) { return static_cast<double*>(q); };
-    auto B = [](void* q) { return static_cast<unsigned char*>(q); };
-    if (int e = ogg_bilinear_dev(p, D(dx), D(dy), ld, D(dlon), D(dlat), df, df2, B(dm), D(dv), B(dfl), D(dv2), B(dfl2), D(dc), D(dc2), nullptr))
-        return e;
+    if (int e = ogg_bilinear_dev(p, dx, dy, ld, dlon, dlat, df, df2, dm, dv, dfl, dv2, dfl2, dc, dc2, nullptr)) return e;
     if (do_fill) {
         const ogg_remap_params q = fill_params(*p);
         const long wsb = ogg_remap_workspace_bytes(&q);
         OGG_REQUIRE(wsb >= 0, OGG_EARG, "ogg_bilinear: the fill does not take these sizes: %s", ogg_last_error());
-        void *ws = nullptr, *ct = nullptr;
+        char* ws;
+        ogg_remap_counts* ct;
         if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
-        if (int e = bufs.alloc(&ct, sizeof(ogg_remap_counts))) return e;
+        if (int e = bufs.alloc(&ct, 1)) return e;
         OGG_HIP_CHECK(hipMemset(ct, 0, sizeof(ogg_remap_counts)));
-        if (int e = ogg_remap_fill_dev(&q, ws, wsb, D(dv), B(dfl), static_cast<ogg_remap_counts*>(ct), nullptr)) return e;
+        if (int e = ogg_remap_fill_dev(&q, ws, wsb, dv, dfl, ct, nullptr)) return e;
         if (vec)
-            if (int e = ogg_remap_fill_dev(&q, ws, wsb, D(dv2), B(dfl2), static_cast<ogg_remap_counts*>(ct), nullptr)) return e;
+            if (int e = ogg_remap_fill_dev(&q, ws, wsb, dv2, dfl2, ct, nullptr)) return e;
     }
     if (rot)
-        if (int e = ogg_bilinear_rotate_dev(p, D(da), ld, D(dv), B(dfl), D(dv2), B(dfl2), D(dc), D(dc2), D(rc), D(rs), D(rc2), D(rs2),
-                                            rotate ? 1 : 0, nullptr))
-            return e;
+        if (int e = ogg_bilinear_rotate_dev(p, da, ld, dv, dfl, dv2, dfl2, dc, dc2, rc, rs, rc2, rs2, rotate ? 1 : 0, nullptr)) return e;
     OGG_HIP_CHECK(hipDeviceSynchronize());
-    OGG_HIP_CHECK(hipMemcpy(values, dv, m1 * 8, hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(flags, dfl, m1, hipMemcpyDeviceToHost));
+    if (int e = bufs.get(values, dv, m1)) return e;
+    if (int e = bufs.get(flags, dfl, m1)) return e;
     if (vec) {
-        OGG_HIP_CHECK(hipMemcpy(values2, dv2, m2 * 8, hipMemcpyDeviceToHost));
-        OGG_HIP_CHECK(hipMemcpy(flags2, dfl2, m2, hipMemcpyDeviceToHost));
+        if (int e = bufs.get(values2, dv2, m2)) return e;
+        if (int e = bufs.get(flags2, dfl2, m2)) return e;
     }
     if (rot) {
-        OGG_HIP_CHECK(hipMemcpy(rot_cos, rc, n1 * 8, hipMemcpyDeviceToHost));
-        OGG_HIP_CHECK(hipMemcpy(rot_sin, rs, n1 * 8, hipMemcpyDeviceToHost));
+        if (int e = bufs.get(rot_cos, rc, n1)) return e;
+        if (int e = bufs.get(rot_sin, rs, n1)) return e;
         if (c) {
-            OGG_HIP_CHECK(hipMemcpy(rot_cos2, rc2, n2 * 8, hipMemcpyDeviceToHost));
-            OGG_HIP_CHECK(hipMemcpy(rot_sin2, rs2, n2 * 8, hipMemcpyDeviceToHost));
+            if (int e = bufs.get(rot_cos2, rc2, n2)) return e;
+            if (int e = bufs.get(rot_sin2, rs2, n2)) return e;
         }
     }
     return OGG_OK;

@@ -17,8 +17,8 @@
 //           straddles the seam or the fold, or holds scattered centres, has a large ball and tests (nearly) everything: slower, as exact.
 //           A lane skips a cube whose box is farther from its own p than its best so far.
 //           Rounding: a difference of two doubles, a product and a square root are each correctly rounded, so every computed
-//           distance is within a few 2^-53 of its value RELATIVELY, however small; MARGIN = 1 + 1e-12 on every comparison of two
-//           computed distances covers that a million times over (the runoff search's margin).
+//           distance is within a few 2^-53 of its value RELATIVELY, however small; MARGIN = 1 + 1e-12 (ogg_sphere.h) on every
+//           comparison of two computed distances covers that a million times over.
 // OGG_COAST_BRUTE=1 streams the whole target list through every tile instead (no index, no pruning): the cross-check.
 //
 // nearest and d2 are a function of the unit vectors and the wet bytes alone: the key makes the order in which targets are met
@@ -30,6 +30,7 @@
 #include <cstring>
 
 #include "ogg_blocks.h"
+#include "ogg_cells.h"
 #include "ogg_common.h"
 #include "ogg_sphere_bins.h"
 
@@ -40,12 +41,10 @@ namespace {
 using ogg::at;
 using ogg::grid_for;
 using ogg::knob;
-using ogg::round256;
 
 constexpr int NT = 256;                 // threads per workgroup (four wavefronts)
 constexpr int MAX_CHUNK = 512;          // the largest OGG_COAST_CHUNK: targets of one LDS chunk
 constexpr long HEAD = 256;
-constexpr double MARGIN = 1.0 + 1e-12;  // covers the rounding of two computed distances that are compared (see above)
 constexpr int F_WET = 1, F_COAST = 2, F_VALID = 4;
 
 static_assert(sizeof(ogg_coast_params) == 24, "ogg_coast_params layout");
@@ -60,27 +59,25 @@ static_assert(sizeof(Head) <= HEAD, "workspace head");
 
 // ---- sets ----------------------------------------------------------------------------------------------------------
 struct Cells {
-    long ny, nx;
-    int periodic, fold, sides;
+    CellTopo t;
+    int sides;
 };
 
 __global__ __launch_bounds__(NT) void flag_kernel(Cells g, const double* __restrict__ x, const double* __restrict__ y, long ld,
                                                   const unsigned char* __restrict__ wet, unsigned char* __restrict__ flags,
                                                   double* __restrict__ u, ogg_coast_counts* counts) {
-    const long n = g.ny * g.nx;
+    const long n = g.t.ny * g.t.nx;
     long long v[3] = {0, 0, 0};
     for (long c = (long)blockIdx.x * NT + threadIdx.x; c < n; c += (long)gridDim.x * NT) {
-        const long j = c / g.nx, i = c % g.nx, k = (2 * j + 1) * ld + 2 * i + 1;
+        const long k = centre_point(c, g.t.nx, ld);
         const double lon = x[k], lat = y[k];
         const bool valid = isfinite(lon) && isfinite(lat);
         const bool w = wet[c] != 0;
         // a neighbour that does not exist is not a neighbour: the grid's edge is no coast
-        const long s = j > 0 ? c - g.nx : -1;
-        const long we = i > 0 ? c - 1 : (g.periodic ? c + g.nx - 1 : -1);
-        const long e = i < g.nx - 1 ? c + 1 : (g.periodic ? c - (g.nx - 1) : -1);
-        const long nn = j < g.ny - 1 ? c + g.nx : (g.fold ? j * g.nx + (g.nx - 1 - i) : -1);
-        const bool coast = (s >= 0 && (wet[s] != 0) != w) || (we >= 0 && (wet[we] != 0) != w) || (e >= 0 && (wet[e] != 0) != w) ||
-                           (nn >= 0 && (wet[nn] != 0) != w);
+        long nb[4];
+        face_neighbours(g.t, c, nb);
+        const bool coast = (nb[0] >= 0 && (wet[nb[0]] != 0) != w) || (nb[1] >= 0 && (wet[nb[1]] != 0) != w) ||
+                           (nb[2] >= 0 && (wet[nb[2]] != 0) != w) || (nb[3] >= 0 && (wet[nb[3]] != 0) != w);
         flags[c] = (unsigned char)((w ? F_WET : 0) | (coast ? F_COAST : 0) | (valid ? F_VALID : 0));
         double t[3];
         unit(lon, lat, t);
@@ -195,12 +192,6 @@ __device__ inline double maxd2(const double* p, const double* lo, const double* 
     return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
 }
 
-struct Best {
-    unsigned long long bits;
-    int cell;
-    long long tests;
-};
-
 struct Chunk {
     double u[3][MAX_CHUNK];
     int c[MAX_CHUNK];
@@ -208,7 +199,8 @@ struct Chunk {
 
 // the targets s0 .. s1 of tu / tc through LDS, chunk by chunk; the lanes with ``act`` test every one of them.  Called by the whole
 // workgroup with the same s0, s1.
-__device__ inline void stream(const Search& s, Chunk& ch, int s0, int s1, bool act, const double* p, Best& best) {
+__device__ inline void stream(const Search& s, Chunk& ch, int s0, int s1, bool act, const double* p, Nearest& best,
+                              long long& tests) {
     for (int base = s0; base < s1; base += s.chunk) {
         const int m = s1 - base < s.chunk ? s1 - base : s.chunk;
         __syncthreads();   // the chunk before this one has been read
@@ -221,12 +213,8 @@ __device__ inline void stream(const Search& s, Chunk& ch, int s0, int s1, bool a
         }
         __syncthreads();
         if (act) {
-            for (int k = 0; k < m; ++k) {
-                const unsigned long long bb = bits_of(dist2(p[0], p[1], p[2], ch.u[0][k], ch.u[1][k], ch.u[2][k]));
-                const int cc = ch.c[k];
-                if (bb < best.bits || (bb == best.bits && cc < best.cell)) best.bits = bb, best.cell = cc;
-            }
-            best.tests += m;
+            for (int k = 0; k < m; ++k) best.offer(bits_of(dist2(p[0], p[1], p[2], ch.u[0][k], ch.u[1][k], ch.u[2][k])), ch.c[k]);
+            tests += m;
         }
     }
 }
@@ -248,9 +236,10 @@ __global__ __launch_bounds__(NT) void search_kernel(Search s, const unsigned cha
     if (__syncthreads_count(q) == 0) return;   // no query of this side in the tile
     double p[3] = {0.0, 0.0, 0.0};
     if (q) p[0] = u[3 * c], p[1] = u[3 * c + 1], p[2] = u[3 * c + 2];
-    Best best{ULLONG_MAX, INT_MAX, 0};
+    Nearest best{ULLONG_MAX, INT_MAX};
+    long long tests = 0;
     if (s.brute) {
-        stream(s, ch, 0, (int)s.nt, q, p, best);
+        stream(s, ch, 0, (int)s.nt, q, p, best, tests);
     } else {
         // the ball of the tile's queries: m the middle of their bounding box, r2 the largest squared distance from m
         double bb[6];
@@ -294,20 +283,20 @@ __global__ __launch_bounds__(NT) void search_kernel(Search s, const unsigned cha
             for (int e = 0; e < total; ++e) {
                 // a lane leaves out a cube whose box is farther from its own p than its best (strictly: ties are still met)
                 bool act = q;
-                if (act && best.cell != INT_MAX) {
-                    double bd;
+                if (act && best.found()) {
+                    double bd;   // read from the key itself, before the box: profiles/nearest_kit_kernel_resources.md
                     memcpy(&bd, &best.bits, 8);
                     act = !(mind2(p, qbox[e], qbox[e] + 3) > bd * MARGIN);
                 }
-                stream(s, ch, qrange[e].x, qrange[e].y, act, p, best);
+                stream(s, ch, qrange[e].x, qrange[e].y, act, p, best, tests);
             }
         }
     }
-    if (q && best.cell != INT_MAX) {
+    if (q && best.found()) {
         nearest[c] = best.cell;
-        memcpy(&d2[c], &best.bits, 8);
+        d2[c] = best.d2();
     }
-    long long v[2] = {q && best.cell != INT_MAX ? 1 : 0, best.tests};
+    long long v[2] = {q && best.found() ? 1 : 0, tests};
     long long* const dst[2] = {&counts->answered, &counts->tests};
     block_add<2>(v, dst);
 }
@@ -344,30 +333,22 @@ long nbins_max() { return (long)OGG_COAST_MAX_CUBES * OGG_COAST_MAX_CUBES * OGG_
 // workspace: head | member / non-empty bytes | positions | block sums | cube counts | cube starts | cube of target | binned u |
 // binned cells | cube ranges | cube boxes
 struct Layout {
-    long flag, pos, bsum, cnt, start, bin, bu, bc, range, box, total;
+    long flag, pos, bsum, range, box, total;
+    CubeIndexLayout index;
 };
 
 Layout layout(const ogg_coast_params& p) {
     Layout l;
     const long nc = ncell_of(p), nb = nbins_max(), ni = std::max(nc, nb), nk = std::min(nc, nb);
-    l.flag = HEAD;
-    l.pos = l.flag + round256(ni);
-    l.bsum = l.pos + round256(ni * 4);
-    l.cnt = l.bsum + round256((ni / SCAN_CH + 2) * 8);
-    l.start = l.cnt + round256(nb * 4);
-    l.bin = l.start + round256(nb * 4);
-    l.bu = l.bin + round256(nc * 4);
-    l.bc = l.bu + round256(nc * 24);
-    l.range = l.bc + round256(nc * 4);
-    l.box = l.range + round256(nk * 8);
-    l.total = l.box + round256(nk * 48);
+    ogg::Sections s{HEAD};
+    l.flag = s.take(ni);
+    l.pos = s.take(ni * 4);
+    l.bsum = s.take((ni / SCAN_CH + 2) * 8);
+    l.index = cube_index_sections(s, nc, nb);
+    l.range = s.take(nk * 8);
+    l.box = s.take(nk * 48);
+    l.total = s.off;
     return l;
-}
-
-int check_ws(const ogg_coast_params& p, const void* ws, long wsb, const char* who) {
-    const long need = layout(p).total;
-    OGG_REQUIRE(ws && wsb >= need, OGG_EARG, "%s: workspace of %ld bytes, %ld needed", who, wsb, need);
-    return OGG_OK;
 }
 
 struct Knobs {
@@ -397,36 +378,25 @@ int search_side(const ogg_coast_params& p, const Knobs& kn, int G, int wet, cons
     Head* head = at<Head>(ws, 0);
     Search s{p.ny, p.nx, kn.tx, kn.ty, wet, kn.chunk, kn.brute, nt, head, nullptr, nullptr, tu, tc};
     if (!kn.brute) {
-        const long nb = (long)G * G * G, nb1 = nb + 1;
-        int* cnt = at<int>(ws, l.cnt);
-        int* start = at<int>(ws, l.start);
-        int* bin = at<int>(ws, l.bin);
-        double* bu = at<double>(ws, l.bu);
-        int* bc = at<int>(ws, l.bc);
+        const long nb = (long)G * G * G;
+        const CubeIndex ci = cube_index_at(ws, l.index);
         unsigned char* ne = at<unsigned char>(ws, l.flag);
         int* cpos = at<int>(ws, l.pos);
         int2* range = at<int2>(ws, l.range);
         double* box = at<double>(ws, l.box);
         long long* bsum = at<long long>(ws, l.bsum);
-        OGG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)nb1 * 4, st));
-        bin_count_kernel<<<grid_for<NT>(nt, 4096), NT, 0, st>>>(tu, nt, G, cnt, bin);
-        OGG_LAUNCH_CHECK();
-        // starts: the exclusive prefix of the counts over nb + 1 cubes (cnt[nb] = 0, so start[nb] = nt)
-        if (int e = exclusive_scan<false>(cnt, nb1, bsum, &head->total, start, st)) return e;
-        OGG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)nb1 * 4, st));   // the cursors of the fill
-        bin_fill_kernel<<<grid_for<NT>(nt, 4096), NT, 0, st>>>(tu, tc, nt, bin, start, cnt, bu, bc);
-        OGG_LAUNCH_CHECK();
-        nonempty_kernel<<<grid_for<NT>(nb, 4096), NT, 0, st>>>(start, nb, ne);
+        if (int e = build_cube_index(tu, tc, nt, G, ci, bsum, &head->total, st)) return e;
+        nonempty_kernel<<<grid_for<NT>(nb, 4096), NT, 0, st>>>(ci.start, nb, ne);
         OGG_LAUNCH_CHECK();
         if (int e = exclusive_scan<false>(ne, nb, bsum, &head->total, cpos, st)) return e;
-        cube_list_kernel<<<grid_for<NT>(nb, 4096), NT, 0, st>>>(start, ne, cpos, nb, range, head);
+        cube_list_kernel<<<grid_for<NT>(nb, 4096), NT, 0, st>>>(ci.start, ne, cpos, nb, range, head);
         OGG_LAUNCH_CHECK();
-        cube_box_kernel<<<grid_for<NT / 64>(std::min(nt, nb), 4096), NT, 0, st>>>(head, range, bu, box);
+        cube_box_kernel<<<grid_for<NT / 64>(std::min(nt, nb), 4096), NT, 0, st>>>(head, range, ci.bu, box);
         OGG_LAUNCH_CHECK();
         s.range = range;
         s.box = box;
-        s.tu = bu;
-        s.tc = bc;
+        s.tu = ci.bu;
+        s.tc = ci.bc;
     }
     const long tiles = ((p.ny + kn.ty - 1) / kn.ty) * ((p.nx + kn.tx - 1) / kn.tx);
     search_kernel<<<(unsigned)tiles, NT, 0, st>>>(s, flags, u, nearest, d2, counts);
@@ -447,7 +417,7 @@ extern "C" int ogg_coast_sets_dev(const ogg_coast_params* p, const double* x, co
                                   void* workspace, long workspace_bytes, unsigned char* flags, double* u, int* land_cell, double* land_u,
                                   int* wet_cell, double* wet_u, ogg_coast_counts* counts, void* stream) {
     if (int e = check_params(p)) return e;
-    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_coast_sets")) return e;
+    if (int e = ogg::check_workspace("ogg_coast_sets", workspace, workspace_bytes, layout(*p).total)) return e;
     OGG_REQUIRE(x && y && wet && flags && u && land_cell && land_u && wet_cell && wet_u && counts, OGG_EARG,
                 "ogg_coast_sets: null x / y / wet / flags / u / land_cell / land_u / wet_cell / wet_u / counts");
     OGG_REQUIRE(ld >= 2 * p->nx + 1, OGG_EARG, "ogg_coast_sets: row stride %ld < 2 nx + 1", ld);
@@ -455,7 +425,7 @@ extern "C" int ogg_coast_sets_dev(const ogg_coast_params* p, const double* x, co
     const Layout l = layout(*p);
     const long nc = ncell_of(*p);
     OGG_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(ogg_coast_counts), st));
-    const Cells g{p->ny, p->nx, (p->topology & OGG_MASK_PERIODIC) ? 1 : 0, (p->topology & OGG_MASK_FOLD) ? 1 : 0, p->sides};
+    const Cells g{cell_topo(p->ny, p->nx, p->topology), p->sides};
     flag_kernel<<<grid_for<NT>(nc, 4096), NT, 0, st>>>(g, x, y, ld, wet, flags, u, counts);
     OGG_LAUNCH_CHECK();
     unsigned char* member = at<unsigned char>(workspace, l.flag);
@@ -475,7 +445,7 @@ extern "C" int ogg_coast_search_dev(const ogg_coast_params* p, const unsigned ch
                                     void* workspace, long workspace_bytes, int* nearest, double* d2, ogg_coast_counts* counts,
                                     void* stream) {
     if (int e = check_params(p)) return e;
-    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_coast_search")) return e;
+    if (int e = ogg::check_workspace("ogg_coast_search", workspace, workspace_bytes, layout(*p).total)) return e;
     const long nc = ncell_of(*p);
     OGG_REQUIRE(n_land >= 0 && n_wet >= 0 && n_land + n_wet <= nc, OGG_EARG, "ogg_coast_search: %ld coastal land and %ld coastal wet of %ld cells",
                 n_land, n_wet, nc);
@@ -505,33 +475,31 @@ extern "C" int ogg_coast_distance(const ogg_coast_params* p, const double* x, co
     ogg::Buffers bufs;   // freed on every exit path
     const size_t nc = (size_t)ncell_of(*p), npt = (size_t)(2 * p->ny + 1) * (2 * p->nx + 1);
     const long wsb = layout(*p).total;
-    void *dx, *dy, *dw, *ws, *df, *du, *lc, *lu, *wc, *wu, *dn, *dd, *ct;
-    if (int e = bufs.put(&dx, x, npt * 8)) return e;
-    if (int e = bufs.put(&dy, y, npt * 8)) return e;
+    double *dx, *dy, *du, *lu, *wu, *dd;
+    unsigned char *dw, *df;
+    char* ws;
+    int *lc, *wc, *dn;
+    ogg_coast_counts* ct;
+    if (int e = bufs.put(&dx, x, npt)) return e;
+    if (int e = bufs.put(&dy, y, npt)) return e;
     if (int e = bufs.put(&dw, wet, nc)) return e;
     if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
     if (int e = bufs.alloc(&df, nc)) return e;
-    if (int e = bufs.alloc(&du, nc * 24)) return e;
-    if (int e = bufs.alloc(&lc, nc * 4)) return e;
-    if (int e = bufs.alloc(&lu, nc * 24)) return e;
-    if (int e = bufs.alloc(&wc, nc * 4)) return e;
-    if (int e = bufs.alloc(&wu, nc * 24)) return e;
-    if (int e = bufs.alloc(&dn, nc * 4)) return e;
-    if (int e = bufs.alloc(&dd, nc * 8)) return e;
-    if (int e = bufs.alloc(&ct, sizeof(ogg_coast_counts))) return e;
-    ogg_coast_counts* dct = static_cast<ogg_coast_counts*>(ct);
-    if (int e = ogg_coast_sets_dev(p, static_cast<double*>(dx), static_cast<double*>(dy), 2 * p->nx + 1, static_cast<unsigned char*>(dw), ws,
-                                   wsb, static_cast<unsigned char*>(df), static_cast<double*>(du), static_cast<int*>(lc),
-                                   static_cast<double*>(lu), static_cast<int*>(wc), static_cast<double*>(wu), dct, nullptr))
+    if (int e = bufs.alloc(&du, nc * 3)) return e;
+    if (int e = bufs.alloc(&lc, nc)) return e;
+    if (int e = bufs.alloc(&lu, nc * 3)) return e;
+    if (int e = bufs.alloc(&wc, nc)) return e;
+    if (int e = bufs.alloc(&wu, nc * 3)) return e;
+    if (int e = bufs.alloc(&dn, nc)) return e;
+    if (int e = bufs.alloc(&dd, nc)) return e;
+    if (int e = bufs.alloc(&ct, 1)) return e;
+    if (int e = ogg_coast_sets_dev(p, dx, dy, 2 * p->nx + 1, dw, ws, wsb, df, du, lc, lu, wc, wu, ct, nullptr)) return e;
+    if (int e = bufs.get(counts, ct, 1)) return e;
+    if (int e = ogg_coast_search_dev(p, df, du, lc, lu, (long)counts->coast_land, wc, wu, (long)counts->coast_wet, ws, wsb, dn, dd, ct, nullptr))
         return e;
-    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_coast_counts), hipMemcpyDeviceToHost));
-    if (int e = ogg_coast_search_dev(p, static_cast<unsigned char*>(df), static_cast<double*>(du), static_cast<int*>(lc),
-                                     static_cast<double*>(lu), (long)counts->coast_land, static_cast<int*>(wc), static_cast<double*>(wu),
-                                     (long)counts->coast_wet, ws, wsb, static_cast<int*>(dn), static_cast<double*>(dd), dct, nullptr))
-        return e;
-    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_coast_counts), hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(nearest, dn, nc * 4, hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(d2, dd, nc * 8, hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(flags, df, nc, hipMemcpyDeviceToHost));
+    if (int e = bufs.get(counts, ct, 1)) return e;
+    if (int e = bufs.get(nearest, dn, nc)) return e;
+    if (int e = bufs.get(d2, dd, nc)) return e;
+    if (int e = bufs.get(flags, df, nc)) return e;
     return OGG_OK;
 }

@@ -70,26 +70,53 @@ class Buffers {
     ~Buffers() {
         for (void* q : p_) (void)hipFree(q);
     }
-    int alloc(void** out, size_t bytes) {
+    // a buffer of n elements of T (a workspace of n bytes is n chars)
+    template <typename T>
+    int alloc(T** out, size_t n) {
+        const size_t bytes = n * sizeof(T);
         hipError_t e = hipMalloc(out, bytes ? bytes : 8);
         if (e != hipSuccess)
             return set_error(e == hipErrorOutOfMemory ? OGG_ENOMEM : OGG_EHIP, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
         p_.push_back(*out);
         return OGG_OK;
     }
-    // a buffer holding a copy of bytes of host memory
-    int put(void** out, const void* src, size_t bytes) {
-        if (int e = alloc(out, bytes)) return e;
-        OGG_HIP_CHECK(hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice));
+    // n elements from host memory into a buffer (send), or back (get); put: a new buffer holding a copy of n elements of host memory
+    template <typename T>
+    static int send(T* dev, const T* host, size_t n) {
+        OGG_HIP_CHECK(hipMemcpy(dev, host, n * sizeof(T), hipMemcpyHostToDevice));
         return OGG_OK;
+    }
+    template <typename T>
+    static int get(T* host, const T* dev, size_t n) {
+        OGG_HIP_CHECK(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost));
+        return OGG_OK;
+    }
+    template <typename T>
+    int put(T** out, const T* host, size_t n) {
+        if (int e = alloc(out, n)) return e;
+        return send(*out, host, n);
     }
 
    private:
     std::vector<void*> p_;
 };
 
-// workspace sections start on 256-byte boundaries
-inline long round256(long v) { return (v + 255) / 256 * 256; }
+// the sections of a workspace, one after the other from ``off`` on 256-byte boundaries (the exchange grid's: 64): take(bytes) gives
+// the next section's offset, and after the last take off is the size of the whole
+struct Sections {
+    long off, align = 256;
+    long take(long bytes) {
+        const long o = off;
+        off += (bytes + align - 1) / align * align;
+        return o;
+    }
+};
+
+// the one refusal of a workspace that is missing or too small for the call ``who``
+inline int check_workspace(const char* who, const void* ws, long wsb, long need) {
+    OGG_REQUIRE(ws && wsb >= need, OGG_EARG, "%s: workspace of %ld bytes, %ld needed", who, wsb, need);
+    return OGG_OK;
+}
 
 // a typed pointer into a workspace
 template <typename P>

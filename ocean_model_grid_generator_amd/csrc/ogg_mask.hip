@@ -15,7 +15,6 @@
 #include <climits>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "ogg_blocks.h"
@@ -28,7 +27,6 @@ namespace {
 using ogg::at;
 using ogg::grid_for;
 using ogg::knob;
-using ogg::round256;
 
 constexpr long LIST_BLOCKS = 1024;   // blocks of the list and apply kernels: each block adds once to a shared counter word
 constexpr long APPLY_BLOCKS = 1024;
@@ -160,8 +158,7 @@ __global__ __launch_bounds__(NT) void mask_seed_kernel(long ny, long nx, const d
         for (long base = (long)blockIdx.x * NT; base < n; base += (long)gridDim.x * NT) {
             const long c = base + threadIdx.x;
             if (c >= n) continue;
-            const long j = c / nx, i = c % nx, k = (2 * j + 1) * ld + 2 * i + 1;
-            unit(x[k], y[k], cu);
+            centre_unit(x, y, c, nx, ld, cu);
             const unsigned long long bits = bits_of(dist2(cu[0], cu[1], cu[2], su[0], su[1], su[2]));
             const unsigned long long v = SECOND ? (bits == want ? (unsigned long long)c : ULLONG_MAX) : bits;
             best = v < best ? v : best;
@@ -188,7 +185,17 @@ int check_params(const ogg_mask_params* p) {
     return OGG_OK;
 }
 
-long ws_bytes(const ogg_mask_params& p) { return 2 * round256(p.ny * p.nx * 4); }
+// workspace: parents | cells per root
+struct Layout {
+    long par, size, total;
+};
+
+Layout layout(const ogg_mask_params& p) {
+    ogg::Sections s{0};
+    return Layout{s.take(p.ny * p.nx * 4), s.take(p.ny * p.nx * 4), s.off};   // a braced list is evaluated left to right
+}
+
+long ws_bytes(const ogg_mask_params& p) { return layout(p).total; }
 
 }  // namespace
 
@@ -203,13 +210,12 @@ extern "C" int ogg_mask_label_dev(const ogg_mask_params* p, const double* depth,
                                   long long* components, ogg_mask_counts* counts, void* stream) {
     if (int e = check_params(p)) return e;
     OGG_REQUIRE(depth && root && components && counts, OGG_EARG, "ogg_mask_label: null depth / root / components / counts");
-    OGG_REQUIRE(workspace && workspace_bytes >= ws_bytes(*p), OGG_EARG, "ogg_mask_label: workspace of %ld bytes, %ld needed",
-                workspace_bytes, ws_bytes(*p));
+    if (int e = ogg::check_workspace("ogg_mask_label", workspace, workspace_bytes, ws_bytes(*p))) return e;
     int th = 0;
     if (int e = knob("OGG_MASK_TILE_ROWS", TH_DEFAULT, 1, TH_MAX, &th)) return e;
     const long n = p->ny * p->nx;
-    int* par = static_cast<int*>(workspace);
-    int* size = at<int>(workspace, round256(n * 4));
+    int* par = at<int>(workspace, layout(*p).par);
+    int* size = at<int>(workspace, layout(*p).size);
     hipStream_t st = ogg::as_stream(stream);
     OGG_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(ogg_mask_counts), st));
     OGG_HIP_CHECK(hipMemsetAsync(size, 0, (size_t)n * 4, st));
@@ -246,10 +252,9 @@ extern "C" int ogg_mask_apply_dev(const ogg_mask_params* p, const double* depth,
     if (int e = check_params(p)) return e;
     OGG_REQUIRE(depth && root && depth_out && wet && counts, OGG_EARG, "ogg_mask_apply: null depth / root / depth_out / wet / counts");
     OGG_REQUIRE(n_kept >= 0 && (kept || n_kept == 0), OGG_EARG, "ogg_mask_apply: %d kept roots", n_kept);
-    OGG_REQUIRE(workspace && workspace_bytes >= ws_bytes(*p), OGG_EARG, "ogg_mask_apply: workspace of %ld bytes, %ld needed",
-                workspace_bytes, ws_bytes(*p));
+    if (int e = ogg::check_workspace("ogg_mask_apply", workspace, workspace_bytes, ws_bytes(*p))) return e;
     const long n = p->ny * p->nx;
-    const int* size = at<int>(workspace, round256(n * 4));
+    const int* size = at<int>(workspace, layout(*p).size);
     hipStream_t st = ogg::as_stream(stream);
     OGG_HIP_CHECK(hipMemsetAsync(&counts->wet_in, 0, 3 * sizeof(long long), st));
     OGG_HIP_CHECK(hipMemsetAsync(&counts->kept, 0, 3 * sizeof(long long), st));
@@ -275,35 +280,36 @@ extern "C" int ogg_ocean_mask(const ogg_mask_params* p, const double* depth, con
     if (int e = knob("OGG_MASK_TILE_ROWS", TH_DEFAULT, 1, TH_MAX, &th)) return e;
     ogg::Buffers bufs;   // freed on every exit path
     const long n = p->ny * p->nx, wsb = ws_bytes(*p);
-    void *dd = nullptr, *ws = nullptr, *dr = nullptr, *dc = nullptr, *ct = nullptr, *dout = nullptr, *dwet = nullptr, *dk = nullptr;
-    if (int e = bufs.alloc(&dd, (size_t)n * 8)) return e;
+    double *dd, *dout;
+    char* ws;
+    int *dr, *dk = nullptr;
+    long long* dc;
+    unsigned char* dwet;
+    ogg_mask_counts* ct;
+    if (int e = bufs.alloc(&dd, (size_t)n)) return e;
     if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
-    if (int e = bufs.alloc(&dr, (size_t)n * 4)) return e;
-    if (int e = bufs.alloc(&dc, (size_t)n * 8)) return e;
-    if (int e = bufs.alloc(&ct, sizeof(ogg_mask_counts))) return e;
-    OGG_HIP_CHECK(hipMemcpy(dd, depth, (size_t)n * 8, hipMemcpyHostToDevice));
-    ogg_mask_counts* dct = static_cast<ogg_mask_counts*>(ct);
-    if (int e = ogg_mask_label_dev(p, static_cast<const double*>(dd), ws, wsb, static_cast<int*>(dr), static_cast<long long*>(dc), dct,
-                                   nullptr))
-        return e;
-    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_mask_counts), hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(root, dr, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (int e = bufs.alloc(&dr, (size_t)n)) return e;
+    if (int e = bufs.alloc(&dc, (size_t)n)) return e;
+    if (int e = bufs.alloc(&ct, 1)) return e;
+    if (int e = bufs.send(dd, depth, (size_t)n)) return e;
+    if (int e = ogg_mask_label_dev(p, dd, ws, wsb, dr, dc, ct, nullptr)) return e;
+    if (int e = bufs.get(counts, ct, 1)) return e;
+    if (int e = bufs.get(root, dr, (size_t)n)) return e;
     std::vector<int> kept;
     if (n_seeds > 0) {
-        const long np = (2 * p->ny + 1) * (2 * p->nx + 1);
-        void *px = nullptr, *py = nullptr, *ps = nullptr, *po = nullptr;
-        if (int e = bufs.alloc(&px, (size_t)np * 8)) return e;
-        if (int e = bufs.alloc(&py, (size_t)np * 8)) return e;
-        if (int e = bufs.alloc(&ps, (size_t)n_seeds * 16)) return e;
-        if (int e = bufs.alloc(&po, (size_t)n_seeds * 16)) return e;
-        OGG_HIP_CHECK(hipMemcpy(px, x, (size_t)np * 8, hipMemcpyHostToDevice));
-        OGG_HIP_CHECK(hipMemcpy(py, y, (size_t)np * 8, hipMemcpyHostToDevice));
-        OGG_HIP_CHECK(hipMemcpy(ps, lonlat, (size_t)n_seeds * 16, hipMemcpyHostToDevice));
-        if (int e = ogg_mask_seed_dev(p, static_cast<const double*>(px), static_cast<const double*>(py), 2 * p->nx + 1, n_seeds,
-                                      static_cast<const double*>(ps), static_cast<long long*>(po), nullptr))
-            return e;
+        const size_t np = (size_t)(2 * p->ny + 1) * (2 * p->nx + 1);
+        double *px, *py, *ps;
+        long long* po;
+        if (int e = bufs.alloc(&px, np)) return e;
+        if (int e = bufs.alloc(&py, np)) return e;
+        if (int e = bufs.alloc(&ps, (size_t)n_seeds * 2)) return e;
+        if (int e = bufs.alloc(&po, (size_t)n_seeds * 2)) return e;
+        if (int e = bufs.send(px, x, np)) return e;
+        if (int e = bufs.send(py, y, np)) return e;
+        if (int e = bufs.send(ps, lonlat, (size_t)n_seeds * 2)) return e;
+        if (int e = ogg_mask_seed_dev(p, px, py, 2 * p->nx + 1, n_seeds, ps, po, nullptr)) return e;
         std::vector<long long> so(2 * (size_t)n_seeds);
-        OGG_HIP_CHECK(hipMemcpy(so.data(), po, (size_t)n_seeds * 16, hipMemcpyDeviceToHost));
+        if (int e = bufs.get(so.data(), po, so.size())) return e;
         for (int s = 0; s < n_seeds; ++s) {
             const long long c = so[2 * s + 1];
             OGG_REQUIRE(c >= 0 && c < n, OGG_EARG, "ocean mask: seed %d (%g, %g) found no cell centre", s, lonlat[2 * s], lonlat[2 * s + 1]);
@@ -317,21 +323,17 @@ extern "C" int ogg_ocean_mask(const ogg_mask_params* p, const double* depth, con
     }
     std::sort(kept.begin(), kept.end());
     kept.erase(std::unique(kept.begin(), kept.end()), kept.end());
-    if (!kept.empty()) {
-        if (int e = bufs.alloc(&dk, kept.size() * 4)) return e;
-        OGG_HIP_CHECK(hipMemcpy(dk, kept.data(), kept.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (int e = bufs.alloc(&dout, (size_t)n * 8)) return e;
+    if (!kept.empty())
+        if (int e = bufs.put(&dk, kept.data(), kept.size())) return e;
+    if (int e = bufs.alloc(&dout, (size_t)n)) return e;
     if (int e = bufs.alloc(&dwet, (size_t)n)) return e;
-    if (int e = ogg_mask_apply_dev(p, static_cast<const double*>(dd), static_cast<const int*>(dr), ws, wsb, static_cast<const int*>(dk),
-                                   (int)kept.size(), static_cast<double*>(dout), static_cast<unsigned char*>(dwet), dct, nullptr))
-        return e;
-    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_mask_counts), hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(depth_out, dout, (size_t)n * 8, hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(wet, dwet, (size_t)n, hipMemcpyDeviceToHost));
+    if (int e = ogg_mask_apply_dev(p, dd, dr, ws, wsb, dk, (int)kept.size(), dout, dwet, ct, nullptr)) return e;
+    if (int e = bufs.get(counts, ct, 1)) return e;
+    if (int e = bufs.get(depth_out, dout, (size_t)n)) return e;
+    if (int e = bufs.get(wet, dwet, (size_t)n)) return e;
     if (capacity > 0 && counts->components > 0) {
         std::vector<long long> list((size_t)counts->components);
-        OGG_HIP_CHECK(hipMemcpy(list.data(), dc, list.size() * 8, hipMemcpyDeviceToHost));
+        if (int e = bufs.get(list.data(), dc, list.size())) return e;
         std::sort(list.begin(), list.end(), [](long long a, long long b) { return a > b; });
         std::copy(list.begin(), list.begin() + std::min<long>(capacity, (long)list.size()), components);
     }

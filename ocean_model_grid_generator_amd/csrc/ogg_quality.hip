@@ -358,11 +358,10 @@ extern "C" int ogg_grid_quality(const ogg_quality_band* band, ogg_grid_quality_r
     auto up = [&bufs](const double* src, long n, const double** dst) -> int {
         *dst = nullptr;
         if (!src) return OGG_OK;
-        void* p = nullptr;
-        if (int e = bufs.alloc(&p, (size_t)(n > 0 ? n : 0) * sizeof(double))) return e;
-        if (n > 0) OGG_HIP_CHECK(hipMemcpy(p, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        *dst = static_cast<const double*>(p);
-        return OGG_OK;
+        double* p;
+        if (int e = bufs.alloc(&p, (size_t)(n > 0 ? n : 0))) return e;
+        *dst = p;
+        return n > 0 ? bufs.send(p, src, (size_t)n) : OGG_OK;
     };
 #define OGG_UP(src, n, dst)                   \
     do {                                      \
@@ -384,10 +383,10 @@ extern "C" int ogg_grid_quality(const ogg_quality_band* band, ogg_grid_quality_r
     OGG_UP(h.y_seam, nxp, &d.y_seam);
 #undef OGG_UP
     const long ws_bytes = ogg_grid_quality_workspace_bytes(h.nx, np);
-    void *ws = nullptr, *res = nullptr;
+    char* ws;
+    ogg_grid_quality_result* res;
     if (int e = bufs.alloc(&ws, (size_t)(ws_bytes > 0 ? ws_bytes : 0))) return e;
-    if (int e = bufs.alloc(&res, sizeof(ogg_grid_quality_result))) return e;
-    if (int e = ogg_grid_quality_band_dev(&d, ws, ws_bytes, static_cast<ogg_grid_quality_result*>(res), nullptr)) return e;
-    OGG_HIP_CHECK(hipMemcpy(out, res, sizeof(ogg_grid_quality_result), hipMemcpyDeviceToHost));
-    return OGG_OK;
+    if (int e = bufs.alloc(&res, 1)) return e;
+    if (int e = ogg_grid_quality_band_dev(&d, ws, ws_bytes, res, nullptr)) return e;
+    return bufs.get(out, res, 1);
 }

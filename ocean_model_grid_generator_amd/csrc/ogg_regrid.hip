@@ -39,7 +39,6 @@ namespace {
 using ogg::at;
 using ogg::grid_for;
 using ogg::knob;
-using ogg::round256;
 
 constexpr int NT = 256;                 // threads per workgroup of the list passes (four wavefronts)
 constexpr int LONG_DEFAULT = 512;       // cells with more entries are walked by whole wavefronts (OGG_REGRID_LONG)
@@ -321,15 +320,16 @@ struct Layout {
 Layout layout(const ogg_regrid_params& p, long n) {
     Layout l;
     const long nk = p.NA * p.NB;
-    l.cur = HEAD;
-    l.seg = l.cur + round256(nk * 4);
-    l.bsum = l.seg + round256((nk + 1) * 4);
-    l.longs = l.bsum + round256(((nk + 1) / SCAN_CH + 2) * 8);
-    l.key0 = l.longs + round256(nk * 4);
-    l.key1 = l.key0 + round256(n * 8);
-    l.pc = l.key1 + round256(n * 8);
-    l.pa = l.pc + round256(n * 4);
-    l.total = l.pa + round256(n * 8);
+    ogg::Sections s{HEAD};
+    l.cur = s.take(nk * 4);
+    l.seg = s.take((nk + 1) * 4);
+    l.bsum = s.take(((nk + 1) / SCAN_CH + 2) * 8);
+    l.longs = s.take(nk * 4);
+    l.key0 = s.take(n * 8);
+    l.key1 = s.take(n * 8);
+    l.pc = s.take(n * 4);
+    l.pa = s.take(n * 8);
+    l.total = s.off;
     return l;
 }
 
@@ -377,8 +377,7 @@ extern "C" int ogg_regrid_transpose_dev(const ogg_regrid_params* p, const int* a
     OGG_REQUIRE((atm_ij && ocn_ij && area) || n_entries == 0, OGG_EARG, "ogg_regrid_transpose: null atm_ij / ocn_ij / area");
     OGG_REQUIRE(counts, OGG_EARG, "ogg_regrid_transpose: null counts");
     const Layout l = layout(*p, n_entries);
-    OGG_REQUIRE(workspace && workspace_bytes >= l.total, OGG_EARG, "ogg_regrid_transpose: workspace of %ld bytes, %ld needed",
-                workspace_bytes, l.total);
+    if (int e = ogg::check_workspace("ogg_regrid_transpose", workspace, workspace_bytes, l.total)) return e;
     hipStream_t st = ogg::as_stream(stream);
     const long nk = p->NA * p->NB;
     OGG_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(ogg_regrid_counts), st));
@@ -416,7 +415,7 @@ extern "C" int ogg_regrid_dev(const ogg_regrid_params* p, const void* f, const d
     OGG_REQUIRE(values || !cover, OGG_EARG, "ogg_regrid: cover needs values");
     OGG_REQUIRE(n_list >= 0 && n_list < (long)INT_MAX, OGG_EARG, "ogg_regrid: %ld entries (< 2^31)", n_list);
     const Layout l = layout(*p, n_list);
-    OGG_REQUIRE(workspace && workspace_bytes >= l.total, OGG_EARG, "ogg_regrid: workspace of %ld bytes, %ld needed", workspace_bytes, l.total);
+    if (int e = ogg::check_workspace("ogg_regrid", workspace, workspace_bytes, l.total)) return e;
     // OGG_REGRID_RECORDS: records a lane sums at once.  Their gathers are independent loads, so more records keep more of them in
     // flight per lane.  Measured at 1/8 degree (profiles/r12_regrid_time.json, ms for 1, 2, 4, 8): 57 levels onto 1 degree 21.3, 14.4,
     // 11.8, 10.5; onto 0.25 degree 18.0, 11.0, 8.5, 7.0; 12 records onto 1 degree 5.2, 3.5, 3.2, 4.2.
@@ -465,42 +464,43 @@ extern "C" int ogg_regrid(const ogg_regrid_params* p, const void* f, const int* 
     const size_t nk = (size_t)p->NA * p->NB, nout = (size_t)p->nrec * nk;
     const size_t fbytes = (size_t)p->nrec * p->ny * p->nx * (p->dtype == OGG_REMAP_FLOAT32 ? 4 : 8);
     const long wsb = layout(*p, n_entries).total;
-    void *df = nullptr, *da = nullptr, *dox = nullptr, *dar = nullptr, *daa = nullptr, *ws = nullptr, *dv = nullptr, *dc = nullptr,
-         *dfr = nullptr, *dn = nullptr, *ct = nullptr;
-    if (int e = bufs.alloc(&da, (size_t)n_entries * 8)) return e;
-    if (int e = bufs.alloc(&dox, (size_t)n_entries * 8)) return e;
-    if (int e = bufs.alloc(&dar, (size_t)n_entries * 8)) return e;
-    if (int e = bufs.alloc(&daa, nk * 8)) return e;
+    char *df = nullptr, *ws;
+    int *da, *dox, *dn = nullptr;
+    double *dar, *daa, *dv = nullptr, *dc = nullptr, *dfr = nullptr;
+    ogg_regrid_counts* ct;
+    if (int e = bufs.alloc(&da, (size_t)n_entries * 2)) return e;
+    if (int e = bufs.alloc(&dox, (size_t)n_entries * 2)) return e;
+    if (int e = bufs.alloc(&dar, (size_t)n_entries)) return e;
+    if (int e = bufs.alloc(&daa, nk)) return e;
     if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
-    if (int e = bufs.alloc(&ct, sizeof(ogg_regrid_counts))) return e;
+    if (int e = bufs.alloc(&ct, 1)) return e;
     if (values) {
         if (int e = bufs.alloc(&df, fbytes)) return e;
-        if (int e = bufs.alloc(&dv, nout * 8)) return e;
-        OGG_HIP_CHECK(hipMemcpy(df, f, fbytes, hipMemcpyHostToDevice));
+        if (int e = bufs.alloc(&dv, nout)) return e;
+        if (int e = bufs.send(df, static_cast<const char*>(f), fbytes)) return e;
     }
     if (cover)
-        if (int e = bufs.alloc(&dc, nout * 8)) return e;
+        if (int e = bufs.alloc(&dc, nout)) return e;
     if (frac)
-        if (int e = bufs.alloc(&dfr, nk * 8)) return e;
+        if (int e = bufs.alloc(&dfr, nk)) return e;
     if (n_out)
-        if (int e = bufs.alloc(&dn, nk * 4)) return e;
+        if (int e = bufs.alloc(&dn, nk)) return e;
     if (n_entries > 0) {
-        OGG_HIP_CHECK(hipMemcpy(da, atm_ij, (size_t)n_entries * 8, hipMemcpyHostToDevice));
-        OGG_HIP_CHECK(hipMemcpy(dox, ocn_ij, (size_t)n_entries * 8, hipMemcpyHostToDevice));
-        OGG_HIP_CHECK(hipMemcpy(dar, area, (size_t)n_entries * 8, hipMemcpyHostToDevice));
+        if (int e = bufs.send(da, atm_ij, (size_t)n_entries * 2)) return e;
+        if (int e = bufs.send(dox, ocn_ij, (size_t)n_entries * 2)) return e;
+        if (int e = bufs.send(dar, area, (size_t)n_entries)) return e;
     }
-    OGG_HIP_CHECK(hipMemcpy(daa, a_atm, nk * 8, hipMemcpyHostToDevice));
-    ogg_regrid_counts* dct = static_cast<ogg_regrid_counts*>(ct);
-    if (int e = ogg_regrid_transpose_dev(p, static_cast<const int*>(da), static_cast<const int*>(dox), static_cast<const double*>(dar),
-                                         n_entries, ws, wsb, dct, nullptr))
-        return e;
-    if (int e = ogg_regrid_dev(p, df, static_cast<const double*>(daa), n_entries, ws, wsb, static_cast<double*>(dv), static_cast<double*>(dc),
-                               static_cast<double*>(dfr), static_cast<int*>(dn), dct, nullptr))
-        return e;
-    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_regrid_counts), hipMemcpyDeviceToHost));
-    if (values) OGG_HIP_CHECK(hipMemcpy(values, dv, nout * 8, hipMemcpyDeviceToHost));
-    if (cover) OGG_HIP_CHECK(hipMemcpy(cover, dc, nout * 8, hipMemcpyDeviceToHost));
-    if (frac) OGG_HIP_CHECK(hipMemcpy(frac, dfr, nk * 8, hipMemcpyDeviceToHost));
-    if (n_out) OGG_HIP_CHECK(hipMemcpy(n_out, dn, nk * 4, hipMemcpyDeviceToHost));
+    if (int e = bufs.send(daa, a_atm, nk)) return e;
+    if (int e = ogg_regrid_transpose_dev(p, da, dox, dar, n_entries, ws, wsb, ct, nullptr)) return e;
+    if (int e = ogg_regrid_dev(p, df, daa, n_entries, ws, wsb, dv, dc, dfr, dn, ct, nullptr)) return e;
+    if (int e = bufs.get(counts, ct, 1)) return e;
+    if (values)
+        if (int e = bufs.get(values, dv, nout)) return e;
+    if (cover)
+        if (int e = bufs.get(cover, dc, nout)) return e;
+    if (frac)
+        if (int e = bufs.get(frac, dfr, nk)) return e;
+    if (n_out)
+        if (int e = bufs.get(n_out, dn, nk)) return e;
     return OGG_OK;
 }

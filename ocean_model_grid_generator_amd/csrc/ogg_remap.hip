@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "ogg_blocks.h"
+#include "ogg_cells.h"
 #include "ogg_common.h"
 
 #pragma clang fp contract(off)
@@ -39,7 +40,6 @@ namespace {
 using ogg::at;
 using ogg::grid_for;
 using ogg::knob;
-using ogg::round256;
 
 constexpr int NT = 256;                 // threads per workgroup (four wavefronts)
 constexpr int REG = 8;                  // entries a lane keeps in registers across records
@@ -217,19 +217,10 @@ __global__ __launch_bounds__(NT) void remap_kernel(Geo g, const T* __restrict__ 
 
 // ---- fill --------------------------------------------------------------------------------------------------------
 struct Topo {
-    long ny, nx, ncell;
+    CellTopo cells;
+    long ncell;
     unsigned long long total;           // nrec * ncell
-    int periodic, fold;
 };
-
-// S, W, E, N of cell c (-1: none)
-__device__ inline void neighbours(const Topo& t, long c, long (&nb)[4]) {
-    const long j = c / t.nx, i = c % t.nx;
-    nb[0] = j > 0 ? c - t.nx : -1;
-    nb[1] = i > 0 ? c - 1 : (t.periodic ? c + t.nx - 1 : -1);
-    nb[2] = i < t.nx - 1 ? c + 1 : (t.periodic ? c - (t.nx - 1) : -1);
-    nb[3] = j < t.ny - 1 ? c + t.nx : (t.fold ? j * t.nx + (t.nx - 1 - i) : -1);
-}
 
 // the flag byte at idx from `want` to `to` by a compare-and-swap of its 32-bit word (flags: 4-byte aligned, rounded up to 4 bytes)
 __device__ inline bool claim(unsigned char* flags, unsigned long long idx, unsigned want, unsigned to) {
@@ -277,7 +268,7 @@ __global__ __launch_bounds__(NT) void remap_fill_first_kernel(Topo t, unsigned c
                 if (idx >= t.total || ((w >> (8 * q)) & 0xFFu) != OGG_REMAP_UNFILLED) continue;
                 const long r = (long)(idx / t.ncell), c = (long)(idx % t.ncell);
                 long nb[4];
-                neighbours(t, c, nb);
+                face_neighbours(t.cells, c, nb);   // a neighbour that does not exist is skipped
                 bool any = false;
                 for (int k = 0; k < 4; ++k) any = any || (nb[k] >= 0 && flags[r * t.ncell + nb[k]] == OGG_REMAP_REMAPPED);
                 if (any) take |= 1u << q, ++cnt;
@@ -313,7 +304,7 @@ __global__ __launch_bounds__(NT) void remap_fill_front_kernel(Topo t, int k, dou
             const unsigned long long idx = queue[lo + q];
             const long r = (long)(idx / t.ncell), c = (long)(idx % t.ncell);
             rb = (unsigned long long)r * t.ncell;
-            neighbours(t, c, nb);
+            face_neighbours(t.cells, c, nb);
             double s = 0.0;
             int m = 0;
             for (int d = 0; d < 4; ++d)
@@ -369,13 +360,16 @@ int check_params(const ogg_remap_params* p) {
     return OGG_OK;
 }
 
-long seg_bytes(const ogg_remap_params& p) { return round256(p.ny * p.nx * 8); }
-long ws_bytes(const ogg_remap_params& p) { return HEAD + seg_bytes(p) + round256(p.nrec * p.ny * p.nx * 4); }
+struct Layout {
+    long seg, queue, total;
+};
 
-int check_ws(const ogg_remap_params& p, const void* ws, long wsb, const char* who) {
-    OGG_REQUIRE(ws && wsb >= ws_bytes(p), OGG_EARG, "%s: workspace of %ld bytes, %ld needed", who, wsb, ws_bytes(p));
-    return OGG_OK;
+Layout layout(const ogg_remap_params& p) {
+    ogg::Sections s{HEAD};
+    return Layout{s.take(p.ny * p.nx * 8), s.take(p.nrec * p.ny * p.nx * 4), s.off};   // a braced list is evaluated left to right
 }
+
+long ws_bytes(const ogg_remap_params& p) { return layout(p).total; }
 
 template <typename T, bool C>
 void launch_remap(dim3 grid, hipStream_t st, const Geo& g, const void* f, const int2* seg, const int* atm_ij, const double* area,
@@ -395,12 +389,12 @@ extern "C" int ogg_remap_check(const ogg_remap_params* p) { return check_params(
 extern "C" int ogg_remap_segments_dev(const ogg_remap_params* p, const int* ocn_ij, long n_entries, void* workspace, long workspace_bytes,
                                       void* stream) {
     if (int e = check_params(p)) return e;
-    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_remap_segments")) return e;
+    if (int e = ogg::check_workspace("ogg_remap_segments", workspace, workspace_bytes, ws_bytes(*p))) return e;
     OGG_REQUIRE(n_entries >= 0 && n_entries < (long)INT_MAX, OGG_EARG, "ogg_remap_segments: %ld entries", n_entries);
     OGG_REQUIRE(ocn_ij || n_entries == 0, OGG_EARG, "ogg_remap_segments: null ocn_ij");
     hipStream_t st = ogg::as_stream(stream);
     Head* h = static_cast<Head*>(workspace);
-    int2* seg = at<int2>(workspace, HEAD);
+    int2* seg = at<int2>(workspace, layout(*p).seg);
     OGG_HIP_CHECK(hipMemsetAsync(&h->seg_bad, 0, sizeof(h->seg_bad), st));
     OGG_HIP_CHECK(hipMemsetAsync(seg, 0, (size_t)p->ny * p->nx * 8, st));
     if (n_entries == 0) return OGG_OK;
@@ -413,7 +407,7 @@ extern "C" int ogg_remap_dev(const ogg_remap_params* p, const void* f, const int
                              const unsigned char* mask, const void* workspace, long workspace_bytes, double* values, unsigned char* flags,
                              ogg_remap_counts* counts, void* stream) {
     if (int e = check_params(p)) return e;
-    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_remap")) return e;
+    if (int e = ogg::check_workspace("ogg_remap", workspace, workspace_bytes, ws_bytes(*p))) return e;
     OGG_REQUIRE(n_entries >= 0 && n_entries < (long)INT_MAX, OGG_EARG, "ogg_remap: %ld entries", n_entries);
     OGG_REQUIRE(f && values && flags && counts && ((atm_ij && area) || n_entries == 0), OGG_EARG,
                 "ogg_remap: null f / atm_ij / area / values / flags / counts");
@@ -427,7 +421,7 @@ extern "C" int ogg_remap_dev(const ogg_remap_params* p, const void* f, const int
     OGG_REQUIRE(nchunk <= 65535, OGG_EARG, "ogg_remap: %ld record chunks (OGG_REMAP_RECORDS=%d): at most 65535", nchunk, rec);
     hipStream_t st = ogg::as_stream(stream);
     const Head* h = static_cast<const Head*>(workspace);
-    const int2* seg = at<int2>(workspace, HEAD);
+    const int2* seg = at<int2>(workspace, layout(*p).seg);
     OGG_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(ogg_remap_counts), st));
     const Geo g{p->ny, p->nx, p->NA, p->NB, p->nrec, rchunk, p->n_fill, long_n, p->fill[0], p->fill[1], &h->seg_bad};
     const long waves = p->ny * ((p->nx + 63) / 64);
@@ -443,7 +437,7 @@ extern "C" int ogg_remap_dev(const ogg_remap_params* p, const void* f, const int
 extern "C" int ogg_remap_fill_dev(const ogg_remap_params* p, void* workspace, long workspace_bytes, double* values, unsigned char* flags,
                                   ogg_remap_counts* counts, void* stream) {
     if (int e = check_params(p)) return e;
-    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_remap_fill")) return e;
+    if (int e = ogg::check_workspace("ogg_remap_fill", workspace, workspace_bytes, ws_bytes(*p))) return e;
     OGG_REQUIRE(p->m0 == 0, OGG_EARG, "ogg_remap_fill: the fill needs the whole grid (m0 = %ld)", p->m0);
     OGG_REQUIRE(values && flags && counts, OGG_EARG, "ogg_remap_fill: null values / flags / counts");
     OGG_REQUIRE(((uintptr_t)flags & 3) == 0, OGG_EARG, "ogg_remap_fill: flags must be 4-byte aligned");
@@ -452,9 +446,8 @@ extern "C" int ogg_remap_fill_dev(const ogg_remap_params* p, void* workspace, lo
     if (int e = knob("OGG_REMAP_FILL_BLOCKS", FILL_BLOCKS_DEFAULT, 1, 1 << 16, &blocks)) return e;
     hipStream_t st = ogg::as_stream(stream);
     Head* h = static_cast<Head*>(workspace);
-    unsigned* queue = at<unsigned>(workspace, HEAD + seg_bytes(*p));
-    const Topo t{p->ny, p->nx, p->ny * p->nx, (unsigned long long)(p->nrec * p->ny * p->nx), (p->topology & OGG_MASK_PERIODIC) ? 1 : 0,
-                 (p->topology & OGG_MASK_FOLD) ? 1 : 0};
+    unsigned* queue = at<unsigned>(workspace, layout(*p).queue);
+    const Topo t{cell_topo(p->ny, p->nx, p->topology), p->ny * p->nx, (unsigned long long)(p->nrec * p->ny * p->nx)};
     OGG_HIP_CHECK(hipMemsetAsync(h, 0, sizeof(Slot) * 3 + sizeof(long long), st));
     remap_fill_first_kernel<<<grid_for<NT>((long)((t.total + 3) / 4), blocks), NT, 0, st>>>(t, flags, queue, h);
     OGG_LAUNCH_CHECK();
@@ -489,36 +482,33 @@ extern "C" int ogg_remap(const ogg_remap_params* p, const void* f, const int* at
     const size_t ncell = (size_t)p->ny * p->nx, npair = (size_t)p->nrec * ncell;
     const size_t fbytes = (size_t)p->nrec * p->NA * p->NB * (p->dtype == OGG_REMAP_FLOAT32 ? 4 : 8);
     const long wsb = ws_bytes(*p);
-    void *df = nullptr, *da = nullptr, *dox = nullptr, *dar = nullptr, *dm = nullptr, *ws = nullptr, *dv = nullptr, *dfl = nullptr,
-         *ct = nullptr;
+    char *df, *ws;
+    int *da, *dox;
+    double *dar, *dv;
+    unsigned char *dm = nullptr, *dfl;
+    ogg_remap_counts* ct;
     if (int e = bufs.alloc(&df, fbytes)) return e;
-    if (int e = bufs.alloc(&da, (size_t)n_entries * 8)) return e;
-    if (int e = bufs.alloc(&dox, (size_t)n_entries * 8)) return e;
-    if (int e = bufs.alloc(&dar, (size_t)n_entries * 8)) return e;
+    if (int e = bufs.alloc(&da, (size_t)n_entries * 2)) return e;
+    if (int e = bufs.alloc(&dox, (size_t)n_entries * 2)) return e;
+    if (int e = bufs.alloc(&dar, (size_t)n_entries)) return e;
     if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
-    if (int e = bufs.alloc(&dv, npair * 8)) return e;
+    if (int e = bufs.alloc(&dv, npair)) return e;
     if (int e = bufs.alloc(&dfl, (npair + 3) / 4 * 4)) return e;
-    if (int e = bufs.alloc(&ct, sizeof(ogg_remap_counts))) return e;
-    OGG_HIP_CHECK(hipMemcpy(df, f, fbytes, hipMemcpyHostToDevice));
+    if (int e = bufs.alloc(&ct, 1)) return e;
+    if (int e = bufs.send(df, static_cast<const char*>(f), fbytes)) return e;
     if (n_entries > 0) {
-        OGG_HIP_CHECK(hipMemcpy(da, atm_ij, (size_t)n_entries * 8, hipMemcpyHostToDevice));
-        OGG_HIP_CHECK(hipMemcpy(dox, ocn_ij, (size_t)n_entries * 8, hipMemcpyHostToDevice));
-        OGG_HIP_CHECK(hipMemcpy(dar, area, (size_t)n_entries * 8, hipMemcpyHostToDevice));
+        if (int e = bufs.send(da, atm_ij, (size_t)n_entries * 2)) return e;
+        if (int e = bufs.send(dox, ocn_ij, (size_t)n_entries * 2)) return e;
+        if (int e = bufs.send(dar, area, (size_t)n_entries)) return e;
     }
-    if (mask) {
-        if (int e = bufs.alloc(&dm, ncell)) return e;
-        OGG_HIP_CHECK(hipMemcpy(dm, mask, ncell, hipMemcpyHostToDevice));
-    }
-    ogg_remap_counts* dct = static_cast<ogg_remap_counts*>(ct);
-    if (int e = ogg_remap_segments_dev(p, static_cast<const int*>(dox), n_entries, ws, wsb, nullptr)) return e;
-    if (int e = ogg_remap_dev(p, df, static_cast<const int*>(da), static_cast<const double*>(dar), n_entries,
-                              static_cast<const unsigned char*>(dm), ws, wsb, static_cast<double*>(dv), static_cast<unsigned char*>(dfl), dct,
-                              nullptr))
-        return e;
+    if (mask)
+        if (int e = bufs.put(&dm, mask, ncell)) return e;
+    if (int e = ogg_remap_segments_dev(p, dox, n_entries, ws, wsb, nullptr)) return e;
+    if (int e = ogg_remap_dev(p, df, da, dar, n_entries, dm, ws, wsb, dv, dfl, ct, nullptr)) return e;
     if (do_fill)
-        if (int e = ogg_remap_fill_dev(p, ws, wsb, static_cast<double*>(dv), static_cast<unsigned char*>(dfl), dct, nullptr)) return e;
-    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_remap_counts), hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(values, dv, npair * 8, hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(flags, dfl, npair, hipMemcpyDeviceToHost));
+        if (int e = ogg_remap_fill_dev(p, ws, wsb, dv, dfl, ct, nullptr)) return e;
+    if (int e = bufs.get(counts, ct, 1)) return e;
+    if (int e = bufs.get(values, dv, npair)) return e;
+    if (int e = bufs.get(flags, dfl, npair)) return e;
     return OGG_OK;
 }

@@ -24,10 +24,10 @@
 #include <climits>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "ogg_blocks.h"
+#include "ogg_cells.h"
 #include "ogg_common.h"
 #include "ogg_keysort.h"
 #include "ogg_sphere_bins.h"
@@ -39,7 +39,6 @@ namespace {
 using ogg::at;
 using ogg::grid_for;
 using ogg::knob;
-using ogg::round256;
 
 constexpr int NT = 256;                 // threads per workgroup (four wavefronts)
 constexpr int REG = 8;                  // sources a lane keeps in registers across records
@@ -47,7 +46,6 @@ constexpr int LONG_N = 32;              // cells with more sources are walked by
 constexpr long HEAD = 256;
 constexpr double D = SPHERE_D;
 constexpr double PAD = 1e-9;            // cubes widened by this much: covers the rounding of a point's cube index
-constexpr double MARGIN = 1.0 + 1e-12;  // covers the rounding of a computed d2
 
 static_assert(sizeof(ogg_runoff_params) == 80, "ogg_runoff_params layout");
 static_assert(sizeof(ogg_runoff_counts) == 64, "ogg_runoff_counts layout");
@@ -61,26 +59,23 @@ static_assert(sizeof(Head) <= HEAD, "workspace head");
 
 // ---- targets -------------------------------------------------------------------------------------------------------
 struct Cells {
-    long ny, nx;
-    int periodic, fold, coast;
+    CellTopo t;
+    int coast;
 };
 
 __global__ __launch_bounds__(NT) void target_flag_kernel(Cells g, const unsigned char* __restrict__ wet, unsigned char* __restrict__ flag,
                                                          ogg_runoff_counts* counts) {
-    const long n = g.ny * g.nx;
+    const long n = g.t.ny * g.t.nx;
     long long v[1] = {0};
     for (long c = (long)blockIdx.x * NT + threadIdx.x; c < n; c += (long)gridDim.x * NT) {
         unsigned char t = 0;
         if (wet[c]) {
             if (!g.coast) {
                 t = 1;
-            } else {
-                const long j = c / g.nx, i = c % g.nx;
-                const long s = j > 0 ? c - g.nx : -1;
-                const long w = i > 0 ? c - 1 : (g.periodic ? c + g.nx - 1 : -1);
-                const long e = i < g.nx - 1 ? c + 1 : (g.periodic ? c - (g.nx - 1) : -1);
-                const long nn = j < g.ny - 1 ? c + g.nx : (g.fold ? j * g.nx + (g.nx - 1 - i) : -1);
-                t = (s < 0 || !wet[s] || w < 0 || !wet[w] || e < 0 || !wet[e] || nn < 0 || !wet[nn]) ? 1 : 0;
+            } else {   // a neighbour that does not exist is land: the grid's edge is a coast
+                long nb[4];
+                face_neighbours(g.t, c, nb);
+                t = (nb[0] < 0 || !wet[nb[0]] || nb[1] < 0 || !wet[nb[1]] || nb[2] < 0 || !wet[nb[2]] || nb[3] < 0 || !wet[nb[3]]) ? 1 : 0;
             }
         }
         flag[c] = t;
@@ -96,10 +91,9 @@ __global__ __launch_bounds__(NT) void target_list_kernel(long ny, long nx, const
     const long n = ny * nx;
     for (long c = (long)blockIdx.x * NT + threadIdx.x; c < n; c += (long)gridDim.x * NT) {
         if (!flag[c]) continue;
-        const long j = c / nx, i = c % nx, k = (2 * j + 1) * ld + 2 * i + 1;
         const long q = pos[c];
         double v[3];
-        unit(x[k], y[k], v);
+        centre_unit(x, y, c, nx, ld, v);
         cell[q] = (int)c;
         u[3 * q] = v[0];
         u[3 * q + 1] = v[1];
@@ -166,14 +160,9 @@ struct Index {
     const int* bc;
 };
 
-struct Best {
-    unsigned long long bits;
-    int cell;
-    long long tests;
-};
-
 // the targets of cube (a, b, c) against the point (px, py, pz), unless the cube misses the sphere or lies beyond the best
-__device__ inline void visit(const Index& ix, int a, int b, int c, double px, double py, double pz, Best& best) {
+__device__ inline void visit(const Index& ix, int a, int b, int c, double px, double py, double pz, Nearest& best,
+                             long long& tests) {
     const double lx = -1.0 + a * ix.h - PAD, hx = -1.0 + (a + 1) * ix.h + PAD;
     const double ly = -1.0 + b * ix.h - PAD, hy = -1.0 + (b + 1) * ix.h + PAD;
     const double lz = -1.0 + c * ix.h - PAD, hz = -1.0 + (c + 1) * ix.h + PAD;
@@ -183,19 +172,12 @@ __device__ inline void visit(const Index& ix, int a, int b, int c, double px, do
     if ((ox * ox + oy * oy) + oz * oz > 1.0 + 1e-6 || (fx + fy) + fz < 1.0 - 1e-6) return;   // misses the unit sphere
     const double gx = lx > px ? lx - px : (px > hx ? px - hx : 0.0), gy = ly > py ? ly - py : (py > hy ? py - hy : 0.0),
                  gz = lz > pz ? lz - pz : (pz > hz ? pz - hz : 0.0);
-    if (best.cell != INT_MAX) {
-        double bd;
-        memcpy(&bd, &best.bits, 8);
-        if ((gx * gx + gy * gy) + gz * gz > bd * MARGIN) return;
-    }
+    if (best.beyond((gx * gx + gy * gy) + gz * gz)) return;
     const int cube = a + ix.G * (b + ix.G * c);
     const int s0 = ix.start[cube], s1 = ix.start[cube + 1];
-    for (int t = s0; t < s1; ++t) {
-        const unsigned long long bb = bits_of(dist2(px, py, pz, ix.bu[3 * t], ix.bu[3 * t + 1], ix.bu[3 * t + 2]));
-        const int cc = ix.bc[t];
-        if (bb < best.bits || (bb == best.bits && cc < best.cell)) best.bits = bb, best.cell = cc;
-    }
-    best.tests += s1 - s0;
+    for (int t = s0; t < s1; ++t)
+        best.offer(bits_of(dist2(px, py, pz, ix.bu[3 * t], ix.bu[3 * t + 1], ix.bu[3 * t + 2])), ix.bc[t]);
+    tests += s1 - s0;
 }
 
 __global__ __launch_bounds__(NT) void search_kernel(Index ix, const double* __restrict__ su, long n, int* __restrict__ tgt,
@@ -204,7 +186,8 @@ __global__ __launch_bounds__(NT) void search_kernel(Index ix, const double* __re
     for (long s = (long)blockIdx.x * NT + threadIdx.x; s < n; s += (long)gridDim.x * NT) {
         const double px = su[3 * s], py = su[3 * s + 1], pz = su[3 * s + 2];
         const int ca = cube_of(px, ix.G), cb = cube_of(py, ix.G), cc = cube_of(pz, ix.G);
-        Best best{ULLONG_MAX, INT_MAX, 0};
+        Nearest best{ULLONG_MAX, INT_MAX};
+        long long tests = 0;
         for (int k = 0; k <= ix.G; ++k) {
             for (int da = -k; da <= k; ++da) {
                 const int a = ca + da;
@@ -216,20 +199,16 @@ __global__ __launch_bounds__(NT) void search_kernel(Index ix, const double* __re
                     const int step = rim ? 1 : (k > 0 ? 2 * k : 1);
                     for (int dc = -k; dc <= k; dc += step) {
                         const int c = cc + dc;
-                        if (c >= 0 && c < ix.G) visit(ix, a, b, c, px, py, pz, best);
+                        if (c >= 0 && c < ix.G) visit(ix, a, b, c, px, py, pz, best, tests);
                     }
                 }
             }
-            if (best.cell != INT_MAX) {
-                const double lb = k * ix.h - 2.0 * PAD;   // every target not yet visited is at least this far
-                double bd;
-                memcpy(&bd, &best.bits, 8);
-                if (lb > 0.0 && lb * lb > bd * MARGIN) break;
-            }
+            const double lb = k * ix.h - 2.0 * PAD;   // every target not yet visited is at least this far
+            if (lb > 0.0 && best.beyond(lb * lb)) break;
         }
         tgt[s] = best.cell;
-        memcpy(&d2[s], &best.bits, 8);
-        v[0] += best.tests;
+        d2[s] = best.d2();
+        v[0] += tests;
     }
     long long* const dst[1] = {&counts->tests};
     block_add<1>(v, dst);
@@ -244,7 +223,7 @@ __global__ __launch_bounds__(NT) void brute_kernel(const int* __restrict__ cell,
     const long s = (long)blockIdx.x * NT + threadIdx.x;
     const bool act = s < n;
     const double px = act ? su[3 * s] : 0.0, py = act ? su[3 * s + 1] : 0.0, pz = act ? su[3 * s + 2] : 0.0;
-    Best best{ULLONG_MAX, INT_MAX, 0};
+    Nearest best{ULLONG_MAX, INT_MAX};
     for (long base = 0; base < nt; base += NT) {
         const long t = base + threadIdx.x;
         if (t < nt) {
@@ -255,17 +234,13 @@ __global__ __launch_bounds__(NT) void brute_kernel(const int* __restrict__ cell,
         }
         __syncthreads();
         const int m = nt - base < NT ? (int)(nt - base) : NT;
-        for (int k = 0; k < m; ++k) {
-            const unsigned long long bb = bits_of(dist2(px, py, pz, lu[0][k], lu[1][k], lu[2][k]));
-            const int cc = lc[k];
-            if (bb < best.bits || (bb == best.bits && cc < best.cell)) best.bits = bb, best.cell = cc;
-        }
+        for (int k = 0; k < m; ++k) best.offer(bits_of(dist2(px, py, pz, lu[0][k], lu[1][k], lu[2][k])), lc[k]);
         __syncthreads();
     }
     long long v[1] = {act ? (long long)nt : 0};
     if (act) {
         tgt[s] = best.cell;
-        memcpy(&d2[s], &best.bits, 8);
+        d2[s] = best.d2();
     }
     long long* const dst[1] = {&counts->tests};
     block_add<1>(v, dst);
@@ -422,32 +397,24 @@ long nbins_max() { return (long)OGG_RUNOFF_MAX_BINS * OGG_RUNOFF_MAX_BINS * OGG_
 // workspace: head | flag bytes | positions | block sums | A_s | cube counts | cube starts | cube of target | binned u | binned cells |
 // keys (two buffers) | segments
 struct Layout {
-    long flag, pos, bsum, As, cnt, start, bin, bu, bc, key0, key1, seg, total;
+    long flag, pos, bsum, As, key0, key1, seg, total;
+    CubeIndexLayout index;
 };
 
 Layout layout(const ogg_runoff_params& p) {
     Layout l;
     const long ni = nitem(p), nc = ncell_of(p), ns = nsrc_of(p), nb = nbins_max();
-    l.flag = HEAD;
-    l.pos = l.flag + round256(ni);
-    l.bsum = l.pos + round256(ni * 4);
-    l.As = l.bsum + round256((std::max(ni, nb) / SCAN_CH + 2) * 8);
-    l.cnt = l.As + round256(ns * 8);
-    l.start = l.cnt + round256(nb * 4);
-    l.bin = l.start + round256(nb * 4);
-    l.bu = l.bin + round256(nc * 4);
-    l.bc = l.bu + round256(nc * 24);
-    l.key0 = l.bc + round256(nc * 4);
-    l.key1 = l.key0 + round256(ns * 8);
-    l.seg = l.key1 + round256(ns * 8);
-    l.total = l.seg + round256(nc * 8);
+    ogg::Sections s{HEAD};
+    l.flag = s.take(ni);
+    l.pos = s.take(ni * 4);
+    l.bsum = s.take((std::max(ni, nb) / SCAN_CH + 2) * 8);
+    l.As = s.take(ns * 8);
+    l.index = cube_index_sections(s, nc, nb);
+    l.key0 = s.take(ns * 8);
+    l.key1 = s.take(ns * 8);
+    l.seg = s.take(nc * 8);
+    l.total = s.off;
     return l;
-}
-
-int check_ws(const ogg_runoff_params& p, const void* ws, long wsb, const char* who) {
-    const long need = layout(p).total;
-    OGG_REQUIRE(ws && wsb >= need, OGG_EARG, "%s: workspace of %ld bytes, %ld needed", who, wsb, need);
-    return OGG_OK;
 }
 
 }  // namespace
@@ -463,15 +430,14 @@ extern "C" int ogg_runoff_targets_dev(const ogg_runoff_params* p, const double* 
                                       void* workspace, long workspace_bytes, int* tgt_cell, double* tgt_u, ogg_runoff_counts* counts,
                                       void* stream) {
     if (int e = check_params(p)) return e;
-    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_runoff_targets")) return e;
+    if (int e = ogg::check_workspace("ogg_runoff_targets", workspace, workspace_bytes, layout(*p).total)) return e;
     OGG_REQUIRE(x && y && wet && tgt_cell && tgt_u && counts, OGG_EARG, "ogg_runoff_targets: null x / y / wet / tgt_cell / tgt_u / counts");
     OGG_REQUIRE(ld >= 2 * p->nx + 1, OGG_EARG, "ogg_runoff_targets: row stride %ld < 2 nx + 1", ld);
     hipStream_t st = ogg::as_stream(stream);
     const Layout l = layout(*p);
     const long nc = ncell_of(*p);
     OGG_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(ogg_runoff_counts), st));
-    const Cells g{p->ny, p->nx, (p->topology & OGG_MASK_PERIODIC) ? 1 : 0, (p->topology & OGG_MASK_FOLD) ? 1 : 0,
-                  p->targets == OGG_RUNOFF_COAST ? 1 : 0};
+    const Cells g{cell_topo(p->ny, p->nx, p->topology), p->targets == OGG_RUNOFF_COAST ? 1 : 0};
     unsigned char* flag = at<unsigned char>(workspace, l.flag);
     int* pos = at<int>(workspace, l.pos);
     target_flag_kernel<<<grid_for<NT>(nc, 4096), NT, 0, st>>>(g, wet, flag, counts);
@@ -486,7 +452,7 @@ extern "C" int ogg_runoff_sources_dev(const ogg_runoff_params* p, const void* f,
                                       long workspace_bytes, int* src_cell, double* src_u, double* ds, ogg_runoff_counts* counts,
                                       void* stream) {
     if (int e = check_params(p)) return e;
-    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_runoff_sources")) return e;
+    if (int e = ogg::check_workspace("ogg_runoff_sources", workspace, workspace_bytes, layout(*p).total)) return e;
     OGG_REQUIRE(f && lon && lat && src_cell && src_u && ds && counts, OGG_EARG,
                 "ogg_runoff_sources: null f / lon / lat / src_cell / src_u / ds / counts");
     hipStream_t st = ogg::as_stream(stream);
@@ -514,7 +480,7 @@ extern "C" int ogg_runoff_search_dev(const ogg_runoff_params* p, const int* tgt_
                                      long n_mapped, void* workspace, long workspace_bytes, int* src_target, double* src_d2,
                                      ogg_runoff_counts* counts, void* stream) {
     if (int e = check_params(p)) return e;
-    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_runoff_search")) return e;
+    if (int e = ogg::check_workspace("ogg_runoff_search", workspace, workspace_bytes, layout(*p).total)) return e;
     OGG_REQUIRE(n_targets >= 0 && n_targets <= ncell_of(*p) && n_mapped >= 0 && n_mapped <= nsrc_of(*p), OGG_EARG,
                 "ogg_runoff_search: %ld targets of %ld cells, %ld mapped of %ld source cells", n_targets, ncell_of(*p), n_mapped,
                 nsrc_of(*p));
@@ -539,22 +505,10 @@ extern "C" int ogg_runoff_search_dev(const ogg_runoff_params* p, const int* tgt_
         OGG_LAUNCH_CHECK();
         return OGG_OK;
     }
-    const long nb = G * G * G;
-    int* cnt = at<int>(workspace, l.cnt);
-    int* start = at<int>(workspace, l.start);
-    int* bin = at<int>(workspace, l.bin);
-    OGG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)(nb + 1) * 4, st));
-    bin_count_kernel<<<grid_for<NT>(n_targets, 4096), NT, 0, st>>>(tgt_u, n_targets, (int)G, cnt, bin);
-    OGG_LAUNCH_CHECK();
-    // starts: the exclusive prefix of the counts over nb + 1 cubes (cnt[nb] = 0, so start[nb] = n_targets)
-    const long nb1 = nb + 1;
-    if (int e = exclusive_scan<false>(cnt, nb1, at<long long>(workspace, l.bsum), &at<Head>(workspace, 0)->total, start, st)) return e;
-    OGG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)nb1 * 4, st));   // the cursors of the fill
-    double* bu = at<double>(workspace, l.bu);
-    int* bc = at<int>(workspace, l.bc);
-    bin_fill_kernel<<<grid_for<NT>(n_targets, 4096), NT, 0, st>>>(tgt_u, tgt_cell, n_targets, bin, start, cnt, bu, bc);
-    OGG_LAUNCH_CHECK();
-    const Index ix{(int)G, 2.0 / (double)G, start, bu, bc};
+    const CubeIndex ci = cube_index_at(workspace, l.index);
+    if (int e = build_cube_index(tgt_u, tgt_cell, n_targets, (int)G, ci, at<long long>(workspace, l.bsum), &at<Head>(workspace, 0)->total, st))
+        return e;
+    const Index ix{(int)G, 2.0 / (double)G, ci.start, ci.bu, ci.bc};
     search_kernel<<<grid_for<NT>(n_mapped, 1L << 20), NT, 0, st>>>(ix, src_u, n_mapped, src_target, src_d2, counts);
     OGG_LAUNCH_CHECK();
     return OGG_OK;
@@ -563,7 +517,7 @@ extern "C" int ogg_runoff_search_dev(const ogg_runoff_params* p, const int* tgt_
 extern "C" int ogg_runoff_segments_dev(const ogg_runoff_params* p, const int* src_target, long n_mapped, void* workspace,
                                        long workspace_bytes, void* stream) {
     if (int e = check_params(p)) return e;
-    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_runoff_segments")) return e;
+    if (int e = ogg::check_workspace("ogg_runoff_segments", workspace, workspace_bytes, layout(*p).total)) return e;
     OGG_REQUIRE(n_mapped >= 0 && n_mapped <= nsrc_of(*p), OGG_EARG, "ogg_runoff_segments: %ld mapped of %ld source cells", n_mapped,
                 nsrc_of(*p));
     OGG_REQUIRE(src_target || n_mapped == 0, OGG_EARG, "ogg_runoff_segments: null src_target");
@@ -589,7 +543,7 @@ extern "C" int ogg_runoff_accumulate_dev(const ogg_runoff_params* p, const void*
                                          long lda, const void* workspace, long workspace_bytes, double* values, int* n_sources,
                                          ogg_runoff_counts* counts, void* stream) {
     if (int e = check_params(p)) return e;
-    if (int e = check_ws(*p, workspace, workspace_bytes, "ogg_runoff_accumulate")) return e;
+    if (int e = ogg::check_workspace("ogg_runoff_accumulate", workspace, workspace_bytes, layout(*p).total)) return e;
     OGG_REQUIRE(n_mapped >= 0 && n_mapped <= nsrc_of(*p), OGG_EARG, "ogg_runoff_accumulate: %ld mapped of %ld source cells", n_mapped,
                 nsrc_of(*p));
     OGG_REQUIRE(f && area && values && n_sources && counts && (src_cell || n_mapped == 0), OGG_EARG,
@@ -623,55 +577,50 @@ extern "C" int ogg_runoff(const ogg_runoff_params* p, const double* x, const dou
     const size_t nc = (size_t)ncell_of(*p), ns = (size_t)nsrc_of(*p), npt = (size_t)(2 * p->ny + 1) * (2 * p->nx + 1);
     const size_t fbytes = (size_t)p->nrec * ns * (p->dtype == OGG_REMAP_FLOAT32 ? 4 : 8);
     const long wsb = layout(*p).total;
-    void *dx, *dy, *da, *dw, *df, *dlon, *dlat, *ws, *tc, *tu, *sc, *su, *sds, *st, *sd, *dv, *dn, *ct;
-    if (int e = bufs.alloc(&dx, npt * 8)) return e;
-    if (int e = bufs.alloc(&dy, npt * 8)) return e;
-    if (int e = bufs.alloc(&da, nc * 4 * 8)) return e;
+    double *dx, *dy, *da, *dlon, *dlat, *tu, *su, *sds, *sd, *dv;
+    unsigned char* dw;
+    char *df, *ws;
+    int *tc, *sc, *st, *dn;
+    ogg_runoff_counts* ct;
+    if (int e = bufs.alloc(&dx, npt)) return e;
+    if (int e = bufs.alloc(&dy, npt)) return e;
+    if (int e = bufs.alloc(&da, nc * 4)) return e;
     if (int e = bufs.alloc(&dw, nc)) return e;
     if (int e = bufs.alloc(&df, fbytes)) return e;
-    if (int e = bufs.alloc(&dlon, (size_t)(p->NA + 1) * 8)) return e;
-    if (int e = bufs.alloc(&dlat, (size_t)(p->NB + 1) * 8)) return e;
+    if (int e = bufs.alloc(&dlon, (size_t)p->NA + 1)) return e;
+    if (int e = bufs.alloc(&dlat, (size_t)p->NB + 1)) return e;
     if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
-    if (int e = bufs.alloc(&tc, nc * 4)) return e;
-    if (int e = bufs.alloc(&tu, nc * 24)) return e;
-    if (int e = bufs.alloc(&sc, ns * 4)) return e;
-    if (int e = bufs.alloc(&su, ns * 24)) return e;
-    if (int e = bufs.alloc(&sds, (size_t)p->NB * 8)) return e;
-    if (int e = bufs.alloc(&st, ns * 4)) return e;
-    if (int e = bufs.alloc(&sd, ns * 8)) return e;
-    if (int e = bufs.alloc(&dv, (size_t)p->nrec * nc * 8)) return e;
-    if (int e = bufs.alloc(&dn, nc * 4)) return e;
-    if (int e = bufs.alloc(&ct, sizeof(ogg_runoff_counts))) return e;
-    OGG_HIP_CHECK(hipMemcpy(dx, x, npt * 8, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(dy, y, npt * 8, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(da, area, nc * 4 * 8, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(dw, wet, nc, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(df, f, fbytes, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(dlon, lon, (size_t)(p->NA + 1) * 8, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(dlat, lat, (size_t)(p->NB + 1) * 8, hipMemcpyHostToDevice));
-    ogg_runoff_counts* dct = static_cast<ogg_runoff_counts*>(ct);
-    if (int e = ogg_runoff_targets_dev(p, static_cast<double*>(dx), static_cast<double*>(dy), 2 * p->nx + 1, static_cast<unsigned char*>(dw),
-                                       ws, wsb, static_cast<int*>(tc), static_cast<double*>(tu), dct, nullptr))
-        return e;
-    if (int e = ogg_runoff_sources_dev(p, df, static_cast<double*>(dlon), static_cast<double*>(dlat), ws, wsb, static_cast<int*>(sc),
-                                       static_cast<double*>(su), static_cast<double*>(sds), dct, nullptr))
-        return e;
-    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_runoff_counts), hipMemcpyDeviceToHost));
+    if (int e = bufs.alloc(&tc, nc)) return e;
+    if (int e = bufs.alloc(&tu, nc * 3)) return e;
+    if (int e = bufs.alloc(&sc, ns)) return e;
+    if (int e = bufs.alloc(&su, ns * 3)) return e;
+    if (int e = bufs.alloc(&sds, (size_t)p->NB)) return e;
+    if (int e = bufs.alloc(&st, ns)) return e;
+    if (int e = bufs.alloc(&sd, ns)) return e;
+    if (int e = bufs.alloc(&dv, (size_t)p->nrec * nc)) return e;
+    if (int e = bufs.alloc(&dn, nc)) return e;
+    if (int e = bufs.alloc(&ct, 1)) return e;
+    if (int e = bufs.send(dx, x, npt)) return e;
+    if (int e = bufs.send(dy, y, npt)) return e;
+    if (int e = bufs.send(da, area, nc * 4)) return e;
+    if (int e = bufs.send(dw, wet, nc)) return e;
+    if (int e = bufs.send(df, static_cast<const char*>(f), fbytes)) return e;
+    if (int e = bufs.send(dlon, lon, (size_t)p->NA + 1)) return e;
+    if (int e = bufs.send(dlat, lat, (size_t)p->NB + 1)) return e;
+    if (int e = ogg_runoff_targets_dev(p, dx, dy, 2 * p->nx + 1, dw, ws, wsb, tc, tu, ct, nullptr)) return e;
+    if (int e = ogg_runoff_sources_dev(p, df, dlon, dlat, ws, wsb, sc, su, sds, ct, nullptr)) return e;
+    if (int e = bufs.get(counts, ct, 1)) return e;
     const long nt = (long)counts->targets, nm = (long)counts->mapped;
-    if (int e = ogg_runoff_search_dev(p, static_cast<int*>(tc), static_cast<double*>(tu), nt, static_cast<double*>(su), nm, ws, wsb,
-                                      static_cast<int*>(st), static_cast<double*>(sd), dct, nullptr))
-        return e;
-    if (int e = ogg_runoff_segments_dev(p, static_cast<int*>(st), nm, ws, wsb, nullptr)) return e;
-    if (int e = ogg_runoff_accumulate_dev(p, df, static_cast<int*>(sc), nm, static_cast<double*>(da), 2 * p->nx, ws, wsb,
-                                          static_cast<double*>(dv), static_cast<int*>(dn), dct, nullptr))
-        return e;
-    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_runoff_counts), hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(values, dv, (size_t)p->nrec * nc * 8, hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(n_sources, dn, nc * 4, hipMemcpyDeviceToHost));
+    if (int e = ogg_runoff_search_dev(p, tc, tu, nt, su, nm, ws, wsb, st, sd, ct, nullptr)) return e;
+    if (int e = ogg_runoff_segments_dev(p, st, nm, ws, wsb, nullptr)) return e;
+    if (int e = ogg_runoff_accumulate_dev(p, df, sc, nm, da, 2 * p->nx, ws, wsb, dv, dn, ct, nullptr)) return e;
+    if (int e = bufs.get(counts, ct, 1)) return e;
+    if (int e = bufs.get(values, dv, (size_t)p->nrec * nc)) return e;
+    if (int e = bufs.get(n_sources, dn, nc)) return e;
     if (nm > 0) {
-        OGG_HIP_CHECK(hipMemcpy(src_cell, sc, (size_t)nm * 4, hipMemcpyDeviceToHost));
-        OGG_HIP_CHECK(hipMemcpy(src_target, st, (size_t)nm * 4, hipMemcpyDeviceToHost));
-        OGG_HIP_CHECK(hipMemcpy(src_d2, sd, (size_t)nm * 8, hipMemcpyDeviceToHost));
+        if (int e = bufs.get(src_cell, sc, (size_t)nm)) return e;
+        if (int e = bufs.get(src_target, st, (size_t)nm)) return e;
+        if (int e = bufs.get(src_d2, sd, (size_t)nm)) return e;
     }
     return OGG_OK;
 }

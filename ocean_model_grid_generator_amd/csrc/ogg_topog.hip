@@ -454,8 +454,7 @@ int band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* work
     const long rows = out_rows(b);
     if (rows == 0) return OGG_OK;
     OGG_REQUIRE(b.x && b.y && b.x_next && b.y_next && out, OGG_EARG, "ogg_topog_band: null x / y / x_next / y_next / out");
-    OGG_REQUIRE(workspace && workspace_bytes >= ogg_topog_workspace_bytes(), OGG_EARG, "ogg_topog_band: workspace of %ld bytes, %ld needed",
-                workspace_bytes, ogg_topog_workspace_bytes());
+    if (int e = ogg::check_workspace("ogg_topog_band", workspace, workspace_bytes, ogg_topog_workspace_bytes())) return e;
     const ogg_topog_source& q = *src;
     const int shift = b.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0;
     Geo g{b.x, b.y, b.x_next, b.y_next, b.nx, b.nx + 1, b.j0, b.n_cell_rows, b.j0 >> shift, b.nx >> shift, 0, shift, b.refine,
@@ -533,42 +532,41 @@ int topog_host(const ogg_topog_band* band, const ogg_topog_source* src, void* ou
     ogg::Buffers bufs;   // freed on every exit path
     const long nxp = h.nx + 1, n = h.n_cell_rows;
     ogg_topog_band d = h;
-    void *px = nullptr, *py = nullptr;
-    if (int e = bufs.alloc(&px, (size_t)(n + 1) * nxp * sizeof(double))) return e;
-    if (int e = bufs.alloc(&py, (size_t)(n + 1) * nxp * sizeof(double))) return e;
-    const size_t body = (size_t)n * nxp * sizeof(double), row = (size_t)nxp * sizeof(double);
-    OGG_HIP_CHECK(hipMemcpy(px, h.x, body, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(py, h.y, body, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(static_cast<char*>(px) + body, h.x_next ? h.x_next : h.x + n * nxp, row, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(static_cast<char*>(py) + body, h.y_next ? h.y_next : h.y + n * nxp, row, hipMemcpyHostToDevice));
-    d.x = static_cast<const double*>(px), d.y = static_cast<const double*>(py);
+    double *px, *py;
+    if (int e = bufs.alloc(&px, (size_t)(n + 1) * nxp)) return e;
+    if (int e = bufs.alloc(&py, (size_t)(n + 1) * nxp)) return e;
+    const size_t body = (size_t)n * nxp, row = (size_t)nxp;   // doubles
+    if (int e = bufs.send(px, h.x, body)) return e;
+    if (int e = bufs.send(py, h.y, body)) return e;
+    if (int e = bufs.send(px + body, h.x_next ? h.x_next : h.x + n * nxp, row)) return e;
+    if (int e = bufs.send(py + body, h.y_next ? h.y_next : h.y + n * nxp, row)) return e;
+    d.x = px, d.y = py;
     d.x_next = d.x + n * nxp, d.y_next = d.y + n * nxp;
     const ogg_topog_source& hs = *src;
     ogg_topog_source ds = hs;
     const long nsrc = hs.Nx * hs.Ny;
     const size_t esize = hs.dtype == OGG_TOPOG_INT16 ? 2 : (hs.dtype == OGG_TOPOG_FLOAT64 ? 8 : 4);
-    void* raw = nullptr;
-    if (int e = bufs.alloc(&raw, (size_t)nsrc * esize)) return e;
-    OGG_HIP_CHECK(hipMemcpy(raw, hs.data, (size_t)nsrc * esize, hipMemcpyHostToDevice));
+    char* raw;
+    if (int e = bufs.put(&raw, static_cast<const char*>(hs.data), (size_t)nsrc * esize)) return e;
     ds.data = raw;
     if (hs.dtype == OGG_TOPOG_FLOAT32 || hs.dtype == OGG_TOPOG_FLOAT64) {
-        void *qd = nullptr, *bad = nullptr;
-        if (int e = bufs.alloc(&qd, (size_t)nsrc * sizeof(int))) return e;
-        if (int e = bufs.alloc(&bad, sizeof(int))) return e;
-        if (int e = ogg_topog_quantize_dev(&ds, static_cast<int*>(qd), static_cast<int*>(bad), nullptr)) return e;
+        int *qd, *bad;
+        if (int e = bufs.alloc(&qd, (size_t)nsrc)) return e;
+        if (int e = bufs.alloc(&bad, 1)) return e;
+        if (int e = ogg_topog_quantize_dev(&ds, qd, bad, nullptr)) return e;
         int nb = 0;
-        OGG_HIP_CHECK(hipMemcpy(&nb, bad, sizeof(int), hipMemcpyDeviceToHost));
+        if (int e = bufs.get(&nb, bad, 1)) return e;
         OGG_REQUIRE(nb == 0, OGG_EARG, "ogg_topog: a quantised source value exceeds %d in magnitude (quantum %g too small)", OGG_TOPOG_MAX_Q,
                     hs.quantum);
         ds.data = qd, ds.dtype = OGG_TOPOG_INT32, ds.n_fill = 0;
     }
     const long nrec = rows * (h.nx >> (h.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0));
-    void *ws = nullptr, *res = nullptr;
+    char *ws, *res;
     if (int e = bufs.alloc(&ws, (size_t)ogg_topog_workspace_bytes())) return e;
     const size_t rec_bytes = plane ? sizeof(ogg_topog_plane_record) : sizeof(ogg_topog_record);
     if (int e = bufs.alloc(&res, (size_t)nrec * rec_bytes)) return e;
     if (int e = band_dev(&d, &ds, ws, ogg_topog_workspace_bytes(), res, nullptr, plane)) return e;
-    OGG_HIP_CHECK(hipMemcpy(out, res, (size_t)nrec * rec_bytes, hipMemcpyDeviceToHost));
+    if (int e = bufs.get(static_cast<char*>(out), res, (size_t)nrec * rec_bytes)) return e;
     return OGG_OK;
 }
 

@@ -424,23 +424,28 @@ long end_row(const ogg_xgrid_band& b) { return (b.j0 + b.n_cell_rows + 1) / 2; }
 long out_rows(const ogg_xgrid_band& b) { return std::max(0L, end_row(b) - first_row(b)); }
 long next_rows(const ogg_xgrid_band& b) { return out_rows(b) > 0 ? 2 * end_row(b) - (b.j0 + b.n_cell_rows) + 1 : 0; }
 long n_waves(const ogg_xgrid_band& b) { return (out_rows(b) * (b.nx / 2) + TT - 1) / TT; }
-long round64(long v) { return (v + 63) / 64 * 64; }
-long ws_bytes(const ogg_xgrid_band& b, const ogg_xgrid_atm& a) { return WS_HEAD + round64((a.NB + 1) * 8) + 2 * round64(n_waves(b) * 8); }
 
+// workspace: head (the total) | dsin (NB + 1 doubles) | kept per wave | offsets per wave; sections rounded to 64 bytes
 struct Layout {
     long long* total;
     double* dsin;
     long long *kept, *off;
 };
 
+struct Offsets {
+    long dsin, kept, off, total;
+};
+
+Offsets offsets(const ogg_xgrid_band& b, const ogg_xgrid_atm& a) {
+    ogg::Sections s{WS_HEAD, 64};
+    return Offsets{s.take((a.NB + 1) * 8), s.take(n_waves(b) * 8), s.take(n_waves(b) * 8), s.off};   // evaluated left to right
+}
+
+long ws_bytes(const ogg_xgrid_band& b, const ogg_xgrid_atm& a) { return offsets(b, a).total; }
+
 Layout layout(void* ws, const ogg_xgrid_band& b, const ogg_xgrid_atm& a) {
-    char* p = static_cast<char*>(ws);
-    Layout l;
-    l.total = reinterpret_cast<long long*>(p);
-    l.dsin = reinterpret_cast<double*>(p + WS_HEAD);
-    l.kept = reinterpret_cast<long long*>(p + WS_HEAD + round64((a.NB + 1) * 8));
-    l.off = l.kept + round64(n_waves(b) * 8) / 8;
-    return l;
+    const Offsets o = offsets(b, a);
+    return Layout{ogg::at<long long>(ws, 0), ogg::at<double>(ws, o.dsin), ogg::at<long long>(ws, o.kept), ogg::at<long long>(ws, o.off)};
 }
 
 int check_dev_args(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, const void* workspace, long workspace_bytes) {
@@ -449,9 +454,7 @@ int check_dev_args(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, const v
     if (int e = check_atm_shape(*atm)) return e;
     if (out_rows(*band) > 0)
         OGG_REQUIRE(band->x && band->y && band->x_next && band->y_next, OGG_EARG, "ogg_xgrid_band: null x / y / x_next / y_next");
-    OGG_REQUIRE(workspace && workspace_bytes >= ws_bytes(*band, *atm), OGG_EARG, "ogg_xgrid: workspace of %ld bytes, %ld needed",
-                workspace_bytes, ws_bytes(*band, *atm));
-    return OGG_OK;
+    return ogg::check_workspace("ogg_xgrid", workspace, workspace_bytes, ws_bytes(*band, *atm));
 }
 
 Geo make_geo(const ogg_xgrid_band& b) {
@@ -537,46 +540,47 @@ extern "C" int ogg_xgrid(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, l
     OGG_REQUIRE(h.x && h.y && a_poly, OGG_EARG, "ogg_xgrid: null x / y / a_poly");
     ogg::Buffers bufs;   // freed on every exit path
     const long nxp = h.nx + 1, n = h.n_cell_rows, nn = next_rows(h);
-    const size_t body = (size_t)n * nxp * sizeof(double), tail = (size_t)nn * nxp * sizeof(double);
-    void *px = nullptr, *py = nullptr, *pm = nullptr, *pa = nullptr, *pb = nullptr, *ws = nullptr, *ap = nullptr, *ct = nullptr;
+    const size_t body = (size_t)n * nxp, tail = (size_t)nn * nxp;   // doubles
+    double *px, *py, *pa, *pb, *ap, *la;
+    unsigned char* pm;
+    char* ws;
+    int *li, *lo;
+    ogg_xgrid_counts* ct;
     if (int e = bufs.alloc(&px, body + tail)) return e;
     if (int e = bufs.alloc(&py, body + tail)) return e;
-    OGG_HIP_CHECK(hipMemcpy(px, h.x, body, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(py, h.y, body, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(static_cast<char*>(px) + body, h.x_next ? h.x_next : h.x + n * nxp, tail, hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(static_cast<char*>(py) + body, h.y_next ? h.y_next : h.y + n * nxp, tail, hipMemcpyHostToDevice));
+    if (int e = bufs.send(px, h.x, body)) return e;
+    if (int e = bufs.send(py, h.y, body)) return e;
+    if (int e = bufs.send(px + body, h.x_next ? h.x_next : h.x + n * nxp, tail)) return e;
+    if (int e = bufs.send(py + body, h.y_next ? h.y_next : h.y + n * nxp, tail)) return e;
     ogg_xgrid_band d = h;
-    d.x = static_cast<const double*>(px), d.y = static_cast<const double*>(py);
+    d.x = px, d.y = py;
     d.x_next = d.x + n * nxp, d.y_next = d.y + n * nxp;
     if (h.mask) {
-        if (int e = bufs.alloc(&pm, (size_t)nc)) return e;
-        OGG_HIP_CHECK(hipMemcpy(pm, h.mask, (size_t)nc, hipMemcpyHostToDevice));
-        d.mask = static_cast<const unsigned char*>(pm);
+        if (int e = bufs.put(&pm, h.mask, (size_t)nc)) return e;
+        d.mask = pm;
     }
-    if (int e = bufs.alloc(&pa, (size_t)(atm->NA + 1) * sizeof(double))) return e;
-    if (int e = bufs.alloc(&pb, (size_t)(atm->NB + 1) * sizeof(double))) return e;
-    OGG_HIP_CHECK(hipMemcpy(pa, atm->lon, (size_t)(atm->NA + 1) * sizeof(double), hipMemcpyHostToDevice));
-    OGG_HIP_CHECK(hipMemcpy(pb, atm->lat, (size_t)(atm->NB + 1) * sizeof(double), hipMemcpyHostToDevice));
-    const ogg_xgrid_atm da{static_cast<const double*>(pa), static_cast<const double*>(pb), atm->NA, atm->NB};
+    if (int e = bufs.alloc(&pa, (size_t)atm->NA + 1)) return e;
+    if (int e = bufs.alloc(&pb, (size_t)atm->NB + 1)) return e;
+    if (int e = bufs.send(pa, atm->lon, (size_t)atm->NA + 1)) return e;
+    if (int e = bufs.send(pb, atm->lat, (size_t)atm->NB + 1)) return e;
+    const ogg_xgrid_atm da{pa, pb, atm->NA, atm->NB};
     const long wsb = ws_bytes(d, da);
     if (int e = bufs.alloc(&ws, (size_t)wsb)) return e;
-    if (int e = bufs.alloc(&ap, (size_t)nc * sizeof(double))) return e;
-    if (int e = bufs.alloc(&ct, sizeof(ogg_xgrid_counts))) return e;
-    if (int e = ogg_xgrid_count_dev(&d, &da, ws, wsb, static_cast<double*>(ap), static_cast<ogg_xgrid_counts*>(ct), nullptr)) return e;
-    OGG_HIP_CHECK(hipMemcpy(counts, ct, sizeof(ogg_xgrid_counts), hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(a_poly, ap, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (int e = bufs.alloc(&ap, (size_t)nc)) return e;
+    if (int e = bufs.alloc(&ct, 1)) return e;
+    if (int e = ogg_xgrid_count_dev(&d, &da, ws, wsb, ap, ct, nullptr)) return e;
+    if (int e = bufs.get(counts, ct, 1)) return e;
+    if (int e = bufs.get(a_poly, ap, (size_t)nc)) return e;
     const long long kept = counts->kept;
     OGG_REQUIRE(kept <= capacity, OGG_ESHAPE, "ogg_xgrid: %lld exchange cells, capacity %ld", kept, capacity);
     if (kept == 0) return OGG_OK;
     OGG_REQUIRE(atm_ij && ocn_ij && area, OGG_EARG, "ogg_xgrid: null atm_ij / ocn_ij / area");
-    void *li = nullptr, *lo = nullptr, *la = nullptr;
-    if (int e = bufs.alloc(&li, (size_t)kept * 2 * sizeof(int))) return e;
-    if (int e = bufs.alloc(&lo, (size_t)kept * 2 * sizeof(int))) return e;
-    if (int e = bufs.alloc(&la, (size_t)kept * sizeof(double))) return e;
-    if (int e = ogg_xgrid_write_dev(&d, &da, ws, wsb, static_cast<int*>(li), static_cast<int*>(lo), static_cast<double*>(la), nullptr))
-        return e;
-    OGG_HIP_CHECK(hipMemcpy(atm_ij, li, (size_t)kept * 2 * sizeof(int), hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(ocn_ij, lo, (size_t)kept * 2 * sizeof(int), hipMemcpyDeviceToHost));
-    OGG_HIP_CHECK(hipMemcpy(area, la, (size_t)kept * sizeof(double), hipMemcpyDeviceToHost));
+    if (int e = bufs.alloc(&li, (size_t)kept * 2)) return e;
+    if (int e = bufs.alloc(&lo, (size_t)kept * 2)) return e;
+    if (int e = bufs.alloc(&la, (size_t)kept)) return e;
+    if (int e = ogg_xgrid_write_dev(&d, &da, ws, wsb, li, lo, la, nullptr)) return e;
+    if (int e = bufs.get(atm_ij, li, (size_t)kept * 2)) return e;
+    if (int e = bufs.get(ocn_ij, lo, (size_t)kept * 2)) return e;
+    if (int e = bufs.get(area, la, (size_t)kept)) return e;
     return OGG_OK;
 }

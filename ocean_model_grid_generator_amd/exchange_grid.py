@@ -38,9 +38,7 @@ def atm_edges(lon_edges, lat_edges):
     lon, lat = L.as_f64(lon_edges).reshape(-1), L.as_f64(lat_edges).reshape(-1)
     if lon.size < 2 or lat.size < 2:
         raise ValueError("exchange grid: the atmosphere needs at least two lon and two lat edges")
-    d = L.XgridAtm(lon=lon.ctypes.data, lat=lat.ctypes.data, NA=lon.size - 1, NB=lat.size - 1)
-    if L.load().ogg_xgrid_check_atm(ctypes.byref(d)) != L.OGG_OK:
-        raise ValueError(L.load().ogg_last_error().decode())
+    L.checked("ogg_xgrid_check_atm", L.XgridAtm(lon=lon.ctypes.data, lat=lat.ctypes.data, NA=lon.size - 1, NB=lat.size - 1))
     return lon, lat
 
 
@@ -59,7 +57,7 @@ def check_args(threshold, Re):
 
 
 def counts_dict(c):
-    return {f: int(getattr(c, f)) for f in L.XGRID_COUNT_FIELDS}
+    return L.counts_dict(L.XGRID_COUNT_FIELDS, c)
 
 
 # ---- results ---------------------------------------------------------------------------------------------------

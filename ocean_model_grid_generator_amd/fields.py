@@ -54,6 +54,21 @@ def cell_mask(mask, shape, who):
     return m
 
 
+def wet_mask(wet, shape, who):
+    """the wet mask an analysis needs, as cell_mask gives it; ``who``: the analysis, in front of the refusal"""
+    if wet is None:
+        raise ValueError("%s: a wet mask is needed (depth > 0 of a topography or mask != 0 of an ocean mask)" % who)
+    return cell_mask(wet, shape, "%s: the wet mask" % who)
+
+
+def resolve_topology(periodic, fold, detect):
+    """(periodic, fold) as booleans; what the caller left None comes from detect()"""
+    if periodic is None or fold is None:
+        p, f = detect()
+        periodic, fold = (p if periodic is None else periodic), (f if fold is None else fold)
+    return bool(periodic), bool(fold)
+
+
 # ---- reading ---------------------------------------------------------------------------------------------------
 def _num(atts, key):
     v = atts.get(key)

@@ -62,13 +62,11 @@ def params(shape, lon, lat, field=None, normalize="area"):
         p.fill[k] = float(f)
     if field is not None and tuple(field.data.shape[-2:]) != tuple(shape):
         raise ValueError("regrid: the field is %s, the model cells %s" % (field.data.shape[-2:], tuple(shape)))
-    if L.load().ogg_regrid_check(ctypes.byref(p)) != L.OGG_OK:
-        raise ValueError(L.load().ogg_last_error().decode())
-    return p
+    return L.checked("ogg_regrid_check", p)
 
 
 def counts_dict(c):
-    return {f: int(c[k]) for k, f in enumerate(L.REGRID_COUNT_FIELDS)}
+    return L.counts_dict(L.REGRID_COUNT_FIELDS, c)
 
 
 def result(values, cover, frac, n_entries, counts, field, lon, lat, a_atm, normalize, masked, cell_weight=None):
@@ -136,7 +134,7 @@ def regrid_to_latlon(x, y, field, lon_edges, lat_edges, mask=None, normalize="ar
     L.call("ogg_regrid", ctypes.byref(p), None if field is None else field.records.ctypes.data, atm.ctypes.data, ocn.ctypes.data,
            area.ctypes.data, area.size, a_atm.ctypes.data, None if values is None else values.ctypes.data,
            None if cv is None else cv.ctypes.data, frac.ctypes.data, nent.ctypes.data, ctypes.byref(counts))
-    c = {f: int(getattr(counts, f)) for f in L.REGRID_COUNT_FIELDS}
+    c = counts_dict(counts)
     res = result(values, cv, frac, nent, c, field, lon, lat, a_atm, normalize, mask is not None,
                  None if field is None else _cell_weight(ocn, area, shape))
     if not cover:

@@ -78,9 +78,7 @@ def params(ny, nx, periodic, fold, min_depth=0.0, mode="mask", keep_min_cells=0,
         raise ValueError("ocean mask: mode must be 'mask' or 'deepen', not %r" % (mode,))
     p = L.MaskParams(ny=int(ny), nx=int(nx), topology=topology_flags(periodic, fold), mode=MODES[mode], fill=float(fill),
                      min_depth=float(min_depth), keep_min_cells=int(keep_min_cells))
-    if L.load().ogg_mask_check(ctypes.byref(p)) != L.OGG_OK:
-        raise ValueError(L.load().ogg_last_error().decode())
-    return p
+    return L.checked("ogg_mask_check", p)
 
 
 def _seeds(seeds):
@@ -157,7 +155,7 @@ def ocean_mask(depth, x, y, min_depth=0.0, mode="mask", seeds=(), keep_min_cells
     counts = L.MaskCounts()
     L.call("ogg_ocean_mask", ctypes.byref(p), d.ctypes.data, L.ptr(xc), L.ptr(yc), int(s.shape[0]), s.ctypes.data if s.shape[0] else None,
            out.ctypes.data, wet.ctypes.data, root.ctypes.data, cells.ctypes.data, comps.ctypes.data, cap, ctypes.byref(counts))
-    cdict = {f: int(getattr(counts, f)) for f in L.MASK_COUNT_FIELDS}
+    cdict = L.counts_dict(L.MASK_COUNT_FIELDS, counts)
     comps = comps[:cdict["components"]]
     kept = _kept_roots(root, cells[:s.shape[0]], cdict, s.shape[0])
     return result(out, wet, root, cdict, comps, kept, cells[:s.shape[0]], s, x, y, stride, periodic, fold, min_depth, mode, keep_min_cells)
@@ -204,8 +202,7 @@ def ocean_mask_dev(depth, x, y, min_depth=0.0, mode="mask", seeds=(), keep_min_c
         so = torch.empty(2 * s.shape[0], dtype=torch.int64, device=dev)
         L.call("ogg_mask_seed_dev", ctypes.byref(p), x.data_ptr(), y.data_ptr(), x.shape[1], int(s.shape[0]), ll.data_ptr(), so.data_ptr(), st)
         cells = so.cpu().numpy()[1::2].copy()
-    c = counts.cpu().numpy()
-    cdict = {f: int(c[k]) for k, f in enumerate(L.MASK_COUNT_FIELDS)}
+    cdict = L.counts_dict(L.MASK_COUNT_FIELDS, counts)
     seed_roots = root.view(-1)[torch.from_numpy(cells).to(dev)].cpu().numpy() if cells.size else np.zeros(0, np.int32)
     for k in range(cells.size):
         if seed_roots[k] < 0:
@@ -218,8 +215,7 @@ def ocean_mask_dev(depth, x, y, min_depth=0.0, mode="mask", seeds=(), keep_min_c
     wet = torch.empty((ny, nx), dtype=torch.uint8, device=dev)
     L.call("ogg_mask_apply_dev", ctypes.byref(p), depth.data_ptr(), root.data_ptr(), ws.data_ptr(), wsb, kt.data_ptr(), len(kept),
            out.data_ptr(), wet.data_ptr(), counts.data_ptr(), st)
-    c = counts.cpu().numpy()
-    cdict = {f: int(c[k]) for k, f in enumerate(L.MASK_COUNT_FIELDS)}
+    cdict = L.counts_dict(L.MASK_COUNT_FIELDS, counts)
     comp = np.sort(comps[:cdict["components"]].cpu().numpy())[::-1]
     return result(out.cpu().numpy(), wet.cpu().numpy(), root.cpu().numpy(), cdict, comp, kept, cells, s, x, y, stride, periodic, fold,
                   min_depth, mode, keep_min_cells)

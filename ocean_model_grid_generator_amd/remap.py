@@ -112,13 +112,11 @@ def params(ny, nx, source, m0=0, periodic=False, fold=False, fill_max=None):
         p.fill[k] = float(f)
     if fill_max is not None and int(fill_max) < 0:
         raise ValueError("remap: fill_max must be >= 0 (%r)" % (fill_max,))
-    if L.load().ogg_remap_check(ctypes.byref(p)) != L.OGG_OK:
-        raise ValueError(L.load().ogg_last_error().decode())
-    return p
+    return L.checked("ogg_remap_check", p)
 
 
 def counts_dict(c):
-    return {f: int(c[k]) for k, f in enumerate(L.REMAP_COUNT_FIELDS)}
+    return L.counts_dict(L.REMAP_COUNT_FIELDS, c)
 
 
 def result(values, flags, counts, source, periodic, fold, fill, fill_max, masked):
@@ -158,7 +156,7 @@ def remap(x, y, source, lon_edges=None, lat_edges=None, mask=None, fill=True, fi
     atm, ocn, area = (np.ascontiguousarray(lists[k]) for k in ("atm", "ocn", "area"))
     L.call("ogg_remap", ctypes.byref(p), source.records.ctypes.data, atm.ctypes.data, ocn.ctypes.data, area.ctypes.data, area.size,
            None if m is None else m.ctypes.data, 1 if fill else 0, values.ctypes.data, flags.ctypes.data, ctypes.byref(counts))
-    c = {f: int(getattr(counts, f)) for f in L.REMAP_COUNT_FIELDS}
+    c = counts_dict(counts)
     rs = (source.nrec,) + shape
     return result(values.reshape(rs), flags[:npair].reshape(rs), c, source, periodic, fold, fill, fill_max, m is not None)
 

@@ -47,15 +47,11 @@ def params(ny, nx, source, targets="coast", periodic=False, fold=False, Re=X.DEF
                        targets=TARGETS[targets], Re=float(Re))
     for k, f in enumerate(source.fill):
         p.fill[k] = float(f)
-    if L.load().ogg_runoff_check(ctypes.byref(p)) != L.OGG_OK:
-        raise ValueError(L.load().ogg_last_error().decode())
-    return p
+    return L.checked("ogg_runoff_check", p)
 
 
 def _wet(wet, shape):
-    if wet is None:
-        raise ValueError("runoff: a wet mask is needed (depth > 0 of a topography or mask != 0 of an ocean mask)")
-    return F.cell_mask(wet, shape, "runoff: the wet mask")
+    return F.wet_mask(wet, shape, "runoff")
 
 
 def cell_area(area):
@@ -141,7 +137,7 @@ def runoff(x, y, area, source, wet, targets="coast", lon_edges=None, lat_edges=N
     rc = lib.ogg_runoff(ctypes.byref(p), x.ctypes.data, y.ctypes.data, area.ctypes.data, m.ctypes.data, source.records.ctypes.data,
                         source.lon.ctypes.data, source.lat.ctypes.data, values.ctypes.data, nsrc.ctypes.data, sc.ctypes.data, st.ctypes.data,
                         sd.ctypes.data, ctypes.byref(c))
-    counts = {f: int(getattr(c, f)) for f in L.RUNOFF_COUNT_FIELDS}
+    counts = L.counts_dict(L.RUNOFF_COUNT_FIELDS, c)
     if rc != L.OGG_OK:
         _check_targets(counts, targets)
         raise L.OggHipError(rc, lib.ogg_last_error().decode())
@@ -196,7 +192,7 @@ def runoff_dev(x, y, area, source, wet, targets="coast", Re=X.DEFAULT_RE, keep_l
     L.call("ogg_runoff_segments_dev", ctypes.byref(p), sdst.data_ptr(), nm, ws.data_ptr(), wsb, st)
     L.call("ogg_runoff_accumulate_dev", ctypes.byref(p), f.data_ptr(), sc.data_ptr(), nm, area.data_ptr(), nxp - 1, ws.data_ptr(), wsb,
            values.data_ptr(), nsrc.data_ptr(), counts.data_ptr(), st)
-    cd = {k: int(v) for k, v in zip(L.RUNOFF_COUNT_FIELDS, counts.cpu().numpy())}
+    cd = L.counts_dict(L.RUNOFF_COUNT_FIELDS, counts)
     lists = None
     if keep_lists:
         lists = {"tgt_cell": tc[:nt].cpu().numpy(), "tgt_u": tu[:nt].cpu().numpy(), "src_u": su[:nm].cpu().numpy(), "ds": ds.cpu().numpy()}
