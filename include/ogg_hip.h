@@ -78,7 +78,9 @@ const char* ogg_version(void);
 #define OGG_ABI_BASIN_RULE 25
 #define OGG_ABI_BASIN_RULE_RECORD 26
 #define OGG_ABI_BASIN_COUNTS 27
-#define OGG_ABI_N 28
+#define OGG_ABI_XGRID_CS_ATM 28
+#define OGG_ABI_XGRID_CS_COUNTS 29
+#define OGG_ABI_N 30
 long ogg_abi_sizeof(int which);
 int ogg_device_count(int* count);
 int ogg_set_device(int device);
@@ -746,6 +748,77 @@ int ogg_xgrid_write_dev(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, co
  * a_poly filled: call again with that capacity). */
 int ogg_xgrid(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, long capacity, int* atm_ij, int* ocn_ij, double* area,
               double* a_poly, ogg_xgrid_counts* counts);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Exchange grid with a cubed-sphere atmosphere (an addition: the reference has none).  First-order conservative overlaps of a gnomonic
+ * cubed-sphere atmosphere (six faces of N x N cells) with the MOM6 h-cells of the STITCHED supergrid (an ogg_xgrid_band, as above).
+ * All arithmetic is fp64 without fused multiply-add.
+ * Atmosphere: a table t_0 < .. < t_N with t_0 = -1 and t_N = 1 exactly, 1 <= N <= 4096, the same on both axes and on all six faces,
+ * and six frames F_f = (e_u, e_v, e_n)_f, f = 0 .. 5, rows of a 3 x 3 matrix.  Cell (f, J, I) is the set of unit vectors P with
+ * P.e_n > 0, xi = P.e_u / P.e_n in [t_I, t_I+1] and eta = P.e_v / P.e_n in [t_J, t_J+1].  ogg_xgrid_cs_check_atm (HOST pointers, no
+ * device work) returns OGG_EARG unless the table is strictly increasing with those ends, every frame is orthonormal and right-handed
+ * (e_u x e_v = e_n) within 1e-12, the six normals are pairwise orthogonal or opposite within 1e-12, and every e_u, e_v is +- some
+ * face's normal within 1e-12: together these make the frames a cube in any rotation.
+ * Ocean cell (m, n): corners C0 .. C3 as above.
+ *   vectors   P_k = (cos phi cos lam, cos phi sin lam, sin phi), lam = mod360(x_k) * D, phi = y_k * D, D = pi / 180 (one fp64
+ *             constant), mod360 with numpy's % semantics: exact, so a grid stated whole turns away gives the same bits.  There is no
+ *             pole substitution: a pole corner is a point like any other, and two pole corners make a triangle.
+ *   edges     great circles (FMS's rule whenever one side of the exchange is a cubed sphere), NOT straight in (lambda, phi) as in
+ *             the lat-lon section above
+ *   skipped   a cell with a non-finite corner is DEGENERATE; a cell with two corners more than 30 degrees apart (P_i . P_j <
+ *             OGG_XGRID_CS_COS_WIDE) is WIDE (no model cell is that large; the rule lets the faces below work without homogeneous
+ *             clipping).  A_poly is NaN for both and they emit nothing.
+ *   area      A_poly = (Re * Re) * (O3(P0, P1, P2) + O3(P0, P2, P3)), O3(a, b, c) = 2 atan2(a . ((b - a) x (c - a)),
+ *             1 + a.b + b.c + c.a): the triple product over the differences, dot products summed x, y, z left to right.
+ *             A_poly <= 0: the cell is INVERTED and emits nothing.
+ *   faces     face f is a candidate of a cell when all four corners have w_k = P_k . e_n > 0.05 (necessary for overlap: a point of
+ *             a face is within 54.74 degrees of its centre and a cell is at most 30 across, so an overlapping cell has every
+ *             w >= cos 84.74 = 0.092).  The test can admit a face the polygon misses; such pairs clip to nothing.  A face and its
+ *             opposite cannot both pass it, so a cell has at most three candidate faces.  On a candidate
+ *             face the polygon is (xi_k, eta_k) = ((P_k . e_u) / w_k, (P_k . e_v) / w_k), k = 0 .. 3: great-circle edges and the
+ *             atmosphere's grid lines are both straight in this plane.
+ *   rows      every J with t_J < eta_max and t_J+1 > eta_min; columns: every I with t_I < xi_max and t_I+1 > xi_min (no shifts)
+ *   clip      the Sutherland-Hodgman of the lat-lon section word for word, xi in the place of lambda and eta in the place of phi:
+ *             xi >= t_I, xi <= t_I+1, eta >= t_J, eta <= t_J+1 in this order, inclusive inside tests, the same emission rule and
+ *             the same canonical-order crossing with the clipped coordinate set to the line's value exactly
+ *   A_x       a pair whose atmosphere cell contains all four (xi_k, eta_k), inclusive, takes A_x = A_poly (the two area formulas
+ *             round differently).  Otherwise a fan from vertex 0 of the clipped polygon v_0 .. v_n-1 (0 when n < 3):
+ *             A_x = (Re * Re) * sum_k=1..n-2 O2(v_0, v_k, v_k+1), left to right, with r = sqrt(1 + xi * xi + eta * eta),
+ *             num = ((xi_b - xi_a) * (eta_c - eta_a) - (eta_b - eta_a) * (xi_c - xi_a)) / (r_a * r_b * r_c),
+ *             d(p, q) = (xi_p * xi_q + eta_p * eta_q + 1) / (r_p * r_q), O2 = 2 atan2(num, 1 + d(a, b) + d(b, c) + d(c, a)):
+ *             the 2-D cross product of exact differences is the well-conditioned form of the triple product
+ *   keep      A_x > 0 and A_x > threshold * min(A_poly, A_atm(J, I)), A_atm(J, I) = (Re * Re) * (O2(c00, c10, c11) + O2(c00, c11,
+ *             c01)) over the cell's table corners c00 = (t_I, t_J), c10 = (t_I+1, t_J), c11, c01 = (t_I, t_J+1), the same on every
+ *             face; an optional uint8 mask (0: the cell emits nothing)
+ * Order: ocean cells row-major (m, n), then f ascending, then J, then I.  Nothing is summed across cells, so the list is bit-identical
+ * for any band split.  Counts over the band's cells: cells, degenerate, wide and inverted ignore the mask; face_candidates counts the
+ * (cell, face) pairs that pass the w test and candidates sums rows x columns over them, both over unmasked cells with A_poly > 0.
+ * ---------------------------------------------------------------------------------------------------- */
+#define OGG_XGRID_CS_COS_WIDE 0.86602540378443864676 /* cos 30 degrees */
+typedef struct ogg_xgrid_cs_atm {
+    const double* t;      /* N + 1 table entries */
+    long N;
+    double frames[6][9];  /* e_u, e_v, e_n of faces 0 .. 5 (always host memory: part of the struct) */
+} ogg_xgrid_cs_atm;
+typedef struct ogg_xgrid_cs_counts {
+    long long cells, degenerate, wide, inverted, masked, face_candidates, candidates, kept;
+} ogg_xgrid_cs_counts;
+/* of the count and write steps (it holds the N x N table of A_atm), -1 if bad */
+long ogg_xgrid_cs_workspace_bytes(const ogg_xgrid_band* band, const ogg_xgrid_cs_atm* atm);
+/* the checks of the table and the frames (HOST pointer in *atm): OGG_EARG unless they are as above */
+int ogg_xgrid_cs_check_atm(const ogg_xgrid_cs_atm* atm);
+/* count step, device pointers (band rows, mask, atm->t), on a stream: A_poly of the band's cells into a_poly, the counts into *counts
+ * (device memory), and into the workspace what the write step needs.  The frames are checked on the host; the table is not read there. */
+int ogg_xgrid_cs_count_dev(const ogg_xgrid_band* band, const ogg_xgrid_cs_atm* atm, void* workspace, long workspace_bytes,
+                           double* a_poly, ogg_xgrid_cs_counts* counts, void* stream);
+/* write step, after the count step on the same band, atmosphere and workspace: the list (counts->kept entries, device memory):
+ * atm_fij[k] = (I, J, f), ocn_ij[k] = (n, m) (0-based, m counted in the whole grid), area[k] = A_x.  The step redoes the clipping. */
+int ogg_xgrid_cs_write_dev(const ogg_xgrid_band* band, const ogg_xgrid_cs_atm* atm, const void* workspace, long workspace_bytes,
+                           int* atm_fij, int* ocn_ij, double* area, void* stream);
+/* HOST pointers throughout, staged through device memory, with the capacity protocol of ogg_xgrid (OGG_ESHAPE with *counts and a_poly
+ * filled when counts->kept > capacity: call again with that capacity). */
+int ogg_xgrid_cs(const ogg_xgrid_band* band, const ogg_xgrid_cs_atm* atm, long capacity, int* atm_fij, int* ocn_ij, double* area,
+                 double* a_poly, ogg_xgrid_cs_counts* counts);
 
 /* ------------------------------------------------------------------------------------------------------
  * Ocean mask: minimum depth and connected basins (an addition: the reference has none; GFDL's preprocessing calls this step "ice9").

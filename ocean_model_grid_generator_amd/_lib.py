@@ -119,6 +119,19 @@ class XgridCounts(ctypes.Structure):
     _fields_ = [(f, c_longlong) for f in XGRID_COUNT_FIELDS]
 
 
+class XgridCsAtm(ctypes.Structure):
+    """ogg_xgrid_cs_atm of include/ogg_hip.h"""
+    _fields_ = [("t", c_void_p), ("N", c_long), ("frames", (c_double * 9) * 6)]
+
+
+XGRID_CS_COUNT_FIELDS = ("cells", "degenerate", "wide", "inverted", "masked", "face_candidates", "candidates", "kept")
+
+
+class XgridCsCounts(ctypes.Structure):
+    """ogg_xgrid_cs_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in XGRID_CS_COUNT_FIELDS]
+
+
 class MaskParams(ctypes.Structure):
     """ogg_mask_params of include/ogg_hip.h"""
     _fields_ = [("ny", c_long), ("nx", c_long), ("topology", c_int), ("mode", c_int), ("fill", c_double), ("min_depth", c_double),
@@ -249,7 +262,8 @@ ABI_MIRRORS = {"LATLON_BAND": LatlonBand, "BIPOLAR_BAND": BipolarBand, "DPOLE_BA
                "XGRID_COUNTS": XgridCounts, "MASK_PARAMS": MaskParams, "MASK_COUNTS": MaskCounts, "REMAP_PARAMS": RemapParams,
                "REMAP_COUNTS": RemapCounts, "RUNOFF_PARAMS": RunoffParams, "RUNOFF_COUNTS": RunoffCounts, "REGRID_PARAMS": RegridParams,
                "REGRID_COUNTS": RegridCounts, "BILINEAR_PARAMS": BilinearParams, "COAST_PARAMS": CoastParams, "COAST_COUNTS": CoastCounts,
-               "BASIN_PARAMS": BasinParams, "BASIN_RULE": BASIN_RULE, "BASIN_RULE_RECORD": BASIN_RECORD, "BASIN_COUNTS": BasinCounts}
+               "BASIN_PARAMS": BasinParams, "BASIN_RULE": BASIN_RULE, "BASIN_RULE_RECORD": BASIN_RECORD, "BASIN_COUNTS": BasinCounts,
+               "XGRID_CS_ATM": XgridCsAtm, "XGRID_CS_COUNTS": XgridCsCounts}
 ABI = {name: code for code, name in enumerate(ABI_MIRRORS)}
 
 
@@ -351,6 +365,12 @@ SIGNATURES = {
                             c_void_p],
     "ogg_xgrid": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_long, c_void_p, c_void_p, c_void_p, c_void_p,
                   ctypes.POINTER(XgridCounts)],
+    "ogg_xgrid_cs_check_atm": [ctypes.POINTER(XgridCsAtm)],
+    "ogg_xgrid_cs_count_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCsAtm), c_void_p, c_long, c_void_p, c_void_p, c_void_p],
+    "ogg_xgrid_cs_write_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCsAtm), c_void_p, c_long, c_void_p, c_void_p, c_void_p,
+                               c_void_p],
+    "ogg_xgrid_cs": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCsAtm), c_long, c_void_p, c_void_p, c_void_p, c_void_p,
+                     ctypes.POINTER(XgridCsCounts)],
     "ogg_mask_check": [ctypes.POINTER(MaskParams)],
     "ogg_mask_label_dev": [ctypes.POINTER(MaskParams), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_mask_seed_dev": [ctypes.POINTER(MaskParams), c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p],
@@ -425,6 +445,7 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_xgrid_band_out_rows": [ctypes.POINTER(XgridBand)],
                 "ogg_xgrid_band_next_rows": [ctypes.POINTER(XgridBand)],
                 "ogg_xgrid_workspace_bytes": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm)],
+                "ogg_xgrid_cs_workspace_bytes": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCsAtm)],
                 "ogg_mask_workspace_bytes": [ctypes.POINTER(MaskParams)],
                 "ogg_remap_workspace_bytes": [ctypes.POINTER(RemapParams)],
                 "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],

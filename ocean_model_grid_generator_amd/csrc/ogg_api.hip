@@ -226,6 +226,8 @@ long ogg_abi_sizeof(int which) {
         case OGG_ABI_BASIN_RULE: return (long)sizeof(ogg_basin_rule);
         case OGG_ABI_BASIN_RULE_RECORD: return (long)sizeof(ogg_basin_rule_record);
         case OGG_ABI_BASIN_COUNTS: return (long)sizeof(ogg_basin_counts);
+        case OGG_ABI_XGRID_CS_ATM: return (long)sizeof(ogg_xgrid_cs_atm);
+        case OGG_ABI_XGRID_CS_COUNTS: return (long)sizeof(ogg_xgrid_cs_counts);
         default: return -1L;
     }
 }

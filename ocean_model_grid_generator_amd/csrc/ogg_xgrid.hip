@@ -15,60 +15,26 @@
 #include <cmath>
 #include <vector>
 
-#include "ogg_common.h"
-#include "ogg_math.h"
+#include "ogg_clip.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int TT = 64;                    // threads per workgroup: one wavefront
+using namespace ogg::xg;
+
 constexpr int PV = 6;                     // polygon vertices at most: two runs of one pole corner
-constexpr int SCAN_T = 1024;
-constexpr double D2R = 3.14159265358979323846 / 180.0;
-constexpr long WS_HEAD = 64;              // workspace: total kept (int64), sin(b_J+1 D) - sin(b_J D), kept per wavefront, offsets
 
 enum { ST_OK = 0, ST_DEGENERATE = 1, ST_POLE = 2, ST_INVERTED = 3 };
-
-struct Geo {
-    const double *x, *y, *xn, *yn;
-    const unsigned char* mask;
-    long nxp, nxo, j0, n, m0, ncells;
-    double Re2, thr;
-};
 
 struct AtmD {
     const double *a, *b, *dsin;
     long NA, NB;
 };
 
-// x mod 360 with numpy's % semantics (as ogg_topog.hip)
-OGG_DEV double mod360(double x) {
-    double m = fmod(x, 360.0);
-    if (m != 0.0) {
-        if (m < 0.0) m += 360.0;
-    } else {
-        m = 0.0;
-    }
-    return m;
-}
-
 OGG_DEV double wrap180(double d) { return mod360(d + 180.0) - 180.0; }
 
 OGG_DEV long floor_div(long u, long n) { return u >= 0 ? u / n : -((-u + n - 1) / n); }
-
-// first k in [lo, hi) with pred(k) (pred false .. true over the range), hi when none
-template <typename P>
-OGG_DEV long lower_bound(long lo, long hi, P pred) {
-    while (lo < hi) {
-        const long mid = lo + (hi - lo) / 2;
-        if (pred(mid))
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    return lo;
-}
 
 // E(h) = 1 - sin(h) / h
 OGG_DEV double efun(double h) {
@@ -92,18 +58,17 @@ OGG_DEV double gfun(double p1, double p2, double pr) {
 struct AreaAcc {
     double l0, p0, lk, pk, s;
     int n;
-};
-
-OGG_DEV void area_push(AreaAcc& a, double l, double p) {
-    const double ln = l * D2R, pn = p * D2R;
-    if (a.n == 0) {
-        a.l0 = ln, a.p0 = pn, a.s = 0.0;
-    } else {
-        const double dl = ln - a.lk;
-        if (dl != 0.0) a.s = a.s + dl * gfun(a.pk, pn, a.p0);
+    OGG_DEV void push(double l, double p) {
+        const double ln = l * D2R, pn = p * D2R;
+        if (n == 0) {
+            l0 = ln, p0 = pn, s = 0.0;
+        } else {
+            const double dl = ln - lk;
+            if (dl != 0.0) s = s + dl * gfun(pk, pn, p0);
+        }
+        lk = ln, pk = pn, ++n;
     }
-    a.lk = ln, a.pk = pn, ++a.n;
-}
+};
 
 OGG_DEV double area_close(AreaAcc& a, double Re2) {
     if (a.n == 0) return 0.0;
@@ -112,89 +77,9 @@ OGG_DEV double area_close(AreaAcc& a, double Re2) {
     return -Re2 * a.s;
 }
 
-// Sutherland-Hodgman against S: 0 lam >= c, 1 lam <= c, 2 phi >= c, 3 phi <= c, the four passes chained: every vertex a pass emits
-// goes straight into the next pass, and the last pass's into the area, all in registers.  A pass emits its first vertex when inside,
-// then for each edge (v_k, v_k+1) its crossing (ends on two sides) and v_k+1 when inside; the closing edge gives its crossing only.
-template <int S>
-OGG_DEV bool inside(double l, double p, double c) {
-    return S == 0 ? l >= c : (S == 1 ? l <= c : (S == 2 ? p >= c : p <= c));
-}
-
-template <int S>
-OGG_DEV void crossing(double al, double ap, double bl, double bp, double c, double& ol, double& op) {
-    if (S < 2) {   // the edge's ends in canonical order (lam, phi)
-        const bool fwd = al < bl || (al == bl && ap <= bp);
-        const double le = fwd ? al : bl, pe = fwd ? ap : bp, lf = fwd ? bl : al, pf = fwd ? bp : ap;
-        ol = c, op = pe + (c - le) * ((pf - pe) / (lf - le));
-    } else {       // (phi, lam)
-        const bool fwd = ap < bp || (ap == bp && al <= bl);
-        const double le = fwd ? al : bl, pe = fwd ? ap : bp, lf = fwd ? bl : al, pf = fwd ? bp : ap;
-        ol = le + (c - pe) * ((lf - le) / (pf - pe)), op = c;
-    }
-}
-
-struct Pass {
-    double fl, fp, pl, pp;
-    bool started, fin, pin;
-};
-
-struct Clip {
-    Pass ps[4];
-    double c[4];
-    AreaAcc acc;
-};
-
-template <int S>
-OGG_DEV void clip_push(Clip& k, double l, double p) {
-    if constexpr (S == 4) {
-        area_push(k.acc, l, p);
-    } else {
-        Pass& s = k.ps[S];
-        const bool in = inside<S>(l, p, k.c[S]);
-        double xl = 0.0, xp = 0.0;
-        int nx = 0;
-        if (!s.started) {
-            s.started = true, s.fl = l, s.fp = p, s.fin = in;
-        } else if (in != s.pin) {
-            crossing<S>(s.pl, s.pp, l, p, k.c[S], xl, xp);
-            nx = 1;
-        }
-        s.pl = l, s.pp = p, s.pin = in;
-        const int n_out = nx + (in ? 1 : 0);
-#pragma unroll 1
-        for (int j = 0; j < n_out; ++j) {   // one call site: the chain does not multiply the code
-            const bool x = j == 0 && nx == 1;
-            clip_push<S + 1>(k, x ? xl : l, x ? xp : p);
-        }
-    }
-}
-
-template <int S>
-OGG_DEV void clip_close(Clip& k) {
-    if constexpr (S < 4) {
-        Pass& s = k.ps[S];
-        if (s.started && s.fin != s.pin) {
-            double xl, xp;
-            crossing<S>(s.pl, s.pp, s.fl, s.fp, k.c[S], xl, xp);
-            clip_push<S + 1>(k, xl, xp);
-        }
-        clip_close<S + 1>(k);
-    }
-}
-
-OGG_DEV const double* row_of(const double* p, const double* pn, const Geo& g, long r) {
-    return r < g.n ? p + r * g.nxp : pn + (r - g.n) * g.nxp;
-}
-
 OGG_DEV double col_edge(const AtmD& a, long u, int hi) {
     const long k = floor_div(u, a.NA);
     return a.a[u - k * a.NA + hi] + 360.0 * (double)k;
-}
-
-template <typename T>
-OGG_DEV T wave_sum(T v) {
-    for (int o = TT / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, TT);
-    return v;
 }
 
 template <bool WRITE>
@@ -212,12 +97,8 @@ __global__ __launch_bounds__(TT) void xgrid_kernel(Geo g, AtmD a, double* a_poly
     long long cnt = 0;
     int st = ST_DEGENERATE, npole = 0, masked = 0;
     if (live) {
-        const long mr = c / g.nxo, n = c - mr * g.nxo;
-        const long r0 = 2 * (g.m0 + mr) - g.j0;
-        const double *x0 = row_of(g.x, g.xn, g, r0), *y0 = row_of(g.y, g.yn, g, r0);
-        const double *x2 = row_of(g.x, g.xn, g, r0 + 2), *y2 = row_of(g.y, g.yn, g, r0 + 2);
-        const double cx[4] = {x0[2 * n], x0[2 * n + 2], x2[2 * n + 2], x2[2 * n]};
-        const double cy[4] = {y0[2 * n], y0[2 * n + 2], y2[2 * n + 2], y2[2 * n]};
+        double cx[4], cy[4];
+        cell_corners(g, c, cx, cy);
         masked = g.mask ? (g.mask[c] == 0) : 0;
         bool pc[4];
         double L[4];
@@ -251,7 +132,7 @@ __global__ __launch_bounds__(TT) void xgrid_kernel(Geo g, AtmD a, double* a_poly
                 st = ST_POLE;
             } else {
                 AreaAcc acc{};
-                for (int k = 0; k < nv; ++k) area_push(acc, vl[k][lane], vp[k][lane]);
+                for (int k = 0; k < nv; ++k) acc.push(vl[k][lane], vp[k][lane]);
                 A = area_close(acc, g.Re2);
                 st = A > 0.0 ? ST_OK : ST_INVERTED;
             }
@@ -274,11 +155,7 @@ __global__ __launch_bounds__(TT) void xgrid_kernel(Geo g, AtmD a, double* a_poly
         if (!WRITE) a_poly[c] = A;
     }
     // inclusive scan of the candidate counts over the wavefront
-    long long incl = cnt;
-    for (int o = 1; o < TT; o <<= 1) {
-        const long long v = __shfl_up(incl, o, TT);
-        if (lane >= o) incl += v;
-    }
+    const long long incl = wave_scan(cnt, lane);
     s_incl[lane] = incl;
     const long long T = __shfl(incl, TT - 1, TT);
     __syncthreads();
@@ -290,15 +167,7 @@ __global__ __launch_bounds__(TT) void xgrid_kernel(Geo g, AtmD a, double* a_poly
         int I = 0, J = 0, o = 0;
         double ax = 0.0;
         if (t < T) {
-            int lo = 0, hi = TT;   // the owner: the first cell whose inclusive count exceeds t
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (s_incl[mid] > t)
-                    hi = mid;
-                else
-                    lo = mid + 1;
-            }
-            o = lo;
+            o = owner_of(s_incl, t);
             const long long q = t - (o ? s_incl[o - 1] : 0);
             const int nc = s_ncol[o];
             J = s_jlo[o] + (int)(q / nc);
@@ -311,7 +180,7 @@ __global__ __launch_bounds__(TT) void xgrid_kernel(Geo g, AtmD a, double* a_poly
             if (s_box[0][o] >= clo && s_box[1][o] <= chi && s_box[2][o] >= blo && s_box[3][o] <= bhi) {
                 ax = ap;   // every vertex inside every half-plane: the clip returns the polygon as it is
             } else {
-                Clip k{};
+                Clip<AreaAcc> k{};
                 k.c[0] = clo, k.c[1] = chi, k.c[2] = blo, k.c[3] = bhi;
                 const int nv = s_nv[o];
                 for (int v = 0; v < nv; ++v) clip_push<0>(k, vl[v][o], vp[v][o]);
@@ -342,12 +211,9 @@ __global__ __launch_bounds__(TT) void xgrid_kernel(Geo g, AtmD a, double* a_poly
         const int n_mask = wave_sum(live && masked ? 1 : 0);
         const long long n_cand = wave_sum(cnt);
         if (lane == 0) {
-            auto add = [](long long* p, long long v) {
-                if (v) atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-            };
-            add(&counts->cells, n_live), add(&counts->pole_cells, n_pole), add(&counts->degenerate, n_deg);
-            add(&counts->pole_enclosing, n_enc), add(&counts->inverted, n_inv), add(&counts->masked, n_mask);
-            add(&counts->candidates, n_cand), add(&counts->kept, run);
+            count_add(&counts->cells, n_live), count_add(&counts->pole_cells, n_pole), count_add(&counts->degenerate, n_deg);
+            count_add(&counts->pole_enclosing, n_enc), count_add(&counts->inverted, n_inv), count_add(&counts->masked, n_mask);
+            count_add(&counts->candidates, n_cand), count_add(&counts->kept, run);
             wave_kept[w] = run;
         }
     }
@@ -360,41 +226,6 @@ __global__ void xgrid_dsin_kernel(const double* b, long n, double* out) {
         const double b1 = b[k] * D2R, b2 = b[k + 1] * D2R;
         out[k] = 2.0 * cos((b1 + b2) / 2.0) * sin((b2 - b1) / 2.0);
     }
-}
-
-// exclusive offsets of the kept pairs of every wavefront, and their total: one workgroup, contiguous chunks per thread
-__global__ __launch_bounds__(SCAN_T) void xgrid_scan_kernel(const long long* in, long n, long long* out, long long* total) {
-    __shared__ long long part[SCAN_T];
-    const int t = threadIdx.x;
-    const long chunk = (n + SCAN_T - 1) / SCAN_T;
-    const long lo = t * chunk, hi = std::min(n, lo + chunk);
-    long long s = 0;
-    for (long i = lo; i < hi; ++i) s += in[i];
-    part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < SCAN_T; o <<= 1) {
-        const long long v = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    long long r = t ? part[t - 1] : 0;
-    for (long i = lo; i < hi; ++i) {
-        out[i] = r;
-        r += in[i];
-    }
-    if (t == SCAN_T - 1) *total = part[SCAN_T - 1];
-}
-
-int check_band(const ogg_xgrid_band& b) {
-    OGG_REQUIRE(b.nx >= 2 && b.ny >= 2 && b.nx % 2 == 0 && b.ny % 2 == 0, OGG_EARG,
-                "exchange grid: model cells are 2 x 2 supergrid cells, but the supergrid has %ld x %ld cells; generate it with "
-                "--ensure_nj_even", b.ny, b.nx);
-    OGG_REQUIRE(b.j0 >= 0 && b.n_cell_rows >= 0 && b.j0 + b.n_cell_rows <= b.ny, OGG_EARG,
-                "ogg_xgrid_band: cell rows %ld .. %ld of a grid of %ld", b.j0, b.j0 + b.n_cell_rows - 1, b.ny);
-    OGG_REQUIRE(b.Re > 0.0 && std::isfinite(b.Re), OGG_EARG, "ogg_xgrid_band: Re = %g", b.Re);
-    OGG_REQUIRE(b.threshold >= 0.0 && std::isfinite(b.threshold), OGG_EARG, "ogg_xgrid_band: threshold = %g", b.threshold);
-    return OGG_OK;
 }
 
 int check_atm_shape(const ogg_xgrid_atm& a) {
@@ -418,12 +249,6 @@ int check_atm_host(const ogg_xgrid_atm& a) {
                 a.lat[0], a.lat[a.NB]);
     return OGG_OK;
 }
-
-long first_row(const ogg_xgrid_band& b) { return (b.j0 + 1) / 2; }
-long end_row(const ogg_xgrid_band& b) { return (b.j0 + b.n_cell_rows + 1) / 2; }
-long out_rows(const ogg_xgrid_band& b) { return std::max(0L, end_row(b) - first_row(b)); }
-long next_rows(const ogg_xgrid_band& b) { return out_rows(b) > 0 ? 2 * end_row(b) - (b.j0 + b.n_cell_rows) + 1 : 0; }
-long n_waves(const ogg_xgrid_band& b) { return (out_rows(b) * (b.nx / 2) + TT - 1) / TT; }
 
 // workspace: head (the total) | dsin (NB + 1 doubles) | kept per wave | offsets per wave; sections rounded to 64 bytes
 struct Layout {
@@ -455,12 +280,6 @@ int check_dev_args(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, const v
     if (out_rows(*band) > 0)
         OGG_REQUIRE(band->x && band->y && band->x_next && band->y_next, OGG_EARG, "ogg_xgrid_band: null x / y / x_next / y_next");
     return ogg::check_workspace("ogg_xgrid", workspace, workspace_bytes, ws_bytes(*band, *atm));
-}
-
-Geo make_geo(const ogg_xgrid_band& b) {
-    Geo g{b.x, b.y, b.x_next, b.y_next, b.mask, b.nx + 1, b.nx / 2, b.j0, b.n_cell_rows, first_row(b), 0, b.Re * b.Re, b.threshold};
-    g.ncells = out_rows(b) * g.nxo;
-    return g;
 }
 
 }  // namespace
@@ -539,26 +358,12 @@ extern "C" int ogg_xgrid(const ogg_xgrid_band* band, const ogg_xgrid_atm* atm, l
     if (rows == 0) return OGG_OK;
     OGG_REQUIRE(h.x && h.y && a_poly, OGG_EARG, "ogg_xgrid: null x / y / a_poly");
     ogg::Buffers bufs;   // freed on every exit path
-    const long nxp = h.nx + 1, n = h.n_cell_rows, nn = next_rows(h);
-    const size_t body = (size_t)n * nxp, tail = (size_t)nn * nxp;   // doubles
-    double *px, *py, *pa, *pb, *ap, *la;
-    unsigned char* pm;
+    double *pa, *pb, *ap, *la;
     char* ws;
     int *li, *lo;
     ogg_xgrid_counts* ct;
-    if (int e = bufs.alloc(&px, body + tail)) return e;
-    if (int e = bufs.alloc(&py, body + tail)) return e;
-    if (int e = bufs.send(px, h.x, body)) return e;
-    if (int e = bufs.send(py, h.y, body)) return e;
-    if (int e = bufs.send(px + body, h.x_next ? h.x_next : h.x + n * nxp, tail)) return e;
-    if (int e = bufs.send(py + body, h.y_next ? h.y_next : h.y + n * nxp, tail)) return e;
-    ogg_xgrid_band d = h;
-    d.x = px, d.y = py;
-    d.x_next = d.x + n * nxp, d.y_next = d.y + n * nxp;
-    if (h.mask) {
-        if (int e = bufs.put(&pm, h.mask, (size_t)nc)) return e;
-        d.mask = pm;
-    }
+    ogg_xgrid_band d;
+    if (int e = stage_band(bufs, h, &d)) return e;
     if (int e = bufs.alloc(&pa, (size_t)atm->NA + 1)) return e;
     if (int e = bufs.alloc(&pb, (size_t)atm->NB + 1)) return e;
     if (int e = bufs.send(pa, atm->lon, (size_t)atm->NA + 1)) return e;

@@ -666,7 +666,9 @@ class AnalysisFlags(object):
                     remap_fill_max=None, runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast",
                     coast_distance_file=None, coast_distance_sides="both", basin_codes_file=None, basin_rules=None, basin_seed_max_km=None,
                     xgrid_frac_file=None, interp_source=None, interp_var=None, interp_vector=None, interp_points="h",
-                    interp_file="interp.nc", interp_no_fill=False, interp_fill_max=None, interp_no_rotate=False)
+                    interp_file="interp.nc", interp_no_fill=False, interp_fill_max=None, interp_no_rotate=False, xgrid_cs=None,
+                    xgrid_cs_spacing="equiangular", xgrid_cs_lon_shift=0.0, xgrid_cs_file="atmos_mosaic_tile%dXocean_mosaic_tile1.nc",
+                    xgrid_cs_frac_file=None)
 
     def __init__(self, **flags):
         unknown = sorted(set(flags) - set(self.DEFAULTS))
@@ -685,6 +687,7 @@ def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
     _validate_coast_distance_flags(a.coast_distance_file, a.coast_distance_sides, a.topog_source)
     _validate_basin_flags(a.basin_codes_file, a.basin_rules, a.basin_seed_max_km, a.topog_source)
     _validate_frac_flags(a.xgrid_frac_file, a.xgrid_atm)
+    _validate_xgrid_cs_flags(a.xgrid_cs, a.xgrid_cs_spacing, a.xgrid_cs_file, a.xgrid_cs_frac_file, a.xgrid_atm, a.xgrid_file)
     _validate_interp_flags(a.interp_source, a.interp_var, a.interp_vector, a.interp_points, skip_metrics, a.interp_no_fill,
                            a.interp_fill_max, a.interp_no_rotate)
 
@@ -701,7 +704,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast", xgrid_frac_file=None,
          interp_source=None, interp_var=None, interp_vector=None, interp_points="h", interp_file="interp.nc", interp_no_fill=False,
          interp_fill_max=None, interp_no_rotate=False, topog_roughness=False, coast_distance_file=None, coast_distance_sides="both",
-         basin_codes_file=None, basin_rules=None, basin_seed_max_km=None):
+         basin_codes_file=None, basin_rules=None, basin_seed_max_km=None, xgrid_cs=None, xgrid_cs_spacing="equiangular",
+         xgrid_cs_lon_shift=0.0, xgrid_cs_file="atmos_mosaic_tile%dXocean_mosaic_tile1.nc", xgrid_cs_frac_file=None):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -742,7 +746,10 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     ``ocean_mask_file``), written to FILE; also an addition.  ``basin_codes_file`` (--basin_codes_file FILE, needs ``topog_source`` and
     ``basin_rules``, --basin_rules FILE): the integer basin of every wet cell of the topography by the ordered seeded floods of the
     rule file (basin_codes.py; a seed farther than ``basin_seed_max_km`` from every cell centre is off the grid; the edited wet set
-    with ``ocean_mask_file``), written to FILE; also an addition."""
+    with ``ocean_mask_file``), written to FILE; also an addition.  ``xgrid_cs`` (--xgrid_cs N): write the exchange grid of the model
+    cells with a gnomonic cubed-sphere atmosphere of six tiles of N x N cells (exchange_grid_cs.py; ``xgrid_cs_spacing``: equiangular
+    or edge_equidistant; the module's default cube turned by ``xgrid_cs_lon_shift`` degrees; the wet set of ``xgrid_atm``) to the six
+    files ``xgrid_cs_file`` % tile, and the ocean and land fractions of its cells to ``xgrid_cs_frac_file``; also an addition."""
     flags = dict(locals())   # the arguments, by name: taken before anything else is bound
     import time
 
@@ -1090,6 +1097,10 @@ def _run_analyses(a, g, cut=None):
         _write_xgrid(xres, a.xgrid_file)
         if a.xgrid_frac_file and xres is not None:   # rank 0's list, not built a second time
             _write_frac(g.regrid_to_latlon(cut, None, X.regular_atm(*a.xgrid_atm), mask=wet, lists=xres), a.xgrid_frac_file)
+    if a.xgrid_cs is not None:
+        from . import exchange_grid_cs as XC
+        _write_xgrid_cs(g.exchange_grid_cs(cut, XC.cubed_sphere_atm(a.xgrid_cs, a.xgrid_cs_spacing, lon_shift=a.xgrid_cs_lon_shift),
+                                           mask=wet), a.xgrid_cs_file, a.xgrid_cs_frac_file)
     if a.remap_source is not None:
         from . import remap as R
         _write_results(R, R.write_remapped, [(src, g.remap(cut, src, mask=wet, fill=not a.remap_no_fill, fill_max=a.remap_fill_max))
@@ -1130,6 +1141,10 @@ class _StitchedArrays(object):
     def exchange_grid(self, cut, atm, mask=None):
         from . import exchange_grid as X
         return X.exchange_grid(self.x, self.y, *atm, mask=mask, Re=_default_Re)
+
+    def exchange_grid_cs(self, cut, atm, mask=None):
+        from . import exchange_grid_cs as XC
+        return XC.exchange_grid_cs(self.x, self.y, atm, mask=mask, Re=_default_Re)
 
     def regrid_to_latlon(self, cut, field, atm, mask=None, lists=None):
         from . import latlon_regrid as G
@@ -1328,6 +1343,33 @@ def _validate_frac_flags(xgrid_frac_file, xgrid_atm):
         raise ValueError("--xgrid_frac_file needs --xgrid_atm: the fractions are of that atmosphere's cells")
 
 
+def _validate_xgrid_cs_flags(xgrid_cs, spacing, pattern, frac_file, xgrid_atm, xgrid_file):
+    if xgrid_cs is None:
+        if frac_file:
+            raise ValueError("--xgrid_cs_frac_file needs --xgrid_cs: the fractions are of that atmosphere's cells")
+        return
+    from . import exchange_grid_cs as XC
+    if not 1 <= int(xgrid_cs) <= XC.N_MAX:
+        raise ValueError("--xgrid_cs must be 1 .. %d (%r)" % (XC.N_MAX, xgrid_cs))
+    if spacing not in XC.SPACINGS:
+        raise ValueError("--xgrid_cs_spacing must be one of %s (%r)" % (", ".join(XC.SPACINGS), spacing))
+    paths = XC.tile_paths(str(pattern))
+    if xgrid_atm is not None and os.path.abspath(str(xgrid_file)) in [os.path.abspath(q) for q in paths]:
+        raise ValueError("--xgrid_cs_file would write %s, which is --xgrid_file of --xgrid_atm: give one of them another name"
+                         % xgrid_file)
+
+
+def _write_xgrid_cs(res, pattern, frac_file):
+    if res is None:   # not rank 0
+        return
+    from . import exchange_grid_cs as XC
+    for line in XC.summary_lines(res):
+        print(line)
+    XC.write_xgrid_cs(str(pattern), res)
+    if frac_file:
+        XC.write_frac_cs(str(frac_file), res)
+
+
 def _write_frac(res, fnam):
     from . import latlon_regrid as G
     for line in G.summary_lines(res):
@@ -1460,6 +1502,18 @@ def build_parser():
     parser.add_argument("--xgrid_frac_file", type=str, required=False, default=None,
                         help="write the ocean / land fraction, area and exchange-cell count of every --xgrid_atm atmosphere cell to this "
                              "file (wet cells only when --topog_source is given)")
+    parser.add_argument("--xgrid_cs", type=int, required=False, default=None, metavar="N",
+                        help="write the atmosphere x ocean exchange grid of a gnomonic cubed-sphere atmosphere of six tiles of N x N "
+                             "cells into the six files of --xgrid_cs_file (wet cells only when --topog_source is given)")
+    parser.add_argument("--xgrid_cs_spacing", type=str, choices=["equiangular", "edge_equidistant"], required=False,
+                        default="equiangular", help="the spacing of the cubed sphere's grid lines, default equiangular")
+    parser.add_argument("--xgrid_cs_lon_shift", type=float, required=False, default=0.0,
+                        help="turn the cubed sphere by this many degrees about the polar axis (default 0: tile 1 centred on 0 E)")
+    parser.add_argument("--xgrid_cs_file", type=str, required=False, default="atmos_mosaic_tile%dXocean_mosaic_tile1.nc",
+                        help="pattern of the six exchange-grid files, %%d the tile number; default "
+                             "atmos_mosaic_tile%%dXocean_mosaic_tile1.nc")
+    parser.add_argument("--xgrid_cs_frac_file", type=str, required=False, default=None,
+                        help="write the ocean / land fraction and area of every --xgrid_cs atmosphere cell to this file")
     parser.add_argument("--interp_source", type=str, required=False, default=None,
                         help="a global lat-lon file (NetCDF classic / 64-bit offset) whose --interp_var scalars and --interp_vector "
                              "vectors are interpolated bilinearly at the grid's points into --interp_file")

@@ -1371,13 +1371,18 @@ class Supergrid(object):
 
     def xgrid_lists(self, cut, atm, mask=None, threshold=1e-6, halo=None):
         """[(piece index, first model row, counts, a_poly, atm, ocn, area)] of THIS rank's pieces (device tensors), the exchange grid
-        of each piece computed on the buffers the pass left in HBM.  ``atm``: (lon, lat) edges as float64 device tensors; ``mask``:
+        of each piece computed on the buffers the pass left in HBM.  ``atm``: (lon, lat) edges as float64 device tensors, or a cubed
+        sphere (a dict of exchange_grid_cs.cubed_sphere_atm with its table "t" a device tensor; atm then has three columns); ``mask``:
         None or a uint8 device tensor of every model cell of the stitched grid."""
-        from . import exchange_grid as X
         p, st = self.plan, self._stream()
         halo = self.xgrid_halo(cut) if halo is None else halo   # (held until the kernels have run: the bands point into it)
-        lon, lat = atm
-        desc = L.XgridAtm(lon=lon.data_ptr(), lat=lat.data_ptr(), NA=lon.numel() - 1, NB=lat.numel() - 1)
+        if isinstance(atm, dict):
+            from . import exchange_grid_cs as X
+            desc = X.atm_desc(atm, atm["t"].data_ptr())
+        else:
+            from . import exchange_grid as X
+            lon, lat = atm
+            desc = L.XgridAtm(lon=lon.data_ptr(), lat=lat.data_ptr(), NA=lon.numel() - 1, NB=lat.numel() - 1)
         ny = self.stitched_rows(cut) - 1
         out = []
         for k, q, _, band in self._bands(cut, lambda q: L.XgridBand(nx=p.Ni, ny=ny, j0=q["j0"], n_cell_rows=q["n_cell"], Re=float(p.Re),
@@ -1389,16 +1394,18 @@ class Supergrid(object):
         self.torch.cuda.synchronize(self.device)
         return out
 
-    def _gather_xgrid(self, cut, lon, lat, hm, threshold):
+    def _gather_xgrid(self, cut, lon, lat, hm, threshold, cs=None):
         """Every rank's xgrid_lists on rank 0 in piece order, the canonical order of the list (None on the other ranks): [(piece index,
         first model row, counts, a_poly, atm, ocn, area)], on the device or, under gloo, the CPU.  ``hm``: None or a uint8 host
-        array of every model cell."""
+        array of every model cell.  ``cs``: a cubed-sphere atmosphere (host arrays) in the place of the edges lon, lat."""
         torch = self.torch
         ncol = self.plan.Ni // 2
+        fields, atm_cols = (L.XGRID_COUNT_FIELDS, 2) if cs is None else (L.XGRID_CS_COUNT_FIELDS, 3)
 
         def records(g):
             to = lambda a: torch.from_numpy(a).to(g.device)   # noqa: E731
-            return g.xgrid_lists(cut, (to(lon), to(lat)), None if hm is None else to(hm), threshold)
+            atm = (to(lon), to(lat)) if cs is None else dict(cs, t=to(cs["t"]))
+            return g.xgrid_lists(cut, atm, None if hm is None else to(hm), threshold)
 
         def send(e):   # counts first, then the arrays (when there are any), then a_poly
             _, _, counts, a_poly, atm_ij, ocn_ij, area = e
@@ -1408,10 +1415,10 @@ class Supergrid(object):
             m0, rows, _ = self._xgrid_rows(q)
             if rows == 0:
                 return None
-            counts = take(len(L.XGRID_COUNT_FIELDS), torch.int64)
-            n = int(counts[L.XGRID_COUNT_FIELDS.index("kept")])
+            counts = take(len(fields), torch.int64)
+            n = int(counts[fields.index("kept")])
             lists = [take(s, d) if n else torch.empty(s, dtype=d, device=counts.device)
-                     for s, d in (((n, 2), torch.int32), ((n, 2), torch.int32), (n, torch.float64))]
+                     for s, d in (((n, atm_cols), torch.int32), ((n, 2), torch.int32), (n, torch.float64))]
             return (k, m0, counts, take((rows, ncol), torch.float64), *lists)
         got = self._gather(self.quality_pieces(cut), records, send, recv)
         if got is not None:
@@ -1441,6 +1448,24 @@ class Supergrid(object):
             return None
         hostp = [(m0,) + tuple(t.cpu().numpy() for t in ts) for _, m0, *ts in got]
         return X.assemble(hostp, shape, lon, lat, float(self.plan.Re), threshold, mask is not None)
+
+    def exchange_grid_cs(self, cut, atm, mask=None, threshold=1e-6):
+        """exchange_grid with a cubed-sphere atmosphere (exchange_grid_cs.result on rank 0, None on the other ranks).  ``atm``: a
+        cubed sphere of exchange_grid_cs.cubed_sphere_atm or cubed_sphere_from_corners.  The same pieces, halo rows and gather; the
+        atmosphere index has three columns (I, J, face)."""
+        from . import exchange_grid as X
+        from . import exchange_grid_cs as XC
+        nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
+        X.check_grid(nyp, nxp)
+        X.check_args(threshold, self.plan.Re)
+        atm = XC.checked_atm(atm)
+        shape = ((nyp - 1) // 2, (nxp - 1) // 2)
+        hm = XC.host_mask(mask, shape)
+        got = self._gather_xgrid(cut, None, None, hm, threshold, cs=atm)
+        if got is None:
+            return None
+        hostp = [(m0,) + tuple(t.cpu().numpy() for t in ts) for _, m0, *ts in got]
+        return XC.assemble(hostp, shape, atm, float(self.plan.Re), threshold, mask is not None)
 
     # -- ocean mask ---------------------------------------------------------------------------------------------------
     def _stitched(self, cut, fields, point_rows):
