@@ -141,6 +141,12 @@ int ogg_mdist_dev(long n, const double* x1, const double* x2, double* out, void*
 int ogg_grid_metrics_midas_dev(long nrows_xy, long ni1, const double* x, const double* y, long n_pt_rows,
                                long n_cell_rows, double Re, int latlon_areafix, double* dx, double* dy,
                                double* area, double* angle, void* stream);
+/* The kernel ogg_grid_metrics_midas_dev would launch for ni1 columns and n_pt_rows point rows under the current environment (host only, no
+ * device is touched): *tile_rows = the instantiation of the LDS-staged tile kernel (4, 6, 8 or 12), or 0 for the streaming kernel
+ * (OGG_MIDAS_TILE_ROWS=0); *rows_per_block = the point rows one workgroup walks.  metrics: whether any of dx, dy, area is asked for (the
+ * streaming kernel walks at least 4 rows then, at least 1 for an angle-only call).  Both branches aim at OGG_MIDAS_TARGET_WG workgroups
+ * (default 2048). */
+int ogg_grid_metrics_midas_plan(long ni1, long n_pt_rows, int metrics, int* tile_rows, int* rows_per_block);
 /* generate_grid_metrics_MIDAS(x, y, Re, latlon_areafix): dx (nj1 x ni1-1), dy (nj1-1 x ni1), area (nj1-1 x ni1-1) */
 int ogg_grid_metrics_midas(long nj1, long ni1, const double* x, const double* y, double Re, int latlon_areafix,
                            double* dx, double* dy, double* area);

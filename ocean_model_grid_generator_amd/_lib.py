@@ -284,6 +284,7 @@ SIGNATURES = {
     "ogg_generate_latlon_grid": [c_long, c_long, c_double, c_double, c_double, c_double, c_int, c_void_p, c_void_p],
     "ogg_grid_metrics_midas_dev": [c_long, c_long, c_void_p, c_void_p, c_long, c_long, c_double, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p],
+    "ogg_grid_metrics_midas_plan": [c_long, c_long, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
     "ogg_grid_metrics_midas": [c_long, c_long, c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p],
     "ogg_angle_x": [c_long, c_long, c_void_p, c_void_p, c_void_p],
     "ogg_bipolar_projection": [c_long, c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p],

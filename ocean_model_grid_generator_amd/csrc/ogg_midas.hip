@@ -281,7 +281,41 @@ long midas_env(const char* name, long dflt) {
     return (e && *e) ? atol(e) : dflt;
 }
 
+// What a call launches: tile_rows = the instantiation TR of midas_tile_kernel (4, 6, 8, 12), or 0 for the streaming kernel; rpb = point rows
+// per workgroup.  Both branches aim at OGG_MIDAS_TARGET_WG workgroups (default 2048: small bands use fewer rows per workgroup).
+struct MidasPlan {
+    int tile_rows, rpb;
+};
+
+MidasPlan midas_plan(long ni1, long n_pt_rows, bool metrics) {
+    const long gx = (ni1 + MIDAS_TX - 1) / MIDAS_TX;
+    // rows per tile of the LDS-staged kernel: 6 -> 7 staged rows x 258 columns x 16 B = 28.9 KB, five workgroups per CU (the
+    // kernel's 5 waves per SIMD); fewer for small bands (>= ~2048 workgroups); 0: the streaming kernel
+    const long tile_rows = midas_env("OGG_MIDAS_TILE_ROWS", 6);
+    long target = midas_env("OGG_MIDAS_TARGET_WG", 2048);
+    if (target < 1) target = 2048;
+    if (target > n_pt_rows * gx) target = n_pt_rows * gx;  // one row per workgroup either way; keeps the sum below in range for any setting
+    long rpb = (n_pt_rows * gx + target - 1) / target;
+    if (tile_rows > 0) {
+        rpb = rpb < 2 ? 2 : (rpb > tile_rows ? tile_rows : rpb);
+        rpb = rpb > TILE_ROWS_MAX ? TILE_ROWS_MAX : rpb;
+        if (rpb > n_pt_rows) rpb = n_pt_rows;
+        // the smallest instantiation that holds the tile (its static LDS sets how many workgroups a CU takes)
+        return {rpb <= 4 ? 4 : rpb <= 6 ? 6 : rpb <= 8 ? 8 : TILE_ROWS_MAX, (int)rpb};
+    }
+    rpb = rpb < (metrics ? 4 : 1) ? (metrics ? 4 : 1) : (rpb > MIDAS_ROWS ? MIDAS_ROWS : rpb);
+    return {0, (int)rpb};
+}
+
 }  // namespace
+
+extern "C" int ogg_grid_metrics_midas_plan(long ni1, long n_pt_rows, int metrics, int* tile_rows, int* rows_per_block) {
+    OGG_REQUIRE(tile_rows && rows_per_block, OGG_EARG, "ogg_grid_metrics_midas_plan: null output");
+    OGG_REQUIRE(ni1 >= 2 && n_pt_rows >= 1, OGG_ESHAPE, "ogg_grid_metrics_midas_plan: %ld point rows x %ld columns", n_pt_rows, ni1);
+    const MidasPlan pl = midas_plan(ni1, n_pt_rows, metrics != 0);
+    *tile_rows = pl.tile_rows, *rows_per_block = pl.rpb;
+    return OGG_OK;
+}
 
 extern "C" int ogg_grid_metrics_midas_dev(long nrows_xy, long ni1, const double* x, const double* y, long n_pt_rows,
                                           long n_cell_rows, double Re, int latlon_areafix, double* dx, double* dy,
@@ -296,16 +330,11 @@ extern "C" int ogg_grid_metrics_midas_dev(long nrows_xy, long ni1, const double*
     if (!(dy || area)) n_cell_rows = 0;
     const long gx = (ni1 + MIDAS_TX - 1) / MIDAS_TX;
     hipStream_t s = ogg::as_stream(stream);
-    // rows per tile of the LDS-staged kernel: 6 -> 7 staged rows x 258 columns x 16 B = 28.9 KB, five workgroups per CU (the
-    // kernel's 5 waves per SIMD); fewer for small bands (>= ~2048 workgroups); 0: the streaming kernel
-    long tile_rows = midas_env("OGG_MIDAS_TILE_ROWS", 6);
-    if (tile_rows > 0) {
-        long rpb = (n_pt_rows * gx + 2047) / 2048;
-        rpb = rpb < 2 ? 2 : (rpb > tile_rows ? tile_rows : rpb);
-        rpb = rpb > TILE_ROWS_MAX ? TILE_ROWS_MAX : rpb;
-        if (rpb > n_pt_rows) rpb = n_pt_rows;
-        MidasParams p{nrows_xy, ni1, n_pt_rows, n_cell_rows, (int)rpb, x, y, Re, pow(Re, 2.0), dx, dy, area, angle};
-        dim3 grid((unsigned)gx, (unsigned)((n_pt_rows + rpb - 1) / rpb));
+    const MidasPlan pl = midas_plan(ni1, n_pt_rows, metrics);
+    const long rpb = pl.rpb;
+    MidasParams p{nrows_xy, ni1, n_pt_rows, n_cell_rows, (int)rpb, x, y, Re, pow(Re, 2.0), dx, dy, area, angle};
+    dim3 grid((unsigned)gx, (unsigned)((n_pt_rows + rpb - 1) / rpb));
+    if (pl.tile_rows > 0) {
 #define OGG_MIDAS_LAUNCH(TR)                                                            \
     do {                                                                               \
         if (!metrics)                                                                  \
@@ -315,23 +344,16 @@ extern "C" int ogg_grid_metrics_midas_dev(long nrows_xy, long ni1, const double*
         else                                                                           \
             midas_tile_kernel<TR, true, false><<<grid, MIDAS_TX, 0, s>>>(p);           \
     } while (0)
-        // the smallest instantiation that holds the tile (its static LDS sets how many workgroups a CU takes)
-        if (rpb <= 4)
-            OGG_MIDAS_LAUNCH(4);
-        else if (rpb <= 6)
-            OGG_MIDAS_LAUNCH(6);
-        else if (rpb <= 8)
-            OGG_MIDAS_LAUNCH(8);
-        else
-            OGG_MIDAS_LAUNCH(TILE_ROWS_MAX);
+        switch (pl.tile_rows) {
+            case 4: OGG_MIDAS_LAUNCH(4); break;
+            case 6: OGG_MIDAS_LAUNCH(6); break;
+            case 8: OGG_MIDAS_LAUNCH(8); break;
+            default: OGG_MIDAS_LAUNCH(TILE_ROWS_MAX); break;
+        }
 #undef OGG_MIDAS_LAUNCH
         OGG_LAUNCH_CHECK();
         return OGG_OK;
     }
-    long rpb = (n_pt_rows * gx + 2047) / 2048;  // aim at >= 2048 workgroups
-    rpb = rpb < (metrics ? 4 : 1) ? (metrics ? 4 : 1) : (rpb > MIDAS_ROWS ? MIDAS_ROWS : rpb);
-    MidasParams p{nrows_xy, ni1, n_pt_rows, n_cell_rows, (int)rpb, x, y, Re, pow(Re, 2.0), dx, dy, area, angle};
-    dim3 grid((unsigned)gx, (unsigned)((n_pt_rows + rpb - 1) / rpb));
     if (!metrics)
         midas_angle_kernel<false, true><<<grid, MIDAS_TX, 0, s>>>(p);
     else if (latlon_areafix)

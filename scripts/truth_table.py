@@ -13,7 +13,7 @@ reference's lines would return if fp64 arithmetic did not round.  |fp64 referenc
 own rounding error, and it is the yardstick the GPU kernels are held to (tests/test_gpu_truth.py): a kernel that is no
 further from the truth than the fp64 reference is cannot be told apart from "the reference on another libm".
 
-Three groups ("next round" item 1):
+The groups (the first three: VERDICT round 3, "next round" item 1):
 
   dp   OGG:522-601  displacedPoleCap_metrics_quad(4): numerical_hi / numerical_hj (4th-order central differences of the
                     haversine distance of re-projected probes, eps = 1e-3) + 4 x 4 Lobatto means, on cells of the cap
@@ -42,6 +42,10 @@ Three groups ("next round" item 1):
   small_metrics     every dx, dy and area of the same four caps (orders 5 / 4; reduced row sets of the other coded orders), one fixture per cap:
 
     python scripts/truth_table.py --groups small_metrics     ->  tests/golden/truth_small_caps_metrics*.npz   (two minutes on 8 processes)
+
+  stencil           every dx, dy, area (both forms) and angle_x of the generic stencil on four hand-made meshes and nine windows of them:
+
+    python scripts/truth_table.py --groups stencil           ->  tests/golden/truth_stencil_*.npz   (seconds on 8 processes)
 
 Stored per value: hi = fp64(truth), lo = fp64(truth - hi)  (so that v - truth = (v - hi) - lo to 1e-32 relative), and
 the oracle's distance from the truth as measured when the fixture was made (`*_eref`), which the tests use as the unit
@@ -932,6 +936,105 @@ def small_metrics_group(pool, quick):
     return files
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# stencil: EVERY dx, dy, area (latlon_areafix on and off) and angle_x of the generic stencil (OGG:687-729 as coded, on the fp64 mesh, nothing
+# rounded) on the four meshes of tests/stencil_meshes.py and on nine windows of them, each window a mesh of its own.  One fixture per mesh
+# and one for the windows, tests/golden/truth_stencil_*.npz (names, scale and bound: tests/stencil_bounds.py; tests/test_stencil_bounds_cpu.py,
+# tests/test_gpu_stencil_truth.py).  Stored per mesh: the mesh (x, y: the INPUT, with the bits this host's libm gave the caps), per field hi =
+# fp64(truth) and lo = fp32(truth - hi), the oracle's largest and median |error| / s per field (`_R`, `_Rmed`; s = stencil_bounds.scales: one
+# class per field) and the number of points the angle check leaves out (`_angle_nsing`, from the mesh alone).  A window stores no mesh: it
+# is cut from its mesh's.
+# ---------------------------------------------------------------------------------------------------------------
+def stencil_edge(xa, ya, xb, yb):
+    """(L / Re, dxi, sin(lv)) of the edge b -> a in exact arithmetic.  OGG:695-702, 711."""
+    lv = (M(0.5) * (ya + yb)) * PI180
+    dxi = mdist_exact(xa, xb) * PI180
+    a = (ya - yb) * PI180
+    return mp.sqrt(a ** 2 + (dxi * mp.cos(lv)) ** 2), dxi, mp.sin(lv)
+
+
+def stencil_row(args):
+    """Point row j of a mesh from its fp64 rows j and j + 1 (None above the last row): [dx, angle, dy, area, area_nofix] of the row, each a list
+    of (hi, lo) (the last three empty above the last row)."""
+    x0, y0, x1, y1 = args
+    n = len(x0)
+    X0, Y0 = [M(v) for v in x0], [M(v) for v in y0]
+    e0 = [stencil_edge(X0[i + 1], Y0[i + 1], X0[i], Y0[i]) for i in range(n - 1)]
+    dx = [split(RE * e[0]) for e in e0]
+    ang = []
+    for i in range(n):
+        l, r = max(i - 1, 0), min(i + 1, n - 1)                                          # OGG:725-727: centred, one-sided at the two ends
+        ang.append(split(mp.atan2(Y0[r] - Y0[l], (X0[r] - X0[l]) * mp.cos(Y0[i] * PI180)) / PI180))
+    dy, area, area2 = [], [], []
+    if x1 is not None:
+        X1, Y1 = [M(v) for v in x1], [M(v) for v in y1]
+        e1 = [stencil_edge(X1[i + 1], Y1[i + 1], X1[i], Y1[i]) for i in range(n - 1)]
+        ej = [stencil_edge(X1[i], Y1[i], X0[i], Y0[i]) for i in range(n)]
+        dy = [split(RE * e[0]) for e in ej]
+        for i in range(n - 1):
+            area.append(split((M(RE) ** 2) * ((M(0.5) * (e1[i][1] + e0[i][1])) * (e1[i][2] - e0[i][2]))))         # OGG:713
+            area2.append(split(M(0.25) * ((RE * e1[i][0] + RE * e0[i][0]) * (RE * ej[i + 1][0] + RE * ej[i][0]))))   # OGG:715
+    return [dx, ang, dy, area, area2]
+
+
+def stencil_truth(pool, sb, name, x, y):
+    """{fixture key: array} of one mesh (or window) and the table line of the oracle's distances."""
+    nj1, ni1 = x.shape
+    res = pool.map(stencil_row, [(x[j], y[j], x[j + 1] if j + 1 < nj1 else None, y[j + 1] if j + 1 < nj1 else None) for j in range(nj1)], chunksize=1)
+    shp = sb.shapes(nj1, ni1)
+    out = {}
+    orc_f, s = sb.oracle(x, y), sb.scales(x, y)
+    sing = sb.angle_singular(x, y)
+    out[name + "_angle_nsing"] = np.array(int(sing.sum()))
+    for k, f in ((0, "dx"), (1, "angle"), (2, "dy"), (3, "area"), (4, "area_nofix")):
+        rows = [r[k] for r in res if r[k]]
+        t = np.array(rows, dtype=np.float64).reshape(shp[f] + (2,))
+        hi, lo = t[..., 0].copy(), t[..., 1].astype(np.float32)
+        out["%s_%s_hi" % (name, f)], out["%s_%s_lo" % (name, f)] = hi, lo
+        if hi.size == 0:
+            out["%s_%s_R" % (name, f)], out["%s_%s_Rmed" % (name, f)] = np.array(0.0), np.array(0.0)
+            continue
+        d = sb.distance(orc_f[f], hi, lo, f)
+        held = ~sing if f == "angle" else np.ones(hi.shape, bool)
+        zero = (hi == 0) & (lo == 0)
+        assert np.all(d[zero & held] == 0), (name, f)                                     # the oracle itself keeps the exact-zero rule
+        assert np.all(s[f][held & ~zero] > 0), (name, f)
+        q = np.where(held & ~zero, d / np.where(s[f] > 0, s[f], 1.0), 0.0)
+        out["%s_%s_R" % (name, f)], out["%s_%s_Rmed" % (name, f)] = np.array(q.max()), np.array(np.median(q[held & ~zero]) if (held & ~zero).any() else 0.0)
+        jw, iw = np.unravel_index(q.argmax(), q.shape)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rel = np.where(held & ~zero, d / np.abs(hi), 0.0)
+        print("stencil %-8s %-10s oracle vs truth: |error| / s max %.2f (row %d column %d) median %.2f; relative max %.1e median %.1e; %d exact zeros, %d left out" % (
+            name, f, q.max(), jw, iw, float(out["%s_%s_Rmed" % (name, f)]), rel.max(), np.median(rel[held & ~zero]) if (held & ~zero).any() else 0.0,
+            int((zero & held).sum()), int((~held).sum())), flush=True)
+    return out
+
+
+def stencil_group(pool, quick):
+    """{fixture file name: {key: array}}: one file per mesh, one for the windows.  --quick: the first three rows of every mesh (cut before the
+    truth is taken, so the rows it holds are the full fixture's: dx and angle of rows 0-2, dy and areas of rows 0-1) and the windows of at most
+    three columns."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import stencil_bounds as sb
+    import stencil_meshes as sm
+    meshes = {m: sm.BUILDERS[m]() for m in sm.MESHES}
+    files = {}
+    t0 = time.time()
+    for m in sm.MESHES:
+        x, y = meshes[m]
+        out = {"dps": np.array(mp.mp.dps), m + "_x": x, m + "_y": y}
+        out.update(stencil_truth(pool, sb, m, x[:3] if quick else x, y[:3] if quick else y))
+        files[sb.FILES[m]] = out
+    out = {"dps": np.array(mp.mp.dps)}
+    for w in sm.WINDOWS:
+        if quick and sm.WINDOWS[w][4] > 3:
+            continue
+        out.update(stencil_truth(pool, sb, w, *sm.window(meshes, w)))
+    files[sb.FILES["windows"]] = out
+    print("stencil: %.0f s" % (time.time() - t0), flush=True)
+    return files
+
+
 GROUPS = {"md": md_group, "bq": bq_group, "bp": bp_group, "dp": dp_group, "dp4": lambda pool, quick: dp_group(pool, quick, "dp4"),
           "ax": ax_group, "dm": dm_group, "bq16": bq16_group, "mdso": mdso_group}
 
@@ -942,7 +1045,7 @@ def main():
     ap.add_argument("--procs", type=int, default=8)
     ap.add_argument("--quick", action="store_true", help="a thin sample (smoke run of this script; does not overwrite the fixture)")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "truth_table.npz"))
-    ap.add_argument("--metrics-dir", default=None, help="where `small_metrics` writes its files (default: tests/golden, or the temp directory with --quick)")
+    ap.add_argument("--metrics-dir", default=None, help="where `small_metrics` and `stencil` write their files (default: tests/golden, or the temp directory with --quick)")
     a = ap.parse_args()
     if "small" in a.groups:                                                    # its own fixture; truth_table.npz is not rewritten
         with Pool(a.procs) as pool:
@@ -962,6 +1065,17 @@ def main():
             save_npz_reproducibly(path, arrays)
             print("wrote", path, os.path.getsize(path), "bytes")
         a.groups = [g for g in a.groups if g != "small_metrics"]
+        if not a.groups:
+            return
+    if "stencil" in a.groups:                                                  # one fixture per mesh + the windows; truth_table.npz is not rewritten
+        with Pool(a.procs) as pool:
+            files = stencil_group(pool, a.quick)
+        where = a.metrics_dir or (os.path.dirname(SMALL_OUT) if not a.quick else tempfile.gettempdir())
+        for name, arrays in sorted(files.items()):
+            path = os.path.join(where, name if not a.quick else name.replace(".npz", "_quick.npz"))
+            save_npz_reproducibly(path, arrays)
+            print("wrote", path, os.path.getsize(path), "bytes")
+        a.groups = [g for g in a.groups if g != "stencil"]
         if not a.groups:
             return
     out = {"dps": np.array(mp.mp.dps)}

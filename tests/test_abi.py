@@ -20,7 +20,7 @@ def declared_symbols():
 def test_header_declares_a_reasonable_surface():
     syms = declared_symbols()
     assert len(syms) >= 40
-    for must in ("ogg_grid_metrics_midas", "ogg_angle_x", "ogg_bipolar_cap_metrics_quad", "ogg_displaced_pole_metrics_quad",
+    for must in ("ogg_grid_metrics_midas", "ogg_grid_metrics_midas_plan", "ogg_angle_x", "ogg_bipolar_cap_metrics_quad", "ogg_displaced_pole_metrics_quad",
                  "ogg_bipolar_cap_mesh", "ogg_displaced_pole_mesh", "ogg_phi_mercator", "ogg_generate_latlon_grid"):
         assert must in syms
 

@@ -27,6 +27,8 @@ import numpy as np
 import pytest
 
 import angle_bounds
+import stencil_bounds
+import stencil_plans
 from oracle import ogg_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -125,36 +127,61 @@ def test_midas_golden_distorted_mesh(ogg, fvec):
     assert maxrel(area2, fvec["md_area_nofix"]) < 5e-15
     ang = ogg.angle_x(x, y)
     assert maxabs(ang, fvec["md_angle"]) < 1e-12
+    # ... and every element within its conditioned bound of the oracle (tests/stencil_bounds.py)
+    stencil_bounds.check_against_oracle(x, y, {"dx": dx, "dy": dy, "area": area, "area_nofix": area2, "angle": ang}, name="golden distorted mesh")
 
 
 @pytest.mark.parametrize("shape", [(1, 2), (1, 300), (2, 2), (40, 2), (3, 65), (17, 64), (33, 257), (200, 1000)])
 def test_midas_ragged_shapes(ogg, shape):
+    """Lat-lon meshes with 0.05 degrees of noise to +-80 degrees and to +-89.99 degrees (the noise carries points of the outer rows past the
+    pole).  The relative lines stay on both ranges: at +-80 degrees the conditioned bound of dx and dy, 2.5 s, is 1.4e-15 to 6e-15 of the value,
+    not always under their 2e-15 (tests/test_stencil_bounds_cpu.py::test_check_against_oracle); the conditioned check is added to them."""
     rng = np.random.default_rng(shape[0] * 1000 + shape[1])
     nj, ni = shape
-    x = np.tile(-300 + np.arange(ni) * 360.0 / max(ni - 1, 1), (nj, 1)) + rng.normal(0, 0.05, shape)
-    y = np.tile(np.linspace(-80, 80, nj).reshape(nj, 1), (1, ni)) + rng.normal(0, 0.05, shape)
-    dx, dy, area = ogg.generate_grid_metrics_MIDAS(x, y)
-    odx, ody, oar = orc.generate_grid_metrics_MIDAS(x, y)
-    assert dx.shape == odx.shape and dy.shape == ody.shape and area.shape == oar.shape     # a single row: dy and area are empty, like numpy's
-    assert maxrel(dx, odx) < 2e-15 and maxrel(dy, ody) < 2e-15
-    assert maxabs(area, oar) <= 5e-12 * (np.abs(oar).max() if oar.size else 1.0)
-    assert maxabs(ogg.angle_x(x, y), orc.angle_x(x, y)) < 1e-11
+    for lat_max in (80.0, 89.99):
+        x = np.tile(-300 + np.arange(ni) * 360.0 / max(ni - 1, 1), (nj, 1)) + rng.normal(0, 0.05, shape)
+        y = np.tile(np.linspace(-lat_max, lat_max, nj).reshape(nj, 1), (1, ni)) + rng.normal(0, 0.05, shape)
+        dx, dy, area = ogg.generate_grid_metrics_MIDAS(x, y)
+        odx, ody, oar = orc.generate_grid_metrics_MIDAS(x, y)
+        assert dx.shape == odx.shape and dy.shape == ody.shape and area.shape == oar.shape     # a single row: dy and area are empty, like numpy's
+        # against the ORACLE the relative lines hold next to the pole as well: the device does the oracle's operations on the oracle's bits,
+        # so lv is the same double and the two cos(lv) differ by an ulp of a well-conditioned call.  (Against the truth they would not
+        # hold there: the rounding of lv itself is what the conditioned bound allows for.)  A failure here is an arithmetic difference.
+        assert maxrel(dx, odx) < 2e-15 and maxrel(dy, ody) < 2e-15
+        assert maxabs(area, oar) <= 5e-12 * (np.abs(oar).max() if oar.size else 1.0)
+        ang = ogg.angle_x(x, y)
+        assert maxabs(ang, orc.angle_x(x, y)) < 1e-11
+        rep = stencil_bounds.check_against_oracle(x, y, {"dx": dx, "dy": dy, "area": area, "angle": ang,
+                                                         "area_nofix": ogg.generate_grid_metrics_MIDAS(x, y, latlon_areafix=False)[2]},
+                                                  name="ragged %s to %g degrees" % (shape, lat_max))
+        record("midas_ragged_%dx%d_lat%g" % (nj, ni, lat_max), **{f: r["worst_over_bound"] for f, r in rep.items()})
 
 
 @pytest.mark.parametrize("shape", [(2, 2), (5, 63), (7, 258), (31, 513), (200, 1000), (64, 5761)])
-def test_midas_tile_heights_and_streaming_kernel_agree_bitwise(ogg, shape, monkeypatch):
+def test_midas_tile_heights_and_streaming_kernel_agree_bitwise(hip, ogg, shape, monkeypatch):
     """Two implementations of the generic stencil kernel -- the LDS-staged tile walk (mdist from one reduction, non-temporal stores)
     at every tile height, and the streaming walk of rounds 1-3 (OGG_MIDAS_TILE_ROWS=0: rows straight from global memory, wave shuffles,
     mdist from two reductions) -- must give the same BITS on a distorted mesh whose longitudes wrap around, for both area forms and for
-    the angle-only call."""
+    the angle-only call.  At the default target of 2048 workgroups every one of these shapes plans two rows per tile whatever the setting, so
+    the settings are run again with OGG_MIDAS_TARGET_WG=1, one workgroup per column tile, where each plans the height its name says (as
+    far as the mesh has rows: at most 12, 16 for the streaming kernel); the plan is asserted through the library's query."""
     rng = np.random.default_rng(shape[0] * 7919 + shape[1])
     nj, ni = shape
     x = np.tile(-300 + np.arange(ni) * 720.0 / max(ni - 1, 1), (nj, 1)) + rng.normal(0, 0.05, shape)     # twice around: mod 360 at work
     y = np.tile(np.linspace(-89.5, 89.5, nj).reshape(nj, 1), (1, ni)) + rng.normal(0, 0.05, shape)
     x[0, 0], x[-1, -1] = x[0, 1], x[-1, -2] + 1e-20                                                       # a zero and a tiny difference
     ref = None
-    for rows in ("0", "1", "2", "4", "6", "8", "12", "99"):
+    gx = (ni + 255) // 256
+    for target, rows in [(t, r) for t in (None, "1") for r in ("0", "1", "2", "4", "6", "8", "12", "99")]:
         monkeypatch.setenv("OGG_MIDAS_TILE_ROWS", rows)
+        if target is None:
+            monkeypatch.delenv("OGG_MIDAS_TARGET_WG", raising=False)
+            want = (4, min(2, nj)) if rows != "0" else (0, 4)
+        else:
+            monkeypatch.setenv("OGG_MIDAS_TARGET_WG", target)
+            h = min(int(rows), 12, nj)
+            want = (4 if h <= 4 else 6 if h <= 6 else 8 if h <= 8 else 12, h) if rows != "0" else (0, min(max(nj * gx, 4), 16))
+        assert stencil_plans.planned(hip, ni, nj, True) == want, (target, rows)
         got = ogg.generate_grid_metrics_MIDAS(x, y) + ogg.generate_grid_metrics_MIDAS(x, y, latlon_areafix=False)[2:] + (ogg.angle_x(x, y),)
         if ref is None:
             ref = got
@@ -162,7 +189,7 @@ def test_midas_tile_heights_and_streaming_kernel_agree_bitwise(ogg, shape, monke
             assert maxrel(got[0], odx) < 2e-15 and maxrel(got[1], ody) < 2e-15 and maxabs(got[2], oar) <= 5e-12 * np.abs(oar).max()
             continue
         for k, (a, b) in enumerate(zip(ref, got)):
-            assert np.array_equal(a, b), (rows, k, float(np.abs(a - b).max()))
+            assert np.array_equal(a, b), (target, rows, k, float(np.abs(a - b).max()))
 
 
 def test_midas_mercator_r8_band(ogg):
@@ -173,7 +200,10 @@ def test_midas_mercator_r8_band(ogg):
     odx, ody, oar = orc.generate_grid_metrics_MIDAS(xo, yo)
     record("midas_r8_band", dx=maxabs(dx, odx), dy=maxabs(dy, ody), area=maxabs(area, oar), area_rel=maxrel(area, oar))
     assert maxrel(dx, odx) < 2e-15 and maxrel(dy, ody) < 2e-15 and maxrel(area, oar) < 5e-12
-    assert np.array_equal(ogg.angle_x(xo, yo), orc.angle_x(xo, yo))     # atan2(0, +) == 0 on a lat-lon mesh
+    ang = ogg.angle_x(xo, yo)
+    assert np.array_equal(ang, orc.angle_x(xo, yo))     # atan2(0, +) == 0 on a lat-lon mesh
+    rep = stencil_bounds.check_against_oracle(xo, yo, {"dx": dx, "dy": dy, "area": area, "angle": ang}, name="Mercator 1/8 degree band")
+    record("midas_r8_band_conditioned", **{f: r["worst_over_bound"] for f, r in rep.items()})
 
 
 def test_midas_mercator_r16_band(ogg):

@@ -5,6 +5,7 @@ test_gpu_parity.py (module docstring there)."""
 import numpy as np
 import pytest
 
+import stencil_bounds
 from oracle import ogg_oracle as orc
 from test_gpu_parity import _check_supergrid, dp_quad_rel_tol
 
@@ -117,6 +118,9 @@ def test_midas_and_angle_random_meshes(ogg, seed):
         assert dx.shape == odx.shape and dy.shape == ody.shape and area.shape == oarea.shape
         assert np.all(np.abs(dx - odx) <= 1e-9 + 5e-15 * np.abs(odx)) and np.all(np.abs(dy - ody) <= 1e-9 + 5e-15 * np.abs(ody))
         assert np.all(np.abs(area - oarea) <= 1e-3 + 5e-11 * np.abs(oarea))
+        stencil_bounds.check_against_oracle(x, y, {"dx": dx, "dy": dy, "area": area, "angle": a}, name="random mesh %d" % seed)
+    else:
+        stencil_bounds.check_against_oracle(x, y, {"angle": a}, name="random mesh %d" % seed)
 
 
 @pytest.mark.parametrize("seed", range(6))
