@@ -80,7 +80,10 @@ const char* ogg_version(void);
 #define OGG_ABI_BASIN_COUNTS 27
 #define OGG_ABI_XGRID_CS_ATM 28
 #define OGG_ABI_XGRID_CS_COUNTS 29
-#define OGG_ABI_N 30
+#define OGG_ABI_LAYOUT_PARAMS 30
+#define OGG_ABI_LAYOUT_CANDIDATE 31
+#define OGG_ABI_LAYOUT_RECORD 32
+#define OGG_ABI_N 33
 long ogg_abi_sizeof(int which);
 int ogg_device_count(int* count);
 int ogg_set_device(int device);
@@ -1314,6 +1317,99 @@ int ogg_basin_codes_dev(const ogg_basin_params* p, const ogg_basin_rule* rules, 
 /* HOST pointers throughout, staged through device memory: x, y (2 ny + 1) x (2 nx + 1) */
 int ogg_basin_codes(const ogg_basin_params* p, const ogg_basin_rule* rules, const double* x, const double* y, const unsigned char* wet,
                     unsigned char* code, short* rule, ogg_basin_rule_record* records, ogg_basin_counts* counts);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Processor layouts and mask tables (an addition: the reference has none).  For a decomposition of the model cells into px x py
+ * blocks (MOM6's LAYOUT = px,py) the blocks that hold no ocean, which a model run leaves without a process (MASKTABLE =
+ * mask_table.<n>.<px>x<py>), and for many candidate layouts at once the record from which one is chosen.
+ *   cells    ny x nx model cells, one wet byte per cell (0: land), ny * nx < 2^31.  topology: OGG_MASK_PERIODIC | OGG_MASK_FOLD, the
+ *            neighbour rule of csrc/ogg_cells.h: the fold partner of (ny-1, i) is (ny-1, nx-1-i).
+ *   extents  ogg_layout_extent(npts, ndivs, begin, end) divides 0 .. npts-1 into ndivs blocks, 1 <= ndivs <= npts, by FMS's
+ *            mpp_compute_extent restated in integers:
+ *                isg = 0; ieg = npts-1
+ *                sym = (ndivs odd and npts even) ? (ndivs < npts/2) : (ndivs%2 == npts%2)
+ *                is = 0; imax = ieg; ndmax = ndivs
+ *                for nd = 0 .. ndivs-1:
+ *                    if nd < (ndivs-1)/2 + 1:
+ *                        ie = is + ceil((imax-is+1) / (ndmax-nd)) - 1          # ceil(a/d) = (a+d-1)/d in integers
+ *                        m = ndivs-1-nd
+ *                        if m > nd and sym:
+ *                            begin[m] = max(isg+ieg-ie, ie+1); end[m] = max(isg+ieg-is, ie+1)
+ *                            imax = begin[m]-1; ndmax = ndmax-1
+ *                    else if sym: is = begin[nd]; ie = end[nd]
+ *                    else:        ie = is + ceil((imax-is+1) / (ndmax-nd)) - 1
+ *                    begin[nd] = is; end[nd] = ie; is = ie+1
+ *            The result is a partition into non-empty consecutive blocks (end[nd] + 1 = begin[nd + 1]), mirror-symmetric whenever
+ *            sym holds, with block sizes that differ by at most 2.  One __host__ __device__ body serves this function and the sweep
+ *            kernel; it keeps the begins alone and reads end[nd] as begin[nd + 1] - 1, which the partition allows.  FMS forms the
+ *            quotient in single precision; for npts < 1e7 the integer ceiling is the same number, since the smallest fraction 1/d
+ *            exceeds the quotient's rounding error.  CAVEAT: the rule is written from FMS's rule as understood here; no copy of FMS or
+ *            FRE-NCtools was on hand to verify it against.  Explicit extents (ogg_layout_blocks_dev) therefore tie a table to a
+ *            model's own decomposition, whatever its rule.
+ *   layout   (px, py) with px <= nx, py <= ny, both <= OGG_LAYOUT_MAX_DIV: the x extents from (nx, px), the y extents from (ny, py).
+ *            Block (a, b) holds columns bx[a] .. ex[a] and rows by[b] .. ey[b]; wet(a, b) is the number of wet cells in it.
+ *   halo     h >= 0.  The neighbourhood of block (a, b) is the SET of cells reached from (j, i) with by-h <= j <= ey+h and
+ *            bx-h <= i <= ex+h: a column outside 0 .. nx-1 wraps modulo nx on a periodic grid and is dropped otherwise; a row below 0
+ *            is dropped; a row ny + k maps on a folded grid to row ny-1-k at column nx-1-i', i' the column after wrapping, and is
+ *            dropped when k >= ny or without a fold.  nbr(a, b) is the number of wet cells in that set (each cell once); the kernels
+ *            get it from a few rectangles of the summed-area table, the overlap of the rows past the fold with the rows below it
+ *            taken off.
+ *   masked   a block is MASKED when nbr(a, b) = 0; with h = 0, when all its own cells are land.
+ *   record   of a layout: blocks = px * py; masked; pes = blocks - masked; max_block_cells = largest x size * largest y size;
+ *            max_block_edge = largest x size + largest y size; min_block_size = the smallest size in either direction; max_wet = the
+ *            largest wet(a, b); masked_cells = the cells in masked blocks; wet_total = the wet cells of the grid; status:
+ *            OGG_LAYOUT_TOO_FINE: px > nx, py > ny, either above OGG_LAYOUT_MAX_DIV (or below 1, which ogg_layout_check refuses on
+ *            the host): every other field is 0.  OGG_LAYOUT_FOLD_ASYMMETRIC: a folded grid whose x extents are not mirror images,
+ *            bx[a] + ex[px-1-a] != nx-1 for some a; FMS refuses such a decomposition of a tripolar grid.  The other fields are
+ *            filled all the same.
+ *   ranking  (host code over the records, layout.py) for a target of T processes: among the records with status == 0 and pes == T
+ *            the smallest key (max_block_cells, max_block_edge, blocks, px); the cost of a step goes with the block size, not the wet
+ *            count.
+ *   table    of one layout: the masked blocks in ascending (b, a), written 1-based as "a+1,b+1".
+ * Everything is an integer: the result is bit-identical for any launch geometry (OGG_LAYOUT_TILE_ROWS, the rows of a tile of the
+ * table's column pass, 4 .. 1024, default 32; OGG_LAYOUT_GRID, the workgroups of the sweep, 0: one per candidate) and any rank
+ * count on the gathered wet set.
+ * ---------------------------------------------------------------------------------------------------- */
+#define OGG_LAYOUT_MAX_DIV 4096
+#define OGG_LAYOUT_MAX_CANDIDATES (1 << 20)
+enum { OGG_LAYOUT_TOO_FINE = 1, OGG_LAYOUT_FOLD_ASYMMETRIC = 2 };
+/* ny * nx < 2^31 */
+typedef struct ogg_layout_params {
+    long ny, nx;               /* model cells */
+    int topology;              /* OGG_MASK_PERIODIC | OGG_MASK_FOLD */
+    int halo;                  /* h >= 0 */
+} ogg_layout_params;
+typedef struct ogg_layout_candidate {
+    int px, py;
+} ogg_layout_candidate;
+typedef struct ogg_layout_record {
+    int blocks, masked, pes;
+    int max_block_cells, max_block_edge, min_block_size;
+    int max_wet, masked_cells, wet_total;
+    int status;                /* OGG_LAYOUT_TOO_FINE | OGG_LAYOUT_FOLD_ASYMMETRIC */
+} ogg_layout_record;
+/* the extents of the rule above (host only, no device work): begin and end have room for ndivs entries; end may be NULL */
+int ogg_layout_extent(long npts, long ndivs, int* begin, int* end);
+/* the checks of *p (sizes, topology, halo) and of the n candidates (HOST memory, NULL with n = 0; every px, py >= 1 and n <=
+ * OGG_LAYOUT_MAX_CANDIDATES): OGG_EARG with the reason, before any device work.  A candidate finer than the grid is no error: its
+ * record says OGG_LAYOUT_TOO_FINE. */
+int ogg_layout_check(const ogg_layout_params* p, const ogg_layout_candidate* candidates, long n);
+long ogg_layout_workspace_bytes(const ogg_layout_params* p);   /* -1 on a bad *p */
+/* the summed-area table of wet (device memory, ny * nx bytes) into the workspace: (ny + 1) x (nx + 1) int32 counts */
+int ogg_layout_table_dev(const ogg_layout_params* p, const unsigned char* wet, void* workspace, long workspace_bytes, void* stream);
+/* after ogg_layout_table_dev on the same workspace: the records (device memory) of the n candidates (device memory, n <=
+ * OGG_LAYOUT_MAX_CANDIDATES; a px or py below 1 counts as OGG_LAYOUT_TOO_FINE), one workgroup per candidate */
+int ogg_layout_sweep_dev(const ogg_layout_params* p, const ogg_layout_candidate* candidates, long n, const void* workspace,
+                         long workspace_bytes, ogg_layout_record* records, void* stream);
+/* after ogg_layout_table_dev on the same workspace: wet(a, b) and nbr(a, b) of every block of one layout (device memory, py x px
+ * int32 each).  xbegin, ybegin: HOST memory, NULL for the rule's extents, else the px (py) first columns (rows) of the blocks,
+ * strictly increasing from 0 and below nx (ny); px, py <= OGG_LAYOUT_MAX_DIV. */
+int ogg_layout_blocks_dev(const ogg_layout_params* p, int px, int py, const int* xbegin, const int* ybegin, void* workspace,
+                          long workspace_bytes, int* block_wet, int* block_nbr, void* stream);
+/* HOST pointers throughout, staged through device memory: the table, then the records of the n candidates (records NULL with n = 0),
+ * then, unless block_wet and block_nbr are NULL, the blocks of the layout (px, py) with xbegin, ybegin as above */
+int ogg_layouts(const ogg_layout_params* p, const unsigned char* wet, const ogg_layout_candidate* candidates, long n,
+                ogg_layout_record* records, int px, int py, const int* xbegin, const int* ybegin, int* block_wet, int* block_nbr);
 
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);

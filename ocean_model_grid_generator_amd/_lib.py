@@ -254,6 +254,19 @@ class BilinearParams(ctypes.Structure):
 BILINEAR_H, BILINEAR_U, BILINEAR_V, BILINEAR_C = 0, 1, 2, 3            # OGG_BILINEAR_H ... OGG_BILINEAR_C
 BILINEAR_POINTS = {"h": BILINEAR_H, "u": BILINEAR_U, "v": BILINEAR_V, "c": BILINEAR_C}
 
+class LayoutParams(ctypes.Structure):
+    """ogg_layout_params of include/ogg_hip.h"""
+    _fields_ = [("ny", c_long), ("nx", c_long), ("topology", c_int), ("halo", c_int)]
+
+
+# ogg_layout_candidate and ogg_layout_record as numpy records (8 and 40 bytes)
+LAYOUT_CANDIDATE = np.dtype([("px", "<i4"), ("py", "<i4")])
+LAYOUT_RECORD_FIELDS = ("blocks", "masked", "pes", "max_block_cells", "max_block_edge", "min_block_size", "max_wet", "masked_cells",
+                        "wet_total", "status")
+LAYOUT_RECORD = np.dtype([(f, "<i4") for f in LAYOUT_RECORD_FIELDS])
+LAYOUT_MAX_DIV, LAYOUT_MAX_CANDIDATES = 4096, 1 << 20                  # OGG_LAYOUT_MAX_DIV, OGG_LAYOUT_MAX_CANDIDATES
+LAYOUT_TOO_FINE, LAYOUT_FOLD_ASYMMETRIC = 1, 2                         # OGG_LAYOUT_TOO_FINE, OGG_LAYOUT_FOLD_ASYMMETRIC
+
 # OGG_ABI_* of include/ogg_hip.h, in code order: name -> the mirror of ogg_<name> (a ctypes.Structure or a numpy record), whose size
 # ogg_abi_sizeof(code) must give (tests/test_abi.py)
 ABI_MIRRORS = {"LATLON_BAND": LatlonBand, "BIPOLAR_BAND": BipolarBand, "DPOLE_BAND": DpoleBand, "QUALITY_EXTREMUM": QualityExtremum,
@@ -263,7 +276,8 @@ ABI_MIRRORS = {"LATLON_BAND": LatlonBand, "BIPOLAR_BAND": BipolarBand, "DPOLE_BA
                "REMAP_COUNTS": RemapCounts, "RUNOFF_PARAMS": RunoffParams, "RUNOFF_COUNTS": RunoffCounts, "REGRID_PARAMS": RegridParams,
                "REGRID_COUNTS": RegridCounts, "BILINEAR_PARAMS": BilinearParams, "COAST_PARAMS": CoastParams, "COAST_COUNTS": CoastCounts,
                "BASIN_PARAMS": BasinParams, "BASIN_RULE": BASIN_RULE, "BASIN_RULE_RECORD": BASIN_RECORD, "BASIN_COUNTS": BasinCounts,
-               "XGRID_CS_ATM": XgridCsAtm, "XGRID_CS_COUNTS": XgridCsCounts}
+               "XGRID_CS_ATM": XgridCsAtm, "XGRID_CS_COUNTS": XgridCsCounts, "LAYOUT_PARAMS": LayoutParams, "LAYOUT_CANDIDATE": LAYOUT_CANDIDATE,
+               "LAYOUT_RECORD": LAYOUT_RECORD}
 ABI = {name: code for code, name in enumerate(ABI_MIRRORS)}
 
 
@@ -424,6 +438,14 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "ogg_bilinear": [ctypes.POINTER(BilinearParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_layout_extent": [c_long, c_long, c_void_p, c_void_p],
+    "ogg_layout_check": [ctypes.POINTER(LayoutParams), c_void_p, c_long],
+    "ogg_layout_table_dev": [ctypes.POINTER(LayoutParams), c_void_p, c_void_p, c_long, c_void_p],
+    "ogg_layout_sweep_dev": [ctypes.POINTER(LayoutParams), c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p],
+    "ogg_layout_blocks_dev": [ctypes.POINTER(LayoutParams), c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p,
+                              c_void_p],
+    "ogg_layouts": [ctypes.POINTER(LayoutParams), c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                    c_void_p],
     "ogg_event_create": [ctypes.POINTER(c_void_p)],
     "ogg_event_destroy": [c_void_p],
     "ogg_event_record": [c_void_p, c_void_p],
@@ -452,7 +474,8 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],
                 "ogg_coast_workspace_bytes": [ctypes.POINTER(CoastParams)],
                 "ogg_basin_workspace_bytes": [ctypes.POINTER(BasinParams)],
-                "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long]}
+                "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long],
+                "ogg_layout_workspace_bytes": [ctypes.POINTER(LayoutParams)]}
 
 _lib = None
 

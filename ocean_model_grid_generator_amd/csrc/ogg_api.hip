@@ -228,6 +228,9 @@ long ogg_abi_sizeof(int which) {
         case OGG_ABI_BASIN_COUNTS: return (long)sizeof(ogg_basin_counts);
         case OGG_ABI_XGRID_CS_ATM: return (long)sizeof(ogg_xgrid_cs_atm);
         case OGG_ABI_XGRID_CS_COUNTS: return (long)sizeof(ogg_xgrid_cs_counts);
+        case OGG_ABI_LAYOUT_PARAMS: return (long)sizeof(ogg_layout_params);
+        case OGG_ABI_LAYOUT_CANDIDATE: return (long)sizeof(ogg_layout_candidate);
+        case OGG_ABI_LAYOUT_RECORD: return (long)sizeof(ogg_layout_record);
         default: return -1L;
     }
 }

@@ -668,7 +668,8 @@ class AnalysisFlags(object):
                     xgrid_frac_file=None, interp_source=None, interp_var=None, interp_vector=None, interp_points="h",
                     interp_file="interp.nc", interp_no_fill=False, interp_fill_max=None, interp_no_rotate=False, xgrid_cs=None,
                     xgrid_cs_spacing="equiangular", xgrid_cs_lon_shift=0.0, xgrid_cs_file="atmos_mosaic_tile%dXocean_mosaic_tile1.nc",
-                    xgrid_cs_frac_file=None)
+                    xgrid_cs_frac_file=None, mask_table_layout=None, mask_table_dir=None, layout_sweep=None, layout_target_pes=None,
+                    layout_report=None, layout_halo=0, layout_min_block=2, layout_xextent=None, layout_yextent=None)
 
     def __init__(self, **flags):
         unknown = sorted(set(flags) - set(self.DEFAULTS))
@@ -686,6 +687,7 @@ def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
     _validate_runoff_flags(a.runoff_source, a.runoff_var, a.topog_source, a.runoff_targets, skip_metrics)
     _validate_coast_distance_flags(a.coast_distance_file, a.coast_distance_sides, a.topog_source)
     _validate_basin_flags(a.basin_codes_file, a.basin_rules, a.basin_seed_max_km, a.topog_source)
+    _validate_layout_flags(a)
     _validate_frac_flags(a.xgrid_frac_file, a.xgrid_atm)
     _validate_xgrid_cs_flags(a.xgrid_cs, a.xgrid_cs_spacing, a.xgrid_cs_file, a.xgrid_cs_frac_file, a.xgrid_atm, a.xgrid_file)
     _validate_interp_flags(a.interp_source, a.interp_var, a.interp_vector, a.interp_points, skip_metrics, a.interp_no_fill,
@@ -705,7 +707,9 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          interp_source=None, interp_var=None, interp_vector=None, interp_points="h", interp_file="interp.nc", interp_no_fill=False,
          interp_fill_max=None, interp_no_rotate=False, topog_roughness=False, coast_distance_file=None, coast_distance_sides="both",
          basin_codes_file=None, basin_rules=None, basin_seed_max_km=None, xgrid_cs=None, xgrid_cs_spacing="equiangular",
-         xgrid_cs_lon_shift=0.0, xgrid_cs_file="atmos_mosaic_tile%dXocean_mosaic_tile1.nc", xgrid_cs_frac_file=None):
+         xgrid_cs_lon_shift=0.0, xgrid_cs_file="atmos_mosaic_tile%dXocean_mosaic_tile1.nc", xgrid_cs_frac_file=None,
+         mask_table_layout=None, mask_table_dir=None, layout_sweep=None, layout_target_pes=None, layout_report=None, layout_halo=0,
+         layout_min_block=2, layout_xextent=None, layout_yextent=None):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -749,7 +753,14 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     with ``ocean_mask_file``), written to FILE; also an addition.  ``xgrid_cs`` (--xgrid_cs N): write the exchange grid of the model
     cells with a gnomonic cubed-sphere atmosphere of six tiles of N x N cells (exchange_grid_cs.py; ``xgrid_cs_spacing``: equiangular
     or edge_equidistant; the module's default cube turned by ``xgrid_cs_lon_shift`` degrees; the wet set of ``xgrid_atm``) to the six
-    files ``xgrid_cs_file`` % tile, and the ocean and land fractions of its cells to ``xgrid_cs_frac_file``; also an addition."""
+    files ``xgrid_cs_file`` % tile, and the ocean and land fractions of its cells to ``xgrid_cs_frac_file``; also an addition.
+    ``mask_table_layout`` (--mask_table_layout PX PY, repeatable, needs ``topog_source``): the FMS mask table of each layout, the
+    blocks without a wet cell within ``layout_halo`` cells (layout.py; the edited wet set with ``ocean_mask_file``; the block sizes
+    of ``layout_xextent`` / ``layout_yextent`` instead of the rule's for one layout), written to ``mask_table_dir`` under its default
+    name with the LAYOUT and MASKTABLE lines printed; ``layout_sweep`` (--layout_sweep MAX_BLOCKS): the record of every layout of at
+    most MAX_BLOCKS blocks whose blocks have at least ``layout_min_block`` cells a side, and with ``layout_target_pes`` the layout
+    of the smallest blocks among those that run on exactly that many processes, whose table is written when no layout is named;
+    ``layout_report``: the ranking and the tables as JSON; also an addition."""
     flags = dict(locals())   # the arguments, by name: taken before anything else is bound
     import time
 
@@ -1074,7 +1085,7 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
 
 def _run_analyses(a, g, cut=None):
     """The analyses that follow the grid (``a``: AnalysisFlags), each printed and written as it is done, in their one order: quality
-    report, topography and ocean mask, distance to the coast, basin codes, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
+    report, topography and ocean mask, distance to the coast, basin codes, processor layouts and mask tables, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
     Supergrid with its ``cut`` (main) or the _StitchedArrays of main_function_level."""
     if a.quality_report:
         _write_quality_report(g.quality(cut), a.quality_report)
@@ -1091,6 +1102,9 @@ def _run_analyses(a, g, cut=None):
     if a.basin_codes_file:
         from . import basin_codes as BC
         _write_basin_codes(g.basin_codes(cut, wet, BC.read_rules(str(a.basin_rules)), seed_max_km=a.basin_seed_max_km), a.basin_codes_file)
+    if _layout_wanted(a):
+        from . import layout as LY
+        LY.run_flags(a, lambda **kw: g.layouts(cut, wet, **kw), lambda px, py, **kw: g.mask_table(cut, wet, px, py, **kw))
     if a.xgrid_atm is not None:
         from . import exchange_grid as X
         xres = g.exchange_grid(cut, X.regular_atm(*a.xgrid_atm), mask=wet)
@@ -1167,6 +1181,20 @@ class _StitchedArrays(object):
         from . import runoff as RO
         return BC.basin_codes(self.x, self.y, wet, rules, seed_max_distance=None if seed_max_km is None else 1000.0 * seed_max_km,
                               Re=_default_Re, area=None if self.metrics[2] is None else RO.cell_area(self.metrics[2]))
+
+    def _topology(self):
+        from . import ocean_mask as M
+        return M.detect_topology(self.x, self.y, 2)
+
+    def layouts(self, cut, wet, **args):
+        from . import layout as LY
+        periodic, fold = self._topology()
+        return LY.layouts(wet, periodic=periodic, fold=fold, **args)
+
+    def mask_table(self, cut, wet, px, py, **args):
+        from . import layout as LY
+        periodic, fold = self._topology()
+        return LY.mask_table(wet, px, py, periodic=periodic, fold=fold, **args)
 
     def bilinear(self, cut, source, source2=None, **args):
         from . import bilinear as B
@@ -1266,6 +1294,15 @@ def _validate_basin_flags(basin_codes_file, basin_rules, basin_seed_max_km, topo
         raise ValueError("--basin_codes_file needs --topog_source: the basins are those of the topography's wet cells")
     if basin_seed_max_km is not None and not (float(basin_seed_max_km) >= 0.0):
         raise ValueError("--basin_seed_max_km must be >= 0, not %r" % (basin_seed_max_km,))
+
+
+def _layout_wanted(a):
+    return bool(a.mask_table_layout) or a.layout_sweep is not None
+
+
+def _validate_layout_flags(a):
+    from . import layout as LY
+    LY.validate_flags(a, a.topog_source)
 
 
 def _write_basin_codes(res, fnam):
@@ -1499,6 +1536,8 @@ def build_parser():
                         help="the rule file of --basin_codes_file: code seed_lon seed_lat lon_w lon_e lat_s lat_n [name] per line")
     parser.add_argument("--basin_seed_max_km", type=float, required=False, default=None,
                         help="a seed farther than this from every cell centre is off the grid (default: any distance)")
+    from . import layout as LY
+    LY.add_flags(parser)
     parser.add_argument("--xgrid_frac_file", type=str, required=False, default=None,
                         help="write the ocean / land fraction, area and exchange-cell count of every --xgrid_atm atmosphere cell to this "
                              "file (wet cells only when --topog_source is given)")

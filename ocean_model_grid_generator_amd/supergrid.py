@@ -1641,6 +1641,34 @@ class Supergrid(object):
         return BC.basin_codes_dev(xy[0], xy[1], wet, rules, seed_max_distance=None if seed_max_km is None else 1000.0 * seed_max_km,
                                   Re=float(self.plan.Re), area=None if area is None else RO.cell_area(area.cpu().numpy()))
 
+    # -- processor layouts and mask tables ----------------------------------------------------------------------------
+    def _layout_table(self, cut, wet, halo):
+        """The layout.DeviceTable of the wet set ``wet`` (one value per model cell, 0: land) on rank 0's GPU, None on the other ranks:
+        the periodic seam and the fold come from the stitched points gathered there, as basin_codes gathers them."""
+        from . import fields as F
+        from . import layout as LY
+        from . import ocean_mask as M
+        xy = self.stitched_xy(cut)
+        if xy is None:
+            return None
+        shape = ((xy[0].shape[0] - 1) // 2, (xy[0].shape[1] - 1) // 2)
+        m = F.wet_mask(wet.cpu().numpy() if hasattr(wet, "cpu") else wet, shape, "layouts")
+        periodic, fold = M.topology_of_device_grid(xy[0], xy[1])
+        return LY.DeviceTable(self.torch.from_numpy(m).to(self.device), periodic, fold, halo)
+
+    def layouts(self, cut, wet, candidates=None, max_blocks=None, halo=0, min_block=2):
+        """The records of the candidate layouts (layout.layouts' dict on rank 0, None on the other ranks) of the stitched grid's model
+        cells with the wet set ``wet``: integers of the gathered wet set, so the same bits for any number of ranks."""
+        from . import layout as LY
+        t = self._layout_table(cut, wet, halo)
+        return None if t is None else LY.layouts_dev(None, candidates=candidates, max_blocks=max_blocks, min_block=min_block, table=t)
+
+    def mask_table(self, cut, wet, px, py, halo=0, xextent=None, yextent=None):
+        """The mask table of the layout (px, py) (layout.mask_table's dict on rank 0, None on the other ranks), as layouts()."""
+        from . import layout as LY
+        t = self._layout_table(cut, wet, halo)
+        return None if t is None else LY.mask_table_dev(None, px, py, xextent=xextent, yextent=yextent, table=t)
+
     # -- bilinear interpolation ---------------------------------------------------------------------------------------
     def stitched_angle(self, cut):
         """The stitched angle_dx ((nyp, nxp) float64 device tensor) on rank 0's device, None on the other ranks (_stitched)."""
