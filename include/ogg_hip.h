@@ -83,7 +83,9 @@ const char* ogg_version(void);
 #define OGG_ABI_LAYOUT_PARAMS 30
 #define OGG_ABI_LAYOUT_CANDIDATE 31
 #define OGG_ABI_LAYOUT_RECORD 32
-#define OGG_ABI_N 33
+#define OGG_ABI_LOCATE_PARAMS 33
+#define OGG_ABI_LOCATE_COUNTS 34
+#define OGG_ABI_N 35
 long ogg_abi_sizeof(int which);
 int ogg_device_count(int* count);
 int ogg_set_device(int device);
@@ -1410,6 +1412,109 @@ int ogg_layout_blocks_dev(const ogg_layout_params* p, int px, int py, const int*
  * then, unless block_wet and block_nbr are NULL, the blocks of the layout (px, py) with xbegin, ybegin as above */
 int ogg_layouts(const ogg_layout_params* p, const unsigned char* wet, const ogg_layout_candidate* candidates, long n,
                 ogg_layout_record* records, int px, int py, const int* xbegin, const int* ybegin, int* block_wet, int* block_nbr);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Point location (an addition: the reference has none).  The inverse of every other analysis here: given a longitude and a latitude,
+ * the model cell that holds the point, where in the cell it lies, and a model field there (moorings, tide gauges, profiles, section
+ * end points, mask and basin seeds, the depth at a river mouth).  The definition needs no walk over the grid: every cell has a key
+ * for every point, and the answer is the best key.
+ *   cells    those of the cell-set analyses: ny x nx model cells, c = j * nx + i; the corners of cell (j, i) are the supergrid points
+ *            (2j, 2i) SW = a, (2j, 2i+2) SE = b, (2j+2, 2i+2) NE = c, (2j+2, 2i) NW = d.  Edges are GREAT CIRCLES between the corners'
+ *            unit vectors, the rule of the cubed-sphere exchange grid (not the lat-lon polygons of the lat-lon exchange grid).
+ *            ny * nx * OGG_LOCATE_MAX_TOUCH < 2^31 (the index's entries are counted in 32 bits), and fewer than 2^31 queries.
+ *   corner table  cu[(ny+1)(nx+1)][3]: unit(x, y) of csrc/ogg_sphere.h (the one shared implementation, "Runoff mapping") of every
+ *            corner (J, I).  With OGG_MASK_PERIODIC corner column nx takes the bits of column 0 of its row; with OGG_MASK_FOLD the
+ *            top-row corner I takes the bits of the smallest I among its copies, I and nx - I after the periodic reduction.  (The
+ *            table is formed from the canonical copy's x and y.)  A shared corner is therefore one set of bits in every cell that has
+ *            it.  cu and the queries' vectors qu[n][3] (the same unit()) are device outputs.
+ *   edge measure  n(a,b) = (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx) and T(p; a,b) = (px*nx + py*ny) + pz*nz, every product
+ *            rounded, no FMA.  In this order T(p; b,a) = -T(p; a,b) EXACTLY: what one cell sees across a face, its neighbour sees
+ *            negated, bit for bit.  S = T(p; a,b), E = T(p; b,c), N = T(p; c,d), W = T(p; d,a).
+ *   orientation  O = ((a+b)+(c+d)) . ((n_S+n_E)+(n_N+n_W)), the sums by component, the dot product in T's order; sigma = +1 when
+ *            O > 0, -1 when O < 0.  A cell whose O is 0 or not finite holds no point (a NaN corner, a fully collapsed cell).
+ *   box      L2 the largest dist2 ("Runoff mapping") between two of the cell's corners, pad = 0.25 * L2 + 2^-40; p is in the cell's
+ *            box when every component of p lies within [min over the corners - pad, max over the corners + pad].  The box is part of
+ *            the definition: it bounds what sliver and half-collapsed cells can claim, and it is what the search index registers.
+ *   key      m_c(p) = min(sigma S, sigma E, sigma N, sigma W).  Cell c is a candidate of p when p is in its box and
+ *            m_c >= -OGG_LOCATE_TOL.
+ *   answer   the candidate with the largest m_c, ties to the smaller c.  No candidate, or a query vector with a component that is
+ *            not finite (a longitude or latitude that is not finite): cell = -1 and s = t = m = NaN.
+ *   position s = sigma W / (sigma W + sigma E) and t = sigma S / (sigma S + sigma N), each clamped to [0, 1], and 0.5 when the
+ *            denominator is not > 0.  An edge whose two corners have the same bits has a zero normal; its measure is replaced
+ *            through the opposite edge: N collapsed: sigma N := sigma (c . n_S) - sigma S; S collapsed: sigma S := sigma (a . n_N) -
+ *            sigma N; E collapsed: sigma E := sigma (b . n_W) - sigma W; W collapsed: sigma W := sigma (a . n_E) - sigma E (the dot
+ *            products in T's order); both of a pair collapsed: 0.5.  (s, t) is exact on parallelograms in the small-cell limit, s = 0
+ *            on the W edge and 1 on the E edge; it is the inverse of no particular map.
+ *   sampling a field on the model cells, f[r][j][i], r < nrec, OGG_REMAP_FLOAT32 or OGG_REMAP_FLOAT64; a value is MISSING by the
+ *            remap's rule (NaN, or one of up to two fill values compared in the field's own type); an optional wet byte per cell.  A
+ *            cell is USED when it exists, is wet and its value is not missing.
+ *            OGG_LOCATE_CELL: the value of cell c.  OGG_LOCATE_BILINEAR: index-space bilinear between the four nearest centres:
+ *            fx = |s - 0.5|, fy = |t - 0.5|; C00 = c; C10 c's E neighbour when s >= 0.5, else its W neighbour; C01 c's N neighbour
+ *            when t >= 0.5, else its S neighbour; C11 the neighbour of C10 in that same y direction (none when C10 is none);
+ *            neighbours are face_neighbours of csrc/ogg_cells.h, so across the fold this is "x first, then N".  Weights in the order
+ *            C00, C10, C01, C11: (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy.  Over the used cells, in that order, W = sum of w and
+ *            S = sum of (w * f), in fp64 from 0; the value is S / W.
+ *   flags    one byte per (record, point): 0 no cell; 1 all four used (CELL: the cell is used); 2 fewer than four used; 3 none
+ *            used, or the containing cell is dry, or W is not > 0.  With flag 0 or 3 the value is OGG_REMAP_FILL.
+ * Every output of a query is a function of cu, the topology flags and that query's own qu: no index, cube count, knob
+ * (OGG_LOCATE_CUBES: cubes per axis of the index, 0: from the cell count; OGG_LOCATE_BRUTE=1: every cell that can hold a point is
+ * tested for every query), query order or rank count changes a bit.
+ * OGG_LOCATE_TOL: near a vertex the four rounded half-plane tests of the cells around it can disagree in a pinwheel, so that no cell
+ * has m >= 0; on jittered lat-lon meshes of 0.01 to 3 degrees the worst best-m over corners, edge midpoints and their 1-ulp
+ * neighbours is about -1e-17 (tests/test_locate_cpu.py measures it).  2^-50 covers that a hundred times over and stays below 4e-6
+ * of a cell's own T scale for cells down to 100 m across; grids with cells of a few metres are outside its design.
+ * Output layout: cell int32, s, t, m fp64, one per query; values (nrec, n) fp64 and flags (nrec, n) bytes.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { OGG_LOCATE_CELL = 0, OGG_LOCATE_BILINEAR = 1 };
+#define OGG_LOCATE_TOL 8.8817841970012523e-16   /* 2^-50 */
+#define OGG_LOCATE_MAX_CUBES 128   /* the largest OGG_LOCATE_CUBES: cubes per axis of the search index */
+#define OGG_LOCATE_MAX_TOUCH 27    /* a cell whose box touches more cubes than this is on the large-cells list */
+typedef struct ogg_locate_params {
+    long ny, nx;               /* model cells */
+    long n;                    /* queries (>= 0) */
+    long nrec;                 /* records of the sampled field (0: nothing is sampled) */
+    int topology;              /* OGG_MASK_PERIODIC | OGG_MASK_FOLD */
+    int mode;                  /* OGG_LOCATE_CELL / OGG_LOCATE_BILINEAR */
+    int dtype;                 /* OGG_REMAP_FLOAT32 / OGG_REMAP_FLOAT64 */
+    int n_fill;                /* 0 .. 2 fill values */
+    double fill[2];
+} ogg_locate_params;
+typedef struct ogg_locate_counts {
+    long long located;         /* queries with a cell (search step) */
+    long long outside;         /* finite queries without a candidate (search step) */
+    long long invalid;         /* queries with a coordinate that is not finite (search step) */
+    long long large_cells;     /* cells on the large-cells list; with OGG_LOCATE_BRUTE every cell that can hold a point (index step) */
+    long long cubes;           /* cubes per axis of the index, 0 for brute force (index step) */
+    long long tests;           /* (query, cell) box tests (search step) */
+    long long flag0, flag1, flag2, flag3;   /* (record, point) pairs by flag (sample step) */
+} ogg_locate_counts;
+long ogg_locate_workspace_bytes(const ogg_locate_params* p);   /* of the sets, index and search steps, -1 on a bad *p */
+/* the checks of *p (sizes, topology, mode, dtype, fills): OGG_EARG with the reason, before any device work */
+int ogg_locate_check(const ogg_locate_params* p);
+/* sets step, device pointers, on a stream: x, y the supergrid points (2 ny + 1 rows of ld doubles); cu the corner table
+ * ((ny + 1) * (nx + 1) * 3 doubles); the per-cell records (sigma times the four normals, the box) go into the workspace.  *counts
+ * (device memory) is zeroed. */
+int ogg_locate_sets_dev(const ogg_locate_params* p, const double* x, const double* y, long ld, void* workspace, long workspace_bytes,
+                        double* cu, ogg_locate_counts* counts, void* stream);
+/* index step, after the sets step on the same workspace: every cell that can hold a point registered in every cube its box touches, or
+ * on the large-cells list; large_cells and cubes into *counts */
+int ogg_locate_index_dev(const ogg_locate_params* p, void* workspace, long workspace_bytes, ogg_locate_counts* counts, void* stream);
+/* search step, after the index step on the same workspace: lon, lat (n doubles each, degrees) -> qu (3 n doubles), cell, s, t, m as
+ * above; located, outside, invalid and tests into *counts, from zero */
+int ogg_locate_search_dev(const ogg_locate_params* p, const double* cu, const double* lon, const double* lat, void* workspace,
+                          long workspace_bytes, double* qu, int* cell, double* s, double* t, double* m, ogg_locate_counts* counts,
+                          void* stream);
+/* sample step (nrec >= 1, no workspace): f (nrec, ny, nx) of p->dtype, wet one byte per cell or NULL, cell, s, t of n queries ->
+ * values (nrec, n) and flags (nrec, n); flag0 .. flag3 into *counts, from zero */
+int ogg_locate_sample_dev(const ogg_locate_params* p, const int* cell, const double* s, const double* t, const void* f,
+                          const unsigned char* wet, double* values, unsigned char* flags, ogg_locate_counts* counts, void* stream);
+/* HOST pointers throughout, staged through device memory: the three steps on the supergrid x, y ((2 ny + 1) x (2 nx + 1)); cu and qu
+ * may be NULL */
+int ogg_locate(const ogg_locate_params* p, const double* x, const double* y, const double* lon, const double* lat, int* cell, double* s,
+               double* t, double* m, double* cu, double* qu, ogg_locate_counts* counts);
+/* HOST pointers throughout: the sample step on located points; *counts gets flag0 .. flag3 and keeps its other fields */
+int ogg_locate_sample(const ogg_locate_params* p, const int* cell, const double* s, const double* t, const void* f,
+                      const unsigned char* wet, double* values, unsigned char* flags, ogg_locate_counts* counts);
 
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);

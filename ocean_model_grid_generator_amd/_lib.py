@@ -267,6 +267,26 @@ LAYOUT_RECORD = np.dtype([(f, "<i4") for f in LAYOUT_RECORD_FIELDS])
 LAYOUT_MAX_DIV, LAYOUT_MAX_CANDIDATES = 4096, 1 << 20                  # OGG_LAYOUT_MAX_DIV, OGG_LAYOUT_MAX_CANDIDATES
 LAYOUT_TOO_FINE, LAYOUT_FOLD_ASYMMETRIC = 1, 2                         # OGG_LAYOUT_TOO_FINE, OGG_LAYOUT_FOLD_ASYMMETRIC
 
+
+class LocateParams(ctypes.Structure):
+    """ogg_locate_params of include/ogg_hip.h"""
+    _fields_ = [("ny", c_long), ("nx", c_long), ("n", c_long), ("nrec", c_long), ("topology", c_int), ("mode", c_int), ("dtype", c_int),
+                ("n_fill", c_int), ("fill", c_double * 2)]
+
+
+LOCATE_COUNT_FIELDS = ("located", "outside", "invalid", "large_cells", "cubes", "tests", "flag0", "flag1", "flag2", "flag3")
+
+
+class LocateCounts(ctypes.Structure):
+    """ogg_locate_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in LOCATE_COUNT_FIELDS]
+
+
+LOCATE_CELL, LOCATE_BILINEAR = 0, 1                                    # OGG_LOCATE_CELL, OGG_LOCATE_BILINEAR
+LOCATE_MODES = {"cell": LOCATE_CELL, "bilinear": LOCATE_BILINEAR}
+LOCATE_TOL = 2.0 ** -50                                                # OGG_LOCATE_TOL
+LOCATE_MAX_CUBES, LOCATE_MAX_TOUCH = 128, 27                           # OGG_LOCATE_MAX_CUBES, OGG_LOCATE_MAX_TOUCH
+
 # OGG_ABI_* of include/ogg_hip.h, in code order: name -> the mirror of ogg_<name> (a ctypes.Structure or a numpy record), whose size
 # ogg_abi_sizeof(code) must give (tests/test_abi.py)
 ABI_MIRRORS = {"LATLON_BAND": LatlonBand, "BIPOLAR_BAND": BipolarBand, "DPOLE_BAND": DpoleBand, "QUALITY_EXTREMUM": QualityExtremum,
@@ -277,7 +297,7 @@ ABI_MIRRORS = {"LATLON_BAND": LatlonBand, "BIPOLAR_BAND": BipolarBand, "DPOLE_BA
                "REGRID_COUNTS": RegridCounts, "BILINEAR_PARAMS": BilinearParams, "COAST_PARAMS": CoastParams, "COAST_COUNTS": CoastCounts,
                "BASIN_PARAMS": BasinParams, "BASIN_RULE": BASIN_RULE, "BASIN_RULE_RECORD": BASIN_RECORD, "BASIN_COUNTS": BasinCounts,
                "XGRID_CS_ATM": XgridCsAtm, "XGRID_CS_COUNTS": XgridCsCounts, "LAYOUT_PARAMS": LayoutParams, "LAYOUT_CANDIDATE": LAYOUT_CANDIDATE,
-               "LAYOUT_RECORD": LAYOUT_RECORD}
+               "LAYOUT_RECORD": LAYOUT_RECORD, "LOCATE_PARAMS": LocateParams, "LOCATE_COUNTS": LocateCounts}
 ABI = {name: code for code, name in enumerate(ABI_MIRRORS)}
 
 
@@ -446,6 +466,17 @@ SIGNATURES = {
                               c_void_p],
     "ogg_layouts": [ctypes.POINTER(LayoutParams), c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                     c_void_p],
+    "ogg_locate_check": [ctypes.POINTER(LocateParams)],
+    "ogg_locate_sets_dev": [ctypes.POINTER(LocateParams), c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p],
+    "ogg_locate_index_dev": [ctypes.POINTER(LocateParams), c_void_p, c_long, c_void_p, c_void_p],
+    "ogg_locate_search_dev": [ctypes.POINTER(LocateParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_locate_sample_dev": [ctypes.POINTER(LocateParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p],
+    "ogg_locate": [ctypes.POINTER(LocateParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                   c_void_p, ctypes.POINTER(LocateCounts)],
+    "ogg_locate_sample": [ctypes.POINTER(LocateParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                          ctypes.POINTER(LocateCounts)],
     "ogg_event_create": [ctypes.POINTER(c_void_p)],
     "ogg_event_destroy": [c_void_p],
     "ogg_event_record": [c_void_p, c_void_p],
@@ -475,7 +506,8 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_coast_workspace_bytes": [ctypes.POINTER(CoastParams)],
                 "ogg_basin_workspace_bytes": [ctypes.POINTER(BasinParams)],
                 "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long],
-                "ogg_layout_workspace_bytes": [ctypes.POINTER(LayoutParams)]}
+                "ogg_layout_workspace_bytes": [ctypes.POINTER(LayoutParams)],
+                "ogg_locate_workspace_bytes": [ctypes.POINTER(LocateParams)]}
 
 _lib = None
 

@@ -231,6 +231,8 @@ long ogg_abi_sizeof(int which) {
         case OGG_ABI_LAYOUT_PARAMS: return (long)sizeof(ogg_layout_params);
         case OGG_ABI_LAYOUT_CANDIDATE: return (long)sizeof(ogg_layout_candidate);
         case OGG_ABI_LAYOUT_RECORD: return (long)sizeof(ogg_layout_record);
+        case OGG_ABI_LOCATE_PARAMS: return (long)sizeof(ogg_locate_params);
+        case OGG_ABI_LOCATE_COUNTS: return (long)sizeof(ogg_locate_counts);
         default: return -1L;
     }
 }

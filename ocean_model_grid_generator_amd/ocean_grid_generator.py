@@ -669,7 +669,8 @@ class AnalysisFlags(object):
                     interp_file="interp.nc", interp_no_fill=False, interp_fill_max=None, interp_no_rotate=False, xgrid_cs=None,
                     xgrid_cs_spacing="equiangular", xgrid_cs_lon_shift=0.0, xgrid_cs_file="atmos_mosaic_tile%dXocean_mosaic_tile1.nc",
                     xgrid_cs_frac_file=None, mask_table_layout=None, mask_table_dir=None, layout_sweep=None, layout_target_pes=None,
-                    layout_report=None, layout_halo=0, layout_min_block=2, layout_xextent=None, layout_yextent=None)
+                    layout_report=None, layout_halo=0, layout_min_block=2, layout_xextent=None, layout_yextent=None,
+                    locate_points=None, locate_file="points.nc", locate_mode="bilinear")
 
     def __init__(self, **flags):
         unknown = sorted(set(flags) - set(self.DEFAULTS))
@@ -687,6 +688,7 @@ def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
     _validate_runoff_flags(a.runoff_source, a.runoff_var, a.topog_source, a.runoff_targets, skip_metrics)
     _validate_coast_distance_flags(a.coast_distance_file, a.coast_distance_sides, a.topog_source)
     _validate_basin_flags(a.basin_codes_file, a.basin_rules, a.basin_seed_max_km, a.topog_source)
+    _validate_locate_flags(a.locate_points, a.locate_file, a.locate_mode)
     _validate_layout_flags(a)
     _validate_frac_flags(a.xgrid_frac_file, a.xgrid_atm)
     _validate_xgrid_cs_flags(a.xgrid_cs, a.xgrid_cs_spacing, a.xgrid_cs_file, a.xgrid_cs_frac_file, a.xgrid_atm, a.xgrid_file)
@@ -709,7 +711,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          basin_codes_file=None, basin_rules=None, basin_seed_max_km=None, xgrid_cs=None, xgrid_cs_spacing="equiangular",
          xgrid_cs_lon_shift=0.0, xgrid_cs_file="atmos_mosaic_tile%dXocean_mosaic_tile1.nc", xgrid_cs_frac_file=None,
          mask_table_layout=None, mask_table_dir=None, layout_sweep=None, layout_target_pes=None, layout_report=None, layout_halo=0,
-         layout_min_block=2, layout_xextent=None, layout_yextent=None):
+         layout_min_block=2, layout_xextent=None, layout_yextent=None, locate_points=None, locate_file="points.nc",
+         locate_mode="bilinear"):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -760,7 +763,11 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     name with the LAYOUT and MASKTABLE lines printed; ``layout_sweep`` (--layout_sweep MAX_BLOCKS): the record of every layout of at
     most MAX_BLOCKS blocks whose blocks have at least ``layout_min_block`` cells a side, and with ``layout_target_pes`` the layout
     of the smallest blocks among those that run on exactly that many processes, whose table is written when no layout is named;
-    ``layout_report``: the ranking and the tables as JSON; also an addition."""
+    ``layout_report``: the ranking and the tables as JSON; also an addition.  ``locate_points`` (--locate_points FILE): for every
+    point of that file (``lon lat [name]`` lines, or a NetCDF file with 1-D lon and lat) the model cell that holds it, its fractional
+    position in the cell and the key's margin (locate.py), written to ``locate_file``; with ``topog_source`` also the depth sampled
+    there (``locate_mode``: bilinear between the four nearest wet cell centres, or the cell's own) and the cell's wet byte (the edited
+    depth and wet set with ``ocean_mask_file``); allowed with ``skip_metrics``; also an addition."""
     flags = dict(locals())   # the arguments, by name: taken before anything else is bound
     import time
 
@@ -1085,7 +1092,7 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
 
 def _run_analyses(a, g, cut=None):
     """The analyses that follow the grid (``a``: AnalysisFlags), each printed and written as it is done, in their one order: quality
-    report, topography and ocean mask, distance to the coast, basin codes, processor layouts and mask tables, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
+    report, topography and ocean mask, distance to the coast, basin codes, point location, processor layouts and mask tables, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
     Supergrid with its ``cut`` (main) or the _StitchedArrays of main_function_level."""
     if a.quality_report:
         _write_quality_report(g.quality(cut), a.quality_report)
@@ -1102,6 +1109,11 @@ def _run_analyses(a, g, cut=None):
     if a.basin_codes_file:
         from . import basin_codes as BC
         _write_basin_codes(g.basin_codes(cut, wet, BC.read_rules(str(a.basin_rules)), seed_max_km=a.basin_seed_max_km), a.basin_codes_file)
+    if a.locate_points:
+        from . import locate as LOC
+        lon, lat, names = LOC.read_points(str(a.locate_points))
+        depth = None if topo is None else LOC.depth_field(topo["depth"])
+        _write_locate(g.sample(cut, lon, lat, depth, wet=wet, mode=a.locate_mode, names=names), wet, a.locate_file)
     if _layout_wanted(a):
         from . import layout as LY
         LY.run_flags(a, lambda **kw: g.layouts(cut, wet, **kw), lambda px, py, **kw: g.mask_table(cut, wet, px, py, **kw))
@@ -1181,6 +1193,13 @@ class _StitchedArrays(object):
         from . import runoff as RO
         return BC.basin_codes(self.x, self.y, wet, rules, seed_max_distance=None if seed_max_km is None else 1000.0 * seed_max_km,
                               Re=_default_Re, area=None if self.metrics[2] is None else RO.cell_area(self.metrics[2]))
+
+    def sample(self, cut, lon, lat, field, wet=None, mode="bilinear", fill_values=(), names=None):
+        from . import locate as LOC
+        res = LOC.locate(self.x, self.y, lon, lat, names=names)
+        if field is not None:
+            LOC.sample_located(res, field, wet, mode, fill_values)
+        return res
 
     def _topology(self):
         from . import ocean_mask as M
@@ -1281,6 +1300,27 @@ def _write_coast_distance(res, fnam):
     for line in CD.summary_lines(res):
         print(line)
     CD.write_coast_distance(str(fnam), res)
+
+
+def _validate_locate_flags(locate_points, locate_file, locate_mode):
+    if locate_mode not in ("bilinear", "cell"):
+        raise ValueError("--locate_mode must be bilinear or cell, not %r" % (locate_mode,))
+    if not locate_points:
+        if locate_mode != "bilinear" or locate_file != "points.nc":
+            raise ValueError("--locate_file and --locate_mode need --locate_points")
+        return
+    if not locate_file:
+        raise ValueError("--locate_points needs a --locate_file to write")
+
+
+def _write_locate(res, wet, fnam):
+    if res is None:   # not rank 0
+        return
+    from . import locate as LOC
+    LOC.set_wet(res, wet)
+    for line in LOC.summary_lines(res):
+        print(line)
+    LOC.write_locate(str(fnam), res)
 
 
 def _validate_basin_flags(basin_codes_file, basin_rules, basin_seed_max_km, topog_source):
@@ -1536,6 +1576,12 @@ def build_parser():
                         help="the rule file of --basin_codes_file: code seed_lon seed_lat lon_w lon_e lat_s lat_n [name] per line")
     parser.add_argument("--basin_seed_max_km", type=float, required=False, default=None,
                         help="a seed farther than this from every cell centre is off the grid (default: any distance)")
+    parser.add_argument("--locate_points", type=str, required=False, default=None,
+                        help="a file of points (`lon lat [name]` per line, # starts a comment; or NetCDF with 1-D lon and lat): write "
+                             "the model cell that holds each, its position in the cell and, with --topog_source, the depth there")
+    parser.add_argument("--locate_file", type=str, required=False, default="points.nc", help="point-location output file, default points.nc")
+    parser.add_argument("--locate_mode", type=str, choices=["bilinear", "cell"], required=False, default="bilinear",
+                        help="how the depth is sampled: bilinear (default) between the four nearest wet cell centres, or the cell's own")
     from . import layout as LY
     LY.add_flags(parser)
     parser.add_argument("--xgrid_frac_file", type=str, required=False, default=None,

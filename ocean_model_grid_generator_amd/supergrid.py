@@ -1626,6 +1626,22 @@ class Supergrid(object):
             return None
         return CD.coast_distance_dev(xy[0], xy[1], wet, sides=sides, Re=float(self.plan.Re))
 
+    # -- point location -----------------------------------------------------------------------------------------------
+    def locate(self, cut, lon, lat, names=None):
+        """The model cells of the stitched grid that hold the points lon, lat (locate.result on rank 0, None on the other ranks), on
+        rank 0's GPU with the stitched points gathered there, as coast_distance does: the same bits for any number of ranks by
+        construction."""
+        return self.sample(cut, lon, lat, None, names=names)
+
+    def sample(self, cut, lon, lat, field, wet=None, mode="bilinear", fill_values=(), names=None):
+        """locate() with the field ``field`` (a fields.Field or an array (..., ny, nx) on the model cells; None: nothing is sampled)
+        sampled at the points, under the optional wet set ``wet``: the result's "samples" holds the values and flags."""
+        from . import locate as LOC
+        xy = self.stitched_xy(cut)
+        if xy is None:
+            return None
+        return LOC.locate_dev(xy[0], xy[1], lon, lat, names=names, field=field, wet=wet, mode=mode, fill_values=fill_values)
+
     # -- basin codes --------------------------------------------------------------------------------------------------
     def basin_codes(self, cut, wet, rules, seed_max_km=None):
         """The basin codes (basin_codes.result on rank 0, None on the other ranks) of the model cells of the stitched grid with the wet
