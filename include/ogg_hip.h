@@ -85,7 +85,10 @@ const char* ogg_version(void);
 #define OGG_ABI_LAYOUT_RECORD 32
 #define OGG_ABI_LOCATE_PARAMS 33
 #define OGG_ABI_LOCATE_COUNTS 34
-#define OGG_ABI_N 35
+#define OGG_ABI_TOPOG_PROJECTION 35
+#define OGG_ABI_TOPOG_LAYER 36
+#define OGG_ABI_TOPOG_MERGE_RECORD 37
+#define OGG_ABI_N 38
 long ogg_abi_sizeof(int which);
 int ogg_device_count(int* count);
 int ogg_set_device(int device);
@@ -685,6 +688,81 @@ int ogg_topog_plane_band_dev(const ogg_topog_band* band, const ogg_topog_source*
                              ogg_topog_plane_record* out, void* stream);
 /* ogg_topog with the plane moments (HOST pointers, the same staging); out holds plane records */
 int ogg_topog_plane(const ogg_topog_band* band, const ogg_topog_source* src, ogg_topog_plane_record* out);
+
+/* Layered topography (opt-in; without it every record, output and file above is what it was): the topography sampled from an ORDERED
+ * list of 1 .. OGG_TOPOG_MAX_SOURCES layers, the first layer that has a value for a sample giving it.  A layer is a source raster
+ * with a kind, a projection and an integer multiplier q_mul >= 1.  The usual use: a polar-stereographic raster in metres (BedMachine,
+ * IBCSO) over a global lat-lon one.
+ * The sample positions (unwrap, refine's a, b, the pole test, s, t, the bilinear lon and lat) are exactly those of "Topography by
+ * refined sampling"; they depend on no layer.
+ *   kinds     OGG_TOPOG_LATLON: the source as above.  OGG_TOPOG_POLAR_STEREO: the four box numbers of the source mean X0, dX, Y0, dY
+ *             (src.lon0, dlon, lat0, dlat in that order): metres, cell EDGES X0 + I * dX and Y0 + J * dY, dX, dY > 0, row 0 the lowest Y
+ *   project   polar stereographic on an ellipsoid (Snyder, Map Projections: A Working Manual, eqs. 21-33 / 21-34 with the t of 15-9),
+ *             written so that numpy and the device evaluate one expression.  h = +1 (north) or -1 (south), lon0 the central meridian,
+ *             a the semi-major axis, e the eccentricity (0: a sphere; 0 <= e < 0.2), K a constant the caller computes, all fp64:
+ *               phi = h * lat * (pi / 180), lam = h * (lon - lon0) * (pi / 180) (left to right), s = sin phi, c = cos phi,
+ *               rho = ((K * c) / (1 + s)) * exp(e * atanh(e * s)),   X = h * (rho * sin lam),   Y = -h * (rho * cos lam)
+ *             K = a * m_ts / t_ts with m_ts = cos phi_ts / sqrt(1 - e^2 sin^2 phi_ts) and t_ts = c / (1 + s) * exp(e * atanh(e * s)) at
+ *             phi_ts = h * lat_ts; for phi_ts = 90 degrees K = 2 a / sqrt((1 + e)^(1 + e) * (1 - e)^(1 - e)).  (c / (1 + s) is Snyder's
+ *             tan(pi / 4 - phi / 2).)  The kernel takes exp and atanh from short series (csrc/ogg_math.h), sin and cos from the device
+ *             library; a is not read on the device.  A sample with h * lat >= 90 - OGG_TOPOG_POLE_EPS has X = Y = +0 exactly
+ *   gate      a sample is projected in a layer only when its lon and lat are finite and h * lat >= lat_gate (an input, >= -80: the
+ *             projection grows without bound towards the other pole); otherwise it is MISSING in that layer, for one compare
+ *   index     projected: I = floor((X - X0) * inv_dX), J = floor((Y - Y0) * inv_dY), inv_d = 1.0 / d once in fp64; outside
+ *             [0, Nx) x [0, Ny) the sample is MISSING in that layer.  Lat-lon layers index as above (periodic and regional rules)
+ *   pole      the samples of a pole-enclosing cell sit at that pole: a lat-lon layer reads its polar row as above; a projected layer
+ *             takes lat = +-90 for them (lon as above, which only the finite test reads), so one of that hemisphere reads the element
+ *             at (+0, +0) and one of the other hemisphere is refused by its gate
+ *   merge     a sample takes q = q_mul_k * q_k from the first layer k, in list order, in which it is not MISSING (outside, gated,
+ *             a fill value, NaN); n_from[k] counts the samples taken from layer k; a sample MISSING in every layer counts in n_missing.
+ *             |q_mul_k * q_k| <= OGG_TOPOG_MAX_Q is demanded of every value stored in layer k, not only of the sampled ones:
+ *             ogg_topog_layer_range_dev tells, ogg_topog_layers refuses; nothing is clamped.  n_wet counts (double)q < wet_below of
+ *             layers[0].src (stated in the list's quantum); the other layers' wet_below is not read
+ *   refine    refine > 0 replaces R as above.  Otherwise every layer k gives a value v_k and R = clamp(max_k v_k, 1, 256), CLAMPED
+ *             when the maximum exceeds 256 or some v_k is not a number.  Lat-lon: v_k is the expression above, unconditionally (so a
+ *             list of one lat-lon layer gives the records above bit for bit).  Projected: the four corners (L, y), after the unwrap
+ *             and the polar substitution, are projected like samples; a corner COUNTS when it is finite and passes the gate; when at
+ *             least one counting corner also indexes inside the raster, v_k = ceil(oversample * max(spanX / dX, spanY / dY)) with the
+ *             spans (max - min) over the counting corners; otherwise v_k = 1
+ *   record    ogg_topog_merge_record: base holds what ogg_topog_record holds, over the merged samples, then n_from[4].  A model
+ *             cell's record is the exact integer combination of its four supergrid cells', and partial records of a model row split
+ *             over two bands combine exactly (n_from adds).  All accumulation is in integers: the same bits for any split into
+ *             bands and any number of ranks.
+ * The plane fit lives in ONE raster's index space and has no meaning across layers or in a projected raster's: there is no plane
+ * form of these entry points, and the Python layer refuses --topog_roughness with a list or a projected source. */
+#define OGG_TOPOG_MAX_SOURCES 4
+enum { OGG_TOPOG_LATLON = 0, OGG_TOPOG_POLAR_STEREO = 1 };
+typedef struct ogg_topog_projection {
+    int h;               /* +1 north, -1 south */
+    int reserved;
+    double lon0, a, e, K, lat_gate;
+} ogg_topog_projection;
+typedef struct ogg_topog_layer {
+    ogg_topog_source src;
+    int kind;            /* OGG_TOPOG_LATLON or OGG_TOPOG_POLAR_STEREO */
+    int q_mul;           /* q = q_mul * (the source's q) */
+    ogg_topog_projection proj;   /* read for OGG_TOPOG_POLAR_STEREO only */
+} ogg_topog_layer;
+typedef struct ogg_topog_merge_record {
+    ogg_topog_record base;
+    long long n_from[OGG_TOPOG_MAX_SOURCES];
+} ogg_topog_merge_record;
+/* ogg_topog_band_dev over layers: device pointers throughout, the same band and workspace contracts; out holds merge records.
+ * Every argument is validated before any device work (OGG_EARG with a message): n_layers outside 1 .. 4, a bad kind, h not +-1,
+ * e outside [0, 0.2), K not positive, dX or dY <= 0, lat_gate < -80, q_mul < 1.  The range of q_mul * q is NOT among them: it is
+ * the caller's to check once per layer with ogg_topog_layer_range_dev (the host form and the Python layer do); a layer that was
+ * not checked can wrap silently in the records (never in memory) */
+int ogg_topog_layers_band_dev(const ogg_topog_band* band, int n_layers, const ogg_topog_layer* layers, void* workspace,
+                              long workspace_bytes, ogg_topog_merge_record* out, void* stream);
+/* *n_bad (device int) is set non-zero when some stored value of the layer's raster (device memory, INT16 or INT32) has
+ * |q_mul * q| > OGG_TOPOG_MAX_Q; the caller must then refuse the layer (the host form does) */
+int ogg_topog_layer_range_dev(const ogg_topog_layer* layer, int* n_bad, void* stream);
+/* HOST pointers in *band and the layers, staged and quantised like ogg_topog; out is host memory */
+int ogg_topog_layers(const ogg_topog_band* band, int n_layers, const ogg_topog_layer* layers, ogg_topog_merge_record* out);
+/* the sampling kernel's own projection applied to n points (device pointers): X, Y as above and gate_ok[k] (int) = 1 when the point
+ * is finite and passes the gate (0: X = Y = 0 are stored).  Test-only: it holds the device projection to a truth on its own */
+int ogg_topog_project_dev(const ogg_topog_projection* proj, long n, const double* lon, const double* lat, double* X, double* Y,
+                          int* gate_ok, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Atmosphere x ocean exchange grid (an addition: the reference has none).  First-order conservative overlaps of a rectilinear global

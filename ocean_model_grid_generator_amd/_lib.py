@@ -99,6 +99,24 @@ TOPOG_MOMENT_FIELDS = ("sx", "sy", "sxx", "sxy", "syy", "sxq", "syq", "n_far")
 # ogg_topog_plane_record as a numpy record (120 bytes): the fields of ogg_topog_record (its ``base``), then the moments
 TOPOG_PLANE_RECORD = np.dtype(TOPOG_RECORD.descr + [(f, "<i8") for f in TOPOG_MOMENT_FIELDS])
 
+TOPOG_MAX_SOURCES = 4                                                  # OGG_TOPOG_MAX_SOURCES
+TOPOG_LATLON, TOPOG_POLAR_STEREO = 0, 1                                # OGG_TOPOG_LATLON, OGG_TOPOG_POLAR_STEREO
+
+
+class TopogProjection(ctypes.Structure):
+    """ogg_topog_projection of include/ogg_hip.h"""
+    _fields_ = [("h", c_int), ("reserved", c_int), ("lon0", c_double), ("a", c_double), ("e", c_double), ("K", c_double),
+                ("lat_gate", c_double)]
+
+
+class TopogLayer(ctypes.Structure):
+    """ogg_topog_layer of include/ogg_hip.h"""
+    _fields_ = [("src", TopogSource), ("kind", c_int), ("q_mul", c_int), ("proj", TopogProjection)]
+
+
+# ogg_topog_merge_record as a numpy record (88 bytes): the fields of ogg_topog_record (its ``base``), then n_from[4]
+TOPOG_MERGE_RECORD = np.dtype(TOPOG_RECORD.descr + [("n_from", "<i8", (TOPOG_MAX_SOURCES,))])
+
 
 class XgridAtm(ctypes.Structure):
     """ogg_xgrid_atm of include/ogg_hip.h"""
@@ -297,7 +315,8 @@ ABI_MIRRORS = {"LATLON_BAND": LatlonBand, "BIPOLAR_BAND": BipolarBand, "DPOLE_BA
                "REGRID_COUNTS": RegridCounts, "BILINEAR_PARAMS": BilinearParams, "COAST_PARAMS": CoastParams, "COAST_COUNTS": CoastCounts,
                "BASIN_PARAMS": BasinParams, "BASIN_RULE": BASIN_RULE, "BASIN_RULE_RECORD": BASIN_RECORD, "BASIN_COUNTS": BasinCounts,
                "XGRID_CS_ATM": XgridCsAtm, "XGRID_CS_COUNTS": XgridCsCounts, "LAYOUT_PARAMS": LayoutParams, "LAYOUT_CANDIDATE": LAYOUT_CANDIDATE,
-               "LAYOUT_RECORD": LAYOUT_RECORD, "LOCATE_PARAMS": LocateParams, "LOCATE_COUNTS": LocateCounts}
+               "LAYOUT_RECORD": LAYOUT_RECORD, "LOCATE_PARAMS": LocateParams, "LOCATE_COUNTS": LocateCounts, "TOPOG_PROJECTION": TopogProjection,
+               "TOPOG_LAYER": TopogLayer, "TOPOG_MERGE_RECORD": TOPOG_MERGE_RECORD}
 ABI = {name: code for code, name in enumerate(ABI_MIRRORS)}
 
 
@@ -394,6 +413,10 @@ SIGNATURES = {
     "ogg_topog": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p],
     "ogg_topog_plane_band_dev": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p, c_long, c_void_p, c_void_p],
     "ogg_topog_plane": [ctypes.POINTER(TopogBand), ctypes.POINTER(TopogSource), c_void_p],
+    "ogg_topog_layers_band_dev": [ctypes.POINTER(TopogBand), c_int, ctypes.POINTER(TopogLayer), c_void_p, c_long, c_void_p, c_void_p],
+    "ogg_topog_layer_range_dev": [ctypes.POINTER(TopogLayer), c_void_p, c_void_p],
+    "ogg_topog_layers": [ctypes.POINTER(TopogBand), c_int, ctypes.POINTER(TopogLayer), c_void_p],
+    "ogg_topog_project_dev": [ctypes.POINTER(TopogProjection), c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_xgrid_check_atm": [ctypes.POINTER(XgridAtm)],
     "ogg_xgrid_count_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_void_p, c_long, c_void_p, c_void_p, c_void_p],
     "ogg_xgrid_write_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_void_p, c_long, c_void_p, c_void_p, c_void_p,

@@ -233,6 +233,9 @@ long ogg_abi_sizeof(int which) {
         case OGG_ABI_LAYOUT_RECORD: return (long)sizeof(ogg_layout_record);
         case OGG_ABI_LOCATE_PARAMS: return (long)sizeof(ogg_locate_params);
         case OGG_ABI_LOCATE_COUNTS: return (long)sizeof(ogg_locate_counts);
+        case OGG_ABI_TOPOG_PROJECTION: return (long)sizeof(ogg_topog_projection);
+        case OGG_ABI_TOPOG_LAYER: return (long)sizeof(ogg_topog_layer);
+        case OGG_ABI_TOPOG_MERGE_RECORD: return (long)sizeof(ogg_topog_merge_record);
         default: return -1L;
     }
 }

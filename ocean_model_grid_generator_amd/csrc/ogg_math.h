@@ -356,6 +356,23 @@ OGG_DEV double atan2_lib_any(double y, double x) {
     return r;
 }
 
+// atanh(z) for |z| <= 0.2 and exp(w) for |w| <= 0.041, the two factors of the ellipsoid's term exp(e atanh(e sin phi)) of the polar
+// stereographic projection (include/ogg_hip.h, "Layered topography"; e < 0.2, so |e sin phi| < 0.2 and |e atanh(.)| < 0.041): their
+// Taylor series with the coefficients as scalar operands, one fma per term, where the library's atanh brings a log and a division and
+// its exp a reduction and an ldexp.  atanh z = z + z w (1/3 + w/5 + .. + w^11/25), w = z^2: the
+// first term left out is w^12/27 <= 2.5e-20 of the result.  exp w = 1 + w (1 + w/2 + .. + w^7/8!): the first term left out is
+// w^9/9! <= 8.1e-19.  Either is within an ulp of the function; ogg_topog_project_dev holds the projection built on them to a 50-digit truth
+// (tests/test_gpu_topog_layers.py).  Outside those ranges they are simply wrong: ogg_topog_layers refuses e >= 0.2.
+static __constant__ double kAtanhSmall[12] = {1.0 / 3.0,  1.0 / 5.0,  1.0 / 7.0,  1.0 / 9.0,  1.0 / 11.0, 1.0 / 13.0,
+                                              1.0 / 15.0, 1.0 / 17.0, 1.0 / 19.0, 1.0 / 21.0, 1.0 / 23.0, 1.0 / 25.0};
+static __constant__ double kExpSmall[8] = {1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0};
+
+OGG_DEV double atanh_small(double z) {
+    const double w = z * z;
+    return fma(z * w, horner_scalar<12>(kAtanhSmall, w), z);
+}
+OGG_DEV double exp_small(double w) { return fma(w, horner_scalar<8>(kExpSmall, w), 1.0); }
+
 // Neighbour lanes of a wave64 through DPP wave shifts (gfx9: wave_shr:1 = 0x138, wave_shl:1 = 0x130): two VALU moves per
 // double instead of two ds_bpermute round trips through the LDS crossbar.  The end lanes keep their own value, like
 // __shfl_up / __shfl_down with delta 1, and both words of the double travel together.  Called in uniform control flow (every kernel

@@ -146,6 +146,45 @@ OGG_DEV Origin setup_origin(const Geo& g, const Src& s, long m, long io) {
     return o;
 }
 
+// the raster element (is, js) of a sample of a lat-lon source, by the index rules of the header; true when the sample is MISSING (no
+// index is formed, or it lies outside a regional raster): is, js are then in range but mean nothing
+OGG_DEV bool latlon_index(const Src& s, int pole, double lon, double lat, int& is, int& js) {
+    const long Nx = s.Nx, Ny = s.Ny;
+    const double dNx = (double)Nx, dNy = (double)Ny, inv_Nx = 1.0 / dNx;
+    bool miss = false;
+    if (s.periodic) {
+        const double fi = floor((lon - s.lon0) * s.inv_dlon);
+        // fi mod Nx without an integer division: fi is an integral double (|fi| < 2^52 below), so fi - Nx * floor(fi / Nx),
+        // taken with the reciprocal and set right by one step either way, is exact
+        miss = !(fabs(fi) < 4.0e15);   // a longitude that is not finite (or beyond any grid): no index is formed from it
+        double r = miss ? 0.0 : fi - dNx * floor(fi * inv_Nx);
+        r = r < 0.0 ? r + dNx : r;
+        r = r >= dNx ? r - dNx : r;
+        is = (int)r;
+    } else {
+        // a regional raster is met on its own longitude branch: d = (lon - lon0) mod 360 before the range test.  A d already in
+        // [0, 360) is left as it is; one turn below or above, mod360(d) is d + 360 or d - 360 bit for bit (fmod(d, 360) = d for
+        // |d| < 360 and = d - 360, exactly, for 360 <= d < 720), so only a grid stated further away pays the fmod
+        double d = lon - s.lon0;
+        if (!(d >= 0.0 && d < 360.0)) d = (d < 0.0 && d >= -360.0) ? d + 360.0 : ((d >= 360.0 && d < 720.0) ? d - 360.0 : mod360(d));
+        const double fi = floor(d * s.inv_dlon);
+        miss = !(fi >= 0.0 && fi < dNx);   // NaN (a longitude that is not finite) included
+        is = miss ? 0 : (int)fi;
+    }
+    if (pole != 0) {
+        js = pole < 0 ? 0 : (int)(Ny - 1);
+    } else {
+        double fj = floor((lat - s.lat0) * s.inv_dlat);
+        if (s.periodic && fabs(fj) < INFINITY) {   // a latitude that is not finite is MISSING, not clamped
+            fj = fj < 0.0 ? 0.0 : (fj > dNy - 1.0 ? dNy - 1.0 : fj);
+        } else if (!(fj >= 0.0 && fj < dNy)) {
+            miss = true, fj = 0.0;
+        }
+        js = (int)fj;
+    }
+    return miss;
+}
+
 struct Acc {
     int n, nm, nw, mn, mx;
     long long sum, sumsq;
@@ -175,8 +214,7 @@ OGG_DEV void sample_cell(const Src& s, const Cell& c, const double* S, const dou
     if (f >= RR) return;
     int a = f % R, b = f / R;
     const int step_b = TT / R, step_a = TT % R;
-    const long Nx = s.Nx, Ny = s.Ny;
-    const double dNx = (double)Nx, dNy = (double)Ny, inv_Nx = 1.0 / dNx;
+    const long Nx = s.Nx;
     [[maybe_unused]] bool far_cell = false;   // PLANE only: no origin, or a pole-enclosing cell (no latitude): every valid sample is far
     if constexpr (PLANE) far_cell = !pl.o.valid || c.pole != 0;
     for (; f < RR; f += TT) {
@@ -190,38 +228,8 @@ OGG_DEV void sample_cell(const Src& s, const Cell& c, const double* S, const dou
         } else {
             lon = c.L00 + 360.0 * sa;
         }
-        bool miss = false;
         int is, js;
-        if (s.periodic) {
-            const double fi = floor((lon - s.lon0) * s.inv_dlon);
-            // fi mod Nx without an integer division: fi is an integral double (|fi| < 2^52 below), so fi - Nx * floor(fi / Nx),
-            // taken with the reciprocal and set right by one step either way, is exact
-            miss = !(fabs(fi) < 4.0e15);   // a longitude that is not finite (or beyond any grid): no index is formed from it
-            double r = miss ? 0.0 : fi - dNx * floor(fi * inv_Nx);
-            r = r < 0.0 ? r + dNx : r;
-            r = r >= dNx ? r - dNx : r;
-            is = (int)r;
-        } else {
-            // a regional raster is met on its own longitude branch: d = (lon - lon0) mod 360 before the range test.  A d already in
-            // [0, 360) is left as it is; one turn below or above, mod360(d) is d + 360 or d - 360 bit for bit (fmod(d, 360) = d for
-            // |d| < 360 and = d - 360, exactly, for 360 <= d < 720), so only a grid stated further away pays the fmod
-            double d = lon - s.lon0;
-            if (!(d >= 0.0 && d < 360.0)) d = (d < 0.0 && d >= -360.0) ? d + 360.0 : ((d >= 360.0 && d < 720.0) ? d - 360.0 : mod360(d));
-            const double fi = floor(d * s.inv_dlon);
-            miss = !(fi >= 0.0 && fi < dNx);   // NaN (a longitude that is not finite) included
-            is = miss ? 0 : (int)fi;
-        }
-        if (c.pole != 0) {
-            js = c.pole < 0 ? 0 : (int)(Ny - 1);
-        } else {
-            double fj = floor((lat - s.lat0) * s.inv_dlat);
-            if (s.periodic && fabs(fj) < INFINITY) {   // a latitude that is not finite is MISSING, not clamped
-                fj = fj < 0.0 ? 0.0 : (fj > dNy - 1.0 ? dNy - 1.0 : fj);
-            } else if (!(fj >= 0.0 && fj < dNy)) {
-                miss = true, fj = 0.0;
-            }
-            js = (int)fj;
-        }
+        bool miss = latlon_index(s, c.pole, lon, lat, is, js);
         if (!miss) {
             int q;
             if (DT == OGG_TOPOG_INT16) {
@@ -367,6 +375,263 @@ __global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned l
     }
 }
 
+// ---- layered topography (include/ogg_hip.h, "Layered topography") ------------------------------------------------------------
+// topog_layers_kernel: the walk of topog_band_kernel -- one wavefront per output cell, runs of cells from the counter, the S / U table,
+// lane-private integer accumulators, shuffle reductions -- with every sample offered to the layers in list order.  The layers are a
+// kernel argument, so their descriptors arrive in scalar registers; the kernel is instantiated per number of layers and the loop over
+// them is unrolled (no indexed copy of the argument, and a short list stays in registers), and kind and dtype are uniform over the
+// wavefront.  A projected layer costs a sample two sincos, one division and the two short
+// series of ogg_math.h; a sample that fails the gate costs one compare.  The refinement of a cell takes the layers' corner
+// projections: lane 16 c + 4 k + p projects corner p of supergrid cell c in layer k, so the up to 64 projections of an output cell
+// run side by side, and shuffles within the 16 lanes of a cell reduce them to its R.
+constexpr int NLAY = OGG_TOPOG_MAX_SOURCES;
+static_assert(NLAY == 4 && TT == 16 * NLAY, "one lane per (supergrid cell, layer, corner)");
+static_assert(sizeof(ogg_topog_merge_record) == 88, "ogg_topog_merge_record layout");
+
+struct Layer {
+    Src s;   // a projected layer: lon0, lat0, inv_dlon, inv_dlat, dlon, dlat hold X0, Y0, 1 / dX, 1 / dY, dX, dY; periodic is false
+    int kind, q_mul;
+    double h, plon0, e, K, gate;
+};
+struct Layers {
+    int n;
+    Layer l[NLAY];
+};
+
+// X, Y of the header's projection; false (and nothing stored) when the point is not finite or fails the gate
+OGG_DEV bool stereo_project(const Layer& L, double lon, double lat, double& X, double& Y) {
+    if (!(fabs(lon) < INFINITY && fabs(lat) < INFINITY)) return false;
+    const double hl = L.h * lat;
+    if (!(hl >= L.gate)) return false;
+    if (hl >= 90.0 - OGG_TOPOG_POLE_EPS) {
+        X = 0.0, Y = 0.0;
+        return true;
+    }
+    const double phi = hl * ogg::kPi180, lam = L.h * (lon - L.plon0) * ogg::kPi180;
+    double sp, cp, sl, cl;
+    sincos(phi, &sp, &cp);
+    sincos(lam, &sl, &cl);
+    double rho = (L.K * cp) / (1.0 + sp);
+    if (L.e != 0.0) rho = rho * ogg::exp_small(L.e * ogg::atanh_small(L.e * sp));   // e = 0: the factor is exp(+0) = 1, which changes no bit
+    X = L.h * (rho * sl), Y = -L.h * (rho * cl);
+    return true;
+}
+
+// the raster element of a sample in a projected layer; true when the sample is MISSING in it (gated, or outside the raster)
+OGG_DEV bool stereo_index(const Layer& L, int pole, double lon, double lat, int& is, int& js) {
+    double X, Y;
+    if (!stereo_project(L, lon, pole != 0 ? 90.0 * (double)pole : lat, X, Y)) return true;
+    const double fi = floor((X - L.s.lon0) * L.s.inv_dlon), fj = floor((Y - L.s.lat0) * L.s.inv_dlat);
+    if (!(fi >= 0.0 && fi < (double)L.s.Nx && fj >= 0.0 && fj < (double)L.s.Ny)) return true;
+    is = (int)fi, js = (int)fj;
+    return false;
+}
+
+// the value of a sample in one layer (times q_mul); true when it is MISSING there.  STEREO = false: the list has no projected layer
+template <bool STEREO>
+OGG_DEV bool layer_value(const Layer& L, int pole, double lon, double lat, int& q) {
+    int is = 0, js = 0;
+    const bool miss =
+        (!STEREO || L.kind == OGG_TOPOG_LATLON) ? latlon_index(L.s, pole, lon, lat, is, js) : stereo_index(L, pole, lon, lat, is, js);
+    if (miss) return true;   // is, js of a missing sample mean nothing: nothing is read
+    int v;
+    if (L.s.dtype == OGG_TOPOG_INT16) {
+        v = static_cast<const short*>(L.s.data)[(long)js * L.s.Nx + is];
+        if (v == L.s.fill0 || v == L.s.fill1) return true;
+    } else {
+        v = static_cast<const int*>(L.s.data)[(long)js * L.s.Nx + is];
+        if (v == OGG_TOPOG_MISSING_Q) return true;
+    }
+    q = v * L.q_mul;   // |q| <= OGG_TOPOG_MAX_Q: ogg_topog_layer_range_dev
+    return false;
+}
+
+struct LAcc {
+    Acc a;
+    int from[NLAY];
+};
+
+template <int NL, bool STEREO>
+OGG_DEV void sample_cell_layers(const Layers& ly, const Cell& c, const double* S, const double* U, int lane, LAcc& acc) {
+    const int R = c.R;
+    const int RR = R * R;
+    int f = lane;
+    if (f >= RR) return;
+    int a = f % R, b = f / R;
+    const int step_b = TT / R, step_a = TT % R;
+    const int wet_q = ly.l[0].s.wet_q;
+    for (; f < RR; f += TT) {
+        const double sa = S[a], ua = U[a];
+        double lon, lat = 0.0;   // the positions of sample_cell, operation for operation
+        if (c.pole == 0) {
+            const double tb = S[b], vb = U[b];
+            const double w00 = ua * vb, w01 = sa * vb, w10 = ua * tb, w11 = sa * tb;
+            lon = w00 * c.L00 + w01 * c.L01 + w10 * c.L10 + w11 * c.L11;
+            lat = w00 * c.y00 + w01 * c.y01 + w10 * c.y10 + w11 * c.y11;
+        } else {
+            lon = c.L00 + 360.0 * sa;
+        }
+        bool miss = true;
+        int q = 0;
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            if (miss) {
+                miss = layer_value<STEREO>(ly.l[k], c.pole, lon, lat, q);
+                acc.from[k] += miss ? 0 : 1;
+            }
+        }
+        if (!miss) {
+            acc.a.n += 1;
+            acc.a.nw += q < wet_q ? 1 : 0;
+            acc.a.sum += q;
+            acc.a.sumsq += (long long)q * q;
+            acc.a.mn = q < acc.a.mn ? q : acc.a.mn;
+            acc.a.mx = q > acc.a.mx ? q : acc.a.mx;
+        } else {
+            acc.a.nm += 1;
+        }
+        a += step_a, b += step_b;
+        if (a >= R) a -= R, b += 1;
+    }
+}
+
+// shuffles within aligned groups of W lanes (W = 4: the corners of one layer; W = 16: the layers of one supergrid cell)
+template <int W>
+OGG_DEV double group_max(double v) {
+    for (int o = W / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, TT));
+    return v;
+}
+
+// v_k of the header's "refine" for the layer and corner of this lane (every lane of a group of four returns the layer's value):
+// cl is the lane's supergrid cell (geometry only), lon and lat its corner (L, y)
+template <bool STEREO>
+OGG_DEV double layer_refine_value(const Layer& L, const Cell& cl, double lon, double lat, double oversample) {
+    if (!STEREO || L.kind == OGG_TOPOG_LATLON) {   // the expression of setup_cell
+        const double span_l = fmax(fmax(cl.L00, cl.L01), fmax(cl.L10, cl.L11)) - fmin(fmin(cl.L00, cl.L01), fmin(cl.L10, cl.L11));
+        const double span_y = fmax(fmax(cl.y00, cl.y01), fmax(cl.y10, cl.y11)) - fmin(fmin(cl.y00, cl.y01), fmin(cl.y10, cl.y11));
+        const double any = (cl.L00 + cl.L01) + (cl.L10 + cl.L11) + (cl.y00 + cl.y01) + (cl.y10 + cl.y11);
+        return any != any ? any : ceil(oversample * fmax(span_l / L.s.dlon, span_y / L.s.dlat));
+    }
+    double X = 0.0, Y = 0.0;
+    const bool counts = stereo_project(L, lon, lat, X, Y);
+    const double fi = floor((X - L.s.lon0) * L.s.inv_dlon), fj = floor((Y - L.s.lat0) * L.s.inv_dlat);
+    const bool inside = counts && fi >= 0.0 && fi < (double)L.s.Nx && fj >= 0.0 && fj < (double)L.s.Ny;
+    const double ninf = -INFINITY;   // a corner that does not count takes no part in a maximum
+    const double xmax = group_max<4>(counts ? X : ninf), xmin = -group_max<4>(counts ? -X : ninf);
+    const double ymax = group_max<4>(counts ? Y : ninf), ymin = -group_max<4>(counts ? -Y : ninf);
+    const bool any_inside = group_max<4>(inside ? 1.0 : 0.0) > 0.0;
+    return any_inside ? ceil(oversample * fmax((xmax - xmin) / L.s.dlon, (ymax - ymin) / L.s.dlat)) : 1.0;
+}
+
+// NL: the number of layers, so that a short list keeps its descriptors in scalar registers through the sample loop.  STEREO: whether
+// any layer is projected; a list of lat-lon layers alone carries none of the projection's code or registers
+template <int NL, bool STEREO>
+__global__ __launch_bounds__(TT) void topog_layers_kernel(Geo g, Layers ly, unsigned long long* counter, ogg_topog_merge_record* out) {
+    __shared__ double S[RMAX], U[RMAX];
+    __shared__ Cell cells[4];
+    __shared__ long long take;
+    const int lane = threadIdx.x;
+    int table_R = 0;
+    const int side = 1 << g.shift;
+    Geo g1 = g;   // setup_cell for the geometry alone: with refine = 1 it reads no source
+    g1.refine = 1;
+    for (;;) {
+        if (lane == 0) take = (long long)atomicAdd(counter, (unsigned long long)TR);
+        __syncthreads();
+        const long long c0 = take;
+        __syncthreads();
+        if (c0 >= g.total) break;
+        const long long c1 = c0 + TR < g.total ? c0 + TR : g.total;
+        for (long long c = c0; c < c1; ++c) {
+            const long m = g.m0 + (long)(c / g.nxo), io = (long)(c % g.nxo);
+            if (lane < side * side) {   // lane = 2 dj + di
+                const long j = (m << g.shift) + (lane >> 1), i = (io << g.shift) + (lane & 1);
+                Cell cl;
+                if (j >= g.j0 && j < g.j0 + g.n) {
+                    cl = setup_cell(g1, ly.l[0].s, j, i);
+                    cl.R = g.refine;
+                } else {
+                    cl.valid = 0, cl.R = 0, cl.pole = 0, cl.clamped = 0;
+                }
+                cells[lane] = cl;
+            }
+            __syncthreads();
+            if (g.refine <= 0) {   // R from the layers: lane = 16 cell + 4 layer + corner
+                const int ci = lane >> 4, k = (lane >> 2) & 3, p = lane & 3;
+                const Cell& cl = cells[ci < side * side ? ci : 0];
+                const bool live = ci < side * side && cl.valid;
+                const double lon = (&cl.L00)[p], lat = (&cl.y00)[p];   // L00, L01, L10, L11 and y00 .. y11 lie in this order
+                double v = 1.0;   // a layer that is not there asks for nothing
+#pragma unroll
+                for (int kk = 0; kk < NL; ++kk) {   // every lane takes part in the shuffles of every layer; it keeps its own layer's value
+                    const double vk = layer_refine_value<STEREO>(ly.l[kk], cl, lon, lat, g.oversample);
+                    v = kk == k ? vk : v;
+                }
+                const bool nan = group_max<16>(v != v ? 1.0 : 0.0) > 0.0;
+                const double vmax = group_max<16>(v != v ? 1.0 : v);
+                if (live && (lane & 15) == 0) {
+                    if (nan || !(vmax <= (double)RMAX)) {
+                        cells[ci].R = RMAX, cells[ci].clamped = 1;
+                    } else {
+                        cells[ci].R = vmax < 1.0 ? 1 : (int)vmax;
+                    }
+                }
+                __syncthreads();
+            }
+            LAcc acc{{0, 0, 0, INT_MAX, INT_MIN, 0, 0}, {0, 0, 0, 0}};
+            int Rmax = 0, n_pole = 0, n_clamped = 0;
+            for (int k = 0; k < side * side; ++k) {
+                const Cell cl = cells[k];
+                if (!cl.valid) continue;
+                Rmax = cl.R > Rmax ? cl.R : Rmax;
+                n_pole += cl.pole != 0;
+                n_clamped += cl.clamped;
+                if (cl.R != table_R) {   // s = (a + 0.5) / R and 1 - s for this R
+                    __syncthreads();
+                    for (int a = lane; a < cl.R; a += TT) {
+                        const double sv = ((double)a + 0.5) / (double)cl.R;
+                        S[a] = sv, U[a] = 1.0 - sv;
+                    }
+                    __syncthreads();
+                    table_R = cl.R;
+                }
+                sample_cell_layers<NL, STEREO>(ly, cl, S, U, lane, acc);
+            }
+            ogg_topog_record r;
+            r.n = wave_sum(acc.a.n), r.n_missing = wave_sum(acc.a.nm), r.n_wet = wave_sum(acc.a.nw);
+            r.sum = wave_sum(acc.a.sum), r.sumsq = wave_sum(acc.a.sumsq);
+            r.min = wave_min(acc.a.mn), r.max = wave_max(acc.a.mx);
+            r.R = Rmax, r.n_pole = (short)n_pole, r.n_clamped = (short)n_clamped;
+            const int f0 = wave_sum(acc.from[0]), f1 = wave_sum(acc.from[1]), f2 = wave_sum(acc.from[2]), f3 = wave_sum(acc.from[3]);
+            if (lane == 0) {
+                out[c].base = r;
+                out[c].n_from[0] = f0, out[c].n_from[1] = f1, out[c].n_from[2] = f2, out[c].n_from[3] = f3;
+            }
+            __syncthreads();   // cells[] is rewritten for the next output cell
+        }
+    }
+}
+
+// |q_mul * q| <= OGG_TOPOG_MAX_Q of every stored value (DT: INT16 with its fills, INT32 with OGG_TOPOG_MISSING_Q)
+template <typename T>
+__global__ void topog_range_kernel(const T* v, long n, int fill0, int fill1, int q_mul, int* n_bad) {
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
+        const int q = v[k];
+        const bool missing = sizeof(T) == 2 ? (q == fill0 || q == fill1) : q == OGG_TOPOG_MISSING_Q;
+        const long long p = (long long)q * q_mul;
+        if (!missing && (p > OGG_TOPOG_MAX_Q || p < -(long long)OGG_TOPOG_MAX_Q)) *n_bad = 1;   // every writer stores the same value
+    }
+}
+
+__global__ void topog_project_kernel(Layer L, long n, const double* lon, const double* lat, double* X, double* Y, int* gate_ok) {
+    const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    double x = 0.0, y = 0.0;
+    const bool ok = stereo_project(L, lon[k], lat[k], x, y);
+    X[k] = ok ? x : 0.0, Y[k] = ok ? y : 0.0, gate_ok[k] = ok ? 1 : 0;
+}
+
 template <typename T>
 __global__ void topog_quantize_kernel(const T* v, long n, double quantum, int n_fill, double f0, double f1, int* q, int* n_bad) {
     const long stride = (long)gridDim.x * blockDim.x;
@@ -427,6 +692,11 @@ int wet_threshold(double w) {
     return c > 2147483647.0 ? INT_MAX : (c < -2147483647.0 ? INT_MIN + 1 : (int)c);
 }
 
+Src make_src(const ogg_topog_source& q) {
+    return Src{q.data, q.dtype, int16_fill(q, 0), int16_fill(q, 1), wet_threshold(q.wet_below), q.Nx, q.Ny, q.lon0, q.lat0, 1.0 / q.dlon,
+               1.0 / q.dlat, q.dlon, q.dlat, fabs((double)q.Nx * q.dlon - 360.0) <= 1e-9};
+}
+
 long out_rows(const ogg_topog_band& b) {
     if (b.n_cell_rows == 0) return 0;
     const int sh = b.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0;
@@ -460,8 +730,7 @@ int band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* work
     Geo g{b.x, b.y, b.x_next, b.y_next, b.nx, b.nx + 1, b.j0, b.n_cell_rows, b.j0 >> shift, b.nx >> shift, 0, shift, b.refine,
           b.oversample};
     g.total = rows * g.nxo;
-    Src s{q.data, q.dtype, int16_fill(q, 0), int16_fill(q, 1), wet_threshold(q.wet_below), q.Nx, q.Ny, q.lon0, q.lat0, 1.0 / q.dlon,
-          1.0 / q.dlat, q.dlon, q.dlat, fabs((double)q.Nx * q.dlon - 360.0) <= 1e-9};
+    const Src s = make_src(q);
     hipStream_t st = ogg::as_stream(stream);
     OGG_HIP_CHECK(hipMemsetAsync(workspace, 0, sizeof(unsigned long long), st));
     int dev = 0, n_cu = 0;
@@ -578,4 +847,188 @@ extern "C" int ogg_topog(const ogg_topog_band* band, const ogg_topog_source* src
 
 extern "C" int ogg_topog_plane(const ogg_topog_band* band, const ogg_topog_source* src, ogg_topog_plane_record* out) {
     return topog_host(band, src, out, true);
+}
+
+// ---- layered topography: entry points ------------------------------------------------------------------------------------------
+namespace {
+
+int check_projection(const ogg_topog_projection& p, int k) {
+    OGG_REQUIRE(p.h == 1 || p.h == -1, OGG_EARG, "ogg_topog_layers: layer %d: hemisphere h = %d (+1 or -1)", k, p.h);
+    OGG_REQUIRE(p.e >= 0.0 && p.e < 0.2, OGG_EARG, "ogg_topog_layers: layer %d: eccentricity e = %g outside [0, 0.2)", k, p.e);
+    OGG_REQUIRE(p.K > 0.0 && std::isfinite(p.K) && std::isfinite(p.lon0), OGG_EARG, "ogg_topog_layers: layer %d: K = %g, lon0 = %g", k,
+                p.K, p.lon0);
+    OGG_REQUIRE(p.lat_gate >= -80.0 && p.lat_gate <= 90.0, OGG_EARG,
+                "ogg_topog_layers: layer %d: lat_gate = %g: the gate latitude (h * lat) must lie in [-80, 90]", k, p.lat_gate);
+    return OGG_OK;
+}
+
+int check_layer(const ogg_topog_layer& l, int k, bool sampled) {
+    OGG_REQUIRE(l.kind == OGG_TOPOG_LATLON || l.kind == OGG_TOPOG_POLAR_STEREO, OGG_EARG, "ogg_topog_layers: layer %d: kind = %d", k, l.kind);
+    OGG_REQUIRE(l.q_mul >= 1 && l.q_mul <= OGG_TOPOG_MAX_Q, OGG_EARG, "ogg_topog_layers: layer %d: q_mul = %d (1 .. %d)", k, l.q_mul,
+                OGG_TOPOG_MAX_Q);
+    if (l.kind == OGG_TOPOG_POLAR_STEREO) {
+        OGG_REQUIRE(l.src.dlon > 0.0 && l.src.dlat > 0.0, OGG_EARG, "ogg_topog_layers: layer %d: dX and dY must be positive (%g, %g)", k,
+                    l.src.dlon, l.src.dlat);
+        OGG_REQUIRE(std::isfinite(l.src.lon0) && std::isfinite(l.src.lat0) && std::isfinite(l.src.dlon) && std::isfinite(l.src.dlat), OGG_EARG,
+                    "ogg_topog_layers: layer %d: X0, dX, Y0, dY must be finite", k);
+        if (int e = check_projection(l.proj, k)) return e;
+    }
+    return check_source(l.src, sampled);
+}
+
+int check_layers(int n_layers, const ogg_topog_layer* layers, bool sampled) {
+    OGG_REQUIRE(n_layers >= 1 && n_layers <= OGG_TOPOG_MAX_SOURCES, OGG_EARG, "ogg_topog_layers: n_layers = %d (1 .. %d)", n_layers,
+                OGG_TOPOG_MAX_SOURCES);
+    OGG_REQUIRE(layers, OGG_EARG, "ogg_topog_layers: null layers");
+    for (int k = 0; k < n_layers; ++k)
+        if (int e = check_layer(layers[k], k, sampled)) return e;
+    return OGG_OK;
+}
+
+Layer make_layer(const ogg_topog_layer& l) {
+    Layer L{make_src(l.src), l.kind, l.q_mul, 1.0, 0.0, 0.0, 1.0, 0.0};
+    if (l.kind == OGG_TOPOG_POLAR_STEREO) {
+        L.s.periodic = false;
+        L.h = (double)l.proj.h, L.plon0 = l.proj.lon0, L.e = l.proj.e, L.K = l.proj.K, L.gate = l.proj.lat_gate;
+    }
+    return L;
+}
+
+}  // namespace
+
+// DEVICE pointers.  The caller has run ogg_topog_layer_range_dev on every layer and read n_bad = 0: the kernel forms q_mul * q in
+// int and does not look at its range again, so a layer that skipped that check can wrap silently (in the records, never in memory).
+extern "C" int ogg_topog_layers_band_dev(const ogg_topog_band* band, int n_layers, const ogg_topog_layer* layers, void* workspace,
+                                         long workspace_bytes, ogg_topog_merge_record* out, void* stream) {
+    OGG_REQUIRE(band, OGG_EARG, "ogg_topog_layers: null band");
+    if (int e = check_layers(n_layers, layers, true)) return e;
+    if (int e = check_band(*band)) return e;
+    const ogg_topog_band& b = *band;
+    const long rows = out_rows(b);
+    if (rows == 0) return OGG_OK;
+    OGG_REQUIRE(b.x && b.y && b.x_next && b.y_next && out, OGG_EARG, "ogg_topog_layers: null x / y / x_next / y_next / out");
+    if (int e = ogg::check_workspace("ogg_topog_layers", workspace, workspace_bytes, ogg_topog_workspace_bytes())) return e;
+    const int shift = b.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0;
+    Geo g{b.x, b.y, b.x_next, b.y_next, b.nx, b.nx + 1, b.j0, b.n_cell_rows, b.j0 >> shift, b.nx >> shift, 0, shift, b.refine,
+          b.oversample};
+    g.total = rows * g.nxo;
+    Layers ly;
+    ly.n = n_layers;
+    for (int k = 0; k < NLAY; ++k) ly.l[k] = make_layer(layers[k < n_layers ? k : 0]);   // the slots past n are never read
+    hipStream_t st = ogg::as_stream(stream);
+    OGG_HIP_CHECK(hipMemsetAsync(workspace, 0, sizeof(unsigned long long), st));
+    int dev = 0, n_cu = 0;
+    OGG_HIP_CHECK(hipGetDevice(&dev));
+    OGG_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    const long takes = (g.total + TR - 1) / TR;
+    const long wgs = std::min(takes, (long)(n_cu > 0 ? n_cu : 256) * 32);   // as ogg_topog_band_dev
+    auto* counter = static_cast<unsigned long long*>(workspace);
+    bool stereo = false;
+    for (int k = 0; k < n_layers; ++k) stereo = stereo || layers[k].kind == OGG_TOPOG_POLAR_STEREO;
+    const unsigned nwg = (unsigned)wgs;
+#define OGG_LAYERS_LAUNCH(NL)                                                              \
+    if (stereo)                                                                            \
+        topog_layers_kernel<NL, true><<<nwg, TT, 0, st>>>(g, ly, counter, out);            \
+    else                                                                                   \
+        topog_layers_kernel<NL, false><<<nwg, TT, 0, st>>>(g, ly, counter, out);           \
+    break
+    switch (n_layers) {
+        case 1: OGG_LAYERS_LAUNCH(1);
+        case 2: OGG_LAYERS_LAUNCH(2);
+        case 3: OGG_LAYERS_LAUNCH(3);
+        default: OGG_LAYERS_LAUNCH(4);
+    }
+#undef OGG_LAYERS_LAUNCH
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+extern "C" int ogg_topog_layer_range_dev(const ogg_topog_layer* layer, int* n_bad, void* stream) {
+    OGG_REQUIRE(layer && n_bad, OGG_EARG, "ogg_topog_layer_range: null pointer");
+    if (int e = check_layer(*layer, 0, true)) return e;
+    hipStream_t st = ogg::as_stream(stream);
+    OGG_HIP_CHECK(hipMemsetAsync(n_bad, 0, sizeof(int), st));
+    const ogg_topog_source& s = layer->src;
+    const long n = s.Nx * s.Ny;
+    const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 65536);
+    if (s.dtype == OGG_TOPOG_INT16)
+        topog_range_kernel<short><<<blocks, 256, 0, st>>>(static_cast<const short*>(s.data), n, int16_fill(s, 0), int16_fill(s, 1),
+                                                          layer->q_mul, n_bad);
+    else
+        topog_range_kernel<int><<<blocks, 256, 0, st>>>(static_cast<const int*>(s.data), n, 0, 0, layer->q_mul, n_bad);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+extern "C" int ogg_topog_project_dev(const ogg_topog_projection* proj, long n, const double* lon, const double* lat, double* X, double* Y,
+                                     int* gate_ok, void* stream) {
+    OGG_REQUIRE(proj && n >= 0, OGG_EARG, "ogg_topog_project: null projection or n = %ld", n);
+    if (int e = check_projection(*proj, 0)) return e;
+    ogg_topog_layer l{};   // the kernel's Layer of the projection alone: no raster, which stereo_project does not read
+    l.src.dlon = l.src.dlat = 1.0;
+    l.kind = OGG_TOPOG_POLAR_STEREO, l.q_mul = 1, l.proj = *proj;
+    if (n == 0) return OGG_OK;
+    OGG_REQUIRE(lon && lat && X && Y && gate_ok, OGG_EARG, "ogg_topog_project: null array");
+    topog_project_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ogg::as_stream(stream)>>>(make_layer(l), n, lon, lat, X, Y, gate_ok);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+// HOST pointers: the grid rows and every layer's raster copied to device memory (a float raster quantised there), the range of
+// q_mul * q checked, one band, the merge records copied back (synchronous)
+extern "C" int ogg_topog_layers(const ogg_topog_band* band, int n_layers, const ogg_topog_layer* layers, ogg_topog_merge_record* out) {
+    OGG_REQUIRE(band && out, OGG_EARG, "ogg_topog_layers: null pointer");
+    if (int e = check_layers(n_layers, layers, false)) return e;
+    if (int e = check_band(*band)) return e;
+    const ogg_topog_band& h = *band;
+    OGG_REQUIRE(h.x && h.y, OGG_EARG, "ogg_topog_layers: null x / y");
+    const long rows = out_rows(h);
+    if (rows == 0) return OGG_OK;
+    ogg::Buffers bufs;   // freed on every exit path
+    const long nxp = h.nx + 1, n = h.n_cell_rows;
+    ogg_topog_band d = h;
+    double *px, *py;
+    if (int e = bufs.alloc(&px, (size_t)(n + 1) * nxp)) return e;
+    if (int e = bufs.alloc(&py, (size_t)(n + 1) * nxp)) return e;
+    const size_t body = (size_t)n * nxp, row = (size_t)nxp;   // doubles
+    if (int e = bufs.send(px, h.x, body)) return e;
+    if (int e = bufs.send(py, h.y, body)) return e;
+    if (int e = bufs.send(px + body, h.x_next ? h.x_next : h.x + n * nxp, row)) return e;
+    if (int e = bufs.send(py + body, h.y_next ? h.y_next : h.y + n * nxp, row)) return e;
+    d.x = px, d.y = py;
+    d.x_next = d.x + n * nxp, d.y_next = d.y + n * nxp;
+    ogg_topog_layer dl[OGG_TOPOG_MAX_SOURCES];
+    int* bad;
+    if (int e = bufs.alloc(&bad, 1)) return e;
+    for (int k = 0; k < n_layers; ++k) {
+        dl[k] = layers[k];
+        ogg_topog_source& ds = dl[k].src;
+        const long nsrc = ds.Nx * ds.Ny;
+        const size_t esize = ds.dtype == OGG_TOPOG_INT16 ? 2 : (ds.dtype == OGG_TOPOG_FLOAT64 ? 8 : 4);
+        char* raw;
+        if (int e = bufs.put(&raw, static_cast<const char*>(ds.data), (size_t)nsrc * esize)) return e;
+        ds.data = raw;
+        int nb = 0;
+        if (ds.dtype == OGG_TOPOG_FLOAT32 || ds.dtype == OGG_TOPOG_FLOAT64) {
+            int* qd;
+            if (int e = bufs.alloc(&qd, (size_t)nsrc)) return e;
+            if (int e = ogg_topog_quantize_dev(&ds, qd, bad, nullptr)) return e;
+            if (int e = bufs.get(&nb, bad, 1)) return e;
+            OGG_REQUIRE(nb == 0, OGG_EARG, "ogg_topog_layers: layer %d: a quantised value exceeds %d in magnitude (quantum %g too small)", k,
+                        OGG_TOPOG_MAX_Q, ds.quantum);
+            ds.data = qd, ds.dtype = OGG_TOPOG_INT32, ds.n_fill = 0;
+        }
+        if (int e = ogg_topog_layer_range_dev(&dl[k], bad, nullptr)) return e;
+        if (int e = bufs.get(&nb, bad, 1)) return e;
+        OGG_REQUIRE(nb == 0, OGG_EARG, "ogg_topog_layers: layer %d: q_mul = %d times a stored value exceeds %d in magnitude", k, dl[k].q_mul,
+                    OGG_TOPOG_MAX_Q);
+    }
+    const long nrec = rows * (h.nx >> (h.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0));
+    char* ws;
+    ogg_topog_merge_record* res;
+    if (int e = bufs.alloc(&ws, (size_t)ogg_topog_workspace_bytes())) return e;
+    if (int e = bufs.alloc(&res, (size_t)nrec)) return e;
+    if (int e = ogg_topog_layers_band_dev(&d, n_layers, dl, ws, ogg_topog_workspace_bytes(), res, nullptr)) return e;
+    if (int e = bufs.get(out, res, (size_t)nrec)) return e;
+    return OGG_OK;
 }

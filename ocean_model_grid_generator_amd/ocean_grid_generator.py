@@ -659,8 +659,8 @@ def _description(head, names, merc_span, latUp_SO, lat0_SO, displaced_pole, sout
 class AnalysisFlags(object):
     """main()'s flags of the analyses that follow the grid (its docstring describes them), with main()'s defaults: what main() hands
     to either of its paths.  An unknown name is a TypeError."""
-    DEFAULTS = dict(quality_report=None, topog_source=None, topog_var="elevation", topog_file="topog.nc", topog_refine=None,
-                    topog_roughness=False, xgrid_atm=None,
+    DEFAULTS = dict(quality_report=None, topog_source=None, topog_var="elevation", topog_proj=None, topog_file="topog.nc",
+                    topog_refine=None, topog_roughness=False, xgrid_atm=None,
                     xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False,
                     mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False,
                     remap_fill_max=None, runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast",
@@ -680,10 +680,11 @@ class AnalysisFlags(object):
 
 
 def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
-    """Every refusal of the flags, on both of main()'s paths: before any device work and before any source file is opened."""
+    """Every refusal of the flags, on both of main()'s paths: before any device work and before any source file is read (with
+    --topog_roughness the header of the one topography file is, for its grid mapping)."""
     _validate_flags(match_dy, r_dp, lat_dp)
     _validate_mask_flags(a.ocean_mask_file, a.topog_source)
-    _validate_roughness_flags(a.topog_roughness, a.topog_source)
+    _validate_roughness_flags(a.topog_roughness, a.topog_source, a.topog_proj, a.topog_var)
     _validate_remap_flags(a.remap_source, a.remap_var)
     _validate_runoff_flags(a.runoff_source, a.runoff_var, a.topog_source, a.runoff_targets, skip_metrics)
     _validate_coast_distance_flags(a.coast_distance_file, a.coast_distance_sides, a.topog_source)
@@ -712,7 +713,7 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          xgrid_cs_lon_shift=0.0, xgrid_cs_file="atmos_mosaic_tile%dXocean_mosaic_tile1.nc", xgrid_cs_frac_file=None,
          mask_table_layout=None, mask_table_dir=None, layout_sweep=None, layout_target_pes=None, layout_report=None, layout_halo=0,
          layout_min_block=2, layout_xextent=None, layout_yextent=None, locate_points=None, locate_file="points.nc",
-         locate_mode="bilinear"):
+         locate_mode="bilinear", topog_proj=None):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -731,7 +732,12 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     sample that raster (variable ``topog_var``) on the model cells of the stitched grid straight from HBM and write ``topog_file``
     (topography.py; ``topog_refine``: R x R samples per supergrid cell instead of R from the cell's size; ``topog_roughness``
     (--topog_roughness): also fit a plane to every cell's samples and write the roughness h2 about it, the bottom slopes slope_east and
-    slope_north, and plane_flag); also an addition.
+    slope_north, and plane_flag); also an addition.  ``topog_source`` may also be a list of up to four files or Sources in order of
+    priority (--topog_source repeated; ``topog_var`` and ``topog_proj`` then one value, or a list of one per source), and a source may
+    be a polar-stereographic raster in metres (a CF grid mapping in the file, or ``topog_proj``, --topog_proj
+    stere:S,lat_ts=-71,lon0=0): every sample takes the first source that has a value for it, ``topog_file`` also holds n_from_source,
+    and ``topog_roughness`` is refused (topography.py, "Layered topography" in the header).  One lat-lon source, however it is spelt,
+    takes the single-source path and writes the file it always wrote.
     ``xgrid_atm`` (--xgrid_atm NLON NLAT): write the exchange grid of the model cells with a regular global NLON x NLAT atmosphere to
     ``xgrid_file`` (exchange_grid.py; only cells with depth > 0 when ``topog_source`` is given too); also an addition.
     ``ocean_mask_file`` (--ocean_mask_file FILE, needs ``topog_source``): the ocean mask of that topography (ocean_mask.py: cells
@@ -1098,7 +1104,8 @@ def _run_analyses(a, g, cut=None):
         _write_quality_report(g.quality(cut), a.quality_report)
     topo = None
     if a.topog_source is not None:
-        topo = g.topography(cut, _topog_source(a.topog_source, a.topog_var), refine=a.topog_refine, plane=bool(a.topog_roughness))
+        topo = g.topography(cut, _topog_source(a.topog_source, a.topog_var, a.topog_proj), refine=a.topog_refine,
+                            plane=bool(a.topog_roughness))
         mask = None
         if a.ocean_mask_file:
             mask = g.ocean_mask(cut, topo, **_mask_args(a.mask_min_depth, a.mask_deepen, a.mask_seed, a.mask_keep_cells))
@@ -1237,13 +1244,21 @@ def _write_quality_report(rep, fnam):
         json.dump(rep, f, indent=1)
 
 
-def _topog_source(source, var):
+def _topog_source(source, var, proj=None):
+    """What the topography samples: ``source`` a file, a topography.Source, or a list of either in order of priority (``var`` and
+    ``proj``: one value, or one per source).  One lat-lon source, alone or in a list, gives the Source it always gave."""
     from . import topography as T
-    if isinstance(source, T.Source):
-        return source
-    src = T.read_source(str(source), var)
-    print(src.note)
-    return src
+    if isinstance(source, (T.Source, T.SourceList)):
+        return T.as_sources(source)
+    items = list(source) if isinstance(source, (list, tuple)) else [source]
+    var, proj = T.per_source(var, len(items), "--topog_var", "elevation"), T.per_source(proj, len(items), "--topog_proj")
+    srcs = []
+    for s, v, pr in zip(items, var, proj):
+        if not isinstance(s, T.Source):
+            s = T.read_source(str(s), v, projection=pr)
+            print(s.note)
+        srcs.append(s)
+    return T.as_sources(srcs)
 
 
 def _write_topog(res, fnam):
@@ -1259,9 +1274,27 @@ def _validate_mask_flags(ocean_mask_file, topog_source):
         raise ValueError("--ocean_mask_file needs --topog_source: the ocean mask is made from the topography")
 
 
-def _validate_roughness_flags(topog_roughness, topog_source):
+def _validate_roughness_flags(topog_roughness, topog_source, topog_proj=None, topog_var=None):
     if topog_roughness and topog_source is None:
         raise ValueError("--topog_roughness needs --topog_source: the roughness and the bottom slopes come from the topography's samples")
+    if topog_roughness and _topog_layered(topog_source, topog_proj, topog_var):
+        from . import topography as T
+        raise ValueError("--topog_roughness: " + T.NO_PLANE)
+
+
+def _topog_layered(topog_source, topog_proj=None, topog_var=None):
+    """whether the flags ask for layered topography, told before any device work: more than one source, a projection flag, a
+    projected Source, or one file whose variable names a polar stereographic grid mapping (its header is read; --topog_proj latlon
+    overrides the mapping)"""
+    from . import topography as T
+    items = list(topog_source) if isinstance(topog_source, (list, tuple)) else [topog_source]
+    projs = [topog_proj] if isinstance(topog_proj, str) else list(topog_proj or [])
+    if len(items) > 1 or any(p not in (None, "latlon") for p in projs) or \
+            any(getattr(s, "projection", None) is not None or hasattr(s, "sources") for s in items):
+        return True
+    if isinstance(items[0], T.Source) or "latlon" in projs:
+        return False
+    return T.file_projection(str(items[0]), T.per_source(topog_var, 1, "--topog_var", "elevation")[0]) is not None
 
 
 def _validate_remap_flags(remap_source, remap_var):
@@ -1524,9 +1557,15 @@ def build_parser():
     parser.add_argument("--quality_report", type=str, required=False, default=None,
                         help="write a grid-quality report (cell sizes, aspect ratio, non-orthogonality, smoothness, sub-grid seams) "
                              "of the stitched grid to this JSON file and print a summary")
-    parser.add_argument("--topog_source", type=str, required=False, default=None,
-                        help="bathymetry raster (NetCDF classic / 64-bit offset) to sample on the model cells of the grid into --topog_file")
-    parser.add_argument("--topog_var", type=str, required=False, default="elevation", help="variable of --topog_source, default elevation")
+    parser.add_argument("--topog_source", type=str, required=False, default=None, action="append",
+                        help="bathymetry raster (NetCDF classic / 64-bit offset) to sample on the model cells of the grid into --topog_file; "
+                             "repeat it (up to four times) for layers in order of priority: every sample takes the first that has a "
+                             "value for it; a source may be a polar-stereographic raster in metres (a CF grid mapping, or --topog_proj)")
+    parser.add_argument("--topog_var", type=str, required=False, default=None, action="append",
+                        help="variable of --topog_source, default elevation; once, or once per --topog_source")
+    parser.add_argument("--topog_proj", type=str, required=False, default=None, action="append", metavar="PROJ",
+                        help="projection of a --topog_source that states none: stere:S,lat_ts=-71,lon0=0[,a=..,rf=..], or latlon; once, "
+                             "or once per --topog_source")
     parser.add_argument("--topog_file", type=str, required=False, default="topog.nc", help="topography output file, default topog.nc")
     parser.add_argument("--topog_refine", type=int, required=False, default=None,
                         help="R x R samples in every supergrid cell (default: from each cell's size, twice the raster's resolution)")

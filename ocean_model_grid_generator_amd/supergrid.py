@@ -1296,7 +1296,8 @@ class Supergrid(object):
         """[(piece index, first output row, int64 device tensor of records)] of THIS rank's pieces of the stitched grid, sampled on the
         buffers the pass left in HBM.  A piece's last cell row takes its upper point row from the next piece (quality_halo); a model
         row whose two supergrid rows lie in two pieces gets a partial record from each, combined exactly by the caller.  ``plane``:
-        plane records (ogg_topog_plane_band_dev)."""
+        plane records (ogg_topog_plane_band_dev).  ``source``: a topography.DeviceSource, or a DeviceSourceList (merge records,
+        ogg_topog_layers_band_dev)."""
         from . import topography as T
         p, st = self.plan, self._stream()
         halo = self.quality_halo(cut) if halo is None else halo   # (held until the kernels have run: the bands point into it)
@@ -1318,16 +1319,22 @@ class Supergrid(object):
 
     def topography(self, cut, source, refine=None, oversample=2.0, cells="model", plane=False):
         """Topography of the stitched grid of every rank (topography.result on rank 0, None on the other ranks): ``source`` a
-        topography.DeviceSource on this rank's GPU, or a topography.Source to upload there.  Every piece is sampled by the rank that holds it; rank 0 gathers the integer records
+        topography.DeviceSource (DeviceSourceList) on this rank's GPU, or a topography.Source (SourceList: layers in order of priority,
+        every rank uploads every one) to upload there.  Every piece is sampled by the rank that holds it; rank 0 gathers the integer records
         (_gather) and combines them exactly, so the result is bit-identical for any number of ranks.  ``plane``: plane records through
         the same gather, and the stitched latitudes gathered on rank 0 (_stitched) for the slopes of the plane."""
         from . import topography as T
         if isinstance(source, T.Source):
             source = T.DeviceSource(source, self.device)
+        elif isinstance(source, T.SourceList):
+            source = T.DeviceSourceList(source, self.device)
+        layered = isinstance(source, T.DeviceSourceList)
+        if layered and plane:
+            raise ValueError(T.NO_PLANE)
         nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
         T.check_args(nyp, nxp, cells, refine, oversample)
         sh = 1 if cells == "model" else 0
-        words = T.record_words(plane)
+        words = T.record_words(plane, layered)
 
         def recv(k, q, take):
             if q["n_cell"] == 0:
