@@ -2,20 +2,32 @@
 // supergrid cells, or one supergrid cell) is filled with R x R samples per supergrid cell, each sample looks up its source raster
 // element, and the cell keeps integer sums, extremes and counts.
 //
-// topog_band_kernel: one wavefront per workgroup.  A wavefront takes runs of TR consecutive output cells of a row from a counter in
-// the workspace (so the cells that need many samples -- R up to 256 next to a pole -- do not hold up a static share), and owns each
-// output cell it takes: lanes 0..3 set up the (up to) four supergrid cells of it (unwrapped corners, R, pole test) into LDS, then the
-// whole wavefront walks the flattened samples f = b * R + a of each supergrid cell, lane l taking f = l, l + 64, ...: consecutive
-// lanes are consecutive a (along i, i.e. along a raster row), so one gather instruction touches a few 128-B lines.  s = (a + 0.5) / R
-// and 1 - s come from a per-wavefront LDS table rebuilt when R changes (two fp64 divisions per sample would otherwise dominate).
-// Each lane keeps its own counts, sums and extremes in registers; the wavefront reduces them with shuffles (integers: exact, in any
-// order) and lane 0 stores the record.  No atomics touch a result; the only atomic is the work counter.
+// topog_walk: the one sampling walk, one wavefront per workgroup.  A wavefront takes runs of TR consecutive output cells of a row
+// from a counter in the workspace (so the cells that need many samples -- R up to 256 next to a pole -- do not hold up a static
+// share), and owns each output cell it takes: lanes 0..3 set up the (up to) four supergrid cells of it (unwrapped corners, R, pole
+// test) into LDS, then the whole wavefront walks the flattened samples f = b * R + a of each supergrid cell, lane l taking f = l,
+// l + 64, ...: consecutive lanes are consecutive a (along i, i.e. along a raster row), so one gather instruction touches a few 128-B
+// lines.  s = (a + 0.5) / R and 1 - s come from a per-wavefront LDS table rebuilt when R changes (two fp64 divisions per sample would
+// otherwise dominate).  Each lane keeps its own counts, sums and extremes in registers; the wavefront reduces them with shuffles
+// (integers: exact, in any order) and lane 0 stores the record.  No atomics touch a result; the only atomic is the work counter.
+// The positions of the samples are formed in the walk alone, so every entry point samples the same points bit for bit.  Where R comes
+// from when the band does not fix it, what a sample is worth and what the record holds are a sampler's: the hooks listed at
+// topog_walk, resolved at compile time, so that a hook a sampler has no use for is an empty function.
 //
-// PLANE (ogg_topog_plane_band_dev): the same walk also keeps the integer moments of the least-squares plane of "Plane-fit
-// topography".  Lane 0 sets up the output cell's origin (its raster column and row) into LDS next to cells[]; a sample's offsets
-// from it are int32 differences of the indices the loop already has (the periodic column offset folded into [-Nx/2, Nx/2) with two
-// conditional steps: the same residue as the definition's fold of the unreduced index), tested against the limit, and accumulated
-// as int32 sums and 32 x 32 + 64-bit multiply-adds per lane.  The PLANE = false instantiations are the code they were.
+// SingleSampler<DT, PLANE> (topog_band_kernel; "Topography by refined sampling"): one lat-lon raster, its dtype a compile-time
+// constant; R of a supergrid cell is the setting-up lane's own affair.  PLANE (ogg_topog_plane_band_dev) also keeps the integer
+// moments of the least-squares plane of "Plane-fit topography".  Lane 0 sets up the output cell's origin (its raster column and row)
+// into LDS; a sample's offsets from it are int32 differences of the indices the sample already has (the periodic column offset
+// folded into [-Nx/2, Nx/2) with two conditional steps: the same residue as the definition's fold of the unreduced index), tested
+// against the limit, and accumulated as int32 sums and 32 x 32 + 64-bit multiply-adds per lane.  PLANE = false carries none of it.
+//
+// LayerSampler<NL, STEREO> (topog_layers_kernel; "Layered topography"): every sample is offered to the layers in list order.  The
+// layers are a kernel argument, so their descriptors arrive in scalar registers; the kernel is instantiated per number of layers and
+// the loop over them is unrolled (no indexed copy of the argument, and a short list stays in registers), and kind and dtype are
+// uniform over the wavefront.  A projected layer costs a sample two sincos, one division and the two short series of ogg_math.h; a
+// sample that fails the gate costs one compare.  The refinement of a cell takes the layers' corner projections: lane 16 c + 4 k + p
+// projects corner p of supergrid cell c in layer k, so the up to 64 projections of an output cell run side by side, and shuffles
+// within the 16 lanes of a cell reduce them to its R.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -73,7 +85,8 @@ OGG_DEV double mod360(double x) {
 
 OGG_DEV double wrap180(double d) { return mod360(d + 180.0) - 180.0; }
 
-OGG_DEV Cell setup_cell(const Geo& g, const Src& s, long j, long i) {
+// the geometry of supergrid cell (j, i) of the band: corners with unwrapped longitudes, the pole test, R as the band fixes it (0: not)
+OGG_DEV Cell cell_geometry(const Geo& g, long j, long i) {
     Cell c;
     c.valid = 1;
     const long r = j - g.j0;   // 0 .. n - 1
@@ -90,24 +103,28 @@ OGG_DEV Cell setup_cell(const Geo& g, const Src& s, long j, long i) {
     c.L01 = fabs(c.y01) >= pl ? l00 : l01;
     c.L10 = fabs(c.y10) >= pl ? l11 : l10;
     c.L11 = fabs(c.y11) >= pl ? l10 : l11;
-    c.clamped = 0;
-    if (g.refine > 0) {
-        c.R = g.refine;
-    } else {
-        const double span_l = fmax(fmax(c.L00, c.L01), fmax(c.L10, c.L11)) - fmin(fmin(c.L00, c.L01), fmin(c.L10, c.L11));
-        const double span_y = fmax(fmax(c.y00, c.y01), fmax(c.y10, c.y11)) - fmin(fmin(c.y00, c.y01), fmin(c.y10, c.y11));
-        // fmax / fmin drop a NaN operand; a cell with a NaN corner has no span, and its R is clamped
-        const double any = (c.L00 + c.L01) + (c.L10 + c.L11) + (c.y00 + c.y01) + (c.y10 + c.y11);
-        const double v = any != any ? any : ceil(g.oversample * fmax(span_l / s.dlon, span_y / s.dlat));
-        if (!(v <= (double)RMAX)) {
-            c.R = RMAX, c.clamped = 1;
-        } else {
-            c.R = v < 1.0 ? 1 : (int)v;
-        }
-    }
+    c.R = g.refine, c.clamped = 0;
     const double w = wrap180(c.L01 - c.L00) + wrap180(c.L11 - c.L01) + wrap180(c.L10 - c.L11) + wrap180(c.L00 - c.L10);
     c.pole = fabs(w) > 180.0 ? ((c.y00 + c.y01 + c.y10 + c.y11 > 0.0) ? 1 : -1) : 0;
     return c;
+}
+
+// v of the header's "refine" for a lat-lon raster of spacing dlon x dlat
+OGG_DEV double latlon_refine_value(const Cell& c, double dlon, double dlat, double oversample) {
+    const double span_l = fmax(fmax(c.L00, c.L01), fmax(c.L10, c.L11)) - fmin(fmin(c.L00, c.L01), fmin(c.L10, c.L11));
+    const double span_y = fmax(fmax(c.y00, c.y01), fmax(c.y10, c.y11)) - fmin(fmin(c.y00, c.y01), fmin(c.y10, c.y11));
+    // fmax / fmin drop a NaN operand; a cell with a NaN corner has no span, and its R is clamped
+    const double any = (c.L00 + c.L01) + (c.L10 + c.L11) + (c.y00 + c.y01) + (c.y10 + c.y11);
+    return any != any ? any : ceil(oversample * fmax(span_l / dlon, span_y / dlat));
+}
+
+// R of a cell from its refinement value: not <= RMAX, or NaN: RMAX and clamped; below 1: 1
+OGG_DEV void set_refine(Cell& c, double v) {
+    if (!(v <= (double)RMAX)) {
+        c.R = RMAX, c.clamped = 1;
+    } else {
+        c.R = v < 1.0 ? 1 : (int)v;
+    }
 }
 
 // the origin of an output cell's plane fit, set up once per output cell.  valid = 0: the cell has no origin, or one so far outside
@@ -185,98 +202,33 @@ OGG_DEV bool latlon_index(const Src& s, int pole, double lon, double lat, int& i
     return miss;
 }
 
+// element (is, js) of a raster of int16 (with its fills) or int32 (with OGG_TOPOG_MISSING_Q) as an integer; true when it is MISSING.
+// dtype is s.dtype, handed over apart so that a caller that knows it at compile time says so
+OGG_DEV bool raster_value(const Src& s, int dtype, int is, int js, int& v) {
+    if (dtype == OGG_TOPOG_INT16) {
+        v = static_cast<const short*>(s.data)[(long)js * s.Nx + is];
+        return v == s.fill0 || v == s.fill1;
+    }
+    v = static_cast<const int*>(s.data)[(long)js * s.Nx + is];
+    return v == OGG_TOPOG_MISSING_Q;
+}
+
+// what a lane keeps of the samples it takes
 struct Acc {
     int n, nm, nw, mn, mx;
     long long sum, sumsq;
 };
 
-// the moments of the plane fit: a lane sees at most 4 * 256 * 256 / 64 = 4096 samples of a record, |offset| <= 2^15, |q| <= 2^21
-struct PAcc {
-    int sx, sy, nfar;
-    long long sxx, sxy, syy, sxq, syq;
-};
-
-// what a lane carries for the plane fit through the supergrid cells of one output cell.  PLANE = false: nothing -- no origin, no
-// moments, no LDS behind it -- so the sampling without the plane cannot touch any of it
-template <bool PLANE>
-struct PlaneLane {};
-template <>
-struct PlaneLane<true> {
-    PAcc acc;
-    Origin o;   // the output cell's origin, read from LDS once
-};
-
-template <int DT, bool PLANE>
-OGG_DEV void sample_cell(const Src& s, const Cell& c, const double* S, const double* U, int lane, Acc& acc, PlaneLane<PLANE>& pl) {
-    const int R = c.R;
-    const int RR = R * R;
-    int f = lane;
-    if (f >= RR) return;
-    int a = f % R, b = f / R;
-    const int step_b = TT / R, step_a = TT % R;
-    const long Nx = s.Nx;
-    [[maybe_unused]] bool far_cell = false;   // PLANE only: no origin, or a pole-enclosing cell (no latitude): every valid sample is far
-    if constexpr (PLANE) far_cell = !pl.o.valid || c.pole != 0;
-    for (; f < RR; f += TT) {
-        const double sa = S[a], ua = U[a];
-        double lon, lat = 0.0;
-        if (c.pole == 0) {
-            const double tb = S[b], vb = U[b];
-            const double w00 = ua * vb, w01 = sa * vb, w10 = ua * tb, w11 = sa * tb;
-            lon = w00 * c.L00 + w01 * c.L01 + w10 * c.L10 + w11 * c.L11;
-            lat = w00 * c.y00 + w01 * c.y01 + w10 * c.y10 + w11 * c.y11;
-        } else {
-            lon = c.L00 + 360.0 * sa;
-        }
-        int is, js;
-        bool miss = latlon_index(s, c.pole, lon, lat, is, js);
-        if (!miss) {
-            int q;
-            if (DT == OGG_TOPOG_INT16) {
-                const int v = static_cast<const short*>(s.data)[(long)js * Nx + is];
-                miss = v == s.fill0 || v == s.fill1;
-                q = v;
-            } else {
-                q = static_cast<const int*>(s.data)[(long)js * Nx + is];
-                miss = q == OGG_TOPOG_MISSING_Q;
-            }
-            if (!miss) {
-                acc.n += 1;
-                acc.nw += q < s.wet_q ? 1 : 0;
-                acc.sum += q;
-                acc.sumsq += (long long)q * q;
-                acc.mn = q < acc.mn ? q : acc.mn;
-                acc.mx = q > acc.mx ? q : acc.mx;
-                if constexpr (PLANE) {
-                    // The definition forms the offsets as integral doubles and tests them against the limit before any cast.  Here
-                    // they are int32 differences, which is the same test: is, js and Nx, Ny lie in [0, 2^30) (check_source), a
-                    // periodic origin is a residue in [0, Nx) less Nx div 2 and its row is clamped to [0, Ny), and a regional origin
-                    // is admitted (valid) only in [-2^16, 2^30 + 2^16), so every difference and every step of the fold below stays
-                    // within +-(2^31 - 1); an origin outside that gate is more than 2^15 from every sample, which far_cell says.
-                    // With |dI|, |dJ| < 2^31 - 2^15 the unsigned compare of d + 2^15 against 2^16 is |d| > 2^15.
-                    const Origin& o = pl.o;
-                    PAcc& pacc = pl.acc;
-                    int dI = is - o.oI;
-                    if (s.periodic) {   // ((fi - fI0 + hN) mod Nx) - hN from the two residues
-                        dI += dI < 0 ? (int)Nx : 0;
-                        dI -= dI >= (int)Nx ? (int)Nx : 0;
-                        dI -= (int)(Nx >> 1);
-                    }
-                    const int dJ = js - o.J0;
-                    const bool far = far_cell || (unsigned)(dI + MAXO) > 2u * MAXO || (unsigned)(dJ + MAXO) > 2u * MAXO;
-                    const int eI = far ? 0 : dI, eJ = far ? 0 : dJ, eq = far ? 0 : q;
-                    pacc.nfar += far ? 1 : 0;
-                    pacc.sx += eI, pacc.sy += eJ;
-                    pacc.sxx += (long long)eI * eI, pacc.sxy += (long long)eI * eJ, pacc.syy += (long long)eJ * eJ;
-                    pacc.sxq += (long long)eI * eq, pacc.syq += (long long)eJ * eq;
-                }
-            }
-        }
-        if (miss) acc.nm += 1;
-        a += step_a, b += step_b;
-        if (a >= R) a -= R, b += 1;
-    }
+OGG_DEV void count_valid(Acc& acc, int q, int wet_q) {
+    acc.n += 1;
+    acc.nw += q < wet_q ? 1 : 0;
+    acc.sum += q;
+    acc.sumsq += (long long)q * q;
+    acc.mn = q < acc.mn ? q : acc.mn;
+    acc.mx = q > acc.mx ? q : acc.mx;
 }
+
+OGG_DEV void count_missing(Acc& acc) { acc.nm += 1; }
 
 OGG_DEV long long wave_sum(long long v) {
     for (int o = TT / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, TT);
@@ -295,17 +247,44 @@ OGG_DEV int wave_max(int v) {
     return v;
 }
 
-template <int DT, bool PLANE>
-__global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned long long* counter, void* records) {
-    auto* out = static_cast<std::conditional_t<PLANE, ogg_topog_plane_record, ogg_topog_record>*>(records);
+// a lane's share of the R x R samples of supergrid cell c: their positions, each handed to the sampler
+template <class Sampler>
+OGG_DEV void sample_cell(Sampler& sm, const Cell& c, const double* S, const double* U, int lane, Acc& acc) {
+    const int R = c.R;
+    const int RR = R * R;
+    int f = lane;
+    if (f >= RR) return;
+    int a = f % R, b = f / R;
+    const int step_b = TT / R, step_a = TT % R;
+    for (; f < RR; f += TT) {
+        const double sa = S[a], ua = U[a];
+        double lon, lat = 0.0;
+        if (c.pole == 0) {
+            const double tb = S[b], vb = U[b];
+            const double w00 = ua * vb, w01 = sa * vb, w10 = ua * tb, w11 = sa * tb;
+            lon = w00 * c.L00 + w01 * c.L01 + w10 * c.L10 + w11 * c.L11;
+            lat = w00 * c.y00 + w01 * c.y01 + w10 * c.y10 + w11 * c.y11;
+        } else {
+            lon = c.L00 + 360.0 * sa;
+        }
+        sm.sample(c, lon, lat, acc);
+        a += step_a, b += step_b;
+        if (a >= R) a -= R, b += 1;
+    }
+}
+
+// The walk.  A Sampler has
+//   lane_refine(g, cl)            R of supergrid cell cl by the lane that sets it up, where one lane can tell
+//   stage(g, m, io, lane)         what the sampler keeps in LDS for output cell (m, io), before the barrier that publishes cells[]
+//   begin(g, cells, side, lane)   after it: R of the cells where that takes the wavefront (then closed by a barrier of the sampler's
+//                                 own), and the lane's state for the output cell
+//   sample(c, lon, lat, acc)      one sample of supergrid cell c at (lon, lat), or at lon alone where c encloses a pole, counted in acc
+//   finish(c, r, lane)            the record of output cell c; r, its base, is the same in every lane
+template <class Sampler>
+OGG_DEV void topog_walk(const Geo& g, unsigned long long* counter, Sampler& sm) {
     __shared__ double S[RMAX], U[RMAX];
     __shared__ Cell cells[4];
     __shared__ long long take;
-    [[maybe_unused]] Origin* org = nullptr;   // PLANE only: the output cell's origin in LDS, next to cells[]
-    if constexpr (PLANE) {
-        __shared__ Origin origin;
-        org = &origin;
-    }
     const int lane = threadIdx.x;
     int table_R = 0;
     const int side = 1 << g.shift;
@@ -322,19 +301,17 @@ __global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned l
                 const long j = (m << g.shift) + (lane >> 1), i = (io << g.shift) + (lane & 1);
                 Cell cl;
                 if (j >= g.j0 && j < g.j0 + g.n) {
-                    cl = setup_cell(g, s, j, i);
+                    cl = cell_geometry(g, j, i);
+                    sm.lane_refine(g, cl);
                 } else {
                     cl.valid = 0, cl.R = 0, cl.pole = 0, cl.clamped = 0;
                 }
                 cells[lane] = cl;
             }
-            if constexpr (PLANE) {
-                if (lane == 0) *org = setup_origin(g, s, m, io);
-            }
+            sm.stage(g, m, io, lane);
             __syncthreads();
+            sm.begin(g, cells, side, lane);
             Acc acc{0, 0, 0, INT_MAX, INT_MIN, 0, 0};
-            PlaneLane<PLANE> pl;
-            if constexpr (PLANE) pl.acc = PAcc{0, 0, 0, 0, 0, 0, 0, 0}, pl.o = *org;
             int Rmax = 0, n_pole = 0, n_clamped = 0;
             for (int k = 0; k < side * side; ++k) {
                 const Cell cl = cells[k];
@@ -351,39 +328,115 @@ __global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned l
                     __syncthreads();
                     table_R = cl.R;
                 }
-                sample_cell<DT, PLANE>(s, cl, S, U, lane, acc, pl);
+                sample_cell(sm, cl, S, U, lane, acc);
             }
-            const int n = wave_sum(acc.n), nm = wave_sum(acc.nm), nw = wave_sum(acc.nw);
-            const long long sum = wave_sum(acc.sum), sumsq = wave_sum(acc.sumsq);
-            const int mn = wave_min(acc.mn), mx = wave_max(acc.mx);
             ogg_topog_record r;
-            r.n = n, r.n_missing = nm, r.n_wet = nw, r.sum = sum, r.sumsq = sumsq;
-            r.min = mn, r.max = mx, r.R = Rmax, r.n_pole = (short)n_pole, r.n_clamped = (short)n_clamped;
-            if constexpr (PLANE) {
-                const PAcc& a = pl.acc;
-                ogg_topog_plane_record p;   // the wavefront's moments; a lane's sums of offsets fit int32, the wavefront's need not
-                p.base = r;
-                p.sx = wave_sum((long long)a.sx), p.sy = wave_sum((long long)a.sy), p.n_far = wave_sum(a.nfar);
-                p.sxx = wave_sum(a.sxx), p.sxy = wave_sum(a.sxy), p.syy = wave_sum(a.syy);
-                p.sxq = wave_sum(a.sxq), p.syq = wave_sum(a.syq);
-                if (lane == 0) out[c] = p;
-            } else {
-                if (lane == 0) out[c] = r;
-            }
+            r.n = wave_sum(acc.n), r.n_missing = wave_sum(acc.nm), r.n_wet = wave_sum(acc.nw);
+            r.sum = wave_sum(acc.sum), r.sumsq = wave_sum(acc.sumsq);
+            r.min = wave_min(acc.mn), r.max = wave_max(acc.mx);
+            r.R = Rmax, r.n_pole = (short)n_pole, r.n_clamped = (short)n_clamped;
+            sm.finish(c, r, lane);
             __syncthreads();   // cells[] is rewritten for the next output cell
         }
     }
 }
 
+// the moments of the plane fit: a lane sees at most 4 * 256 * 256 / 64 = 4096 samples of a record, |offset| <= 2^15, |q| <= 2^21
+struct PAcc {
+    int sx, sy, nfar;
+    long long sxx, sxy, syy, sxq, syq;
+};
+
+// what a lane carries for the plane fit through the supergrid cells of one output cell.  PLANE = false: nothing -- no origin, no
+// moments, no LDS behind it -- so the sampling without the plane cannot touch any of it
+template <bool PLANE>
+struct PlaneLane {};
+template <>
+struct PlaneLane<true> {
+    PAcc acc;
+    Origin o;       // the output cell's origin, read from LDS once
+    Origin* lds;    // where lane 0 puts it
+};
+
+template <int DT, bool PLANE>
+struct SingleSampler {
+    using Record = std::conditional_t<PLANE, ogg_topog_plane_record, ogg_topog_record>;
+    const Src& s;
+    Record* out;
+    PlaneLane<PLANE> pl;
+
+    OGG_DEV void lane_refine(const Geo& g, Cell& cl) {
+        if (g.refine <= 0) set_refine(cl, latlon_refine_value(cl, s.dlon, s.dlat, g.oversample));
+    }
+    OGG_DEV void stage(const Geo& g, long m, long io, int lane) {
+        if constexpr (PLANE) {
+            if (lane == 0) *pl.lds = setup_origin(g, s, m, io);
+        }
+    }
+    OGG_DEV void begin(const Geo&, Cell*, int, int) {
+        if constexpr (PLANE) pl.acc = PAcc{0, 0, 0, 0, 0, 0, 0, 0}, pl.o = *pl.lds;
+    }
+    OGG_DEV void sample(const Cell& c, double lon, double lat, Acc& acc) {
+        int is, js, q;
+        bool miss = latlon_index(s, c.pole, lon, lat, is, js);
+        if (!miss) miss = raster_value(s, DT, is, js, q);
+        if (miss) {
+            count_missing(acc);
+            return;
+        }
+        count_valid(acc, q, s.wet_q);
+        if constexpr (PLANE) {
+            // The definition forms the offsets as integral doubles and tests them against the limit before any cast.  Here
+            // they are int32 differences, which is the same test: is, js and Nx, Ny lie in [0, 2^30) (check_source), a
+            // periodic origin is a residue in [0, Nx) less Nx div 2 and its row is clamped to [0, Ny), and a regional origin
+            // is admitted (valid) only in [-2^16, 2^30 + 2^16), so every difference and every step of the fold below stays
+            // within +-(2^31 - 1); an origin outside that gate is more than 2^15 from every sample, which far_cell says.
+            // With |dI|, |dJ| < 2^31 - 2^15 the unsigned compare of d + 2^15 against 2^16 is |d| > 2^15.
+            const Origin& o = pl.o;
+            PAcc& pacc = pl.acc;
+            const bool far_cell = !o.valid || c.pole != 0;   // no origin, or a pole-enclosing cell (no latitude): every valid sample is far
+            const int Nx = (int)s.Nx;
+            int dI = is - o.oI;
+            if (s.periodic) {   // ((fi - fI0 + hN) mod Nx) - hN from the two residues
+                dI += dI < 0 ? Nx : 0;
+                dI -= dI >= Nx ? Nx : 0;
+                dI -= (int)(s.Nx >> 1);
+            }
+            const int dJ = js - o.J0;
+            const bool far = far_cell || (unsigned)(dI + MAXO) > 2u * MAXO || (unsigned)(dJ + MAXO) > 2u * MAXO;
+            const int eI = far ? 0 : dI, eJ = far ? 0 : dJ, eq = far ? 0 : q;
+            pacc.nfar += far ? 1 : 0;
+            pacc.sx += eI, pacc.sy += eJ;
+            pacc.sxx += (long long)eI * eI, pacc.sxy += (long long)eI * eJ, pacc.syy += (long long)eJ * eJ;
+            pacc.sxq += (long long)eI * eq, pacc.syq += (long long)eJ * eq;
+        }
+    }
+    OGG_DEV void finish(long long c, const ogg_topog_record& r, int lane) {
+        if constexpr (PLANE) {
+            const PAcc& a = pl.acc;
+            ogg_topog_plane_record p;   // the wavefront's moments; a lane's sums of offsets fit int32, the wavefront's need not
+            p.base = r;
+            p.sx = wave_sum((long long)a.sx), p.sy = wave_sum((long long)a.sy), p.n_far = wave_sum(a.nfar);
+            p.sxx = wave_sum(a.sxx), p.sxy = wave_sum(a.sxy), p.syy = wave_sum(a.syy);
+            p.sxq = wave_sum(a.sxq), p.syq = wave_sum(a.syq);
+            if (lane == 0) out[c] = p;
+        } else {
+            if (lane == 0) out[c] = r;
+        }
+    }
+};
+
+template <int DT, bool PLANE>
+__global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned long long* counter, void* records) {
+    SingleSampler<DT, PLANE> sm{s, static_cast<typename SingleSampler<DT, PLANE>::Record*>(records), {}};
+    if constexpr (PLANE) {
+        __shared__ Origin origin;
+        sm.pl.lds = &origin;
+    }
+    topog_walk(g, counter, sm);
+}
+
 // ---- layered topography (include/ogg_hip.h, "Layered topography") ------------------------------------------------------------
-// topog_layers_kernel: the walk of topog_band_kernel -- one wavefront per output cell, runs of cells from the counter, the S / U table,
-// lane-private integer accumulators, shuffle reductions -- with every sample offered to the layers in list order.  The layers are a
-// kernel argument, so their descriptors arrive in scalar registers; the kernel is instantiated per number of layers and the loop over
-// them is unrolled (no indexed copy of the argument, and a short list stays in registers), and kind and dtype are uniform over the
-// wavefront.  A projected layer costs a sample two sincos, one division and the two short
-// series of ogg_math.h; a sample that fails the gate costs one compare.  The refinement of a cell takes the layers' corner
-// projections: lane 16 c + 4 k + p projects corner p of supergrid cell c in layer k, so the up to 64 projections of an output cell
-// run side by side, and shuffles within the 16 lanes of a cell reduce them to its R.
 constexpr int NLAY = OGG_TOPOG_MAX_SOURCES;
 static_assert(NLAY == 4 && TT == 16 * NLAY, "one lane per (supergrid cell, layer, corner)");
 static_assert(sizeof(ogg_topog_merge_record) == 88, "ogg_topog_merge_record layout");
@@ -435,64 +488,9 @@ OGG_DEV bool layer_value(const Layer& L, int pole, double lon, double lat, int& 
         (!STEREO || L.kind == OGG_TOPOG_LATLON) ? latlon_index(L.s, pole, lon, lat, is, js) : stereo_index(L, pole, lon, lat, is, js);
     if (miss) return true;   // is, js of a missing sample mean nothing: nothing is read
     int v;
-    if (L.s.dtype == OGG_TOPOG_INT16) {
-        v = static_cast<const short*>(L.s.data)[(long)js * L.s.Nx + is];
-        if (v == L.s.fill0 || v == L.s.fill1) return true;
-    } else {
-        v = static_cast<const int*>(L.s.data)[(long)js * L.s.Nx + is];
-        if (v == OGG_TOPOG_MISSING_Q) return true;
-    }
+    if (raster_value(L.s, L.s.dtype, is, js, v)) return true;
     q = v * L.q_mul;   // |q| <= OGG_TOPOG_MAX_Q: ogg_topog_layer_range_dev
     return false;
-}
-
-struct LAcc {
-    Acc a;
-    int from[NLAY];
-};
-
-template <int NL, bool STEREO>
-OGG_DEV void sample_cell_layers(const Layers& ly, const Cell& c, const double* S, const double* U, int lane, LAcc& acc) {
-    const int R = c.R;
-    const int RR = R * R;
-    int f = lane;
-    if (f >= RR) return;
-    int a = f % R, b = f / R;
-    const int step_b = TT / R, step_a = TT % R;
-    const int wet_q = ly.l[0].s.wet_q;
-    for (; f < RR; f += TT) {
-        const double sa = S[a], ua = U[a];
-        double lon, lat = 0.0;   // the positions of sample_cell, operation for operation
-        if (c.pole == 0) {
-            const double tb = S[b], vb = U[b];
-            const double w00 = ua * vb, w01 = sa * vb, w10 = ua * tb, w11 = sa * tb;
-            lon = w00 * c.L00 + w01 * c.L01 + w10 * c.L10 + w11 * c.L11;
-            lat = w00 * c.y00 + w01 * c.y01 + w10 * c.y10 + w11 * c.y11;
-        } else {
-            lon = c.L00 + 360.0 * sa;
-        }
-        bool miss = true;
-        int q = 0;
-#pragma unroll
-        for (int k = 0; k < NL; ++k) {
-            if (miss) {
-                miss = layer_value<STEREO>(ly.l[k], c.pole, lon, lat, q);
-                acc.from[k] += miss ? 0 : 1;
-            }
-        }
-        if (!miss) {
-            acc.a.n += 1;
-            acc.a.nw += q < wet_q ? 1 : 0;
-            acc.a.sum += q;
-            acc.a.sumsq += (long long)q * q;
-            acc.a.mn = q < acc.a.mn ? q : acc.a.mn;
-            acc.a.mx = q > acc.a.mx ? q : acc.a.mx;
-        } else {
-            acc.a.nm += 1;
-        }
-        a += step_a, b += step_b;
-        if (a >= R) a -= R, b += 1;
-    }
 }
 
 // shuffles within aligned groups of W lanes (W = 4: the corners of one layer; W = 16: the layers of one supergrid cell)
@@ -506,12 +504,7 @@ OGG_DEV double group_max(double v) {
 // cl is the lane's supergrid cell (geometry only), lon and lat its corner (L, y)
 template <bool STEREO>
 OGG_DEV double layer_refine_value(const Layer& L, const Cell& cl, double lon, double lat, double oversample) {
-    if (!STEREO || L.kind == OGG_TOPOG_LATLON) {   // the expression of setup_cell
-        const double span_l = fmax(fmax(cl.L00, cl.L01), fmax(cl.L10, cl.L11)) - fmin(fmin(cl.L00, cl.L01), fmin(cl.L10, cl.L11));
-        const double span_y = fmax(fmax(cl.y00, cl.y01), fmax(cl.y10, cl.y11)) - fmin(fmin(cl.y00, cl.y01), fmin(cl.y10, cl.y11));
-        const double any = (cl.L00 + cl.L01) + (cl.L10 + cl.L11) + (cl.y00 + cl.y01) + (cl.y10 + cl.y11);
-        return any != any ? any : ceil(oversample * fmax(span_l / L.s.dlon, span_y / L.s.dlat));
-    }
+    if (!STEREO || L.kind == OGG_TOPOG_LATLON) return latlon_refine_value(cl, L.s.dlon, L.s.dlat, oversample);
     double X = 0.0, Y = 0.0;
     const bool counts = stereo_project(L, lon, lat, X, Y);
     const double fi = floor((X - L.s.lon0) * L.s.inv_dlon), fj = floor((Y - L.s.lat0) * L.s.inv_dlat);
@@ -526,90 +519,61 @@ OGG_DEV double layer_refine_value(const Layer& L, const Cell& cl, double lon, do
 // NL: the number of layers, so that a short list keeps its descriptors in scalar registers through the sample loop.  STEREO: whether
 // any layer is projected; a list of lat-lon layers alone carries none of the projection's code or registers
 template <int NL, bool STEREO>
-__global__ __launch_bounds__(TT) void topog_layers_kernel(Geo g, Layers ly, unsigned long long* counter, ogg_topog_merge_record* out) {
-    __shared__ double S[RMAX], U[RMAX];
-    __shared__ Cell cells[4];
-    __shared__ long long take;
-    const int lane = threadIdx.x;
-    int table_R = 0;
-    const int side = 1 << g.shift;
-    Geo g1 = g;   // setup_cell for the geometry alone: with refine = 1 it reads no source
-    g1.refine = 1;
-    for (;;) {
-        if (lane == 0) take = (long long)atomicAdd(counter, (unsigned long long)TR);
-        __syncthreads();
-        const long long c0 = take;
-        __syncthreads();
-        if (c0 >= g.total) break;
-        const long long c1 = c0 + TR < g.total ? c0 + TR : g.total;
-        for (long long c = c0; c < c1; ++c) {
-            const long m = g.m0 + (long)(c / g.nxo), io = (long)(c % g.nxo);
-            if (lane < side * side) {   // lane = 2 dj + di
-                const long j = (m << g.shift) + (lane >> 1), i = (io << g.shift) + (lane & 1);
-                Cell cl;
-                if (j >= g.j0 && j < g.j0 + g.n) {
-                    cl = setup_cell(g1, ly.l[0].s, j, i);
-                    cl.R = g.refine;
-                } else {
-                    cl.valid = 0, cl.R = 0, cl.pole = 0, cl.clamped = 0;
-                }
-                cells[lane] = cl;
-            }
-            __syncthreads();
-            if (g.refine <= 0) {   // R from the layers: lane = 16 cell + 4 layer + corner
-                const int ci = lane >> 4, k = (lane >> 2) & 3, p = lane & 3;
-                const Cell& cl = cells[ci < side * side ? ci : 0];
-                const bool live = ci < side * side && cl.valid;
-                const double lon = (&cl.L00)[p], lat = (&cl.y00)[p];   // L00, L01, L10, L11 and y00 .. y11 lie in this order
-                double v = 1.0;   // a layer that is not there asks for nothing
+struct LayerSampler {
+    const Layers& ly;
+    ogg_topog_merge_record* out;
+    int from[NLAY];   // the samples each layer gave this lane
+
+    OGG_DEV void lane_refine(const Geo&, Cell&) {}
+    OGG_DEV void stage(const Geo&, long, long, int) {}
+    OGG_DEV void begin(const Geo& g, Cell* cells, int side, int lane) {
+        if (g.refine <= 0) {   // R from the layers: lane = 16 cell + 4 layer + corner
+            const int ci = lane >> 4, k = (lane >> 2) & 3, p = lane & 3;
+            const Cell& cl = cells[ci < side * side ? ci : 0];
+            const bool live = ci < side * side && cl.valid;
+            const double lon = (&cl.L00)[p], lat = (&cl.y00)[p];   // L00, L01, L10, L11 and y00 .. y11 lie in this order
+            double v = 1.0;   // a layer that is not there asks for nothing
 #pragma unroll
-                for (int kk = 0; kk < NL; ++kk) {   // every lane takes part in the shuffles of every layer; it keeps its own layer's value
-                    const double vk = layer_refine_value<STEREO>(ly.l[kk], cl, lon, lat, g.oversample);
-                    v = kk == k ? vk : v;
-                }
-                const bool nan = group_max<16>(v != v ? 1.0 : 0.0) > 0.0;
-                const double vmax = group_max<16>(v != v ? 1.0 : v);
-                if (live && (lane & 15) == 0) {
-                    if (nan || !(vmax <= (double)RMAX)) {
-                        cells[ci].R = RMAX, cells[ci].clamped = 1;
-                    } else {
-                        cells[ci].R = vmax < 1.0 ? 1 : (int)vmax;
-                    }
-                }
-                __syncthreads();
+            for (int kk = 0; kk < NL; ++kk) {   // every lane takes part in the shuffles of every layer; it keeps its own layer's value
+                const double vk = layer_refine_value<STEREO>(ly.l[kk], cl, lon, lat, g.oversample);
+                v = kk == k ? vk : v;
             }
-            LAcc acc{{0, 0, 0, INT_MAX, INT_MIN, 0, 0}, {0, 0, 0, 0}};
-            int Rmax = 0, n_pole = 0, n_clamped = 0;
-            for (int k = 0; k < side * side; ++k) {
-                const Cell cl = cells[k];
-                if (!cl.valid) continue;
-                Rmax = cl.R > Rmax ? cl.R : Rmax;
-                n_pole += cl.pole != 0;
-                n_clamped += cl.clamped;
-                if (cl.R != table_R) {   // s = (a + 0.5) / R and 1 - s for this R
-                    __syncthreads();
-                    for (int a = lane; a < cl.R; a += TT) {
-                        const double sv = ((double)a + 0.5) / (double)cl.R;
-                        S[a] = sv, U[a] = 1.0 - sv;
-                    }
-                    __syncthreads();
-                    table_R = cl.R;
-                }
-                sample_cell_layers<NL, STEREO>(ly, cl, S, U, lane, acc);
+            const bool nan = group_max<16>(v != v ? 1.0 : 0.0) > 0.0;   // fmax drops a NaN, so it is carried apart
+            const double vmax = group_max<16>(v != v ? 1.0 : v);
+            if (live && (lane & 15) == 0) set_refine(cells[ci], nan ? (double)NAN : vmax);
+            __syncthreads();
+        }
+        for (int k = 0; k < NLAY; ++k) from[k] = 0;
+    }
+    OGG_DEV void sample(const Cell& c, double lon, double lat, Acc& acc) {
+        bool miss = true;
+        int q = 0;
+#pragma unroll
+        for (int k = 0; k < NL; ++k) {
+            if (miss) {
+                miss = layer_value<STEREO>(ly.l[k], c.pole, lon, lat, q);
+                from[k] += miss ? 0 : 1;
             }
-            ogg_topog_record r;
-            r.n = wave_sum(acc.a.n), r.n_missing = wave_sum(acc.a.nm), r.n_wet = wave_sum(acc.a.nw);
-            r.sum = wave_sum(acc.a.sum), r.sumsq = wave_sum(acc.a.sumsq);
-            r.min = wave_min(acc.a.mn), r.max = wave_max(acc.a.mx);
-            r.R = Rmax, r.n_pole = (short)n_pole, r.n_clamped = (short)n_clamped;
-            const int f0 = wave_sum(acc.from[0]), f1 = wave_sum(acc.from[1]), f2 = wave_sum(acc.from[2]), f3 = wave_sum(acc.from[3]);
-            if (lane == 0) {
-                out[c].base = r;
-                out[c].n_from[0] = f0, out[c].n_from[1] = f1, out[c].n_from[2] = f2, out[c].n_from[3] = f3;
-            }
-            __syncthreads();   // cells[] is rewritten for the next output cell
+        }
+        if (!miss) {
+            count_valid(acc, q, ly.l[0].s.wet_q);
+        } else {
+            count_missing(acc);
         }
     }
+    OGG_DEV void finish(long long c, const ogg_topog_record& r, int lane) {
+        const int f0 = wave_sum(from[0]), f1 = wave_sum(from[1]), f2 = wave_sum(from[2]), f3 = wave_sum(from[3]);
+        if (lane == 0) {
+            out[c].base = r;
+            out[c].n_from[0] = f0, out[c].n_from[1] = f1, out[c].n_from[2] = f2, out[c].n_from[3] = f3;
+        }
+    }
+};
+
+template <int NL, bool STEREO>
+__global__ __launch_bounds__(TT) void topog_layers_kernel(Geo g, Layers ly, unsigned long long* counter, ogg_topog_merge_record* out) {
+    LayerSampler<NL, STEREO> sm{ly, out, {}};
+    topog_walk(g, counter, sm);
 }
 
 // |q_mul * q| <= OGG_TOPOG_MAX_Q of every stored value (DT: INT16 with its fills, INT32 with OGG_TOPOG_MISSING_Q)
@@ -703,6 +667,43 @@ long out_rows(const ogg_topog_band& b) {
     return ((b.j0 + b.n_cell_rows - 1) >> sh) - (b.j0 >> sh) + 1;
 }
 
+Geo make_geo(const ogg_topog_band& b) {
+    const int shift = b.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0;
+    Geo g{b.x, b.y, b.x_next, b.y_next, b.nx, b.nx + 1, b.j0, b.n_cell_rows, b.j0 >> shift, b.nx >> shift, 0, shift, b.refine,
+          b.oversample};
+    g.total = out_rows(b) * g.nxo;
+    return g;
+}
+
+// what a launch of the walk needs first: the counter at the head of the workspace cleared, and the number of persistent workgroups
+int walk_launch(const Geo& g, void* workspace, hipStream_t st, unsigned long long** counter, unsigned* wgs) {
+    OGG_HIP_CHECK(hipMemsetAsync(workspace, 0, sizeof(unsigned long long), st));
+    int dev = 0, n_cu = 0;
+    OGG_HIP_CHECK(hipGetDevice(&dev));
+    OGG_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    const long takes = (g.total + TR - 1) / TR;
+    *wgs = (unsigned)std::min(takes, (long)(n_cu > 0 ? n_cu : 256) * 32);   // 32 one-wave workgroups per CU, persistent
+    *counter = static_cast<unsigned long long*>(workspace);
+    return OGG_OK;
+}
+
+// HOST band h as device band d: its grid rows, and the row that follows them, copied to device memory
+int stage_band(ogg::Buffers& bufs, const ogg_topog_band& h, ogg_topog_band* d) {
+    const long nxp = h.nx + 1, n = h.n_cell_rows;
+    *d = h;
+    double *px, *py;
+    if (int e = bufs.alloc(&px, (size_t)(n + 1) * nxp)) return e;
+    if (int e = bufs.alloc(&py, (size_t)(n + 1) * nxp)) return e;
+    const size_t body = (size_t)n * nxp, row = (size_t)nxp;   // doubles
+    if (int e = bufs.send(px, h.x, body)) return e;
+    if (int e = bufs.send(py, h.y, body)) return e;
+    if (int e = bufs.send(px + body, h.x_next ? h.x_next : h.x + n * nxp, row)) return e;
+    if (int e = bufs.send(py + body, h.y_next ? h.y_next : h.y + n * nxp, row)) return e;
+    d->x = px, d->y = py;
+    d->x_next = d->x + n * nxp, d->y_next = d->y + n * nxp;
+    return OGG_OK;
+}
+
 }  // namespace
 
 extern "C" long ogg_topog_workspace_bytes(void) { return 256; }
@@ -726,29 +727,22 @@ int band_dev(const ogg_topog_band* band, const ogg_topog_source* src, void* work
     OGG_REQUIRE(b.x && b.y && b.x_next && b.y_next && out, OGG_EARG, "ogg_topog_band: null x / y / x_next / y_next / out");
     if (int e = ogg::check_workspace("ogg_topog_band", workspace, workspace_bytes, ogg_topog_workspace_bytes())) return e;
     const ogg_topog_source& q = *src;
-    const int shift = b.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0;
-    Geo g{b.x, b.y, b.x_next, b.y_next, b.nx, b.nx + 1, b.j0, b.n_cell_rows, b.j0 >> shift, b.nx >> shift, 0, shift, b.refine,
-          b.oversample};
-    g.total = rows * g.nxo;
+    const Geo g = make_geo(b);
     const Src s = make_src(q);
     hipStream_t st = ogg::as_stream(stream);
-    OGG_HIP_CHECK(hipMemsetAsync(workspace, 0, sizeof(unsigned long long), st));
-    int dev = 0, n_cu = 0;
-    OGG_HIP_CHECK(hipGetDevice(&dev));
-    OGG_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    const long takes = (g.total + TR - 1) / TR;
-    const long wgs = std::min(takes, (long)(n_cu > 0 ? n_cu : 256) * 32);   // 32 one-wave workgroups per CU, persistent
-    auto* counter = static_cast<unsigned long long*>(workspace);
+    unsigned long long* counter;
+    unsigned wgs;
+    if (int e = walk_launch(g, workspace, st, &counter, &wgs)) return e;
     if (plane) {
         if (q.dtype == OGG_TOPOG_INT16)
-            topog_band_kernel<OGG_TOPOG_INT16, true><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+            topog_band_kernel<OGG_TOPOG_INT16, true><<<wgs, TT, 0, st>>>(g, s, counter, out);
         else
-            topog_band_kernel<OGG_TOPOG_INT32, true><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+            topog_band_kernel<OGG_TOPOG_INT32, true><<<wgs, TT, 0, st>>>(g, s, counter, out);
     } else {
         if (q.dtype == OGG_TOPOG_INT16)
-            topog_band_kernel<OGG_TOPOG_INT16, false><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+            topog_band_kernel<OGG_TOPOG_INT16, false><<<wgs, TT, 0, st>>>(g, s, counter, out);
         else
-            topog_band_kernel<OGG_TOPOG_INT32, false><<<(unsigned)wgs, TT, 0, st>>>(g, s, counter, out);
+            topog_band_kernel<OGG_TOPOG_INT32, false><<<wgs, TT, 0, st>>>(g, s, counter, out);
     }
     OGG_LAUNCH_CHECK();
     return OGG_OK;
@@ -788,6 +782,26 @@ extern "C" int ogg_topog_quantize_dev(const ogg_topog_source* src, int* q, int* 
 
 namespace {
 
+// HOST raster of *s as a device one that the walk samples: copied to device memory, a float one quantised there (the descriptor is
+// then int32 without fills).  *n_bad != 0: a quantised value exceeds OGG_TOPOG_MAX_Q, and the caller says so in its own words
+int stage_raster(ogg::Buffers& bufs, ogg_topog_source* s, int* n_bad) {
+    const long nsrc = s->Nx * s->Ny;
+    const size_t esize = s->dtype == OGG_TOPOG_INT16 ? 2 : (s->dtype == OGG_TOPOG_FLOAT64 ? 8 : 4);
+    char* raw;
+    if (int e = bufs.put(&raw, static_cast<const char*>(s->data), (size_t)nsrc * esize)) return e;
+    s->data = raw;
+    *n_bad = 0;
+    if (s->dtype == OGG_TOPOG_FLOAT32 || s->dtype == OGG_TOPOG_FLOAT64) {
+        int *qd, *bad;
+        if (int e = bufs.alloc(&qd, (size_t)nsrc)) return e;
+        if (int e = bufs.alloc(&bad, 1)) return e;
+        if (int e = ogg_topog_quantize_dev(s, qd, bad, nullptr)) return e;
+        if (int e = bufs.get(n_bad, bad, 1)) return e;
+        s->data = qd, s->dtype = OGG_TOPOG_INT32, s->n_fill = 0;
+    }
+    return OGG_OK;
+}
+
 // the host-pointer forms: grid rows and raster copied to device memory, one band, the records (plane records when ``plane``) copied
 // back (synchronous)
 int topog_host(const ogg_topog_band* band, const ogg_topog_source* src, void* out, bool plane) {
@@ -799,36 +813,13 @@ int topog_host(const ogg_topog_band* band, const ogg_topog_source* src, void* ou
     const long rows = out_rows(h);
     if (rows == 0) return OGG_OK;
     ogg::Buffers bufs;   // freed on every exit path
-    const long nxp = h.nx + 1, n = h.n_cell_rows;
-    ogg_topog_band d = h;
-    double *px, *py;
-    if (int e = bufs.alloc(&px, (size_t)(n + 1) * nxp)) return e;
-    if (int e = bufs.alloc(&py, (size_t)(n + 1) * nxp)) return e;
-    const size_t body = (size_t)n * nxp, row = (size_t)nxp;   // doubles
-    if (int e = bufs.send(px, h.x, body)) return e;
-    if (int e = bufs.send(py, h.y, body)) return e;
-    if (int e = bufs.send(px + body, h.x_next ? h.x_next : h.x + n * nxp, row)) return e;
-    if (int e = bufs.send(py + body, h.y_next ? h.y_next : h.y + n * nxp, row)) return e;
-    d.x = px, d.y = py;
-    d.x_next = d.x + n * nxp, d.y_next = d.y + n * nxp;
-    const ogg_topog_source& hs = *src;
-    ogg_topog_source ds = hs;
-    const long nsrc = hs.Nx * hs.Ny;
-    const size_t esize = hs.dtype == OGG_TOPOG_INT16 ? 2 : (hs.dtype == OGG_TOPOG_FLOAT64 ? 8 : 4);
-    char* raw;
-    if (int e = bufs.put(&raw, static_cast<const char*>(hs.data), (size_t)nsrc * esize)) return e;
-    ds.data = raw;
-    if (hs.dtype == OGG_TOPOG_FLOAT32 || hs.dtype == OGG_TOPOG_FLOAT64) {
-        int *qd, *bad;
-        if (int e = bufs.alloc(&qd, (size_t)nsrc)) return e;
-        if (int e = bufs.alloc(&bad, 1)) return e;
-        if (int e = ogg_topog_quantize_dev(&ds, qd, bad, nullptr)) return e;
-        int nb = 0;
-        if (int e = bufs.get(&nb, bad, 1)) return e;
-        OGG_REQUIRE(nb == 0, OGG_EARG, "ogg_topog: a quantised source value exceeds %d in magnitude (quantum %g too small)", OGG_TOPOG_MAX_Q,
-                    hs.quantum);
-        ds.data = qd, ds.dtype = OGG_TOPOG_INT32, ds.n_fill = 0;
-    }
+    ogg_topog_band d;
+    if (int e = stage_band(bufs, h, &d)) return e;
+    ogg_topog_source ds = *src;
+    int nb = 0;
+    if (int e = stage_raster(bufs, &ds, &nb)) return e;
+    OGG_REQUIRE(nb == 0, OGG_EARG, "ogg_topog: a quantised source value exceeds %d in magnitude (quantum %g too small)", OGG_TOPOG_MAX_Q,
+                ds.quantum);
     const long nrec = rows * (h.nx >> (h.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0));
     char *ws, *res;
     if (int e = bufs.alloc(&ws, (size_t)ogg_topog_workspace_bytes())) return e;
@@ -908,24 +899,16 @@ extern "C" int ogg_topog_layers_band_dev(const ogg_topog_band* band, int n_layer
     if (rows == 0) return OGG_OK;
     OGG_REQUIRE(b.x && b.y && b.x_next && b.y_next && out, OGG_EARG, "ogg_topog_layers: null x / y / x_next / y_next / out");
     if (int e = ogg::check_workspace("ogg_topog_layers", workspace, workspace_bytes, ogg_topog_workspace_bytes())) return e;
-    const int shift = b.cells == OGG_TOPOG_MODEL_CELLS ? 1 : 0;
-    Geo g{b.x, b.y, b.x_next, b.y_next, b.nx, b.nx + 1, b.j0, b.n_cell_rows, b.j0 >> shift, b.nx >> shift, 0, shift, b.refine,
-          b.oversample};
-    g.total = rows * g.nxo;
+    const Geo g = make_geo(b);
     Layers ly;
     ly.n = n_layers;
     for (int k = 0; k < NLAY; ++k) ly.l[k] = make_layer(layers[k < n_layers ? k : 0]);   // the slots past n are never read
     hipStream_t st = ogg::as_stream(stream);
-    OGG_HIP_CHECK(hipMemsetAsync(workspace, 0, sizeof(unsigned long long), st));
-    int dev = 0, n_cu = 0;
-    OGG_HIP_CHECK(hipGetDevice(&dev));
-    OGG_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    const long takes = (g.total + TR - 1) / TR;
-    const long wgs = std::min(takes, (long)(n_cu > 0 ? n_cu : 256) * 32);   // as ogg_topog_band_dev
-    auto* counter = static_cast<unsigned long long*>(workspace);
+    unsigned long long* counter;
+    unsigned nwg;
+    if (int e = walk_launch(g, workspace, st, &counter, &nwg)) return e;
     bool stereo = false;
     for (int k = 0; k < n_layers; ++k) stereo = stereo || layers[k].kind == OGG_TOPOG_POLAR_STEREO;
-    const unsigned nwg = (unsigned)wgs;
 #define OGG_LAYERS_LAUNCH(NL)                                                              \
     if (stereo)                                                                            \
         topog_layers_kernel<NL, true><<<nwg, TT, 0, st>>>(g, ly, counter, out);            \
@@ -985,39 +968,17 @@ extern "C" int ogg_topog_layers(const ogg_topog_band* band, int n_layers, const 
     const long rows = out_rows(h);
     if (rows == 0) return OGG_OK;
     ogg::Buffers bufs;   // freed on every exit path
-    const long nxp = h.nx + 1, n = h.n_cell_rows;
-    ogg_topog_band d = h;
-    double *px, *py;
-    if (int e = bufs.alloc(&px, (size_t)(n + 1) * nxp)) return e;
-    if (int e = bufs.alloc(&py, (size_t)(n + 1) * nxp)) return e;
-    const size_t body = (size_t)n * nxp, row = (size_t)nxp;   // doubles
-    if (int e = bufs.send(px, h.x, body)) return e;
-    if (int e = bufs.send(py, h.y, body)) return e;
-    if (int e = bufs.send(px + body, h.x_next ? h.x_next : h.x + n * nxp, row)) return e;
-    if (int e = bufs.send(py + body, h.y_next ? h.y_next : h.y + n * nxp, row)) return e;
-    d.x = px, d.y = py;
-    d.x_next = d.x + n * nxp, d.y_next = d.y + n * nxp;
+    ogg_topog_band d;
+    if (int e = stage_band(bufs, h, &d)) return e;
     ogg_topog_layer dl[OGG_TOPOG_MAX_SOURCES];
     int* bad;
     if (int e = bufs.alloc(&bad, 1)) return e;
     for (int k = 0; k < n_layers; ++k) {
         dl[k] = layers[k];
-        ogg_topog_source& ds = dl[k].src;
-        const long nsrc = ds.Nx * ds.Ny;
-        const size_t esize = ds.dtype == OGG_TOPOG_INT16 ? 2 : (ds.dtype == OGG_TOPOG_FLOAT64 ? 8 : 4);
-        char* raw;
-        if (int e = bufs.put(&raw, static_cast<const char*>(ds.data), (size_t)nsrc * esize)) return e;
-        ds.data = raw;
         int nb = 0;
-        if (ds.dtype == OGG_TOPOG_FLOAT32 || ds.dtype == OGG_TOPOG_FLOAT64) {
-            int* qd;
-            if (int e = bufs.alloc(&qd, (size_t)nsrc)) return e;
-            if (int e = ogg_topog_quantize_dev(&ds, qd, bad, nullptr)) return e;
-            if (int e = bufs.get(&nb, bad, 1)) return e;
-            OGG_REQUIRE(nb == 0, OGG_EARG, "ogg_topog_layers: layer %d: a quantised value exceeds %d in magnitude (quantum %g too small)", k,
-                        OGG_TOPOG_MAX_Q, ds.quantum);
-            ds.data = qd, ds.dtype = OGG_TOPOG_INT32, ds.n_fill = 0;
-        }
+        if (int e = stage_raster(bufs, &dl[k].src, &nb)) return e;
+        OGG_REQUIRE(nb == 0, OGG_EARG, "ogg_topog_layers: layer %d: a quantised value exceeds %d in magnitude (quantum %g too small)", k,
+                    OGG_TOPOG_MAX_Q, dl[k].src.quantum);
         if (int e = ogg_topog_layer_range_dev(&dl[k], bad, nullptr)) return e;
         if (int e = bufs.get(&nb, bad, 1)) return e;
         OGG_REQUIRE(nb == 0, OGG_EARG, "ogg_topog_layers: layer %d: q_mul = %d times a stored value exceeds %d in magnitude", k, dl[k].q_mul,
