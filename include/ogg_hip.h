@@ -88,7 +88,9 @@ const char* ogg_version(void);
 #define OGG_ABI_TOPOG_PROJECTION 35
 #define OGG_ABI_TOPOG_LAYER 36
 #define OGG_ABI_TOPOG_MERGE_RECORD 37
-#define OGG_ABI_N 38
+#define OGG_ABI_XGRID_CURV_SRC 38
+#define OGG_ABI_XGRID_CURV_COUNTS 39
+#define OGG_ABI_N 40
 long ogg_abi_sizeof(int which);
 int ogg_device_count(int* count);
 int ogg_set_device(int device);
@@ -908,6 +910,87 @@ int ogg_xgrid_cs_write_dev(const ogg_xgrid_band* band, const ogg_xgrid_cs_atm* a
  * filled when counts->kept > capacity: call again with that capacity). */
 int ogg_xgrid_cs(const ogg_xgrid_band* band, const ogg_xgrid_cs_atm* atm, long capacity, int* atm_fij, int* ocn_ij, double* area,
                  double* a_poly, ogg_xgrid_cs_counts* counts);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Exchange grid with a curvilinear source grid (an addition: the reference has none).  First-order conservative overlaps of the cells
+ * of any logically rectangular mesh on the sphere (another model's tripolar grid, a sea-ice or land mosaic, a regional parent, a
+ * rotated-pole reanalysis) with the MOM6 h-cells of the STITCHED supergrid (an ogg_xgrid_band, as above): the list that
+ * ogg_remap_dev consumes, with (I, J) of the source cell in the place of the atmosphere's.  All arithmetic is fp64 without fused
+ * multiply-add, every product rounded before it is added.
+ * Target cell (m, n): corners C0 .. C3 as above.
+ * Source: sx, sy in degrees, (NB + 1) x (NA + 1) cell corners of row stride ld >= NA + 1, NA * NB < 2^31 and NA * NB *
+ * OGG_LOCATE_MAX_TOUCH < 2^31.  Source cell (J, I) has the corners (J, I), (J, I+1), (J+1, I+1), (J+1, I), and its list index is
+ * q = J * NA + I.  An optional byte per source cell masks it: a masked source cell (0) emits nothing.
+ *   vectors   of both grids by the cubed-sphere section's rule: mod360, then the unit vector (a mesh stated whole turns away gives
+ *             the same bits); no pole substitution.  Edges are great circles.
+ *   target    DEGENERATE, WIDE (OGG_XGRID_CS_COS_WIDE) and INVERTED word for word as in the cubed-sphere section; A_poly is that
+ *             section's O3 fan, (Re * Re) * (O3(P0, P1, P2) + O3(P0, P2, P3)).  Only cells with A_poly > 0 are valid.
+ *   source    DEGENERATE and WIDE as for the target; A_src the same O3 fan over the cell's corners Q0 .. Q3.  A_src < 0: the cell is
+ *             REVERSED, its corners are taken in the order 0, 3, 2, 1 and A_src is formed again in that order (a mesh stored north
+ *             to south works).  A_src not > 0 after that (0, or not finite): the cell is FLAT and emits nothing.  A_src is NaN for
+ *             DEGENERATE and WIDE cells.  The other cells are valid.
+ *   normals   n_e = n(a, b) of "Point location" for the edges S = (Q0, Q1), E = (Q1, Q2), N = (Q2, Q3), W = (Q3, Q0) of the oriented
+ *             source cell, and the measure T(p; a, b) of that section, formula and rounding order.  The region of a source cell is
+ *             the intersection of its four half-spaces T >= 0: for a convex cell, the cell.  A collapsed edge has a zero normal
+ *             and clips nothing.  (The region of a non-convex cell is smaller than the cell; of a bow-tie, one lobe or nothing.)
+ *   shared    T(a; a, b) and T(b; a, b) are 0 in exact arithmetic but a rounding-sized number of either sign as computed, and an
+ *   corners   end that comes out negative would be cut off with a sliver of the cell (1e-12 of a half-degree cell).  So the measure
+ *             d(v; e) of a vertex v against edge e = (Q_a, Q_b) is exactly 0 when the three components of v equal those of Q_a or of
+ *             Q_b, and T(v; Q_a, Q_b) otherwise.  A mesh laid over itself, or over a mesh that shares its corners, then gives each
+ *             cell whole: a cell that holds a target cell's four corners gives A_poly bit for bit.
+ *   box       every valid cell of either grid has the padded box of "Point location": the component-wise min and max of its corner
+ *             vectors, minus and plus 0.25 * L2 + 2^-40.  A pair is a CANDIDATE when both cells are valid and unmasked and the two
+ *             boxes intersect, closed intervals on all three axes.  The box is part of the definition, so no index changes a bit.
+ *   clip      Sutherland-Hodgman of the target polygon P0 .. P3 against the half-spaces of S, E, N, W in this order, inclusive inside
+ *             tests (T >= 0), the emission rule of the lat-lon section: a pass emits its first vertex when inside, then per edge the
+ *             crossing and then the end, and for the closing edge its crossing only.  The crossing of (v_k, v_k+1) with the measures
+ *             d: order the ends as (e, f) lexicographically by (x, y, z); t = d_e / (d_e - d_f); w = e + t * (f - e) by component;
+ *             the crossing is w / sqrt((w_x w_x + w_y w_y) + w_z w_z).  The result has at most 8 vertices.
+ *   A_x       all sixteen measures of the target's corners >= 0: A_x = A_poly.  Otherwise (Re * Re) times the O3 fan from vertex 0
+ *             of the clipped polygon, sum_k=1..n-2 O3(v_0, v_k, v_k+1) left to right from 0; 0 with fewer than 3 vertices.
+ *   keep      A_x > 0 and A_x > threshold * min(A_poly, A_src)
+ * Order: target cells row-major (m, n), then q ascending.  Nothing is summed across pairs, so the list is bit-identical for any band
+ * split, any index (OGG_XGRID_CURV_CUBES: cubes per axis of the index over the source cells, 0: from their number;
+ * OGG_XGRID_CURV_BRUTE=1: every valid source cell is tested against every target cell) and any launch geometry.
+ * Counts: cells, degenerate, wide, inverted (they ignore the mask) and masked over the band's model cells; src_cells, src_degenerate,
+ * src_wide, src_reversed, src_flat (they ignore the source mask), src_masked and src_large (valid unmasked source cells on the index's
+ * large-cells list; every one of them with the brute knob) over the whole source, in every band's call; candidates and kept.
+ * Out of scope: source cells wider than 30 degrees (they are WIDE), second-order weights, the reverse direction.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct ogg_xgrid_curv_src {
+    const double *x, *y;       /* (NB + 1) rows of ld doubles: the corners in degrees */
+    long NA, NB, ld;
+    const unsigned char* mask; /* NULL, or one byte per source cell (NB x NA) */
+} ogg_xgrid_curv_src;
+typedef struct ogg_xgrid_curv_counts {
+    long long cells, degenerate, wide, inverted, masked;
+    long long src_cells, src_degenerate, src_wide, src_reversed, src_flat, src_masked, src_large;
+    long long candidates, kept;
+} ogg_xgrid_curv_counts;
+/* the checks of the source's shape (no pointer is read): OGG_EARG unless it is as above */
+int ogg_xgrid_curv_check(const ogg_xgrid_curv_src* src);
+/* candidates < 0: the bytes of the sets workspace of a band and a source; candidates >= 0: the bytes of the pair workspace of a list of
+ * that many candidates.  -1 on a bad band or source, or with 2^31 candidates or more. */
+long ogg_xgrid_curv_workspace_bytes(const ogg_xgrid_band* band, const ogg_xgrid_curv_src* src, long candidates);
+/* sets step, device pointers, on a stream: the source cells' records and A_src (a_src, NB x NA doubles), their index, the band's
+ * cells' records and A_poly (a_poly, (m1 - m0) x nx / 2 doubles), and the candidates of every model cell counted; every count but
+ * kept into *counts (device memory).  counts->candidates sizes the pair workspace. */
+int ogg_xgrid_curv_sets_dev(const ogg_xgrid_band* band, const ogg_xgrid_curv_src* src, void* workspace, long workspace_bytes,
+                            double* a_poly, double* a_src, ogg_xgrid_curv_counts* counts, void* stream);
+/* clip step, after the sets step on the same band, source and workspace, with candidates = counts->candidates: the candidates as
+ * sorted keys (target cell << 32) | q, A_x of every one and the kept pairs counted, into the pair workspace; counts->kept (the
+ * length of the band's list) into *counts */
+int ogg_xgrid_curv_clip_dev(const ogg_xgrid_band* band, const ogg_xgrid_curv_src* src, const void* workspace, long workspace_bytes,
+                            long candidates, void* pair_workspace, long pair_workspace_bytes, ogg_xgrid_curv_counts* counts,
+                            void* stream);
+/* write step, after the clip step on the same pair workspace: the list (counts->kept entries, device memory): src_ij[k] = (I, J),
+ * ocn_ij[k] = (n, m) (0-based, m counted in the whole grid), area[k] = A_x */
+int ogg_xgrid_curv_write_dev(const ogg_xgrid_band* band, const ogg_xgrid_curv_src* src, long candidates, const void* pair_workspace,
+                             long pair_workspace_bytes, int* src_ij, int* ocn_ij, double* area, void* stream);
+/* HOST pointers throughout, staged through device memory, with the capacity protocol of ogg_xgrid (OGG_ESHAPE with *counts, a_poly and
+ * a_src filled when counts->kept > capacity: call again with that capacity). */
+int ogg_xgrid_curv(const ogg_xgrid_band* band, const ogg_xgrid_curv_src* src, long capacity, int* src_ij, int* ocn_ij, double* area,
+                   double* a_poly, double* a_src, ogg_xgrid_curv_counts* counts);
 
 /* ------------------------------------------------------------------------------------------------------
  * Ocean mask: minimum depth and connected basins (an addition: the reference has none; GFDL's preprocessing calls this step "ice9").

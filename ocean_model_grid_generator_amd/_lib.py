@@ -150,6 +150,20 @@ class XgridCsCounts(ctypes.Structure):
     _fields_ = [(f, c_longlong) for f in XGRID_CS_COUNT_FIELDS]
 
 
+class XgridCurvSrc(ctypes.Structure):
+    """ogg_xgrid_curv_src of include/ogg_hip.h"""
+    _fields_ = [("x", c_void_p), ("y", c_void_p), ("NA", c_long), ("NB", c_long), ("ld", c_long), ("mask", c_void_p)]
+
+
+XGRID_CURV_COUNT_FIELDS = ("cells", "degenerate", "wide", "inverted", "masked", "src_cells", "src_degenerate", "src_wide", "src_reversed",
+                           "src_flat", "src_masked", "src_large", "candidates", "kept")
+
+
+class XgridCurvCounts(ctypes.Structure):
+    """ogg_xgrid_curv_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in XGRID_CURV_COUNT_FIELDS]
+
+
 class MaskParams(ctypes.Structure):
     """ogg_mask_params of include/ogg_hip.h"""
     _fields_ = [("ny", c_long), ("nx", c_long), ("topology", c_int), ("mode", c_int), ("fill", c_double), ("min_depth", c_double),
@@ -316,7 +330,8 @@ ABI_MIRRORS = {"LATLON_BAND": LatlonBand, "BIPOLAR_BAND": BipolarBand, "DPOLE_BA
                "BASIN_PARAMS": BasinParams, "BASIN_RULE": BASIN_RULE, "BASIN_RULE_RECORD": BASIN_RECORD, "BASIN_COUNTS": BasinCounts,
                "XGRID_CS_ATM": XgridCsAtm, "XGRID_CS_COUNTS": XgridCsCounts, "LAYOUT_PARAMS": LayoutParams, "LAYOUT_CANDIDATE": LAYOUT_CANDIDATE,
                "LAYOUT_RECORD": LAYOUT_RECORD, "LOCATE_PARAMS": LocateParams, "LOCATE_COUNTS": LocateCounts, "TOPOG_PROJECTION": TopogProjection,
-               "TOPOG_LAYER": TopogLayer, "TOPOG_MERGE_RECORD": TOPOG_MERGE_RECORD}
+               "TOPOG_LAYER": TopogLayer, "TOPOG_MERGE_RECORD": TOPOG_MERGE_RECORD, "XGRID_CURV_SRC": XgridCurvSrc,
+               "XGRID_CURV_COUNTS": XgridCurvCounts}
 ABI = {name: code for code, name in enumerate(ABI_MIRRORS)}
 
 
@@ -429,6 +444,15 @@ SIGNATURES = {
                                c_void_p],
     "ogg_xgrid_cs": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCsAtm), c_long, c_void_p, c_void_p, c_void_p, c_void_p,
                      ctypes.POINTER(XgridCsCounts)],
+    "ogg_xgrid_curv_check": [ctypes.POINTER(XgridCurvSrc)],
+    "ogg_xgrid_curv_sets_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCurvSrc), c_void_p, c_long, c_void_p, c_void_p, c_void_p,
+                                c_void_p],
+    "ogg_xgrid_curv_clip_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCurvSrc), c_void_p, c_long, c_long, c_void_p, c_long,
+                                c_void_p, c_void_p],
+    "ogg_xgrid_curv_write_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCurvSrc), c_long, c_void_p, c_long, c_void_p, c_void_p,
+                                 c_void_p, c_void_p],
+    "ogg_xgrid_curv": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCurvSrc), c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                       ctypes.POINTER(XgridCurvCounts)],
     "ogg_mask_check": [ctypes.POINTER(MaskParams)],
     "ogg_mask_label_dev": [ctypes.POINTER(MaskParams), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_mask_seed_dev": [ctypes.POINTER(MaskParams), c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p],
@@ -523,6 +547,7 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_xgrid_band_next_rows": [ctypes.POINTER(XgridBand)],
                 "ogg_xgrid_workspace_bytes": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm)],
                 "ogg_xgrid_cs_workspace_bytes": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCsAtm)],
+                "ogg_xgrid_curv_workspace_bytes": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridCurvSrc), c_long],
                 "ogg_mask_workspace_bytes": [ctypes.POINTER(MaskParams)],
                 "ogg_remap_workspace_bytes": [ctypes.POINTER(RemapParams)],
                 "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],

@@ -236,6 +236,8 @@ long ogg_abi_sizeof(int which) {
         case OGG_ABI_TOPOG_PROJECTION: return (long)sizeof(ogg_topog_projection);
         case OGG_ABI_TOPOG_LAYER: return (long)sizeof(ogg_topog_layer);
         case OGG_ABI_TOPOG_MERGE_RECORD: return (long)sizeof(ogg_topog_merge_record);
+        case OGG_ABI_XGRID_CURV_SRC: return (long)sizeof(ogg_xgrid_curv_src);
+        case OGG_ABI_XGRID_CURV_COUNTS: return (long)sizeof(ogg_xgrid_curv_counts);
         default: return -1L;
     }
 }

@@ -5,7 +5,7 @@
 //           the four edge normals (T(p; sigma n) = sigma T(p; n) up to the sign of an exact zero, so the search needs no sigma; the
 //           winner's m is formed again as sigma T(p; n) at the end) and the padded box.  A cell
 //           that holds no point (O zero or not finite) gets an empty box and is never registered.
-// index     the cube grid of ogg_sphere_bins.h: every cell registered in every cube its box touches, by count -> exclusive_scan ->
+// index     the cube grid of ogg_box_index.h (shared with the curvilinear exchange grid): every cell registered in every cube its box touches, by count -> exclusive_scan ->
 //           fill (ogg_blocks.h); a cell that touches more than OGG_LOCATE_MAX_TOUCH cubes goes on the large-cells list, which every
 //           query tests.  p in a cell's box implies cube_of(lo) <= cube_of(p) <= cube_of(hi) on every axis (cube_of is monotone), so
 //           the cube of p together with the large list holds every candidate of p: the search equals the brute-force argmax.
@@ -22,6 +22,7 @@
 #include <cstring>
 
 #include "ogg_blocks.h"
+#include "ogg_box_index.h"
 #include "ogg_cells.h"
 #include "ogg_common.h"
 #include "ogg_sphere_bins.h"
@@ -36,23 +37,16 @@ using ogg::knob;
 
 constexpr int NT = 256;                 // threads per workgroup (four wavefronts)
 constexpr int CH = 128;                 // cell records of one LDS chunk
-constexpr int NF = 18;                  // doubles of a cell record: sigma n_S, sigma n_E, sigma n_N, sigma n_W, box lo, box hi
-constexpr long HEAD = 256;
-constexpr long NBMAX = (long)OGG_LOCATE_MAX_CUBES * OGG_LOCATE_MAX_CUBES * OGG_LOCATE_MAX_CUBES;
+constexpr int NF = BOX_NF;              // doubles of a cell record: sigma n_S, sigma n_E, sigma n_N, sigma n_W, box lo, box hi
+constexpr long HEAD = BOX_HEAD;
+constexpr long NBMAX = BOX_NBMAX;
 constexpr long long MAGIC = 0x6c6f63617465ll;   // the head of a workspace whose index is built
-constexpr double PAD0 = 9.094947017729282e-13;  // 2^-40
 
 static_assert(sizeof(ogg_locate_params) == 64, "ogg_locate_params layout");
 static_assert(sizeof(ogg_locate_counts) == 80, "ogg_locate_counts layout");
 static_assert(NT == BLOCKS_NT, "block_add and block_scan work over a workgroup of BLOCKS_NT threads");
 
-struct Head {
-    long long total;                    // the last scan's total (unused with TAIL scans)
-    long long nlarge;                   // cells on the large list
-    long long G;                        // cubes per axis of the index in use
-    long long magic;                    // MAGIC + G once the index is built
-};
-static_assert(sizeof(Head) <= HEAD, "workspace head");
+using Head = BoxHead;   // magic: MAGIC + G once the index is built
 
 // ---- the definition's arithmetic -----------------------------------------------------------------------------------
 __device__ inline void cross(const double* a, const double* b, double* n) {
@@ -116,53 +110,12 @@ __global__ __launch_bounds__(NT) void record_kernel(long ny, long nx, const doub
         double* r = rec + c * NF;
         if (sigma == 0.0) {   // holds no point: an empty box
             for (int f = 0; f < 12; ++f) r[f] = 0.0;
-            for (int a = 0; a < 3; ++a) r[12 + a] = INFINITY, r[15 + a] = -INFINITY;
+            empty_box(r);
             continue;
         }
         for (int v = 0; v < 4; ++v)
             for (int a = 0; a < 3; ++a) r[3 * v + a] = sigma * nn[v][a];
-        double L2 = 0.0;
-        for (int v = 0; v < 4; ++v)
-            for (int w = v + 1; w < 4; ++w) L2 = fmax(L2, dist2(q[v][0], q[v][1], q[v][2], q[w][0], q[w][1], q[w][2]));
-        const double pad = 0.25 * L2 + PAD0;
-        for (int a = 0; a < 3; ++a) {
-            r[12 + a] = fmin(fmin(q[0][a], q[1][a]), fmin(q[2][a], q[3][a])) - pad;
-            r[15 + a] = fmax(fmax(q[0][a], q[1][a]), fmax(q[2][a], q[3][a])) + pad;
-        }
-    }
-}
-
-// ---- index ---------------------------------------------------------------------------------------------------------
-// FILL = false: the cubes' counts and the large list; FILL = true: the entries (cnt holds the cursors)
-template <bool FILL>
-__global__ __launch_bounds__(NT) void touch_kernel(long n, const double* __restrict__ rec, int G, int brute, Head* head,
-                                                   int* __restrict__ cnt, const int* __restrict__ start, int* __restrict__ entries,
-                                                   int* __restrict__ large, ogg_locate_counts* counts) {
-    for (long c = (long)blockIdx.x * NT + threadIdx.x; c < n; c += (long)gridDim.x * NT) {
-        const double* r = rec + c * NF;
-        if (!(r[12] <= r[15])) continue;   // holds no point
-        int b0[3], b1[3];
-        for (int a = 0; a < 3; ++a) b0[a] = cube_of(r[12 + a], G), b1[a] = cube_of(r[15 + a], G);
-        const long touch = (long)(b1[0] - b0[0] + 1) * (b1[1] - b0[1] + 1) * (b1[2] - b0[2] + 1);
-        if (brute || touch > OGG_LOCATE_MAX_TOUCH) {
-            if (!FILL) large[atomicAdd(ull(&head->nlarge), 1ull)] = (int)c;
-            continue;
-        }
-        for (int kz = b0[2]; kz <= b1[2]; ++kz)
-            for (int ky = b0[1]; ky <= b1[1]; ++ky)
-                for (int kx = b0[0]; kx <= b1[0]; ++kx) {
-                    const int b = kx + G * (ky + G * kz);
-                    if (FILL)
-                        entries[(long)start[b] + atomicAdd(&cnt[b], 1)] = (int)c;
-                    else
-                        atomicAdd(&cnt[b], 1);
-                }
-    }
-    if (FILL && blockIdx.x == 0 && threadIdx.x == 0) {   // the count pass, an earlier launch, has finished the large list
-        head->G = G;
-        head->magic = MAGIC + G;
-        counts->large_cells = head->nlarge;
-        counts->cubes = brute ? 0 : G;
+        padded_box(q, r);
     }
 }
 
@@ -476,21 +429,10 @@ extern "C" int ogg_locate_index_dev(const ogg_locate_params* p, void* workspace,
     hipStream_t st = ogg::as_stream(stream);
     const Layout l = layout(*p);
     const long nc = ncell_of(*p);
-    const int G = brute ? 1 : (cubes > 0 ? cubes : (int)std::min<long>(std::max<long>((long)ceil(sqrt((double)nc) / 8.0), 1), OGG_LOCATE_MAX_CUBES));
-    const long nb = (long)G * G * G;
-    Head* head = at<Head>(workspace, 0);
-    const double* rec = at<double>(workspace, l.rec);
-    int *cnt = at<int>(workspace, l.cnt), *start = at<int>(workspace, l.start), *entries = at<int>(workspace, l.entries);
-    int* large = at<int>(workspace, l.large);
-    OGG_HIP_CHECK(hipMemsetAsync(head, 0, HEAD, st));
-    OGG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)(nb + 1) * 4, st));
-    touch_kernel<false><<<grid_for<NT>(nc, 4096), NT, 0, st>>>(nc, rec, G, brute, head, cnt, start, entries, large, counts);
-    OGG_LAUNCH_CHECK();
-    if (int e = exclusive_scan<true>(cnt, nb, at<long long>(workspace, l.bsum), &head->total, start, st)) return e;
-    OGG_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)(nb + 1) * 4, st));   // the cursors of the fill
-    touch_kernel<true><<<grid_for<NT>(nc, 4096), NT, 0, st>>>(nc, rec, G, brute, head, cnt, start, entries, large, counts);
-    OGG_LAUNCH_CHECK();
-    return OGG_OK;
+    const int G = brute ? 1 : (cubes > 0 ? cubes : box_default_cubes(nc));
+    return build_box_index(nc, at<double>(workspace, l.rec), G, brute, at<Head>(workspace, 0), MAGIC, workspace,
+                           BoxIndexLayout{l.cnt, l.start, l.entries, l.large}, at<long long>(workspace, l.bsum), &counts->large_cells,
+                           &counts->cubes, st);
 }
 
 extern "C" int ogg_locate_search_dev(const ogg_locate_params* p, const double* cu, const double* lon, const double* lat, void* workspace,

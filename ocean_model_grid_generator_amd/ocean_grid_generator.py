@@ -670,7 +670,9 @@ class AnalysisFlags(object):
                     xgrid_cs_spacing="equiangular", xgrid_cs_lon_shift=0.0, xgrid_cs_file="atmos_mosaic_tile%dXocean_mosaic_tile1.nc",
                     xgrid_cs_frac_file=None, mask_table_layout=None, mask_table_dir=None, layout_sweep=None, layout_target_pes=None,
                     layout_report=None, layout_halo=0, layout_min_block=2, layout_xextent=None, layout_yextent=None,
-                    locate_points=None, locate_file="points.nc", locate_mode="bilinear")
+                    locate_points=None, locate_file="points.nc", locate_mode="bilinear", remap_source_grid=None,
+                    remap_source_corners=None, xgrid_curv_grid=None, xgrid_curv_corners=None,
+                    xgrid_curv_file="source_mosaic_tile1Xocean_mosaic_tile1.nc")
 
     def __init__(self, **flags):
         unknown = sorted(set(flags) - set(self.DEFAULTS))
@@ -686,6 +688,8 @@ def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
     _validate_mask_flags(a.ocean_mask_file, a.topog_source)
     _validate_roughness_flags(a.topog_roughness, a.topog_source, a.topog_proj, a.topog_var)
     _validate_remap_flags(a.remap_source, a.remap_var)
+    _validate_curv_flags(a.remap_source_grid, a.remap_source_corners, a.remap_source, a.xgrid_curv_grid, a.xgrid_curv_corners,
+                         a.xgrid_curv_file, a.xgrid_atm, a.xgrid_file)
     _validate_runoff_flags(a.runoff_source, a.runoff_var, a.topog_source, a.runoff_targets, skip_metrics)
     _validate_coast_distance_flags(a.coast_distance_file, a.coast_distance_sides, a.topog_source)
     _validate_basin_flags(a.basin_codes_file, a.basin_rules, a.basin_seed_max_km, a.topog_source)
@@ -713,7 +717,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          xgrid_cs_lon_shift=0.0, xgrid_cs_file="atmos_mosaic_tile%dXocean_mosaic_tile1.nc", xgrid_cs_frac_file=None,
          mask_table_layout=None, mask_table_dir=None, layout_sweep=None, layout_target_pes=None, layout_report=None, layout_halo=0,
          layout_min_block=2, layout_xextent=None, layout_yextent=None, locate_points=None, locate_file="points.nc",
-         locate_mode="bilinear", topog_proj=None):
+         locate_mode="bilinear", topog_proj=None, remap_source_grid=None, remap_source_corners=None, xgrid_curv_grid=None,
+         xgrid_curv_corners=None, xgrid_curv_file="source_mosaic_tile1Xocean_mosaic_tile1.nc"):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -773,7 +778,11 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     point of that file (``lon lat [name]`` lines, or a NetCDF file with 1-D lon and lat) the model cell that holds it, its fractional
     position in the cell and the key's margin (locate.py), written to ``locate_file``; with ``topog_source`` also the depth sampled
     there (``locate_mode``: bilinear between the four nearest wet cell centres, or the cell's own) and the cell's wet byte (the edited
-    depth and wet set with ``ocean_mask_file``); allowed with ``skip_metrics``; also an addition."""
+    depth and wet set with ``ocean_mask_file``); allowed with ``skip_metrics``; also an addition.  ``remap_source_grid``
+    (--remap_source_grid FILE): ``remap_source`` holds fields on the cells of that curvilinear grid (a MOM6 supergrid, of which every
+    second point is taken, or the two 2-D corner variables ``remap_source_corners``), remapped through the list of
+    exchange_grid_curv.py.  ``xgrid_curv_grid`` (--xgrid_curv_grid FILE): write the exchange grid of the model cells with the cells
+    of that curvilinear grid (``xgrid_curv_corners`` likewise) to ``xgrid_curv_file``; both also additions."""
     flags = dict(locals())   # the arguments, by name: taken before anything else is bound
     import time
 
@@ -1134,10 +1143,15 @@ def _run_analyses(a, g, cut=None):
         from . import exchange_grid_cs as XC
         _write_xgrid_cs(g.exchange_grid_cs(cut, XC.cubed_sphere_atm(a.xgrid_cs, a.xgrid_cs_spacing, lon_shift=a.xgrid_cs_lon_shift),
                                            mask=wet), a.xgrid_cs_file, a.xgrid_cs_frac_file)
+    if a.xgrid_curv_grid is not None:
+        from . import exchange_grid_curv as XV
+        _write_xgrid_curv(g.exchange_grid_curv(cut, *XV.read_source_corners(str(a.xgrid_curv_grid), a.xgrid_curv_corners), mask=wet),
+                          a.xgrid_curv_file)
     if a.remap_source is not None:
         from . import remap as R
         _write_results(R, R.write_remapped, [(src, g.remap(cut, src, mask=wet, fill=not a.remap_no_fill, fill_max=a.remap_fill_max))
-                                             for src in _read_sources(R, a.remap_source, a.remap_var)], a.remap_file)
+                                             for src in _read_sources(R, a.remap_source, a.remap_var, a.remap_source_grid,
+                                                                      a.remap_source_corners)], a.remap_file)
     if a.runoff_source is not None:
         from . import runoff as RO
         _write_results(RO, RO.write_runoff, [(src, g.runoff(cut, src, wet, targets=a.runoff_targets))
@@ -1178,6 +1192,10 @@ class _StitchedArrays(object):
     def exchange_grid_cs(self, cut, atm, mask=None):
         from . import exchange_grid_cs as XC
         return XC.exchange_grid_cs(self.x, self.y, atm, mask=mask, Re=_default_Re)
+
+    def exchange_grid_curv(self, cut, src_lon, src_lat, mask=None):
+        from . import exchange_grid_curv as XV
+        return XV.exchange_grid_curv(self.x, self.y, src_lon, src_lat, mask=mask, Re=_default_Re)
 
     def regrid_to_latlon(self, cut, field, atm, mask=None, lists=None):
         from . import latlon_regrid as G
@@ -1300,6 +1318,32 @@ def _topog_layered(topog_source, topog_proj=None, topog_var=None):
 def _validate_remap_flags(remap_source, remap_var):
     if remap_source is not None and not remap_var:
         raise ValueError("--remap_source needs at least one --remap_var")
+
+
+def _validate_curv_flags(remap_source_grid, remap_source_corners, remap_source, xgrid_curv_grid, xgrid_curv_corners, xgrid_curv_file,
+                         xgrid_atm, xgrid_file):
+    """the flags of the curvilinear sources: --remap_source_grid and --xgrid_curv_grid with their corner variables"""
+    if remap_source_grid is not None and remap_source is None:
+        raise ValueError("--remap_source_grid needs --remap_source: it is the grid of that file's fields")
+    if remap_source_corners and remap_source_grid is None:
+        raise ValueError("--remap_source_corners needs --remap_source_grid")
+    if xgrid_curv_corners and xgrid_curv_grid is None:
+        raise ValueError("--xgrid_curv_corners needs --xgrid_curv_grid")
+    for name, c in (("--remap_source_corners", remap_source_corners), ("--xgrid_curv_corners", xgrid_curv_corners)):
+        if c and len(c) != 2:
+            raise ValueError("%s takes two variable names, LONVAR LATVAR (%r)" % (name, c))
+    if xgrid_curv_grid is not None and xgrid_atm is not None and str(xgrid_curv_file) == str(xgrid_file):
+        raise ValueError("--xgrid_curv_file would write %s, which is --xgrid_file of --xgrid_atm: give one of them another name"
+                         % (xgrid_curv_file,))
+
+
+def _write_xgrid_curv(res, fnam):
+    if res is None:   # not rank 0
+        return
+    from . import exchange_grid_curv as XV
+    for line in XV.summary_lines(res):
+        print(line)
+    XV.write_xgrid_curv(str(fnam), res)
 
 
 def _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targets, skip_metrics):
@@ -1494,11 +1538,12 @@ def _write_xgrid(res, fnam):
     X.write_xgrid(str(fnam), res)
 
 
-def _read_sources(module, path, names):
-    """The variables ``names`` of the lat-lon file ``path`` as the Sources of remap or runoff (``module``), each announced."""
+def _read_sources(module, path, names, grid=None, corners=None):
+    """The variables ``names`` of the lat-lon file ``path`` as the Sources of remap or runoff (``module``), each announced.  ``grid``:
+    the file of the curvilinear grid the variables live on (remap alone), ``corners`` its two corner variables or None."""
     out = []
     for name in names:
-        src = module.read_source(str(path), name)
+        src = module.read_source(str(path), name) if grid is None else module.read_curvilinear_source(str(path), name, str(grid), corners)
         print(src.note)
         out.append(src)
     return out
@@ -1592,6 +1637,18 @@ def build_parser():
     parser.add_argument("--remap_var", type=str, action="append", required=False, default=None,
                         help="a variable of --remap_source (repeatable)")
     parser.add_argument("--remap_file", type=str, required=False, default="remapped.nc", help="remap output file, default remapped.nc")
+    parser.add_argument("--remap_source_grid", type=str, required=False, default=None,
+                        help="the curvilinear grid of --remap_source (a MOM6 supergrid, of which every second point is taken, or a file "
+                             "named by --remap_source_corners): its variables are then fields on that grid's cells")
+    parser.add_argument("--remap_source_corners", type=str, nargs=2, required=False, default=None, metavar=("LONVAR", "LATVAR"),
+                        help="two 2-D variables of --remap_source_grid that hold the cells' corners")
+    parser.add_argument("--xgrid_curv_grid", type=str, required=False, default=None,
+                        help="a curvilinear source grid (as --remap_source_grid): write the exchange grid of the model cells with its "
+                             "cells into --xgrid_curv_file (wet cells only when --topog_source is given)")
+    parser.add_argument("--xgrid_curv_corners", type=str, nargs=2, required=False, default=None, metavar=("LONVAR", "LATVAR"),
+                        help="two 2-D variables of --xgrid_curv_grid that hold the cells' corners")
+    parser.add_argument("--xgrid_curv_file", type=str, required=False, default="source_mosaic_tile1Xocean_mosaic_tile1.nc",
+                        help="exchange-grid output file of --xgrid_curv_grid")
     parser.add_argument("--remap_no_fill", action="store_true", help="leave wet cells the source does not cover unfilled")
     parser.add_argument("--remap_fill_max", type=int, required=False, default=None,
                         help="fill wet cells at most N cells away from a remapped cell (default: no limit)")

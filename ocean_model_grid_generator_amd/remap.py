@@ -8,10 +8,11 @@ ogg_remap); every value is a fixed function of the list, the source and values a
 bit-identical for any launch geometry and any number of ranks.
 
     python -m ocean_model_grid_generator_amd.remap ocean_hgrid.nc SOURCE --var V [--var V2 ...] [--topog topog.nc | --mask ocean_mask.nc]
-        [--no_fill] [--fill_max N] -o remapped.nc [--json summary.json]
+        [--source_grid SRC_GRID.nc [--source_corners LONVAR LATVAR]] [--no_fill] [--fill_max N] -o remapped.nc [--json summary.json]
 
 SOURCE is a NetCDF classic / 64-bit-offset file; each variable's last two dimensions are latitude and longitude (either order) on
-uniform 1-D coordinates spanning 360 degrees of longitude; every dimension ahead of them is a record dimension.
+uniform 1-D coordinates spanning 360 degrees of longitude; every dimension ahead of them is a record dimension.  With --source_grid
+the source's variables are fields on the cells of that curvilinear grid (exchange_grid_curv.py gives the weights).
 """
 import argparse
 import ctypes
@@ -41,6 +42,29 @@ class Source(F.Field):
         self.lon, self.lat = X.atm_edges(lon_edges, lat_edges)
         if self.data.shape[-2:] != (self.lat.size - 1, self.lon.size - 1):
             raise ValueError("remap source: data %s and %d x %d cells (lat x lon edges - 1)" % (self.data.shape, self.lat.size - 1, self.lon.size - 1))
+
+    NA = property(lambda self: self.lon.size - 1)
+    NB = property(lambda self: self.lat.size - 1)
+
+
+class CurvilinearSource(F.Field):
+    """A field on the cells of a curvilinear grid: a fields.Field with data (..., NB, NA) and the cells' corners corner_lon, corner_lat
+    ((NB + 1) x (NA + 1), degrees), cell (J, I) between corners (J, I) and (J + 1, I + 1); rows may run north to south.  The weights are
+    the list of exchange_grid_curv.py (great-circle edges; source cells wider than 30 degrees give nothing).  mask: None, or one value
+    per source cell (0: the cell gives nothing)."""
+    _who = "remap source"
+
+    def __init__(self, data, corner_lon, corner_lat, fill=(), name="field", lead_dims=None, coords=(), atts=(), note="", record_dim=None,
+                 mask=None):
+        from . import exchange_grid_curv as XC
+        F.Field.__init__(self, data, fill, name, lead_dims, coords, atts, note, record_dim)
+        self.corner_lon, self.corner_lat, self.mask = XC.checked_source(corner_lon, corner_lat, mask)
+        if self.data.shape[-2:] != (self.NB, self.NA):
+            raise ValueError("remap source: data %s and %d x %d cells (corners - 1)" % (self.data.shape, self.NB, self.NA))
+        XC.src_desc(None, None, self.NA, self.NB)
+
+    NA = property(lambda self: self.corner_lon.shape[1] - 1)
+    NB = property(lambda self: self.corner_lon.shape[0] - 1)
 
 
 class _Last2(object):
@@ -101,11 +125,29 @@ def _read_source(path, var, records=False):
                   record_dim=v.dims[0] if v.is_record else None)
 
 
+def read_curvilinear_source(path, var, grid_path, corner_names=None):
+    """A CurvilinearSource from two NetCDF classic or 64-bit-offset files: the byte / short / float / double variable ``var`` of
+    ``path``, whose last two dimensions are the rows and columns of the source's cells, and the cells' corners from ``grid_path``
+    (exchange_grid_curv.read_source_corners: a MOM6 supergrid, of which every second point is taken, or the two 2-D variables
+    ``corner_names``).  Values are unpacked and missing values found as for read_source; record variables are refused."""
+    from . import exchange_grid_curv as XC
+    h, v = F.open_variable(path, var, "sources", False)
+    data, fills, lead, coords, keep = F.read_values(path, h, v, False, keep=("units", "long_name", "standard_name"))
+    lon, lat = XC.read_source_corners(grid_path, corner_names)
+    NB, NA = data.shape[-2:]
+    if lon.shape != (NB + 1, NA + 1):
+        raise ValueError("%s: %s has %d x %d cells, but %s gives %d x %d corners (cells + 1 each way are needed)"
+                         % (path, var, NB, NA, grid_path, lon.shape[0], lon.shape[1]))
+    note = "%s: %s %s, %d records of %d x %d cells on the curvilinear grid of %s" % (
+        path, var, tuple(v.dims), int(np.prod(v.shape[:-2], dtype=np.int64)), NB, NA, grid_path)
+    return CurvilinearSource(data, lon, lat, fill=fills, name=var, lead_dims=lead, coords=coords, atts=keep, note=note)
+
+
 # ---- arguments -----------------------------------------------------------------------------------------------
 def params(ny, nx, source, m0=0, periodic=False, fold=False, fill_max=None):
     """an ogg_remap_params, checked by the library (OGG_EARG -> ValueError)"""
     from . import ocean_mask as M
-    p = L.RemapParams(ny=int(ny), nx=int(nx), m0=int(m0), NA=source.lon.size - 1, NB=source.lat.size - 1, nrec=source.nrec,
+    p = L.RemapParams(ny=int(ny), nx=int(nx), m0=int(m0), NA=source.NA, NB=source.NB, nrec=source.nrec,
                       dtype=_DTYPES[source.data.dtype], n_fill=len(source.fill), topology=M.topology_flags(periodic, fold),
                       fill_max=-1 if fill_max is None else int(fill_max))
     for k, f in enumerate(source.fill):
@@ -125,7 +167,7 @@ def result(values, flags, counts, source, periodic, fold, fill, fill_max, masked
         raise ValueError("remap: %d list entries lie outside the cells or the source: the list belongs to other edges or rows"
                          % counts["bad_entries"])
     shape = tuple(source.data.shape[:-2]) + values.shape[-2:]
-    summary = dict(counts, var=source.name, records=source.nrec, source_shape=[source.lat.size - 1, source.lon.size - 1],
+    summary = dict(counts, var=source.name, records=source.nrec, source_shape=[source.NB, source.NA],
                    shape=list(values.shape[-2:]), periodic=bool(periodic), fold=bool(fold), fill=bool(fill),
                    fill_max=None if fill_max is None else int(fill_max), masked=bool(masked))
     del summary["bad_entries"]
@@ -136,15 +178,21 @@ def result(values, flags, counts, source, periodic, fold, fill, fill_max, masked
 def remap(x, y, source, lon_edges=None, lat_edges=None, mask=None, fill=True, fill_max=None, fill_values=(),
           threshold=X.DEFAULT_THRESHOLD, Re=X.DEFAULT_RE):
     """The conservative remap of ``source`` onto the model cells of a stitched supergrid x, y ((ny + 1) x (nx + 1), degrees; nx, ny
-    even), on one GPU through the host-pointer entries (ogg_xgrid for the list, ogg_remap for the rest).  ``source``: a Source, or an
+    even), on one GPU through the host-pointer entries (ogg_xgrid, or ogg_xgrid_curv for a CurvilinearSource, for the list, ogg_remap
+    for the rest).  ``source``: a Source, a CurvilinearSource, or an
     array (..., NB, NA) with lon_edges, lat_edges and fill_values.  mask: None or one value per model cell (0: dry).  fill: fill
     the wet cells the source leaves empty (up to fill_max steps, None: no limit).  A dict: values, flags (the source's leading
     dimensions, then (ny / 2, nx / 2)), counts, summary."""
     from . import ocean_mask as M
-    if not isinstance(source, Source):
+    if not isinstance(source, (Source, CurvilinearSource)):
         source = Source(source, lon_edges, lat_edges, fill=fill_values)
     x, y = L.as_f64(x), L.as_f64(y)
-    lists = X.exchange_grid(x, y, source.lon, source.lat, mask=mask, Re=Re, threshold=threshold)
+    if isinstance(source, CurvilinearSource):
+        from . import exchange_grid_curv as XC
+        lists = XC.exchange_grid_curv(x, y, source.corner_lon, source.corner_lat, mask=mask, src_mask=source.mask, Re=Re, threshold=threshold)
+        lists["atm"] = lists["src"]
+    else:
+        lists = X.exchange_grid(x, y, source.lon, source.lat, mask=mask, Re=Re, threshold=threshold)
     shape = lists["a_poly"].shape
     m = F.cell_mask(mask, shape, "remap: the mask")
     periodic, fold = M.detect_topology(x, y, 2)
@@ -195,7 +243,8 @@ def fill_dev(p, values, flags, counts, stream, device):
 
 
 def remap_dev(x, y, source, mask=None, fill=True, fill_max=None, threshold=X.DEFAULT_THRESHOLD, Re=X.DEFAULT_RE):
-    """remap() on one GPU with the grid x, y as float64 device tensors ((ny + 1) x (nx + 1), contiguous rows) and a Source: the
+    """remap() on one GPU with the grid x, y as float64 device tensors ((ny + 1) x (nx + 1), contiguous rows) and a Source or a
+    CurvilinearSource: the
     list, the segments, the remap and the fill all on the device, on its current stream.  The same dict as remap(), with host arrays."""
     import torch
     from . import ocean_mask as M
@@ -208,7 +257,14 @@ def remap_dev(x, y, source, mask=None, fill=True, fill_max=None, threshold=X.DEF
     periodic, fold = M.topology_of_device_grid(x, y)
     p = params(shape[0], shape[1], source, 0, periodic, fold, fill_max)
     st = torch.cuda.current_stream(dev).cuda_stream
-    atm, ocn, area, mt = X.whole_grid_lists_dev(x, y, source.lon, source.lat, m, Re, threshold, st, dev)
+    if isinstance(source, CurvilinearSource):
+        from . import exchange_grid_curv as XC
+        up = lambda a: None if a is None else torch.from_numpy(a).to(dev)   # noqa: E731
+        sx, sy, sm, mt = up(source.corner_lon), up(source.corner_lat), up(source.mask), up(m)
+        desc = XC.src_desc(sx.data_ptr(), sy.data_ptr(), source.NA, source.NB, mask_ptr=None if sm is None else sm.data_ptr())
+        _, _, _, _, atm, ocn, area = XC.band_lists_dev(XC.whole_band(x, y, mt, Re, threshold), desc, st, dev)
+    else:
+        atm, ocn, area, mt = X.whole_grid_lists_dev(x, y, source.lon, source.lat, m, Re, threshold, st, dev)
     f = torch.from_numpy(source.records).to(dev)
     values, flags, counts = piece_dev(p, f, atm, ocn, area, mt, st, dev)
     if fill:
@@ -262,6 +318,11 @@ def main(argv=None):
     p.add_argument("grid", help="ocean_hgrid.nc (NetCDF classic / 64-bit offset)")
     p.add_argument("source", help="the lat-lon source (NetCDF classic / 64-bit offset)")
     p.add_argument("--var", action="append", required=True, help="a variable of the source (repeatable)")
+    p.add_argument("--source_grid", default=None,
+                   help="the source's own curvilinear grid: a MOM6 supergrid (every second point of x, y), or a file named by "
+                        "--source_corners; the source's variables are then fields on that grid's cells")
+    p.add_argument("--source_corners", nargs=2, default=None, metavar=("LONVAR", "LATVAR"),
+                   help="two 2-D variables of --source_grid that hold the cells' corners")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--topog", default=None, help="topog.nc: cells with depth > 0 are wet")
     g.add_argument("--mask", default=None, help="ocean_mask.nc: cells with mask != 0 are wet")
@@ -270,9 +331,13 @@ def main(argv=None):
     p.add_argument("-o", "--output", default="remapped.nc")
     p.add_argument("--json", default=None, help="write the summaries as JSON to this file")
     a = p.parse_args(argv)
+    if a.source_corners and not a.source_grid:
+        p.error("--source_corners needs --source_grid")
     grid = netcdf3.read_doubles(a.grid, names=("x", "y"))
     mask = mask_from_file(a.topog or a.mask) if (a.topog or a.mask) else None
-    return F.run_variables(a.var, lambda var: read_source(a.source, var),
+    read = (lambda var: read_curvilinear_source(a.source, var, a.source_grid, a.source_corners)) if a.source_grid else \
+        (lambda var: read_source(a.source, var))
+    return F.run_variables(a.var, read,
                            lambda src: remap(grid["x"], grid["y"], src, mask=mask, fill=not a.no_fill, fill_max=a.fill_max),
                            summary_lines, write_remapped, a.output, a.json)
 

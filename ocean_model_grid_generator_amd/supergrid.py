@@ -1379,17 +1379,28 @@ class Supergrid(object):
     def xgrid_lists(self, cut, atm, mask=None, threshold=1e-6, halo=None):
         """[(piece index, first model row, counts, a_poly, atm, ocn, area)] of THIS rank's pieces (device tensors), the exchange grid
         of each piece computed on the buffers the pass left in HBM.  ``atm``: (lon, lat) edges as float64 device tensors, or a cubed
-        sphere (a dict of exchange_grid_cs.cubed_sphere_atm with its table "t" a device tensor; atm then has three columns); ``mask``:
-        None or a uint8 device tensor of every model cell of the stitched grid."""
+        sphere (a dict of exchange_grid_cs.cubed_sphere_atm with its table "t" a device tensor; atm then has three columns), or a
+        curvilinear source (a dict {"curv": (corner lon, corner lat, mask or None)} of device tensors; atm is then the source cell
+        (I, J) and the counts are ogg_xgrid_curv_counts); ``mask``: None or a uint8 device tensor of every model cell of the stitched
+        grid."""
         p, st = self.plan, self._stream()
         halo = self.xgrid_halo(cut) if halo is None else halo   # (held until the kernels have run: the bands point into it)
-        if isinstance(atm, dict):
+        if isinstance(atm, dict) and "curv" in atm:
+            from . import exchange_grid_curv as XV
+            sx, sy, sm = atm["curv"]
+            desc = XV.src_desc(sx.data_ptr(), sy.data_ptr(), sx.shape[1] - 1, sx.shape[0] - 1, ld=sx.stride(0),
+                               mask_ptr=None if sm is None else sm.data_ptr())
+
+            def lists(*a):   # without A_src, the same in every piece (exchange_grid_curv.source_areas_dev gives it once)
+                m0, counts, a_poly, _, sij, ocn, area = XV.band_lists_dev(*a)
+                return m0, counts, a_poly, sij, ocn, area
+        elif isinstance(atm, dict):
             from . import exchange_grid_cs as X
-            desc = X.atm_desc(atm, atm["t"].data_ptr())
+            desc, lists = X.atm_desc(atm, atm["t"].data_ptr()), X.band_lists_dev
         else:
             from . import exchange_grid as X
             lon, lat = atm
-            desc = L.XgridAtm(lon=lon.data_ptr(), lat=lat.data_ptr(), NA=lon.numel() - 1, NB=lat.numel() - 1)
+            desc, lists = L.XgridAtm(lon=lon.data_ptr(), lat=lat.data_ptr(), NA=lon.numel() - 1, NB=lat.numel() - 1), X.band_lists_dev
         ny = self.stitched_rows(cut) - 1
         out = []
         for k, q, _, band in self._bands(cut, lambda q: L.XgridBand(nx=p.Ni, ny=ny, j0=q["j0"], n_cell_rows=q["n_cell"], Re=float(p.Re),
@@ -1397,21 +1408,27 @@ class Supergrid(object):
                                          skip=lambda q: self._xgrid_rows(q)[1] == 0):
             band.x_next, band.y_next = halo[k][0].data_ptr(), halo[k][1].data_ptr()
             band.mask = None if mask is None else mask.data_ptr() + self._xgrid_rows(q)[0] * (p.Ni // 2)
-            out.append((k,) + X.band_lists_dev(band, desc, st, self.device))
+            out.append((k,) + lists(band, desc, st, self.device))
         self.torch.cuda.synchronize(self.device)
         return out
 
-    def _gather_xgrid(self, cut, lon, lat, hm, threshold, cs=None):
+    def _gather_xgrid(self, cut, lon, lat, hm, threshold, cs=None, curv=None):
         """Every rank's xgrid_lists on rank 0 in piece order, the canonical order of the list (None on the other ranks): [(piece index,
         first model row, counts, a_poly, atm, ocn, area)], on the device or, under gloo, the CPU.  ``hm``: None or a uint8 host
-        array of every model cell.  ``cs``: a cubed-sphere atmosphere (host arrays) in the place of the edges lon, lat."""
+        array of every model cell.  ``cs``: a cubed-sphere atmosphere (host arrays) in the place of the edges lon, lat.  ``curv``:
+        a curvilinear source (corner lon, corner lat, mask or None as host arrays) in their place."""
         torch = self.torch
         ncol = self.plan.Ni // 2
         fields, atm_cols = (L.XGRID_COUNT_FIELDS, 2) if cs is None else (L.XGRID_CS_COUNT_FIELDS, 3)
+        if curv is not None:
+            fields = L.XGRID_CURV_COUNT_FIELDS
 
         def records(g):
             to = lambda a: torch.from_numpy(a).to(g.device)   # noqa: E731
-            atm = (to(lon), to(lat)) if cs is None else dict(cs, t=to(cs["t"]))
+            if curv is not None:
+                atm = {"curv": tuple(None if a is None else to(a) for a in curv)}
+            else:
+                atm = (to(lon), to(lat)) if cs is None else dict(cs, t=to(cs["t"]))
             return g.xgrid_lists(cut, atm, None if hm is None else to(hm), threshold)
 
         def send(e):   # counts first, then the arrays (when there are any), then a_poly
@@ -1474,6 +1491,29 @@ class Supergrid(object):
         hostp = [(m0,) + tuple(t.cpu().numpy() for t in ts) for _, m0, *ts in got]
         return XC.assemble(hostp, shape, atm, float(self.plan.Re), threshold, mask is not None)
 
+    def exchange_grid_curv(self, cut, src_lon, src_lat, mask=None, src_mask=None, threshold=1e-6):
+        """exchange_grid with a curvilinear source grid (exchange_grid_curv.result on rank 0, None on the other ranks).  src_lon,
+        src_lat: the source's cell corners ((NB + 1) x (NA + 1), degrees); src_mask: None or one value per source cell.  The source is
+        whole on every rank, the target is banded as for the other lists: the same pieces, halo rows and gather."""
+        from . import exchange_grid as X
+        from . import exchange_grid_curv as XV
+        nyp, nxp = self.stitched_rows(cut), self.plan.Ni + 1
+        X.check_grid(nyp, nxp)
+        X.check_args(threshold, self.plan.Re)
+        lon, lat, sm = XV.checked_source(src_lon, src_lat, src_mask)
+        XV.src_desc(None, None, lon.shape[1] - 1, lon.shape[0] - 1)
+        shape = ((nyp - 1) // 2, (nxp - 1) // 2)
+        hm = XV.host_mask(mask, shape)
+        got = self._gather_xgrid(cut, None, None, hm, threshold, curv=(lon, lat, sm))
+        if got is None:
+            return None
+        a_src, counts = XV.source_areas_dev(*(None if a is None else self.torch.from_numpy(a).to(self.device) for a in (lon, lat, sm)),
+                                            Re=float(self.plan.Re), stream=self._stream())
+        hostp = [(m0, c.cpu().numpy(), ap.cpu().numpy(), a_src) + tuple(t.cpu().numpy() for t in ts) for _, m0, c, ap, *ts in got]
+        if not hostp:   # no piece holds a model row: the source's counts alone
+            hostp = [(0, counts, np.zeros((0, shape[1])), a_src, np.zeros((0, 2), np.int32), np.zeros((0, 2), np.int32), np.zeros(0))]
+        return XV.assemble(hostp, shape, float(self.plan.Re), threshold, mask is not None, sm is not None)
+
     # -- ocean mask ---------------------------------------------------------------------------------------------------
     def _stitched(self, cut, fields, point_rows):
         """The stitched ``fields`` (float64 device tensors, contiguous) on rank 0's device, None on the other ranks: the point rows
@@ -1525,7 +1565,8 @@ class Supergrid(object):
 
     # -- conservative remap -------------------------------------------------------------------------------------------
     def remap(self, cut, source, mask=None, fill=True, fill_max=None, threshold=1e-6):
-        """The conservative remap (remap.result on rank 0, None on the other ranks) of ``source`` (a remap.Source) onto the model cells
+        """The conservative remap (remap.result on rank 0, None on the other ranks) of ``source`` (a remap.Source, or a
+        remap.CurvilinearSource, whose list is that of exchange_grid_curv) onto the model cells
         of the stitched grid.  ``mask``: None or one value per model cell (0: dry).  Every rank builds the lists of its own pieces
         (xgrid_lists, the source's edges as the atmosphere) and remaps their cells on its GPU; rank 0 gathers the values, flags and
         counts in piece order (_gather) and fills on its GPU with the topology of the stitched grid, as ocean_mask does.  Nothing is
@@ -1547,7 +1588,11 @@ class Supergrid(object):
             mt = None if hm is None else to(hm)
             f = to(source.records)
             out = []
-            for k, m0, _, a_poly, atm, ocn, area in g.xgrid_lists(cut, (to(source.lon), to(source.lat)), mt, threshold):
+            if isinstance(source, R.CurvilinearSource):
+                atm_ = {"curv": tuple(None if a is None else to(a) for a in (source.corner_lon, source.corner_lat, source.mask))}
+            else:
+                atm_ = (to(source.lon), to(source.lat))
+            for k, m0, _, a_poly, atm, ocn, area in g.xgrid_lists(cut, atm_, mt, threshold):
                 p = R.params(a_poly.shape[0], shape[1], source, m0)
                 rows = None if mt is None else mt[m0:m0 + a_poly.shape[0]]
                 out.append((k,) + R.piece_dev(p, f, atm, ocn, area, rows, g._stream(), g.device))
