@@ -90,7 +90,9 @@ const char* ogg_version(void);
 #define OGG_ABI_TOPOG_MERGE_RECORD 37
 #define OGG_ABI_XGRID_CURV_SRC 38
 #define OGG_ABI_XGRID_CURV_COUNTS 39
-#define OGG_ABI_N 40
+#define OGG_ABI_SPREAD_PARAMS 40
+#define OGG_ABI_SPREAD_COUNTS 41
+#define OGG_ABI_N 42
 long ogg_abi_sizeof(int which);
 int ogg_device_count(int* count);
 int ogg_set_device(int device);
@@ -1206,6 +1208,91 @@ int ogg_runoff_accumulate_dev(const ogg_runoff_params* p, const void* f, const i
 int ogg_runoff(const ogg_runoff_params* p, const double* x, const double* y, const double* area, const unsigned char* wet,
                const void* f, const double* lon, const double* lat, double* values, int* n_sources, int* src_cell, int* src_target,
                double* src_d2, ogg_runoff_counts* counts);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Runoff spreading (an addition: the reference has none).  The mapped runoff of every loaded cell (a MOUTH) spread over the wet cells
+ * within a radius, conserving the mass flux, as MOM6, CESM and ACCESS set-ups do before they use a mapped runoff: the mapping alone
+ * puts a whole river into one cell.
+ *   cells       the runoff mapping's: ny x nx model cells, c = j * nx + i, ny * nx < 2^31; centre the supergrid point (2j+1, 2i+1),
+ *               unit vector u_c by the mapping's formula, A_c as the mapping forms it; wet one byte per cell; cls NULL or one int32
+ *               class per cell (a basin code; 0 is a class like any other); load one int32 per cell (the mapping's n_sources, or any
+ *               array): load[c] > 0 makes c a MOUTH.  The mouth list is in ascending c.
+ *   candidates  the cells that are wet, whose centre coordinates are both finite and with 0 < A_c < +inf.  A mouth that is no
+ *               candidate is refused: OGG_EARG names the first such cell in ascending c, before any value is written.
+ *   receivers   R(m): the candidates t with d2(u_m, u_t) <= r2, d2 = (dx * dx + dy * dy) + dz * dz, d = u_m - u_t, no FMA, and with
+ *               cls also cls[t] == cls[m].  r2 is fp64, 0 < r2 <= 4: the squared chord of the radius, (2 sin(R / (2 Re)))^2.  m is
+ *               in R(m).  Membership is a function of d2 alone: a receiver reachable both ways round a periodic band is one
+ *               receiver, and the seam and the fold are no special cases.
+ *   weights     from correctly rounded + - * / only.  a = min(A_t / A_m, 256.0); g = 1.0 (OGG_SPREAD_UNIFORM) or h * h with
+ *               h = 1.0 - d2 / r2 (OGG_SPREAD_BIWEIGHT); q(m, t) = (long long) floor((a * g) * 16777216.0), so 0 <= q <= 2^32 and
+ *               q(m, m) = 2^24; W_m = the sum of q(m, t) over R(m) in int64 (exact, so its order is free; W_m > 0);
+ *               s(m, t) = (double) q / (double) W_m, each conversion rounded to nearest even.  A receiver with d2 == r2 has q = 0: it
+ *               counts as a receiver and contributes its +0.0 term.
+ *   values      F = v[r][m] * A_m; T[r][t] = the sum over the mouths m with t in R(m), in ASCENDING m, left to right from +0.0, of
+ *               F * s(m, t), each product rounded before it is added; out[r][t] = T / A_t.  n_mouths[t]: the number of those
+ *               mouths; a cell with none gets +0.0 whatever its input.  Input values are not inspected: NaN, negative values and
+ *               -0.0 go through the arithmetic.
+ *   limits      the pair count P = the sum of |R(m)| over the mouths must be below OGG_SPREAD_MAX_PAIRS, else OGG_EARG names P (the
+ *               environment's OGG_SPREAD_MAX_PAIRS_TEST can lower the limit, never raise it).
+ * Every output is a function of u, A, wet, cls, load and v alone: the cubes of the index (OGG_SPREAD_CUBES 1 .. OGG_SPREAD_MAX_CUBES
+ * per axis, default clamp(floor(2 / sqrt(r2)), 1, OGG_SPREAD_MAX_CUBES); OGG_SPREAD_BRUTE=1 tests every candidate), the launch geometry
+ * and, on the gathered grid, the rank count change no bit.  Caveats: a disc reaches across an isthmus narrower than the radius unless
+ * classes keep it out; the biweight shape is not CESM's exponential e-folding (exp is not bit-reproducible between hosts and the
+ * device); the area ratio is capped at 256.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { OGG_SPREAD_UNIFORM = 0, OGG_SPREAD_BIWEIGHT = 1 };
+#define OGG_SPREAD_MAX_CUBES 64          /* the largest OGG_SPREAD_CUBES: cubes per axis of the candidate index */
+#define OGG_SPREAD_MAX_PAIRS (1L << 30)  /* P must be below this */
+/* ny * nx < 2^31, nrec * ny * nx < 2^32 */
+typedef struct ogg_spread_params {
+    long ny, nx;               /* model cells */
+    long nrec;                 /* records of v */
+    int shape;                 /* OGG_SPREAD_UNIFORM / OGG_SPREAD_BIWEIGHT */
+    int use_classes;           /* 1: receivers share their mouth's class (cls must be given) */
+    double r2;                 /* squared chordal radius, 0 < r2 <= 4 */
+} ogg_spread_params;
+typedef struct ogg_spread_counts {
+    long long candidates;      /* candidate cells (sets step) */
+    long long mouths;          /* mouths (sets step) */
+    long long pairs;           /* P (count step) */
+    long long max_receivers;   /* the largest |R(m)| (count step) */
+    long long loaded;          /* cells with n_mouths > 0 (apply step) */
+    long long max_mouths;      /* the largest n_mouths (apply step) */
+    long long tests;           /* distance tests of the count step */
+    long long cubes;           /* cubes per axis of the index, 0 for brute force (sets step) */
+} ogg_spread_counts;
+/* of every step with n_pairs = P; with n_pairs = 0 of the sets and count steps, which run before P is known.  The smaller workspace is
+ * a PREFIX of the larger: its bytes copied to the front of the larger one carry the sets step's index over.  -1 on a bad *p or when
+ * n_pairs is not below the limit (ogg_last_error names P). */
+long ogg_spread_workspace_bytes(const ogg_spread_params* p, long n_pairs);
+/* the checks of *p (sizes, shape, use_classes, r2): OGG_EARG with the reason, before any device work */
+int ogg_spread_check(const ogg_spread_params* p);
+/* sets step, device pointers, on a stream: x, y the supergrid points (2 ny + 1 rows of ld doubles), area the supergrid area (2 ny rows
+ * of lda doubles), wet and load per cell; u (3 per cell), A and the candidate flag cand (one byte) of EVERY cell, the mouth list
+ * mouth_cell (room for ny * nx) in ascending c; the candidates sorted into cubes in the workspace; *counts (device memory) is zeroed
+ * and gets candidates, mouths and cubes.  Waits for the stream: a mouth that is no candidate is OGG_EARG here. */
+int ogg_spread_sets_dev(const ogg_spread_params* p, const double* x, const double* y, long ld, const double* area, long lda,
+                        const unsigned char* wet, const int* load, void* workspace, long workspace_bytes, double* u, double* A,
+                        unsigned char* cand, int* mouth_cell, ogg_spread_counts* counts, void* stream);
+/* count step (n_mouths: the sets step's count): mouth_n = |R(m)| and mouth_W = W_m of every mouth; pairs, max_receivers and tests
+ * into *counts.  cls: NULL unless use_classes. */
+int ogg_spread_count_dev(const ogg_spread_params* p, const double* u, const double* A, const int* cls, const int* mouth_cell,
+                         long n_mouths, void* workspace, long workspace_bytes, int* mouth_n, long long* mouth_W,
+                         ogg_spread_counts* counts, void* stream);
+/* pairs step (n_pairs: the count step's pairs, which the workspace must be sized for): every pair's key sorted, and every cell's
+ * mouths as a segment in ascending mouth order, into the workspace */
+int ogg_spread_pairs_dev(const ogg_spread_params* p, const double* u, const int* cls, const int* mouth_cell, const int* mouth_n,
+                         long n_mouths, long n_pairs, void* workspace, long workspace_bytes, void* stream);
+/* apply step, after the pairs step: out (nrec * ny * nx fp64, record-major) and n_mouths (ny * nx) as above from v (nrec * ny * nx
+ * fp64); loaded and max_mouths into *counts. */
+int ogg_spread_apply_dev(const ogg_spread_params* p, const double* v, const double* u, const double* A, const int* mouth_cell,
+                         const long long* mouth_W, long n_mouths, long n_pairs, const void* workspace, long workspace_bytes, double* out,
+                         int* n_mouths_out, ogg_spread_counts* counts, void* stream);
+/* HOST pointers throughout, staged through device memory: the four steps on the supergrid x, y ((2 ny + 1) x (2 nx + 1)) and area
+ * (2 ny x 2 nx).  mouth_cell, mouth_n, mouth_W: room for ny * nx (counts->mouths are written).  cls: NULL unless use_classes. */
+int ogg_runoff_spread(const ogg_spread_params* p, const double* x, const double* y, const double* area, const unsigned char* wet,
+                      const int* cls, const int* load, const double* v, double* out, int* n_mouths, int* mouth_cell, int* mouth_n,
+                      long long* mouth_W, ogg_spread_counts* counts);
 
 /* ------------------------------------------------------------------------------------------------------
  * Conservative regrid to a lat-lon grid (an addition: the reference has none).  Fields on the model cells aggregated first-order

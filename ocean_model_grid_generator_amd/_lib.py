@@ -221,6 +221,23 @@ RUNOFF_COAST, RUNOFF_WET = 0, 1                                        # OGG_RUN
 RUNOFF_MAX_BINS = 160                                                  # OGG_RUNOFF_MAX_BINS
 
 
+class SpreadParams(ctypes.Structure):
+    """ogg_spread_params of include/ogg_hip.h"""
+    _fields_ = [("ny", c_long), ("nx", c_long), ("nrec", c_long), ("shape", c_int), ("use_classes", c_int), ("r2", c_double)]
+
+
+SPREAD_COUNT_FIELDS = ("candidates", "mouths", "pairs", "max_receivers", "loaded", "max_mouths", "tests", "cubes")
+
+
+class SpreadCounts(ctypes.Structure):
+    """ogg_spread_counts of include/ogg_hip.h"""
+    _fields_ = [(f, c_longlong) for f in SPREAD_COUNT_FIELDS]
+
+
+SPREAD_UNIFORM, SPREAD_BIWEIGHT = 0, 1                                 # OGG_SPREAD_UNIFORM, OGG_SPREAD_BIWEIGHT
+SPREAD_MAX_CUBES, SPREAD_MAX_PAIRS = 64, 1 << 30                       # OGG_SPREAD_MAX_CUBES, OGG_SPREAD_MAX_PAIRS
+
+
 class CoastParams(ctypes.Structure):
     """ogg_coast_params of include/ogg_hip.h"""
     _fields_ = [("ny", c_long), ("nx", c_long), ("topology", c_int), ("sides", c_int)]
@@ -331,7 +348,7 @@ ABI_MIRRORS = {"LATLON_BAND": LatlonBand, "BIPOLAR_BAND": BipolarBand, "DPOLE_BA
                "XGRID_CS_ATM": XgridCsAtm, "XGRID_CS_COUNTS": XgridCsCounts, "LAYOUT_PARAMS": LayoutParams, "LAYOUT_CANDIDATE": LAYOUT_CANDIDATE,
                "LAYOUT_RECORD": LAYOUT_RECORD, "LOCATE_PARAMS": LocateParams, "LOCATE_COUNTS": LocateCounts, "TOPOG_PROJECTION": TopogProjection,
                "TOPOG_LAYER": TopogLayer, "TOPOG_MERGE_RECORD": TOPOG_MERGE_RECORD, "XGRID_CURV_SRC": XgridCurvSrc,
-               "XGRID_CURV_COUNTS": XgridCurvCounts}
+               "XGRID_CURV_COUNTS": XgridCurvCounts, "SPREAD_PARAMS": SpreadParams, "SPREAD_COUNTS": SpreadCounts}
 ABI = {name: code for code, name in enumerate(ABI_MIRRORS)}
 
 
@@ -479,6 +496,17 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p],
     "ogg_runoff": [ctypes.POINTER(RunoffParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                    c_void_p, c_void_p, c_void_p, ctypes.POINTER(RunoffCounts)],
+    "ogg_spread_check": [ctypes.POINTER(SpreadParams)],
+    "ogg_spread_sets_dev": [ctypes.POINTER(SpreadParams), c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_spread_count_dev": [ctypes.POINTER(SpreadParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p,
+                             c_void_p, c_void_p, c_void_p],
+    "ogg_spread_pairs_dev": [ctypes.POINTER(SpreadParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_long,
+                             c_void_p],
+    "ogg_spread_apply_dev": [ctypes.POINTER(SpreadParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p,
+                             c_long, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_runoff_spread": [ctypes.POINTER(SpreadParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(SpreadCounts)],
     "ogg_coast_check": [ctypes.POINTER(CoastParams)],
     "ogg_coast_sets_dev": [ctypes.POINTER(CoastParams), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
@@ -551,6 +579,7 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_mask_workspace_bytes": [ctypes.POINTER(MaskParams)],
                 "ogg_remap_workspace_bytes": [ctypes.POINTER(RemapParams)],
                 "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],
+                "ogg_spread_workspace_bytes": [ctypes.POINTER(SpreadParams), c_long],
                 "ogg_coast_workspace_bytes": [ctypes.POINTER(CoastParams)],
                 "ogg_basin_workspace_bytes": [ctypes.POINTER(BasinParams)],
                 "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long],

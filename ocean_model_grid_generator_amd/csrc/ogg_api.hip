@@ -238,6 +238,8 @@ long ogg_abi_sizeof(int which) {
         case OGG_ABI_TOPOG_MERGE_RECORD: return (long)sizeof(ogg_topog_merge_record);
         case OGG_ABI_XGRID_CURV_SRC: return (long)sizeof(ogg_xgrid_curv_src);
         case OGG_ABI_XGRID_CURV_COUNTS: return (long)sizeof(ogg_xgrid_curv_counts);
+        case OGG_ABI_SPREAD_PARAMS: return (long)sizeof(ogg_spread_params);
+        case OGG_ABI_SPREAD_COUNTS: return (long)sizeof(ogg_spread_counts);
         default: return -1L;
     }
 }

@@ -664,6 +664,7 @@ class AnalysisFlags(object):
                     xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False,
                     mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False,
                     remap_fill_max=None, runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast",
+                    runoff_spread_km=None, runoff_spread_shape="biweight", runoff_spread_by_basin=False,
                     coast_distance_file=None, coast_distance_sides="both", basin_codes_file=None, basin_rules=None, basin_seed_max_km=None,
                     xgrid_frac_file=None, interp_source=None, interp_var=None, interp_vector=None, interp_points="h",
                     interp_file="interp.nc", interp_no_fill=False, interp_fill_max=None, interp_no_rotate=False, xgrid_cs=None,
@@ -691,6 +692,8 @@ def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
     _validate_curv_flags(a.remap_source_grid, a.remap_source_corners, a.remap_source, a.xgrid_curv_grid, a.xgrid_curv_corners,
                          a.xgrid_curv_file, a.xgrid_atm, a.xgrid_file)
     _validate_runoff_flags(a.runoff_source, a.runoff_var, a.topog_source, a.runoff_targets, skip_metrics)
+    _validate_runoff_spread_flags(a.runoff_spread_km, a.runoff_spread_shape, a.runoff_spread_by_basin, a.runoff_source,
+                                  a.basin_codes_file, a.basin_rules)
     _validate_coast_distance_flags(a.coast_distance_file, a.coast_distance_sides, a.topog_source)
     _validate_basin_flags(a.basin_codes_file, a.basin_rules, a.basin_seed_max_km, a.topog_source)
     _validate_locate_flags(a.locate_points, a.locate_file, a.locate_mode)
@@ -718,7 +721,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          mask_table_layout=None, mask_table_dir=None, layout_sweep=None, layout_target_pes=None, layout_report=None, layout_halo=0,
          layout_min_block=2, layout_xextent=None, layout_yextent=None, locate_points=None, locate_file="points.nc",
          locate_mode="bilinear", topog_proj=None, remap_source_grid=None, remap_source_corners=None, xgrid_curv_grid=None,
-         xgrid_curv_corners=None, xgrid_curv_file="source_mosaic_tile1Xocean_mosaic_tile1.nc"):
+         xgrid_curv_corners=None, xgrid_curv_file="source_mosaic_tile1Xocean_mosaic_tile1.nc", runoff_spread_km=None,
+         runoff_spread_shape="biweight", runoff_spread_by_basin=False):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -782,7 +786,10 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     (--remap_source_grid FILE): ``remap_source`` holds fields on the cells of that curvilinear grid (a MOM6 supergrid, of which every
     second point is taken, or the two 2-D corner variables ``remap_source_corners``), remapped through the list of
     exchange_grid_curv.py.  ``xgrid_curv_grid`` (--xgrid_curv_grid FILE): write the exchange grid of the model cells with the cells
-    of that curvilinear grid (``xgrid_curv_corners`` likewise) to ``xgrid_curv_file``; both also additions."""
+    of that curvilinear grid (``xgrid_curv_corners`` likewise) to ``xgrid_curv_file``; both also additions.  ``runoff_spread_km``
+    (--runoff_spread_km R, needs ``runoff_source``): the mapped runoff of every loaded cell spread over the wet cells within R km
+    before it is written (runoff.py, "Runoff spreading"; ``runoff_spread_shape``: biweight or uniform; ``runoff_spread_by_basin``:
+    within the basin of the mouth, by the codes of ``basin_codes_file``, which must be asked for in the same call); also an addition."""
     flags = dict(locals())   # the arguments, by name: taken before anything else is bound
     import time
 
@@ -1122,9 +1129,11 @@ def _run_analyses(a, g, cut=None):
     wet = _xgrid_mask(topo)   # of the topography as written: the wet set of everything below
     if a.coast_distance_file:
         _write_coast_distance(g.coast_distance(cut, wet, sides=a.coast_distance_sides), a.coast_distance_file)
+    basins = None
     if a.basin_codes_file:
         from . import basin_codes as BC
-        _write_basin_codes(g.basin_codes(cut, wet, BC.read_rules(str(a.basin_rules)), seed_max_km=a.basin_seed_max_km), a.basin_codes_file)
+        basins = g.basin_codes(cut, wet, BC.read_rules(str(a.basin_rules)), seed_max_km=a.basin_seed_max_km)
+        _write_basin_codes(basins, a.basin_codes_file)
     if a.locate_points:
         from . import locate as LOC
         lon, lat, names = LOC.read_points(str(a.locate_points))
@@ -1154,8 +1163,14 @@ def _run_analyses(a, g, cut=None):
                                                                       a.remap_source_corners)], a.remap_file)
     if a.runoff_source is not None:
         from . import runoff as RO
-        _write_results(RO, RO.write_runoff, [(src, g.runoff(cut, src, wet, targets=a.runoff_targets))
-                                             for src in _read_sources(RO, a.runoff_source, a.runoff_var)], a.runoff_file)
+        spread = {}
+        if a.runoff_spread_km is not None:   # the classes: the basin codes as written (rank 0 holds them)
+            by_basin = a.runoff_spread_by_basin and basins is not None
+            spread = dict(spread_km=a.runoff_spread_km, spread_shape=a.runoff_spread_shape,
+                          spread_classes=basins["code"].astype(np.int32) if by_basin else None)
+        _write_results(RO, lambda fnam, out: RO.write_runoff(fnam, out, spread_classes="basin"),
+                       [(src, g.runoff(cut, src, wet, targets=a.runoff_targets, **spread))
+                        for src in _read_sources(RO, a.runoff_source, a.runoff_var)], a.runoff_file)
     if a.interp_source is not None:
         _write_interp(_interp_results(a.interp_source, a.interp_var, a.interp_vector, a.interp_points, lambda s1, s2: g.bilinear(
             cut, s1, s2, points=a.interp_points, mask=wet if a.interp_points == "h" else None, fill=not a.interp_no_fill,
@@ -1205,9 +1220,9 @@ class _StitchedArrays(object):
         from . import remap as R
         return R.remap(self.x, self.y, source, Re=_default_Re, **args)
 
-    def runoff(self, cut, source, wet, targets="coast"):
+    def runoff(self, cut, source, wet, targets="coast", **spread):
         from . import runoff as RO
-        return RO.runoff(self.x, self.y, self.metrics[2], source, wet, targets=targets, Re=_default_Re)
+        return RO.runoff(self.x, self.y, self.metrics[2], source, wet, targets=targets, Re=_default_Re, **spread)
 
     def coast_distance(self, cut, wet, sides="both"):
         from . import coast_distance as CD
@@ -1357,6 +1372,19 @@ def _validate_runoff_flags(runoff_source, runoff_var, topog_source, runoff_targe
         raise ValueError("--runoff_source needs --topog_source: the runoff goes to the wet cells of the topography")
     if runoff_targets not in ("coast", "wet"):
         raise ValueError("--runoff_targets must be coast or wet, not %r" % (runoff_targets,))
+
+
+def _validate_runoff_spread_flags(km, shape, by_basin, runoff_source, basin_codes_file, basin_rules):
+    if km is None:
+        if by_basin:
+            raise ValueError("--runoff_spread_by_basin needs --runoff_spread_km")
+        return
+    if runoff_source is None:
+        raise ValueError("--runoff_spread_km needs --runoff_source: it spreads the mapped runoff")
+    from . import runoff as RO
+    RO.check_spread_flags(km, shape, bool(by_basin), "--runoff_spread_km", "--runoff_spread_shape", "--runoff_spread_by_basin")
+    if by_basin and not (basin_codes_file and basin_rules):
+        raise ValueError("--runoff_spread_by_basin needs --basin_codes_file and --basin_rules in the same call: the classes are its codes")
 
 
 def _validate_coast_distance_flags(coast_distance_file, coast_distance_sides, topog_source):
@@ -1658,6 +1686,12 @@ def build_parser():
     parser.add_argument("--runoff_var", type=str, action="append", required=False, default=None,
                         help="a variable of --runoff_source (repeatable)")
     parser.add_argument("--runoff_file", type=str, required=False, default="runoff.nc", help="runoff output file, default runoff.nc")
+    parser.add_argument("--runoff_spread_km", type=float, required=False, default=None,
+                        help="spread the mapped runoff of every loaded cell over the wet cells within this many km (needs --runoff_source)")
+    parser.add_argument("--runoff_spread_shape", type=str, choices=["biweight", "uniform"], required=False, default="biweight",
+                        help="the weights of --runoff_spread_km: a biweight of the chordal distance (default) or uniform")
+    parser.add_argument("--runoff_spread_by_basin", action="store_true", required=False, default=False,
+                        help="keep the spread runoff within the basin of its mouth (needs --basin_codes_file and --basin_rules)")
     parser.add_argument("--runoff_targets", type=str, choices=["coast", "wet"], required=False, default="coast",
                         help="coast (default): wet cells next to land; wet: every wet cell")
     parser.add_argument("--coast_distance_file", type=str, required=False, default=None,

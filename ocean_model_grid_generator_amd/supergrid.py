@@ -1656,16 +1656,21 @@ class Supergrid(object):
                             hm is not None, shape, self._stream(), self.device)
 
     # -- runoff mapping -----------------------------------------------------------------------------------------------
-    def runoff(self, cut, source, wet, targets="coast"):
+    def runoff(self, cut, source, wet, targets="coast", spread_km=None, spread_shape="biweight", spread_classes=None, keep_lists=False):
         """The runoff mapping (runoff.result on rank 0, None on the other ranks) of ``source`` (a remap.Source) onto the model cells of
         the stitched grid with the wet set ``wet`` (one value per model cell, 0: land), on rank 0's GPU with the stitched points and
-        area gathered there, as ocean_mask does: the same bits for any number of ranks by construction."""
+        area gathered there, as ocean_mask does: the same bits for any number of ranks by construction.  ``spread_km``: the mapped
+        values spread over the wet cells within that radius (runoff.spread_dev; ``spread_classes``: one integer per model cell), on
+        the same gathered grid."""
         from . import runoff as RO
         xy = self.stitched_xy(cut)
         area = self.stitched_area(cut)
         if xy is None:
             return None
-        return RO.runoff_dev(xy[0], xy[1], area, source, wet, targets=targets, Re=float(self.plan.Re))
+        if spread_km is None:
+            return RO.runoff_dev(xy[0], xy[1], area, source, wet, targets=targets, Re=float(self.plan.Re), keep_lists=keep_lists)
+        return RO.runoff_dev(xy[0], xy[1], area, source, wet, targets=targets, Re=float(self.plan.Re), keep_lists=keep_lists,
+                             spread_km=spread_km, spread_shape=spread_shape, spread_classes=spread_classes)
 
     # -- distance to the coast ----------------------------------------------------------------------------------------
     def coast_distance(self, cut, wet, sides="both"):
