@@ -1764,6 +1764,76 @@ int ogg_locate(const ogg_locate_params* p, const double* x, const double* y, con
 int ogg_locate_sample(const ogg_locate_params* p, const int* cell, const double* s, const double* t, const void* f,
                       const unsigned char* wet, double* values, unsigned char* flags, ogg_locate_counts* counts);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Regional grids (an addition: the reference makes the global tripolar grid only).  A patch of sphere with its own equator through
+ * the domain: a lat-lon or a Mercator lattice in a ROTATED frame (lam', phi') whose point (0, 0) is the domain centre (lon_c, lat_c)
+ * and whose x axis at the centre is turned by ``tilt`` degrees counter-clockwise from east.  Neither periodic nor pole-holding.
+ *   rotation  with p' = (cos phi' cos lam', cos phi' sin lam', sin phi') the geographic unit vector relative to the centre meridian
+ *            is p = Ry(-lat_c) Rx(tilt) p' = cos phi' (cos lam' q1 + sin lam' q2) + sin phi' q3 with, cl, sl the cosine and sine of
+ *            lat_c and ct, st those of tilt,  q1 = (cl, 0, sl),  q2 = (-sl st, ct, cl st),  q3 = (-sl ct, -st, cl ct).
+ *            a_i = cos lam'_i q1 + sin lam'_i q2 and e_i = -sin lam'_i q1 + cos lam'_i q2 (the grid's x direction, the same on every
+ *            row) belong to a column, cos phi'_j and sin phi'_j to a row: p = cos phi'_j a_i + sin phi'_j q3.
+ *   points   x = lon_c + atan2(p_y, p_x) in degrees: continuous over the domain whatever lon_c is, no jump at +-180, stated on
+ *            lon_c's own turn.  y = atan2(p_z, sqrt(p_x^2 + p_y^2)) in degrees (no asin: conditioned next to the poles).
+ *   lattice  nx by ny SUPERGRID cells, both even (nx/2 by ny/2 model cells); point (j, i), j = 0 .. ny, i = 0 .. nx, has
+ *            lam'_i = (i - nx/2) delta, delta degrees per supergrid step, and
+ *              OGG_REGIONAL_LATLON    phi'_j = (j - ny/2) delta: generate_latlon_grid (OGG:832-846), rotated;
+ *              OGG_REGIONAL_MERCATOR  phi'_j = atan(sinh(t_j)), t_j = (j - ny/2) delta pi/180: the lattice of phi_mercator (OGG:298-301)
+ *                                     with Ni = 360/delta, rotated: an oblique Mercator with isotropic cells.  cos phi' = 1/cosh(t)
+ *                                     and sin phi' = tanh(t), not taken from phi'.
+ *   metrics  the MIDAS lat-lon formulas (OGG:687-716 with latlon_areafix) stated in the rotated frame, where they are EXACT: a
+ *            rotation is an isometry, so they hold on the sphere.
+ *              dx(j, i)   = Re cos phi'_j delta pi/180                              (ny+1) x nx
+ *              dy(j, i)   = Re (phi'_{j+1} - phi'_j)                                ny x (nx+1)
+ *              area(j, i) = Re^2 delta pi/180 (sin phi'_{j+1} - sin phi'_j)         ny x nx
+ *            The device forms the two differences without cancellation: lat-lon rows have phi'_{j+1} - phi'_j = delta pi/180 and
+ *            sin phi'_{j+1} - sin phi'_j = 2 cos(phi'_{j+1/2}) sin(delta pi/360); Mercator rows, with h = delta pi/360 and t_m =
+ *            t_j + h, have phi'_{j+1} - phi'_j = 2 atan(sinh h / cosh t_m) (phi' = 2 atan(tanh(t/2)) and the addition theorem of the
+ *            tangent) and sin phi'_{j+1} - sin phi'_j = sinh(2 h) / (cosh t_j cosh t_{j+1}).
+ *   identity with lat_c = 0 and tilt = 0 the rotation is the identity and the grid IS the lattice shifted by lon_c: the device writes
+ *            x = lon_c + lam'_i, y = phi'_j (Mercator: atan(sinh(t_j)) in degrees) and angle_dx = 0 as such, which is what the statements
+ *            above give in exact arithmetic; no arctangent of a sine and a cosine comes between.
+ *   angle_dx(j, i) = atan2(e . n, e . ee) in degrees, (ny+1) x (nx+1), ee and n the geographic east and north at p.  This is the
+ *            ANALYTIC angle of the grid's x direction, not the reference's finite difference angle_x (OGG:719-729) of the mesh; the
+ *            two agree to O(delta^2).  (a_i, e_i, q3) is a right-handed orthonormal frame and e is perpendicular to p, which gives
+ *            with h = sqrt(p_x^2 + p_y^2):  e . n = e_z / h  and  e . ee = (cos phi'_j q3_z - sin phi'_j a_z) / h,  so
+ *            angle_dx = atan2(e_z(i), cos phi'_j q3_z - sin phi'_j a_z(i)): no product of small differences.
+ *   refused  with OGG_EARG and the reason, before any device work: nx or ny odd or below 2 (or above 2^22); delta, Re not positive;
+ *            an argument that is not finite, or lon_c or tilt above 1e6 in magnitude; |lam'| >= 180 at the edge; |phi'| > 89 at the edge; |lat_c| > 90; a domain whose rotated
+ *            rectangle (widened by 1e-9 degrees) holds a geographic pole -- a point of the mesh could sit on it, a cell could have it
+ *            as a corner, and the analyses treat such cells as special cases.
+ * Every value is a function of (j, i) and the parameters alone: no launch geometry and no split into bands changes a bit.
+ * Workspace: the column table (a_i, e_z(i)) and the row table (cos phi', sin phi', dx, dy, area per row), a few doubles per row and
+ * column, filled by ogg_regional_tables_dev and read by every band of the same parameters.
+ * Parameters: every entry takes the same nine scalars first, by value (no struct: the table of OGG_ABI_* size codes is unchanged):
+ *   nx, ny        supergrid cells, both even and >= 2
+ *   lon_c, lat_c  the domain centre, degrees;  tilt  degrees counter-clockwise from east
+ *   delta         degrees per supergrid step in the rotated frame;  Re  sphere radius, metres
+ *   kind          OGG_REGIONAL_LATLON / OGG_REGIONAL_MERCATOR;  metrics  0: x and y only, 1: all six fields
+ * ---------------------------------------------------------------------------------------------------- */
+enum { OGG_REGIONAL_LATLON = 0, OGG_REGIONAL_MERCATOR = 1 };
+#define OGG_REGIONAL_MAX_CELLS 4194304   /* the largest nx, ny: 2^22 */
+/* the checks of the parameters listed above: OGG_EARG with the reason, no device work */
+int ogg_regional_check(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int kind, int metrics);
+/* -1 on bad parameters */
+long ogg_regional_workspace_bytes(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int kind, int metrics);
+/* the two tables into the workspace (device memory): one small launch */
+int ogg_regional_tables_dev(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int kind, int metrics,
+                            void* workspace, long workspace_bytes, void* stream);
+/* after ogg_regional_tables_dev on the same workspace with the same parameters: the point rows j0 .. j0 + nrows - 1 (0 <= j0, j0 +
+ * nrows <= ny + 1) and the cell rows among them (j < ny) of the grid, one launch.  Every array begins at the band's first row:
+ *   x, y, angle_dx   nrows x (nx+1)
+ *   dx               nrows x nx
+ *   dy               (cell rows of the band) x (nx+1);  area  (cell rows of the band) x nx
+ * With metrics == 0 only x and y are written and the other four may be NULL. */
+int ogg_regional_band_dev(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int kind, int metrics,
+                          long j0, long nrows, const void* workspace, long workspace_bytes, double* x, double* y, double* dx, double* dy,
+                          double* area, double* angle_dx, void* stream);
+/* HOST pointers, staged through device memory: the whole grid, x, y, angle_dx (ny+1) x (nx+1), dx (ny+1) x nx, dy ny x (nx+1), area
+ * ny x nx; with metrics == 0 only x and y */
+int ogg_regional_grid(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int kind, int metrics,
+                      double* x, double* y, double* dx, double* dy, double* area, double* angle_dx);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

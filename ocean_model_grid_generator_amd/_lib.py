@@ -238,6 +238,12 @@ SPREAD_UNIFORM, SPREAD_BIWEIGHT = 0, 1                                 # OGG_SPR
 SPREAD_MAX_CUBES, SPREAD_MAX_PAIRS = 64, 1 << 30                       # OGG_SPREAD_MAX_CUBES, OGG_SPREAD_MAX_PAIRS
 
 
+# the nine scalars every ogg_regional_* entry takes first: nx, ny, lon_c, lat_c, tilt, delta, Re, kind, metrics
+REGIONAL_ARGS = [c_long, c_long, c_double, c_double, c_double, c_double, c_double, c_int, c_int]
+REGIONAL_LATLON, REGIONAL_MERCATOR = 0, 1                              # OGG_REGIONAL_LATLON, OGG_REGIONAL_MERCATOR
+REGIONAL_MAX_CELLS = 1 << 22                                           # OGG_REGIONAL_MAX_CELLS
+
+
 class CoastParams(ctypes.Structure):
     """ogg_coast_params of include/ogg_hip.h"""
     _fields_ = [("ny", c_long), ("nx", c_long), ("topology", c_int), ("sides", c_int)]
@@ -507,6 +513,11 @@ SIGNATURES = {
                              c_long, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_runoff_spread": [ctypes.POINTER(SpreadParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(SpreadCounts)],
+    "ogg_regional_check": REGIONAL_ARGS,
+    "ogg_regional_tables_dev": REGIONAL_ARGS + [c_void_p, c_long, c_void_p],
+    "ogg_regional_band_dev": REGIONAL_ARGS + [c_long, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p],
+    "ogg_regional_grid": REGIONAL_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_coast_check": [ctypes.POINTER(CoastParams)],
     "ogg_coast_sets_dev": [ctypes.POINTER(CoastParams), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
@@ -580,6 +591,7 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_remap_workspace_bytes": [ctypes.POINTER(RemapParams)],
                 "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],
                 "ogg_spread_workspace_bytes": [ctypes.POINTER(SpreadParams), c_long],
+                "ogg_regional_workspace_bytes": REGIONAL_ARGS,
                 "ogg_coast_workspace_bytes": [ctypes.POINTER(CoastParams)],
                 "ogg_basin_workspace_bytes": [ctypes.POINTER(BasinParams)],
                 "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long],

@@ -1,0 +1,37 @@
+"""The device entries of the regional grids (ogg_regional_tables_dev / ogg_regional_band_dev) held to their extents with the harness
+of tests/test_gpu_extents.py: every case runs plain, with every byte of the arena 0xFF and with seeded random bytes; the guard bands
+must be intact and the three results the same bytes.  The six fields and the workspace are exact-size views of the arena, flush
+against their guards: the lanes beyond a row's last point or last cell, the last row's missing dy and area, and a band that begins
+in the middle of the arrays must write nothing else.  The cases are recorded in that module's COVERED set, which its census
+(test_every_device_entry_ran_guarded) reads: this module's name sorts before it, so in a run of the whole GPU suite the entries are
+covered when the census runs."""
+import numpy as np
+import pytest
+
+import test_gpu_extents as TE
+from test_gpu_extents import arena, record_entries, three_runs   # noqa: F401  (fixtures of the harness)
+
+pytestmark = pytest.mark.gpu
+FAR_BELOW = TE.PEAK_USED // 4
+ENTRIES = {"ogg_regional_tables_dev", "ogg_regional_band_dev"}
+
+
+@pytest.fixture(scope="module")
+def R(hip):
+    from ocean_model_grid_generator_amd import regional
+    return regional
+
+
+@pytest.mark.parametrize("kind", ["latlon", "mercator"])
+@pytest.mark.parametrize("metrics", [True, False])
+@pytest.mark.parametrize("nx, ny", [(2, 2), (130, 4), (4, 130)])
+def test_the_two_entries(R, arena, three_runs, nx, ny, metrics, kind):
+    for bands in (1, 3, ny + 1):
+        res = three_runs(lambda: R.regional_grid_dev(-140.5, 55.0, nx, ny, 0.25, kind, tilt=40.0, metrics=metrics, bands=bands),
+                         "regional %dx%d %s metrics=%s bands=%d" % (nx, ny, kind, metrics, bands))
+        assert ENTRIES <= TE.COVERED
+        assert sorted(res) == (sorted(R.FIELDS) if metrics else ["x", "y"])
+        for f, v in res.items():
+            a = np.frombuffer(v[3], dtype=np.float64)
+            assert v[2] == R.shapes(nx, ny)[f] and np.all(np.isfinite(a)), f
+    assert arena.used(guards=True) < FAR_BELOW
