@@ -769,6 +769,76 @@ int ogg_topog_project_dev(const ogg_topog_projection* proj, long n, const double
                           int* gate_ok, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Face topography (opt-in; without it every record, output and file above is what it was): what lies BETWEEN two neighbouring model
+ * cells, for MOM6's sub-grid topography at velocity points (its "porous barriers" read a lowest, a highest and an average depth on
+ * every u and v face).  One lat-lon source (no list, no projected source), integer records only, no connectivity search.  Where this
+ * text and "Topography by refined sampling" above could disagree about a sample, that section wins: a face's samples are its samples.
+ *   grid      the STITCHED supergrid x, y ((ny + 1) x (nx + 1), row stride ld >= nx + 1), ny and nx even; model cells nym = ny / 2 by
+ *             nxm = nx / 2; topology = OGG_MASK_PERIODIC | OGG_MASK_FOLD, the ocean mask's flags
+ *   u faces   (jm, I), jm = 0 .. nym - 1, I = 0 .. nxm, on supergrid point column 2 I.  The face's BLOCK is supergrid rows 2 jm + dj
+ *             (dj = 0, 1) of column 2 I - 1 (west side) and column 2 I (east side).  At I = 0 the west side is absent, with PERIODIC it
+ *             is column nx - 1; at I = nxm the east side is absent, with PERIODIC it is column 0: the faces I = 0 and I = nxm then
+ *             hold the same record, byte for byte
+ *   v faces   (J, im), J = 0 .. nym, im = 0 .. nxm - 1, on supergrid point row 2 J.  The block is supergrid columns 2 im + di
+ *             (di = 0, 1) of row 2 J - 1 (south side) and row 2 J (north side).  At J = 0 the south side is absent.  At J = nym the
+ *             north side is absent; with FOLD it is row ny - 1 of columns nx - 1 - (2 im + di), read with its lines reversed (below)
+ *   refine    every present supergrid cell of the block gets its R by the topography's rule (spans, oversample, clamp at 256); the
+ *             block's R is the largest of them, n_clamped counts the clamped cells; refine > 0 replaces R for every cell (nothing is
+ *             clamped).  Every present cell of the block is then sampled at R x R: positions (unwrap, pole-corner substitution, s, t,
+ *             the bilinear lon and lat), index and value are exactly the topography's for a cell of that R
+ *   lines     a line runs across the face, from one side's cell centre line to the other's, along the grid's own coordinate.  u face,
+ *             line (dj, b): the samples (a, b), a = 0 .. R - 1, of cell (2 jm + dj, west) and of cell (2 jm + dj, east).  v face, line
+ *             (di, a): the samples (a, b), b = 0 .. R - 1, of cell (south, 2 im + di) and of cell (north, 2 im + di); on the fold the
+ *             north side gives the samples (R - 1 - a, b) of cell (ny - 1, nx - 1 - (2 im + di)).  A two-sided face has 2 R lines of up
+ *             to 2 R samples, a one-sided face 2 R lines of up to R samples.  The RIDGE of a line is the largest q among its samples
+ *             that are not MISSING; a line none of whose samples has a value is a missing line
+ *   pole      if a present cell of the block ENCLOSES a pole (the topography's pole test) the face has no lines: its record has the
+ *             POLE flag, n = n_missing = n_lines = n_lines_missing = n_dry_lines = 0, ridge_sum = 0 and extremes as for "none" (R,
+ *             n_clamped and the other flags as for any face).  Cells with pole corners are sampled like any other
+ *   record    n, n_missing: samples of the block with and without a value; n_lines, n_lines_missing: lines with a ridge and missing
+ *             lines; n_dry_lines: lines with a ridge that is not wet, !(ridge < wet_q), wet_q the topography's integer threshold of
+ *             (double)q < wet_below; lo: the smallest ridge, the deepest way through the face (the SILL), INT32_MAX when none; hi: the
+ *             largest ridge, INT32_MIN when none; ridge_sum (int64): the sum of the ridges; q_min: the smallest valid sample of the
+ *             block, INT32_MAX when none; R, n_clamped; flags: OGG_FACE_ONE_SIDED (a side is absent), OGG_FACE_POLE, OGG_FACE_SEAM
+ *             (the periodic partner was used), OGG_FACE_FOLD (the fold partner was used)
+ * Everything is an integer, so a record is exact: no launch shape, work order or split of the output rows changes a bit of it.
+ * Outputs (host side, quantum as in the topography): depth_max = -lo * quantum (the sill, the deepest passage), depth_min = -hi *
+ * quantum (the shallowest), depth_ave = -(ridge_sum / n_lines) * quantum, open_fraction = 1 - n_dry_lines / n_lines.  Depths are not
+ * clamped at zero: a face over land has negative depths, and n_dry_lines is the wet test.
+ * Why lines: they are the paths a flow takes across the face if it follows the grid, and a line's highest point is what that path
+ * must clear: a ridge anywhere between the two cell centres counts, not only one on the face line itself, and a gap in the ridge
+ * one line wide still shows as lo.  It needs no search and no ordering.  It is NOT Adcroft's thin-wall coarsening, and it finds no
+ * passage that runs diagonally through the block.
+ * ---------------------------------------------------------------------------------------------------- */
+#define OGG_FACE_ONE_SIDED 1
+#define OGG_FACE_POLE 2
+#define OGG_FACE_SEAM 4
+#define OGG_FACE_FOLD 8
+/* A face record is OGG_TOPOG_FACE_WORDS int64 words (56 bytes, little-endian), no struct of this header, so that the set of structs
+ * and their OGG_ABI_* codes stays what it was.  Byte offsets: 0 n, 8 n_missing, 16 ridge_sum (int64 each); 24 n_lines, 28
+ * n_lines_missing, 32 n_dry_lines, 36 lo, 40 hi, 44 q_min, 48 R (int32 each); 52 n_clamped, 54 flags (int16 each). */
+#define OGG_TOPOG_FACE_WORDS 7
+/* The grid of a call is the whole stitched grid as ONE band of model cells: grid->nx, grid->n_cell_rows = ny, grid->j0 = 0,
+ * grid->cells = OGG_TOPOG_MODEL_CELLS, grid->x, grid->y of (ny + 1) rows of ld doubles (ld >= nx + 1), grid->refine and
+ * grid->oversample as for a band; x_next and y_next are not read.  The output rows: u-face rows [ju0, ju1) of 0 .. nym and v-face rows
+ * [jv0, jv1) of 0 .. nym + 1 (any slice; an empty range skips that family).
+ * ogg_topog_faces_check: OGG_EARG with a reason for odd or empty sizes, ld < nx + 1, bad ranges, a bad topology, refine outside
+ * 0 .. 256, a bad oversample and a bad source (device != 0: the source must be int16 or int32, as ogg_topog_faces_dev needs it).  No
+ * device work, no pointer of *grid or *src is followed. */
+int ogg_topog_faces_check(const ogg_topog_band* grid, long ld, int topology, long ju0, long ju1, long jv0, long jv1,
+                          const ogg_topog_source* src, int device);
+/* device pointers throughout: out_u holds (ju1 - ju0) x (nxm + 1) records, row-major (jm - ju0, I), out_v (jv1 - jv0) x nxm records,
+ * (J - jv0, im); only the ranges' rows.  One wavefront owns each face record; wavefronts take runs of faces from the counters at the
+ * head of the workspace (ogg_topog_workspace_bytes; work distribution only), the line ridges are combined in LDS by integer maxima. */
+int ogg_topog_faces_dev(const ogg_topog_band* grid, long ld, int topology, long ju0, long ju1, long jv0, long jv1,
+                        const ogg_topog_source* src, void* workspace, long workspace_bytes, long long* out_u, long long* out_v,
+                        void* stream);
+/* HOST pointers in *grid and *src, staged like ogg_topog; out_u, out_v are host memory.  A float source is quantised on the device
+ * first (OGG_EARG when |q| > OGG_TOPOG_MAX_Q). */
+int ogg_topog_faces(const ogg_topog_band* grid, long ld, int topology, long ju0, long ju1, long jv0, long jv1,
+                    const ogg_topog_source* src, long long* out_u, long long* out_v);
+
+/* ------------------------------------------------------------------------------------------------------
  * Atmosphere x ocean exchange grid (an addition: the reference has none).  First-order conservative overlaps of a rectilinear global
  * atmosphere with the MOM6 h-cells of the STITCHED supergrid x, y ((ny + 1) x (nx + 1), degrees; nx and ny even), as FMS's
  * make_coupler_mosaic lists them.  All arithmetic is fp64 without fused multiply-add.

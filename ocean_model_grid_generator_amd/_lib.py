@@ -118,6 +118,14 @@ class TopogLayer(ctypes.Structure):
 TOPOG_MERGE_RECORD = np.dtype(TOPOG_RECORD.descr + [("n_from", "<i8", (TOPOG_MAX_SOURCES,))])
 
 
+FACE_ONE_SIDED, FACE_POLE, FACE_SEAM, FACE_FOLD = 1, 2, 4, 8           # OGG_FACE_* of include/ogg_hip.h
+TOPOG_FACE_WORDS = 7                                                   # OGG_TOPOG_FACE_WORDS
+# a face record (OGG_TOPOG_FACE_WORDS int64 words, 56 bytes) as a numpy record: the byte offsets of include/ogg_hip.h
+TOPOG_FACE_RECORD = np.dtype([("n", "<i8"), ("n_missing", "<i8"), ("ridge_sum", "<i8"), ("n_lines", "<i4"), ("n_lines_missing", "<i4"),
+                              ("n_dry_lines", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("q_min", "<i4"), ("R", "<i4"), ("n_clamped", "<i2"),
+                              ("flags", "<i2")])
+
+
 class XgridAtm(ctypes.Structure):
     """ogg_xgrid_atm of include/ogg_hip.h"""
     _fields_ = [("lon", c_void_p), ("lat", c_void_p), ("NA", c_long), ("NB", c_long)]
@@ -455,6 +463,10 @@ SIGNATURES = {
     "ogg_topog_layer_range_dev": [ctypes.POINTER(TopogLayer), c_void_p, c_void_p],
     "ogg_topog_layers": [ctypes.POINTER(TopogBand), c_int, ctypes.POINTER(TopogLayer), c_void_p],
     "ogg_topog_project_dev": [ctypes.POINTER(TopogProjection), c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_topog_faces_check": [ctypes.POINTER(TopogBand), c_long, c_int, c_long, c_long, c_long, c_long, ctypes.POINTER(TopogSource), c_int],
+    "ogg_topog_faces_dev": [ctypes.POINTER(TopogBand), c_long, c_int, c_long, c_long, c_long, c_long, ctypes.POINTER(TopogSource), c_void_p, c_long, c_void_p,
+                            c_void_p, c_void_p],
+    "ogg_topog_faces": [ctypes.POINTER(TopogBand), c_long, c_int, c_long, c_long, c_long, c_long, ctypes.POINTER(TopogSource), c_void_p, c_void_p],
     "ogg_xgrid_check_atm": [ctypes.POINTER(XgridAtm)],
     "ogg_xgrid_count_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_void_p, c_long, c_void_p, c_void_p, c_void_p],
     "ogg_xgrid_write_dev": [ctypes.POINTER(XgridBand), ctypes.POINTER(XgridAtm), c_void_p, c_long, c_void_p, c_void_p, c_void_p,

@@ -247,6 +247,20 @@ OGG_DEV int wave_max(int v) {
     return v;
 }
 
+// the position of sample (a, b) of supergrid cell c, S and U the tables of c.R: the one place a sample's position is formed
+OGG_DEV void sample_position(const Cell& c, const double* S, const double* U, int a, int b, double& lon, double& lat) {
+    const double sa = S[a], ua = U[a];
+    lat = 0.0;
+    if (c.pole == 0) {
+        const double tb = S[b], vb = U[b];
+        const double w00 = ua * vb, w01 = sa * vb, w10 = ua * tb, w11 = sa * tb;
+        lon = w00 * c.L00 + w01 * c.L01 + w10 * c.L10 + w11 * c.L11;
+        lat = w00 * c.y00 + w01 * c.y01 + w10 * c.y10 + w11 * c.y11;
+    } else {
+        lon = c.L00 + 360.0 * sa;
+    }
+}
+
 // a lane's share of the R x R samples of supergrid cell c: their positions, each handed to the sampler
 template <class Sampler>
 OGG_DEV void sample_cell(Sampler& sm, const Cell& c, const double* S, const double* U, int lane, Acc& acc) {
@@ -257,16 +271,8 @@ OGG_DEV void sample_cell(Sampler& sm, const Cell& c, const double* S, const doub
     int a = f % R, b = f / R;
     const int step_b = TT / R, step_a = TT % R;
     for (; f < RR; f += TT) {
-        const double sa = S[a], ua = U[a];
-        double lon, lat = 0.0;
-        if (c.pole == 0) {
-            const double tb = S[b], vb = U[b];
-            const double w00 = ua * vb, w01 = sa * vb, w10 = ua * tb, w11 = sa * tb;
-            lon = w00 * c.L00 + w01 * c.L01 + w10 * c.L10 + w11 * c.L11;
-            lat = w00 * c.y00 + w01 * c.y01 + w10 * c.y10 + w11 * c.y11;
-        } else {
-            lon = c.L00 + 360.0 * sa;
-        }
+        double lon, lat;
+        sample_position(c, S, U, a, b, lon, lat);
         sm.sample(c, lon, lat, acc);
         a += step_a, b += step_b;
         if (a >= R) a -= R, b += 1;
@@ -434,6 +440,172 @@ __global__ __launch_bounds__(TT) void topog_band_kernel(Geo g, Src s, unsigned l
         sm.pl.lds = &origin;
     }
     topog_walk(g, counter, sm);
+}
+
+// ---- face topography (include/ogg_hip.h, "Face topography") ---------------------------------------------------------------------
+// One wavefront per workgroup owns each face record and takes runs of TR faces of one family from a counter in the workspace, as the
+// walk does.  Lanes 0 .. 3 set up the block's cells (lane = 2 d + side: d the line group dj or di, side 0 west / south, 1 east /
+// north) with the walk's cell_geometry and refine rule; the block's R is their largest, and every present cell is walked at that R
+// with the walk's sample_position, lane l taking the flattened samples f = b R + a = l, l + 64, ..., so consecutive lanes are
+// consecutive a (along a raster row).  The ridge of line k lives in LDS (ridge[d R + k], INT_MIN: no sample yet) and takes every
+// sample by an LDS integer max, exact in any order.  On a u face consecutive lanes share a line (b), and 64 lanes would hit a few LDS
+// addresses: the run of equal b among the 64 samples of a step is first reduced across lanes by a segmented scan (shuffles by 1, 2,
+// 4, .. below min(R, 64); lane - o lies in the same run exactly when a >= o), and the last lane of each run alone goes to LDS.  On a
+// v face consecutive lanes are consecutive lines (a), and each goes to LDS itself.  After a barrier the wavefront reduces the 2 R
+// lines with shuffles and lane 0 stores the record.  No atomic touches global memory but the work counter.
+// the record as the header lays it out in OGG_TOPOG_FACE_WORDS int64 words (little-endian), and the call's parameters
+struct FaceRecord {
+    long long n, n_missing, ridge_sum;
+    int n_lines, n_lines_missing, n_dry_lines, lo, hi, q_min, R;
+    short n_clamped, flags;
+};
+static_assert(sizeof(FaceRecord) == 8 * OGG_TOPOG_FACE_WORDS && alignof(FaceRecord) == 8, "face record layout");
+struct FaceParams {
+    long nx, ny, ld;
+    const double *x, *y;
+    int topology, refine;
+    double oversample;
+    long ju0, ju1, jv0, jv1;
+};
+
+struct Faces {
+    long nxm, nym, nx, ny;
+    long r0, per_row, total;   // the first output row, faces per row, faces of this launch
+    int periodic, fold;
+};
+
+// supergrid cell k = 2 d + side of the block of face (row, col) (a u face (jm, I) or a v face (J, im)): false when that side is
+// absent; rev: the fold partner, whose lines are read reversed
+template <bool VFACE>
+OGG_DEV bool face_cell(const Faces& fc, long row, long col, int k, long& j, long& i, bool& partner) {
+    const int d = k >> 1, side = k & 1;
+    partner = false;
+    if (!VFACE) {
+        j = 2 * row + d;
+        i = 2 * col - 1 + side;
+        if (side == 0 && col == 0) i = fc.nx - 1, partner = true;
+        if (side == 1 && col == fc.nxm) i = 0, partner = true;
+        return !partner || fc.periodic;
+    }
+    i = 2 * col + d;
+    j = 2 * row - 1 + side;
+    if (side == 0 && row == 0) return false;
+    if (side == 1 && row == fc.nym) {
+        j = fc.ny - 1, i = fc.nx - 1 - i, partner = true;
+        return fc.fold != 0;
+    }
+    return true;
+}
+
+template <int DT, bool VFACE>
+__global__ __launch_bounds__(TT) void topog_faces_kernel(Geo g, Src s, Faces fc, unsigned long long* counter, FaceRecord* out) {
+    __shared__ double S[RMAX], U[RMAX];
+    __shared__ Cell cells[4];
+    __shared__ int ridge[2 * RMAX];
+    __shared__ long long take;
+    const int lane = threadIdx.x;
+    int table_R = 0;
+    for (;;) {
+        if (lane == 0) take = (long long)atomicAdd(counter, (unsigned long long)TR);
+        __syncthreads();
+        const long long c0 = take;
+        __syncthreads();
+        if (c0 >= fc.total) break;
+        const long long c1 = c0 + TR < fc.total ? c0 + TR : fc.total;
+        for (long long c = c0; c < c1; ++c) {
+            const long row = fc.r0 + (long)(c / fc.per_row), col = (long)(c % fc.per_row);
+            if (lane < 4) {
+                long j, i;
+                bool partner;
+                Cell cl;
+                if (face_cell<VFACE>(fc, row, col, lane, j, i, partner)) {
+                    cl = cell_geometry(g, j, i);
+                    if (g.refine <= 0) set_refine(cl, latlon_refine_value(cl, s.dlon, s.dlat, g.oversample));
+                } else {
+                    cl.valid = 0, cl.R = 0, cl.pole = 0, cl.clamped = 0;
+                }
+                cells[lane] = cl;
+            }
+            __syncthreads();
+            int R = 0, n_pole = 0, n_clamped = 0, n_present = 0;
+            for (int k = 0; k < 4; ++k) {
+                const Cell& cl = cells[k];
+                if (!cl.valid) continue;
+                R = cl.R > R ? cl.R : R;
+                n_pole += cl.pole != 0, n_clamped += cl.clamped, n_present += 1;
+            }
+            // the flags, from the face's place alone
+            int flags = n_present < 4 ? OGG_FACE_ONE_SIDED : 0;
+            if (!VFACE && (col == 0 || col == fc.nxm) && fc.periodic) flags |= OGG_FACE_SEAM;
+            const bool on_fold = VFACE && row == fc.nym && fc.fold;
+            if (on_fold) flags |= OGG_FACE_FOLD;
+            if (n_pole) flags |= OGG_FACE_POLE;
+            if (R != table_R) {   // s = (a + 0.5) / R and 1 - s for this R; the barrier above closed the last face's reads
+                for (int a = lane; a < R; a += TT) {
+                    const double sv = ((double)a + 0.5) / (double)R;
+                    S[a] = sv, U[a] = 1.0 - sv;
+                }
+                table_R = R;
+            }
+            for (int k = lane; k < 2 * R; k += TT) ridge[k] = INT_MIN;
+            __syncthreads();
+            int n = 0, nm = 0, qmin = INT_MAX;
+            const int RR = R * R;
+            int scan_top = R < TT ? R : TT;   // the scan's shifts stay below the longest run of a step
+            for (int k = 0; k < 4 && !n_pole; ++k) {
+                Cell cl = cells[k];
+                if (!cl.valid) continue;
+                cl.R = R;
+                const int d = k >> 1;
+                const bool rev = on_fold && (k & 1);
+                int a = lane % R, b = lane / R;
+                const int step_b = TT / R, step_a = TT % R;
+                for (int f0 = 0; f0 < RR; f0 += TT) {   // the same trips in every lane: the shuffles below need them all
+                    const bool live = f0 + lane < RR;
+                    int q = INT_MIN;
+                    if (live) {
+                        double lon, lat;
+                        sample_position(cl, S, U, a, b, lon, lat);
+                        int is, js, v;
+                        bool miss = latlon_index(s, 0, lon, lat, is, js);
+                        if (!miss) miss = raster_value(s, DT, is, js, v);
+                        n += miss ? 0 : 1, nm += miss ? 1 : 0;
+                        if (!miss) q = v, qmin = v < qmin ? v : qmin;
+                    }
+                    if (VFACE) {
+                        if (q != INT_MIN) atomicMax(&ridge[d * R + (rev ? R - 1 - a : a)], q);
+                    } else {
+                        for (int o = 1; o < scan_top; o <<= 1) {
+                            const int up = __shfl_up(q, o, TT);
+                            if (lane >= o && a >= o) q = up > q ? up : q;
+                        }
+                        const bool last = lane == TT - 1 || a == R - 1;   // of its run in this step (a dead lane's q is INT_MIN)
+                        if (live && last && q != INT_MIN) atomicMax(&ridge[d * R + b], q);
+                    }
+                    a += step_a, b += step_b;
+                    if (a >= R) a -= R, b += 1;
+                }
+            }
+            __syncthreads();
+            int nl = 0, nlm = 0, ndry = 0, lo = INT_MAX, hi = INT_MIN;
+            long long rsum = 0;
+            for (int k = lane; k < 2 * R && !n_pole; k += TT) {
+                const int r = ridge[k];
+                const bool ok = r != INT_MIN;
+                nl += ok ? 1 : 0, nlm += ok ? 0 : 1;
+                ndry += ok && !(r < s.wet_q) ? 1 : 0;
+                lo = ok && r < lo ? r : lo, hi = r > hi ? r : hi;
+                rsum += ok ? r : 0;
+            }
+            FaceRecord r;
+            r.n = wave_sum((long long)n), r.n_missing = wave_sum((long long)nm), r.ridge_sum = wave_sum(rsum);
+            r.n_lines = wave_sum(nl), r.n_lines_missing = wave_sum(nlm), r.n_dry_lines = wave_sum(ndry);
+            r.lo = wave_min(lo), r.hi = wave_max(hi), r.q_min = wave_min(qmin);
+            r.R = R, r.n_clamped = (short)n_clamped, r.flags = (short)flags;
+            if (lane == 0) out[c] = r;
+            __syncthreads();   // cells[], ridge[] and the tables are rewritten for the next face
+        }
+    }
 }
 
 // ---- layered topography (include/ogg_hip.h, "Layered topography") ------------------------------------------------------------
@@ -991,5 +1163,135 @@ extern "C" int ogg_topog_layers(const ogg_topog_band* band, int n_layers, const 
     if (int e = bufs.alloc(&res, (size_t)nrec)) return e;
     if (int e = ogg_topog_layers_band_dev(&d, n_layers, dl, ws, ogg_topog_workspace_bytes(), res, nullptr)) return e;
     if (int e = bufs.get(out, res, (size_t)nrec)) return e;
+    return OGG_OK;
+}
+
+// ---- face topography: entry points ---------------------------------------------------------------------------------------------
+namespace {
+
+int check_faces(const FaceParams* pp, const ogg_topog_source* src, bool sampled) {
+    OGG_REQUIRE(pp && src, OGG_EARG, "ogg_topog_faces: null pointer");
+    const FaceParams& p = *pp;
+    OGG_REQUIRE(p.nx >= 2 && p.ny >= 2 && p.nx < (1L << 30) && p.ny < (1L << 30), OGG_EARG, "ogg_topog_faces: %ld x %ld supergrid cells",
+                p.ny, p.nx);
+    OGG_REQUIRE(p.nx % 2 == 0 && p.ny % 2 == 0, OGG_EARG,
+                "ogg_topog_faces: faces lie between model cells of 2 x 2 supergrid cells, but the supergrid has %ld x %ld cells", p.ny, p.nx);
+    OGG_REQUIRE(p.ld >= p.nx + 1, OGG_EARG, "ogg_topog_faces: row stride ld = %ld below nx + 1 = %ld", p.ld, p.nx + 1);
+    const long nym = p.ny / 2;
+    OGG_REQUIRE(p.ju0 >= 0 && p.ju0 <= p.ju1 && p.ju1 <= nym, OGG_EARG, "ogg_topog_faces: u-face rows [%ld, %ld) outside 0 .. %ld", p.ju0,
+                p.ju1, nym);
+    OGG_REQUIRE(p.jv0 >= 0 && p.jv0 <= p.jv1 && p.jv1 <= nym + 1, OGG_EARG, "ogg_topog_faces: v-face rows [%ld, %ld) outside 0 .. %ld",
+                p.jv0, p.jv1, nym + 1);
+    OGG_REQUIRE((p.topology & ~(OGG_MASK_PERIODIC | OGG_MASK_FOLD)) == 0, OGG_EARG, "ogg_topog_faces: topology flags %d", p.topology);
+    OGG_REQUIRE(p.refine >= 0 && p.refine <= RMAX, OGG_EARG, "ogg_topog_faces: refine = %d (0 or 1 .. %d)", p.refine, RMAX);
+    OGG_REQUIRE(p.refine > 0 || (p.oversample > 0.0 && std::isfinite(p.oversample)), OGG_EARG, "ogg_topog_faces: oversample = %g",
+                p.oversample);
+    return check_source(*src, sampled);
+}
+
+template <bool VFACE>
+int launch_faces(const Geo& g, const Src& s, const Faces& fc, int dtype, unsigned long long* counter, FaceRecord* out,
+                 hipStream_t st) {
+    if (fc.total == 0) return OGG_OK;
+    int dev = 0, n_cu = 0;
+    OGG_HIP_CHECK(hipGetDevice(&dev));
+    OGG_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    const long takes = (fc.total + TR - 1) / TR;
+    const unsigned wgs = (unsigned)std::min(takes, (long)(n_cu > 0 ? n_cu : 256) * 32);   // as walk_launch
+    if (dtype == OGG_TOPOG_INT16)
+        topog_faces_kernel<OGG_TOPOG_INT16, VFACE><<<wgs, TT, 0, st>>>(g, s, fc, counter, out);
+    else
+        topog_faces_kernel<OGG_TOPOG_INT32, VFACE><<<wgs, TT, 0, st>>>(g, s, fc, counter, out);
+    OGG_LAUNCH_CHECK();
+    return OGG_OK;
+}
+
+// the parameters of a call: the whole stitched grid as one band of model cells (j0 = 0, n_cell_rows = ny; x_next, y_next not read)
+int face_params(const ogg_topog_band* grid, long ld, int topology, long ju0, long ju1, long jv0, long jv1, FaceParams* p) {
+    OGG_REQUIRE(grid, OGG_EARG, "ogg_topog_faces: null grid");
+    OGG_REQUIRE(grid->j0 == 0 && grid->cells == OGG_TOPOG_MODEL_CELLS, OGG_EARG,
+                "ogg_topog_faces: the grid is the whole stitched grid as one band of model cells (j0 = %ld, cells = %d)", grid->j0, grid->cells);
+    *p = FaceParams{grid->nx, grid->n_cell_rows, ld, grid->x, grid->y, topology, grid->refine, grid->oversample, ju0, ju1, jv0, jv1};
+    return OGG_OK;
+}
+
+}  // namespace
+
+extern "C" int ogg_topog_faces_check(const ogg_topog_band* grid, long ld, int topology, long ju0, long ju1, long jv0, long jv1,
+                                     const ogg_topog_source* src, int device) {
+    FaceParams p;
+    if (int e = face_params(grid, ld, topology, ju0, ju1, jv0, jv1, &p)) return e;
+    return check_faces(&p, src, device != 0);
+}
+
+namespace {
+
+int faces_dev(const FaceParams* pp, const ogg_topog_source* src, void* workspace, long workspace_bytes, FaceRecord* out_u, FaceRecord* out_v,
+              void* stream) {
+    if (int e = check_faces(pp, src, true)) return e;
+    const FaceParams& p = *pp;
+    const long nu = p.ju1 - p.ju0, nv = p.jv1 - p.jv0;
+    if (nu == 0 && nv == 0) return OGG_OK;
+    OGG_REQUIRE(p.x && p.y && (nu == 0 || out_u) && (nv == 0 || out_v), OGG_EARG, "ogg_topog_faces: null x / y / out_u / out_v");
+    if (int e = ogg::check_workspace("ogg_topog_faces", workspace, workspace_bytes, ogg_topog_workspace_bytes())) return e;
+    // the walk's geometry of the whole grid: rows 0 .. ny - 1 at stride ld, the row that follows them the grid's last point row
+    const Geo g{p.x, p.y, p.x + p.ny * p.ld, p.y + p.ny * p.ld, p.nx, p.ld, 0, p.ny, 0, 0, 0, 0, p.refine, p.oversample};
+    const Src s = make_src(*src);
+    const long nxm = p.nx / 2, nym = p.ny / 2;
+    const int periodic = (p.topology & OGG_MASK_PERIODIC) != 0, fold = (p.topology & OGG_MASK_FOLD) != 0;
+    hipStream_t st = ogg::as_stream(stream);
+    unsigned long long* counters = static_cast<unsigned long long*>(workspace);   // one per family
+    OGG_HIP_CHECK(hipMemsetAsync(workspace, 0, 2 * sizeof(unsigned long long), st));
+    const Faces fu{nxm, nym, p.nx, p.ny, p.ju0, nxm + 1, nu * (nxm + 1), periodic, fold};
+    const Faces fv{nxm, nym, p.nx, p.ny, p.jv0, nxm, nv * nxm, periodic, fold};
+    if (int e = launch_faces<false>(g, s, fu, src->dtype, counters, out_u, st)) return e;
+    if (int e = launch_faces<true>(g, s, fv, src->dtype, counters + 1, out_v, st)) return e;
+    return OGG_OK;
+}
+
+}  // namespace
+
+extern "C" int ogg_topog_faces_dev(const ogg_topog_band* grid, long ld, int topology, long ju0, long ju1, long jv0, long jv1,
+                                   const ogg_topog_source* src, void* workspace, long workspace_bytes, long long* out_u, long long* out_v,
+                                   void* stream) {
+    FaceParams p;
+    if (int e = face_params(grid, ld, topology, ju0, ju1, jv0, jv1, &p)) return e;
+    return faces_dev(&p, src, workspace, workspace_bytes, reinterpret_cast<FaceRecord*>(out_u), reinterpret_cast<FaceRecord*>(out_v), stream);
+}
+
+// HOST pointers: the grid and the raster copied to device memory (a float raster quantised there), both families in one device call,
+// the records of the two ranges copied back (synchronous)
+extern "C" int ogg_topog_faces(const ogg_topog_band* grid, long ld, int topology, long ju0, long ju1, long jv0, long jv1,
+                               const ogg_topog_source* src, long long* out_u_words, long long* out_v_words) {
+    FaceParams h;
+    if (int e = face_params(grid, ld, topology, ju0, ju1, jv0, jv1, &h)) return e;
+    if (int e = check_faces(&h, src, false)) return e;
+    FaceRecord *out_u = reinterpret_cast<FaceRecord*>(out_u_words), *out_v = reinterpret_cast<FaceRecord*>(out_v_words);
+    const long nxm = h.nx / 2;
+    const long nu = (h.ju1 - h.ju0) * (nxm + 1), nv = (h.jv1 - h.jv0) * nxm;
+    if (nu == 0 && nv == 0) return OGG_OK;
+    OGG_REQUIRE(h.x && h.y && (nu == 0 || out_u) && (nv == 0 || out_v), OGG_EARG, "ogg_topog_faces: null x / y / out_u / out_v");
+    ogg::Buffers bufs;   // freed on every exit path
+    FaceParams d = h;
+    const size_t npt = (size_t)h.ny * h.ld + (size_t)h.nx + 1;   // the last row ends at its last point
+    double *px, *py;
+    if (int e = bufs.put(&px, h.x, npt)) return e;
+    if (int e = bufs.put(&py, h.y, npt)) return e;
+    d.x = px, d.y = py;
+    ogg_topog_source ds = *src;
+    int nb = 0;
+    if (int e = stage_raster(bufs, &ds, &nb)) return e;
+    OGG_REQUIRE(nb == 0, OGG_EARG, "ogg_topog_faces: a quantised source value exceeds %d in magnitude (quantum %g too small)",
+                OGG_TOPOG_MAX_Q, ds.quantum);
+    char* ws;
+    FaceRecord *ru, *rv;
+    if (int e = bufs.alloc(&ws, (size_t)ogg_topog_workspace_bytes())) return e;
+    if (int e = bufs.alloc(&ru, (size_t)std::max(nu, 1L))) return e;
+    if (int e = bufs.alloc(&rv, (size_t)std::max(nv, 1L))) return e;
+    if (int e = faces_dev(&d, &ds, ws, ogg_topog_workspace_bytes(), ru, rv, nullptr)) return e;
+    if (nu)
+        if (int e = bufs.get(out_u, ru, (size_t)nu)) return e;
+    if (nv)
+        if (int e = bufs.get(out_v, rv, (size_t)nv)) return e;
     return OGG_OK;
 }

@@ -660,7 +660,7 @@ class AnalysisFlags(object):
     """main()'s flags of the analyses that follow the grid (its docstring describes them), with main()'s defaults: what main() hands
     to either of its paths.  An unknown name is a TypeError."""
     DEFAULTS = dict(quality_report=None, topog_source=None, topog_var="elevation", topog_proj=None, topog_file="topog.nc",
-                    topog_refine=None, topog_roughness=False, xgrid_atm=None,
+                    topog_refine=None, topog_roughness=False, topog_faces_file=None, xgrid_atm=None,
                     xgrid_file="atmos_mosaic_tile1Xocean_mosaic_tile1.nc", ocean_mask_file=None, mask_min_depth=0.0, mask_deepen=False,
                     mask_seed=None, mask_keep_cells=0, remap_source=None, remap_var=None, remap_file="remapped.nc", remap_no_fill=False,
                     remap_fill_max=None, runoff_source=None, runoff_var=None, runoff_file="runoff.nc", runoff_targets="coast",
@@ -688,6 +688,7 @@ def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
     _validate_flags(match_dy, r_dp, lat_dp)
     _validate_mask_flags(a.ocean_mask_file, a.topog_source)
     _validate_roughness_flags(a.topog_roughness, a.topog_source, a.topog_proj, a.topog_var)
+    _validate_faces_flags(a.topog_faces_file, a.topog_source, a.topog_proj, a.topog_var)
     _validate_remap_flags(a.remap_source, a.remap_var)
     _validate_curv_flags(a.remap_source_grid, a.remap_source_corners, a.remap_source, a.xgrid_curv_grid, a.xgrid_curv_corners,
                          a.xgrid_curv_file, a.xgrid_atm, a.xgrid_file)
@@ -722,7 +723,7 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          layout_min_block=2, layout_xextent=None, layout_yextent=None, locate_points=None, locate_file="points.nc",
          locate_mode="bilinear", topog_proj=None, remap_source_grid=None, remap_source_corners=None, xgrid_curv_grid=None,
          xgrid_curv_corners=None, xgrid_curv_file="source_mosaic_tile1Xocean_mosaic_tile1.nc", runoff_spread_km=None,
-         runoff_spread_shape="biweight", runoff_spread_by_basin=False):
+         runoff_spread_shape="biweight", runoff_spread_by_basin=False, topog_faces_file=None):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -789,7 +790,10 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     of that curvilinear grid (``xgrid_curv_corners`` likewise) to ``xgrid_curv_file``; both also additions.  ``runoff_spread_km``
     (--runoff_spread_km R, needs ``runoff_source``): the mapped runoff of every loaded cell spread over the wet cells within R km
     before it is written (runoff.py, "Runoff spreading"; ``runoff_spread_shape``: biweight or uniform; ``runoff_spread_by_basin``:
-    within the basin of the mouth, by the codes of ``basin_codes_file``, which must be asked for in the same call); also an addition."""
+    within the basin of the mouth, by the codes of ``basin_codes_file``, which must be asked for in the same call); also an addition.
+    ``topog_faces_file`` (--topog_faces_file FILE, needs one lat-lon ``topog_source``): the face topography of the model grid
+    (face_topography.py: the sill, the shallowest and the mean ridge depth of the grid-following lines across every u and v face,
+    with ``topog_refine``), written to FILE; not edited by ``ocean_mask_file``; also an addition."""
     flags = dict(locals())   # the arguments, by name: taken before anything else is bound
     import time
 
@@ -1120,12 +1124,14 @@ def _run_analyses(a, g, cut=None):
         _write_quality_report(g.quality(cut), a.quality_report)
     topo = None
     if a.topog_source is not None:
-        topo = g.topography(cut, _topog_source(a.topog_source, a.topog_var, a.topog_proj), refine=a.topog_refine,
-                            plane=bool(a.topog_roughness))
+        tsrc = _topog_source(a.topog_source, a.topog_var, a.topog_proj)
+        topo = g.topography(cut, tsrc, refine=a.topog_refine, plane=bool(a.topog_roughness))
         mask = None
         if a.ocean_mask_file:
             mask = g.ocean_mask(cut, topo, **_mask_args(a.mask_min_depth, a.mask_deepen, a.mask_seed, a.mask_keep_cells))
         topo = _write_topog_and_mask(topo, mask, a.topog_file, a.ocean_mask_file)
+        if a.topog_faces_file:   # from the same raster; not edited by the mask
+            _write_topog_faces(g.face_topography(cut, tsrc, refine=a.topog_refine), a.topog_faces_file)
     wet = _xgrid_mask(topo)   # of the topography as written: the wet set of everything below
     if a.coast_distance_file:
         _write_coast_distance(g.coast_distance(cut, wet, sides=a.coast_distance_sides), a.coast_distance_file)
@@ -1195,6 +1201,10 @@ class _StitchedArrays(object):
     def topography(self, cut, source, refine=None, plane=False):
         from . import topography as T
         return T.topography(self.x, self.y, source, refine=refine, plane=plane)
+
+    def face_topography(self, cut, source, refine=None):
+        from . import face_topography as FT
+        return FT.face_topography(self.x, self.y, source, refine=refine)
 
     def ocean_mask(self, cut, topo, **args):
         from . import ocean_mask as M, topography as T
@@ -1300,6 +1310,26 @@ def _write_topog(res, fnam):
         print(line)
     T.write_topog(str(fnam), res)
     return res
+
+
+def _write_topog_faces(res, fnam):
+    from . import face_topography as FT
+    if res is None:   # not rank 0
+        return None
+    for line in FT.summary_lines(res):
+        print(line)
+    FT.write_topog_faces(str(fnam), res)
+    return res
+
+
+def _validate_faces_flags(topog_faces_file, topog_source, topog_proj=None, topog_var=None):
+    if not topog_faces_file:
+        return
+    if topog_source is None:
+        raise ValueError("--topog_faces_file needs --topog_source: the faces are sampled from the topography's raster")
+    if _topog_layered(topog_source, topog_proj, topog_var):
+        from . import face_topography as FT
+        raise ValueError("--topog_faces_file: " + FT.NO_FACES)
 
 
 def _validate_mask_flags(ocean_mask_file, topog_source):
@@ -1645,6 +1675,9 @@ def build_parser():
     parser.add_argument("--topog_roughness", action="store_true",
                         help="also fit a plane to every cell's samples of --topog_source and write the roughness h2 about it, the bottom "
                              "slopes slope_east and slope_north, and plane_flag into --topog_file")
+    parser.add_argument("--topog_faces_file", type=str, required=False, default=None,
+                        help="write the face topography of the model grid (the sill, the shallowest and the mean ridge depth of the "
+                             "grid-following lines across every u and v face) of the one lat-lon --topog_source to this file")
     parser.add_argument("--xgrid_atm", type=int, nargs=2, required=False, default=None, metavar=("NLON", "NLAT"),
                         help="write the atmosphere x ocean exchange grid of a regular global NLON x NLAT atmosphere into --xgrid_file "
                              "(wet cells only when --topog_source is given)")

@@ -1683,6 +1683,20 @@ class Supergrid(object):
             return None
         return CD.coast_distance_dev(xy[0], xy[1], wet, sides=sides, Re=float(self.plan.Re))
 
+    # -- face topography ----------------------------------------------------------------------------------------------
+    def face_topography(self, cut, source, refine=None, oversample=2.0, sea_level=None):
+        """The face topography (face_topography.result on rank 0, None on the other ranks) of the stitched grid from ``source`` (one
+        lat-lon topography.Source or DeviceSource), on rank 0's GPU with the stitched points gathered there, as coast_distance does:
+        the same bits for any number of ranks by construction.  Band-sharded face sampling is not done."""
+        from . import face_topography as FT
+        from . import topography as T
+        if isinstance(source, (T.DeviceSourceList, T.SourceList)) or getattr(getattr(source, "source", source), "projection", None) is not None:
+            raise ValueError(FT.NO_FACES)
+        xy = self.stitched_xy(cut)
+        if xy is None:
+            return None
+        return FT.face_topography_dev(xy[0], xy[1], source, refine=refine, oversample=oversample, sea_level=sea_level)
+
     # -- point location -----------------------------------------------------------------------------------------------
     def locate(self, cut, lon, lat, names=None):
         """The model cells of the stitched grid that hold the points lon, lat (locate.result on rank 0, None on the other ranks), on

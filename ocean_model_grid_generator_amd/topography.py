@@ -9,7 +9,7 @@ in the header): the roughness h2 about that plane and its slope, the resolved bo
 
     python -m ocean_model_grid_generator_amd.topography ocean_hgrid.nc SOURCE [SOURCE ...] -o topog.nc [--var elevation] [--refine R]
         [--oversample F] [--quantum Q] [--sea_level L] [--supergrid_cells] [--roughness] [--json summary.json]
-        [--source_box LON0 DLON LAT0 DLAT] [--source_proj stere:S,lat_ts=-71,lon0=0]
+        [--source_box LON0 DLON LAT0 DLAT] [--source_proj stere:S,lat_ts=-71,lon0=0] [--faces topog_faces.nc]
 
 SOURCE is a NetCDF classic / 64-bit-offset file (a short, float or double variable on uniform 1-D lon / lat coordinates) or a .npy
 array with --source_box (cell edges: lon0 + is * dlon, lat0 + js * dlat, row 0 southmost).
@@ -841,14 +841,29 @@ def main(argv=None):
     p.add_argument("--roughness", action="store_true", help="also fit a plane to every cell's samples: the roughness h2 about it, the "
                                                               "bottom slopes slope_east and slope_north, and plane_flag")
     p.add_argument("--json", default=None, help="write the summary as JSON to this file")
+    p.add_argument("--faces", default=None, metavar="FILE",
+                   help="also write the face topography of the model grid to FILE (face_topography.py: the sill, the shallowest and "
+                        "the mean ridge depth of the lines across every u and v face); one lat-lon source only")
     a = p.parse_args(argv)
+    if a.faces and (len(a.source) > 1 or any(pr not in (None, "latlon") for pr in a.source_proj or [])):   # before any file is read
+        from . import face_topography as FT
+        raise ValueError("--faces: " + FT.NO_FACES)
     src = read_sources(a.source, a.var, a.source_proj, a.source_box, a.quantum)
+    if a.faces and isinstance(src, SourceList):   # the file states a projection
+        from . import face_topography as FT
+        raise ValueError("--faces: " + FT.NO_FACES)
     g = netcdf3.read_doubles(a.grid, names=("x", "y"))
     res = topography(g["x"], g["y"], src, refine=a.refine, oversample=a.oversample, sea_level=a.sea_level,
                      cells="supergrid" if a.supergrid_cells else "model", plane=a.roughness)
     for line in summary_lines(res):
         print(line)
     write_topog(a.output, res)
+    if a.faces:
+        from . import face_topography as FT
+        faces = FT.face_topography(g["x"], g["y"], src, refine=a.refine, oversample=a.oversample, sea_level=a.sea_level)
+        for line in FT.summary_lines(faces):
+            print(line)
+        FT.write_topog_faces(a.faces, faces)
     if a.json:
         with open(a.json, "w") as fh:
             json.dump(res["summary"], fh, indent=1)
@@ -856,5 +871,7 @@ def main(argv=None):
 
 
 if __name__ == "__main__":
-    main()
+    # run as a script this file is the module __main__; the package's modules (face_topography.py) know the classes of the imported one
+    from ocean_model_grid_generator_amd import topography as _module
+    _module.main()
     sys.exit(0)
