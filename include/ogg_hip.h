@@ -771,7 +771,8 @@ int ogg_topog_project_dev(const ogg_topog_projection* proj, long n, const double
 /* ------------------------------------------------------------------------------------------------------
  * Face topography (opt-in; without it every record, output and file above is what it was): what lies BETWEEN two neighbouring model
  * cells, for MOM6's sub-grid topography at velocity points (its "porous barriers" read a lowest, a highest and an average depth on
- * every u and v face).  One lat-lon source (no list, no projected source), integer records only, no connectivity search.  Where this
+ * every u and v face).  One lat-lon source (no list, no projected source), integer records only, no connectivity search ("Sill depths"
+ * below searches: it takes these sills as face weights and gives the depth at which every cell is connected to a seed).  Where this
  * text and "Topography by refined sampling" above could disagree about a sample, that section wins: a face's samples are its samples.
  *   grid      the STITCHED supergrid x, y ((ny + 1) x (nx + 1), row stride ld >= nx + 1), ny and nx even; model cells nym = ny / 2 by
  *             nxm = nx / 2; topology = OGG_MASK_PERIODIC | OGG_MASK_FOLD, the ocean mask's flags
@@ -1637,6 +1638,59 @@ int ogg_basin_codes_dev(const ogg_basin_params* p, const ogg_basin_rule* rules, 
 /* HOST pointers throughout, staged through device memory: x, y (2 ny + 1) x (2 nx + 1) */
 int ogg_basin_codes(const ogg_basin_params* p, const ogg_basin_rule* rules, const double* x, const double* y, const unsigned char* wet,
                     unsigned char* code, short* rule, ogg_basin_rule_record* records, ogg_basin_counts* counts);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Sill depths (an addition: the reference has none).  The deepest connection of every model cell to a set of seed cells: the
+ * widest-path ("bottleneck") depth over integer face weights, the regions of equal sill depth and the gate faces that limit them.  It
+ * answers at what depth a marginal sea is connected to the open ocean on THIS grid, and at which face, without running the ocean mask
+ * at one threshold after another.
+ *   cells     c = j * nx + i of ny x nx model cells, ny * nx < 2^31; topology = OGG_MASK_PERIODIC | OGG_MASK_FOLD
+ *   weights   int32, in quanta, positive down: wu[ny][nx + 1], wu[j][I] between cells (j, I - 1) and (j, I); wv[ny + 1][nx], wv[J][i]
+ *             between cells (J - 1, i) and (J, i): the layout of the face topography's fields.  A weight is read as
+ *             min(max(w, 0), 2^bits - 1), 1 <= bits <= OGG_SILL_MAX_BITS; every face that is read and whose weight that changes is
+ *             counted in n_clamped
+ *   passages  triples (a, b, w): every interior u face and every interior v face; with PERIODIC and nx > 2, (j, nx - 1) ~ (j, 0) with
+ *             w = min(wu[j][0], wu[j][nx]) (with nx <= 2 the seam adds nothing); with FOLD, (ny - 1, i) ~ (ny - 1, nx - 1 - i) for
+ *             i < nx - 1 - i with w = min(wv[ny][i], wv[ny][nx - 1 - i]).  wv[0][*] is never read; without the matching flag wu[*][0],
+ *             wu[*][nx] and wv[ny][*] are never read either, nor is the middle face wv[ny][(nx - 1) / 2] of an odd fold row
+ *   seeds     n_seeds >= 1 cell indices (int64, device memory); an index outside 0 .. ny * nx - 1 is ignored and counted in
+ *             n_bad_seeds; duplicates are allowed
+ *   b         int32 per cell: OGG_SILL_SEED at a seed; elsewhere the maximum over all paths of passages from the cell to any seed of
+ *             the minimum w on the path; 0 when no path has a positive minimum (dry cells and cut-off water)
+ *   region    int32 per cell: -1 where b = 0; the cell's own index at a seed; elsewhere the smallest cell index of the connected
+ *             component of cells joined by a passage with b[a] == b[b] and w >= b[a]
+ *   gates     one byte per face, gate_u[ny][nx + 1] and gate_v[ny + 1][nx]; for a passage (a, b, w), a the west / south / first-named
+ *             cell: 1 if 0 < b[a] == w < b[b] (a is the enclosed side), 2 if 0 < b[b] == w < b[a] (b is), 0 otherwise.  The seam's code is
+ *             written to columns 0 and nx alike; the fold's code at wv[ny][nx - 1 - i] has the roles swapped; faces that are never
+ *             read hold 0.  Every region with 0 < b < OGG_SILL_SEED has at least one gate
+ *   counts    OGG_SILL_COUNT_WORDS int64 words, in this order: rounds (= bits), n_clamped, n_bad_seeds, n_connected (cells with
+ *             0 < b < OGG_SILL_SEED), n_cut_off (cells with b = 0 that have a passage of weight > 0), n_regions (cells with
+ *             region[c] == c, seeds included), n_gate_faces (non-zero gate bytes: a seam gate counts in both of its columns, a fold
+ *             gate at both of its faces)
+ *   parameters  every entry takes the same six scalars first, by value: ny, nx, topology, bits, n_seeds (>= 1) and tile_rows.  No
+ *             struct of this header, as for the face topography and the regional grids: the set of structs and their OGG_ABI_*
+ *             codes stays what it was
+ * b is decided bit by bit from the top, one labelling of the whole plane per bit with the ocean mask's union-find, so a call is
+ * 5 * bits + 7 launches at most whatever a component's diameter, on the caller's stream without a host round trip.  Everything is an
+ * integer: no tile height, launch shape or knob changes a bit.  tile_rows: the rows of a labelling tile, 1 .. 64, or 0 for
+ * OGG_SILL_TILE_ROWS (default 32), read when the call is set up.
+ * Connections go through faces only (right for a C-grid: a diagonal passage does not exist); a channel one cell wide counts as open;
+ * b is relative to the chosen seeds.
+ * ---------------------------------------------------------------------------------------------------- */
+#define OGG_SILL_SEED (1 << 30)
+#define OGG_SILL_MAX_BITS 30
+#define OGG_SILL_COUNT_WORDS 7
+long ogg_sill_workspace_bytes(long ny, long nx);   /* -1 unless ny, nx >= 1 and ny * nx < 2^31 */
+/* the checks of the six scalars: OGG_EARG with the reason, before any device work */
+int ogg_sill_check(long ny, long nx, int topology, int bits, int n_seeds, int tile_rows);
+/* device pointers throughout, on a stream: wu (ny * (nx + 1) int32), wv ((ny + 1) * nx int32), seeds (n_seeds int64), b and region
+ * (ny * nx int32 each), gate_u and gate_v (one byte per face), counts (OGG_SILL_COUNT_WORDS int64) */
+int ogg_sill_depth_dev(long ny, long nx, int topology, int bits, int n_seeds, int tile_rows, const int* wu, const int* wv,
+                       const long long* seeds, void* workspace, long workspace_bytes, int* b, int* region, unsigned char* gate_u,
+                       unsigned char* gate_v, long long* counts, void* stream);
+/* HOST pointers throughout, staged through device memory */
+int ogg_sill_depth(long ny, long nx, int topology, int bits, int n_seeds, int tile_rows, const int* wu, const int* wv,
+                   const long long* seeds, int* b, int* region, unsigned char* gate_u, unsigned char* gate_v, long long* counts);
 
 /* ------------------------------------------------------------------------------------------------------
  * Processor layouts and mask tables (an addition: the reference has none).  For a decomposition of the model cells into px x py

@@ -291,6 +291,12 @@ BASIN_MAX_RULES, BASIN_MAX_PASS_RULES = 4096, 255                      # OGG_BAS
 BASIN_TOOK, BASIN_SEED_LAND, BASIN_SEED_OUTSIDE, BASIN_SEED_CODED, BASIN_SEED_OFF_GRID, BASIN_SEED_INVALID = range(6)   # OGG_BASIN_TOOK ...
 
 
+# the six scalars every ogg_sill_* entry takes first: ny, nx, topology, bits, n_seeds, tile_rows; the counts are int64 words
+SILL_ARGS = [c_long, c_long, c_int, c_int, c_int, c_int]
+SILL_COUNT_FIELDS = ("rounds", "n_clamped", "n_bad_seeds", "n_connected", "n_cut_off", "n_regions", "n_gate_faces")   # OGG_SILL_COUNT_WORDS
+SILL_SEED, SILL_MAX_BITS = 1 << 30, 30                                 # OGG_SILL_SEED, OGG_SILL_MAX_BITS
+
+
 class RegridParams(ctypes.Structure):
     """ogg_regrid_params of include/ogg_hip.h"""
     _fields_ = [("ny", c_long), ("nx", c_long), ("NA", c_long), ("NB", c_long), ("nrec", c_long), ("dtype", c_int), ("n_fill", c_int),
@@ -537,6 +543,10 @@ SIGNATURES = {
                              c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_coast_distance": [ctypes.POINTER(CoastParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            ctypes.POINTER(CoastCounts)],
+    "ogg_sill_check": SILL_ARGS,
+    "ogg_sill_depth_dev": SILL_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p],
+    "ogg_sill_depth": SILL_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_basin_check": [ctypes.POINTER(BasinParams), c_void_p],
     "ogg_basin_plan": [ctypes.POINTER(BasinParams), c_void_p, c_void_p, ctypes.POINTER(c_int)],
     "ogg_basin_codes_dev": [ctypes.POINTER(BasinParams), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long,
@@ -606,6 +616,7 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_regional_workspace_bytes": REGIONAL_ARGS,
                 "ogg_coast_workspace_bytes": [ctypes.POINTER(CoastParams)],
                 "ogg_basin_workspace_bytes": [ctypes.POINTER(BasinParams)],
+                "ogg_sill_workspace_bytes": [c_long, c_long],
                 "ogg_regrid_workspace_bytes": [ctypes.POINTER(RegridParams), c_long],
                 "ogg_layout_workspace_bytes": [ctypes.POINTER(LayoutParams)],
                 "ogg_locate_workspace_bytes": [ctypes.POINTER(LocateParams)]}

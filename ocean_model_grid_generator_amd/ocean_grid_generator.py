@@ -673,7 +673,8 @@ class AnalysisFlags(object):
                     layout_report=None, layout_halo=0, layout_min_block=2, layout_xextent=None, layout_yextent=None,
                     locate_points=None, locate_file="points.nc", locate_mode="bilinear", remap_source_grid=None,
                     remap_source_corners=None, xgrid_curv_grid=None, xgrid_curv_corners=None,
-                    xgrid_curv_file="source_mosaic_tile1Xocean_mosaic_tile1.nc")
+                    xgrid_curv_file="source_mosaic_tile1Xocean_mosaic_tile1.nc", sill_depth_file=None, sill_seed=None,
+                    sill_weights="cells", sill_min_cells=16, sill_report=None)
 
     def __init__(self, **flags):
         unknown = sorted(set(flags) - set(self.DEFAULTS))
@@ -697,6 +698,7 @@ def _validate_all(match_dy, r_dp, lat_dp, skip_metrics, a):
                                   a.basin_codes_file, a.basin_rules)
     _validate_coast_distance_flags(a.coast_distance_file, a.coast_distance_sides, a.topog_source)
     _validate_basin_flags(a.basin_codes_file, a.basin_rules, a.basin_seed_max_km, a.topog_source)
+    _validate_sill_flags(a.sill_depth_file, a.sill_seed, a.sill_weights, a.sill_min_cells, a.sill_report, a.topog_source, a.topog_faces_file)
     _validate_locate_flags(a.locate_points, a.locate_file, a.locate_mode)
     _validate_layout_flags(a)
     _validate_frac_flags(a.xgrid_frac_file, a.xgrid_atm)
@@ -723,7 +725,8 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
          layout_min_block=2, layout_xextent=None, layout_yextent=None, locate_points=None, locate_file="points.nc",
          locate_mode="bilinear", topog_proj=None, remap_source_grid=None, remap_source_corners=None, xgrid_curv_grid=None,
          xgrid_curv_corners=None, xgrid_curv_file="source_mosaic_tile1Xocean_mosaic_tile1.nc", runoff_spread_km=None,
-         runoff_spread_shape="biweight", runoff_spread_by_basin=False, topog_faces_file=None):
+         runoff_spread_shape="biweight", runoff_spread_by_basin=False, topog_faces_file=None, sill_depth_file=None, sill_seed=None,
+         sill_weights="cells", sill_min_cells=16, sill_report=None):
     """Build the supergrid and write it.  Same flags as the reference's main() (OGG:855-1449); the defaults of ``grids`` and
     ``match_dy`` are the argparse defaults (the reference's own function defaults fail its own validation, OGG:870-888).
 
@@ -793,7 +796,13 @@ def main(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=0.0, lon_dp=80.
     within the basin of the mouth, by the codes of ``basin_codes_file``, which must be asked for in the same call); also an addition.
     ``topog_faces_file`` (--topog_faces_file FILE, needs one lat-lon ``topog_source``): the face topography of the model grid
     (face_topography.py: the sill, the shallowest and the mean ridge depth of the grid-following lines across every u and v face,
-    with ``topog_refine``), written to FILE; not edited by ``ocean_mask_file``; also an addition."""
+    with ``topog_refine``), written to FILE; not edited by ``ocean_mask_file``; also an addition.  ``sill_depth_file``
+    (--sill_depth_file FILE, needs ``topog_source``): the sill depth of every wet model cell, the depth of its deepest connection to
+    a seed, with the regions of equal sill depth and their gate faces (sill_depth.py; ``sill_seed``: (lon, lat) pairs, default the
+    deepest wet cell; ``sill_weights``: cells, a face as deep as the shallower of its two cells, or faces, the sills of
+    ``topog_faces_file``, which must be asked for in the same call; ``sill_min_cells``: the smallest region listed as a basin;
+    ``sill_report``: the basin list as JSON; the edited depth and wet set with ``ocean_mask_file``; allowed with ``skip_metrics``,
+    which leaves the areas out), written to FILE; also an addition."""
     flags = dict(locals())   # the arguments, by name: taken before anything else is bound
     import time
 
@@ -1118,11 +1127,11 @@ def main_function_level(inverse_resolution, gridfilename="ocean_hgrid.nc", r_dp=
 
 def _run_analyses(a, g, cut=None):
     """The analyses that follow the grid (``a``: AnalysisFlags), each printed and written as it is done, in their one order: quality
-    report, topography and ocean mask, distance to the coast, basin codes, point location, processor layouts and mask tables, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
+    report, topography and ocean mask, distance to the coast, basin codes, sill depths, point location, processor layouts and mask tables, exchange grid and the fractions of its list, remap, runoff, bilinear.  ``g`` does the work: the
     Supergrid with its ``cut`` (main) or the _StitchedArrays of main_function_level."""
     if a.quality_report:
         _write_quality_report(g.quality(cut), a.quality_report)
-    topo = None
+    topo = faces = None
     if a.topog_source is not None:
         tsrc = _topog_source(a.topog_source, a.topog_var, a.topog_proj)
         topo = g.topography(cut, tsrc, refine=a.topog_refine, plane=bool(a.topog_roughness))
@@ -1131,7 +1140,7 @@ def _run_analyses(a, g, cut=None):
             mask = g.ocean_mask(cut, topo, **_mask_args(a.mask_min_depth, a.mask_deepen, a.mask_seed, a.mask_keep_cells))
         topo = _write_topog_and_mask(topo, mask, a.topog_file, a.ocean_mask_file)
         if a.topog_faces_file:   # from the same raster; not edited by the mask
-            _write_topog_faces(g.face_topography(cut, tsrc, refine=a.topog_refine), a.topog_faces_file)
+            faces = _write_topog_faces(g.face_topography(cut, tsrc, refine=a.topog_refine), a.topog_faces_file)
     wet = _xgrid_mask(topo)   # of the topography as written: the wet set of everything below
     if a.coast_distance_file:
         _write_coast_distance(g.coast_distance(cut, wet, sides=a.coast_distance_sides), a.coast_distance_file)
@@ -1140,6 +1149,10 @@ def _run_analyses(a, g, cut=None):
         from . import basin_codes as BC
         basins = g.basin_codes(cut, wet, BC.read_rules(str(a.basin_rules)), seed_max_km=a.basin_seed_max_km)
         _write_basin_codes(basins, a.basin_codes_file)
+    if a.sill_depth_file:   # the depth as written: edited by the mask when there is one
+        _write_sill_depth(g.sill_depth(cut, topo["depth"], wet, faces=faces if a.sill_weights == "faces" else None,
+                                       seeds=[tuple(s) for s in (a.sill_seed or ())], weights=a.sill_weights,
+                                       min_cells=int(a.sill_min_cells)), a.sill_depth_file, a.sill_report)
     if a.locate_points:
         from . import locate as LOC
         lon, lat, names = LOC.read_points(str(a.locate_points))
@@ -1243,6 +1256,12 @@ class _StitchedArrays(object):
         from . import runoff as RO
         return BC.basin_codes(self.x, self.y, wet, rules, seed_max_distance=None if seed_max_km is None else 1000.0 * seed_max_km,
                               Re=_default_Re, area=None if self.metrics[2] is None else RO.cell_area(self.metrics[2]))
+
+    def sill_depth(self, cut, depth, wet, faces=None, seeds=(), quantum=0.01, weights="cells", min_cells=16):
+        from . import runoff as RO
+        from . import sill_depth as SD
+        return SD.sill_depth(depth, self.x, self.y, wet=wet, faces=faces, seeds=seeds, quantum=quantum, weights=weights,
+                             area=None if self.metrics[2] is None else RO.cell_area(self.metrics[2]), min_cells=min_cells)
 
     def sample(self, cut, lon, lat, field, wet=None, mode="bilinear", fill_values=(), names=None):
         from . import locate as LOC
@@ -1478,6 +1497,35 @@ def _layout_wanted(a):
 def _validate_layout_flags(a):
     from . import layout as LY
     LY.validate_flags(a, a.topog_source)
+
+
+def _validate_sill_flags(sill_depth_file, sill_seed, sill_weights, sill_min_cells, sill_report, topog_source, topog_faces_file):
+    if sill_weights not in ("cells", "faces"):
+        raise ValueError("--sill_weights must be cells or faces, not %r" % (sill_weights,))
+    if not sill_depth_file:
+        if sill_seed or sill_weights != "cells" or sill_min_cells != 16 or sill_report:
+            raise ValueError("--sill_seed, --sill_weights, --sill_min_cells and --sill_report need --sill_depth_file")
+        return
+    if topog_source is None:
+        raise ValueError("--sill_depth_file needs --topog_source: the sill depths are those of the topography's wet cells")
+    if sill_weights == "faces" and not topog_faces_file:
+        raise ValueError("--sill_weights faces needs --topog_faces_file in the same call: the weights are its sills")
+    if not int(sill_min_cells) >= 1:
+        raise ValueError("--sill_min_cells must be >= 1, not %r" % (sill_min_cells,))
+    for s in sill_seed or ():
+        if len(s) != 2 or not (np.isfinite(float(s[0])) and abs(float(s[1])) <= 90.0):
+            raise ValueError("--sill_seed needs a longitude and a latitude in degrees, not %r" % (tuple(s),))
+
+
+def _write_sill_depth(res, fnam, report):
+    if res is None:   # not rank 0
+        return
+    from . import sill_depth as SD
+    for line in SD.summary_lines(res):
+        print(line)
+    SD.write_sill_depth(str(fnam), res)
+    if report:
+        SD.write_report(str(report), res)
 
 
 def _write_basin_codes(res, fnam):
@@ -1739,6 +1787,17 @@ def build_parser():
                         help="the rule file of --basin_codes_file: code seed_lon seed_lat lon_w lon_e lat_s lat_n [name] per line")
     parser.add_argument("--basin_seed_max_km", type=float, required=False, default=None,
                         help="a seed farther than this from every cell centre is off the grid (default: any distance)")
+    parser.add_argument("--sill_depth_file", type=str, required=False, default=None,
+                        help="write the sill depth of every wet model cell of the --topog_source topography (the --ocean_mask_file "
+                             "depth and mask when given): the depth of its deepest connection to a seed, with regions and gates")
+    parser.add_argument("--sill_seed", type=float, nargs=2, action="append", required=False, default=None, metavar=("LON", "LAT"),
+                        help="a point in the open ocean (repeatable); default: the deepest wet cell")
+    parser.add_argument("--sill_weights", type=str, choices=["cells", "faces"], required=False, default="cells",
+                        help="cells (default): a face is as deep as the shallower of its two cells; faces: the sills of "
+                             "--topog_faces_file, which must be given in the same call")
+    parser.add_argument("--sill_min_cells", type=int, required=False, default=16,
+                        help="regions of equal sill depth smaller than this are not listed as basins (default 16)")
+    parser.add_argument("--sill_report", type=str, required=False, default=None, help="write the basin list as JSON to this file")
     parser.add_argument("--locate_points", type=str, required=False, default=None,
                         help="a file of points (`lon lat [name]` per line, # starts a comment; or NetCDF with 1-D lon and lat): write "
                              "the model cell that holds each, its position in the cell and, with --topog_source, the depth there")

@@ -1728,6 +1728,23 @@ class Supergrid(object):
         return BC.basin_codes_dev(xy[0], xy[1], wet, rules, seed_max_distance=None if seed_max_km is None else 1000.0 * seed_max_km,
                                   Re=float(self.plan.Re), area=None if area is None else RO.cell_area(area.cpu().numpy()))
 
+    # -- sill depths --------------------------------------------------------------------------------------------------
+    def sill_depth(self, cut, depth, wet, faces=None, seeds=(), quantum=0.01, weights="cells", min_cells=16):
+        """The sill depths (sill_depth.result on rank 0, None on the other ranks) of the model cells of the stitched grid with the cell
+        depths ``depth`` and the wet set ``wet`` (one value per model cell each), on rank 0's GPU with the stitched points gathered
+        there, as basin_codes does: integers of the gathered plane, so the same bits for any number of ranks.  ``faces``: rank 0's
+        face_topography result, for weights='faces'.  The basins' areas come from the stitched area unless the plan skips the
+        metrics.  Band-sharded search is not done."""
+        from . import runoff as RO
+        from . import sill_depth as SD
+        xy = self.stitched_xy(cut)
+        area = None if self.plan.skip_metrics else self.stitched_area(cut)
+        if xy is None:
+            return None
+        d = self.torch.from_numpy(np.ascontiguousarray(depth.cpu().numpy() if hasattr(depth, "cpu") else depth, dtype=np.float64))
+        return SD.sill_depth_dev(d.to(self.device), xy[0], xy[1], wet=wet, faces=faces, seeds=seeds, quantum=quantum, weights=weights,
+                                 area=None if area is None else RO.cell_area(area.cpu().numpy()), min_cells=min_cells)
+
     # -- processor layouts and mask tables ----------------------------------------------------------------------------
     def _layout_table(self, cut, wet, halo):
         """The layout.DeviceTable of the wet set ``wet`` (one value per model cell, 0: land) on rank 0's GPU, None on the other ranks:
