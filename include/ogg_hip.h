@@ -1958,6 +1958,55 @@ int ogg_regional_band_dev(long nx, long ny, double lon_c, double lat_c, double t
 int ogg_regional_grid(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int kind, int metrics,
                       double* x, double* y, double* dx, double* dy, double* area, double* angle_dx);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Stereographic regional grids (an addition, as "Regional grids"): the oblique stereographic projection about the domain centre, the
+ * conformal lattice for pan-Arctic and circum-Antarctic domains and every shelf domain that reaches a pole.  The domain MAY hold a
+ * geographic pole -- as a mesh point (the centre of a grid with lat_c = +-90 only), as a cell corner or inside a cell.  Not periodic,
+ * at most a hemisphere.
+ *   frame    the rotation triple of "Regional grids", relative to the centre meridian: with cl, sl of lat_c and ct, st of tilt
+ *              q1 = (cl, 0, sl) the centre,  q2 = (-sl st, ct, cl st) the grid's x direction at the centre,  q3 = (-sl ct, -st, cl ct).
+ *   plane    d = delta pi/180;  X_i = (i - nx/2) d,  Y_j = (j - ny/2) d  in units of Re: delta is degrees per supergrid step AT THE
+ *            CENTRE, where the scale is true.  nx by ny supergrid cells, both even; points j = 0 .. ny, i = 0 .. nx.
+ *   points   rho2 = X^2 + Y^2,  m = 1 + rho2/4,  p = (X q2 + Y q3 + (1 - rho2/4) q1) / m: a unit vector, no sine or cosine per point.
+ *            x = lon_c + atan2(p_y, p_x) in degrees,  y = atan2(p_z, sqrt(p_x^2 + p_y^2)) in degrees, as for the other kinds.
+ *   angle_dx the grid's x direction at p is parallel to t = q2 - (X/2) (q1 + p);  angle_dx = atan2(t_z, p_x t_y - p_y t_x) in degrees:
+ *            analytic, as for the other kinds.  (m t = (1 + (Y^2 - X^2)/4) q2 - X q1 - (X Y/2) q3, and m^2 (p_x t_y - p_y t_x) is m
+ *            times the z component of (1 + (X^2 - Y^2)/4) q3 - Y q1 - (X Y/2) q2: the device evaluates these two.)
+ *   metrics  exact on the sphere; the physical length is Re times the plane length over m, and the grid lines are circles:
+ *              dx(j, i)   = Re (4/a) atan(a d / (a^2 + X_i X_{i+1})),  a = sqrt(4 + Y_j^2)                     (ny+1) x nx
+ *              dy(j, i)   = Re (4/b) atan(b d / (b^2 + Y_j Y_{j+1})),  b = sqrt(4 + X_i^2)                     ny x (nx+1)
+ *              area(j, i) = Re^2 [(Y_{j+1} dxh(j+1, i) - Y_j dxh(j, i)) + (X_{i+1} dyh(j, i+1) - X_i dyh(j, i))] / 2   ny x nx
+ *            with dxh = dx/Re, dyh = dy/Re: Gauss-Bonnet for four circular edges of geodesic curvature Y_j/2, -X_{i+1}/2, -Y_{j+1}/2,
+ *            X_i/2 that meet at right angles.  The area is a difference of neighbouring terms and loses eps |Y| / d when evaluated
+ *            literally; the device takes each difference apart so that none is left (csrc/ogg_regional_stereo.hip, "area").
+ *            The whole domain, A = (nx/2) d, B = (ny/2) d, a = sqrt(4 + B^2), b = sqrt(4 + A^2), has the area
+ *              8 Re^2 [(B/a) atan(A/a) + (A/b) atan(B/b)],  which tends to 4 pi Re^2 as the domain grows.
+ *   poles    x has its jump of 360 degrees on the meridian opposite lon_c BEYOND a pole of the domain: the cells across that half
+ *            meridian have corners a turn apart (the file-based analyses unwrap each cell's corners on their own turn).  With lat_c =
+ *            +-90 EXACTLY the centre point is the pole, p_x = p_y = 0, and has by definition x = lon_c, y = lat_c, angle_dx = tilt,
+ *            the limit along the meridian lon_c: no bit depends on the sign of a zero.  (The device takes cl = 0 there, not the cosine
+ *            of pi/2 rounded.)
+ *   refused  with OGG_EARG and the reason, before any device work: nx or ny odd, below 2 or above 2^22; delta or Re not positive; an
+ *            argument that is not finite, lon_c or tilt above 1e6 in magnitude, |lat_c| > 90; a corner farther than 90 degrees from the
+ *            centre, d sqrt((nx/2)^2 + (ny/2)^2) > 2; a mesh point other than that exact centre within 1e-9 degrees of a pole (the
+ *            north pole lies at 2 (q2_z, q3_z) / (1 + q1_z) in the plane, the south pole at -2 (q2_z, q3_z) / (1 - q1_z)).
+ * Every value is a function of (j, i) and the parameters alone: no launch geometry and no split into bands changes a bit.
+ * The entries take the scalars of "Regional grids" without kind: nx, ny, lon_c, lat_c, tilt, delta, Re, metrics; the workspace holds a
+ * column and a row table, filled by ogg_regional_stereo_tables_dev and read by every band of the same parameters; the arrays of
+ * ogg_regional_stereo_band_dev begin at the band's first row and have the extents of ogg_regional_band_dev.
+ * ---------------------------------------------------------------------------------------------------- */
+int ogg_regional_stereo_check(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int metrics);
+/* -1 on bad parameters */
+long ogg_regional_stereo_workspace_bytes(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int metrics);
+int ogg_regional_stereo_tables_dev(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int metrics,
+                                   void* workspace, long workspace_bytes, void* stream);
+int ogg_regional_stereo_band_dev(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int metrics, long j0,
+                                 long nrows, const void* workspace, long workspace_bytes, double* x, double* y, double* dx, double* dy,
+                                 double* area, double* angle_dx, void* stream);
+/* HOST pointers, staged through device memory: the whole grid; with metrics == 0 only x and y */
+int ogg_regional_stereo_grid(long nx, long ny, double lon_c, double lat_c, double tilt, double delta, double Re, int metrics, double* x,
+                             double* y, double* dx, double* dy, double* area, double* angle_dx);
+
 /* per-launch timing of the dominant kernels with HIP events on the given stream: start/stop bracket */
 int ogg_event_create(void** ev);
 int ogg_event_destroy(void* ev);

@@ -248,7 +248,8 @@ SPREAD_MAX_CUBES, SPREAD_MAX_PAIRS = 64, 1 << 30                       # OGG_SPR
 
 # the nine scalars every ogg_regional_* entry takes first: nx, ny, lon_c, lat_c, tilt, delta, Re, kind, metrics
 REGIONAL_ARGS = [c_long, c_long, c_double, c_double, c_double, c_double, c_double, c_int, c_int]
-REGIONAL_LATLON, REGIONAL_MERCATOR = 0, 1                              # OGG_REGIONAL_LATLON, OGG_REGIONAL_MERCATOR
+REGIONAL_STEREO_ARGS = REGIONAL_ARGS[:7] + [c_int]                     # the ogg_regional_stereo_* entries: the same without kind
+REGIONAL_LATLON, REGIONAL_MERCATOR = 0, 1                             # OGG_REGIONAL_LATLON, OGG_REGIONAL_MERCATOR
 REGIONAL_MAX_CELLS = 1 << 22                                           # OGG_REGIONAL_MAX_CELLS
 
 
@@ -536,6 +537,11 @@ SIGNATURES = {
     "ogg_regional_band_dev": REGIONAL_ARGS + [c_long, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_void_p],
     "ogg_regional_grid": REGIONAL_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "ogg_regional_stereo_check": REGIONAL_STEREO_ARGS,
+    "ogg_regional_stereo_tables_dev": REGIONAL_STEREO_ARGS + [c_void_p, c_long, c_void_p],
+    "ogg_regional_stereo_band_dev": REGIONAL_STEREO_ARGS + [c_long, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                            c_void_p, c_void_p],
+    "ogg_regional_stereo_grid": REGIONAL_STEREO_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "ogg_coast_check": [ctypes.POINTER(CoastParams)],
     "ogg_coast_sets_dev": [ctypes.POINTER(CoastParams), c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
@@ -614,6 +620,7 @@ LONG_GETTERS = {"ogg_abi_sizeof": [c_int],
                 "ogg_runoff_workspace_bytes": [ctypes.POINTER(RunoffParams)],
                 "ogg_spread_workspace_bytes": [ctypes.POINTER(SpreadParams), c_long],
                 "ogg_regional_workspace_bytes": REGIONAL_ARGS,
+                "ogg_regional_stereo_workspace_bytes": REGIONAL_STEREO_ARGS,
                 "ogg_coast_workspace_bytes": [ctypes.POINTER(CoastParams)],
                 "ogg_basin_workspace_bytes": [ctypes.POINTER(BasinParams)],
                 "ogg_sill_workspace_bytes": [c_long, c_long],

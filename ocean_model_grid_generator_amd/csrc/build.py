@@ -10,7 +10,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["ogg_api.hip", "ogg_axes.hip", "ogg_midas.hip", "ogg_bipolar.hip", "ogg_dpole.hip", "ogg_elementwise.hip", "ogg_latlon_fused.hip", "ogg_pass.hip", "ogg_reduce.hip", "ogg_quality.hip", "ogg_topog.hip", "ogg_xgrid.hip", "ogg_xgrid_cs.hip", "ogg_xgrid_curv.hip", "ogg_mask.hip", "ogg_remap.hip", "ogg_runoff.hip", "ogg_spread.hip", "ogg_regional.hip", "ogg_coast.hip", "ogg_basin.hip", "ogg_sill.hip", "ogg_regrid.hip", "ogg_bilinear.hip", "ogg_layout.hip", "ogg_locate.hip"]
+SOURCES = ["ogg_api.hip", "ogg_axes.hip", "ogg_midas.hip", "ogg_bipolar.hip", "ogg_dpole.hip", "ogg_elementwise.hip", "ogg_latlon_fused.hip", "ogg_pass.hip", "ogg_reduce.hip", "ogg_quality.hip", "ogg_topog.hip", "ogg_xgrid.hip", "ogg_xgrid_cs.hip", "ogg_xgrid_curv.hip", "ogg_mask.hip", "ogg_remap.hip", "ogg_runoff.hip", "ogg_spread.hip", "ogg_regional.hip", "ogg_regional_stereo.hip", "ogg_coast.hip", "ogg_basin.hip", "ogg_sill.hip", "ogg_regrid.hip", "ogg_bilinear.hip", "ogg_layout.hip", "ogg_locate.hip"]
 HEADERS = ["ogg_common.h", "ogg_math.h", "ogg_keysort.h", "ogg_blocks.h", "ogg_sphere.h", "ogg_sphere_bins.h", "ogg_box_index.h", "ogg_cells.h", "ogg_label.h", "ogg_clip.h","ogg_bipolar_dev.h", "ogg_dpole_dev.h", "ogg_latlon_fused_dev.h", "../../include/ogg_hip.h"]
 LIB = os.path.join(HERE, "libogg_hip.so")
 HASH_FILE = os.path.join(HERE, "libogg_hip.srchash")   # source hash of the library next to it (a built artefact, git-ignored like the .so)

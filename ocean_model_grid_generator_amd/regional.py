@@ -8,7 +8,8 @@ counter-clockwise from east.  The supergrid has nx by ny cells, both even, of ``
 "latlon" (equal steps of the rotated latitude) or "mercator" (isotropic cells: an oblique Mercator).  The metrics are analytic and
 exact on the sphere.  Two kernels (ogg_regional_tables_dev, ogg_regional_band_dev): a small one for a column and a row table, and
 the write-bound one over a band of rows; no band split changes a bit.  The file has the layout of the tripolar main(), so every
-file-based analysis command reads it unchanged.
+file-based analysis command reads it unchanged.  Both kinds refuse a domain that holds a geographic pole; the stereographic kind
+(regional_stereo.py, a command of its own, to which ``--kind stereographic`` forwards) admits one.
 
     python -m ocean_model_grid_generator_amd.regional --lon_c LON --lat_c LAT [--tilt DEG] -r INV_RES
         (--cells NI NJ | --extent_km LX LY) [--kind latlon|mercator] [-f ocean_hgrid.nc] [--no_changing_meta] [--skip_metrics]
@@ -166,7 +167,22 @@ def summary_lines(s):
     return out
 
 
+def _without_kind(argv, kind):
+    """argv without ``--kind <kind>`` / ``--kind=<kind>``, or None when it does not ask for that kind"""
+    for k, a in enumerate(argv):
+        if a == "--kind" and argv[k + 1:k + 2] == [kind]:
+            return argv[:k] + argv[k + 2:]
+        if a == "--kind=" + kind:
+            return argv[:k] + argv[k + 1:]
+    return None
+
+
 def main(argv=None):
+    # the stereographic kind is a command of its own (regional_stereo: another lattice, other entries); --kind stereographic forwards
+    rest = _without_kind(list(sys.argv[1:] if argv is None else argv), "stereographic")
+    if rest is not None:
+        from . import regional_stereo
+        return regional_stereo.main(rest)
     ap = argparse.ArgumentParser(prog="python -m ocean_model_grid_generator_amd.regional",
                                  description="a regional supergrid on a rotated pole, in the file layout of the tripolar grid")
     ap.add_argument("--lon_c", type=float, required=True, help="longitude of the domain centre, degrees")
@@ -178,7 +194,8 @@ def main(argv=None):
     g.add_argument("--cells", type=int, nargs=2, metavar=("NI", "NJ"), help="model cells along x and y")
     g.add_argument("--extent_km", type=float, nargs=2, metavar=("LX", "LY"),
                    help="extent along the rotated equator and the centre meridian, rounded up to whole model cells")
-    ap.add_argument("--kind", choices=sorted(KINDS), default="mercator")
+    ap.add_argument("--kind", choices=sorted(KINDS), default="mercator",
+                    help="(--kind stereographic is the command regional_stereo, which may hold a pole)")
     ap.add_argument("-f", "--gridfilename", default="ocean_hgrid.nc")
     ap.add_argument("--no_changing_meta", action="store_true", help="do not write meta data that might change from run to run")
     ap.add_argument("--skip_metrics", action="store_true", help="x and y only: dx, dy, area are written as -1 and angle_dx as 0")
