@@ -10,7 +10,13 @@
  *   - entry points WITHOUT the _dev suffix take HOST pointers (caller-allocated, caller-owned; the library
  *     stages through device memory it allocates and frees inside the call);
  *   - entry points WITH the _dev suffix take DEVICE pointers and a hipStream_t (passed as void*), enqueue
- *     work and return without synchronising; no allocation, no host sync (graph-capturable);
+ *     work on that stream alone and return without synchronising; no allocation, no host sync (graph-capturable).
+ *     The exceptions, each with "Waits for the stream" in its own comment (tests/test_gpu_streams.py holds every
+ *     other entry to the rule on a side stream, tests/test_stream_contract_cpu.py holds this list to its table):
+ *       ogg_workspace_error_flag_dev, ogg_supergrid_pass_plan_flags_dev, ogg_supergrid_pass_dev,
+ *       ogg_tripolar_pass_dev, ogg_remap_fill_dev, ogg_spread_sets_dev, ogg_layout_blocks_dev;
+ *     and the displaced-pole entries when they are given no workspace (workspace = NULL: see their comments).
+ *     ogg_supergrid_pass_plan_dev takes no stream: it allocates and waits for the device;
  *   - every function returns OGG_OK or an error code; ogg_last_error() gives the text (thread-local);
  *   - no C++ exception crosses this boundary; calls may come from any thread, one call at a time per stream.
  */
@@ -303,7 +309,7 @@ int ogg_displaced_pole_grid_angle_ws_dev(long Ni, long Nj, double lon0, double l
                                          long nrows, double* x, double* y, double* angle_dx, void* workspace,
                                          long workspace_bytes, void* stream);
 /* Error flag of a workspace used by a displaced-pole call (*flag != 0: a look-back wait gave up, the results of that call are
- * invalid; never observed, the spin is bounded so that a grid always drains).  Synchronises the stream. */
+ * invalid; never observed, the spin is bounded so that a grid always drains).  Waits for the stream: the flag is read on the host. */
 int ogg_workspace_error_flag_dev(const void* workspace, int* flag, void* stream);
 
 /* numerical_hi / numerical_hj (OGG:535-562; great_arc_distance OGG:522-532) on the lattice j[n_j] x i[n_i].
@@ -395,11 +401,13 @@ int ogg_symmetry_coverage(int which, int order, long n, double lon0, double lon_
  *   metrics         0 writes coordinates and angle_dx only
  *   events5         NULL, or 5 events from ogg_event_create (entries may be NULL), recorded on the stream before A and after A, B, C, D,
  *                   so that the caller can time the launches (ogg_event_elapsed_ms)
- *   alg_bytes4      NULL, or 4 doubles on the host: the bytes each launch writes (its share of the 48 B per cell) */
+ *   alg_bytes4      NULL, or 4 doubles on the host: the bytes each launch writes (its share of the 48 B per cell)
+ * Waits for the stream: the call is plan + run + destroy (below), and the destroy waits for the run before it frees the plan's own
+ * workspaces.  A caller that must not wait keeps a plan (ogg_supergrid_pass_plan_dev, ogg_supergrid_pass_run_dev). */
 int ogg_supergrid_pass_dev(int n_latlon, const ogg_latlon_band* latlon, long ni1, double lon0, double lenlon, double Re, int metrics,
                            const ogg_bipolar_band* cap, const ogg_dpole_band* south_cap, void** events5, double* alg_bytes4,
                            void* stream);
-/* the pass without a southern cap: ogg_supergrid_pass_dev with south_cap, events5 and alg_bytes4 NULL */
+/* the pass without a southern cap: ogg_supergrid_pass_dev with south_cap, events5 and alg_bytes4 NULL.  Waits for the stream, as it does. */
 int ogg_tripolar_pass_dev(int n_latlon, const ogg_latlon_band* latlon, long ni1, double lon0, double lenlon, double Re,
                           int metrics, const ogg_bipolar_band* cap, void* stream);
 /* ogg_supergrid_pass_dev in two steps, for a caller that runs the pass of one set of bands many times (a rank's step loop): the plan holds the kernel
@@ -429,7 +437,7 @@ int ogg_supergrid_pass_run_dev(void* plan, void** events5, double* alg_bytes4, v
 int ogg_supergrid_pass_plan_destroy(void* plan);
 long ogg_supergrid_pass_plan_slots(const void* plan);          /* workspace slots of the plan: 2, or 1 (every pass runs its own launch A) */
 long ogg_supergrid_pass_plan_carried_runs(const void* plan);   /* runs so far that started with launch B */
-/* Waits for `stream`, then *flags = bit 1 / bit 2: a look-back wait of the displaced-pole mesh / quadrature timed out, in either slot, in
+/* Waits for the stream, then *flags = bit 1 / bit 2: a look-back wait of the displaced-pole mesh / quadrature timed out, in either slot, in
  * a pass since the slot's words were last cleared.  Results of such a pass are invalid; never observed. */
 int ogg_supergrid_pass_plan_flags_dev(const void* plan, int* flags, void* stream);
 
@@ -1194,7 +1202,8 @@ int ogg_remap_dev(const ogg_remap_params* p, const void* f, const int* atm_ij, c
                   const unsigned char* mask, const void* workspace, long workspace_bytes, double* values, unsigned char* flags,
                   ogg_remap_counts* counts, void* stream);
 /* fill step on the remap step's values and flags of the whole grid (m0 = 0): front by front, one launch per front for all records;
- * the host reads the frontier length every few fronts.  Updates filled, unfilled, max_distance, fronts and launches in *counts. */
+ * the host reads the frontier length every few fronts.  Updates filled, unfilled, max_distance, fronts and launches in *counts.
+ * Waits for the stream: every OGG_REMAP_FRONTS_PER_READ fronts, to read the queue's head and stop when the front is empty. */
 int ogg_remap_fill_dev(const ogg_remap_params* p, void* workspace, long workspace_bytes, double* values, unsigned char* flags,
                        ogg_remap_counts* counts, void* stream);
 /* HOST pointers throughout, staged through device memory: the three steps (the fill when do_fill != 0) on the list atm_ij / ocn_ij /
@@ -1777,7 +1786,8 @@ int ogg_layout_sweep_dev(const ogg_layout_params* p, const ogg_layout_candidate*
                          long workspace_bytes, ogg_layout_record* records, void* stream);
 /* after ogg_layout_table_dev on the same workspace: wet(a, b) and nbr(a, b) of every block of one layout (device memory, py x px
  * int32 each).  xbegin, ybegin: HOST memory, NULL for the rule's extents, else the px (py) first columns (rows) of the blocks,
- * strictly increasing from 0 and below nx (ny); px, py <= OGG_LAYOUT_MAX_DIV. */
+ * strictly increasing from 0 and below nx (ny); px, py <= OGG_LAYOUT_MAX_DIV.  Waits for the stream: the block begins are copied to the
+ * device from memory of the call's own, before the one launch that reads them. */
 int ogg_layout_blocks_dev(const ogg_layout_params* p, int px, int py, const int* xbegin, const int* ybegin, void* workspace,
                           long workspace_bytes, int* block_wet, int* block_nbr, void* stream);
 /* HOST pointers throughout, staged through device memory: the table, then the records of the n candidates (records NULL with n = 0),

@@ -246,6 +246,9 @@ __global__ __launch_bounds__(NT) void brute_kernel(const int* __restrict__ cell,
     block_add<1>(v, dst);
 }
 
+// the cubes per axis the host chose, into the counts: one thread, in the stream's order
+__global__ void bins_kernel(ogg_runoff_counts* __restrict__ counts, long long G) { counts->bins = G; }
+
 // ---- segments ------------------------------------------------------------------------------------------------------
 // keys of NT consecutive sources sorted in LDS by rank (the keys are unique)
 __global__ __launch_bounds__(NT) void sort_block_kernel(const int* __restrict__ tgt, long n, unsigned long long* __restrict__ out) {
@@ -496,8 +499,8 @@ extern "C" int ogg_runoff_search_dev(const ogg_runoff_params* p, const int* tgt_
     const Layout l = layout(*p);
     long long G = 0;
     if (!brute) G = bins > 0 ? bins : std::min<long>(std::max<long>((long)ceil(sqrt((double)n_targets / 24.0)), 1), OGG_RUNOFF_MAX_BINS);
-    OGG_HIP_CHECK(hipMemcpyAsync(&counts->bins, &G, sizeof(G), hipMemcpyHostToDevice, st));
-    OGG_HIP_CHECK(hipStreamSynchronize(st));   // G lives on this frame
+    bins_kernel<<<1, 1, 0, st>>>(counts, G);   // G as a kernel argument: no copy from this frame, so no wait for the stream
+    OGG_LAUNCH_CHECK();
     if (n_mapped == 0) return OGG_OK;
     if (brute) {
         brute_kernel<<<(unsigned)((n_mapped + NT - 1) / NT), NT, 0, st>>>(tgt_cell, tgt_u, n_targets, src_u, n_mapped, src_target, src_d2,

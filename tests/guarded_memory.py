@@ -9,7 +9,9 @@ Under ``guarded`` every such allocation is an exact-size view into one Arena:
   rounded up), and at least ``guard`` bytes of pattern lie on either side;
 * memory is bumped and never reused until the next reset(), so a late write to a tensor that was dropped still lands in the arena;
 * reset("ff") makes every byte 0xFF (doubles and floats read as NaN, int32 as -1, flag bytes as 255), reset(("random", seed)) makes
-  them seeded random bytes: a result that depends on what its torch.empty memory held differs between the two;
+  them seeded random bytes: a result that depends on what its torch.empty memory held differs between the two; reset("00") makes every
+  byte 0 (tests/test_gpu_streams.py: a step that runs before the step it depends on reads counts and indices of 0, never an address
+  out of range);
 * check() lists every changed guard byte with the tensor it belongs to.
 
 The guard is 64 KiB on each side: a condition, not a measurement.  It covers one whole extra row of the widest small input used in
@@ -78,10 +80,10 @@ class Arena(object):
         self.reset("ff")
 
     def reset(self, pattern="ff"):
-        """Refill: "ff" (every byte 0xFF) or ("random", seed) (seeded random bytes); everything handed out before is forgotten.  (The
-        pattern is laid down as take() advances, _fill_to: the first block now.)"""
-        if pattern != "ff" and not (isinstance(pattern, tuple) and len(pattern) == 2 and pattern[0] == "random"):
-            raise ValueError("pattern: 'ff' or ('random', seed), not %r" % (pattern,))
+        """Refill: "ff" (every byte 0xFF), "00" (every byte 0) or ("random", seed) (seeded random bytes); everything handed out before
+        is forgotten.  (The pattern is laid down as take() advances, _fill_to: the first block now.)"""
+        if pattern not in ("ff", "00") and not (isinstance(pattern, tuple) and len(pattern) == 2 and pattern[0] == "random"):
+            raise ValueError("pattern: 'ff', '00' or ('random', seed), not %r" % (pattern,))
         self.pattern = pattern
         self.records = []            # (owner, start, end, row bytes, stride bytes): the tensor is buf[start:end], padding included
         self._cursor = self._handed = self._filled = 0
@@ -93,8 +95,8 @@ class Arena(object):
         while self._filled < min(top, self.nbytes):
             lo = self._filled
             hi = min(lo + BLOCK, self.nbytes)
-            if self.pattern == "ff":
-                self.buf[lo:hi].fill_(0xFF)
+            if self.pattern in ("ff", "00"):
+                self.buf[lo:hi].fill_(0xFF if self.pattern == "ff" else 0)
             else:
                 g = torch.Generator(device=self.device).manual_seed(int(self.pattern[1]) * 1000003 + lo // BLOCK)
                 self.buf[lo:hi].random_(0, 256, generator=g)

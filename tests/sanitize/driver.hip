@@ -13,6 +13,8 @@
 
 extern "C" long fake_hip_launches(void);
 extern "C" long fake_hip_copies(void);
+extern "C" long fake_hip_stream_ops(void* stream, int kind);   // 0 launches, 1 asynchronous copies, 2 asynchronous memsets, 3 event records
+extern "C" long fake_hip_sync_calls(int kind);                 // 0 hipMemcpy, 1 hipMemset, 2 hipDeviceSynchronize
 
 namespace {
 
@@ -25,6 +27,30 @@ int g_fail = 0;
             fprintf(stderr, "\n");                               \
             g_fail += 1;                                         \
         }                                                        \
+    } while (0)
+
+// What a device entry that is given a stream of its own must leave alone: the null stream's calls of every kind and the process's
+// synchronous copies, memsets and device-wide waits.  after - before must be all zero across such a call.
+struct OffStream {
+    long v[7];
+    OffStream() {
+        for (int k = 0; k < 4; ++k) v[k] = fake_hip_stream_ops(nullptr, k);
+        for (int k = 0; k < 3; ++k) v[4 + k] = fake_hip_sync_calls(k);
+    }
+    bool operator==(const OffStream& o) const { return memcmp(v, o.v, sizeof v) == 0; }
+};
+const char* const OFF_STREAM_NAMES = "null-stream launches / copies / memsets / records, hipMemcpy, hipMemset, hipDeviceSynchronize";
+hipStream_t own_stream() {
+    static hipStream_t s = nullptr;
+    if (!s && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) s = nullptr;
+    return s;
+}
+#define CHECK_ON_STREAM(before, what)                                                                                                        \
+    do {                                                                                                                                     \
+        const OffStream after_;                                                                                                              \
+        CHECK(after_ == (before), "%s left its stream (%s): %ld %ld %ld %ld %ld %ld %ld", what, OFF_STREAM_NAMES, after_.v[0] - (before).v[0], \
+              after_.v[1] - (before).v[1], after_.v[2] - (before).v[2], after_.v[3] - (before).v[3], after_.v[4] - (before).v[4],             \
+              after_.v[5] - (before).v[5], after_.v[6] - (before).v[6]);                                                                     \
     } while (0)
 
 bool inside(const void* p, size_t bytes, const void* ws, size_t ws_bytes) {
@@ -235,9 +261,13 @@ void check_pass_plan(double r, bool displaced, int world, int rank, int symmetry
     // the launch sizes add up to the roles' workgroups, and running the plan issues exactly its launches
     CHECK(P.nb == (unsigned)(P.B.share.n_wg + P.B.n_mesh + P.B.n_dmesh + P.B.n_guard + P.B.n_fast + P.B.n_dquad + P.B.share.n_help) || !P.launch_b,
           "launch B: %u workgroups", P.nb);
-    const long before = fake_hip_launches();
-    CHECK(run_pass_plan_any(P, nullptr, nullptr, nullptr) == OGG_OK, "run_pass_plan_any: %s", ogg_last_error());
+    const long before = fake_hip_launches(), on_stream = fake_hip_stream_ops(own_stream(), 0);
+    const OffStream off;
+    CHECK(run_pass_plan_any(P, nullptr, nullptr, own_stream()) == OGG_OK, "run_pass_plan_any: %s", ogg_last_error());
+    CHECK_ON_STREAM(off, "run_pass_plan_any");
     const long launched = fake_hip_launches() - before;
+    CHECK(fake_hip_stream_ops(own_stream(), 0) - on_stream == launched, "%ld of a pass's %ld launches went to its stream",
+          fake_hip_stream_ops(own_stream(), 0) - on_stream, launched);
     CHECK(launched == (P.na > 0) + (P.launch_b ? 1 : 0) + ((P.have_quad && (P.qp.has_guard || (P.qp.p.top_src && P.qp.has_top))) ? 1 : 0) + (P.dq_literal ? 1 : 0),
           "a pass issued %ld launches", launched);
 }
@@ -281,10 +311,22 @@ void plan_handle_life_cycle() {
             }
             CHECK(H.slot[0].B.ll.row_tab != H.slot[1].B.ll.row_tab || !want, "the two slots share a row table");
         }
-        for (int k = 0; k < 5; ++k) CHECK(ogg_supergrid_pass_run_dev(h, nullptr, nullptr, nullptr) == OGG_OK, "run %d", k);
+        {
+            const OffStream off;
+            const long on_stream = fake_hip_stream_ops(own_stream(), 0);
+            for (int k = 0; k < 5; ++k) CHECK(ogg_supergrid_pass_run_dev(h, nullptr, nullptr, own_stream()) == OGG_OK, "run %d", k);
+            CHECK_ON_STREAM(off, "ogg_supergrid_pass_run_dev");
+            CHECK(fake_hip_stream_ops(own_stream(), 0) - on_stream >= 5, "five passes, %ld launches on their stream", fake_hip_stream_ops(own_stream(), 0) - on_stream);
+        }
         CHECK(ogg_supergrid_pass_plan_carried_runs(h) == 4, "carried runs %ld", ogg_supergrid_pass_plan_carried_runs(h));
         int flags = -1;
-        CHECK(ogg_supergrid_pass_plan_flags_dev(h, &flags, nullptr) == OGG_OK && flags == 0, "flags");
+        {   // waits for its stream by contract and reads the words with hipMemcpy: no launch, no device-wide wait, nothing on the null stream
+            const OffStream off;
+            CHECK(ogg_supergrid_pass_plan_flags_dev(h, &flags, own_stream()) == OGG_OK && flags == 0, "flags");
+            OffStream after;
+            after.v[4] = off.v[4];   // (its hipMemcpy calls are the contract)
+            CHECK(after == off, "ogg_supergrid_pass_plan_flags_dev left its stream");
+        }
         CHECK(ogg_supergrid_pass_plan_destroy(h) == OGG_OK, "destroy");
     }
     // a workspace that is too small is refused with a message, not overrun
@@ -292,6 +334,29 @@ void plan_handle_life_cycle() {
     void* h = nullptr;
     CHECK(ogg_supergrid_pass_plan_dev(1, &ll, ni1, -300.0, 360.0, 6371e3, 1, &cap, nullptr, &h) == OGG_EARG && !h && strstr(ogg_last_error(), "workspace too small"),
           "small workspace: %s", ogg_last_error());
+}
+
+// two more device entries of the linked translation units on a stream of their own: an elementwise launch, and the error flag of a
+// workspace, which copies one word on its stream and waits for that stream (its contract) -- neither touches the null stream
+void on_a_stream_of_their_own() {
+    std::vector<double> out(1000, 0.0);
+    std::vector<unsigned> ws(64, 0u);
+    const long launches = fake_hip_stream_ops(own_stream(), 0), copies = fake_hip_stream_ops(own_stream(), 1);
+    const OffStream off;
+    CHECK(ogg_fill_dev((long)out.size(), 2.5, out.data(), own_stream()) == OGG_OK, "ogg_fill_dev: %s", ogg_last_error());
+    int flag = -1;
+    CHECK(ogg_workspace_error_flag_dev(ws.data(), &flag, own_stream()) == OGG_OK && flag == 0, "ogg_workspace_error_flag_dev: %d", flag);
+    CHECK_ON_STREAM(off, "ogg_fill_dev / ogg_workspace_error_flag_dev");
+    CHECK(fake_hip_stream_ops(own_stream(), 0) - launches == 1 && fake_hip_stream_ops(own_stream(), 1) - copies == 1,
+          "one launch and one copy on the stream: %ld, %ld", fake_hip_stream_ops(own_stream(), 0) - launches, fake_hip_stream_ops(own_stream(), 1) - copies);
+    // the counters can move: a launch and a memset that name no stream, and the process-wide calls
+    const OffStream before;
+    CHECK(ogg_fill_dev((long)out.size(), 2.5, out.data(), nullptr) == OGG_OK, "ogg_fill_dev on the null stream");
+    CHECK(hipMemsetAsync(ws.data(), 0xFF, 8, nullptr) == hipSuccess && ws[0] == 0u, "a deferred memset ran at once");
+    CHECK(hipDeviceSynchronize() == hipSuccess && ws[0] == 0xFFFFFFFFu && ws[1] == 0xFFFFFFFFu && ws[2] == 0u, "the deferred memset after the device-wide wait");
+    const OffStream after;
+    CHECK(after.v[0] - before.v[0] == 1 && after.v[2] - before.v[2] == 1 && after.v[6] - before.v[6] == 1 && after.v[1] == before.v[1],
+          "the counts of the null stream and of the device-wide wait did not move as called");
 }
 
 }  // namespace
@@ -347,6 +412,7 @@ int main() {
             check_pass_plan(r, displaced, 2, 0, OGG_SYM_MIRROR);
         }
     plan_handle_life_cycle();
+    on_a_stream_of_their_own();
     if (g_fail) {
         fprintf(stderr, "%d check(s) failed\n", g_fail);
         return 1;

@@ -4,6 +4,11 @@
 // runtime performs asynchronously are DEFERRED here -- queued on their stream and executed as late as the API allows (at the event /
 // stream / device synchronisation that orders them) -- so that host code which reuses a staging buffer before waiting for the copy
 // that reads it moves the wrong bytes, and the driver's round-trip comparison sees it.
+//
+// Every call is counted where it lands: launches, asynchronous copies, asynchronous memsets and event records per stream
+// (fake_hip_stream_ops), the synchronous hipMemcpy and hipMemset and the device-wide hipDeviceSynchronize per process (fake_hip_sync_calls).
+// A device entry that is given a stream of its own must leave the null stream's counts and the process-wide ones where they were: a
+// launch that forgot its stream argument moves the first, an internal synchronous call the second.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
@@ -16,14 +21,18 @@
 namespace {
 
 struct Op {
-    int kind;   // 0: memcpy, 1: event record
+    int kind;   // 0: memcpy, 1: event record, 2: memset (src unused, value)
     void* dst;
     const void* src;
     size_t bytes;
     void* event;
+    int value;
 };
+enum { OPS_LAUNCH = 0, OPS_COPY = 1, OPS_MEMSET = 2, OPS_RECORD = 3, OPS_N = 4 };
+enum { SYNC_MEMCPY = 0, SYNC_MEMSET = 1, SYNC_DEVICE = 2, SYNC_N = 3 };
 struct Stream {
     std::deque<Op> q;
+    long ops[OPS_N] = {0, 0, 0, 0};   // calls that named this stream, by kind
 };
 struct Event {
     Stream* stream = nullptr;   // where the last record sits
@@ -35,6 +44,7 @@ std::vector<Stream*> g_streams;
 Stream g_null_stream;
 int g_device = 0;
 long g_launches = 0, g_copies = 0;
+long g_sync_calls[SYNC_N] = {0, 0, 0};
 
 Stream* S(hipStream_t s) { return s ? reinterpret_cast<Stream*>(s) : &g_null_stream; }
 
@@ -45,6 +55,8 @@ void run_until(Stream* st, Event* until) {   // execute queued operations, up to
         if (op.kind == 0) {
             if (op.bytes) memcpy(op.dst, op.src, op.bytes);
             g_copies += 1;
+        } else if (op.kind == 2) {
+            if (op.bytes) memset(op.dst, op.value, op.bytes);
         } else {
             Event* e = static_cast<Event*>(op.event);
             e->pending = false;
@@ -64,6 +76,16 @@ extern "C" {
 
 long fake_hip_launches(void) { return g_launches; }
 long fake_hip_copies(void) { return g_copies; }
+// calls of one kind (0 launches, 1 hipMemcpyAsync, 2 hipMemsetAsync, 3 hipEventRecord) that named `stream`; NULL is the null stream
+long fake_hip_stream_ops(void* stream, int kind) {
+    std::lock_guard<std::mutex> g(g_mu);
+    return kind >= 0 && kind < OPS_N ? S(static_cast<hipStream_t>(stream))->ops[kind] : -1;
+}
+// calls of the process so far: 0 hipMemcpy, 1 hipMemset, 2 hipDeviceSynchronize
+long fake_hip_sync_calls(int kind) {
+    std::lock_guard<std::mutex> g(g_mu);
+    return kind >= 0 && kind < SYNC_N ? g_sync_calls[kind] : -1;
+}
 
 hipError_t hipGetDeviceCount(int* n) {
     *n = 2;
@@ -110,19 +132,28 @@ hipError_t hipHostFree(void* p) {
 }
 hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) {
     std::lock_guard<std::mutex> g(g_mu);
+    g_sync_calls[SYNC_MEMCPY] += 1;
     drain_all();
     if (bytes) memcpy(dst, src, bytes);
     return hipSuccess;
 }
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t s) {
     std::lock_guard<std::mutex> g(g_mu);
-    S(s)->q.push_back(Op{0, dst, src, bytes, nullptr});
+    S(s)->ops[OPS_COPY] += 1;
+    S(s)->q.push_back(Op{0, dst, src, bytes, nullptr, 0});
     return hipSuccess;
 }
 hipError_t hipMemset(void* p, int v, size_t bytes) {
     std::lock_guard<std::mutex> g(g_mu);
+    g_sync_calls[SYNC_MEMSET] += 1;
     drain_all();
     memset(p, v, bytes);
+    return hipSuccess;
+}
+hipError_t hipMemsetAsync(void* p, int v, size_t bytes, hipStream_t s) {   // deferred like a copy: in its stream's order, as late as allowed
+    std::lock_guard<std::mutex> g(g_mu);
+    S(s)->ops[OPS_MEMSET] += 1;
+    S(s)->q.push_back(Op{2, p, nullptr, bytes, nullptr, v});
     return hipSuccess;
 }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
@@ -139,6 +170,7 @@ hipError_t hipStreamSynchronize(hipStream_t s) {
 }
 hipError_t hipDeviceSynchronize(void) {
     std::lock_guard<std::mutex> g(g_mu);
+    g_sync_calls[SYNC_DEVICE] += 1;
     drain_all();
     return hipSuccess;
 }
@@ -163,7 +195,8 @@ hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     Event* ev = reinterpret_cast<Event*>(e);
     if (ev->pending && ev->stream) run_until(ev->stream, ev);   // a re-record: the earlier one is resolved first
     ev->stream = S(s), ev->pending = true;
-    S(s)->q.push_back(Op{1, nullptr, nullptr, 0, ev});
+    S(s)->ops[OPS_RECORD] += 1;
+    S(s)->q.push_back(Op{1, nullptr, nullptr, 0, ev, 0});
     return hipSuccess;
 }
 hipError_t hipEventSynchronize(hipEvent_t e) {
@@ -178,8 +211,10 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) {
 }
 
 // kernel launches: nothing runs
-hipError_t hipLaunchKernel(const void*, dim3, dim3, void**, size_t, hipStream_t) {
+hipError_t hipLaunchKernel(const void*, dim3, dim3, void**, size_t, hipStream_t s) {
+    std::lock_guard<std::mutex> g(g_mu);
     g_launches += 1;
+    S(s)->ops[OPS_LAUNCH] += 1;
     return hipSuccess;
 }
 struct FakeConfig {

@@ -56,6 +56,9 @@ def test_patterns():
     a.reset("ff")
     assert np.isnan(a.take(3, torch.float64).numpy()).all() and np.isnan(a.take(3, torch.float32).numpy()).all()
     assert a.take(3, torch.int32).tolist() == [-1] * 3 and a.take(3, torch.uint8).tolist() == [255] * 3
+    a.reset("00")
+    assert a.take(3, torch.float64).tolist() == [0.0] * 3 and a.take(3, torch.int64).tolist() == [0] * 3 and a.check() == []
+    assert not a.buf.numpy().any() and not a.pristine.numpy().any()
     a.reset(("random", 3))
     one = a.buf.numpy().copy()
     assert len(np.unique(one)) == 256
